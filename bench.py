@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- batched CKKS encode+encrypt throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU under torch.distributed.run -- RANK/LOCAL_RANK/WORLD_SIZE in the env; called
    WITHOUT that env, `--gpus N` launches itself under torch.distributed.run on 127.0.0.1.  With fewer than N
    devices visible the line is still printed, for the devices there are, and says so: `n_gpus` is what ran,
@@ -12,7 +12,17 @@ resident in HBM.  Top-level workload = BASELINE config 2: n=4096, 3x30-bit prime
 batch 65536 PER GPU (weak scaling: every rank encrypts its own contiguous block of the batch
 index; no data-path collective).  Prints ONE JSON line on rank 0.
 
-Objects in the line beside the driver's contract fields:
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the contract fields
+(metric, value, unit, ms_per_step, ...) of the top-level workload; nothing else.
+
+--dump-outputs DIR  after the timed steps, rank 0 writes what its last step computed: DIR/c0.npy and DIR/c1.npy
+                    (float64 residues of a fixed, seeded sample of records, [k, nprimes, n]; c1 absent for the
+                    encode-only workload), DIR/records.npy (the batch indices of that sample) and DIR/status.npy
+                    (float32, every record).  The inputs are a fixed function of the arguments, so two builds can
+                    be compared output for output.
+--full              everything below, measured after the contract measurement.
+
+Objects in the line beside the driver's contract fields (--full only):
   roofline      -- bound "hbm": achieved = algorithmic bytes per step / measured step time against the
                    8 TB/s HBM peak; `kernels` lists every kernel of the step with ITS OWN algorithmic
                    bytes, its HIP-event-measured duration and its PMC-measured HBM traffic (null when
@@ -370,6 +380,28 @@ def bench_values_device(B, n, dev, seed=0xC0FFEE, first=0):
     return out
 
 
+DUMP_POLY_BYTES = 48 << 20      # budget of the sampled c0 / c1 records in a --dump-outputs directory (float64)
+DUMP_SEED = 0x5EA1
+
+
+def dump_outputs(path, c0, c1, status):
+    """Write the outputs of the last step as float arrays: a fixed, seeded sample of the records of c0 (and c1) --
+    residues below 2^31, exact in float64 -- with their batch indices, and every record's status byte."""
+    import numpy as np
+    import torch
+    B, npr, n = c0.shape
+    polys = [("c0", c0)] + ([("c1", c1)] if c1 is not None else [])
+    k = max(1, min(B, DUMP_POLY_BYTES // (8 * npr * n * len(polys))))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False)) if k < B else np.arange(B)
+    os.makedirs(path, exist_ok=True)
+    sel = torch.from_numpy(idx).to(c0.device)
+    for name, t in polys:
+        a = t.index_select(0, sel).cpu().numpy().view(np.uint32).astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+    np.save(os.path.join(path, "records.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), status.cpu().numpy().astype(np.float32))
+
+
 def cpu_baseline(n, npr, mode, budget_s=10.0):
     """(budget: seconds of CPU work of the main sample; $SE_BENCH_CPU_BUDGET_S overrides -- the CPU tests use it)
     Reference CPU path on this box's host cores over a bounded sample of the same workload
@@ -606,104 +638,12 @@ def verify_gather(be, ctx, mode, n, npr, B, world, c0_all, c1_all, seeds_all):
     return bool(st.all()), k, None
 
 
-def run_config(be, coll, name, B, steps, warmup, rank, world, want_cpu, cpu_budget, want_gather, src_hash,
-               on_core=None):
-    """One workload: timed region per the driver's contract, per-kernel profile, optional gather.
-    `on_core(res)` is called with the contract fields + roofline as soon as they exist (before the gather
-    and the CPU baseline)."""
-    import numpy as np
-    import vectors as V
+def kernel_roofline(be, ctx, step, name, B, steps, ms_per_step, rank, src_hash):
+    """--full: the roofline object of one workload -- per-kernel durations from separate profiled steps, the
+    engine clock sampled over further steps, and the PMC / SQ profiles stamped for these kernel sources."""
     torch = be.torch
     n, npr, mode, _ = WORKLOADS[name]
-    dist = coll.dist
-    use_dist = coll.on
     bpu = bytes_per_unit(mode, n, npr)
-    if be.idle:
-        # a rank without a device of its own: the same collectives in the same order (class Collectives), no work
-        coll.timed(lambda: None, steps, warmup)
-        coll.exchange_times(0.0, steps, None)
-        if want_cpu:
-            coll.cold_wait()
-        return {}
-    active = world
-    if be.oversubscribed:                            # only the ranks that own a device work
-        active = min(world, be.ndev)
-        want_gather = False
-    ctx = be.mod.Context(n, npr, be.dev.index if be.dev.type == "cuda" else be.local_rank)
-    sk = V.secret_key(n)
-    if mode == "sym":
-        ctx.set_secret_key(sk)
-    elif mode == "asym":
-        pk0, pk1 = ctx.gen_public_key(sk, bytes(64), bytes(range(64)))   # fixed seeds, gen_pk on the GPU
-        ctx.set_public_key(pk0, pk1)
-
-    # ---- synthetic inputs, resident in HBM before timing; rank r owns batch block r ----------
-    first = rank * B
-    vals = be.values(B, n, first)
-    ss_np, sd_np = V.bench_seeds(B, first=first) if mode != "encode" else (np.zeros((B, 64), np.uint8),) * 2
-    ss, sd = torch.from_numpy(ss_np).to(be.dev), torch.from_numpy(sd_np).to(be.dev)
-    rec = (npr, n)
-    rec_bytes = 4 * npr * n
-    # The root of a gathered run produces its block in place inside the gathered slab.
-    gather_plan = None
-    c0_all = c1_all = c0 = c1 = None
-    if want_gather and use_dist and world > 1:
-        # The root ALLOCATES the gathered slab(s) before anybody commits to a plan (a failed allocation
-        # after the plan was agreed would leave the other ranks waiting in the gather): full form, else
-        # the seed-compressed form (c0 + 64-byte shareable seeds; c1 = expand(seed)), else no gather.
-        code = 0
-        if rank == 0:
-            slabs = 1 if mode == "encode" else 2
-            margin = 6 << 30
-            for plan, need in (("full", world * B * rec_bytes * slabs),
-                               ("seed-compressed", world * B * rec_bytes + B * rec_bytes)):
-                if plan == "seed-compressed" and mode != "sym":
-                    continue
-                if plan == "full" and os.environ.get("SE_BENCH_TEST_NO_FULL_GATHER"):
-                    continue                          # test hook: pretend the root cannot hold both slabs
-                if be.free_bytes() < need + margin:
-                    continue
-                try:
-                    c0_all = torch.empty((world * B,) + rec, dtype=torch.int32, device=be.dev)
-                    if plan == "full" and mode != "encode":
-                        c1_all = torch.empty((world * B,) + rec, dtype=torch.int32, device=be.dev)
-                    elif mode != "encode":
-                        c1 = torch.empty((B,) + rec, dtype=torch.int32, device=be.dev)
-                    code = 1 if plan == "full" else 2
-                    break
-                except RuntimeError:                 # out of memory: drop what we got, try the smaller form
-                    c0_all = c1_all = c1 = None
-                    if not be.stub:
-                        torch.cuda.empty_cache()
-        gather_plan = {0: None, 1: "full", 2: "seed-compressed"}[coll.agree(code)]   # the root decides for everybody
-    if gather_plan and rank == 0:
-        c0 = c0_all[:B]                             # the root produces its block in place inside the slab
-        if c1_all is not None:
-            c1 = c1_all[:B]
-    else:
-        c0 = torch.empty((B,) + rec, dtype=torch.int32, device=be.dev)
-        c1 = torch.empty((B,) + rec, dtype=torch.int32, device=be.dev) if mode != "encode" else None
-    status = torch.zeros(B, dtype=torch.uint8, device=be.dev)
-
-    def step():
-        if mode == "sym":
-            ctx.encrypt_sym(vals, ss, sd, c0, c1, status=status)
-        elif mode == "asym":
-            ctx.encrypt_asym(vals, sd, c0, c1, status=status)
-        else:
-            ctx.encode_ntt(vals, c0, status=status)
-
-    fence = coll.fence
-
-    if os.environ.get("SE_BENCH_DEBUG_FLAGS"):          # A/B of pipeline shapes (tools/c4_ab.sh)
-        ctx.set_debug_flags(int(os.environ["SE_BENCH_DEBUG_FLAGS"]))
-    ctx.reserve(B)  # scratch allocation is not a step
-    elapsed = coll.timed(step, steps, warmup)
-    ranks, elapsed = coll.exchange_times(elapsed, steps, device_label(be))
-    if not os.environ.get("SE_BENCH_SKIP_STATUS"):   # timing-only ablation builds produce garbage
-        assert bool(status.all()), "an encode overflowed on synthetic data"
-    ms_per_step = elapsed / steps * 1e3
-
     # ---- per-kernel durations with HIP events on the launch stream (separate profiled steps) ---
     ctx.set_profiling(True)
     ctx.stage_ms(reset=True)
@@ -847,6 +787,110 @@ def run_config(be, coll, name, B, steps, warmup, rank, world, want_cpu, cpu_budg
                 "sampled_clock": clock,
                 "dominant_kernel": dom, "kernels": kernels, "valu": valu,
                 "profile_source_sha256": src_hash}
+    return roofline
+
+
+def run_config(be, coll, name, B, steps, warmup, rank, world, want_cpu, cpu_budget, want_gather, src_hash,
+               on_core=None, full=True, dump_dir=None):
+    """One workload: timed region per the driver's contract, then (`full`) per-kernel profile and roofline,
+    optional gather.  `dump_dir`: rank 0 writes the outputs of the last timed step there (dump_outputs).
+    `on_core(res)` is called with the contract fields + roofline as soon as they exist (before the gather
+    and the CPU baseline)."""
+    import numpy as np
+    import vectors as V
+    torch = be.torch
+    n, npr, mode, _ = WORKLOADS[name]
+    dist = coll.dist
+    use_dist = coll.on
+    bpu = bytes_per_unit(mode, n, npr)
+    if be.idle:
+        # a rank without a device of its own: the same collectives in the same order (class Collectives), no work
+        coll.timed(lambda: None, steps, warmup)
+        coll.exchange_times(0.0, steps, None)
+        if want_cpu:
+            coll.cold_wait()
+        return {}
+    active = world
+    if be.oversubscribed:                            # only the ranks that own a device work
+        active = min(world, be.ndev)
+        want_gather = False
+    ctx = be.mod.Context(n, npr, be.dev.index if be.dev.type == "cuda" else be.local_rank)
+    sk = V.secret_key(n)
+    if mode == "sym":
+        ctx.set_secret_key(sk)
+    elif mode == "asym":
+        pk0, pk1 = ctx.gen_public_key(sk, bytes(64), bytes(range(64)))   # fixed seeds, gen_pk on the GPU
+        ctx.set_public_key(pk0, pk1)
+
+    # ---- synthetic inputs, resident in HBM before timing; rank r owns batch block r ----------
+    first = rank * B
+    vals = be.values(B, n, first)
+    ss_np, sd_np = V.bench_seeds(B, first=first) if mode != "encode" else (np.zeros((B, 64), np.uint8),) * 2
+    ss, sd = torch.from_numpy(ss_np).to(be.dev), torch.from_numpy(sd_np).to(be.dev)
+    rec = (npr, n)
+    rec_bytes = 4 * npr * n
+    # The root of a gathered run produces its block in place inside the gathered slab.
+    gather_plan = None
+    c0_all = c1_all = c0 = c1 = None
+    if want_gather and use_dist and world > 1:
+        # The root ALLOCATES the gathered slab(s) before anybody commits to a plan (a failed allocation
+        # after the plan was agreed would leave the other ranks waiting in the gather): full form, else
+        # the seed-compressed form (c0 + 64-byte shareable seeds; c1 = expand(seed)), else no gather.
+        code = 0
+        if rank == 0:
+            slabs = 1 if mode == "encode" else 2
+            margin = 6 << 30
+            for plan, need in (("full", world * B * rec_bytes * slabs),
+                               ("seed-compressed", world * B * rec_bytes + B * rec_bytes)):
+                if plan == "seed-compressed" and mode != "sym":
+                    continue
+                if plan == "full" and os.environ.get("SE_BENCH_TEST_NO_FULL_GATHER"):
+                    continue                          # test hook: pretend the root cannot hold both slabs
+                if be.free_bytes() < need + margin:
+                    continue
+                try:
+                    c0_all = torch.empty((world * B,) + rec, dtype=torch.int32, device=be.dev)
+                    if plan == "full" and mode != "encode":
+                        c1_all = torch.empty((world * B,) + rec, dtype=torch.int32, device=be.dev)
+                    elif mode != "encode":
+                        c1 = torch.empty((B,) + rec, dtype=torch.int32, device=be.dev)
+                    code = 1 if plan == "full" else 2
+                    break
+                except RuntimeError:                 # out of memory: drop what we got, try the smaller form
+                    c0_all = c1_all = c1 = None
+                    if not be.stub:
+                        torch.cuda.empty_cache()
+        gather_plan = {0: None, 1: "full", 2: "seed-compressed"}[coll.agree(code)]   # the root decides for everybody
+    if gather_plan and rank == 0:
+        c0 = c0_all[:B]                             # the root produces its block in place inside the slab
+        if c1_all is not None:
+            c1 = c1_all[:B]
+    else:
+        c0 = torch.empty((B,) + rec, dtype=torch.int32, device=be.dev)
+        c1 = torch.empty((B,) + rec, dtype=torch.int32, device=be.dev) if mode != "encode" else None
+    status = torch.zeros(B, dtype=torch.uint8, device=be.dev)
+
+    def step():
+        if mode == "sym":
+            ctx.encrypt_sym(vals, ss, sd, c0, c1, status=status)
+        elif mode == "asym":
+            ctx.encrypt_asym(vals, sd, c0, c1, status=status)
+        else:
+            ctx.encode_ntt(vals, c0, status=status)
+
+    fence = coll.fence
+
+    if os.environ.get("SE_BENCH_DEBUG_FLAGS"):          # A/B of pipeline shapes (tools/c4_ab.sh)
+        ctx.set_debug_flags(int(os.environ["SE_BENCH_DEBUG_FLAGS"]))
+    ctx.reserve(B)  # scratch allocation is not a step
+    elapsed = coll.timed(step, steps, warmup)
+    ranks, elapsed = coll.exchange_times(elapsed, steps, device_label(be))
+    if not os.environ.get("SE_BENCH_SKIP_STATUS"):   # timing-only ablation builds produce garbage
+        assert bool(status.all()), "an encode overflowed on synthetic data"
+    ms_per_step = elapsed / steps * 1e3
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, c0, c1, status)
+    roofline = kernel_roofline(be, ctx, step, name, B, steps, ms_per_step, rank, src_hash) if full else None
 
     unit = "ciphertexts/s" if mode != "encode" else "plaintexts/s"
     res = {
@@ -859,8 +903,9 @@ def run_config(be, coll, name, B, steps, warmup, rank, world, want_cpu, cpu_budg
         "config": {"workload": DESCR[name] + f", batch={B} per GPU", "n": n, "nprimes": npr, "mode": mode,
                    "batch_per_gpu": B, "global_batch": active * B, "parallelism": f"batch-sharded x{active}",
                    "bytes_per_unit": bpu},
-        "roofline": roofline, "cpu_baseline": None,
     }
+    if full:
+        res.update({"roofline": roofline, "cpu_baseline": None})
     if ranks:
         res["ranks"] = ranks
     req = int(os.environ.get("SE_BENCH_REQUESTED_GPUS", "0"))
@@ -981,11 +1026,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="batch per GPU (0 = workload default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, CPU baseline, further workloads and (N>1) the gather")
     ap.add_argument("--others", default=None,
-                    help="comma list of further workloads reported under other_configs "
+                    help="--full: comma list of further workloads reported under other_configs "
                          "(default: c3,c4,c5,c1 at N=1, c4 at N>1 when the main workload is c2; 'none')")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gather", action="store_true", help="N>1: skip the timed final gather")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-gather", action="store_true", help="--full, N>1: skip the timed final gather")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ:
@@ -1014,17 +1063,19 @@ def main():
     if dist is not None and world > 1 and dist.get_backend() != "gloo":
         cold = dist.new_group(backend="gloo")          # socket barrier for the ranks that wait on rank 0's CPU work
     coll = Collectives(be, dist, world, cold)
-    src_hash = kernel_source_hash()
+    src_hash = kernel_source_hash() if args.full else None
     # N > 1 too: north_star wants the CPU reference "in the same run"; shorter sample there (the other ranks wait)
-    want_cpu = not args.no_cpu_baseline
-    want_gather = world > 1 and not args.no_gather
+    want_cpu = args.full and not args.no_cpu_baseline
+    want_gather = args.full and world > 1 and not args.no_gather
     B = args.batch or WORKLOADS[args.workload][3]
     deadline = Deadline(rank)
     deadline_s = float(os.environ.get("SE_BENCH_DEADLINE_S", "600"))
     line = run_config(be, coll, args.workload, B, args.steps, args.warmup, rank, world, want_cpu,
                       10.0 if world == 1 else 6.0, want_gather, src_hash,
-                      on_core=lambda res: deadline.arm(deadline_s, res))
-    if args.others is None:
+                      on_core=lambda res: deadline.arm(deadline_s, res), full=args.full, dump_dir=args.dump_outputs)
+    if not args.full:
+        others = []
+    elif args.others is None:
         others = [] if args.workload != "c2" or args.batch else (["c3", "c4", "c5", "c1"] if world == 1 else ["c4"])
     else:
         others = [w for w in args.others.split(",") if w and w != "none"]

@@ -153,7 +153,7 @@ def test_bench_ranks_over_rccl(env, tmp_path):
     envp = dict(os.environ, SE_BENCH_CPU_BUDGET_S="1.0", SE_BENCH_NO_CLOCK="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--workload", "c2", "--batch", "4096", "--others", "none"]
+           "--warmup", "1", "--workload", "c2", "--batch", "4096", "--others", "none", "--full"]
     r = subprocess.run(cmd, env=envp, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -160,7 +160,8 @@ def test_bench_rank_logic_two_ranks_gloo(tmp_path):
     stub context of tests/stub_context.py in place of the library): rank r encrypts block r of the batch
     index (`first = rank * B`), the line reports n_gpus = 2 with the whole-job rate, and the gathered
     slab on rank 0 is bit-identical to the single-process order (checked inside the run)."""
-    d = _run_bench(2, ["--steps", "2", "--warmup", "1", "--workload", "c1", "--batch", "3", "--others", "none"],
+    d = _run_bench(2, ["--steps", "2", "--warmup", "1", "--workload", "c1", "--batch", "3", "--others", "none",
+                       "--full"],
                    tmp_path)
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["config"]["batch_per_gpu"] == 3 and d["config"]["global_batch"] == 6
@@ -184,7 +185,7 @@ def test_bench_flags_a_gather_that_lost_bytes(tmp_path):
     os.environ["SE_BENCH_TEST_CORRUPT_GATHER"] = "1"
     try:
         d = _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "4", "--others", "none",
-                           "--no-cpu-baseline"], tmp_path)
+                           "--no-cpu-baseline", "--full"], tmp_path)
     finally:
         os.environ.pop("SE_BENCH_TEST_CORRUPT_GATHER", None)
     g = d["gather"]
@@ -196,7 +197,7 @@ def test_bench_flags_a_gather_that_lost_bytes(tmp_path):
 def test_bench_three_ranks_seed_and_encode_forms(tmp_path):
     """Three ranks, encode-only workload (one slab): gather verified for every rank's block."""
     d = _run_bench(3, ["--steps", "1", "--warmup", "1", "--workload", "c5", "--batch", "2", "--others", "none",
-                       "--no-cpu-baseline"], tmp_path)
+                       "--no-cpu-baseline", "--full"], tmp_path)
     assert d["n_gpus"] == 3 and d["gather"]["gather_verified"] is True and d["gather"]["verified_records"] == 6
 
 
@@ -206,7 +207,7 @@ def test_bench_seed_compressed_gather_is_verified_too(tmp_path):
     os.environ["SE_BENCH_TEST_NO_FULL_GATHER"] = "1"
     try:
         d = _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "3", "--others", "none",
-                           "--no-cpu-baseline"], tmp_path)
+                           "--no-cpu-baseline", "--full"], tmp_path)
     finally:
         os.environ.pop("SE_BENCH_TEST_NO_FULL_GATHER", None)
     g = d["gather"]
@@ -220,7 +221,8 @@ def test_launcher_with_more_ranks_than_devices(tmp_path):
     CPU baseline (the idle rank waits for it)."""
     os.environ["SE_BENCH_STUB_DEVICES"] = "1"
     try:
-        d = _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2", "--others", "c1"],
+        d = _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2", "--others", "c1",
+                           "--full"],
                        tmp_path)
     finally:
         os.environ.pop("SE_BENCH_STUB_DEVICES", None)
@@ -237,7 +239,8 @@ def test_bench_gathered_slab_is_single_process_order(tmp_path):
     dump = tmp_path / "slab.npz"
     os.environ["SE_BENCH_DUMP"] = str(dump)
     try:
-        _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2", "--others", "none"],
+        _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2", "--others", "none",
+                       "--full"],
                    tmp_path)
     finally:
         os.environ.pop("SE_BENCH_DUMP", None)
@@ -255,7 +258,8 @@ def test_bench_line_survives_a_rank_lost_in_the_gather(tmp_path):
     os.environ["SE_BENCH_TEST_HANG"] = "gather"
     os.environ["SE_BENCH_DEADLINE_S"] = "4"
     try:
-        d = _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2", "--others", "none"],
+        d = _run_bench(2, ["--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2", "--others", "none",
+                           "--full"],
                        tmp_path)
     finally:
         os.environ.pop("SE_BENCH_TEST_HANG", None)
@@ -289,7 +293,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     127.0.0.1, a free port) and prints the same ONE line: n_gpus = 2, the whole-job rate, the gather, and
     every rank's own step time next to the process group's world size."""
     d, _ = _run_bench_plain(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c1", "--batch", "3",
-                             "--others", "none"], tmp_path)
+                             "--others", "none", "--full"], tmp_path)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 6 and "requested_gpus" not in d
     assert d["ranks"]["world_size"] == 2 and len(d["ranks"]["ms_per_step"]) == 2
     assert all(t is not None and t > 0 for t in d["ranks"]["ms_per_step"])
@@ -307,3 +311,38 @@ def test_bench_with_fewer_devices_than_requested(tmp_path):
     d, _ = _run_bench_plain(["--gpus", "8", "--steps", "1", "--warmup", "1", "--workload", "c1", "--batch", "2",
                              "--others", "none"], tmp_path, {"SE_BENCH_STUB_DEVICES": "1"})
     assert d["n_gpus"] == 1 and d["requested_gpus"] == 8 and d["value"] > 0 and "ranks" not in d
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the contract fields of the top-level workload only (the roofline, the CPU baseline and the
+    further workloads need --full), and --dump-outputs writes the records of the last timed step as float arrays
+    equal to the oracle's; a batch larger than the dump budget is sampled at fixed, seeded record indices."""
+    import torch
+    import bench
+    from oracle.pyoracle import Oracle
+    out = tmp_path / "out"
+    d, _ = _run_bench_plain(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c1", "--batch", "3",
+                             "--dump-outputs", str(out)], tmp_path)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "ciphertexts/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    for key in ("roofline", "cpu_baseline", "other_configs", "gather"):
+        assert key not in d, key
+    n, npr, B = 1024, 1, 3
+    ok, c0, c1 = Oracle(n, npr).encrypt_sym_batch(V.bench_values(B, n), *V.bench_seeds(B), V.secret_key(n),
+                                                  nthreads=1)
+    got = {f: np.load(out / (f + ".npy")) for f in ("c0", "c1", "records", "status")}
+    assert got["c0"].dtype == np.float64 and got["status"].dtype == np.float32
+    assert (got["records"] == np.arange(B)).all() and (got["status"] == 1).all()
+    assert (got["c0"] == c0).all() and (got["c1"] == c1).all()
+    # sampled form: a budget of 4 records out of 10, the same indices every time
+    t = torch.arange(10 * 2 * 8, dtype=torch.int32).reshape(10, 2, 8)
+    old = bench.DUMP_POLY_BYTES
+    bench.DUMP_POLY_BYTES = 4 * 2 * (8 * 2 * 8)
+    try:
+        bench.dump_outputs(str(tmp_path / "a"), t, t + 1, torch.ones(10, dtype=torch.uint8))
+        bench.dump_outputs(str(tmp_path / "b"), t, t + 1, torch.ones(10, dtype=torch.uint8))
+    finally:
+        bench.DUMP_POLY_BYTES = old
+    idx = np.load(tmp_path / "a" / "records.npy").astype(np.int64)
+    assert len(idx) == 4 and (np.diff(idx) > 0).all() and (idx == np.load(tmp_path / "b" / "records.npy")).all()
+    assert (np.load(tmp_path / "a" / "c1.npy") == t.numpy()[idx] + 1).all()

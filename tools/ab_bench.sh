@@ -9,7 +9,7 @@ for rep in 1 2; do
 for which in ${AB_LIBS:-new old}; do
   if [ $which = new ]; then cp /tmp/new.so $L/libseal_embedded_amd.so; else cp $L/$which.so $L/libseal_embedded_amd.so || continue; fi
   for w in ${AB_WL:-c2 c3 c5}; do
-    python bench.py --steps 8 --warmup 2 --workload $w --no-cpu-baseline --others none ${AB_ARGS:-} 2>/dev/null | python -c "
+    python bench.py --steps 8 --warmup 2 --workload $w --no-cpu-baseline --others none --full ${AB_ARGS:-} 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('%-8s' % '$which', '$w', '%.3f ms' % d['ms_per_step'], {k['kernel'][2:]: round(k['ms_per_step'], 3) for k in d['roofline']['kernels']})"
   done

@@ -67,7 +67,7 @@ tail -3 $OUT/pytest_multi.log | sed 's/^/   /' | tee -a $SUMMARY
 
 # 3. two ranks, BASELINE C2, with the timed + verified gather: RCCL P2P between two devices
 step bench_c2_2gpu 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 \
-     bench.py --gpus 2 --workload c2 --steps 5 --warmup 2 --others none --no-cpu-baseline
+     bench.py --gpus 2 --workload c2 --steps 5 --warmup 2 --others none --no-cpu-baseline --full
 last_json $OUT/bench_c2_2gpu.log | tee -a $SUMMARY
 
 # 4. all devices, C4 (the sharded BASELINE config): resident measurement only, then with the gather
@@ -75,7 +75,7 @@ step bench_c4_nogather 900 python -m torch.distributed.run --nnodes=1 --nproc-pe
      bench.py --gpus $N --workload c4 --steps 5 --warmup 2 --others none --no-cpu-baseline --no-gather
 last_json $OUT/bench_c4_nogather.log | tee -a $SUMMARY
 step bench_c4_gather 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29543 \
-     bench.py --gpus $N --workload c4 --steps 5 --warmup 2 --others none --no-cpu-baseline
+     bench.py --gpus $N --workload c4 --steps 5 --warmup 2 --others none --no-cpu-baseline --full
 last_json $OUT/bench_c4_gather.log | tee -a $SUMMARY
 
 # 5. the native C entry (one process, one context + worker per device, hipMemcpyPeerAsync gather, self-verified)
