@@ -322,8 +322,7 @@ int se_amd_stage_ms(se_amd_ctx *ctx, float *ms, uint64_t *launches, int reset)
 int se_amd_set_reject_list_capacity(se_amd_ctx *ctx, uint32_t cap)
 {
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
-    ctx->c.rej_cap     = cap;
-    ctx->c.rows_cap    = 0;  // force re-allocation with the new stride
+    ctx->c.rej_cap = cap;   // the next call grows the reject lists to the new stride
     return SE_SUCCESS;
 }
 
@@ -413,8 +412,7 @@ int se_amd_set_asym_chunks(se_amd_ctx *ctx, size_t chunks)
 int se_amd_set_speculation_capacity(se_amd_ctx *ctx, uint32_t cap)
 {
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
-    ctx->c.spec_cap    = cap ? cap : 1;
-    ctx->c.rows_cap    = 0;  // force re-allocation with the new stride
+    ctx->c.spec_cap = cap ? cap : 1;   // the next call grows the candidate rows to the new stride
     return SE_SUCCESS;
 }
 
@@ -431,16 +429,11 @@ static int host_pipe(se_amd_ctx *ctx, HostPipe **out)
     Context &c = ctx->c;
     if (!c.host_pipe)
     {
-        HostPipe *hp = new HostPipe();
-        int rc       = hp->init(c.device);
-        if (rc)
-        {
-            delete hp;
-            return rc;
-        }
-        c.host_pipe = hp;
+        auto hp = std::make_unique<HostPipe>();
+        if (int rc = hp->init(c.device)) return rc;
+        c.host_pipe = std::move(hp);
     }
-    *out = c.host_pipe;
+    *out = c.host_pipe.get();
     return 0;
 }
 

@@ -23,37 +23,6 @@ static thread_local std::string g_last_error;
 void set_last_error(const std::string &msg) { g_last_error = msg; }
 const std::string &last_error() { return g_last_error; }
 
-namespace {
-// temporary device allocation, wiped and freed on every path out of its scope
-struct DevTemp
-{
-    void *p      = nullptr;
-    size_t bytes = 0;
-    bool wipe    = false;
-    hipError_t alloc(size_t n, bool secret = false)
-    {
-        bytes = n;
-        wipe  = secret;
-        return hipMalloc(&p, n);
-    }
-    ~DevTemp()
-    {
-        if (!p) return;
-        if (wipe) (void)hipMemset(p, 0, bytes);
-        (void)hipFree(p);
-    }
-    template <typename T>
-    T *as() const { return static_cast<T *>(p); }
-};
-}  // namespace
-
-// Zero a device slab that held secret-dependent data before it is freed (best effort: errors are ignored, the
-// free follows either way).
-static void wipe_device(void *p, size_t bytes)
-{
-    if (p && bytes) (void)hipMemset(p, 0, bytes);
-}
-
 int hip_fail(hipError_t e, const char *what)
 {
     char buf[512];
@@ -64,41 +33,10 @@ int hip_fail(hipError_t e, const char *what)
 
 Context::~Context()
 {
+    // nothing may still use the scratch when the members wipe and free it (the auxiliary streams are non-blocking)
     (void)hipSetDevice(device);
-    delete host_pipe;
-    for (auto &ev : events)
-    {
-        (void)hipEventDestroy(ev.start);
-        (void)hipEventDestroy(ev.stop);
-    }
-    if (aux_stream) (void)hipStreamDestroy(aux_stream);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (ev_cbd) (void)hipEventDestroy(ev_cbd);
-    if (ev_enc) (void)hipEventDestroy(ev_enc);
-    if (ev_done) (void)hipEventDestroy(ev_done);
-    for (auto &e : ev_prime)
-        if (e) (void)hipEventDestroy(e);
-    if (spec_stream) (void)hipStreamDestroy(spec_stream);
-    if (cand_stream) (void)hipStreamDestroy(cand_stream);
-    for (auto &e : ev_cand)
-        if (e) (void)hipEventDestroy(e);
-    // nothing may still be writing the scratch when it is wiped (the streams above were non-blocking)
+    host_pipe.reset();
     (void)hipDeviceSynchronize();
-    // secret-bearing slabs are zeroed before they go back to the allocator: NTT(s), the error polynomials
-    // e / e0|e1, the ternary u, the per-ciphertext seeds of the speculation path and `a` (recomputable from the
-    // shareable seed, kept out of freed memory all the same)
-    const size_t n = hp.n, np = hp.nprimes;
-    wipe_device(d_s_hat, 2 * np * n * sizeof(uint32_t));
-    wipe_device(d_err, scratch_cap * 2 * n);
-    wipe_device(d_ucodes, scratch_cap * n);
-    wipe_device(d_sp_seeds, sp_cap * 64);
-    wipe_device(d_a, a_cap * np * n * sizeof(uint32_t));
-    void *ptrs[] = {d_inv_map, d_ifft_w, d_ntt_rw, d_s_hat, d_pk0, d_pk1, d_intt_rw, d_map, d_gather,
-                    d_err,     d_ucodes, d_ctr,    d_rej, d_a,   d_spec, d_general, d_compact,
-                    d_sp_seeds, d_sp_ctr, d_sp_ctrout, d_sp_rows, d_sp_fail, d_sp_prime, d_nrej, d_flagged};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
 }
 
 int Context::init(size_t n, size_t nprimes, int dev)
@@ -179,21 +117,16 @@ int Context::init(size_t n, size_t nprimes, int dev)
         memcpy(rw_all.data() + 2 * tl * j, rw.data(), 2 * n * sizeof(uint32_t));
         append_thread_major(rw_all.data() + 2 * tl * j);
     }
-    SEAMD_HIP(hipMalloc((void **)&d_inv_map, n * sizeof(uint16_t)));
-    SEAMD_HIP(hipMalloc((void **)&d_ifft_w, w.size() * sizeof(double)));
-    SEAMD_HIP(hipMalloc((void **)&d_ntt_rw, rw_all.size() * sizeof(uint32_t)));
+    SEAMD_HIP(d_inv_map.grow(n));
+    SEAMD_HIP(d_ifft_w.grow(w.size()));
+    SEAMD_HIP(d_ntt_rw.grow(rw_all.size()));
     SEAMD_HIP(hipMemcpy(d_inv_map, inv.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_ifft_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_ntt_rw, rw_all.data(), rw_all.size() * sizeof(uint32_t),
                         hipMemcpyHostToDevice));
-    SEAMD_HIP(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
-    SEAMD_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    SEAMD_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-    SEAMD_HIP(hipEventCreateWithFlags(&ev_cbd, hipEventDisableTiming));
-    SEAMD_HIP(hipEventCreateWithFlags(&ev_enc, hipEventDisableTiming));
-    SEAMD_HIP(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
-    for (size_t j = 0; j < (size_t)kMaxPrimes; j++)
-        SEAMD_HIP(hipEventCreateWithFlags(&ev_prime[j], hipEventDisableTiming));
+    SEAMD_HIP(aux_stream.create(hipStreamNonBlocking));
+    for (Event *e : {&ev_fork, &ev_join, &ev_cbd, &ev_enc, &ev_done}) SEAMD_HIP(e->create(hipEventDisableTiming));
+    for (Event &e : ev_prime) SEAMD_HIP(e.create(hipEventDisableTiming));
     {
         std::vector<uint32_t> irw_all(2 * n * nprimes), irw;
         for (size_t j = 0; j < nprimes; j++)
@@ -201,10 +134,10 @@ int Context::init(size_t n, size_t nprimes, int dev)
             host_intt_root_pairs(hp, j, irw);
             memcpy(irw_all.data() + 2 * n * j, irw.data(), 2 * n * sizeof(uint32_t));
         }
-        SEAMD_HIP(hipMalloc((void **)&d_intt_rw, irw_all.size() * sizeof(uint32_t)));
+        SEAMD_HIP(d_intt_rw.grow(irw_all.size()));
         SEAMD_HIP(hipMemcpy(d_intt_rw, irw_all.data(), irw_all.size() * sizeof(uint32_t),
                             hipMemcpyHostToDevice));
-        SEAMD_HIP(hipMalloc((void **)&d_map, n * sizeof(uint16_t)));
+        SEAMD_HIP(d_map.grow(n));
         SEAMD_HIP(hipMemcpy(d_map, index_map.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
         dt.intt_rw   = d_intt_rw;
         dt.index_map = d_map;
@@ -218,7 +151,7 @@ int Context::init(size_t n, size_t nprimes, int dev)
             gather[((e >> 3) * (n / 16) + t) * 8 + (e & 7)] =
                 (uint16_t)sv_slot((uint32_t)(inv[k] & (n / 2 - 1)), (uint32_t)hp.logn);
         }
-        SEAMD_HIP(hipMalloc((void **)&d_gather, n * sizeof(uint16_t)));
+        SEAMD_HIP(d_gather.grow(n));
         SEAMD_HIP(hipMemcpy(d_gather, gather.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
         dt.gather_map = d_gather;
     }
@@ -231,13 +164,10 @@ int Context::init(size_t n, size_t nprimes, int dev)
 // The fused kernel's list of declined plaintexts (kernel_args.h, EncArgs::general): 4 bytes per plaintext.
 int Context::ensure_general(size_t B)
 {
-    if (B <= general_cap && d_general) return 0;
+    if (B < d_general.size()) return 0;
     SEAMD_HIP(hipSetDevice(device));
     SEAMD_HIP(hipDeviceSynchronize());
-    if (d_general) (void)hipFree(d_general);
-    d_general = nullptr, general_cap = 0;
-    SEAMD_HIP(hipMalloc((void **)&d_general, (B + 1) * sizeof(uint32_t)));
-    general_cap = B;
+    SEAMD_HIP(d_general.grow(B + 1));
     return 0;
 }
 
@@ -247,37 +177,20 @@ int Context::ensure_scratch(size_t B, size_t rows)
     // d_err / d_ucodes / d_ctr are per real ciphertext; the reject lists and speculation rows are
     // also needed by the virtual ciphertexts of the small-batch path, which need nothing else
     if (rows < B) rows = B;
-    if (B <= scratch_cap && rows <= rows_cap) return 0;
+    const size_t n = hp.n, rej = rows * (rej_cap ? rej_cap : 1), spec = rows * spec_cap;
+    if (d_err.size() >= B * 2 * n && d_ucodes.size() >= B * n && d_ctr.size() >= B && d_compact.size() >= B &&
+        d_nrej.size() >= B && d_flagged.size() > B && d_rej.size() >= rej && d_spec.size() >= spec)
+        return 0;
     SEAMD_HIP(hipSetDevice(device));
     SEAMD_HIP(hipDeviceSynchronize());
-    const size_t n = hp.n;
-    if (B > scratch_cap)
-    {
-        wipe_device(d_err, scratch_cap * 2 * n);      // e / e0|e1 and u of earlier calls
-        wipe_device(d_ucodes, scratch_cap * n);
-        void *old[] = {d_err, d_ucodes, d_ctr, d_compact, d_nrej, d_flagged};
-        for (void *p : old)
-            if (p) (void)hipFree(p);
-        d_err = nullptr, d_ucodes = nullptr, d_ctr = nullptr, d_compact = nullptr, d_nrej = nullptr, d_flagged = nullptr;
-        scratch_cap = 0;
-        SEAMD_HIP(hipMalloc((void **)&d_err, B * 2 * n));
-        SEAMD_HIP(hipMalloc((void **)&d_ucodes, B * n));
-        SEAMD_HIP(hipMalloc((void **)&d_ctr, B * sizeof(uint64_t)));
-        SEAMD_HIP(hipMalloc((void **)&d_compact, B));
-        SEAMD_HIP(hipMalloc((void **)&d_nrej, B * sizeof(uint32_t)));
-        SEAMD_HIP(hipMalloc((void **)&d_flagged, (B + 1) * sizeof(uint32_t)));
-        scratch_cap = B;
-    }
-    if (rows > rows_cap)
-    {
-        if (d_rej) (void)hipFree(d_rej);
-        if (d_spec) (void)hipFree(d_spec);
-        d_rej = nullptr, d_spec = nullptr;
-        rows_cap = 0;
-        SEAMD_HIP(hipMalloc((void **)&d_rej, rows * (size_t)(rej_cap ? rej_cap : 1) * sizeof(uint32_t)));
-        SEAMD_HIP(hipMalloc((void **)&d_spec, rows * (size_t)spec_cap * sizeof(uint32_t)));
-        rows_cap = rows;
-    }
+    SEAMD_HIP(d_err.grow(B * 2 * n));
+    SEAMD_HIP(d_ucodes.grow(B * n));
+    SEAMD_HIP(d_ctr.grow(B));
+    SEAMD_HIP(d_compact.grow(B));
+    SEAMD_HIP(d_nrej.grow(B));
+    SEAMD_HIP(d_flagged.grow(B + 1));
+    SEAMD_HIP(d_rej.grow(rej));
+    SEAMD_HIP(d_spec.grow(spec));
     return 0;
 }
 
@@ -350,10 +263,9 @@ int Context::set_secret_key_impl(const uint8_t *sk_packed)
             }
             expanded[j * n + i] = code + (code == 0 ? hp.q[j] : 0u) - 1u;
         }
-    DevTemp tmp;
-    SEAMD_HIP(tmp.alloc(np * n * sizeof(uint32_t), true));
-    uint32_t *d_tmp = tmp.as<uint32_t>();
-    if (!d_s_hat) SEAMD_HIP(hipMalloc((void **)&d_s_hat, 2 * np * n * sizeof(uint32_t)));
+    DevBuf<uint32_t> d_tmp{Secret::yes};
+    SEAMD_HIP(d_tmp.grow(np * n));
+    SEAMD_HIP(d_s_hat.grow(2 * np * n));
     SEAMD_HIP(hipMemcpy(d_tmp, expanded.data(), np * n * sizeof(uint32_t), hipMemcpyHostToDevice));
     for (size_t j = 0; j < np; j++)
         SEAMD_HIP(launch_ntt_polys(dp, dt, (int)j, d_tmp + j * n, d_s_hat + 2 * j * n, 1, nullptr));
@@ -377,11 +289,10 @@ int Context::set_public_key(const uint32_t *pk0, const uint32_t *pk1)
                 return kErrInvalid;
             }
     std::lock_guard<std::mutex> lk(mu);
-    DevTemp tmp;
-    SEAMD_HIP(tmp.alloc(2 * np * n * sizeof(uint32_t)));
-    uint32_t *d_tmp = tmp.as<uint32_t>();
-    if (!d_pk0) SEAMD_HIP(hipMalloc((void **)&d_pk0, 2 * np * n * sizeof(uint32_t)));
-    if (!d_pk1) SEAMD_HIP(hipMalloc((void **)&d_pk1, 2 * np * n * sizeof(uint32_t)));
+    DevBuf<uint32_t> d_tmp;
+    SEAMD_HIP(d_tmp.grow(2 * np * n));
+    SEAMD_HIP(d_pk0.grow(2 * np * n));
+    SEAMD_HIP(d_pk1.grow(2 * np * n));
     SEAMD_HIP(hipMemcpy(d_tmp, pk0, np * n * sizeof(uint32_t), hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_tmp + np * n, pk1, np * n * sizeof(uint32_t), hipMemcpyHostToDevice));
     for (size_t j = 0; j < np; j++)
@@ -410,11 +321,10 @@ int Context::gen_public_key(const uint8_t *sk_packed, const uint8_t *pk_seed, co
     rc = ensure_scratch(1);
     if (rc) return rc;
     const uint32_t n = (uint32_t)hp.n, np = (uint32_t)hp.nprimes;
-    DevTemp seeds, slab;  // slab [2][np][n]: residues/pk0 then a/pk1
-    SEAMD_HIP(seeds.alloc(128, true));
-    SEAMD_HIP(slab.alloc((size_t)2 * np * n * sizeof(uint32_t)));
-    uint8_t *d_seeds = seeds.as<uint8_t>();
-    uint32_t *d_c    = slab.as<uint32_t>();
+    DevBuf<uint8_t> d_seeds{Secret::yes};
+    DevBuf<uint32_t> d_c;  // [2][np][n]: residues/pk0 then a/pk1
+    SEAMD_HIP(d_seeds.grow(128));
+    SEAMD_HIP(d_c.grow((size_t)2 * np * n));
     SEAMD_HIP(hipMemcpy(d_seeds, ep_seed, 64, hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_seeds + 64, pk_seed, 64, hipMemcpyHostToDevice));
     uint32_t *d_p0 = d_c, *d_p1 = d_c + (size_t)np * n;
@@ -457,42 +367,44 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
     if (rc) return rc;
     const uint32_t n = (uint32_t)hp.n, np = (uint32_t)hp.nprimes;
     const size_t slab = (size_t)K * np * n;
-    DevTemp seeds, keys, codes, ep, pk0, pk1, tmp;
-    SEAMD_HIP(seeds.alloc(K * 192, true));
-    SEAMD_HIP(keys.alloc(K * (n / 4), true));
-    SEAMD_HIP(codes.alloc((size_t)K * n, true));
-    SEAMD_HIP(ep.alloc((size_t)K * n, true));
-    SEAMD_HIP(pk0.alloc(slab * sizeof(uint32_t)));
-    SEAMD_HIP(pk1.alloc(slab * sizeof(uint32_t)));
-    SEAMD_HIP(tmp.alloc((size_t)K * n * sizeof(uint32_t), true));   // NTT(ep): secret as well
-    uint8_t *d_sk_seeds = seeds.as<uint8_t>(), *d_pk_seeds = d_sk_seeds + K * 64, *d_ep_seeds = d_sk_seeds + K * 128;
+    DevBuf<uint8_t> seeds{Secret::yes}, keys{Secret::yes};
+    DevBuf<int8_t> codes{Secret::yes}, ep{Secret::yes};
+    DevBuf<uint32_t> pk0, pk1, tmp{Secret::yes};   // tmp: NTT(ep), secret as well
+    SEAMD_HIP(seeds.grow(K * 192));
+    SEAMD_HIP(keys.grow(K * (n / 4)));
+    SEAMD_HIP(codes.grow((size_t)K * n));
+    SEAMD_HIP(ep.grow((size_t)K * n));
+    SEAMD_HIP(pk0.grow(slab));
+    SEAMD_HIP(pk1.grow(slab));
+    SEAMD_HIP(tmp.grow((size_t)K * n));
+    uint8_t *d_sk_seeds = seeds, *d_pk_seeds = d_sk_seeds + K * 64, *d_ep_seeds = d_sk_seeds + K * 128;
     if (sk_seeds) SEAMD_HIP(hipMemcpy(d_sk_seeds, sk_seeds, K * 64, hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_pk_seeds, pk_seeds, K * 64, hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_ep_seeds, ep_seeds, K * 64, hipMemcpyHostToDevice));
     if (sk_in)
-        SEAMD_HIP(hipMemcpy(keys.p, sk_in, K * (n / 4), hipMemcpyHostToDevice));
+        SEAMD_HIP(hipMemcpy(keys, sk_in, K * (n / 4), hipMemcpyHostToDevice));
     else
     {
-        TernaryArgs ta{d_sk_seeds, codes.as<int8_t>(), nullptr, n, (uint32_t)K, nullptr, (uint32_t)num_cus};
+        TernaryArgs ta{d_sk_seeds, codes, nullptr, n, (uint32_t)K, nullptr, (uint32_t)num_cus};
         SEAMD_HIP(launch_sample_ternary(ta, nullptr));
-        SEAMD_HIP(launch_pack_ternary(codes.as<int8_t>(), keys.as<uint8_t>(), K * (n / 4), nullptr));
+        SEAMD_HIP(launch_pack_ternary(codes, keys, K * (n / 4), nullptr));
     }
-    CbdArgs ca{d_ep_seeds, nullptr, ep.as<int8_t>(), n / 16, (uint32_t)K};
+    CbdArgs ca{d_ep_seeds, nullptr, ep, n / 16, (uint32_t)K};
     SEAMD_HIP(launch_sample_cbd(ca, nullptr));
     for (uint32_t j = 0; j < np; j++)
     {
         // a_j for every key, counter 0 (gen_pk re-seeds per prime, ckks_asym.c:163), into pk1[:, j]
-        UniformArgs ua{d_pk_seeds, nullptr, nullptr, pk1.as<uint32_t>(), d_rej, rej_cap, (uint32_t)K, j, j + 1, np,
+        UniformArgs ua{d_pk_seeds, nullptr, nullptr, pk1, d_rej, rej_cap, (uint32_t)K, j, j + 1, np,
                        d_spec,     spec_cap, 0,      debug_flags};
         SEAMD_HIP(launch_sample_uniform(dp, ua, nullptr));
-        LowerSymArgs sa{keys.as<uint8_t>(), nullptr, ep.as<int8_t>(), pk1.as<uint32_t>() + (size_t)j * n,
-                        pk0.as<uint32_t>() + (size_t)j * n, tmp.as<uint32_t>(), nullptr, (int)j, n / 4, np * n, np * n};
+        LowerSymArgs sa{keys, nullptr, ep, pk1 + (size_t)j * n, pk0 + (size_t)j * n, tmp, nullptr, (int)j, n / 4,
+                        np * n, np * n};
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
     }
     SEAMD_HIP(hipDeviceSynchronize());
-    if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys.p, K * (n / 4), hipMemcpyDeviceToHost));
-    SEAMD_HIP(hipMemcpy(pk0_out, pk0.p, slab * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SEAMD_HIP(hipMemcpy(pk1_out, pk1.p, slab * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys, K * (n / 4), hipMemcpyDeviceToHost));
+    SEAMD_HIP(hipMemcpy(pk0_out, pk0, slab * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SEAMD_HIP(hipMemcpy(pk1_out, pk1, slab * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -501,10 +413,10 @@ void Context::stage_begin(int stage, hipStream_t st)
     if (!profiling) return;
     StageEvent ev;
     ev.stage = stage;
-    (void)hipEventCreate(&ev.start);
-    (void)hipEventCreate(&ev.stop);
+    (void)ev.start.create(hipEventDefault);
+    (void)ev.stop.create(hipEventDefault);
     (void)hipEventRecord(ev.start, st);
-    events.push_back(ev);
+    events.push_back(std::move(ev));
 }
 
 void Context::stage_end(hipStream_t st)
@@ -524,8 +436,6 @@ void Context::collect_events()
             stage_ms[ev.stage] += ms;
             stage_launches[ev.stage]++;
         }
-        (void)hipEventDestroy(ev.start);
-        (void)hipEventDestroy(ev.stop);
     }
     events.clear();
 }
@@ -550,15 +460,10 @@ int Context::encrypt_sym_seeded(const float *d_values, size_t B, const uint8_t *
 {
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
-    if (B > a_cap)
+    if (B * hp.nprimes * hp.n > d_a.size())
     {
         SEAMD_HIP(hipDeviceSynchronize());   // earlier calls may still read the old slab
-        wipe_device(d_a, a_cap * hp.nprimes * hp.n * sizeof(uint32_t));
-        if (d_a) (void)hipFree(d_a);
-        d_a   = nullptr;
-        a_cap = 0;
-        SEAMD_HIP(hipMalloc((void **)&d_a, B * hp.nprimes * hp.n * sizeof(uint32_t)));
-        a_cap = B;
+        SEAMD_HIP(d_a.grow(B * hp.nprimes * hp.n));
     }
     int rc = begin_call(st);
     if (rc) return rc;
@@ -691,8 +596,8 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
                          (debug_flags & 512) || staged_mode == 1);
     if (staged && !cand_stream)
     {
-        SEAMD_HIP(hipStreamCreateWithFlags(&cand_stream, hipStreamNonBlocking));
-        for (auto &e : ev_cand) SEAMD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        SEAMD_HIP(cand_stream.create(hipStreamNonBlocking));
+        for (Event &e : ev_cand) SEAMD_HIP(e.create(hipEventDisableTiming));
     }
     for (uint32_t j = 0; j < np; j++)
     {
@@ -830,33 +735,20 @@ int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, cons
     const size_t total = plan.total;
     int rc             = ensure_scratch(B, B + total);  // reject lists / candidates of the virtual ciphertexts too
     if (rc) return rc;
-    if (total > sp_cap)
+    if (d_sp_seeds.size() < total * 64 || d_sp_ctr.size() < total || d_sp_ctrout.size() < total ||
+        d_sp_rows.size() < total * n || d_sp_prime.size() < total)
     {
         SEAMD_HIP(hipDeviceSynchronize());
-        wipe_device(d_sp_seeds, sp_cap * 64);
-        void *old[] = {d_sp_seeds, d_sp_ctr, d_sp_ctrout, d_sp_rows, d_sp_prime};
-        for (void *p : old)
-            if (p) (void)hipFree(p);
-        d_sp_seeds = nullptr, d_sp_ctr = nullptr, d_sp_ctrout = nullptr, d_sp_rows = nullptr, d_sp_prime = nullptr;
-        sp_cap = 0;
-        SEAMD_HIP(hipMalloc((void **)&d_sp_seeds, total * 64));
-        SEAMD_HIP(hipMalloc((void **)&d_sp_ctr, total * sizeof(uint64_t)));
-        SEAMD_HIP(hipMalloc((void **)&d_sp_ctrout, total * sizeof(uint64_t)));
-        SEAMD_HIP(hipMalloc((void **)&d_sp_rows, total * (size_t)n * sizeof(uint32_t)));
-        SEAMD_HIP(hipMalloc((void **)&d_sp_prime, total));
-        sp_cap = total;
+        SEAMD_HIP(d_sp_seeds.grow(total * 64));
+        SEAMD_HIP(d_sp_ctr.grow(total));
+        SEAMD_HIP(d_sp_ctrout.grow(total));
+        SEAMD_HIP(d_sp_rows.grow(total * n));
+        SEAMD_HIP(d_sp_prime.grow(total));
     }
-    if (B > sp_fail_cap)
-    {
-        SEAMD_HIP(hipDeviceSynchronize());
-        if (d_sp_fail) (void)hipFree(d_sp_fail);
-        d_sp_fail = nullptr, sp_fail_cap = 0;
-        SEAMD_HIP(hipMalloc((void **)&d_sp_fail, 1024 * sizeof(uint32_t)));
-        sp_fail_cap = 1024;
-    }
+    SEAMD_HIP(d_sp_fail.grow(1024));   // small_batch_plan: B <= 1024
     // Three streams whatever the length of the prime chain (the runtime's default of 4 hardware queues is
     // enough): the guesses of ALL primes are ONE launch (UniformArgs::prime_of).
-    if (!spec_stream) SEAMD_HIP(hipStreamCreateWithFlags(&spec_stream, hipStreamNonBlocking));
+    SEAMD_HIP(spec_stream.create(hipStreamNonBlocking));
 
     CbdArgs ca{d_seeds, nullptr, d_err, n / 16, (uint32_t)B};
     EncArgs ea{d_values, d_err, nullptr, d_c0, d_c1, d_ntt_pte, d_pte, d_status, d_general, d_compact};

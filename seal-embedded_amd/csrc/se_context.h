@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "kernels/kernel_args.h"
+#include "se_devmem.h"
 #include "se_host_tables.h"
 #include "se_types.h"
 
@@ -26,7 +28,7 @@ struct HostPipe;
 struct StageEvent
 {
     int stage;
-    hipEvent_t start, stop;
+    Event start, stop;
 };
 
 struct Context
@@ -37,62 +39,53 @@ struct Context
     int device = 0;
     std::vector<uint16_t> index_map;  // host copy (SE_PTRS::index_map_ptr, tests)
 
-    // read-only device slabs
-    uint16_t *d_inv_map = nullptr;
-    double *d_ifft_w    = nullptr;
-    uint32_t *d_ntt_rw  = nullptr;
-    uint32_t *d_intt_rw = nullptr;
-    uint16_t *d_map     = nullptr;
-    uint16_t *d_gather  = nullptr;
-    uint32_t *d_s_hat   = nullptr;
-    uint32_t *d_pk0     = nullptr;
-    uint32_t *d_pk1     = nullptr;
+    // read-only device slabs (NTT(s) is secret)
+    DevBuf<uint16_t> d_inv_map, d_map, d_gather;
+    DevBuf<double> d_ifft_w;
+    DevBuf<uint32_t> d_ntt_rw, d_intt_rw, d_pk0, d_pk1;
+    DevBuf<uint32_t> d_s_hat{Secret::yes};
     bool have_sk = false, have_pk = false;
 
-    // scratch, grown on demand
-    int8_t *d_err      = nullptr;  // [cap][2n]
-    int8_t *d_ucodes   = nullptr;  // [cap][n]
-    uint64_t *d_ctr    = nullptr;  // [cap]
-    uint32_t *d_rej    = nullptr;  // [cap][rej_cap]
-    uint32_t *d_spec   = nullptr;  // [cap][spec_cap] speculative redraw candidates (helper waves)
+    // scratch, grown on demand (ensure_scratch): `cap` ciphertexts, `rows` >= cap rows of the reject lists and
+    // candidates (the virtual ciphertexts of the small-batch path need only these)
+    DevBuf<int8_t> d_err{Secret::yes};     // [cap][2n]
+    DevBuf<int8_t> d_ucodes{Secret::yes};  // [cap][n]
+    DevBuf<uint64_t> d_ctr;                // [cap]
+    DevBuf<uint32_t> d_rej;                // [rows][rej_cap]
+    DevBuf<uint32_t> d_spec;               // [rows][spec_cap] speculative redraw candidates (helper waves)
     uint32_t spec_cap  = 128;
-    uint32_t *d_a      = nullptr;  // [a_cap][np][n]: `a` when the caller does not want c1 back
-    size_t a_cap       = 0;
+    DevBuf<uint32_t> d_a{Secret::yes};     // [B][np][n]: `a` when the caller does not want c1 back
     // small-batch prime speculation (encrypt_sym_small): virtual-ciphertext scratch and streams
-    uint8_t *d_sp_seeds   = nullptr;  // [sp_cap][64]
-    uint64_t *d_sp_ctr    = nullptr;  // [sp_cap] guessed start counters
-    uint64_t *d_sp_ctrout = nullptr;  // [sp_cap] end counters under each guess
-    uint32_t *d_sp_rows   = nullptr;  // [sp_cap][n] a_j under each guess
-    uint8_t *d_sp_prime   = nullptr;  // [sp_cap] prime of each virtual ciphertext
-    uint32_t *d_sp_fail   = nullptr;  // [sp_fail_cap] 0 = chain resolved, j = window of prime j missed
-    size_t sp_cap = 0, sp_fail_cap = 0;
+    DevBuf<uint8_t> d_sp_seeds{Secret::yes};  // [total][64]
+    DevBuf<uint64_t> d_sp_ctr;                // [total] guessed start counters
+    DevBuf<uint64_t> d_sp_ctrout;             // [total] end counters under each guess
+    DevBuf<uint32_t> d_sp_rows{Secret::yes};  // [total][n] a_j under each guess (the same data as d_a)
+    DevBuf<uint8_t> d_sp_prime;               // [total] prime of each virtual ciphertext
+    DevBuf<uint32_t> d_sp_fail;               // [1024] 0 = chain resolved, j = window of prime j missed
     uint32_t small_limit = getenv("SE_AMD_SMALL_LIMIT") ? (uint32_t)atoi(getenv("SE_AMD_SMALL_LIMIT")) : 65536;  // virtual ciphertexts a small call may fan out to
     // ... and the bytes their output rows may take (one n-word row per virtual ciphertext)
     size_t small_bytes = getenv("SE_AMD_SMALL_BYTES") ? (size_t)atoll(getenv("SE_AMD_SMALL_BYTES")) : ((size_t)1 << 30);
-    hipStream_t spec_stream = nullptr;   // the guesses of ALL primes run as one launch on it
+    Stream spec_stream;   // the guesses of ALL primes run as one launch on it
     // staged sampler (k_bulk_pair / k_candidates / k_resolve_wave): candidates on a stream of their own
-    hipStream_t cand_stream = nullptr;
-    hipEvent_t ev_cand[kMaxPrimes] = {};
-    uint32_t *d_nrej = nullptr;          // [scratch_cap] rejected coefficients of the current polynomial
-    uint32_t *d_flagged = nullptr;       // [1 + scratch_cap] staged forms: ciphertexts k_resolve_light left to k_resolve_wave
-    uint8_t *d_compact  = nullptr;  // [scratch_cap] k_encode_rns -> k_ntt_fuse: plaintext b travels as one int32 row
-    uint32_t *d_general = nullptr;  // [1 + general_cap] plaintexts the fast fused kernel declined (count, indices)
-    size_t general_cap  = 0;
-    size_t scratch_cap = 0;   // ciphertexts d_err / d_ucodes / d_ctr hold
-    size_t rows_cap    = 0;   // rows of d_rej / d_spec (>= scratch_cap: virtual ciphertexts need only these)
+    Stream cand_stream;
+    Event ev_cand[kMaxPrimes];
+    DevBuf<uint32_t> d_nrej;      // [cap] rejected coefficients of the current polynomial
+    DevBuf<uint32_t> d_flagged;   // [1 + cap] staged forms: ciphertexts k_resolve_light left to k_resolve_wave
+    DevBuf<uint8_t> d_compact;    // [cap] k_encode_rns -> k_ntt_fuse: plaintext b travels as one int32 row
+    DevBuf<uint32_t> d_general;   // [1 + B] plaintexts the fast fused kernel declined (count, indices)
     uint32_t rej_cap   = 256;
     uint32_t debug_flags = 0;  // timing ablations of the uniform sampler (tests/tools only)
 
     // second stream: the CBD error sampler runs beside the uniform sampler (different seeds, no
     // data dependency); joined before the fused encode+encrypt kernel.
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_cbd = nullptr, ev_enc = nullptr;
-    hipEvent_t ev_prime[kMaxPrimes] = {};
+    Stream aux_stream;
+    Event ev_fork, ev_join, ev_cbd, ev_enc;
+    Event ev_prime[kMaxPrimes];
     // One set of scratch per context: successive calls are ordered on it.  Host threads serialise on
     // `mu`; a call waits (on its own stream) for `ev_done` of the previous call, whatever stream
     // that one ran on, before it touches the scratch or forks the auxiliary streams.
     std::mutex mu;
-    hipEvent_t ev_done = nullptr;
+    Event ev_done;
     bool have_done     = false;
     int num_cus        = 256;
     // public-key path: chunks the batch is cut into so that the CBD sampler of chunk k+1 runs beside the
@@ -108,7 +101,7 @@ struct Context
                            // at n = 4096, B = 65536 both measure the same and fused moves less data
 
     // host-pointer entry points: chunked PCIe pipeline (se_hostpipe.h), created on first use
-    HostPipe *host_pipe = nullptr;
+    std::unique_ptr<HostPipe> host_pipe;
 
     // profiling
     bool profiling = false;

@@ -104,145 +104,59 @@ static bool is_pinned(const void *p)
     return a.type == hipMemoryTypeHost;
 }
 
-// the device slots hold PRNG seeds, plaintext values and m + e between calls: zeroed before they go back to the
-// allocator (callers have drained the streams that used them)
-static int regrow(void **p, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap) return 0;
-    if (*p)
-    {
-        (void)hipMemset(*p, 0, *cap);
-        (void)hipFree(*p);
-    }
-    *p   = nullptr;
-    *cap = 0;
-    SEAMD_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
-    return 0;
-}
-
-// zero the secret-bearing buffers of a slot (s.cap ciphertexts: seeds of e / u, the shareable seed, plaintext values)
-void HostPipe::wipe_slot(Slot &s)
-{
-    if (s.seeds) (void)hipMemset(s.seeds, 0, s.cap * 64);
-    if (s.share_seeds) (void)hipMemset(s.share_seeds, 0, s.cap * 64);
-    if (s.values) (void)hipMemset(s.values, 0, s.cap * values_bytes_per_ct);
-}
-
+// The slots and the ring wipe and free themselves (se_devmem.h) once both streams are drained.
 HostPipe::~HostPipe()
 {
     (void)hipSetDevice(device);
     if (compute) (void)hipStreamSynchronize(compute);
     if (copy) (void)hipStreamSynchronize(copy);
-    for (auto &s : slot)
-    {
-        // secret-bearing slots (seeds of e / u, the shareable seed, values, m + e) are wiped first
-        wipe_slot(s);
-        if (s.pte) (void)hipMemset(s.pte, 0, s.cap_pte);
-        if (s.ntt_pte) (void)hipMemset(s.ntt_pte, 0, s.cap_ntt);   // NTT(m + e) is as sensitive as m + e
-        (void)hipDeviceSynchronize();
-        void *ptrs[] = {s.values, s.seeds, s.share_seeds, s.c0, s.c1, s.ntt_pte, s.pte};
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
-        if (s.computed) (void)hipEventDestroy(s.computed);
-        if (s.copied) (void)hipEventDestroy(s.copied);
-    }
-    for (int r = 0; r < kRing; r++)
-    {
-        if (ring[r])
-        {
-            explicit_bzero(ring[r], ring_bytes);   // the pinned staging ring carried m + e / ciphertext pieces
-            (void)hipHostFree(ring[r]);
-        }
-        if (ring_ev[r]) (void)hipEventDestroy(ring_ev[r]);
-    }
-    if (d_status) (void)hipFree(d_status);
-    if (h_status) (void)hipHostFree(h_status);
-    if (compute) (void)hipStreamDestroy(compute);
-    if (copy) (void)hipStreamDestroy(copy);
-    delete pool;
 }
 
 int HostPipe::init(int dev)
 {
     device = dev;
     SEAMD_HIP(hipSetDevice(device));
-    SEAMD_HIP(hipStreamCreateWithFlags(&compute, hipStreamNonBlocking));
-    SEAMD_HIP(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+    SEAMD_HIP(compute.create(hipStreamNonBlocking));
+    SEAMD_HIP(copy.create(hipStreamNonBlocking));
     for (auto &s : slot)
     {
-        SEAMD_HIP(hipEventCreateWithFlags(&s.computed, hipEventDisableTiming));
-        SEAMD_HIP(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+        SEAMD_HIP(s.computed.create(hipEventDisableTiming));
+        SEAMD_HIP(s.copied.create(hipEventDisableTiming));
     }
-    for (int r = 0; r < kRing; r++)
-        SEAMD_HIP(hipEventCreateWithFlags(&ring_ev[r], hipEventDisableTiming));
-    pool = new CopyPool(default_copy_threads());
+    for (auto &r : ring) SEAMD_HIP(r.ev.create(hipEventDisableTiming));
+    pool = std::make_unique<CopyPool>(default_copy_threads());
     return 0;
 }
 
 int HostPipe::ensure(Context &c, size_t chunk, size_t B, bool want_ntt, bool want_pte, bool staged)
 {
-    const size_t n = c.hp.n, np = c.hp.nprimes;
-    const size_t ct_bytes = np * n * 4;
+    const size_t n = c.hp.n, ct_words = c.hp.nprimes * n;
     for (auto &s : slot)
     {
-        if (chunk > s.cap)
+        if (s.values.size() < chunk * (n / 2) || s.seeds.size() < chunk * 64 || s.share_seeds.size() < chunk * 64 ||
+            s.c0.size() < chunk * ct_words || s.c1.size() < chunk * ct_words)
         {
-            // wipe_slot's memsets run on the null stream, which does not order against the NON-BLOCKING compute / copy
-            // streams: drain them first instead of relying on the callers having done so
-            if (compute) SEAMD_HIP(hipStreamSynchronize(compute));
-            if (copy) SEAMD_HIP(hipStreamSynchronize(copy));
-            wipe_slot(s);
-            values_bytes_per_ct = (n / 2) * sizeof(float);
-            void **ptrs[] = {&s.values, &s.seeds, &s.share_seeds, &s.c0, &s.c1};
-            for (void **p : ptrs)
-                if (*p)
-                {
-                    (void)hipFree(*p);
-                    *p = nullptr;
-                }
-            s.cap = 0;
-            SEAMD_HIP(hipMalloc(&s.values, chunk * (n / 2) * sizeof(float)));
-            SEAMD_HIP(hipMalloc(&s.seeds, chunk * 64));
-            SEAMD_HIP(hipMalloc(&s.share_seeds, chunk * 64));
-            SEAMD_HIP(hipMalloc(&s.c0, chunk * ct_bytes));
-            SEAMD_HIP(hipMalloc(&s.c1, chunk * ct_bytes));
-            s.cap = chunk;
+            // the wipes of the secret buffers run on the null stream, which does not order against the NON-BLOCKING
+            // compute / copy streams: drain them first instead of relying on the callers having done so
+            SEAMD_HIP(hipStreamSynchronize(compute));
+            SEAMD_HIP(hipStreamSynchronize(copy));
+            SEAMD_HIP(s.values.grow(chunk * (n / 2)));
+            SEAMD_HIP(s.seeds.grow(chunk * 64));
+            SEAMD_HIP(s.share_seeds.grow(chunk * 64));
+            SEAMD_HIP(s.c0.grow(chunk * ct_words));
+            SEAMD_HIP(s.c1.grow(chunk * ct_words));
         }
-        int rc;
-        if (want_ntt && (rc = regrow(&s.ntt_pte, &s.cap_ntt, chunk * ct_bytes))) return rc;
-        if (want_pte && (rc = regrow(&s.pte, &s.cap_pte, chunk * n * 8))) return rc;
+        if (want_ntt) SEAMD_HIP(s.ntt_pte.grow(chunk * ct_words));
+        if (want_pte) SEAMD_HIP(s.pte.grow(chunk * n));
     }
-    int rc;
-    if ((rc = regrow(&d_status, &status_cap, B))) return rc;
-    if (B > h_status_cap)
-    {
-        if (h_status) (void)hipHostFree(h_status);
-        h_status = nullptr, h_status_cap = 0;
-        const size_t want = (std::max<size_t>(B, 4096) + 4095) & ~size_t(4095);
-        SEAMD_HIP(hipHostMalloc((void **)&h_status, want, hipHostMallocDefault));
-        h_status_cap = want;
-    }
+    SEAMD_HIP(d_status.grow(B));
+    SEAMD_HIP(h_status.grow((std::max<size_t>(B, 4096) + 4095) & ~size_t(4095)));
     if (staged)
     {
         // ring entries sized to the work: a single small ciphertext must not pin 256 MiB
-        size_t want = std::min(kPieceMax, std::max(chunk * ct_bytes, chunk * n * 8));
+        size_t want = std::min(kPieceMax, std::max(chunk * ct_words * 4, chunk * n * 8));
         want        = (want + 4095) & ~size_t(4095);
-        if (want > ring_bytes)
-        {
-            for (int r = 0; r < kRing; r++)
-            {
-                if (ring[r])
-                {
-                    explicit_bzero(ring[r], ring_bytes);
-                    (void)hipHostFree(ring[r]);
-                }
-                ring[r] = nullptr;
-            }
-            ring_bytes = 0;
-            for (int r = 0; r < kRing; r++) SEAMD_HIP(hipHostMalloc(&ring[r], want, hipHostMallocDefault));
-            ring_bytes = want;
-        }
+        for (auto &r : ring) SEAMD_HIP(r.buf.grow(want));
     }
     return 0;
 }
@@ -306,17 +220,14 @@ int HostPipe::run(Context &c, bool asym, const float *values, size_t B, const ui
             SEAMD_HIP(hipMemcpyAsync(s.share_seeds, share_seeds + lo * 64, cnt * 64,
                                      hipMemcpyHostToDevice, compute));
         if (k >= kSlots) SEAMD_HIP(hipStreamWaitEvent(compute, s.copied, 0));
-        uint8_t *st = (uint8_t *)d_status + lo;
+        uint8_t *st = d_status + lo;
+        uint32_t *s_ntt = ntt_pte ? s.ntt_pte.get() : nullptr;
+        int64_t *s_pte  = pte ? s.pte.get() : nullptr;
         int r;
         if (asym)
-            r = c.encrypt_asym((const float *)s.values, cnt, (const uint8_t *)s.seeds,
-                               (uint32_t *)s.c0, (uint32_t *)s.c1, ntt_pte ? (uint32_t *)s.ntt_pte : nullptr,
-                               pte ? (int64_t *)s.pte : nullptr, st, compute);
+            r = c.encrypt_asym(s.values, cnt, s.seeds, s.c0, s.c1, s_ntt, s_pte, st, compute);
         else
-            r = c.encrypt_sym((const float *)s.values, cnt, (const uint8_t *)s.share_seeds,
-                              (const uint8_t *)s.seeds, (uint32_t *)s.c0, (uint32_t *)s.c1,
-                              ntt_pte ? (uint32_t *)s.ntt_pte : nullptr, pte ? (int64_t *)s.pte : nullptr,
-                              st, compute);
+            r = c.encrypt_sym(s.values, cnt, s.share_seeds, s.seeds, s.c0, s.c1, s_ntt, s_pte, st, compute);
         if (r) return r;
         SEAMD_HIP(hipEventRecord(s.computed, compute));
         return 0;
@@ -324,6 +235,8 @@ int HostPipe::run(Context &c, bool asym, const float *values, size_t B, const ui
 
     // the D2H schedule: per chunk c0, c1, (ntt_pte), (pte); staged outputs in ring-sized pieces
     std::vector<Piece> pieces;
+    size_t ring_bytes = kPieceMax;   // pieces staged through the ring fit every entry
+    for (auto &r : ring) ring_bytes = std::min(ring_bytes, r.buf.size());
     for (size_t k = 0; k < nch; k++)
     {
         Slot &s         = slot[k % kSlots];
@@ -358,8 +271,8 @@ int HostPipe::run(Context &c, bool asym, const float *values, size_t B, const ui
     auto drain_one = [&]() -> int {
         InFlight f = inflight.front();
         inflight.pop_front();
-        SEAMD_HIP(hipEventSynchronize(ring_ev[f.r]));
-        pool->copy(f.dst, ring[f.r], f.bytes);
+        SEAMD_HIP(hipEventSynchronize(ring[f.r].ev));
+        pool->copy(f.dst, ring[f.r].buf, f.bytes);
         return 0;
     };
 
@@ -379,8 +292,8 @@ int HostPipe::run(Context &c, bool asym, const float *values, size_t B, const ui
                 if ((rc = drain_one())) { failure = rc; break; }
             if (failure) break;
             const int r = int(ring_next++ % kRing);
-            SEAMD_HIP(hipMemcpyAsync(ring[r], p.src, p.bytes, hipMemcpyDeviceToHost, copy));
-            SEAMD_HIP(hipEventRecord(ring_ev[r], copy));
+            SEAMD_HIP(hipMemcpyAsync(ring[r].buf, p.src, p.bytes, hipMemcpyDeviceToHost, copy));
+            SEAMD_HIP(hipEventRecord(ring[r].ev, copy));
             inflight.push_back({r, p.dst, p.bytes});
         }
         if (p.last)

@@ -18,9 +18,12 @@
 
 #include <condition_variable>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
+
+#include "se_devmem.h"
 
 namespace seamd {
 
@@ -54,28 +57,31 @@ struct HostPipe
     static constexpr int kRing        = 4;
     static constexpr size_t kPieceMax = size_t(64) << 20;
 
+    // one chunk of ciphertexts on the device; the secret buffers hold PRNG seeds, plaintext values and m + e
     struct Slot
     {
-        void *values = nullptr, *seeds = nullptr, *share_seeds = nullptr;
-        void *c0 = nullptr, *c1 = nullptr, *ntt_pte = nullptr, *pte = nullptr;
-        size_t cap = 0, cap_ntt = 0, cap_pte = 0;
-        hipEvent_t computed = nullptr, copied = nullptr;
+        DevBuf<float> values{Secret::yes};
+        DevBuf<uint8_t> seeds{Secret::yes}, share_seeds{Secret::yes};
+        DevBuf<uint32_t> c0, c1;
+        DevBuf<uint32_t> ntt_pte{Secret::yes};   // NTT(m + e) is as sensitive as m + e
+        DevBuf<int64_t> pte{Secret::yes};
+        Event computed, copied;
     };
 
     int device = 0;
     Slot slot[kSlots];
-    void *ring[kRing]           = {};
-    hipEvent_t ring_ev[kRing]   = {};
-    size_t ring_bytes           = 0;
-    void *d_status              = nullptr;
-    size_t status_cap           = 0;
-    uint8_t *h_status           = nullptr;   // pinned: the status bytes come back on the copy stream, behind the last piece
-    size_t h_status_cap         = 0;
-    hipStream_t compute = nullptr, copy = nullptr;
-    CopyPool *pool      = nullptr;
+    // pinned staging of the pieces that do not go straight into the caller's memory (m + e, ciphertexts)
+    struct RingEntry
+    {
+        PinnedBuf<char> buf{Secret::yes};
+        Event ev;
+    };
+    RingEntry ring[kRing];
+    DevBuf<uint8_t> d_status;
+    PinnedBuf<uint8_t> h_status;   // the status bytes come back on the copy stream, behind the last piece
+    Stream compute, copy;
+    std::unique_ptr<CopyPool> pool;
     size_t chunk_override = 0;  // test hook: ciphertexts per chunk (0 = automatic)
-    size_t values_bytes_per_ct = 0;   // (n / 2) floats: size of one ciphertext's slice of Slot::values
-    void wipe_slot(Slot &s);          // zero the seeds / values a slot holds (before it is freed or regrown)
 
     ~HostPipe();
     int init(int device);

@@ -20,6 +20,7 @@
 #include <sys/random.h>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -27,6 +28,8 @@
 #include "se_context.h"
 
 using seamd::Context;
+using seamd::DevBuf;
+using seamd::Secret;
 
 namespace {
 
@@ -62,13 +65,13 @@ size_t max_primes_for(size_t n)
     }
 }
 
-// Per-degree GPU state: the context plus a device slab carved into the operand buffers of one call.
+// Per-degree GPU state: the context plus a device slab carved into the operand buffers of one call.  The slabs hold
+// secrets between calls (packed secret key, u, e / e1, PRNG seeds, m + e) and wipe themselves when they are freed.
 struct Lower
 {
     se_amd_ctx *h = nullptr;
     size_t n      = 0;
-    uint8_t *slab = nullptr;
-    size_t slab_bytes = 0;
+    DevBuf<uint8_t> slab{Secret::yes};
     double *cplx_in = nullptr, *cplx_out = nullptr;  // [n][2]
     int64_t *i64     = nullptr;                      // [n]
     uint32_t *u32[8] = {};                           // [n] each
@@ -77,8 +80,6 @@ struct Lower
     uint8_t *seed    = nullptr;                      // [64]
     uint64_t *ctr    = nullptr;                      // [2]
     uint32_t *fail   = nullptr;                      // [1]
-    uint8_t *bytes   = nullptr;                      // growable raw buffer (prng_fill_buffer)
-    size_t bytes_cap = 0;
     std::vector<uint32_t> roots_cache[seamd::kMaxPrimes];   // ntt_roots_initialize output per prime (host table)
     Context &c() { return h->c; }
 
@@ -107,97 +108,59 @@ struct Lower
         uint32_t count[seamd::kMaxPrimes] = {}, offset[seamd::kMaxPrimes] = {};
         uint32_t prime_of_step(uint32_t k) const { return (first + k) % chain; }
         uint32_t step_of_prime(uint32_t j) const { return (j + chain - first) % chain; }
-        size_t cap = 0;                                  // virtual ciphertexts the device buffers hold
-        uint8_t *d_meta = nullptr;                       // [cap] x (64 seed + 8 ctr + 8 ctrout + 1 prime), carved below
+        DevBuf<uint8_t> d_meta{Secret::yes};             // [total] x (64 seed + 8 ctr + 8 ctrout + 1 prime), carved below
         uint8_t *d_seeds = nullptr, *d_prime = nullptr;
         uint64_t *d_ctr = nullptr, *d_ctrout = nullptr;
-        uint32_t *d_rows = nullptr;                      // [cap][n]
+        DevBuf<uint32_t> d_rows{Secret::yes};            // [total][n]: a_j under each guessed counter
         std::vector<uint64_t> h_ctrout;
-        hipStream_t st = nullptr, cp = nullptr;
-        hipEvent_t ev_sampled = nullptr, ev_kernel[seamd::kMaxPrimes] = {}, ev_copied[seamd::kMaxPrimes] = {};
+        seamd::Stream st, cp;
+        seamd::Event ev_sampled, ev_kernel[seamd::kMaxPrimes], ev_copied[seamd::kMaxPrimes];
         // precomputed primes
         bool pre[seamd::kMaxPrimes]          = {};
         uint64_t pre_start[seamd::kMaxPrimes] = {}, pre_end[seamd::kMaxPrimes] = {};
         std::vector<int64_t> h_pte;                      // the plaintext d_pte holds (empty: none)
         std::vector<uint8_t> h_key;                      // the packed key d_key holds
         // one slab (one memset wipes it): d_pte [n] int64 | d_out [np][3][n]: c0 | ntt_pte | s_save | d_key [n/4]
-        uint8_t *d_slab = nullptr;
-        size_t slab_bytes = 0;
+        DevBuf<uint8_t> d_slab{Secret::yes};
         int64_t *d_pte  = nullptr;
         uint8_t *d_key  = nullptr;
         uint32_t *d_out = nullptr;
         bool dirty = false;                              // secret-bearing copies exist since the last wipe
-        uint32_t *h_stage = nullptr;                     // pinned [np][4][n]: a | c0 | ntt_pte | s_save
+        seamd::PinnedBuf<uint32_t> h_stage{Secret::yes};   // [np][4][n]: a | c0 | ntt_pte | s_save
     } sym;
+
+    ~Lower()
+    {
+        if (!sym.h_pte.empty()) explicit_bzero(sym.h_pte.data(), sym.h_pte.size() * 8);
+        if (!sym.h_key.empty()) explicit_bzero(sym.h_key.data(), sym.h_key.size());
+        se_amd_destroy(h);
+    }
 };
 
-std::map<size_t, Lower *> g_lower;
+std::map<size_t, std::unique_ptr<Lower>> g_lower;
 
-// prng_fill_buffer's own device scratch (a pure PRNG call needs no parameter set)
+// prng_fill_buffer's own device scratch (a pure PRNG call needs no parameter set): seed, counter, output
 struct PrngScratch
 {
-    int device     = 0;
-    bool ready     = false;
-    uint8_t *seed  = nullptr;   // [64]
-    uint64_t *ctr  = nullptr;   // [1]
-    uint8_t *bytes = nullptr;
-    size_t cap     = 0;
+    int device = 0;
+    DevBuf<uint8_t> seed{Secret::yes};
+    DevBuf<uint64_t> ctr{Secret::yes};
+    DevBuf<uint8_t> bytes{Secret::yes};
 } g_prng;
 
-// The operand slabs hold secrets between calls (packed secret key, u, e / e1, PRNG seeds, m + e):
-// se_amd_lower_shutdown() -- also run at process exit -- wipes and frees them and destroys the per-degree
-// contexts.  The surface stays usable afterwards (state is rebuilt on the next call).
+// se_amd_lower_shutdown() -- also run at process exit -- destroys the per-degree state and the PRNG scratch (their
+// buffers wipe themselves).  The surface stays usable afterwards (state is rebuilt on the next call).
 void lower_shutdown()
 {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     for (auto &kv : g_lower)
     {
-        Lower *L = kv.second;
-        if (hipSetDevice(L->c().device) == hipSuccess)
-        {
-            (void)hipDeviceSynchronize();
-            if (L->slab) (void)hipMemset(L->slab, 0, L->slab_bytes);
-            if (L->bytes) (void)hipMemset(L->bytes, 0, L->bytes_cap);
-            (void)hipDeviceSynchronize();
-            if (L->slab) (void)hipFree(L->slab);
-            if (L->bytes) (void)hipFree(L->bytes);
-            Lower::SymSpec &S = L->sym;
-            const size_t n = L->n, np = L->c().hp.nprimes;
-            if (S.d_rows) (void)hipMemset(S.d_rows, 0, S.cap * n * sizeof(uint32_t));
-            if (S.d_meta) (void)hipMemset(S.d_meta, 0, S.cap * 88);
-            if (S.d_slab) (void)hipMemset(S.d_slab, 0, S.slab_bytes);
-            (void)hipDeviceSynchronize();
-            void *dev[] = {S.d_rows, S.d_meta, S.d_slab};
-            for (void *q : dev)
-                if (q) (void)hipFree(q);
-            if (S.h_stage)
-            {
-                explicit_bzero(S.h_stage, np * 4 * n * sizeof(uint32_t));
-                (void)hipHostFree(S.h_stage);
-            }
-            if (!S.h_pte.empty()) explicit_bzero(S.h_pte.data(), S.h_pte.size() * 8);
-            if (!S.h_key.empty()) explicit_bzero(S.h_key.data(), S.h_key.size());
-            if (S.st) (void)hipStreamDestroy(S.st);
-            if (S.cp) (void)hipStreamDestroy(S.cp);
-            if (S.ev_sampled) (void)hipEventDestroy(S.ev_sampled);
-            for (auto &e : S.ev_kernel)
-                if (e) (void)hipEventDestroy(e);
-            for (auto &e : S.ev_copied)
-                if (e) (void)hipEventDestroy(e);
-        }
-        se_amd_destroy(L->h);
-        delete L;
+        (void)hipSetDevice(kv.second->c().device);
+        (void)hipDeviceSynchronize();
+        kv.second.reset();
     }
     g_lower.clear();
-    if (g_prng.ready && hipSetDevice(g_prng.device) == hipSuccess)
-    {
-        (void)hipMemset(g_prng.seed, 0, 64);
-        (void)hipMemset(g_prng.ctr, 0, 8);
-        if (g_prng.bytes) (void)hipMemset(g_prng.bytes, 0, g_prng.cap);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(g_prng.seed), (void)hipFree(g_prng.ctr);
-        if (g_prng.bytes) (void)hipFree(g_prng.bytes);
-    }
+    if (g_prng.seed) (void)hipSetDevice(g_prng.device);
     g_prng = PrngScratch();
 }
 
@@ -222,15 +185,14 @@ Lower &lower_for_degree(size_t n)
         exit(1);
     }
     register_shutdown();
-    Lower *L = new Lower();
-    L->n     = n;
+    auto L  = std::make_unique<Lower>();
+    L->n    = n;
     int dev  = getenv("SE_AMD_DEVICE") ? atoi(getenv("SE_AMD_DEVICE")) : 0;
     if (se_amd_create(&L->h, n, np, dev) != SE_SUCCESS) die("GPU context");
     if (L->c().ensure_scratch(1) != 0) die("GPU scratch");
     size_t total = 16 * n * 2 + 8 * n + 8 * 4 * n + 2 * n + n / 4 + 64 + 16 + 16;
     LOWER_HIP(hipSetDevice(L->c().device));
-    LOWER_HIP(hipMalloc((void **)&L->slab, total));
-    L->slab_bytes = total;
+    LOWER_HIP(L->slab.grow(total));
     uint8_t *p  = L->slab;
     L->cplx_in  = (double *)p, p += 16 * n;
     L->cplx_out = (double *)p, p += 16 * n;
@@ -241,8 +203,7 @@ Lower &lower_for_degree(size_t n)
     L->seed   = p, p += 64;
     L->ctr    = (uint64_t *)p, p += 16;
     L->fail   = (uint32_t *)p;
-    g_lower[n] = L;
-    return *L;
+    return *(g_lower[n] = std::move(L));
 }
 
 // context for a Parms; checks that the caller's chain is the default one the tables were built for
@@ -353,27 +314,15 @@ void prng_fill_buffer(size_t byte_count, SE_PRNG *prng, void *buffer)
         fprintf(stderr, "Error! prng_fill_buffer: %zu bytes in one call (limit 4 GiB - 1)\n", byte_count);
         exit(1);
     }
-    if (!g_prng.ready)
+    if (!g_prng.seed)
     {
         register_shutdown();
         g_prng.device = getenv("SE_AMD_DEVICE") ? atoi(getenv("SE_AMD_DEVICE")) : 0;
-        LOWER_HIP(hipSetDevice(g_prng.device));
-        LOWER_HIP(hipMalloc((void **)&g_prng.seed, 64));
-        LOWER_HIP(hipMalloc((void **)&g_prng.ctr, 8));
-        g_prng.ready = true;
     }
     LOWER_HIP(hipSetDevice(g_prng.device));
-    if (byte_count > g_prng.cap)
-    {
-        if (g_prng.bytes)
-        {
-            (void)hipMemset(g_prng.bytes, 0, g_prng.cap);   // PRNG output of a secret seed
-            (void)hipFree(g_prng.bytes);
-        }
-        g_prng.bytes = nullptr, g_prng.cap = 0;
-        LOWER_HIP(hipMalloc((void **)&g_prng.bytes, byte_count ? byte_count : 1));
-        g_prng.cap = byte_count ? byte_count : 1;
-    }
+    LOWER_HIP(g_prng.seed.grow(64));
+    LOWER_HIP(g_prng.ctr.grow(1));
+    LOWER_HIP(g_prng.bytes.grow(byte_count ? byte_count : 1));
     up(g_prng.seed, prng->seed, 64);
     up(g_prng.ctr, &prng->counter, 8);
     if (byte_count)
@@ -918,7 +867,7 @@ static void sym_spec_wipe(Lower &L)
     if (!S.h_pte.empty()) explicit_bzero(S.h_pte.data(), S.h_pte.size() * 8);
     if (!S.h_key.empty()) explicit_bzero(S.h_key.data(), S.h_key.size());
     S.h_pte.clear(), S.h_key.clear();
-    if (S.cp && S.d_slab) (void)hipMemsetAsync(S.d_slab, 0, S.slab_bytes, S.cp);
+    if (S.cp && S.d_slab) (void)hipMemsetAsync(S.d_slab, 0, S.d_slab.size(), S.cp);
     // staging rows per prime: a | c0 (the ciphertext: public) | ntt_pte | s_save (NTT(m + e), NTT(s): wiped)
     if (S.h_stage)
         for (size_t pr = 0; pr < np; pr++) explicit_bzero(S.h_stage + (pr * 4 + 2) * n, 2 * n * sizeof(uint32_t));
@@ -932,25 +881,22 @@ static void sym_spec_arm(Lower &L, const Parms *parms, const SE_PRNG *shareable)
     Lower::SymSpec &S = L.sym;
     Context &c        = L.c();
     const size_t n    = L.n;
-    S.armed = S.fetched = false;
-    for (auto &p : S.pre) p = false;
     if (getenv("SE_AMD_LOWER_SPECULATION") && atoi(getenv("SE_AMD_LOWER_SPECULATION")) == 0) return;
     if (parms->nprimes < 1 || parms->nprimes > c.hp.nprimes) return;
     LOWER_HIP(hipSetDevice(c.device));
     if (!S.st)
     {
-        LOWER_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-        LOWER_HIP(hipStreamCreateWithFlags(&S.cp, hipStreamNonBlocking));
-        LOWER_HIP(hipEventCreateWithFlags(&S.ev_sampled, hipEventDisableTiming));
-        for (auto &e : S.ev_kernel) LOWER_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : S.ev_copied) LOWER_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        LOWER_HIP(S.st.create(hipStreamNonBlocking));
+        LOWER_HIP(S.cp.create(hipStreamNonBlocking));
+        LOWER_HIP(S.ev_sampled.create(hipEventDisableTiming));
+        for (auto &e : S.ev_kernel) LOWER_HIP(e.create(hipEventDisableTiming));
+        for (auto &e : S.ev_copied) LOWER_HIP(e.create(hipEventDisableTiming));
         const size_t np = c.hp.nprimes;
-        S.slab_bytes = 8 * n + np * 3 * n * sizeof(uint32_t) + n / 4;
-        LOWER_HIP(hipMalloc((void **)&S.d_slab, S.slab_bytes));
-        S.d_pte = (int64_t *)S.d_slab;
+        LOWER_HIP(S.d_slab.grow(8 * n + np * 3 * n * sizeof(uint32_t) + n / 4));
+        S.d_pte = (int64_t *)S.d_slab.get();
         S.d_out = (uint32_t *)(S.d_slab + 8 * n);
         S.d_key = S.d_slab + 8 * n + np * 3 * n * sizeof(uint32_t);
-        LOWER_HIP(hipHostMalloc((void **)&S.h_stage, np * 4 * n * sizeof(uint32_t), hipHostMallocDefault));
+        LOWER_HIP(S.h_stage.grow(np * 4 * n));
     }
     else
     {
@@ -982,16 +928,9 @@ static void sym_spec_arm(Lower &L, const Parms *parms, const SE_PRNG *shareable)
         total += cnt;
         covered = j + 1;
     }
-    if (total > S.cap)
-    {
-        if (S.d_rows) (void)hipFree(S.d_rows);
-        if (S.d_meta) (void)hipFree(S.d_meta);
-        S.d_rows = nullptr, S.d_meta = nullptr, S.cap = 0;
-        LOWER_HIP(hipMalloc((void **)&S.d_rows, (size_t)total * n * sizeof(uint32_t)));
-        LOWER_HIP(hipMalloc((void **)&S.d_meta, (size_t)total * 88));
-        S.cap      = total;
-    }
-    // carved for THIS plan's `total` (<= cap), so that one upload of total x 88 bytes covers it
+    LOWER_HIP(S.d_rows.grow((size_t)total * n));
+    LOWER_HIP(S.d_meta.grow((size_t)total * 88));
+    // carved for THIS plan's `total` (the buffers may hold more), so that one upload of total x 88 bytes covers it
     S.d_seeds  = S.d_meta;
     S.d_ctr    = (uint64_t *)(S.d_meta + (size_t)total * 64);
     S.d_ctrout = S.d_ctr + total;
@@ -1040,10 +979,14 @@ void ckks_sym_init(const Parms *parms, uint8_t *share_seed_in, uint8_t *seed_in,
     prng_randomize_reset(shareable_prng, share_seed_in);
     prng_randomize_reset(prng, seed_in);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    Lower &L = lower_for_degree(parms->coeff_count);
+    Lower &L          = lower_for_degree(parms->coeff_count);
+    Lower::SymSpec &S = L.sym;
+    // nothing of the previous ciphertext's table survives into this one: an arm that is skipped below leaves the
+    // fast path off (its uploads into S.d_pte would not be ordered behind the wipe the previous chain queued on S.cp)
+    S.armed = S.fetched = false;
+    for (auto &p : S.pre) p = false;
     if (parms->moduli && parms->nprimes <= L.c().hp.nprimes && parms->curr_modulus_idx < parms->nprimes)
         sym_spec_arm(L, parms, shareable_prng);
-    Lower::SymSpec &S = L.sym;
     if (!S.armed)
     {
         sample_add_poly_cbd_generic_inpl_prng_16(conj_vals_int, parms->coeff_count, prng);

@@ -104,7 +104,7 @@ struct se_amd_group
 {
     std::vector<se_amd_ctx *> ctx;
     std::vector<int> device;
-    std::vector<hipStream_t> stream;   // one per member, created on that member's device
+    std::vector<seamd::Stream> stream;   // one per member, created on that member's device
     std::vector<std::unique_ptr<Worker>> worker;   // members 1 .. ndev-1 (member 0 runs on the calling thread)
     std::mutex call;                               // one multi-device call at a time per group
 };
@@ -284,8 +284,8 @@ int se_amd_group_create(se_amd_group **out, size_t degree, size_t nprimes, const
     {
         se_amd_ctx *c = nullptr;
         int rc        = se_amd_create(&c, degree, nprimes, d);
-        hipStream_t st = nullptr;
-        if (rc == SE_SUCCESS && (hipSetDevice(d) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess))
+        seamd::Stream st;
+        if (rc == SE_SUCCESS && (hipSetDevice(d) != hipSuccess || st.create(hipStreamNonBlocking) != hipSuccess))
         {
             seamd::set_last_error("cannot create a stream on device " + std::to_string(d));
             rc = SE_ERR_HIP;
@@ -296,7 +296,7 @@ int se_amd_group_create(se_amd_group **out, size_t degree, size_t nprimes, const
             se_amd_group_destroy(g);
             return rc;
         }
-        g->ctx.push_back(c), g->device.push_back(d), g->stream.push_back(st);
+        g->ctx.push_back(c), g->device.push_back(d), g->stream.push_back(std::move(st));
     }
     // peer access for the gather (every member writes into whichever member is the root); "already
     // enabled" and "same device" are not errors, a pair without a link falls back to staged copies
@@ -320,7 +320,8 @@ void se_amd_group_destroy(se_amd_group *g)
     g->worker.clear();   // joins the member threads
     for (size_t i = 0; i < g->ctx.size(); i++)
     {
-        if (g->stream[i] && hipSetDevice(g->device[i]) == hipSuccess) (void)hipStreamDestroy(g->stream[i]);
+        (void)hipSetDevice(g->device[i]);
+        g->stream[i] = seamd::Stream();
         se_amd_destroy(g->ctx[i]);
     }
     delete g;
