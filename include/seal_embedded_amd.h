@@ -200,6 +200,31 @@ int se_amd_encrypt_asym_device(se_amd_ctx *ctx, const float *d_values, size_t B,
                                const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1,
                                uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
                                void *stream);
+/* ---- key rings: one batch under many keys, chosen per ciphertext ----------------------------------
+ * A context holds at most one secret ring and one public ring of K keys each, independent of the key installed by
+ * se_amd_set_{secret,public}_key.  Host pointers, the layouts se_amd_gen_keys_batch writes: sk [K][n/4] 2-bit packed;
+ * pk0, pk1 [K][np][n] uint32 in NTT form.  Keys are validated as the single-key setters do (2-bit code 3, or a pk
+ * coefficient >= q_j, is refused); installing replaces the ring of that kind after the calls in flight finish.
+ * Device memory: 2 np n 4 bytes per secret key, twice that per public key. */
+int se_amd_set_secret_keyring(se_amd_ctx *ctx, size_t K, const uint8_t *sk_packed);
+int se_amd_set_public_keyring(se_amd_ctx *ctx, size_t K, const uint32_t *pk0, const uint32_t *pk1);
+/* Keyed entries: ciphertext b is encrypted under ring key d_key_idx[b] (d_key_idx: [B] uint32 on the device),
+ * bit-identical to the unkeyed entry with that key installed.  Other arguments as in the unkeyed entries; symmetric:
+ * d_c1 may be NULL, which gives the seed-compressed form of se_amd_encrypt_sym_seeded_device.  SE_ERR_NO_KEY without
+ * a ring of the kind.  A record whose index is >= K gets status 2 and an all-zero c0 (public key: and c1); status 2
+ * takes precedence over 0 (encode overflow). */
+int se_amd_encrypt_sym_keyed_device(se_amd_ctx *ctx, const float *d_values, size_t B, const uint32_t *d_key_idx,
+                                    const uint8_t *d_share_seeds, const uint8_t *d_seeds, uint32_t *d_c0,
+                                    uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
+                                    void *stream);
+int se_amd_encrypt_asym_keyed_device(se_amd_ctx *ctx, const float *d_values, size_t B, const uint32_t *d_key_idx,
+                                     const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte,
+                                     int64_t *d_pte, uint8_t *d_status, void *stream);
+/* se_amd_decrypt_decode_device with ciphertext b decrypted under secret-ring key d_key_idx[b]; the outputs of a
+ * record whose index is >= K are zero. */
+int se_amd_decrypt_decode_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                       const uint32_t *d_key_idx, size_t prime, uint32_t *d_dec_ntt,
+                                       uint32_t *d_pt, float *d_values, void *stream);
 /* BASELINE config 5: encode + RNS reduce + NTT only; out [B][np][n] = NTT(m mod q_j). */
 int se_amd_encode_ntt_device(se_amd_ctx *ctx, const float *d_values, size_t B, uint32_t *d_out,
                              int64_t *d_pte, uint8_t *d_status, void *stream);

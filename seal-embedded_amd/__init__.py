@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_group_partition", "se_amd_group_set_secret_key", "se_amd_group_set_public_key", "se_amd_group_reserve",
     "se_amd_encrypt_sym_multi_device", "se_amd_encrypt_asym_multi_device", "se_amd_encode_ntt_multi_device",
     "se_amd_set_reject_list_capacity", "se_amd_set_speculation_capacity", "se_amd_set_host_chunk", "se_amd_host_tables", "se_amd_ifft_table_sha256", "se_amd_reserve", "se_amd_set_debug_flags", "se_amd_set_pipeline", "se_amd_set_asym_chunks", "se_amd_last_error", "se_amd_version",
+    "se_amd_set_secret_keyring", "se_amd_set_public_keyring", "se_amd_encrypt_sym_keyed_device",
+    "se_amd_encrypt_asym_keyed_device", "se_amd_decrypt_decode_keyed_device",
 )
 
 
@@ -129,6 +131,11 @@ def lib():
     L.se_amd_set_debug_flags.argtypes = [vp, u32]
     L.se_amd_set_pipeline.argtypes = [vp, i32, i32]
     L.se_amd_set_asym_chunks.argtypes = [vp, sz]
+    L.se_amd_set_secret_keyring.argtypes = [vp, sz, vp]
+    L.se_amd_set_public_keyring.argtypes = [vp, sz, vp, vp]
+    L.se_amd_encrypt_sym_keyed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.se_amd_encrypt_asym_keyed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.se_amd_decrypt_decode_keyed_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -326,6 +333,22 @@ class Context:
                                             _ptr(pk0), _ptr(pk1)), "se_amd_gen_keys_batch")
         return sk, pk0, pk1
 
+    # ---- key rings (K keys; the keyed entries choose one per ciphertext)
+    def set_secret_keyring(self, sk_packed):
+        """sk_packed [K][n/4] uint8 (as gen_keys_batch returns it)."""
+        import numpy as np
+        sk = np.ascontiguousarray(sk_packed, dtype=np.uint8).reshape(-1, self.n // 4)
+        _check(self.L.se_amd_set_secret_keyring(self.h, sk.shape[0], _ptr(sk)), "se_amd_set_secret_keyring")
+
+    def set_public_keyring(self, pk0, pk1):
+        """pk0, pk1 [K][np][n] uint32 in NTT form (as gen_keys_batch returns them)."""
+        import numpy as np
+        pk0 = np.ascontiguousarray(pk0, dtype=np.uint32).reshape(-1, self.np, self.n)
+        pk1 = np.ascontiguousarray(pk1, dtype=np.uint32).reshape(-1, self.np, self.n)
+        assert pk0.shape == pk1.shape
+        _check(self.L.se_amd_set_public_keyring(self.h, pk0.shape[0], _ptr(pk0), _ptr(pk1)),
+               "se_amd_set_public_keyring")
+
     def load_keys_from_dir(self, path, want_pk=False):
         _check(self.L.se_amd_load_keys_from_dir(self.h, path.encode(), 1 if want_pk else 0),
                "se_amd_load_keys_from_dir")
@@ -354,6 +377,23 @@ class Context:
                                                  _ptr(c1), _ptr(ntt_pte), _ptr(pte), _ptr(status),
                                                  _stream_ptr()), "se_amd_encrypt_asym_device")
 
+    def encrypt_sym_keyed(self, values, key_idx, share_seeds, seeds, c0, c1=None, ntt_pte=None, pte=None,
+                          status=None):
+        """Ciphertext b under secret-ring key key_idx[b] (int32/uint32 device tensor [B]); c1=None gives the
+        seed-compressed form.  Status 2: key_idx[b] >= K (c0 zero)."""
+        B = values.shape[0]
+        _check(self.L.se_amd_encrypt_sym_keyed_device(self.h, _ptr(values), B, _ptr(key_idx), _ptr(share_seeds),
+                                                      _ptr(seeds), _ptr(c0), _ptr(c1), _ptr(ntt_pte), _ptr(pte),
+                                                      _ptr(status), _stream_ptr()),
+               "se_amd_encrypt_sym_keyed_device")
+
+    def encrypt_asym_keyed(self, values, key_idx, seeds, c0, c1, ntt_pte=None, pte=None, status=None):
+        """Ciphertext b under public-ring key key_idx[b]; status 2: key_idx[b] >= K (c0, c1 zero)."""
+        B = values.shape[0]
+        _check(self.L.se_amd_encrypt_asym_keyed_device(self.h, _ptr(values), B, _ptr(key_idx), _ptr(seeds),
+                                                       _ptr(c0), _ptr(c1), _ptr(ntt_pte), _ptr(pte), _ptr(status),
+                                                       _stream_ptr()), "se_amd_encrypt_asym_keyed_device")
+
     def encode_ntt(self, values, out, pte=None, status=None):
         B = values.shape[0]
         _check(self.L.se_amd_encode_ntt_device(self.h, _ptr(values), B, _ptr(out), _ptr(pte),
@@ -380,6 +420,12 @@ class Context:
         _check(self.L.se_amd_decrypt_decode_device(self.h, _ptr(c0), _ptr(c1), B, prime,
                                                    _ptr(dec_ntt), _ptr(pt), _ptr(values),
                                                    _stream_ptr()), "se_amd_decrypt_decode_device")
+
+    def decrypt_decode_keyed(self, c0, c1, key_idx, prime, dec_ntt=None, pt=None, values=None):
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt_decode_keyed_device(self.h, _ptr(c0), _ptr(c1), B, _ptr(key_idx), prime,
+                                                         _ptr(dec_ntt), _ptr(pt), _ptr(values), _stream_ptr()),
+               "se_amd_decrypt_decode_keyed_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

@@ -79,6 +79,24 @@ __device__ __forceinline__ int opaque_index(int t)
     return t;
 }
 
+// Key rings (kernel_args.h, KeyRing): the keyed kernels read the key rows of record b from key idx[b] of the ring.  b is
+// workgroup-uniform (one plaintext per workgroup, or per half of the pair form), so the key's offset is one scalar word
+// (readfirstlane of the index) times the key stride: SGPRs only, and the per-prime offsets (kb) are the single key's.
+__device__ __forceinline__ size_t key_base(const KeyRing &R, size_t b)
+{
+    return (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)R.idx[b]) * R.stride;
+}
+
+// the tables with the key rows of the ring key at word offset kb
+__device__ __forceinline__ DevTables with_key(const DevTables &T, const KeyRing &R, size_t kb)
+{
+    DevTables Tk = T;
+    Tk.s_hat     = R.k0 + kb;
+    Tk.pk0       = R.k0 + kb;
+    Tk.pk1       = R.k1 + kb;
+    return Tk;
+}
+
 __device__ __forceinline__ void load_quads(uint32_t (&v)[16], const uint32_t *poly, int t)
 {
     const uint32_t *base = poly + quad_index(t, 0);
@@ -579,10 +597,13 @@ __device__ __forceinline__ void encrypt_tail(const DevParams &P, const DevTables
     }
 }
 
-template <int LOGN, int MODE, bool GENERAL>
+// KEYED: the key rows come from the ring (key_base above); everything else is the unkeyed form
+template <int LOGN, int MODE, bool GENERAL, bool KEYED = false>
 __device__ __forceinline__ void encrypt_one(const DevParams &P, const DevTables &T, const EncArgs &A,
-                                            const size_t b, unsigned char *smem)
+                                            const KeyRing &R, const size_t b, unsigned char *smem)
 {
+    size_t kb = 0;
+    if constexpr (KEYED) kb = key_base(R, b);
     const int t = thread_index<GENERAL>();
     using MT = typename std::conditional<GENERAL, int64_t, int32_t>::type;
     MT m[16];
@@ -597,7 +618,10 @@ __device__ __forceinline__ void encrypt_one(const DevParams &P, const DevTables 
             return;
         }
     }
-    encrypt_tail<LOGN, MODE, GENERAL, false>(P, T, A, b, smem, m, small);
+    if constexpr (KEYED)
+        encrypt_tail<LOGN, MODE, GENERAL, false>(P, with_key(T, R, kb), A, b, smem, m, small);
+    else
+        encrypt_tail<LOGN, MODE, GENERAL, false>(P, T, A, b, smem, m, small);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -716,12 +740,14 @@ __device__ __forceinline__ int encode_pair_half(const DevParams &P, const DevTab
     return __ockl_wgred_or_i32(flags);
 }
 
-template <int LOGN, int MODE>
+template <int LOGN, int MODE, bool KEYED = false>
 __device__ __forceinline__ void encrypt_pair(const DevParams &P, const DevTables &T, const EncArgs &A,
-                                             const size_t bA, const bool haveB, unsigned char *smem)
+                                             const KeyRing &R, const size_t bA, const bool haveB, unsigned char *smem)
 {
     const int t     = threadIdx.x;
     const size_t bB = haveB ? bA + 1 : bA;   // an odd batch ends with a workgroup that carries its plaintext twice
+    size_t kbA = 0, kbB = 0;                 // keyed: the two plaintexts' key offsets (SGPRs)
+    if constexpr (KEYED) kbA = key_base(R, bA), kbB = key_base(R, bB);
     int32_t m[16], mo[16];                   // A's coefficients / B's
     const int flags = encode_pair_half<LOGN>(P, T, A.values, bA, bB, smem, m, mo);
     // Per plaintext: declined (general kernel), or coefficients valid -- after an exact redo when one of them sat in the
@@ -753,7 +779,13 @@ __device__ __forceinline__ void encrypt_pair(const DevParams &P, const DevTables
 #pragma nounroll
     for (int p = 0; p < 2; p++)
     {
-        if (run & (1 << p)) encrypt_tail<LOGN, MODE, false, true>(P, T, A, p ? bB : bA, smem, m, true);
+        if (run & (1 << p))
+        {
+            if constexpr (KEYED)
+                encrypt_tail<LOGN, MODE, false, true>(P, with_key(T, R, p ? kbB : kbA), A, p ? bB : bA, smem, m, true);
+            else
+                encrypt_tail<LOGN, MODE, false, true>(P, T, A, p ? bB : bA, smem, m, true);
+        }
         if (p == 0 && (run & 2))
         {
             __syncthreads();
@@ -780,15 +812,34 @@ constexpr int enc_blocks()
     return GENERAL ? 3 : 4;
 }
 
+template <int LOGN, int MODE, bool KEYED>
+__device__ __forceinline__ void encode_encrypt_fast(const DevParams &P, const DevTables &T, const EncArgs &A,
+                                                    const KeyRing &R, unsigned char *smem)
+{
+    if constexpr (enc_pairs<LOGN, MODE>())
+        encrypt_pair<LOGN, MODE, KEYED>(P, T, A, R, (size_t)2 * blockIdx.x, (size_t)2 * blockIdx.x + 1 < A.count, smem);
+    else
+        encrypt_one<LOGN, MODE, false, KEYED>(P, T, A, R, blockIdx.x, smem);
+}
+
+template <int LOGN, int MODE, bool KEYED>
+__device__ __forceinline__ void encode_encrypt_general(const DevParams &P, const DevTables &T, const EncArgs &A,
+                                                       const KeyRing &R, unsigned char *smem)
+{
+    const uint32_t count = A.general[0];
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x)
+    {
+        encrypt_one<LOGN, MODE, true, KEYED>(P, T, A, R, A.general[1 + i], smem);
+        __syncthreads();
+    }
+}
+
 template <int LOGN, int MODE>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS, (enc_blocks<LOGN, MODE, false>()))
 void k_encode_encrypt(DevParams P, DevTables T, EncArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if constexpr (enc_pairs<LOGN, MODE>())
-        encrypt_pair<LOGN, MODE>(P, T, A, (size_t)2 * blockIdx.x, (size_t)2 * blockIdx.x + 1 < A.count, smem);
-    else
-        encrypt_one<LOGN, MODE, false>(P, T, A, blockIdx.x, smem);
+    encode_encrypt_fast<LOGN, MODE, false>(P, T, A, KeyRing{}, smem);
 }
 
 template <int LOGN, int MODE>
@@ -799,9 +850,26 @@ void k_encode_encrypt_general(DevParams P, DevTables T, EncArgs A)
     const uint32_t count = A.general[0];
     for (uint32_t i = blockIdx.x; i < count; i += gridDim.x)
     {
-        encrypt_one<LOGN, MODE, true>(P, T, A, A.general[1 + i], smem);
+        encrypt_one<LOGN, MODE, true>(P, T, A, KeyRing{}, A.general[1 + i], smem);
         __syncthreads();
     }
+}
+
+// keyed twins (symmetric / public-key modes): the same bodies, key rows of record b from ring key R.idx[b]
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS, (enc_blocks<LOGN, MODE, false>()))
+void k_encode_encrypt_keyed(DevParams P, DevTables T, EncArgs A, KeyRing R)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    encode_encrypt_fast<LOGN, MODE, true>(P, T, A, R, smem);
+}
+
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS, (enc_blocks<LOGN, MODE, true>()))
+void k_encode_encrypt_general_keyed(DevParams P, DevTables T, EncArgs A, KeyRing R)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    encode_encrypt_general<LOGN, MODE, true>(P, T, A, R, smem);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -898,21 +966,22 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_encode_rns_general
 
 // n = 16384: at most 96 VGPRs (5 waves per SIMD instead of the 4 the 1024-thread workgroup needs) so
 // that a workgroup fits beside the uniform sampler's chain waves (128 VGPRs, one wave per SIMD).
-template <int LOGN, int MODE>
-__global__ __launch_bounds__(XformGeom<LOGN>::THREADS)
-__attribute__((amdgpu_waves_per_eu(LOGN == 14 ? 5 : (XformGeom<LOGN>::THREADS + 255) / 256))) void k_ntt_fuse(DevParams P, DevTables T, EncArgs A,
-                                                                    int j)
+// KEYED: NTT(s) of ring key R.idx[b] (key_base above) instead of the installed key
+template <int LOGN, int MODE, bool KEYED>
+__device__ __forceinline__ void ntt_fuse_body(const DevParams &P, const DevTables &T, const EncArgs &A,
+                                              const KeyRing &R, int j, unsigned char *smem)
 {
     using G            = XformGeom<LOGN>;
     constexpr int N    = G::N;
     constexpr int CTOP = LOGN - 4;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *lds32  = reinterpret_cast<uint32_t *>(smem);
     const int t      = threadIdx.x;
     const size_t b   = blockIdx.x;
     const int np     = P.nprimes;
     const uint32_t q = P.q[j], two_q = q << 1;
     uint32_t *poly   = A.c0 + (b * np + j) * N;
+    const uint32_t *s_hat = T.s_hat;
+    if constexpr (KEYED) s_hat = R.k0 + key_base(R, b);
 
     // residues of this prime, or the compact int32 plaintext from the last prime's row (k_encode_rns):
     // m + 2 q_j is a representative in (0, 4q) the NTT accepts (modarith.cuh, reduce_signed16)
@@ -931,10 +1000,10 @@ __attribute__((amdgpu_waves_per_eu(LOGN == 14 ? 5 : (XformGeom<LOGN>::THREADS + 
     if constexpr (MODE == kModeSym)
     {
         load_quads(a, A.c1 + (b * np + j) * N, t);
-        if constexpr (!LATE_KEY) load_quads_pairs(w, wp, T.s_hat + (size_t)2 * N * j, t);
+        if constexpr (!LATE_KEY) load_quads_pairs(w, wp, s_hat + (size_t)2 * N * j, t);
     }
     ntt_tiles<LOGN>(x, T.ntt_rw + 2 * xform_table_len(N) * j, q, lds32, t);
-    if constexpr (MODE == kModeSym && LATE_KEY) load_quads_pairs(w, wp, T.s_hat + (size_t)2 * N * j, t);
+    if constexpr (MODE == kModeSym && LATE_KEY) load_quads_pairs(w, wp, s_hat + (size_t)2 * N * j, t);
     // n <= 4096: the symmetric epilogue takes the LAZY transform output and canonicalises once (modarith.cuh,
     // sub_mul_canon); at n >= 8192 that form costs registers the kernel does not have (96-VGPR cap at n = 16384:
     // 36 B of spills) and the separate canonicalisation stays
@@ -971,6 +1040,24 @@ __attribute__((amdgpu_waves_per_eu(LOGN == 14 ? 5 : (XformGeom<LOGN>::THREADS + 
     {
         store_quads(poly, x, t);
     }
+}
+
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS)
+__attribute__((amdgpu_waves_per_eu(LOGN == 14 ? 5 : (XformGeom<LOGN>::THREADS + 255) / 256))) void k_ntt_fuse(DevParams P, DevTables T, EncArgs A,
+                                                                    int j)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ntt_fuse_body<LOGN, MODE, false>(P, T, A, KeyRing{}, j, smem);
+}
+
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS)
+__attribute__((amdgpu_waves_per_eu(LOGN == 14 ? 5 : (XformGeom<LOGN>::THREADS + 255) / 256))) void k_ntt_fuse_keyed(DevParams P, DevTables T,
+                                                                    EncArgs A, KeyRing R, int j)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ntt_fuse_body<LOGN, MODE, true>(P, T, A, R, j, smem);
 }
 
 // Batched stand-alone forward NTT (ntt_inpl, ntt.c:168-189) of `count` polynomials mod q_j,
@@ -1043,14 +1130,13 @@ struct VerifyArgs
     int j;                // prime
 };
 
-template <int LOGN>
-__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_decode(DevParams P, DevTables T,
-                                                                          VerifyArgs A)
+template <int LOGN, bool KEYED>
+__device__ __forceinline__ void decrypt_decode_body(const DevParams &P, const DevTables &T, const VerifyArgs &A,
+                                                    const KeyRing &R, unsigned char *smem)
 {
     using G            = XformGeom<LOGN>;
     constexpr int N    = G::N;
     constexpr int CTOP = LOGN - 4;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *lds32  = reinterpret_cast<uint32_t *>(smem);
     double *plane    = reinterpret_cast<double *>(smem);
     const int t      = threadIdx.x;
@@ -1065,7 +1151,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_decode(Dev
     {
         uint32_t a[16], w[16], wp[16];
         load16(a, A.c1 + rec);
-        load16_pairs(w, wp, T.s_hat, (size_t)j * N + 16 * t);
+        load16_pairs(w, wp, KEYED ? R.k0 + key_base(R, b) : T.s_hat, (size_t)j * N + 16 * t);
 #pragma unroll
         for (int e = 0; e < 16; e++)
             x[e] = csub(csub(mul_shoup_lazy(a[e], w[e], wp[e], q), q) + x[e], q);
@@ -1108,11 +1194,36 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_decode(Dev
 }
 
 template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_decode(DevParams P, DevTables T,
+                                                                          VerifyArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    decrypt_decode_body<LOGN, false>(P, T, A, KeyRing{}, smem);
+}
+
+// keyed twin: ciphertext b decrypted under ring key R.idx[b]
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_decode_keyed(DevParams P, DevTables T,
+                                                                                VerifyArgs A, KeyRing R)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    decrypt_decode_body<LOGN, true>(P, T, A, R, smem);
+}
+
+template <int LOGN>
 static hipError_t launch_vfy(const DevParams &P, const DevTables &T, const VerifyArgs &A, size_t B,
-                             hipStream_t st)
+                             hipStream_t st, const KeyRing *ring)
 {
     using G      = XformGeom<LOGN>;
     size_t shmem = (size_t)G::SLOTS * sizeof(double);
+    if (ring)
+    {
+        (void)hipFuncSetAttribute((const void *)k_decrypt_decode_keyed<LOGN>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        hipLaunchKernelGGL((k_decrypt_decode_keyed<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, A,
+                           *ring);
+        return hipGetLastError();
+    }
     (void)hipFuncSetAttribute((const void *)k_decrypt_decode<LOGN>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     hipLaunchKernelGGL((k_decrypt_decode<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, A);
@@ -1121,17 +1232,17 @@ static hipError_t launch_vfy(const DevParams &P, const DevTables &T, const Verif
 
 hipError_t launch_decrypt_decode(const DevParams &P, const DevTables &T, const uint32_t *c0,
                                  const uint32_t *c1, uint32_t in_primes, int j, uint32_t *dec_ntt,
-                                 uint32_t *pt, float *values, size_t B, hipStream_t st)
+                                 uint32_t *pt, float *values, size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
     VerifyArgs A{c0, c1, dec_ntt, pt, values, in_primes, j};
     switch (P.logn)
     {
-        case 10: return launch_vfy<10>(P, T, A, B, st);
-        case 11: return launch_vfy<11>(P, T, A, B, st);
-        case 12: return launch_vfy<12>(P, T, A, B, st);
-        case 13: return launch_vfy<13>(P, T, A, B, st);
-        case 14: return launch_vfy<14>(P, T, A, B, st);
+        case 10: return launch_vfy<10>(P, T, A, B, st, ring);
+        case 11: return launch_vfy<11>(P, T, A, B, st, ring);
+        case 12: return launch_vfy<12>(P, T, A, B, st, ring);
+        case 13: return launch_vfy<13>(P, T, A, B, st, ring);
+        case 14: return launch_vfy<14>(P, T, A, B, st, ring);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1159,11 +1270,143 @@ hipError_t launch_reduce_small(const DevParams &P, const int8_t *e, uint32_t *ou
 }
 
 // ------------------------------------------------------------------------------------------
+// Key rings (se_context.cpp, set_*_keyring and the keyed entries)
+// ------------------------------------------------------------------------------------------
+// Prime j of K secret keys at once: workgroup k expands packed key k (2-bit codes, sample.c:98-129: 0 -> q-1, 1 -> 0,
+// 2 -> 1; the host has refused code 3), forward NTT (as k_ntt_polys), (value, Shoup) pairs into ring key k's row j.
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ring_secret_ntt(DevParams P, DevTables T, int j,
+                                                                           const uint8_t *packed, uint32_t *ring)
+{
+    using G            = XformGeom<LOGN>;
+    constexpr int N    = G::N;
+    constexpr int CTOP = LOGN - 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds32  = reinterpret_cast<uint32_t *>(smem);
+    const int t      = threadIdx.x;
+    const size_t k   = blockIdx.x;
+    const uint8_t *sk = packed + k * (N / 4);
+    const uint32_t q = P.q[j], two_q = q << 1;
+    uint32_t x[16];
+#pragma unroll
+    for (int e = 0; e < 16; e++)
+    {
+        const uint32_t i    = (uint32_t)(e << CTOP) + (uint32_t)t;
+        const uint32_t code = (sk[i >> 2] >> (6 - 2 * (i & 3))) & 3u;
+        x[e]                = code + (code == 0 ? q : 0u) - 1u;
+    }
+    ntt_tiles<LOGN>(x, T.ntt_rw + 2 * xform_table_len(N) * j, q, lds32, t);
+    uint32_t *po = ring + ((k * P.nprimes + j) * N + 16 * t) * 2;
+#pragma unroll
+    for (int e = 0; e < 16; e++)
+    {
+        const uint32_t v = canon4(x[e], q, two_q);
+        po[2 * e]        = v;
+        po[2 * e + 1]    = (uint32_t)((((uint64_t)v) << 32) / q);
+    }
+}
+
+// k_make_pairs over K whole public-key slabs [K][np][n]: the prime of word i is (i / n) mod np
+__global__ void k_ring_pairs(DevParams P, const uint32_t *vals, uint32_t *pairs, size_t total)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    {
+        const uint32_t q = P.q[(i / P.n) % P.nprimes];
+        const uint32_t v = vals[i];
+        pairs[2 * i]     = v;
+        pairs[2 * i + 1] = (uint32_t)((((uint64_t)v) << 32) / q);
+    }
+}
+
+// The keyed kernels read only the clamped copy: no index the caller passes can form an address outside the ring.
+__global__ void k_key_sanitize(const uint32_t *raw, uint32_t *idx, uint32_t *bad, uint32_t K, size_t B)
+{
+    const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const uint32_t k = raw[b];
+    idx[b]           = k < K ? k : K - 1;
+    if (k >= K) bad[1 + atomicAdd(bad, 1u)] = (uint32_t)b;
+}
+
+// records with an out-of-range index (normally none: the workgroups read a zero count and leave)
+__global__ void k_key_reject(KeyRejectArgs A)
+{
+    const uint32_t count = A.bad[0];
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x)
+    {
+        const size_t b = A.bad[1 + i];
+        if (A.status && threadIdx.x == 0) A.status[b] = 2;
+        for (int r = 0; r < 3; r++)
+        {
+            if (!A.rows[r]) continue;
+            uint32_t *row = A.rows[r] + b * A.words[r];
+            for (size_t w = threadIdx.x; w < A.words[r]; w += blockDim.x) row[w] = 0;
+        }
+    }
+}
+
+template <int LOGN>
+static hipError_t launch_ring_sk(const DevParams &P, const DevTables &T, int j, const uint8_t *packed,
+                                 uint32_t *ring, size_t K, hipStream_t st)
+{
+    using G      = XformGeom<LOGN>;
+    size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
+    (void)hipFuncSetAttribute((const void *)k_ring_secret_ntt<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)shmem);
+    hipLaunchKernelGGL((k_ring_secret_ntt<LOGN>), dim3((unsigned)K), dim3(G::THREADS), shmem, st, P, T, j, packed,
+                       ring);
+    return hipGetLastError();
+}
+
+hipError_t launch_ring_secret_ntt(const DevParams &P, const DevTables &T, int j, const uint8_t *packed, uint32_t *ring,
+                                  size_t K, hipStream_t st)
+{
+    if (K == 0) return hipSuccess;
+    switch (P.logn)
+    {
+        case 10: return launch_ring_sk<10>(P, T, j, packed, ring, K, st);
+        case 11: return launch_ring_sk<11>(P, T, j, packed, ring, K, st);
+        case 12: return launch_ring_sk<12>(P, T, j, packed, ring, K, st);
+        case 13: return launch_ring_sk<13>(P, T, j, packed, ring, K, st);
+        case 14: return launch_ring_sk<14>(P, T, j, packed, ring, K, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_ring_pairs(const DevParams &P, const uint32_t *vals, uint32_t *pairs, size_t K, hipStream_t st)
+{
+    const size_t total = K * P.nprimes * P.n;
+    if (total == 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)64 * (P.num_cus ? P.num_cus : 256u));
+    hipLaunchKernelGGL(k_ring_pairs, dim3(grid), dim3(256), 0, st, P, vals, pairs, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_key_sanitize(const uint32_t *raw, uint32_t *idx, uint32_t *bad, size_t K, size_t B, hipStream_t st)
+{
+    if (B == 0) return hipSuccess;
+    if (K == 0 || K > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_key_sanitize, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, raw, idx, bad,
+                       (uint32_t)K, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_key_reject(const DevParams &P, const KeyRejectArgs &A, size_t B, hipStream_t st)
+{
+    if (B == 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)4 * (P.num_cus ? P.num_cus : 256u));
+    hipLaunchKernelGGL(k_key_reject, dim3(grid), dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers (called from se_context.cpp)
 // ------------------------------------------------------------------------------------------
 template <int LOGN, int MODE>
 static hipError_t launch_enc_mode(const DevParams &P, const DevTables &T, const EncArgs &A, size_t B,
-                                  hipStream_t st)
+                                  hipStream_t st, const KeyRing *ring)
 {
     using G             = XformGeom<LOGN>;
     const size_t planes = (size_t)G::SLOTS * sizeof(double);   // the IFFT's two f64 half-planes
@@ -1185,15 +1428,32 @@ static hipError_t launch_enc_mode(const DevParams &P, const DevTables &T, const 
     Af.count   = B;
     if (enc_pairs<LOGN, MODE>()) shmem_fast = std::max(shmem_fast, (kPairParkWords + (size_t)G::N) * sizeof(uint32_t));
     const unsigned grid_fast = (unsigned)(enc_pairs<LOGN, MODE>() ? (B + 1) / 2 : B);   // two plaintexts per workgroup
+    // the plaintexts the fast form declined (normally none: the workgroups read a zero count and leave)
+    const unsigned cus  = P.num_cus ? P.num_cus : 256u;
+    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)4 * cus);
+    if constexpr (MODE != kModeEncodeOnly)
+    {
+        if (ring)
+        {
+            (void)hipFuncSetAttribute((const void *)k_encode_encrypt_keyed<LOGN, MODE>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_fast);
+            hipLaunchKernelGGL((k_encode_encrypt_keyed<LOGN, MODE>), dim3(grid_fast), dim3(G::THREADS), shmem_fast, st,
+                               P, T, Af, *ring);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            (void)hipFuncSetAttribute((const void *)k_encode_encrypt_general_keyed<LOGN, MODE>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_gen);
+            hipLaunchKernelGGL((k_encode_encrypt_general_keyed<LOGN, MODE>), dim3(grid), dim3(G::THREADS), shmem_gen,
+                               st, P, T, A, *ring);
+            return hipGetLastError();
+        }
+    }
     (void)hipFuncSetAttribute((const void *)k_encode_encrypt<LOGN, MODE>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_fast);
     hipLaunchKernelGGL((k_encode_encrypt<LOGN, MODE>), dim3(grid_fast), dim3(G::THREADS), shmem_fast, st, P, T,
                        Af);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // the plaintexts the fast form declined (normally none: the workgroups read a zero count and leave)
-    const unsigned cus  = P.num_cus ? P.num_cus : 256u;
-    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)4 * cus);
     (void)hipFuncSetAttribute((const void *)k_encode_encrypt_general<LOGN, MODE>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_gen);
     hipLaunchKernelGGL((k_encode_encrypt_general<LOGN, MODE>), dim3(grid), dim3(G::THREADS), shmem_gen, st, P,
@@ -1203,28 +1463,30 @@ static hipError_t launch_enc_mode(const DevParams &P, const DevTables &T, const 
 
 template <int LOGN>
 static hipError_t launch_enc(const DevParams &P, const DevTables &T, const EncArgs &A, int mode,
-                             size_t B, hipStream_t st)
+                             size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (!A.general) return hipErrorInvalidValue;   // the context's list of declined plaintexts
     switch (mode)
     {
-        case kModeSym: return launch_enc_mode<LOGN, kModeSym>(P, T, A, B, st);
-        case kModeAsym: return launch_enc_mode<LOGN, kModeAsym>(P, T, A, B, st);
-        default: return launch_enc_mode<LOGN, kModeEncodeOnly>(P, T, A, B, st);
+        case kModeSym: return launch_enc_mode<LOGN, kModeSym>(P, T, A, B, st, ring);
+        case kModeAsym: return launch_enc_mode<LOGN, kModeAsym>(P, T, A, B, st, ring);
+        default:
+            if (ring) return hipErrorInvalidValue;   // encode-only reads no key
+            return launch_enc_mode<LOGN, kModeEncodeOnly>(P, T, A, B, st, nullptr);
     }
 }
 
 hipError_t launch_encode_encrypt(const DevParams &P, const DevTables &T, const EncArgs &A, int mode,
-                                 size_t B, hipStream_t st)
+                                 size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
     switch (P.logn)
     {
-        case 10: return launch_enc<10>(P, T, A, mode, B, st);
-        case 11: return launch_enc<11>(P, T, A, mode, B, st);
-        case 12: return launch_enc<12>(P, T, A, mode, B, st);
-        case 13: return launch_enc<13>(P, T, A, mode, B, st);
-        case 14: return launch_enc<14>(P, T, A, mode, B, st);
+        case 10: return launch_enc<10>(P, T, A, mode, B, st, ring);
+        case 11: return launch_enc<11>(P, T, A, mode, B, st, ring);
+        case 12: return launch_enc<12>(P, T, A, mode, B, st, ring);
+        case 13: return launch_enc<13>(P, T, A, mode, B, st, ring);
+        case 14: return launch_enc<14>(P, T, A, mode, B, st, ring);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1276,12 +1538,19 @@ hipError_t launch_encode_rns(const DevParams &P, const DevTables &T, const EncAr
 
 template <int LOGN>
 static hipError_t launch_nf(const DevParams &P, const DevTables &T, const EncArgs &A, int mode, int j,
-                            size_t B, hipStream_t st)
+                            size_t B, hipStream_t st, const KeyRing *ring)
 {
     using G      = XformGeom<LOGN>;
     size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
     dim3 grid((unsigned)B), block(G::THREADS);
-    if (mode == kModeSym)
+    if (ring)
+    {
+        if (mode != kModeSym) return hipErrorInvalidValue;   // only the symmetric epilogue reads a key
+        (void)hipFuncSetAttribute((const void *)k_ntt_fuse_keyed<LOGN, kModeSym>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        hipLaunchKernelGGL((k_ntt_fuse_keyed<LOGN, kModeSym>), grid, block, shmem, st, P, T, A, *ring, j);
+    }
+    else if (mode == kModeSym)
     {
         (void)hipFuncSetAttribute((const void *)k_ntt_fuse<LOGN, kModeSym>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
@@ -1297,16 +1566,16 @@ static hipError_t launch_nf(const DevParams &P, const DevTables &T, const EncArg
 }
 
 hipError_t launch_ntt_fuse(const DevParams &P, const DevTables &T, const EncArgs &A, int mode, int j,
-                           size_t B, hipStream_t st)
+                           size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
     switch (P.logn)
     {
-        case 10: return launch_nf<10>(P, T, A, mode, j, B, st);
-        case 11: return launch_nf<11>(P, T, A, mode, j, B, st);
-        case 12: return launch_nf<12>(P, T, A, mode, j, B, st);
-        case 13: return launch_nf<13>(P, T, A, mode, j, B, st);
-        case 14: return launch_nf<14>(P, T, A, mode, j, B, st);
+        case 10: return launch_nf<10>(P, T, A, mode, j, B, st, ring);
+        case 11: return launch_nf<11>(P, T, A, mode, j, B, st, ring);
+        case 12: return launch_nf<12>(P, T, A, mode, j, B, st, ring);
+        case 13: return launch_nf<13>(P, T, A, mode, j, B, st, ring);
+        case 14: return launch_nf<14>(P, T, A, mode, j, B, st, ring);
         default: return hipErrorInvalidValue;
     }
 }

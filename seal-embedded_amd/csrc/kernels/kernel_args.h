@@ -84,15 +84,46 @@ struct TernaryArgs
     uint32_t debug_flags;    // 32 = always the lane-per-ciphertext kernel (tests)
 };
 
+// Key ring of the keyed entries (se_context.h, Context::d_ring_*): K keys, each in the layout of the installed key
+// (DevTables::s_hat / pk0 / pk1: [np][n][2] (value, Shoup)), back to back.  Handed only to the *_keyed kernels, which
+// read record b's key at k0 / k1 + idx[b] * stride; the per-prime offset inside a key is the single key's.
+struct KeyRing
+{
+    const uint32_t *k0;   // symmetric / decrypt: NTT(s) pairs; public key: pk0 pairs
+    const uint32_t *k1;   // public key: pk1 pairs (else = k0)
+    const uint32_t *idx;  // [B] key of each record, already clamped below K (Context::key_prologue)
+    size_t stride;        // words per key: 2 np n
+};
+
+// ring != NULL: the keyed twins of the kernels (k_*_keyed), record b under key ring->idx[b]; the EncArgs /
+// VerifyArgs of the launch are the unkeyed ones
 hipError_t launch_encode_encrypt(const DevParams &, const DevTables &, const EncArgs &, int mode,
-                                 size_t B, hipStream_t);
+                                 size_t B, hipStream_t, const KeyRing *ring = nullptr);
 hipError_t launch_encode_rns(const DevParams &, const DevTables &, const EncArgs &, bool add_err,
                              size_t B, hipStream_t);
 hipError_t launch_ntt_fuse(const DevParams &, const DevTables &, const EncArgs &, int mode, int j,
-                           size_t B, hipStream_t);
+                           size_t B, hipStream_t, const KeyRing *ring = nullptr);
 hipError_t launch_decrypt_decode(const DevParams &, const DevTables &, const uint32_t *c0,
                                  const uint32_t *c1, uint32_t in_primes, int j, uint32_t *dec_ntt,
-                                 uint32_t *pt, float *values, size_t B, hipStream_t);
+                                 uint32_t *pt, float *values, size_t B, hipStream_t,
+                                 const KeyRing *ring = nullptr);
+// key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
+//   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
+//   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)
+//   key_sanitize    : idx[b] = min(raw[b], K - 1); bad = count + records with raw[b] >= K (bad[0] zeroed first)
+//   key_reject      : for every record of `bad`: status 2 and zero rows (row b of rows[r] = words[r] words)
+hipError_t launch_ring_secret_ntt(const DevParams &, const DevTables &, int j, const uint8_t *packed, uint32_t *ring,
+                                  size_t K, hipStream_t);
+hipError_t launch_ring_pairs(const DevParams &, const uint32_t *vals, uint32_t *pairs, size_t K, hipStream_t);
+hipError_t launch_key_sanitize(const uint32_t *raw, uint32_t *idx, uint32_t *bad, size_t K, size_t B, hipStream_t);
+struct KeyRejectArgs
+{
+    const uint32_t *bad;
+    uint8_t *status;      // optional
+    uint32_t *rows[3];    // optional
+    size_t words[3];
+};
+hipError_t launch_key_reject(const DevParams &, const KeyRejectArgs &, size_t B, hipStream_t);
 hipError_t launch_reduce_small(const DevParams &, const int8_t *e, uint32_t *out, size_t count, hipStream_t);
 hipError_t launch_ntt_polys(const DevParams &, const DevTables &, int j, uint32_t *polys,
                             uint32_t *pairs, size_t count, hipStream_t);

@@ -189,6 +189,46 @@ int se_amd_encrypt_asym_device(se_amd_ctx *ctx, const float *d_values, size_t B,
                                as_stream(stream));
 }
 
+int se_amd_set_secret_keyring(se_amd_ctx *ctx, size_t K, const uint8_t *sk_packed)
+{
+    if (!ctx || !sk_packed) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_secret_keyring(K, sk_packed);
+}
+
+int se_amd_set_public_keyring(se_amd_ctx *ctx, size_t K, const uint32_t *pk0, const uint32_t *pk1)
+{
+    if (!ctx || !pk0 || !pk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_public_keyring(K, pk0, pk1);
+}
+
+int se_amd_encrypt_sym_keyed_device(se_amd_ctx *ctx, const float *d_values, size_t B, const uint32_t *d_key_idx,
+                                    const uint8_t *d_share_seeds, const uint8_t *d_seeds, uint32_t *d_c0,
+                                    uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
+                                    void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.encrypt_sym_keyed(d_values, B, d_key_idx, d_share_seeds, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte,
+                                    d_status, as_stream(stream));
+}
+
+int se_amd_encrypt_asym_keyed_device(se_amd_ctx *ctx, const float *d_values, size_t B, const uint32_t *d_key_idx,
+                                     const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte,
+                                     int64_t *d_pte, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.encrypt_asym_keyed(d_values, B, d_key_idx, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status,
+                                     as_stream(stream));
+}
+
+int se_amd_decrypt_decode_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                       const uint32_t *d_key_idx, size_t prime, uint32_t *d_dec_ntt,
+                                       uint32_t *d_pt, float *d_values, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt_decode_keyed(d_c0, d_c1, B, d_key_idx, prime, d_dec_ntt, d_pt, d_values,
+                                       as_stream(stream));
+}
+
 int se_amd_encode_ntt_device(se_amd_ctx *ctx, const float *d_values, size_t B, uint32_t *d_out,
                              int64_t *d_pte, uint8_t *d_status, void *stream)
 {

@@ -171,6 +171,17 @@ int Context::ensure_general(size_t B)
     return 0;
 }
 
+// The keyed calls' clamped indices and list of out-of-range records: 8 bytes per record.
+int Context::ensure_keyed(size_t B)
+{
+    if (B <= d_kidx.size() && B < d_kbad.size()) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    SEAMD_HIP(hipDeviceSynchronize());
+    SEAMD_HIP(d_kidx.grow(B));
+    SEAMD_HIP(d_kbad.grow(B + 1));
+    return 0;
+}
+
 int Context::ensure_scratch(size_t B, size_t rows)
 {
     if (int rc = ensure_general(B)) return rc;
@@ -304,6 +315,84 @@ int Context::set_public_key(const uint32_t *pk0, const uint32_t *pk1)
     dt.pk0  = d_pk0;
     dt.pk1  = d_pk1;
     have_pk = true;
+    return 0;
+}
+
+// Key rings: K keys validated as the single-key setters validate one, installed with O(np) launches whatever K.
+// A ring is replaced only after every call already enqueued on the context has finished (they may read the old one).
+int Context::set_secret_keyring(size_t K, const uint8_t *sk_packed)
+{
+    const size_t n = hp.n, np = hp.nprimes, bytes = K * (n / 4);
+    if (K == 0 || K > 0xFFFFFFFFull)
+    {
+        set_last_error("set_secret_keyring: K must be between 1 and 2^32 - 1");
+        return kErrInvalid;
+    }
+    // code 3 anywhere: a byte with both bits of some 2-bit field set
+    for (size_t i = 0; i < bytes; i++)
+        if (sk_packed[i] & (sk_packed[i] >> 1) & 0x55u)
+        {
+            set_last_error("secret key ring: key " + std::to_string(i / (n / 4)) + " holds an invalid 2-bit code (3)");
+            return kErrInvalid;
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    SEAMD_HIP(hipDeviceSynchronize());   // calls in flight may still read the old ring
+    ring_sk = 0;
+    d_ring_sk.release();                 // wiped (secret)
+    // the packed keys cross the bus as they are and are expanded on the device: no host copy to wipe, and the
+    // device staging buffer is secret (wiped when it is freed below)
+    DevBuf<uint8_t> d_packed{Secret::yes};
+    SEAMD_HIP(d_packed.grow(bytes));
+    SEAMD_HIP(d_ring_sk.grow(2 * K * np * n));
+    SEAMD_HIP(hipMemcpy(d_packed, sk_packed, bytes, hipMemcpyHostToDevice));
+    for (size_t j = 0; j < np; j++)
+        SEAMD_HIP(launch_ring_secret_ntt(dp, dt, (int)j, d_packed, d_ring_sk, K, nullptr));
+    SEAMD_HIP(hipDeviceSynchronize());
+    ring_sk = K;
+    return 0;
+}
+
+int Context::set_public_keyring(size_t K, const uint32_t *pk0, const uint32_t *pk1)
+{
+    const size_t n = hp.n, np = hp.nprimes;
+    if (K == 0 || K > 0xFFFFFFFFull)
+    {
+        set_last_error("set_public_keyring: K must be between 1 and 2^32 - 1");
+        return kErrInvalid;
+    }
+    for (size_t k = 0; k < K; k++)
+        for (size_t j = 0; j < np; j++)
+        {
+            const uint32_t q = hp.q[j];
+            const uint32_t *r0 = pk0 + (k * np + j) * n, *r1 = pk1 + (k * np + j) * n;
+            uint32_t bad = 0;
+            for (size_t i = 0; i < n; i++) bad |= (uint32_t)(r0[i] >= q) | (uint32_t)(r1[i] >= q);
+            if (bad)
+            {
+                set_last_error("public key ring: key " + std::to_string(k) +
+                               " holds a coefficient not reduced modulo its prime");
+                return kErrInvalid;
+            }
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    SEAMD_HIP(hipDeviceSynchronize());   // calls in flight may still read the old ring
+    ring_pk = 0;
+    d_ring_pk0.release();
+    d_ring_pk1.release();
+    const size_t slab = K * np * n;
+    DevBuf<uint32_t> d_tmp;
+    SEAMD_HIP(d_tmp.grow(slab));
+    SEAMD_HIP(d_ring_pk0.grow(2 * slab));
+    SEAMD_HIP(d_ring_pk1.grow(2 * slab));
+    SEAMD_HIP(hipMemcpy(d_tmp, pk0, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SEAMD_HIP(launch_ring_pairs(dp, d_tmp, d_ring_pk0, K, nullptr));
+    SEAMD_HIP(hipDeviceSynchronize());
+    SEAMD_HIP(hipMemcpy(d_tmp, pk1, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SEAMD_HIP(launch_ring_pairs(dp, d_tmp, d_ring_pk1, K, nullptr));
+    SEAMD_HIP(hipDeviceSynchronize());
+    ring_pk = K;
     return 0;
 }
 
@@ -503,9 +592,10 @@ int Context::sample_uniform(const uint8_t *d_seeds, const uint64_t *d_ctr_in, si
 
 int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_share_seeds,
                               const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1,
-                              uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st)
+                              uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st,
+                              const KeyRing *ring)
 {
-    if (!have_sk)
+    if (!have_sk && !ring)
     {
         set_last_error("symmetric encryption needs a secret key (se_amd_set_secret_key)");
         return kErrNoKey;
@@ -516,9 +606,9 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
     {
         // a handful of ciphertexts: latency path (all primes' samplers at once, prime speculation)
         SpecPlan plan;
-        if (split_mode == 2 && small_batch_plan(B, plan) && speculation_pays(B, plan))
+        if (split_mode == 2 && small_batch_plan(B, plan, ring != nullptr) && speculation_pays(B, plan))
             return encrypt_sym_small(plan, d_values, d_share_seeds, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte,
-                                     d_status, st);
+                                     d_status, st, ring);
     }
     int rc = ensure_scratch(B);
     if (rc) return rc;
@@ -549,7 +639,7 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
         stage_end(st);
         if (overlap) SEAMD_HIP(hipStreamWaitEvent(st, ev_join, 0));
         stage_begin(3, st);
-        SEAMD_HIP(launch_encode_encrypt(dp, dt, ea, kModeSym, B, st));
+        SEAMD_HIP(launch_encode_encrypt(dp, dt, ea, kModeSym, B, st, ring));
         stage_end(st);
         return 0;
     }
@@ -650,7 +740,7 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
                 SEAMD_HIP(hipStreamWaitEvent(ax, ev_prime[j], 0));
             }
             stage_begin(5, ax);
-            SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)j, B, ax));
+            SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)j, B, ax, ring));
             stage_end(ax);
         }
     }
@@ -660,16 +750,16 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
         SEAMD_HIP(hipStreamWaitEvent(st, ev_join, 0));
     }
     stage_begin(5, st);
-    SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)np - 1, B, st));
+    SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)np - 1, B, st, ring));
     stage_end(st);
     return 0;
 }
 
 // ---- small-batch prime speculation -----------------------------------------------------------
-bool Context::small_batch_plan(size_t B, SpecPlan &plan) const
+bool Context::small_batch_plan(size_t B, SpecPlan &plan, bool keyed) const
 {
     const uint32_t np = (uint32_t)hp.nprimes;
-    if (!overlap || !have_sk || np < 2 || B == 0 || B > 1024) return false;
+    if (!overlap || !(have_sk || keyed) || np < 2 || B == 0 || B > 1024) return false;
     plan         = SpecPlan{};
     plan.nprimes = np;
     plan.B       = (uint32_t)B;
@@ -726,7 +816,8 @@ bool Context::speculation_pays(size_t B, const SpecPlan &plan) const
 
 int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, const uint8_t *d_share_seeds,
                                const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1,
-                               uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st)
+                               uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st,
+                               const KeyRing *ring)
 {
     if (!d_values || !d_share_seeds || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
     SEAMD_HIP(hipSetDevice(device));
@@ -797,7 +888,7 @@ int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, cons
     for (uint32_t j = 0; j < np; j++)
     {
         stage_begin(5, st);
-        SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)j, B, st));
+        SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)j, B, st, ring));
         stage_end(st);
     }
     return 0;
@@ -805,9 +896,9 @@ int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, cons
 
 int Context::encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d_seeds, uint32_t *d_c0,
                                uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
-                               hipStream_t st)
+                               hipStream_t st, const KeyRing *ring)
 {
-    if (!have_pk)
+    if (!have_pk && !ring)
     {
         set_last_error("asymmetric encryption needs a public key (se_amd_set_public_key)");
         return kErrNoKey;
@@ -865,11 +956,127 @@ int Context::encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d
                    d_pte ? d_pte + lo * n : nullptr,
                    d_status ? d_status + lo : nullptr,
                    d_general};
+        KeyRing rc_chunk{};
+        if (ring)
+        {
+            rc_chunk = *ring;
+            rc_chunk.idx += lo;   // the chunk's records
+        }
         stage_begin(3, st);
-        SEAMD_HIP(launch_encode_encrypt(dp, dt, ea, kModeAsym, cb, st));
+        SEAMD_HIP(launch_encode_encrypt(dp, dt, ea, kModeAsym, cb, st, ring ? &rc_chunk : nullptr));
         stage_end(st);
     }
     return 0;
+}
+
+// ---- keyed entries ---------------------------------------------------------------------------
+// Every call first writes a clamped copy of the caller's indices (d_kidx: the kernels never see an index >= K) and the
+// list of records whose index was out of range (d_kbad); the unkeyed dispatch then runs with the keyed kernels
+// (KeyRing), and a last pass gives the listed records status 2 and zero c0 (and c1 in public-key mode).
+int Context::key_prologue(const uint32_t *d_key_idx, size_t K, size_t B, hipStream_t st)
+{
+    int rc = ensure_keyed(B);
+    if (rc) return rc;
+    SEAMD_HIP(launch_key_sanitize(d_key_idx, d_kidx, d_kbad, K, B, st));
+    return 0;
+}
+
+int Context::encrypt_sym_keyed(const float *d_values, size_t B, const uint32_t *d_key_idx,
+                               const uint8_t *d_share_seeds, const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1,
+                               uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!ring_sk)
+    {
+        set_last_error("keyed symmetric encryption needs a secret key ring (se_amd_set_secret_keyring)");
+        return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    if (!d_values || !d_key_idx || !d_share_seeds || !d_seeds || !d_c0) return kErrInvalid;
+    SEAMD_HIP(hipSetDevice(device));
+    // d_c1 NULL: the seed-compressed form, `a` into context scratch (as encrypt_sym_seeded)
+    if (!d_c1 && B * hp.nprimes * hp.n > d_a.size())
+    {
+        SEAMD_HIP(hipDeviceSynchronize());   // earlier calls may still read the old slab
+        SEAMD_HIP(d_a.grow(B * hp.nprimes * hp.n));
+    }
+    int rc = begin_call(st);
+    if (rc) return rc;
+    rc = key_prologue(d_key_idx, ring_sk, B, st);
+    if (rc == 0)
+    {
+        const KeyRing ring{d_ring_sk, d_ring_sk, d_kidx, (size_t)2 * hp.nprimes * hp.n};
+        rc = encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_c1 ? d_c1 : d_a.get(), d_ntt_pte, d_pte,
+                              d_status, st, &ring);
+    }
+    if (rc == 0)
+    {
+        const KeyRejectArgs ra{d_kbad, d_status, {d_c0, nullptr, nullptr}, {hp.nprimes * hp.n, 0, 0}};
+        hipError_t e = launch_key_reject(dp, ra, B, st);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
+    }
+    return end_call(st, rc);
+}
+
+int Context::encrypt_asym_keyed(const float *d_values, size_t B, const uint32_t *d_key_idx, const uint8_t *d_seeds,
+                                uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte,
+                                uint8_t *d_status, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!ring_pk)
+    {
+        set_last_error("keyed public-key encryption needs a public key ring (se_amd_set_public_keyring)");
+        return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    if (!d_values || !d_key_idx || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
+    int rc = begin_call(st);
+    if (rc) return rc;
+    rc = key_prologue(d_key_idx, ring_pk, B, st);
+    if (rc == 0)
+    {
+        const KeyRing ring{d_ring_pk0, d_ring_pk1, d_kidx, (size_t)2 * hp.nprimes * hp.n};
+        rc = encrypt_asym_impl(d_values, B, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st, &ring);
+    }
+    if (rc == 0)
+    {
+        const KeyRejectArgs ra{d_kbad, d_status, {d_c0, d_c1, nullptr}, {hp.nprimes * hp.n, hp.nprimes * hp.n, 0}};
+        hipError_t e = launch_key_reject(dp, ra, B, st);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
+    }
+    return end_call(st, rc);
+}
+
+// An out-of-range index: the record is decrypted under the clamped index and its outputs are then zeroed.
+int Context::decrypt_decode_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
+                                  size_t prime, uint32_t *d_dec_ntt, uint32_t *d_pt, float *d_values, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!ring_sk)
+    {
+        set_last_error("keyed decrypt needs a secret key ring (se_amd_set_secret_keyring)");
+        return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    if (!d_c0 || !d_c1 || !d_key_idx || prime >= hp.nprimes) return kErrInvalid;
+    int rc = begin_call(st);
+    if (rc) return rc;
+    rc = key_prologue(d_key_idx, ring_sk, B, st);
+    if (rc == 0)
+    {
+        const KeyRing ring{d_ring_sk, d_ring_sk, d_kidx, (size_t)2 * hp.nprimes * hp.n};
+        hipError_t e = launch_decrypt_decode(dp, dt, d_c0, d_c1, (uint32_t)hp.nprimes, (int)prime, d_dec_ntt, d_pt,
+                                             d_values, B, st, &ring);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_decrypt_decode");
+    }
+    if (rc == 0)
+    {
+        const KeyRejectArgs ra{d_kbad, nullptr, {d_dec_ntt, d_pt, reinterpret_cast<uint32_t *>(d_values)},
+                               {hp.n, hp.n, hp.n / 2}};
+        hipError_t e = launch_key_reject(dp, ra, B, st);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
+    }
+    return end_call(st, rc);
 }
 
 // d_out NULL: plain ckks_encode_base (only the int64 plaintexts are written)

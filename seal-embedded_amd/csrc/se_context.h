@@ -45,6 +45,13 @@ struct Context
     DevBuf<uint32_t> d_ntt_rw, d_intt_rw, d_pk0, d_pk1;
     DevBuf<uint32_t> d_s_hat{Secret::yes};
     bool have_sk = false, have_pk = false;
+    // key rings of the keyed entries (se_amd_set_{secret,public}_keyring): K keys, each in the layout of the
+    // installed key ([np][n][2] (value, Shoup)), back to back; independent of d_s_hat / d_pk0 / d_pk1
+    DevBuf<uint32_t> d_ring_sk{Secret::yes};   // [K][np][n][2] NTT(s) pairs
+    DevBuf<uint32_t> d_ring_pk0, d_ring_pk1;   // [K][np][n][2]
+    size_t ring_sk = 0, ring_pk = 0;           // keys in each ring (0 = no ring)
+    DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
+    DevBuf<uint32_t> d_kbad;                   // [1 + cap] count + records whose index was out of range
 
     // scratch, grown on demand (ensure_scratch): `cap` ciphertexts, `rows` >= cap rows of the reject lists and
     // candidates (the virtual ciphertexts of the small-batch path need only these)
@@ -113,6 +120,7 @@ struct Context
     int init(size_t n, size_t nprimes, int device);
     int ensure_scratch(size_t B, size_t rows = 0);
     int ensure_general(size_t B);
+    int ensure_keyed(size_t B);
     int begin_call(hipStream_t st);
     int end_call(hipStream_t st, int rc);
     // u codes (0/1/2 per coefficient) and e1 of ciphertext 0 of the last asymmetric call (host out)
@@ -120,6 +128,9 @@ struct Context
     int set_secret_key(const uint8_t *sk_packed);
     int set_secret_key_impl(const uint8_t *sk_packed);   // caller holds `mu`
     int set_public_key(const uint32_t *pk0, const uint32_t *pk1);
+    // key rings (host pointers, the layouts gen_keys_batch writes); replace the ring of that kind
+    int set_secret_keyring(size_t K, const uint8_t *sk_packed);
+    int set_public_keyring(size_t K, const uint32_t *pk0, const uint32_t *pk1);
     int gen_public_key(const uint8_t *sk_packed, const uint8_t *pk_seed, const uint8_t *ep_seed,
                        uint32_t *pk0_out, uint32_t *pk1_out);
     // K key pairs in one launch chain (host pointers); does not touch the context's installed keys
@@ -137,24 +148,36 @@ struct Context
                      hipStream_t st);
     int encode_ntt(const float *d_values, size_t B, uint32_t *d_out, int64_t *d_pte,
                    uint8_t *d_status, hipStream_t st);
+    // keyed entries: record b under ring key d_key_idx[b] (status 2 and zero c0 / c1 for an index >= K)
+    int encrypt_sym_keyed(const float *d_values, size_t B, const uint32_t *d_key_idx, const uint8_t *d_share_seeds,
+                          const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte,
+                          int64_t *d_pte, uint8_t *d_status, hipStream_t st);
+    int encrypt_asym_keyed(const float *d_values, size_t B, const uint32_t *d_key_idx, const uint8_t *d_seeds,
+                           uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
+                           hipStream_t st);
+    int decrypt_decode_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
+                             size_t prime, uint32_t *d_dec_ntt, uint32_t *d_pt, float *d_values, hipStream_t st);
+    // sanitising pass of a keyed call (d_kidx / d_kbad from the caller's indices); the caller holds `mu`
+    int key_prologue(const uint32_t *d_key_idx, size_t K, size_t B, hipStream_t st);
     int sample_uniform(const uint8_t *d_seeds, const uint64_t *d_ctr_in, size_t B, uint32_t *d_out,
                        uint64_t *d_ctr_out, hipStream_t st);
+    // ring != NULL: the keyed kernels, record b under key ring->idx[b] (keyed entries above)
     int encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_share_seeds,
                          const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte,
-                         int64_t *d_pte, uint8_t *d_status, hipStream_t st);
+                         int64_t *d_pte, uint8_t *d_status, hipStream_t st, const KeyRing *ring = nullptr);
     int encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d_seeds, uint32_t *d_c0,
                           uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
-                          hipStream_t st);
+                          hipStream_t st, const KeyRing *ring = nullptr);
     // Small batches (a handful of ciphertexts): all primes' uniform samplers at once under guessed
     // start counters (kernels/samplers.hip, k_spec_*).  small_batch_plan says whether a batch
     // qualifies (encrypt_sym dispatches on it).  A counter outside its window (~1e-7 per prime) is
     // redone on the device by the masked per-prime chain that follows the selection.
-    bool small_batch_plan(size_t B, SpecPlan &plan) const;
+    bool small_batch_plan(size_t B, SpecPlan &plan, bool keyed = false) const;
     // speculation or the plain per-prime chain for this batch (estimated chain latencies of both)
     bool speculation_pays(size_t B, const SpecPlan &plan) const;
     int encrypt_sym_small(const SpecPlan &plan, const float *d_values, const uint8_t *d_share_seeds,
                           const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte,
-                          int64_t *d_pte, uint8_t *d_status, hipStream_t st);
+                          int64_t *d_pte, uint8_t *d_status, hipStream_t st, const KeyRing *ring = nullptr);
 
     void stage_begin(int stage, hipStream_t st);
     void stage_end(hipStream_t st);
