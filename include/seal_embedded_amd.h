@@ -297,6 +297,32 @@ int se_amd_intt_device(se_amd_ctx *ctx, size_t prime, uint32_t *d_polys, size_t 
 int se_amd_decrypt_decode_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1,
                                  size_t B, size_t prime, uint32_t *d_dec_ntt, uint32_t *d_pt,
                                  float *d_values, void *stream);
+/* Full-modulus decrypt and decode: the receiving side for plaintexts of any size the encoder accepts.  One launch
+ * over ALL primes of every ciphertext: pt_j = INTT(c0_j + c1_j . NTT(s)_j) for j = 0 .. np-1 as above, then the
+ * residues are recombined (incremental Garner / CRT) to the one integer y per coefficient with y = pt_j (mod q_j) for
+ * every j and y in (-Q/2, Q/2], Q = q_0 ... q_{np-1}; for a symmetric ciphertext that is the int64 m + e the
+ * encryption entry reports in d_pte.  Decode is ckks_decode (ckks_tests_common.c:72-115) on y instead of the
+ * single-prime lift: y / scale, fft_inpl, slot pick through the index map.
+ * Range: exact while every |m + e| < min(2^63, Q/2).  d_status[b] = 1 if every recombined coefficient of record b lies
+ * in [-2^63, 2^63), else 0 (a plaintext beyond the range, a wrong key or a corrupted record); the other outputs of a
+ * status-0 record are unspecified.  With one prime this is the single-prime lift (status always 1).
+ * Outputs, each optional (NULL to skip), at least one required: d_pte [B][n] int64, natural order; d_values [B][n/2]
+ * float; d_values_f64 [B][n/2] double, the same slots before the float conversion; d_status [B].  With neither
+ * d_values nor d_values_f64 the FFT is skipped.  Asynchronous on `stream`; no scratch memory is allocated.
+ * SE_ERR_NO_KEY without a secret key (keyed: without a secret ring); SE_ERR_INVALD_ARGUMENT for a NULL d_c0 / d_c1
+ * (/ d_key_idx) or when no output is requested.
+ * Keyed: ciphertext b under secret-ring key d_key_idx[b]; a record whose index is >= K gets status 2 and all-zero
+ * outputs. */
+int se_amd_decrypt_full_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                               int64_t *d_pte, float *d_values, double *d_values_f64,
+                               uint8_t *d_status, void *stream);
+int se_amd_decrypt_full_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                     const uint32_t *d_key_idx, int64_t *d_pte, float *d_values,
+                                     double *d_values_f64, uint8_t *d_status, void *stream);
+/* Host-only: the recombination constants the full-modulus decrypt uses, for inspection and CPU-side checks:
+ * inv[j] = (q_0 ... q_{j-1})^-1 mod q_j and inv_shoup[j] = floor(inv[j] * 2^32 / q_j) for j = 1 .. np-1 (entry 0 is
+ * 0).  inv_shoup may be NULL.  SE_ERR_INVALD_ARGUMENT for an unsupported (degree, nprimes). */
+int se_amd_crt_constants(size_t degree, size_t nprimes, uint32_t *inv, uint32_t *inv_shoup);
 /* prng_fill_buffer (rng.h:78-91): out[i] = SHAKE256(seed[i] || le64(ctr[i]))[0:outlen]. */
 int se_amd_prng_blocks_device(se_amd_ctx *ctx, const uint8_t *d_seeds, const uint64_t *d_ctrs,
                               uint8_t *d_out, size_t outlen, size_t count, void *stream);

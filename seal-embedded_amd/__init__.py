@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_set_reject_list_capacity", "se_amd_set_speculation_capacity", "se_amd_set_host_chunk", "se_amd_host_tables", "se_amd_ifft_table_sha256", "se_amd_reserve", "se_amd_set_debug_flags", "se_amd_set_pipeline", "se_amd_set_asym_chunks", "se_amd_last_error", "se_amd_version",
     "se_amd_set_secret_keyring", "se_amd_set_public_keyring", "se_amd_encrypt_sym_keyed_device",
     "se_amd_encrypt_asym_keyed_device", "se_amd_decrypt_decode_keyed_device",
+    "se_amd_decrypt_full_device", "se_amd_decrypt_full_keyed_device", "se_amd_crt_constants",
 )
 
 
@@ -136,6 +137,9 @@ def lib():
     L.se_amd_encrypt_sym_keyed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.se_amd_encrypt_asym_keyed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.se_amd_decrypt_decode_keyed_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]
+    L.se_amd_decrypt_full_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.se_amd_decrypt_full_keyed_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.se_amd_crt_constants.argtypes = [sz, sz, vp, vp]
     _lib = L
     return L
 
@@ -173,6 +177,14 @@ def host_tables(n, nprimes):
     _check(L.se_amd_host_tables(n, nprimes, _ptr(q), _ptr(cr), C.c_void_p(C.addressof(scale)), _ptr(imap), _ptr(w),
                                 _ptr(rw), _ptr(irw)), "se_amd_host_tables")
     return dict(q=q, const_ratio=cr, scale=scale.value, index_map=imap, ifft_w=w, ntt_rw=rw, intt_rw=irw)
+
+
+def crt_constants(n, nprimes):
+    """Recombination constants of decrypt_full (host only): (inv, inv_shoup) uint32 [np], entry 0 unused."""
+    import numpy as np
+    inv = np.zeros(nprimes, np.uint32); sh = np.zeros(nprimes, np.uint32)
+    _check(lib().se_amd_crt_constants(n, nprimes, _ptr(inv), _ptr(sh)), "se_amd_crt_constants")
+    return inv, sh
 
 
 class Group:
@@ -426,6 +438,22 @@ class Context:
         _check(self.L.se_amd_decrypt_decode_keyed_device(self.h, _ptr(c0), _ptr(c1), B, _ptr(key_idx), prime,
                                                          _ptr(dec_ntt), _ptr(pt), _ptr(values), _stream_ptr()),
                "se_amd_decrypt_decode_keyed_device")
+
+    def decrypt_full(self, c0, c1, pte=None, values=None, values_f64=None, status=None):
+        """All primes recombined: pte int64 [B][n], values float32 / values_f64 float64 [B][n/2], status uint8 [B]
+        (1 = every coefficient fits int64); each optional, at least one required."""
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt_full_device(self.h, _ptr(c0), _ptr(c1), B, _ptr(pte), _ptr(values),
+                                                 _ptr(values_f64), _ptr(status), _stream_ptr()),
+               "se_amd_decrypt_full_device")
+
+    def decrypt_full_keyed(self, c0, c1, key_idx, pte=None, values=None, values_f64=None, status=None):
+        """decrypt_full with ciphertext b under secret-ring key key_idx[b]; status 2 and zero outputs for an
+        index >= K."""
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt_full_keyed_device(self.h, _ptr(c0), _ptr(c1), B, _ptr(key_idx), _ptr(pte),
+                                                       _ptr(values), _ptr(values_f64), _ptr(status), _stream_ptr()),
+               "se_amd_decrypt_full_keyed_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

@@ -1247,6 +1247,189 @@ hipError_t launch_decrypt_decode(const DevParams &P, const DevTables &T, const u
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Full-modulus decrypt and decode: the receiving side for plaintexts larger than one prime.
+// One workgroup per ciphertext, ALL primes in one launch.  Per prime j: pt_j = INTT(c0_j + c1_j . NTT(s)_j) as in
+// decrypt_decode_body (same tiling, thread t holds the coefficients (e << (LOGN-4)) + t), then one step of the
+// incremental Garner recombination folds pt_j into the centred value y of the coefficient:
+//     y_0 = centred(pt_0),   c = centred((pt_j - y_{j-1}) . Q_{j-1}^-1 mod q_j),   y_j = y_{j-1} + Q_{j-1} c
+// with Q_{j-1} = q_0 ... q_{j-1}; y_j is THE representative of the value mod Q_j in (-Q_j/2, Q_j/2] (Q_j odd:
+// |y_j| <= (Q_{j-1} - 1)/2 + Q_{j-1} (q_j - 1)/2 = (Q_j - 1)/2).
+// The state between primes is the int64 y plus one flag per thread.  Q_1 < 2^60, so y_1 always fits; y_2 = y_1 +
+// Q_1 c is formed in 128 bits (|y_2| < 2^89) and the flag is raised when it leaves int64.  From the fourth prime on
+// a value that fits int64 has c = 0 (|y| < 2^63 < Q_{j-1}/2 is already its centred representative), and a non-zero c
+// gives |y_j| >= Q_{j-1}/2 > 2^63: the step is "reduce y mod q_j, compare with pt_j, flag a mismatch".  A flagged
+// coefficient never comes back into range, so its y may be anything afterwards.
+// The decode tail is decrypt_decode_body's with the int64 in place of the single-prime lift (ckks_decode,
+// device/test/ckks_tests_common.c:72-115): same never-contracted FP64 operations, same root table.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t centred_lift(uint32_t x, uint32_t q)
+{
+    return (x > q / 2) ? -(int64_t)(q - x) : (int64_t)x;
+}
+
+template <int LOGN, bool KEYED>
+__device__ __forceinline__ void decrypt_full_body(const DevParams &P, const DevTables &T, const CrtParams &C,
+                                                  const FullArgs &A, const KeyRing &R, unsigned char *smem)
+{
+    using G            = XformGeom<LOGN>;
+    constexpr int N    = G::N;
+    constexpr int CTOP = LOGN - 4;
+    uint32_t *lds32  = reinterpret_cast<uint32_t *>(smem);
+    double *plane    = reinterpret_cast<double *>(smem);
+    const size_t b   = blockIdx.x;
+    const int np     = (int)P.nprimes;
+    const uint32_t *key = T.s_hat;
+    if constexpr (KEYED) key = R.k0 + key_base(R, b);
+
+    int64_t y[16];
+    bool bad = false;
+    uint64_t qprod = 1;   // Q_{j-1}; used for j = 1, 2 only (< 2^60)
+    for (int j = 0; j < np; j++)
+    {
+        const int t      = opaque_index(threadIdx.x);   // per-prime addresses are formed here, not carried
+        const uint32_t q = P.q[j];
+        const size_t rec = (b * np + j) * N + 16 * t;
+        uint32_t x[16];
+        {
+            uint32_t a[16], w[16], wp[16];
+            load16(x, A.c0 + rec);
+            load16(a, A.c1 + rec);
+            load16_pairs(w, wp, key, (size_t)j * N + 16 * t);
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+                x[e] = csub(csub(mul_shoup_lazy(a[e], w[e], wp[e], q), q) + x[e], q);
+        }
+        intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, q, lds32, t);
+        const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
+#pragma unroll
+        for (int e = 0; e < 16; e++) x[e] = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, q), q);
+
+        if (j == 0)
+        {
+#pragma unroll
+            for (int e = 0; e < 16; e++) y[e] = centred_lift(x[e], q);
+        }
+        else
+        {
+            const uint32_t cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+            if (j <= 2)
+            {
+                const uint32_t qi = C.inv[j], qi_sh = C.inv_sh[j];
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                {
+                    // reduce_signed gives q for a negative multiple of q; any representative below 2q serves here
+                    const uint32_t r = reduce_signed(y[e], q, cr_hi, cr_lo);           // [0, q]
+                    const uint32_t d = x[e] + q - r;                                   // [0, 2q)
+                    const int64_t c  = centred_lift(csub(mul_shoup_lazy(d, qi, qi_sh, q), q), q);
+                    // y + Q_{j-1} c in 128 bits
+                    const uint64_t lo  = qprod * (uint64_t)c;
+                    const int64_t hi   = __mul64hi((long long)qprod, (long long)c);
+                    const uint64_t lo2 = lo + (uint64_t)y[e];
+                    const int64_t hi2  = hi + (y[e] >> 63) + (int64_t)(lo2 < lo);
+                    y[e]               = (int64_t)lo2;
+                    bad |= hi2 != (y[e] >> 63);
+                }
+            }
+            else
+            {
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    bad |= csub(reduce_signed(y[e], q, cr_hi, cr_lo), q) != x[e];
+            }
+        }
+        qprod *= q;
+    }
+
+    const int t = threadIdx.x;
+    const bool any_bad = __syncthreads_or(bad) != 0;
+    if (A.status && t == 0) A.status[b] = any_bad ? 0 : 1;
+    if (A.pte)
+    {
+#pragma unroll
+        for (int e = 0; e < 16; e++) A.pte[b * N + (e << CTOP) + t] = y[e];
+    }
+    if (!A.values && !A.values_f64) return;
+
+    double re[16], im[16];
+#pragma unroll
+    for (int e = 0; e < 16; e++)
+    {
+        re[e] = __ddiv_rn((double)y[e], P.scale);
+        im[e] = 0.0;
+    }
+    fft_tiles<LOGN>(re, im, T.ifft_w, plane, t);
+    // this thread holds res[16t + e]; the slot that reads it is inv_map[16t + e] when that is < n/2
+    const uint4 *mp = reinterpret_cast<const uint4 *>(T.inv_map + 16 * t);
+    uint4 m0 = mp[0], m1 = mp[1];
+    uint32_t packed[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+    for (int e = 0; e < 16; e++)
+    {
+        uint32_t i = (packed[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+        if (i < (uint32_t)(N / 2))
+        {
+            if (A.values) A.values[b * (N / 2) + i] = (float)re[e];
+            if (A.values_f64) A.values_f64[b * (N / 2) + i] = re[e];
+        }
+    }
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_full(DevParams P, DevTables T, CrtParams C,
+                                                                        FullArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    decrypt_full_body<LOGN, false>(P, T, C, A, KeyRing{}, smem);
+}
+
+// keyed twin: ciphertext b decrypted under ring key R.idx[b]
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_full_keyed(DevParams P, DevTables T,
+                                                                              CrtParams C, FullArgs A, KeyRing R)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    decrypt_full_body<LOGN, true>(P, T, C, A, R, smem);
+}
+
+template <int LOGN>
+static hipError_t launch_full(const DevParams &P, const DevTables &T, const CrtParams &C, const FullArgs &A, size_t B,
+                              hipStream_t st, const KeyRing *ring)
+{
+    using G = XformGeom<LOGN>;
+    // the INTT exchange takes SLOTS words; the FFT plane (SLOTS doubles) only when slots are decoded
+    const size_t shmem = (size_t)G::SLOTS * ((A.values || A.values_f64) ? sizeof(double) : sizeof(uint32_t));
+    if (ring)
+    {
+        (void)hipFuncSetAttribute((const void *)k_decrypt_full_keyed<LOGN>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        hipLaunchKernelGGL((k_decrypt_full_keyed<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, C, A,
+                           *ring);
+        return hipGetLastError();
+    }
+    (void)hipFuncSetAttribute((const void *)k_decrypt_full<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)shmem);
+    hipLaunchKernelGGL((k_decrypt_full<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, C, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_decrypt_full(const DevParams &P, const DevTables &T, const CrtParams &C, const FullArgs &A, size_t B,
+                               hipStream_t st, const KeyRing *ring)
+{
+    if (B == 0) return hipSuccess;
+    if (!A.c0 || !A.c1 || (!A.pte && !A.values && !A.values_f64 && !A.status)) return hipErrorInvalidValue;
+    switch (P.logn)
+    {
+        case 10: return launch_full<10>(P, T, C, A, B, st, ring);
+        case 11: return launch_full<11>(P, T, C, A, B, st, ring);
+        case 12: return launch_full<12>(P, T, C, A, B, st, ring);
+        case 13: return launch_full<13>(P, T, C, A, B, st, ring);
+        case 14: return launch_full<14>(P, T, C, A, B, st, ring);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 // reduce_set_e_small (ckks_common.c:259-265) for every prime: int8 error -> residues, natural order,
 // into a [count][np][n] slab (public-key generation feeds them to k_ntt_fuse).
 __global__ void k_reduce_small(DevParams P, const int8_t *e, uint32_t *out, int count)

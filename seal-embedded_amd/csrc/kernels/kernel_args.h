@@ -107,6 +107,19 @@ hipError_t launch_decrypt_decode(const DevParams &, const DevTables &, const uin
                                  const uint32_t *c1, uint32_t in_primes, int j, uint32_t *dec_ntt,
                                  uint32_t *pt, float *values, size_t B, hipStream_t,
                                  const KeyRing *ring = nullptr);
+// Full-modulus decrypt (k_decrypt_full): all primes of a ciphertext in one launch, recombined to the centred
+// integer over Q = q_0 ... q_{np-1}.  Every output is optional, at least one must be set.
+struct FullArgs
+{
+    const uint32_t *c0;   // [B][np][n]
+    const uint32_t *c1;   // [B][np][n]
+    int64_t *pte;         // [B][n]    recombined m + e, natural order
+    float *values;        // [B][n/2]  decoded slots
+    double *values_f64;   // [B][n/2]  the same slots before the float conversion
+    uint8_t *status;      // [B]       1 = every coefficient fits int64, else 0
+};
+hipError_t launch_decrypt_full(const DevParams &, const DevTables &, const CrtParams &, const FullArgs &, size_t B,
+                               hipStream_t, const KeyRing *ring = nullptr);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

@@ -279,6 +279,40 @@ int se_amd_decrypt_decode_device(se_amd_ctx *ctx, const uint32_t *d_c0, const ui
     return SE_SUCCESS;
 }
 
+int se_amd_decrypt_full_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                               int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status,
+                               void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt_full(d_c0, d_c1, B, d_pte, d_values, d_values_f64, d_status, as_stream(stream));
+}
+
+int se_amd_decrypt_full_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                     const uint32_t *d_key_idx, int64_t *d_pte, float *d_values,
+                                     double *d_values_f64, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt_full_keyed(d_c0, d_c1, B, d_key_idx, d_pte, d_values, d_values_f64, d_status,
+                                     as_stream(stream));
+}
+
+int se_amd_crt_constants(size_t degree, size_t nprimes, uint32_t *inv, uint32_t *inv_shoup)
+{
+    seamd::HostParams hp;
+    if (!inv || seamd::host_params_init(hp, degree, nprimes) != 0)
+    {
+        seamd::set_last_error("unsupported parameter set (degree, nprimes)");
+        return SE_ERR_INVALD_ARGUMENT;
+    }
+    const seamd::CrtParams c = seamd::host_crt_params(hp);
+    for (size_t j = 0; j < hp.nprimes; j++)
+    {
+        inv[j] = c.inv[j];
+        if (inv_shoup) inv_shoup[j] = c.inv_sh[j];
+    }
+    return SE_SUCCESS;
+}
+
 int se_amd_prng_blocks_device(se_amd_ctx *ctx, const uint8_t *d_seeds, const uint64_t *d_ctrs,
                               uint8_t *d_out, size_t outlen, size_t count, void *stream)
 {

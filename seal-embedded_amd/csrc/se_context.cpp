@@ -77,6 +77,7 @@ int Context::init(size_t n, size_t nprimes, int dev)
     if (const char *e = getenv("SE_AMD_SPECULATION")) spec_mode = atoi(e) ? 1 : 0;
     dp         = to_dev_params(hp);
     dp.num_cus = (uint32_t)num_cus;
+    crt        = host_crt_params(hp);
     rej_cap = (uint32_t)(n / 16 > 256 ? n / 16 : 256);
     // rej_cap >= 3x the expected rejections per polynomial; spec_cap ~ mean + >5 sigma of the draws
     // speculation capacity: the helper waves compute this many candidates per polynomial WHILE the
@@ -1073,6 +1074,59 @@ int Context::decrypt_decode_keyed(const uint32_t *d_c0, const uint32_t *d_c1, si
     {
         const KeyRejectArgs ra{d_kbad, nullptr, {d_dec_ntt, d_pt, reinterpret_cast<uint32_t *>(d_values)},
                                {hp.n, hp.n, hp.n / 2}};
+        hipError_t e = launch_key_reject(dp, ra, B, st);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
+    }
+    return end_call(st, rc);
+}
+
+// Full-modulus decrypt: one launch, no scratch (nothing of the context is written, so no begin_call / end_call).
+int Context::decrypt_full(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, int64_t *d_pte, float *d_values,
+                          double *d_values_f64, uint8_t *d_status, hipStream_t st)
+{
+    if (!have_sk)
+    {
+        set_last_error("decrypt needs the secret key (se_amd_set_secret_key)");
+        return kErrNoKey;
+    }
+    if (!d_c0 || !d_c1 || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    const FullArgs fa{d_c0, d_c1, d_pte, d_values, d_values_f64, d_status};
+    SEAMD_HIP(launch_decrypt_full(dp, dt, crt, fa, B, st));
+    return 0;
+}
+
+// An out-of-range index: the record is decrypted under the clamped index; its status then becomes 2 and its other
+// outputs zero.
+int Context::decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
+                                int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status,
+                                hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!ring_sk)
+    {
+        set_last_error("keyed decrypt needs a secret key ring (se_amd_set_secret_keyring)");
+        return kErrNoKey;
+    }
+    if (!d_c0 || !d_c1 || !d_key_idx || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
+    if (B == 0) return 0;
+    int rc = begin_call(st);
+    if (rc) return rc;
+    rc = key_prologue(d_key_idx, ring_sk, B, st);
+    if (rc == 0)
+    {
+        const KeyRing ring{d_ring_sk, d_ring_sk, d_kidx, (size_t)2 * hp.nprimes * hp.n};
+        const FullArgs fa{d_c0, d_c1, d_pte, d_values, d_values_f64, d_status};
+        hipError_t e = launch_decrypt_full(dp, dt, crt, fa, B, st, &ring);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_decrypt_full");
+    }
+    if (rc == 0)
+    {
+        const KeyRejectArgs ra{d_kbad, d_status,
+                               {reinterpret_cast<uint32_t *>(d_pte), reinterpret_cast<uint32_t *>(d_values),
+                                reinterpret_cast<uint32_t *>(d_values_f64)},
+                               {2 * hp.n, hp.n / 2, hp.n}};
         hipError_t e = launch_key_reject(dp, ra, B, st);
         if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
     }

@@ -35,6 +35,7 @@ struct Context
 {
     HostParams hp;
     DevParams dp;
+    CrtParams crt;   // recombination constants of decrypt_full
     DevTables dt{};
     int device = 0;
     std::vector<uint16_t> index_map;  // host copy (SE_PTRS::index_map_ptr, tests)
@@ -157,6 +158,12 @@ struct Context
                            hipStream_t st);
     int decrypt_decode_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
                              size_t prime, uint32_t *d_dec_ntt, uint32_t *d_pt, float *d_values, hipStream_t st);
+    // full-modulus decrypt: all primes recombined (kernels/kernel_args.h, FullArgs); keyed: status 2 and zero
+    // outputs for an index >= K
+    int decrypt_full(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, int64_t *d_pte, float *d_values,
+                     double *d_values_f64, uint8_t *d_status, hipStream_t st);
+    int decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
+                           int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);
     // sanitising pass of a keyed call (d_kidx / d_kbad from the caller's indices); the caller holds `mu`
     int key_prologue(const uint32_t *d_key_idx, size_t K, size_t B, hipStream_t st);
     int sample_uniform(const uint8_t *d_seeds, const uint64_t *d_ctr_in, size_t B, uint32_t *d_out,

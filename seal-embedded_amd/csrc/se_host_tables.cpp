@@ -125,6 +125,24 @@ DevParams to_dev_params(const HostParams &hp)
     return d;
 }
 
+// Incremental Garner recombination (k_decrypt_full): the step for prime j multiplies by (q_0 ... q_{j-1})^-1 mod q_j.
+// The product is carried mod q_j only, so every intermediate stays below 2^60.
+CrtParams host_crt_params(const HostParams &hp)
+{
+    CrtParams c;
+    memset(&c, 0, sizeof(c));
+    for (size_t j = 1; j < hp.nprimes; j++)
+    {
+        const uint64_t q = hp.q[j];
+        uint64_t prod    = 1;
+        for (size_t i = 0; i < j; i++) prod = prod * (hp.q[i] % q) % q;
+        const uint32_t inv = host_inv_mod((uint32_t)prod, hp.q[j]);
+        c.inv[j]           = inv;
+        c.inv_sh[j]        = (uint32_t)(((uint64_t)inv << 32) / q);
+    }
+    return c;
+}
+
 size_t bitrev(size_t x, size_t nbits)
 {
     size_t r = 0;

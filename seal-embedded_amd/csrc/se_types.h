@@ -27,6 +27,14 @@ struct DevParams
     double small_bound;            // 2 min_j q_j - 64: below it every |m + e| of a plaintext lies in (-2 q_j, 2 q_j)
 };
 
+// Recombination constants of the full-modulus decrypt (k_decrypt_full), passed BY VALUE to that kernel only.
+// With Q_{j-1} = q_0 ... q_{j-1}: inv[j] = Q_{j-1}^-1 mod q_j and its Shoup companion, j >= 1 (entry 0 unused).
+struct CrtParams
+{
+    uint32_t inv[kMaxPrimes];
+    uint32_t inv_sh[kMaxPrimes];   // floor(inv * 2^32 / q_j)
+};
+
 // Device-resident read-only tables (pointers into one HBM slab owned by the context).
 struct DevTables
 {
