@@ -319,6 +319,40 @@ int se_amd_decrypt_full_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint
 int se_amd_decrypt_full_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
                                      const uint32_t *d_key_idx, int64_t *d_pte, float *d_values,
                                      double *d_values_f64, uint8_t *d_status, void *stream);
+/* Weighted sums of records, for the machine in the middle: a gateway or aggregator that holds NO key, receives
+ * ciphertexts and forwards one per group, window or model output.  The entry needs no key, installed or in a ring.
+ * With row = np . n, d_in0 / d_in1 are slabs [B][row] of residues (element (b, j, i) in [0, q_j), NTT form as every
+ * encryption entry writes them) and d_out0 / d_out1 are [G][row]:
+ *     out[g][j][i] = ( sum_k (w_k mod q_j) . in[idx_k][j][i] ) mod q_j,   canonical in [0, q_j),
+ * over the entries k of output row g.  w_k is a signed int32 and w mod q_j its non-negative residue (negative weights
+ * and INT32_MIN are valid).  The map is defined on arbitrary residue slabs and is applied identically to both; the
+ * second pair is optional (d_in1 = d_out1 = NULL).
+ * Entries, CSR form: d_row_ptr [G+1] uint32, non-decreasing, row_ptr[G] <= nnz; d_idx [nnz] uint32; d_w [nnz] int32 or
+ * NULL for all ones.  Row g takes k in [row_ptr[g], row_ptr[g+1]); an empty row is all zero with status 1.
+ * Dense form (d_row_ptr = d_idx = NULL, nnz = G . B): row g takes every record b with weight d_w[g . B + b]; d_w = NULL
+ * with G = 1 is the plain sum of the batch.
+ * d_status [G], optional: 1, or 2 (the key ring's convention) for a row with an index >= B or a row_ptr pair that
+ * decreases or reaches beyond nnz; a status-2 row is all zero in both slabs, other rows are unaffected and nothing is
+ * read out of bounds.  B = 0 with non-empty rows gives those rows status 2; G = 0 is a successful no-op.
+ * SE_ERR_INVALD_ARGUMENT: NULL d_in0 or d_out0; d_in1 and d_out1 not both set or both NULL; only one of d_row_ptr and
+ * d_idx NULL; dense form with nnz != G . B; B, G or nnz at or above 2^32; a slab pointer that is not 16-byte aligned.
+ * Outputs must not overlap inputs (not checked).
+ * Decryption: se_amd_decrypt_full_device on the result gives exactly sum_k w_k (m_b + e_b), the weighted sum of what
+ * the encryption entries report in d_pte, while every coefficient of that sum stays within min(2^63, Q/2); beyond that
+ * range it reports status 0.  Integer weights keep the CKKS scale; noise and range growth are the caller's business.
+ * All records of a row must be under the same key.  Seed-compressed records need se_amd_expand_c1_device first.
+ * Asynchronous on `stream`.  A long row is cut into S slices of its entry list so that a sum with few output rows
+ * still uses the whole chip; S is chosen on the host from G, nnz / G and the number of compute units.  S = 1 is one
+ * launch without scratch; S > 1 writes S partial rows per output row into context scratch (grown on demand, which
+ * synchronises the device; not stream-ordered: calls on one context are serialised on it) and sums them in a second
+ * launch.  Every S gives the same bits. */
+int se_amd_ct_lincomb_device(se_amd_ctx *ctx,
+        const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */, size_t B,
+        size_t G, const uint32_t *d_row_ptr, const uint32_t *d_idx, const int32_t *d_w, size_t nnz,
+        uint32_t *d_out0, uint32_t *d_out1 /* NULL iff d_in1 NULL */,
+        uint8_t *d_status /* [G], optional */, void *stream);
+/* test hook: partial sums a long row is split into (0 = automatic) */
+int se_amd_set_lincomb_split(se_amd_ctx *ctx, uint32_t splits);
 /* Host-only: the recombination constants the full-modulus decrypt uses, for inspection and CPU-side checks:
  * inv[j] = (q_0 ... q_{j-1})^-1 mod q_j and inv_shoup[j] = floor(inv[j] * 2^32 / q_j) for j = 1 .. np-1 (entry 0 is
  * 0).  inv_shoup may be NULL.  SE_ERR_INVALD_ARGUMENT for an unsupported (degree, nprimes). */

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_set_secret_keyring", "se_amd_set_public_keyring", "se_amd_encrypt_sym_keyed_device",
     "se_amd_encrypt_asym_keyed_device", "se_amd_decrypt_decode_keyed_device",
     "se_amd_decrypt_full_device", "se_amd_decrypt_full_keyed_device", "se_amd_crt_constants",
+    "se_amd_ct_lincomb_device", "se_amd_set_lincomb_split",
 )
 
 
@@ -140,6 +141,8 @@ def lib():
     L.se_amd_decrypt_full_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.se_amd_decrypt_full_keyed_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.se_amd_crt_constants.argtypes = [sz, sz, vp, vp]
+    L.se_amd_ct_lincomb_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.se_amd_set_lincomb_split.argtypes = [vp, u32]
     _lib = L
     return L
 
@@ -454,6 +457,27 @@ class Context:
         _check(self.L.se_amd_decrypt_full_keyed_device(self.h, _ptr(c0), _ptr(c1), B, _ptr(key_idx), _ptr(pte),
                                                        _ptr(values), _ptr(values_f64), _ptr(status), _stream_ptr()),
                "se_amd_decrypt_full_keyed_device")
+
+    def ct_lincomb(self, in0, out0, in1=None, out1=None, row_ptr=None, idx=None, w=None, G=None, status=None):
+        """Key-free weighted sums of records: out[g] = sum_k (w_k mod q) . in[idx_k] mod q on one or two slabs
+        [B][np][n].  CSR form: row_ptr [G+1], idx [nnz] (uint32 / int32 bits), w [nnz] int32 or None for all ones.
+        Dense form (row_ptr = idx = None): w [G][B], or None with G = 1 for the plain sum.  status uint8 [G]:
+        2 and a zero row for an index >= B or a bad row_ptr pair."""
+        B = in0.shape[0]
+        if row_ptr is not None:
+            G = row_ptr.numel() - 1
+            nnz = idx.numel() if idx is not None else 0
+        else:
+            if G is None:
+                G = w.shape[0] if w is not None else 1
+            nnz = G * B
+        _check(self.L.se_amd_ct_lincomb_device(self.h, _ptr(in0), _ptr(in1), B, G, _ptr(row_ptr), _ptr(idx), _ptr(w),
+                                               nnz, _ptr(out0), _ptr(out1), _ptr(status), _stream_ptr()),
+               "se_amd_ct_lincomb_device")
+
+    def set_lincomb_split(self, S):
+        """Test hook: slices a row of ct_lincomb is cut into (0 = automatic); every value gives the same bits."""
+        _check(self.L.se_amd_set_lincomb_split(self.h, S), "se_amd_set_lincomb_split")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

@@ -120,6 +120,28 @@ struct FullArgs
 };
 hipError_t launch_decrypt_full(const DevParams &, const DevTables &, const CrtParams &, const FullArgs &, size_t B,
                                hipStream_t, const KeyRing *ring = nullptr);
+// Weighted sums of records of one or two residue slabs (ct_ops.hip: k_ct_lincomb, k_ct_lincomb_sum), key-free:
+//   out[g][j][i] = sum_k (w_k mod q_j) . in[idx_k][j][i]  mod q_j   over the entries k of output row g.
+// CSR form: row g takes the entries [row_ptr[g], row_ptr[g+1]).  Dense form (row_ptr = idx = NULL): row g takes every
+// record b with weight w[g B + b].  w = NULL: all ones.  Status 1, or 2 with an all-zero row for an index >= B or a
+// row_ptr pair that decreases or passes nnz.
+struct LincombArgs
+{
+    const uint32_t *in0, *in1;   // [B][np][n]; in1 / out1 NULL: one slab
+    uint32_t *out0, *out1;       // [G][np][n]
+    const uint32_t *row_ptr;     // [G + 1] or NULL
+    const uint32_t *idx;         // [nnz] or NULL
+    const int32_t *w;            // [nnz] or NULL
+    uint8_t *status;             // [G], optional
+    uint32_t *part;              // S > 1: [slabs][G S][np][n] canonical partial rows (context scratch)
+    uint8_t *flag;               // S > 1: [G S] the slice saw an invalid entry
+    uint32_t B, nnz;
+    size_t G;
+    size_t g0;                   // first output row of the launch (set by the launcher)
+};
+// S slices per output row (1 <= S <= 65 535): S = 1 writes the outputs directly, S > 1 goes through part / flag and a
+// second launch that sums the S partial rows.  Every S gives the same bits (modular sums are exact).
+hipError_t launch_ct_lincomb(const DevParams &, const LincombArgs &, uint32_t S, hipStream_t);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

@@ -296,6 +296,23 @@ int se_amd_decrypt_full_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, cons
                                      as_stream(stream));
 }
 
+int se_amd_ct_lincomb_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t G,
+                             const uint32_t *d_row_ptr, const uint32_t *d_idx, const int32_t *d_w, size_t nnz,
+                             uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_lincomb(d_in0, d_in1, B, G, d_row_ptr, d_idx, d_w, nnz, d_out0, d_out1, d_status,
+                             as_stream(stream));
+}
+
+int se_amd_set_lincomb_split(se_amd_ctx *ctx, uint32_t splits)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    ctx->c.lincomb_split = splits;
+    return SE_SUCCESS;
+}
+
 int se_amd_crt_constants(size_t degree, size_t nprimes, uint32_t *inv, uint32_t *inv_shoup)
 {
     seamd::HostParams hp;

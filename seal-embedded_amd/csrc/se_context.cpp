@@ -1133,6 +1133,67 @@ int Context::decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size
     return end_call(st, rc);
 }
 
+// Slices per output row of ct_lincomb.  A workgroup owns 1024 residues of one output row, so G rows give
+// G * slabs * row / 1024 workgroups: 24 for the whole-batch sum at 4096 x 3, on 256 compute units.  Rows are cut until
+// there are 8 workgroups (32 waves) per compute unit -- all resident at once, twice the 16 waves per CU at which a row
+// gather reaches the HBM rate -- but a slice keeps at least 32 entries: it costs one partial row written and read back.
+uint32_t Context::lincomb_slices(size_t G, size_t nnz, size_t slabs) const
+{
+    const size_t wgs = G * slabs * ((hp.nprimes * hp.n) >> 10), want = (size_t)8 * (size_t)num_cus;
+    if (wgs >= want) return 1;
+    size_t S = (want + wgs - 1) / wgs;
+    const size_t longest = nnz / G / 32;   // by the mean row: no device read-back
+    if (S > longest) S = longest;
+    return (uint32_t)(S < 1 ? 1 : S > 65535 ? 65535 : S);
+}
+
+int Context::ensure_lincomb(size_t part_words, size_t flags)
+{
+    if (part_words <= d_lc_part.size() && flags <= d_lc_flag.size()) return 0;
+    SEAMD_HIP(hipDeviceSynchronize());
+    SEAMD_HIP(d_lc_part.grow(part_words));
+    SEAMD_HIP(d_lc_flag.grow(flags));
+    return 0;
+}
+
+// Key-free.  S = 1 is one launch that touches nothing of the context; S > 1 goes through the context's partial rows and
+// is ordered on them like every other call with scratch.
+int Context::ct_lincomb(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t G, const uint32_t *d_row_ptr,
+                        const uint32_t *d_idx, const int32_t *d_w, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                        uint8_t *d_status, hipStream_t st)
+{
+    constexpr size_t k32 = (size_t)1 << 32;
+    if (!d_in0 || !d_out0 || !d_in1 != !d_out1 || !d_row_ptr != !d_idx) return kErrInvalid;
+    if (B >= k32 || G >= k32 || nnz >= k32) return kErrInvalid;
+    if (!d_row_ptr && nnz != G * B) return kErrInvalid;
+    for (const void *p : {(const void *)d_in0, (const void *)d_in1, (const void *)d_out0, (const void *)d_out1})
+        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (G == 0) return 0;
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    const size_t slabs = d_in1 ? 2 : 1;
+    uint32_t S         = lincomb_split ? lincomb_split : lincomb_slices(G, nnz, slabs);
+    if (S > 65535) S = 65535;
+    LincombArgs la{d_in0, d_in1, d_out0, d_out1, d_row_ptr, d_idx, d_w, d_status, nullptr, nullptr,
+                   (uint32_t)B, (uint32_t)nnz, G, 0};
+    if (S == 1)
+    {
+        SEAMD_HIP(launch_ct_lincomb(dp, la, 1, st));
+        return 0;
+    }
+    int rc = begin_call(st);
+    if (rc) return rc;
+    rc = ensure_lincomb(slabs * G * S * hp.nprimes * hp.n, G * S);
+    if (rc == 0)
+    {
+        la.part      = d_lc_part;
+        la.flag      = d_lc_flag;
+        hipError_t e = launch_ct_lincomb(dp, la, S, st);
+        if (e != hipSuccess) rc = hip_fail(e, "launch_ct_lincomb");
+    }
+    return end_call(st, rc);
+}
+
 // d_out NULL: plain ckks_encode_base (only the int64 plaintexts are written)
 int Context::encode_ntt(const float *d_values, size_t B, uint32_t *d_out, int64_t *d_pte,
                         uint8_t *d_status, hipStream_t st)

@@ -82,6 +82,11 @@ struct Context
     DevBuf<uint8_t> d_compact;    // [cap] k_encode_rns -> k_ntt_fuse: plaintext b travels as one int32 row
     DevBuf<uint32_t> d_general;   // [1 + B] plaintexts the fast fused kernel declined (count, indices)
     uint32_t rej_cap   = 256;
+    // ct_lincomb with a split row: canonical partial rows and the slices' invalid-entry flags (not secret: sums of
+    // ciphertext residues), grown on demand (ensure_lincomb)
+    DevBuf<uint32_t> d_lc_part;   // [slabs][G S][np][n]
+    DevBuf<uint8_t> d_lc_flag;    // [G S]
+    uint32_t lincomb_split = 0;   // test hook (se_amd_set_lincomb_split): slices per output row, 0 = lincomb_slices
     uint32_t debug_flags = 0;  // timing ablations of the uniform sampler (tests/tools only)
 
     // second stream: the CBD error sampler runs beside the uniform sampler (different seeds, no
@@ -164,6 +169,12 @@ struct Context
                      double *d_values_f64, uint8_t *d_status, hipStream_t st);
     int decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
                            int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);
+    // key-free weighted sums of records (kernels/kernel_args.h, LincombArgs)
+    int ct_lincomb(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t G, const uint32_t *d_row_ptr,
+                   const uint32_t *d_idx, const int32_t *d_w, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                   uint8_t *d_status, hipStream_t st);
+    uint32_t lincomb_slices(size_t G, size_t nnz, size_t slabs) const;
+    int ensure_lincomb(size_t part_words, size_t flags);
     // sanitising pass of a keyed call (d_kidx / d_kbad from the caller's indices); the caller holds `mu`
     int key_prologue(const uint32_t *d_key_idx, size_t K, size_t B, hipStream_t st);
     int sample_uniform(const uint8_t *d_seeds, const uint64_t *d_ctr_in, size_t B, uint32_t *d_out,
