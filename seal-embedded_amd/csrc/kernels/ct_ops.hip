@@ -11,6 +11,7 @@
 // kLcFlight input rows are loaded before any of them is used.  Row offsets are 64-bit: B * row * 4 passes 4 GiB at
 // sizes users run (4096 x 3, B = 65 536 is 3.2 GB per slab; 16384 x 13 reaches 4 GiB at B = 5 042).
 #include "kernel_args.h"
+#include "launch.h"
 #include "modarith.cuh"
 
 namespace seamd {
@@ -218,13 +219,9 @@ hipError_t launch_ct_lincomb(const DevParams &P, const LincombArgs &args, uint32
         const uint32_t rows = (uint32_t)(args.G - g0 < 65535 ? args.G - g0 : 65535);
         A.g0                = g0;
         const dim3 grid(chunks * slabs, S, rows);
-        if (args.w)
-            hipLaunchKernelGGL(k_ct_lincomb<false>, grid, dim3(kLcThreads), 0, st, P, A);
-        else
-            hipLaunchKernelGGL(k_ct_lincomb<true>, grid, dim3(kLcThreads), 0, st, P, A);
-        if (S > 1)
-            hipLaunchKernelGGL(k_ct_lincomb_sum, dim3(chunks * slabs, 1, rows), dim3(kLcThreads), 0, st, P, A, S);
-        const hipError_t e = hipGetLastError();
+        hipError_t e = launch(args.w ? k_ct_lincomb<false> : k_ct_lincomb<true>, grid, dim3(kLcThreads), 0, st, P, A);
+        if (e == hipSuccess && S > 1)
+            e = launch(k_ct_lincomb_sum, dim3(chunks * slabs, 1, rows), dim3(kLcThreads), 0, st, P, A, S);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -22,6 +22,7 @@
 
 #include "../se_types.h"
 #include "kernel_args.h"
+#include "launch.h"
 #include "transform.cuh"
 
 namespace seamd {
@@ -1210,41 +1211,27 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_decode_key
     decrypt_decode_body<LOGN, true>(P, T, A, R, smem);
 }
 
-template <int LOGN>
-static hipError_t launch_vfy(const DevParams &P, const DevTables &T, const VerifyArgs &A, size_t B,
-                             hipStream_t st, const KeyRing *ring)
-{
-    using G      = XformGeom<LOGN>;
-    size_t shmem = (size_t)G::SLOTS * sizeof(double);
-    if (ring)
-    {
-        (void)hipFuncSetAttribute((const void *)k_decrypt_decode_keyed<LOGN>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_decrypt_decode_keyed<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, A,
-                           *ring);
-        return hipGetLastError();
-    }
-    (void)hipFuncSetAttribute((const void *)k_decrypt_decode<LOGN>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL((k_decrypt_decode<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_decrypt_decode(const DevParams &P, const DevTables &T, const uint32_t *c0,
                                  const uint32_t *c1, uint32_t in_primes, int j, uint32_t *dec_ntt,
                                  uint32_t *pt, float *values, size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
-    VerifyArgs A{c0, c1, dec_ntt, pt, values, in_primes, j};
-    switch (P.logn)
-    {
-        case 10: return launch_vfy<10>(P, T, A, B, st, ring);
-        case 11: return launch_vfy<11>(P, T, A, B, st, ring);
-        case 12: return launch_vfy<12>(P, T, A, B, st, ring);
-        case 13: return launch_vfy<13>(P, T, A, B, st, ring);
-        case 14: return launch_vfy<14>(P, T, A, B, st, ring);
-        default: return hipErrorInvalidValue;
-    }
+    VerifyArgs A{};
+    A.c0        = c0;
+    A.c1        = c1;
+    A.dec_ntt   = dec_ntt;
+    A.pt        = pt;
+    A.values    = values;
+    A.in_primes = in_primes;
+    A.j         = j;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)B), block(G::THREADS);
+        const size_t shmem = (size_t)G::SLOTS * sizeof(double);
+        if (ring) return launch(k_decrypt_decode_keyed<L>, grid, block, shmem, st, P, T, A, *ring);
+        return launch(k_decrypt_decode<L>, grid, block, shmem, st, P, T, A);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1393,41 +1380,20 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_full_keyed
     decrypt_full_body<LOGN, true>(P, T, C, A, R, smem);
 }
 
-template <int LOGN>
-static hipError_t launch_full(const DevParams &P, const DevTables &T, const CrtParams &C, const FullArgs &A, size_t B,
-                              hipStream_t st, const KeyRing *ring)
-{
-    using G = XformGeom<LOGN>;
-    // the INTT exchange takes SLOTS words; the FFT plane (SLOTS doubles) only when slots are decoded
-    const size_t shmem = (size_t)G::SLOTS * ((A.values || A.values_f64) ? sizeof(double) : sizeof(uint32_t));
-    if (ring)
-    {
-        (void)hipFuncSetAttribute((const void *)k_decrypt_full_keyed<LOGN>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_decrypt_full_keyed<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, C, A,
-                           *ring);
-        return hipGetLastError();
-    }
-    (void)hipFuncSetAttribute((const void *)k_decrypt_full<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem);
-    hipLaunchKernelGGL((k_decrypt_full<LOGN>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, C, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_decrypt_full(const DevParams &P, const DevTables &T, const CrtParams &C, const FullArgs &A, size_t B,
                                hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
     if (!A.c0 || !A.c1 || (!A.pte && !A.values && !A.values_f64 && !A.status)) return hipErrorInvalidValue;
-    switch (P.logn)
-    {
-        case 10: return launch_full<10>(P, T, C, A, B, st, ring);
-        case 11: return launch_full<11>(P, T, C, A, B, st, ring);
-        case 12: return launch_full<12>(P, T, C, A, B, st, ring);
-        case 13: return launch_full<13>(P, T, C, A, B, st, ring);
-        case 14: return launch_full<14>(P, T, C, A, B, st, ring);
-        default: return hipErrorInvalidValue;
-    }
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)B), block(G::THREADS);
+        // the INTT exchange takes SLOTS words; the FFT plane (SLOTS doubles) only when slots are decoded
+        const size_t shmem = (size_t)G::SLOTS * ((A.values || A.values_f64) ? sizeof(double) : sizeof(uint32_t));
+        if (ring) return launch(k_decrypt_full_keyed<L>, grid, block, shmem, st, P, T, C, A, *ring);
+        return launch(k_decrypt_full<L>, grid, block, shmem, st, P, T, C, A);
+    });
 }
 
 // reduce_set_e_small (ckks_common.c:259-265) for every prime: int8 error -> residues, natural order,
@@ -1447,9 +1413,7 @@ hipError_t launch_reduce_small(const DevParams &P, const int8_t *e, uint32_t *ou
 {
     if (count == 0) return hipSuccess;
     size_t total = count * P.n;
-    hipLaunchKernelGGL(k_reduce_small, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, e, out,
-                       (int)count);
-    return hipGetLastError();
+    return launch(k_reduce_small, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, e, out, (int)count);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1528,41 +1492,23 @@ __global__ void k_key_reject(KeyRejectArgs A)
     }
 }
 
-template <int LOGN>
-static hipError_t launch_ring_sk(const DevParams &P, const DevTables &T, int j, const uint8_t *packed,
-                                 uint32_t *ring, size_t K, hipStream_t st)
-{
-    using G      = XformGeom<LOGN>;
-    size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
-    (void)hipFuncSetAttribute((const void *)k_ring_secret_ntt<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem);
-    hipLaunchKernelGGL((k_ring_secret_ntt<LOGN>), dim3((unsigned)K), dim3(G::THREADS), shmem, st, P, T, j, packed,
-                       ring);
-    return hipGetLastError();
-}
-
 hipError_t launch_ring_secret_ntt(const DevParams &P, const DevTables &T, int j, const uint8_t *packed, uint32_t *ring,
                                   size_t K, hipStream_t st)
 {
     if (K == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_ring_sk<10>(P, T, j, packed, ring, K, st);
-        case 11: return launch_ring_sk<11>(P, T, j, packed, ring, K, st);
-        case 12: return launch_ring_sk<12>(P, T, j, packed, ring, K, st);
-        case 13: return launch_ring_sk<13>(P, T, j, packed, ring, K, st);
-        case 14: return launch_ring_sk<14>(P, T, j, packed, ring, K, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_logn(P.logn, [&](auto l) {
+        using G = XformGeom<decltype(l)::value>;
+        return launch(k_ring_secret_ntt<decltype(l)::value>, dim3((unsigned)K), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, j, packed, ring);
+    });
 }
 
 hipError_t launch_ring_pairs(const DevParams &P, const uint32_t *vals, uint32_t *pairs, size_t K, hipStream_t st)
 {
     const size_t total = K * P.nprimes * P.n;
     if (total == 0) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)64 * (P.num_cus ? P.num_cus : 256u));
-    hipLaunchKernelGGL(k_ring_pairs, dim3(grid), dim3(256), 0, st, P, vals, pairs, total);
-    return hipGetLastError();
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)64 * cus_or_default(P.num_cus));
+    return launch(k_ring_pairs, dim3(grid), dim3(256), 0, st, P, vals, pairs, total);
 }
 
 hipError_t launch_key_sanitize(const uint32_t *raw, uint32_t *idx, uint32_t *bad, size_t K, size_t B, hipStream_t st)
@@ -1571,17 +1517,14 @@ hipError_t launch_key_sanitize(const uint32_t *raw, uint32_t *idx, uint32_t *bad
     if (K == 0 || K > 0xFFFFFFFFull) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_key_sanitize, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, raw, idx, bad,
-                       (uint32_t)K, B);
-    return hipGetLastError();
+    return launch(k_key_sanitize, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, raw, idx, bad, (uint32_t)K, B);
 }
 
 hipError_t launch_key_reject(const DevParams &P, const KeyRejectArgs &A, size_t B, hipStream_t st)
 {
     if (B == 0) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)4 * (P.num_cus ? P.num_cus : 256u));
-    hipLaunchKernelGGL(k_key_reject, dim3(grid), dim3(256), 0, st, A);
-    return hipGetLastError();
+    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)4 * cus_or_default(P.num_cus));
+    return launch(k_key_reject, dim3(grid), dim3(256), 0, st, A);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1612,66 +1555,37 @@ static hipError_t launch_enc_mode(const DevParams &P, const DevTables &T, const 
     if (enc_pairs<LOGN, MODE>()) shmem_fast = std::max(shmem_fast, (kPairParkWords + (size_t)G::N) * sizeof(uint32_t));
     const unsigned grid_fast = (unsigned)(enc_pairs<LOGN, MODE>() ? (B + 1) / 2 : B);   // two plaintexts per workgroup
     // the plaintexts the fast form declined (normally none: the workgroups read a zero count and leave)
-    const unsigned cus  = P.num_cus ? P.num_cus : 256u;
-    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)4 * cus);
+    const dim3 fast(grid_fast), gen((unsigned)std::min<size_t>(B, (size_t)4 * cus_or_default(P.num_cus))), block(G::THREADS);
     if constexpr (MODE != kModeEncodeOnly)
     {
         if (ring)
         {
-            (void)hipFuncSetAttribute((const void *)k_encode_encrypt_keyed<LOGN, MODE>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_fast);
-            hipLaunchKernelGGL((k_encode_encrypt_keyed<LOGN, MODE>), dim3(grid_fast), dim3(G::THREADS), shmem_fast, st,
-                               P, T, Af, *ring);
-            e = hipGetLastError();
+            e = launch(k_encode_encrypt_keyed<LOGN, MODE>, fast, block, shmem_fast, st, P, T, Af, *ring);
             if (e != hipSuccess) return e;
-            (void)hipFuncSetAttribute((const void *)k_encode_encrypt_general_keyed<LOGN, MODE>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_gen);
-            hipLaunchKernelGGL((k_encode_encrypt_general_keyed<LOGN, MODE>), dim3(grid), dim3(G::THREADS), shmem_gen,
-                               st, P, T, A, *ring);
-            return hipGetLastError();
+            return launch(k_encode_encrypt_general_keyed<LOGN, MODE>, gen, block, shmem_gen, st, P, T, A, *ring);
         }
     }
-    (void)hipFuncSetAttribute((const void *)k_encode_encrypt<LOGN, MODE>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_fast);
-    hipLaunchKernelGGL((k_encode_encrypt<LOGN, MODE>), dim3(grid_fast), dim3(G::THREADS), shmem_fast, st, P, T,
-                       Af);
-    e = hipGetLastError();
+    e = launch(k_encode_encrypt<LOGN, MODE>, fast, block, shmem_fast, st, P, T, Af);
     if (e != hipSuccess) return e;
-    (void)hipFuncSetAttribute((const void *)k_encode_encrypt_general<LOGN, MODE>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_gen);
-    hipLaunchKernelGGL((k_encode_encrypt_general<LOGN, MODE>), dim3(grid), dim3(G::THREADS), shmem_gen, st, P,
-                       T, A);
-    return hipGetLastError();
-}
-
-template <int LOGN>
-static hipError_t launch_enc(const DevParams &P, const DevTables &T, const EncArgs &A, int mode,
-                             size_t B, hipStream_t st, const KeyRing *ring)
-{
-    if (!A.general) return hipErrorInvalidValue;   // the context's list of declined plaintexts
-    switch (mode)
-    {
-        case kModeSym: return launch_enc_mode<LOGN, kModeSym>(P, T, A, B, st, ring);
-        case kModeAsym: return launch_enc_mode<LOGN, kModeAsym>(P, T, A, B, st, ring);
-        default:
-            if (ring) return hipErrorInvalidValue;   // encode-only reads no key
-            return launch_enc_mode<LOGN, kModeEncodeOnly>(P, T, A, B, st, nullptr);
-    }
+    return launch(k_encode_encrypt_general<LOGN, MODE>, gen, block, shmem_gen, st, P, T, A);
 }
 
 hipError_t launch_encode_encrypt(const DevParams &P, const DevTables &T, const EncArgs &A, int mode,
                                  size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_enc<10>(P, T, A, mode, B, st, ring);
-        case 11: return launch_enc<11>(P, T, A, mode, B, st, ring);
-        case 12: return launch_enc<12>(P, T, A, mode, B, st, ring);
-        case 13: return launch_enc<13>(P, T, A, mode, B, st, ring);
-        case 14: return launch_enc<14>(P, T, A, mode, B, st, ring);
-        default: return hipErrorInvalidValue;
-    }
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        if (!A.general) return hipErrorInvalidValue;   // the context's list of declined plaintexts
+        switch (mode)
+        {
+            case kModeSym: return launch_enc_mode<L, kModeSym>(P, T, A, B, st, ring);
+            case kModeAsym: return launch_enc_mode<L, kModeAsym>(P, T, A, B, st, ring);
+            default:
+                if (ring) return hipErrorInvalidValue;   // encode-only reads no key
+                return launch_enc_mode<L, kModeEncodeOnly>(P, T, A, B, st, nullptr);
+        }
+    });
 }
 
 template <int LOGN, bool ADD_ERR>
@@ -1683,121 +1597,58 @@ static hipError_t launch_enc_rns_e(const DevParams &P, const DevTables &T, const
     if (!A.general) return hipErrorInvalidValue;   // the context's list of declined plaintexts
     hipError_t e = hipMemsetAsync(A.general, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
-    (void)hipFuncSetAttribute((const void *)k_encode_rns<LOGN, ADD_ERR>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL((k_encode_rns<LOGN, ADD_ERR>), dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, A);
-    e = hipGetLastError();
+    e = launch(k_encode_rns<LOGN, ADD_ERR>, dim3((unsigned)B), dim3(G::THREADS), shmem, st, P, T, A);
     if (e != hipSuccess) return e;
     // plaintexts with NaN / infinite values (normally none: the workgroups read a zero count and leave)
-    const unsigned cus  = P.num_cus ? P.num_cus : 256u;
-    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)cus);
-    (void)hipFuncSetAttribute((const void *)k_encode_rns_general<LOGN, ADD_ERR>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL((k_encode_rns_general<LOGN, ADD_ERR>), dim3(grid), dim3(G::THREADS), shmem, st, P, T, A);
-    return hipGetLastError();
-}
-
-template <int LOGN>
-static hipError_t launch_enc_rns(const DevParams &P, const DevTables &T, const EncArgs &A, bool add_err,
-                                 size_t B, hipStream_t st)
-{
-    return add_err ? launch_enc_rns_e<LOGN, true>(P, T, A, B, st) : launch_enc_rns_e<LOGN, false>(P, T, A, B, st);
+    const unsigned grid = (unsigned)std::min<size_t>(B, (size_t)cus_or_default(P.num_cus));
+    return launch(k_encode_rns_general<LOGN, ADD_ERR>, dim3(grid), dim3(G::THREADS), shmem, st, P, T, A);
 }
 
 hipError_t launch_encode_rns(const DevParams &P, const DevTables &T, const EncArgs &A, bool add_err,
                              size_t B, hipStream_t st)
 {
     if (B == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_enc_rns<10>(P, T, A, add_err, B, st);
-        case 11: return launch_enc_rns<11>(P, T, A, add_err, B, st);
-        case 12: return launch_enc_rns<12>(P, T, A, add_err, B, st);
-        case 13: return launch_enc_rns<13>(P, T, A, add_err, B, st);
-        case 14: return launch_enc_rns<14>(P, T, A, add_err, B, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int LOGN>
-static hipError_t launch_nf(const DevParams &P, const DevTables &T, const EncArgs &A, int mode, int j,
-                            size_t B, hipStream_t st, const KeyRing *ring)
-{
-    using G      = XformGeom<LOGN>;
-    size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
-    dim3 grid((unsigned)B), block(G::THREADS);
-    if (ring)
-    {
-        if (mode != kModeSym) return hipErrorInvalidValue;   // only the symmetric epilogue reads a key
-        (void)hipFuncSetAttribute((const void *)k_ntt_fuse_keyed<LOGN, kModeSym>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_ntt_fuse_keyed<LOGN, kModeSym>), grid, block, shmem, st, P, T, A, *ring, j);
-    }
-    else if (mode == kModeSym)
-    {
-        (void)hipFuncSetAttribute((const void *)k_ntt_fuse<LOGN, kModeSym>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_ntt_fuse<LOGN, kModeSym>), grid, block, shmem, st, P, T, A, j);
-    }
-    else
-    {
-        (void)hipFuncSetAttribute((const void *)k_ntt_fuse<LOGN, kModeEncodeOnly>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_ntt_fuse<LOGN, kModeEncodeOnly>), grid, block, shmem, st, P, T, A, j);
-    }
-    return hipGetLastError();
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        return add_err ? launch_enc_rns_e<L, true>(P, T, A, B, st) : launch_enc_rns_e<L, false>(P, T, A, B, st);
+    });
 }
 
 hipError_t launch_ntt_fuse(const DevParams &P, const DevTables &T, const EncArgs &A, int mode, int j,
                            size_t B, hipStream_t st, const KeyRing *ring)
 {
     if (B == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_nf<10>(P, T, A, mode, j, B, st, ring);
-        case 11: return launch_nf<11>(P, T, A, mode, j, B, st, ring);
-        case 12: return launch_nf<12>(P, T, A, mode, j, B, st, ring);
-        case 13: return launch_nf<13>(P, T, A, mode, j, B, st, ring);
-        case 14: return launch_nf<14>(P, T, A, mode, j, B, st, ring);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int LOGN>
-static hipError_t launch_ntt(const DevParams &P, const DevTables &T, int j, uint32_t *polys,
-                             uint32_t *pairs, size_t count, hipStream_t st)
-{
-    using G      = XformGeom<LOGN>;
-    size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
-    (void)hipFuncSetAttribute((const void *)k_ntt_polys<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)shmem);
-    hipLaunchKernelGGL((k_ntt_polys<LOGN>), dim3((unsigned)count), dim3(G::THREADS), shmem, st, P, T,
-                       j, polys, pairs);
-    return hipGetLastError();
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)B), block(G::THREADS);
+        const size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
+        if (ring)
+        {
+            if (mode != kModeSym) return hipErrorInvalidValue;   // only the symmetric epilogue reads a key
+            return launch(k_ntt_fuse_keyed<L, kModeSym>, grid, block, shmem, st, P, T, A, *ring, j);
+        }
+        if (mode == kModeSym) return launch(k_ntt_fuse<L, kModeSym>, grid, block, shmem, st, P, T, A, j);
+        return launch(k_ntt_fuse<L, kModeEncodeOnly>, grid, block, shmem, st, P, T, A, j);
+    });
 }
 
 hipError_t launch_ntt_polys(const DevParams &P, const DevTables &T, int j, uint32_t *polys,
                             uint32_t *pairs, size_t count, hipStream_t st)
 {
     if (count == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_ntt<10>(P, T, j, polys, pairs, count, st);
-        case 11: return launch_ntt<11>(P, T, j, polys, pairs, count, st);
-        case 12: return launch_ntt<12>(P, T, j, polys, pairs, count, st);
-        case 13: return launch_ntt<13>(P, T, j, polys, pairs, count, st);
-        case 14: return launch_ntt<14>(P, T, j, polys, pairs, count, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_logn(P.logn, [&](auto l) {
+        using G = XformGeom<decltype(l)::value>;
+        return launch(k_ntt_polys<decltype(l)::value>, dim3((unsigned)count), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, j, polys, pairs);
+    });
 }
 
 hipError_t launch_make_pairs(const uint32_t *vals, uint32_t *pairs, uint32_t q, size_t count,
                              hipStream_t st)
 {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_make_pairs, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, vals,
-                       pairs, q, (int)count);
-    return hipGetLastError();
+    return launch(k_make_pairs, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, vals, pairs, q, (int)count);
 }
 
 }  // namespace seamd

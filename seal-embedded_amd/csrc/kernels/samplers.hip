@@ -23,6 +23,7 @@
 
 #include "../se_types.h"
 #include "kernel_args.h"
+#include "launch.h"
 #include "keccak.cuh"
 #include "keccak_sync.cuh"
 #include "modarith.cuh"
@@ -1347,7 +1348,7 @@ static void chain_geometry(size_t B, unsigned num_cus, unsigned &threads, unsign
                            unsigned *master_waves = nullptr, bool allow_helpers = false,
                            size_t fill_to = 8)
 {
-    const size_t cus   = num_cus ? num_cus : 256;
+    const size_t cus   = cus_or_default(num_cus);
     const size_t waves = (B + 63) / 64;
     size_t w           = (waves + cus - 1) / cus;   // waves per CU if spread over all CUs
     if (w < 1) w = 1;
@@ -1361,15 +1362,6 @@ static void chain_geometry(size_t B, unsigned num_cus, unsigned &threads, unsign
     if (master_waves) *master_waves = (unsigned)w;
 }
 
-template <int LOGN>
-static hipError_t launch_uniform_wave(const DevParams &P, const UniformArgs &A, hipStream_t st)
-{
-    const unsigned waves_per_wg = 4;   // one per SIMD of the CU a workgroup lands on
-    hipLaunchKernelGGL((k_sample_uniform_wave<LOGN>), dim3((A.B + waves_per_wg - 1) / waves_per_wg),
-                       dim3(64 * waves_per_wg), 0, st, P, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_sample_uniform(const DevParams &P, const UniformArgs &A0, hipStream_t st)
 {
     if (A0.B == 0) return hipSuccess;
@@ -1377,15 +1369,11 @@ hipError_t launch_sample_uniform(const DevParams &P, const UniformArgs &A0, hipS
     // near 4 per SIMD -- tools/ubench5).  debug_flags 32 / 64 force the lane / the wave form (tests).
     if ((A0.B <= uniform_wave_limit(P.num_cus) && !(A0.debug_flags & 32)) || (A0.debug_flags & 64))
     {
-        switch (P.logn)
-        {
-            case 10: return launch_uniform_wave<10>(P, A0, st);
-            case 11: return launch_uniform_wave<11>(P, A0, st);
-            case 12: return launch_uniform_wave<12>(P, A0, st);
-            case 13: return launch_uniform_wave<13>(P, A0, st);
-            case 14: return launch_uniform_wave<14>(P, A0, st);
-            default: return hipErrorInvalidValue;
-        }
+        const unsigned waves_per_wg = 4;   // one per SIMD of the CU a workgroup lands on
+        return for_logn(P.logn, [&](auto l) {
+            return launch(k_sample_uniform_wave<decltype(l)::value>, dim3((A0.B + waves_per_wg - 1) / waves_per_wg),
+                          dim3(64 * waves_per_wg), 0, st, P, A0);
+        });
     }
     unsigned threads, grid_x, mw;
     size_t lds;
@@ -1398,30 +1386,12 @@ hipError_t launch_sample_uniform(const DevParams &P, const UniformArgs &A0, hipS
     // virtual ciphertexts, small_limit)
     if (A.prime_of && threads > 512) return hipErrorInvalidValue;
     dim3 grid(grid_x), block(threads);
-#define SEAMD_LAUNCH_UNIFORM_T(L, T)                                                             \
-    (void)hipFuncSetAttribute((const void *)k_sample_uniform<L, T>,                              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-    hipLaunchKernelGGL((k_sample_uniform<L, T>), grid, block, lds, st, P, A)
-#define SEAMD_LAUNCH_UNIFORM_P(L)                                                                \
-    (void)hipFuncSetAttribute((const void *)k_sample_uniform<L, 512, true>,                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-    hipLaunchKernelGGL((k_sample_uniform<L, 512, true>), grid, block, lds, st, P, A)
-#define SEAMD_LAUNCH_UNIFORM(L)                                                                  \
-    if (A.prime_of) { SEAMD_LAUNCH_UNIFORM_P(L); }                                               \
-    else if (threads > 512) { SEAMD_LAUNCH_UNIFORM_T(L, 1024); } else { SEAMD_LAUNCH_UNIFORM_T(L, 512); }
-    switch (P.logn)
-    {
-        case 10: SEAMD_LAUNCH_UNIFORM(10); break;
-        case 11: SEAMD_LAUNCH_UNIFORM(11); break;
-        case 12: SEAMD_LAUNCH_UNIFORM(12); break;
-        case 13: SEAMD_LAUNCH_UNIFORM(13); break;
-        case 14: SEAMD_LAUNCH_UNIFORM(14); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SEAMD_LAUNCH_UNIFORM
-#undef SEAMD_LAUNCH_UNIFORM_P
-#undef SEAMD_LAUNCH_UNIFORM_T
-    return hipGetLastError();
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        if (A.prime_of) return launch(k_sample_uniform<L, 512, true>, grid, block, lds, st, P, A);
+        if (threads > 512) return launch(k_sample_uniform<L, 1024>, grid, block, lds, st, P, A);
+        return launch(k_sample_uniform<L, 512>, grid, block, lds, st, P, A);
+    });
 }
 
 // ---- staged form (one prime per launch; se_context.cpp runs k_candidates on a stream of its own) ----
@@ -1430,35 +1400,23 @@ hipError_t launch_uniform_bulk_pair(const DevParams &P, const UniformArgs &A, hi
     if (A.B == 0) return hipSuccess;
     if (!A.nrej || A.prime_hi != A.prime_lo + 1) return hipErrorInvalidValue;
     // like chain_geometry: workgroups of w waves, one per CU (84 KiB of reserved LDS), w <= 8 pair waves
-    const size_t cus   = P.num_cus ? P.num_cus : 256;
+    const size_t cus   = cus_or_default(P.num_cus);
     const size_t waves = (2 * (size_t)A.B + 63) / 64;
     size_t w           = (waves + cus - 1) / cus;
     if (w < 1) w = 1;
     if (w > 8) w = 8;
     const unsigned threads = (unsigned)(w * 64), grid = (unsigned)((2 * (size_t)A.B + threads - 1) / threads);
     const size_t lds = 84 * 1024;
-#define SEAMD_LAUNCH_PAIR(L)                                                                                    \
-    (void)hipFuncSetAttribute((const void *)k_bulk_pair<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((k_bulk_pair<L>), dim3(grid), dim3(threads), lds, st, P, A)
-    switch (P.logn)
-    {
-        case 10: SEAMD_LAUNCH_PAIR(10); break;
-        case 11: SEAMD_LAUNCH_PAIR(11); break;
-        case 12: SEAMD_LAUNCH_PAIR(12); break;
-        case 13: SEAMD_LAUNCH_PAIR(13); break;
-        case 14: SEAMD_LAUNCH_PAIR(14); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SEAMD_LAUNCH_PAIR
-    return hipGetLastError();
+    return for_logn(P.logn, [&](auto l) {
+        return launch(k_bulk_pair<decltype(l)::value>, dim3(grid), dim3(threads), lds, st, P, A);
+    });
 }
 
 hipError_t launch_uniform_candidates(const UniformArgs &A, hipStream_t st)
 {
     const size_t total = (size_t)A.B * A.spec_cap;
     if (total == 0 || !A.spec) return hipSuccess;
-    hipLaunchKernelGGL(k_candidates, dim3((unsigned)((total + kCbdThreads - 1) / kCbdThreads)), dim3(kCbdThreads), 0, st, A);
-    return hipGetLastError();
+    return launch(k_candidates, dim3((unsigned)((total + kCbdThreads - 1) / kCbdThreads)), dim3(kCbdThreads), 0, st, A);
 }
 
 hipError_t launch_uniform_resolve(const DevParams &P, const UniformArgs &A, hipStream_t st)
@@ -1471,29 +1429,19 @@ hipError_t launch_uniform_resolve(const DevParams &P, const UniformArgs &A, hipS
     UniformArgs H   = A;
     H.master_waves  = 1;
     // with a flagged list: one workgroup per CU walks it (normally it is empty or a handful of entries)
-    const dim3 hgrid(A.flagged ? std::min<unsigned>((unsigned)((A.B + 3) / 4), P.num_cus ? P.num_cus : 256u) : grid.x);
-#define SEAMD_LAUNCH_RESOLVE(L)                                              \
-    hipLaunchKernelGGL((k_resolve_light<L>), grid, block, 0, st, P, A);      \
-    hipLaunchKernelGGL((k_resolve_wave<L>), hgrid, block, 0, st, P, H)
-    switch (P.logn)
-    {
-        case 10: SEAMD_LAUNCH_RESOLVE(10); break;
-        case 11: SEAMD_LAUNCH_RESOLVE(11); break;
-        case 12: SEAMD_LAUNCH_RESOLVE(12); break;
-        case 13: SEAMD_LAUNCH_RESOLVE(13); break;
-        case 14: SEAMD_LAUNCH_RESOLVE(14); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SEAMD_LAUNCH_RESOLVE
-    return hipGetLastError();
+    const dim3 hgrid(A.flagged ? std::min<unsigned>((unsigned)((A.B + 3) / 4), cus_or_default(P.num_cus)) : grid.x);
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L    = decltype(l)::value;
+        const hipError_t e = launch(k_resolve_light<L>, grid, block, 0, st, P, A);
+        return e != hipSuccess ? e : launch(k_resolve_wave<L>, hgrid, block, 0, st, P, H);
+    });
 }
 
 hipError_t launch_sample_cbd(const CbdArgs &A, hipStream_t st)
 {
     size_t total = (size_t)A.B * A.blocks_per_ct;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sample_cbd, dim3((unsigned)((total + kCbdThreads - 1) / kCbdThreads)), dim3(kCbdThreads), 0, st, A);
-    return hipGetLastError();
+    return launch(k_sample_cbd, dim3((unsigned)((total + kCbdThreads - 1) / kCbdThreads)), dim3(kCbdThreads), 0, st, A);
 }
 
 hipError_t launch_sample_ternary(const TernaryArgs &A, hipStream_t st)
@@ -1511,37 +1459,26 @@ hipError_t launch_sample_ternary(const TernaryArgs &A, hipStream_t st)
         const uint32_t nblocks = (A.n + 95) / 96;
         const double mean      = (double)A.n * (2.0 / 254.0);
         uint32_t W = (A.debug_flags & 4096) ? nblocks + 2 : nblocks + (uint32_t)(mean + 4.7 * sqrt(mean) + 1.0);
-        if (W <= kTernWg && (A.n <= 4096 || A.B <= (size_t)256 * (A.num_cus ? A.num_cus : 256u)))
+        if (W <= kTernWg && (A.n <= 4096 || A.B <= (size_t)256 * cus_or_default(A.num_cus)))
         {
             const uint32_t cpw = std::min<uint32_t>(kTernWg / W, 15u);
             if (!(A.debug_flags & 4096)) W = kTernWg / cpw;
-            hipLaunchKernelGGL(k_sample_ternary_window, dim3((A.B + cpw - 1) / cpw), dim3(kTernWg), 0, st, A, W, cpw);
-            hipLaunchKernelGGL(k_sample_ternary_redo, dim3((A.B + 63) / 64), dim3(64), 0, st, A);
-            return hipGetLastError();
+            const hipError_t e =
+                launch(k_sample_ternary_window, dim3((A.B + cpw - 1) / cpw), dim3(kTernWg), 0, st, A, W, cpw);
+            return e != hipSuccess ? e : launch(k_sample_ternary_redo, dim3((A.B + 63) / 64), dim3(64), 0, st, A);
         }
     }
     if (A.B <= uniform_wave_limit(A.num_cus) && !(A.debug_flags & 32))
     {
         // a handful of chains: one wave per ciphertext (see k_sample_uniform_wave)
-        hipLaunchKernelGGL(k_sample_ternary_wave, dim3((A.B + 3) / 4), dim3(256), 0, st, A);
-        return hipGetLastError();
+        return launch(k_sample_ternary_wave, dim3((A.B + 3) / 4), dim3(256), 0, st, A);
     }
     unsigned threads, grid_x;
     size_t lds;
     chain_geometry(A.B, A.num_cus, threads, grid_x, lds);
-    if (threads > 512)
-    {
-        (void)hipFuncSetAttribute((const void *)k_sample_ternary<1024>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_sample_ternary<1024>, dim3(grid_x), dim3(threads), lds, st, A);
-    }
-    else   // 167 VGPRs, no spill (1.20 -> 1.06 ms per 65 536)
-    {
-        (void)hipFuncSetAttribute((const void *)k_sample_ternary<512>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_sample_ternary<512>, dim3(grid_x), dim3(threads), lds, st, A);
-    }
-    return hipGetLastError();
+    if (threads > 512) return launch(k_sample_ternary<1024>, dim3(grid_x), dim3(threads), lds, st, A);
+    // 167 VGPRs, no spill (1.20 -> 1.06 ms per 65 536)
+    return launch(k_sample_ternary<512>, dim3(grid_x), dim3(threads), lds, st, A);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1612,26 +1549,21 @@ hipError_t launch_spec_setup(const SpecPlan &S, const uint8_t *seeds, uint8_t *s
                              uint8_t *prime_v, hipStream_t st)
 {
     if (S.total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spec_setup, dim3((S.total + 255) / 256), dim3(256), 0, st, S, seeds, seeds_v, ctr_v,
-                       prime_v);
-    return hipGetLastError();
+    return launch(k_spec_setup, dim3((S.total + 255) / 256), dim3(256), 0, st, S, seeds, seeds_v, ctr_v, prime_v);
 }
 
 hipError_t launch_spec_select(const SpecPlan &S, uint32_t n, uint64_t *ctr0, const uint64_t *ctrout_v,
                               const uint32_t *rows, uint32_t *c1, uint32_t *fail, hipStream_t st)
 {
     if (S.B == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spec_select, dim3(S.B), dim3(256), 0, st, S, n, ctr0, ctrout_v, rows, c1, fail);
-    return hipGetLastError();
+    return launch(k_spec_select, dim3(S.B), dim3(256), 0, st, S, n, ctr0, ctrout_v, rows, c1, fail);
 }
 
 hipError_t launch_prng_blocks(const uint8_t *seeds, const uint64_t *ctrs, uint8_t *out,
                               uint32_t outlen, uint32_t count, hipStream_t st)
 {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_prng_blocks, dim3((count + 63) / 64), dim3(64), 0, st, seeds, ctrs, out,
-                       outlen, count);
-    return hipGetLastError();
+    return launch(k_prng_blocks, dim3((count + 63) / 64), dim3(64), 0, st, seeds, ctrs, out, outlen, count);
 }
 
 }  // namespace seamd

@@ -18,6 +18,7 @@
 
 #include "../se_types.h"
 #include "kernel_args.h"
+#include "launch.h"
 #include "transform.cuh"
 
 namespace seamd {
@@ -123,31 +124,15 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_fft_polys(DevParam
     if (first_bad != 0xFFFFFFFFu) atomicMin(A.fail_idx + b, first_bad);
 }
 
-template <int LOGN>
-static hipError_t launch_fft_n(const DevParams &P, const DevTables &T, const FftArgs &A, size_t count,
-                               hipStream_t st)
-{
-    using G      = XformGeom<LOGN>;
-    size_t shmem = (size_t)G::SLOTS * sizeof(double);
-    (void)hipFuncSetAttribute((const void *)k_fft_polys<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem);
-    hipLaunchKernelGGL((k_fft_polys<LOGN>), dim3((unsigned)count), dim3(G::THREADS), shmem, st, P, T, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_fft_polys(const DevParams &P, const DevTables &T, const FftArgs &A, size_t count,
                             hipStream_t st)
 {
     if (count == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_fft_n<10>(P, T, A, count, st);
-        case 11: return launch_fft_n<11>(P, T, A, count, st);
-        case 12: return launch_fft_n<12>(P, T, A, count, st);
-        case 13: return launch_fft_n<13>(P, T, A, count, st);
-        case 14: return launch_fft_n<14>(P, T, A, count, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_logn(P.logn, [&](auto l) {
+        using G = XformGeom<decltype(l)::value>;
+        return launch(k_fft_polys<decltype(l)::value>, dim3((unsigned)count), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(double), st, P, T, A);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -180,9 +165,8 @@ hipError_t launch_reduce_poly(const DevParams &P, int j, const int64_t *pte, con
                               bool add, size_t total, hipStream_t st)
 {
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_reduce_poly, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, j, pte, e,
-                       out, add ? 1 : 0, total);
-    return hipGetLastError();
+    return launch(k_reduce_poly, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, j, pte, e, out,
+                  add ? 1 : 0, total);
 }
 
 // sample_add_poly_cbd_generic_inpl_prng_16's "+=" (sample.c:347-356): m[i] += e[i]
@@ -195,8 +179,7 @@ __global__ void k_add_small(int64_t *m, const int8_t *e, size_t total)
 hipError_t launch_add_small(int64_t *m, const int8_t *e, size_t total, hipStream_t st)
 {
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_add_small, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m, e, total);
-    return hipGetLastError();
+    return launch(k_add_small, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m, e, total);
 }
 
 // set_small_poly_idx packing (sample.c:61-87): four 2-bit codes per byte, first coefficient in the
@@ -212,9 +195,8 @@ __global__ void k_pack_ternary(const int8_t *codes, uint8_t *packed, size_t tota
 hipError_t launch_pack_ternary(const int8_t *codes, uint8_t *packed, size_t total_bytes, hipStream_t st)
 {
     if (total_bytes == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pack_ternary, dim3((unsigned)((total_bytes + 255) / 256)), dim3(256), 0, st, codes,
-                       packed, total_bytes);
-    return hipGetLastError();
+    return launch(k_pack_ternary, dim3((unsigned)((total_bytes + 255) / 256)), dim3(256), 0, st, codes, packed,
+                  total_bytes);
 }
 
 // convert_poly_ternary (sample.c:138-148): entries > 1 (i.e. q_prev - 1) become q - 1
@@ -237,8 +219,7 @@ __global__ void k_ternary_words(const uint32_t *in, uint32_t *out, uint32_t *nre
 hipError_t launch_ternary_words(const uint32_t *in, uint32_t *out, uint32_t *nrej, uint32_t q, uint32_t n, int op,
                                 hipStream_t st)
 {
-    hipLaunchKernelGGL(k_ternary_words, dim3((n + 255) / 256), dim3(256), 0, st, in, out, nrej, q, n, op);
-    return hipGetLastError();
+    return launch(k_ternary_words, dim3((n + 255) / 256), dim3(256), 0, st, in, out, nrej, q, n, op);
 }
 
 __global__ void k_expand_ternary(const uint8_t *packed, uint32_t *out, uint32_t q, uint32_t n)
@@ -249,8 +230,7 @@ __global__ void k_expand_ternary(const uint8_t *packed, uint32_t *out, uint32_t 
 
 hipError_t launch_expand_ternary(const uint8_t *packed, uint32_t *out, uint32_t q, uint32_t n, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_expand_ternary, dim3((n + 255) / 256), dim3(256), 0, st, packed, out, q, n);
-    return hipGetLastError();
+    return launch(k_expand_ternary, dim3((n + 255) / 256), dim3(256), 0, st, packed, out, q, n);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -446,59 +426,36 @@ hipError_t launch_word_ops(const DevParams &P, int j, int op, const uint64_t *a,
                            const uint64_t *c, uint32_t *out, size_t count, hipStream_t st)
 {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_word_ops, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, P, j, op, a, b, c,
-                       out, count);
-    return hipGetLastError();
+    return launch(k_word_ops, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, P, j, op, a, b, c, out,
+                  count);
 }
 
 template <int LOGN>
-static hipError_t launch_lower_n(const DevParams &P, const DevTables &T, const LowerSymArgs *S,
-                                 const LowerAsymArgs *Y, size_t count, hipStream_t st)
-{
-    using G      = XformGeom<LOGN>;
-    size_t shmem = (size_t)G::SLOTS * sizeof(uint32_t);
-    if (S)
-    {
-        (void)hipFuncSetAttribute((const void *)k_lower_sym_prime<LOGN>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_lower_sym_prime<LOGN>), dim3((unsigned)count), dim3(G::THREADS), shmem, st, P,
-                           T, *S);
-    }
-    else
-    {
-        (void)hipFuncSetAttribute((const void *)k_lower_asym_prime<LOGN>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((k_lower_asym_prime<LOGN>), dim3((unsigned)count), dim3(G::THREADS), shmem, st,
-                           P, T, *Y);
-    }
-    return hipGetLastError();
-}
+static auto lower_kernel(const LowerSymArgs &) { return k_lower_sym_prime<LOGN>; }
+template <int LOGN>
+static auto lower_kernel(const LowerAsymArgs &) { return k_lower_asym_prime<LOGN>; }
 
-static hipError_t launch_lower(const DevParams &P, const DevTables &T, const LowerSymArgs *S,
-                               const LowerAsymArgs *Y, size_t count, hipStream_t st)
+template <class Args>
+static hipError_t launch_lower(const DevParams &P, const DevTables &T, const Args &A, size_t count, hipStream_t st)
 {
     if (count == 0) return hipSuccess;
-    switch (P.logn)
-    {
-        case 10: return launch_lower_n<10>(P, T, S, Y, count, st);
-        case 11: return launch_lower_n<11>(P, T, S, Y, count, st);
-        case 12: return launch_lower_n<12>(P, T, S, Y, count, st);
-        case 13: return launch_lower_n<13>(P, T, S, Y, count, st);
-        case 14: return launch_lower_n<14>(P, T, S, Y, count, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_logn(P.logn, [&](auto l) {
+        using G = XformGeom<decltype(l)::value>;
+        return launch(lower_kernel<decltype(l)::value>(A), dim3((unsigned)count), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
 }
 
 hipError_t launch_lower_sym_prime(const DevParams &P, const DevTables &T, const LowerSymArgs &A, size_t count,
                                   hipStream_t st)
 {
-    return launch_lower(P, T, &A, nullptr, count, st);
+    return launch_lower(P, T, A, count, st);
 }
 
 hipError_t launch_lower_asym_prime(const DevParams &P, const DevTables &T, const LowerAsymArgs &A,
                                    size_t count, hipStream_t st)
 {
-    return launch_lower(P, T, nullptr, &A, count, st);
+    return launch_lower(P, T, A, count, st);
 }
 
 }  // namespace seamd

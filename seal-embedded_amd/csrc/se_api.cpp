@@ -352,8 +352,14 @@ int se_amd_sample_ternary_device(se_amd_ctx *ctx, const uint8_t *d_seeds, size_t
 {
     if (!ctx || !d_seeds || !d_codes) return SE_ERR_INVALD_ARGUMENT;
     SEAMD_HIP(hipSetDevice(ctx->c.device));
-    seamd::TernaryArgs ta{d_seeds, d_codes, d_ctr_out, (uint32_t)ctx->c.hp.n, (uint32_t)B, nullptr,
-                          (uint32_t)ctx->c.num_cus, ctx->c.debug_flags};
+    seamd::TernaryArgs ta{};
+    ta.seeds       = d_seeds;
+    ta.codes       = d_codes;
+    ta.ctr_out     = d_ctr_out;
+    ta.n           = (uint32_t)ctx->c.hp.n;
+    ta.B           = (uint32_t)B;
+    ta.num_cus     = (uint32_t)ctx->c.num_cus;
+    ta.debug_flags = ctx->c.debug_flags;
     SEAMD_HIP(seamd::launch_sample_ternary(ta, as_stream(stream)));
     return SE_SUCCESS;
 }
@@ -363,7 +369,12 @@ int se_amd_sample_cbd_device(se_amd_ctx *ctx, const uint8_t *d_seeds, const uint
 {
     if (!ctx || !d_seeds || !d_out) return SE_ERR_INVALD_ARGUMENT;
     SEAMD_HIP(hipSetDevice(ctx->c.device));
-    seamd::CbdArgs ca{d_seeds, d_ctr_base, d_out, (uint32_t)blocks_per_ct, (uint32_t)B};
+    seamd::CbdArgs ca{};
+    ca.seeds         = d_seeds;
+    ca.ctr_base      = d_ctr_base;
+    ca.out           = d_out;
+    ca.blocks_per_ct = (uint32_t)blocks_per_ct;
+    ca.B             = (uint32_t)B;
     SEAMD_HIP(seamd::launch_sample_cbd(ca, as_stream(stream)));
     return SE_SUCCESS;
 }

@@ -231,6 +231,48 @@ int Context::end_call(hipStream_t st, int rc)
     return 0;
 }
 
+// body() between begin_call and end_call; the caller holds `mu`.  body returns 0 or an error code and may leave early
+// (SEAMD_HIP): end_call runs either way.
+template <class Body>
+int Context::call_scope(hipStream_t st, Body &&body)
+{
+    if (int rc = begin_call(st)) return rc;
+    return end_call(st, body());
+}
+
+// A keyed call inside a call scope: sanitise the caller's indices (key_prologue), run body(ring) with the clamped ones
+// over the K keys at k0 / k1, then give the out-of-range records the status and zero rows of `ra` (ra.bad is set here).
+template <class Body>
+int Context::keyed_call(const uint32_t *d_key_idx, size_t K, const uint32_t *k0, const uint32_t *k1, KeyRejectArgs ra,
+                        size_t B, hipStream_t st, Body &&body)
+{
+    return call_scope(st, [&]() -> int {
+        if (int rc = key_prologue(d_key_idx, K, B, st)) return rc;
+        KeyRing ring{};
+        ring.k0     = k0;
+        ring.k1     = k1;
+        ring.idx    = d_kidx;
+        ring.stride = (size_t)2 * hp.nprimes * hp.n;
+        if (int rc = body(ring)) return rc;
+        ra.bad = d_kbad;
+        SEAMD_HIP(launch_key_reject(dp, ra, B, st));
+        return 0;
+    });
+}
+
+// What every launch of the uniform sampler takes from the context; the caller adds seeds, counters, output, B and the
+// prime range.
+UniformArgs Context::uniform_args() const
+{
+    UniformArgs ua{};
+    ua.rej_list    = d_rej;
+    ua.rej_cap     = rej_cap;
+    ua.spec        = d_spec;
+    ua.spec_cap    = spec_cap;
+    ua.debug_flags = debug_flags;
+    return ua;
+}
+
 int Context::fetch_asym_randomness(int8_t *ucodes, int8_t *e1)
 {
     std::lock_guard<std::mutex> lk(mu);
@@ -418,13 +460,26 @@ int Context::gen_public_key(const uint8_t *sk_packed, const uint8_t *pk_seed, co
     SEAMD_HIP(hipMemcpy(d_seeds, ep_seed, 64, hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_seeds + 64, pk_seed, 64, hipMemcpyHostToDevice));
     uint32_t *d_p0 = d_c, *d_p1 = d_c + (size_t)np * n;
-    CbdArgs ca{d_seeds, nullptr, d_err, n / 16, 1};
+    CbdArgs ca{};
+    ca.seeds         = d_seeds;
+    ca.out           = d_err;
+    ca.blocks_per_ct = n / 16;
+    ca.B             = 1;
     SEAMD_HIP(launch_sample_cbd(ca, nullptr));
     SEAMD_HIP(launch_reduce_small(dp, d_err, d_p0, 1, nullptr));
-    EncArgs ea{nullptr, nullptr, nullptr, d_p0, d_p1, nullptr, nullptr, nullptr};
+    EncArgs ea{};
+    ea.c0 = d_p0;
+    ea.c1 = d_p1;
+    UniformArgs ua = uniform_args();
+    ua.seeds       = d_seeds + 64;
+    ua.out         = d_p1;
+    ua.B           = 1;
+    ua.out_primes  = np;
+    ua.debug_flags = 0;   // the default forms, whatever the context's test flags
     for (uint32_t j = 0; j < np; j++)
     {
-        UniformArgs ua{d_seeds + 64, nullptr, nullptr, d_p1, d_rej, rej_cap, 1, j, j + 1, np, d_spec, spec_cap, 0, 0};
+        ua.prime_lo = j;
+        ua.prime_hi = j + 1;
         SEAMD_HIP(launch_sample_uniform(dp, ua, nullptr));
         SEAMD_HIP(launch_ntt_fuse(dp, dt, ea, kModeSym, (int)j, 1, nullptr));
     }
@@ -475,20 +530,42 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
         SEAMD_HIP(hipMemcpy(keys, sk_in, K * (n / 4), hipMemcpyHostToDevice));
     else
     {
-        TernaryArgs ta{d_sk_seeds, codes, nullptr, n, (uint32_t)K, nullptr, (uint32_t)num_cus};
+        TernaryArgs ta{};
+        ta.seeds   = d_sk_seeds;
+        ta.codes   = codes;
+        ta.n       = n;
+        ta.B       = (uint32_t)K;
+        ta.num_cus = (uint32_t)num_cus;
         SEAMD_HIP(launch_sample_ternary(ta, nullptr));
         SEAMD_HIP(launch_pack_ternary(codes, keys, K * (n / 4), nullptr));
     }
-    CbdArgs ca{d_ep_seeds, nullptr, ep, n / 16, (uint32_t)K};
+    CbdArgs ca{};
+    ca.seeds         = d_ep_seeds;
+    ca.out           = ep;
+    ca.blocks_per_ct = n / 16;
+    ca.B             = (uint32_t)K;
     SEAMD_HIP(launch_sample_cbd(ca, nullptr));
+    UniformArgs ua = uniform_args();
+    ua.seeds       = d_pk_seeds;
+    ua.out         = pk1;
+    ua.B           = (uint32_t)K;
+    ua.out_primes  = np;
+    LowerSymArgs sa{};
+    sa.s_small   = keys;
+    sa.ep        = ep;
+    sa.ntt_pte   = tmp;
+    sa.s_stride  = n / 4;
+    sa.a_stride  = np * n;
+    sa.c0_stride = np * n;
     for (uint32_t j = 0; j < np; j++)
     {
         // a_j for every key, counter 0 (gen_pk re-seeds per prime, ckks_asym.c:163), into pk1[:, j]
-        UniformArgs ua{d_pk_seeds, nullptr, nullptr, pk1, d_rej, rej_cap, (uint32_t)K, j, j + 1, np,
-                       d_spec,     spec_cap, 0,      debug_flags};
+        ua.prime_lo = j;
+        ua.prime_hi = j + 1;
         SEAMD_HIP(launch_sample_uniform(dp, ua, nullptr));
-        LowerSymArgs sa{keys, nullptr, ep, pk1 + (size_t)j * n, pk0 + (size_t)j * n, tmp, nullptr, (int)j, n / 4,
-                        np * n, np * n};
+        sa.a  = pk1 + (size_t)j * n;
+        sa.c0 = pk0 + (size_t)j * n;
+        sa.j  = (int)j;
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
     }
     SEAMD_HIP(hipDeviceSynchronize());
@@ -535,10 +612,9 @@ int Context::encrypt_sym(const float *d_values, size_t B, const uint8_t *d_share
                          uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st);
-    return end_call(st, rc);
+    return call_scope(st, [&] {
+        return encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st);
+    });
 }
 
 // Seed-compressed form: `a` goes to context scratch instead of a caller slab.  The scratch is grown, and
@@ -555,10 +631,9 @@ int Context::encrypt_sym_seeded(const float *d_values, size_t B, const uint8_t *
         SEAMD_HIP(hipDeviceSynchronize());   // earlier calls may still read the old slab
         SEAMD_HIP(d_a.grow(B * hp.nprimes * hp.n));
     }
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_a, nullptr, nullptr, d_status, st);
-    return end_call(st, rc);
+    return call_scope(st, [&] {
+        return encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_a, nullptr, nullptr, d_status, st);
+    });
 }
 
 int Context::encrypt_asym(const float *d_values, size_t B, const uint8_t *d_seeds, uint32_t *d_c0,
@@ -566,10 +641,9 @@ int Context::encrypt_asym(const float *d_values, size_t B, const uint8_t *d_seed
                           hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = encrypt_asym_impl(d_values, B, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st);
-    return end_call(st, rc);
+    return call_scope(st, [&] {
+        return encrypt_asym_impl(d_values, B, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st);
+    });
 }
 
 int Context::sample_uniform(const uint8_t *d_seeds, const uint64_t *d_ctr_in, size_t B, uint32_t *d_out,
@@ -577,18 +651,19 @@ int Context::sample_uniform(const uint8_t *d_seeds, const uint64_t *d_ctr_in, si
 {
     if (B == 0) return 0;
     std::lock_guard<std::mutex> lk(mu);
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = ensure_scratch(B);
-    if (rc == 0)
-    {
-        const uint32_t np = (uint32_t)hp.nprimes;
-        UniformArgs ua{d_seeds, d_ctr_in, d_ctr_out, d_out, d_rej, rej_cap, (uint32_t)B, 0, np, np,
-                       d_spec,  spec_cap, 0,         debug_flags};
-        hipError_t e = launch_sample_uniform(dp, ua, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_sample_uniform");
-    }
-    return end_call(st, rc);
+    return call_scope(st, [&]() -> int {
+        if (int rc = ensure_scratch(B)) return rc;
+        UniformArgs ua = uniform_args();
+        ua.seeds       = d_seeds;
+        ua.ctr_in      = d_ctr_in;
+        ua.ctr_out     = d_ctr_out;
+        ua.out         = d_out;
+        ua.B           = (uint32_t)B;
+        ua.prime_hi    = (uint32_t)hp.nprimes;
+        ua.out_primes  = (uint32_t)hp.nprimes;
+        SEAMD_HIP(launch_sample_uniform(dp, ua, st));
+        return 0;
+    });
 }
 
 int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_share_seeds,
@@ -604,19 +679,36 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
     if (B == 0) return 0;
     if (!d_values || !d_share_seeds || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
     SEAMD_HIP(hipSetDevice(device));
-    {
-        // a handful of ciphertexts: latency path (all primes' samplers at once, prime speculation)
-        SpecPlan plan;
-        if (split_mode == 2 && small_batch_plan(B, plan, ring != nullptr) && speculation_pays(B, plan))
-            return encrypt_sym_small(plan, d_values, d_share_seeds, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte,
-                                     d_status, st, ring);
-    }
-    int rc = ensure_scratch(B);
+    // a handful of ciphertexts: latency path (all primes' samplers at once, prime speculation)
+    SpecPlan plan;
+    const bool small = split_mode == 2 && small_batch_plan(B, plan, ring != nullptr) && speculation_pays(B, plan);
+    // ... whose virtual ciphertexts need reject lists / candidates too
+    int rc = ensure_scratch(B, small ? B + plan.total : 0);
     if (rc) return rc;
     const uint32_t n = (uint32_t)hp.n, np = (uint32_t)hp.nprimes;
 
-    CbdArgs ca{d_seeds, nullptr, d_err, n / 16, (uint32_t)B};
-    EncArgs ea{d_values, d_err, nullptr, d_c0, d_c1, d_ntt_pte, d_pte, d_status, d_general, d_compact};
+    CbdArgs ca{};
+    ca.seeds         = d_seeds;
+    ca.out           = d_err;
+    ca.blocks_per_ct = n / 16;
+    ca.B             = (uint32_t)B;
+    EncArgs ea{};
+    ea.values  = d_values;
+    ea.err     = d_err;
+    ea.c0      = d_c0;
+    ea.c1      = d_c1;
+    ea.ntt_pte = d_ntt_pte;
+    ea.pte     = d_pte;
+    ea.status  = d_status;
+    ea.general = d_general;
+    ea.compact = d_compact;
+    // a from the shareable seed, written straight into c1 (ckks_sym.c:220)
+    UniformArgs ua = uniform_args();
+    ua.seeds       = d_share_seeds;
+    ua.out         = d_c1;
+    ua.B           = (uint32_t)B;
+    ua.out_primes  = np;
+    if (small) return encrypt_sym_small(plan, ca, ea, ua, st, ring);
 
     const size_t chain_waves_per_cu = ((B + 63) / 64 + (size_t)num_cus - 1) / (size_t)num_cus;
     const bool split = split_mode == 1 || (split_mode == 2 && (hp.n >= 8192 || chain_waves_per_cu < 4));
@@ -633,8 +725,7 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
         SEAMD_HIP(launch_sample_cbd(ca, cbd_stream));
         stage_end(cbd_stream);
         if (overlap) SEAMD_HIP(hipEventRecord(ev_join, aux_stream));
-        UniformArgs ua{d_share_seeds, nullptr, nullptr, d_c1, d_rej, rej_cap, (uint32_t)B, 0, np, np,
-                       d_spec, spec_cap, 0, debug_flags};
+        ua.prime_hi = np;   // all primes in one launch
         stage_begin(1, st);
         SEAMD_HIP(launch_sample_uniform(dp, ua, st));
         stage_end(st);
@@ -692,11 +783,14 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
     }
     for (uint32_t j = 0; j < np; j++)
     {
-        // a_j from the shareable seed, written straight into c1 (ckks_sym.c:220)
-        UniformArgs ua{d_share_seeds, j ? d_ctr : nullptr, d_ctr, d_c1, d_rej, rej_cap, (uint32_t)B,
-                       j,             j + 1,               np,    d_spec,      spec_cap,
-                       0,             debug_flags,         nullptr, 0, fill, nullptr, d_nrej,
-                       staged ? d_flagged : nullptr};
+        UniformArgs uj = ua;   // a_j; the counter is carried from prime to prime in d_ctr
+        uj.ctr_in      = j ? d_ctr.get() : nullptr;
+        uj.ctr_out     = d_ctr;
+        uj.prime_lo    = j;
+        uj.prime_hi    = j + 1;
+        uj.helper_fill = fill;
+        uj.nrej        = d_nrej;
+        uj.flagged     = staged ? d_flagged.get() : nullptr;
         if (staged)
         {
             // Candidates per ciphertext: here they are pure throughput work beside the chains, and a
@@ -707,23 +801,23 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
                 const double p_rej = (double)(0u - dp.bound[j]) / 4294967296.0;
                 const double mean  = (double)hp.n * p_rej / (1.0 - p_rej);
                 const uint32_t cap = ((uint32_t)(mean + 1.5 * sqrt((double)hp.n * p_rej) + 15.0)) & ~15u;
-                if (cap < ua.spec_cap) ua.spec_cap = cap ? cap : 16u;
+                if (cap < uj.spec_cap) uj.spec_cap = cap ? cap : 16u;
             }
             //   C : (start counters of prime j known) k_candidates_j ───────────┐
             //   S : k_bulk_pair_j ─────────────────────────────────── (wait C) k_resolve_wave_j
             SEAMD_HIP(hipStreamWaitEvent(cand_stream, j ? ev_prime[j - 1] : ev_fork, 0));
-            SEAMD_HIP(launch_uniform_candidates(ua, cand_stream));
+            SEAMD_HIP(launch_uniform_candidates(uj, cand_stream));
             SEAMD_HIP(hipEventRecord(ev_cand[j], cand_stream));
             stage_begin(1, st);
-            SEAMD_HIP(launch_uniform_bulk_pair(dp, ua, st));
+            SEAMD_HIP(launch_uniform_bulk_pair(dp, uj, st));
             SEAMD_HIP(hipStreamWaitEvent(st, ev_cand[j], 0));
-            SEAMD_HIP(launch_uniform_resolve(dp, ua, st));
+            SEAMD_HIP(launch_uniform_resolve(dp, uj, st));
             stage_end(st);
         }
         else
         {
             stage_begin(1, st);
-            SEAMD_HIP(launch_sample_uniform(dp, ua, st));
+            SEAMD_HIP(launch_sample_uniform(dp, uj, st));
             stage_end(st);
         }
         if (late_encode && j == 0)
@@ -815,18 +909,12 @@ bool Context::speculation_pays(size_t B, const SpecPlan &plan) const
     return spec < 0.9 * plain;
 }
 
-int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, const uint8_t *d_share_seeds,
-                               const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1,
-                               uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st,
-                               const KeyRing *ring)
+int Context::encrypt_sym_small(const SpecPlan &plan, const CbdArgs &ca, const EncArgs &ea, const UniformArgs &ua,
+                               hipStream_t st, const KeyRing *ring)
 {
-    if (!d_values || !d_share_seeds || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
-    SEAMD_HIP(hipSetDevice(device));
     const size_t B     = plan.B;
     const uint32_t n   = (uint32_t)hp.n, np = (uint32_t)hp.nprimes;
     const size_t total = plan.total;
-    int rc             = ensure_scratch(B, B + total);  // reject lists / candidates of the virtual ciphertexts too
-    if (rc) return rc;
     if (d_sp_seeds.size() < total * 64 || d_sp_ctr.size() < total || d_sp_ctrout.size() < total ||
         d_sp_rows.size() < total * n || d_sp_prime.size() < total)
     {
@@ -842,9 +930,6 @@ int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, cons
     // enough): the guesses of ALL primes are ONE launch (UniformArgs::prime_of).
     SEAMD_HIP(spec_stream.create(hipStreamNonBlocking));
 
-    CbdArgs ca{d_seeds, nullptr, d_err, n / 16, (uint32_t)B};
-    EncArgs ea{d_values, d_err, nullptr, d_c0, d_c1, d_ntt_pte, d_pte, d_status, d_general, d_compact};
-
     //   S : U_0 (real ciphertexts) ─────────────────────┐ (wait P) select ► redo (masked) ► (wait A) N_0 .. N_{np-1}
     //   A : cbd ► k_encode_rns ─────────────────────────┤
     //   P : setup ► U_{1..np-1} (all guesses, one launch)┘
@@ -852,12 +937,19 @@ int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, cons
     SEAMD_HIP(hipStreamWaitEvent(aux_stream, ev_fork, 0));
     SEAMD_HIP(hipStreamWaitEvent(spec_stream, ev_fork, 0));
 
-    SEAMD_HIP(launch_spec_setup(plan, d_share_seeds, d_sp_seeds, d_sp_ctr, d_sp_prime, spec_stream));
+    SEAMD_HIP(launch_spec_setup(plan, ua.seeds, d_sp_seeds, d_sp_ctr, d_sp_prime, spec_stream));
     {
         // one output row per virtual ciphertext; its prime comes from d_sp_prime
-        UniformArgs ug{d_sp_seeds, d_sp_ctr, d_sp_ctrout, d_sp_rows, d_rej + B * rej_cap, rej_cap, (uint32_t)total,
-                       0,          0,        1,           d_spec + B * spec_cap, spec_cap, 0, debug_flags,
-                       nullptr,    0,        0,           d_sp_prime};
+        UniformArgs ug = uniform_args();
+        ug.seeds       = d_sp_seeds;
+        ug.ctr_in      = d_sp_ctr;
+        ug.ctr_out     = d_sp_ctrout;
+        ug.out         = d_sp_rows;
+        ug.rej_list    = d_rej + B * rej_cap;     // behind the rows of the real ciphertexts
+        ug.spec        = d_spec + B * spec_cap;
+        ug.B           = (uint32_t)total;
+        ug.out_primes  = 1;
+        ug.prime_of    = d_sp_prime;
         SEAMD_HIP(launch_sample_uniform(dp, ug, spec_stream));
         SEAMD_HIP(hipEventRecord(ev_enc, spec_stream));
     }
@@ -870,19 +962,23 @@ int Context::encrypt_sym_small(const SpecPlan &plan, const float *d_values, cons
     stage_end(aux_stream);
     SEAMD_HIP(hipEventRecord(ev_join, aux_stream));
 
-    UniformArgs u0{d_share_seeds, nullptr, d_ctr, d_c1, d_rej, rej_cap, (uint32_t)B, 0, 1, np,
-                   d_spec,        spec_cap, 0,     debug_flags};
+    UniformArgs u0 = ua;   // prime 0 of the real ciphertexts
+    u0.ctr_out     = d_ctr;
+    u0.prime_hi    = 1;
     stage_begin(1, st);
     SEAMD_HIP(launch_sample_uniform(dp, u0, st));
     stage_end(st);
     SEAMD_HIP(hipStreamWaitEvent(st, ev_enc, 0));
-    SEAMD_HIP(launch_spec_select(plan, n, d_ctr, d_sp_ctrout, d_sp_rows, d_c1, d_sp_fail, st));
+    SEAMD_HIP(launch_spec_select(plan, n, d_ctr, d_sp_ctrout, d_sp_rows, ea.c1, d_sp_fail, st));
     // misses (~1e-7 per prime): the ordinary per-prime chain, masked to the ciphertexts that missed;
     // without a miss every workgroup of these launches returns at once
+    UniformArgs ur = u0;
+    ur.ctr_in      = d_ctr;
+    ur.only_from   = d_sp_fail;
     for (uint32_t j = 1; j < np; j++)
     {
-        UniformArgs ur{d_share_seeds, d_ctr,    d_ctr, d_c1,        d_rej,     rej_cap, (uint32_t)B, j, j + 1, np,
-                       d_spec,        spec_cap, 0,     debug_flags, d_sp_fail, 0,       0};
+        ur.prime_lo = j;
+        ur.prime_hi = j + 1;
         SEAMD_HIP(launch_sample_uniform(dp, ur, st));
     }
     SEAMD_HIP(hipStreamWaitEvent(st, ev_join, 0));
@@ -923,7 +1019,14 @@ int Context::encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d
     size_t nchunks  = overlap ? asym_chunks : 1;
     if (nchunks > (size_t)kMaxPrimes) nchunks = kMaxPrimes;   // one join event per chunk
     if (nchunks < 1 || B < 4096 * nchunks) nchunks = 1;        // small batches: one chunk
-    TernaryArgs ta{d_seeds, d_ucodes, d_ctr, n, (uint32_t)B, nullptr, (uint32_t)num_cus, debug_flags};
+    TernaryArgs ta{};
+    ta.seeds       = d_seeds;
+    ta.codes       = d_ucodes;
+    ta.ctr_out     = d_ctr;
+    ta.n           = n;
+    ta.B           = (uint32_t)B;
+    ta.num_cus     = (uint32_t)num_cus;
+    ta.debug_flags = debug_flags;
     stage_begin(2, st);
     SEAMD_HIP(launch_sample_ternary(ta, st));
     stage_end(st);
@@ -937,7 +1040,12 @@ int Context::encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d
     {
         const size_t lo = B * c / nchunks, hi = B * (c + 1) / nchunks, cb = hi - lo;
         if (cb == 0) continue;
-        CbdArgs ca{d_seeds + lo * 64, d_ctr + lo, d_err + lo * 2 * n, 2 * (n / 16), (uint32_t)cb};
+        CbdArgs ca{};
+        ca.seeds         = d_seeds + lo * 64;
+        ca.ctr_base      = d_ctr + lo;
+        ca.out           = d_err + lo * 2 * n;
+        ca.blocks_per_ct = 2 * (n / 16);
+        ca.B             = (uint32_t)cb;
         stage_begin(0, ax);
         SEAMD_HIP(launch_sample_cbd(ca, ax));
         stage_end(ax);
@@ -948,15 +1056,16 @@ int Context::encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d
         const size_t lo = B * c / nchunks, hi = B * (c + 1) / nchunks, cb = hi - lo;
         if (cb == 0) continue;
         if (nchunks > 1) SEAMD_HIP(hipStreamWaitEvent(st, ev_prime[c], 0));
-        EncArgs ea{d_values + lo * (n / 2),
-                   d_err + lo * 2 * n,
-                   d_ucodes + lo * n,
-                   d_c0 + lo * np * n,
-                   d_c1 + lo * np * n,
-                   d_ntt_pte ? d_ntt_pte + lo * np * n : nullptr,
-                   d_pte ? d_pte + lo * n : nullptr,
-                   d_status ? d_status + lo : nullptr,
-                   d_general};
+        EncArgs ea{};
+        ea.values  = d_values + lo * (n / 2);
+        ea.err     = d_err + lo * 2 * n;
+        ea.ucodes  = d_ucodes + lo * n;
+        ea.c0      = d_c0 + lo * np * n;
+        ea.c1      = d_c1 + lo * np * n;
+        ea.ntt_pte = d_ntt_pte ? d_ntt_pte + lo * np * n : nullptr;
+        ea.pte     = d_pte ? d_pte + lo * n : nullptr;
+        ea.status  = d_status ? d_status + lo : nullptr;
+        ea.general = d_general;
         KeyRing rc_chunk{};
         if (ring)
         {
@@ -1001,22 +1110,14 @@ int Context::encrypt_sym_keyed(const float *d_values, size_t B, const uint32_t *
         SEAMD_HIP(hipDeviceSynchronize());   // earlier calls may still read the old slab
         SEAMD_HIP(d_a.grow(B * hp.nprimes * hp.n));
     }
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = key_prologue(d_key_idx, ring_sk, B, st);
-    if (rc == 0)
-    {
-        const KeyRing ring{d_ring_sk, d_ring_sk, d_kidx, (size_t)2 * hp.nprimes * hp.n};
-        rc = encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_c1 ? d_c1 : d_a.get(), d_ntt_pte, d_pte,
-                              d_status, st, &ring);
-    }
-    if (rc == 0)
-    {
-        const KeyRejectArgs ra{d_kbad, d_status, {d_c0, nullptr, nullptr}, {hp.nprimes * hp.n, 0, 0}};
-        hipError_t e = launch_key_reject(dp, ra, B, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
-    }
-    return end_call(st, rc);
+    KeyRejectArgs ra{};
+    ra.status   = d_status;
+    ra.rows[0]  = d_c0;
+    ra.words[0] = hp.nprimes * hp.n;
+    return keyed_call(d_key_idx, ring_sk, d_ring_sk, d_ring_sk, ra, B, st, [&](const KeyRing &ring) {
+        return encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_c1 ? d_c1 : d_a.get(), d_ntt_pte, d_pte,
+                                d_status, st, &ring);
+    });
 }
 
 int Context::encrypt_asym_keyed(const float *d_values, size_t B, const uint32_t *d_key_idx, const uint8_t *d_seeds,
@@ -1031,21 +1132,15 @@ int Context::encrypt_asym_keyed(const float *d_values, size_t B, const uint32_t 
     }
     if (B == 0) return 0;
     if (!d_values || !d_key_idx || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = key_prologue(d_key_idx, ring_pk, B, st);
-    if (rc == 0)
-    {
-        const KeyRing ring{d_ring_pk0, d_ring_pk1, d_kidx, (size_t)2 * hp.nprimes * hp.n};
-        rc = encrypt_asym_impl(d_values, B, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st, &ring);
-    }
-    if (rc == 0)
-    {
-        const KeyRejectArgs ra{d_kbad, d_status, {d_c0, d_c1, nullptr}, {hp.nprimes * hp.n, hp.nprimes * hp.n, 0}};
-        hipError_t e = launch_key_reject(dp, ra, B, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
-    }
-    return end_call(st, rc);
+    KeyRejectArgs ra{};
+    ra.status   = d_status;
+    ra.rows[0]  = d_c0;
+    ra.rows[1]  = d_c1;
+    ra.words[0] = hp.nprimes * hp.n;
+    ra.words[1] = hp.nprimes * hp.n;
+    return keyed_call(d_key_idx, ring_pk, d_ring_pk0, d_ring_pk1, ra, B, st, [&](const KeyRing &ring) {
+        return encrypt_asym_impl(d_values, B, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st, &ring);
+    });
 }
 
 // An out-of-range index: the record is decrypted under the clamped index and its outputs are then zeroed.
@@ -1060,24 +1155,18 @@ int Context::decrypt_decode_keyed(const uint32_t *d_c0, const uint32_t *d_c1, si
     }
     if (B == 0) return 0;
     if (!d_c0 || !d_c1 || !d_key_idx || prime >= hp.nprimes) return kErrInvalid;
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = key_prologue(d_key_idx, ring_sk, B, st);
-    if (rc == 0)
-    {
-        const KeyRing ring{d_ring_sk, d_ring_sk, d_kidx, (size_t)2 * hp.nprimes * hp.n};
-        hipError_t e = launch_decrypt_decode(dp, dt, d_c0, d_c1, (uint32_t)hp.nprimes, (int)prime, d_dec_ntt, d_pt,
-                                             d_values, B, st, &ring);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_decrypt_decode");
-    }
-    if (rc == 0)
-    {
-        const KeyRejectArgs ra{d_kbad, nullptr, {d_dec_ntt, d_pt, reinterpret_cast<uint32_t *>(d_values)},
-                               {hp.n, hp.n, hp.n / 2}};
-        hipError_t e = launch_key_reject(dp, ra, B, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
-    }
-    return end_call(st, rc);
+    KeyRejectArgs ra{};
+    ra.rows[0]  = d_dec_ntt;
+    ra.rows[1]  = d_pt;
+    ra.rows[2]  = reinterpret_cast<uint32_t *>(d_values);
+    ra.words[0] = hp.n;
+    ra.words[1] = hp.n;
+    ra.words[2] = hp.n / 2;
+    return keyed_call(d_key_idx, ring_sk, d_ring_sk, d_ring_sk, ra, B, st, [&](const KeyRing &ring) -> int {
+        SEAMD_HIP(launch_decrypt_decode(dp, dt, d_c0, d_c1, (uint32_t)hp.nprimes, (int)prime, d_dec_ntt, d_pt, d_values,
+                                        B, st, &ring));
+        return 0;
+    });
 }
 
 // Full-modulus decrypt: one launch, no scratch (nothing of the context is written, so no begin_call / end_call).
@@ -1092,7 +1181,13 @@ int Context::decrypt_full(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, 
     if (!d_c0 || !d_c1 || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    const FullArgs fa{d_c0, d_c1, d_pte, d_values, d_values_f64, d_status};
+    FullArgs fa{};
+    fa.c0         = d_c0;
+    fa.c1         = d_c1;
+    fa.pte        = d_pte;
+    fa.values     = d_values;
+    fa.values_f64 = d_values_f64;
+    fa.status     = d_status;
     SEAMD_HIP(launch_decrypt_full(dp, dt, crt, fa, B, st));
     return 0;
 }
@@ -1111,26 +1206,25 @@ int Context::decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size
     }
     if (!d_c0 || !d_c1 || !d_key_idx || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
     if (B == 0) return 0;
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = key_prologue(d_key_idx, ring_sk, B, st);
-    if (rc == 0)
-    {
-        const KeyRing ring{d_ring_sk, d_ring_sk, d_kidx, (size_t)2 * hp.nprimes * hp.n};
-        const FullArgs fa{d_c0, d_c1, d_pte, d_values, d_values_f64, d_status};
-        hipError_t e = launch_decrypt_full(dp, dt, crt, fa, B, st, &ring);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_decrypt_full");
-    }
-    if (rc == 0)
-    {
-        const KeyRejectArgs ra{d_kbad, d_status,
-                               {reinterpret_cast<uint32_t *>(d_pte), reinterpret_cast<uint32_t *>(d_values),
-                                reinterpret_cast<uint32_t *>(d_values_f64)},
-                               {2 * hp.n, hp.n / 2, hp.n}};
-        hipError_t e = launch_key_reject(dp, ra, B, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_key_reject");
-    }
-    return end_call(st, rc);
+    KeyRejectArgs ra{};
+    ra.status   = d_status;
+    ra.rows[0]  = reinterpret_cast<uint32_t *>(d_pte);
+    ra.rows[1]  = reinterpret_cast<uint32_t *>(d_values);
+    ra.rows[2]  = reinterpret_cast<uint32_t *>(d_values_f64);
+    ra.words[0] = 2 * hp.n;
+    ra.words[1] = hp.n / 2;
+    ra.words[2] = hp.n;
+    FullArgs fa{};
+    fa.c0         = d_c0;
+    fa.c1         = d_c1;
+    fa.pte        = d_pte;
+    fa.values     = d_values;
+    fa.values_f64 = d_values_f64;
+    fa.status     = d_status;
+    return keyed_call(d_key_idx, ring_sk, d_ring_sk, d_ring_sk, ra, B, st, [&](const KeyRing &ring) -> int {
+        SEAMD_HIP(launch_decrypt_full(dp, dt, crt, fa, B, st, &ring));
+        return 0;
+    });
 }
 
 // Slices per output row of ct_lincomb.  A workgroup owns 1024 residues of one output row, so G rows give
@@ -1174,24 +1268,30 @@ int Context::ct_lincomb(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, 
     const size_t slabs = d_in1 ? 2 : 1;
     uint32_t S         = lincomb_split ? lincomb_split : lincomb_slices(G, nnz, slabs);
     if (S > 65535) S = 65535;
-    LincombArgs la{d_in0, d_in1, d_out0, d_out1, d_row_ptr, d_idx, d_w, d_status, nullptr, nullptr,
-                   (uint32_t)B, (uint32_t)nnz, G, 0};
+    LincombArgs la{};
+    la.in0     = d_in0;
+    la.in1     = d_in1;
+    la.out0    = d_out0;
+    la.out1    = d_out1;
+    la.row_ptr = d_row_ptr;
+    la.idx     = d_idx;
+    la.w       = d_w;
+    la.status  = d_status;
+    la.B       = (uint32_t)B;
+    la.nnz     = (uint32_t)nnz;
+    la.G       = G;
     if (S == 1)
     {
         SEAMD_HIP(launch_ct_lincomb(dp, la, 1, st));
         return 0;
     }
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = ensure_lincomb(slabs * G * S * hp.nprimes * hp.n, G * S);
-    if (rc == 0)
-    {
-        la.part      = d_lc_part;
-        la.flag      = d_lc_flag;
-        hipError_t e = launch_ct_lincomb(dp, la, S, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_ct_lincomb");
-    }
-    return end_call(st, rc);
+    return call_scope(st, [&]() -> int {
+        if (int rc = ensure_lincomb(slabs * G * S * hp.nprimes * hp.n, G * S)) return rc;
+        la.part = d_lc_part;
+        la.flag = d_lc_flag;
+        SEAMD_HIP(launch_ct_lincomb(dp, la, S, st));
+        return 0;
+    });
 }
 
 // d_out NULL: plain ckks_encode_base (only the int64 plaintexts are written)
@@ -1201,18 +1301,19 @@ int Context::encode_ntt(const float *d_values, size_t B, uint32_t *d_out, int64_
     if (B == 0) return 0;
     if (!d_values || (!d_out && !d_pte)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);   // the list of declined plaintexts is context scratch
-    int rc = begin_call(st);
-    if (rc) return rc;
-    rc = ensure_general(B);
-    if (rc == 0)
-    {
-        EncArgs ea{d_values, nullptr, nullptr, d_out, nullptr, nullptr, d_pte, d_status, d_general};
+    return call_scope(st, [&]() -> int {
+        if (int rc = ensure_general(B)) return rc;
+        EncArgs ea{};
+        ea.values  = d_values;
+        ea.c0      = d_out;
+        ea.pte     = d_pte;
+        ea.status  = d_status;
+        ea.general = d_general;
         stage_begin(3, st);
-        hipError_t e = launch_encode_encrypt(dp, dt, ea, kModeEncodeOnly, B, st);
-        if (e != hipSuccess) rc = hip_fail(e, "launch_encode_encrypt");
+        SEAMD_HIP(launch_encode_encrypt(dp, dt, ea, kModeEncodeOnly, B, st));
         stage_end(st);
-    }
-    return end_call(st, rc);
+        return 0;
+    });
 }
 
 }  // namespace seamd

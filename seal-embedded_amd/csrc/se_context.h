@@ -129,6 +129,8 @@ struct Context
     int ensure_keyed(size_t B);
     int begin_call(hipStream_t st);
     int end_call(hipStream_t st, int rc);
+    // UniformArgs with what the context owns set: reject lists, candidate rows, their capacities, debug_flags
+    UniformArgs uniform_args() const;
     // u codes (0/1/2 per coefficient) and e1 of ciphertext 0 of the last asymmetric call (host out)
     int fetch_asym_randomness(int8_t *ucodes, int8_t *e1);
     int set_secret_key(const uint8_t *sk_packed);
@@ -193,13 +195,21 @@ struct Context
     bool small_batch_plan(size_t B, SpecPlan &plan, bool keyed = false) const;
     // speculation or the plain per-prime chain for this batch (estimated chain latencies of both)
     bool speculation_pays(size_t B, const SpecPlan &plan) const;
-    int encrypt_sym_small(const SpecPlan &plan, const float *d_values, const uint8_t *d_share_seeds,
-                          const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1, uint32_t *d_ntt_pte,
-                          int64_t *d_pte, uint8_t *d_status, hipStream_t st, const KeyRing *ring = nullptr);
+    // (the argument blocks are encrypt_sym_impl's: error sampler, encode kernels, sampler of `a` without its primes)
+    int encrypt_sym_small(const SpecPlan &plan, const CbdArgs &ca, const EncArgs &ea, const UniformArgs &ua,
+                          hipStream_t st, const KeyRing *ring);
 
     void stage_begin(int stage, hipStream_t st);
     void stage_end(hipStream_t st);
     void collect_events();
+
+private:
+    // the call protocol of the entries with scratch, and of the keyed ones on top of it (se_context.cpp)
+    template <class Body>
+    int call_scope(hipStream_t st, Body &&body);
+    template <class Body>
+    int keyed_call(const uint32_t *d_key_idx, size_t K, const uint32_t *k0, const uint32_t *k1, KeyRejectArgs ra,
+                   size_t B, hipStream_t st, Body &&body);
 };
 
 void set_last_error(const std::string &msg);

@@ -235,6 +235,30 @@ void put_prng(Lower &L, const SE_PRNG *prng)
     up(L.ctr, &prng->counter, 8);
 }
 
+// one polynomial from the PRNG put_prng uploaded: n CBD samples into L.i8[0] / the ternary codes, end counter in ctr[1]
+seamd::CbdArgs cbd_one(Lower &L, size_t n)
+{
+    seamd::CbdArgs ca{};
+    ca.seeds         = L.seed;
+    ca.ctr_base      = L.ctr;
+    ca.out           = L.i8[0];
+    ca.blocks_per_ct = (uint32_t)(n / 16);
+    ca.B             = 1;
+    return ca;
+}
+
+seamd::TernaryArgs ternary_one(Lower &L, size_t n)
+{
+    seamd::TernaryArgs ta{};   // num_cus 0: the launcher's default
+    ta.seeds   = L.seed;
+    ta.codes   = L.i8[0];
+    ta.ctr_out = L.ctr + 1;
+    ta.n       = (uint32_t)n;
+    ta.B       = 1;
+    ta.ctr_in  = L.ctr;
+    return ta;
+}
+
 const char *data_path()
 {
     const char *p = getenv("SE_AMD_DATA_PATH");
@@ -464,7 +488,12 @@ bool ckks_encode_base(const Parms *parms, const flpt *values, size_t values_len,
     up(L.cplx_in, cv, 16 * n);
     const uint32_t none = 0xFFFFFFFFu;
     up(L.fail, &none, 4);
-    seamd::FftArgs fa{L.cplx_in, L.cplx_out, L.i64, L.fail, 1};
+    seamd::FftArgs fa{};
+    fa.in       = L.cplx_in;
+    fa.out_cplx = L.cplx_out;
+    fa.out_int  = L.i64;
+    fa.fail_idx = L.fail;
+    fa.mode     = 1;
     seamd::DevParams dp = L.c().dp;
     dp.n_inv            = parms->scale / (double)n;  // ckks_common.c:183 (the caller's scale)
     LOWER_HIP(seamd::launch_fft_polys(dp, L.c().dt, fa, 1, nullptr));
@@ -559,7 +588,10 @@ static void fft_generic(se_complex *vec, size_t n, int mode)
     Lower &L = lower_for_degree(n);
     LOWER_HIP(hipSetDevice(L.c().device));
     up(L.cplx_in, vec, 16 * n);
-    seamd::FftArgs fa{L.cplx_in, L.cplx_out, nullptr, nullptr, mode};
+    seamd::FftArgs fa{};
+    fa.in       = L.cplx_in;
+    fa.out_cplx = L.cplx_out;
+    fa.mode     = mode;
     LOWER_HIP(seamd::launch_fft_polys(L.c().dp, L.c().dt, fa, 1, nullptr));
     down(vec, L.cplx_out, 16 * n);
 }
@@ -642,8 +674,16 @@ static void uniform_on_device(Lower &L, const Parms *parms, SE_PRNG *prng)
     if (L.sym.armed && L.sym.st) LOWER_HIP(hipStreamSynchronize(L.sym.st));   // the speculation shares c.d_rej / c.d_spec
     const uint32_t j = (uint32_t)prime_of(parms);
     put_prng(L, prng);
-    seamd::UniformArgs ua{L.seed, L.ctr, L.ctr + 1, L.u32[0], c.d_rej, c.rej_cap, 1, j, j + 1, 1,
-                          c.d_spec, c.spec_cap, 0, c.debug_flags, nullptr, j, 0};
+    seamd::UniformArgs ua = c.uniform_args();
+    ua.seeds          = L.seed;
+    ua.ctr_in         = L.ctr;
+    ua.ctr_out        = L.ctr + 1;
+    ua.out            = L.u32[0];
+    ua.B              = 1;
+    ua.prime_lo       = j;
+    ua.prime_hi       = j + 1;
+    ua.out_primes     = 1;
+    ua.out_prime_base = j;   // the one row of the output
     LOWER_HIP(seamd::launch_sample_uniform(c.dp, ua, nullptr));
     const uint64_t before = prng->counter;
     down(&prng->counter, L.ctr + 1, 8);
@@ -744,8 +784,7 @@ void sample_small_poly_ternary_prng_96(PolySizeType n, SE_PRNG *prng, ZZ *poly)
     Lower &L = lower_for_degree(n);
     LOWER_HIP(hipSetDevice(L.c().device));
     put_prng(L, prng);
-    seamd::TernaryArgs ta{L.seed, L.i8[0], L.ctr + 1, (uint32_t)n, 1, L.ctr};
-    LOWER_HIP(seamd::launch_sample_ternary(ta, nullptr));
+    LOWER_HIP(seamd::launch_sample_ternary(ternary_one(L, n), nullptr));
     std::vector<int8_t> codes(n);
     down(codes.data(), L.i8[0], n);
     const uint64_t before = prng->counter;
@@ -760,8 +799,7 @@ void sample_poly_cbd_generic_prng_16(PolySizeType n, SE_PRNG *prng, int8_t *poly
     Lower &L = lower_for_degree(n);
     LOWER_HIP(hipSetDevice(L.c().device));
     put_prng(L, prng);
-    seamd::CbdArgs ca{L.seed, L.ctr, L.i8[0], (uint32_t)(n / 16), 1};
-    LOWER_HIP(seamd::launch_sample_cbd(ca, nullptr));
+    LOWER_HIP(seamd::launch_sample_cbd(cbd_one(L, n), nullptr));
     down(poly, L.i8[0], n);
     const uint64_t before = prng->counter;
     prng->counter += n / 16;
@@ -775,8 +813,7 @@ void sample_add_poly_cbd_generic_inpl_prng_16(int64_t *poly, PolySizeType n, SE_
     LOWER_HIP(hipSetDevice(L.c().device));
     put_prng(L, prng);
     up(L.i64, poly, 8 * n);
-    seamd::CbdArgs ca{L.seed, L.ctr, L.i8[0], (uint32_t)(n / 16), 1};
-    LOWER_HIP(seamd::launch_sample_cbd(ca, nullptr));
+    LOWER_HIP(seamd::launch_sample_cbd(cbd_one(L, n), nullptr));
     LOWER_HIP(seamd::launch_add_small(L.i64, L.i8[0], n, nullptr));
     down(poly, L.i64, 8 * n);
     const uint64_t before = prng->counter;
@@ -950,9 +987,16 @@ static void sym_spec_arm(Lower &L, const Parms *parms, const SE_PRNG *shareable)
         }
     up(S.d_meta, meta.data(), meta.size());
     explicit_bzero(meta.data(), meta.size());
-    seamd::UniformArgs ug{S.d_seeds, S.d_ctr, S.d_ctrout, S.d_rows, c.d_rej + c.rej_cap, c.rej_cap, total,
-                          0,         0,       1,          c.d_spec + c.spec_cap, c.spec_cap, 0, c.debug_flags,
-                          nullptr,   0,       0,          S.d_prime};
+    seamd::UniformArgs ug = c.uniform_args();
+    ug.seeds      = S.d_seeds;
+    ug.ctr_in     = S.d_ctr;
+    ug.ctr_out    = S.d_ctrout;
+    ug.out        = S.d_rows;
+    ug.rej_list   = c.d_rej + c.rej_cap;     // row 0 is the real ciphertext's
+    ug.spec       = c.d_spec + c.spec_cap;
+    ug.B          = total;
+    ug.out_primes = 1;
+    ug.prime_of   = S.d_prime;
     LOWER_HIP(seamd::launch_sample_uniform(c.dp, ug, S.st));
     LOWER_HIP(hipEventRecord(S.ev_sampled, S.st));
     memcpy(S.seed, shareable->seed, 64);
@@ -998,8 +1042,7 @@ void ckks_sym_init(const Parms *parms, uint8_t *share_seed_in, uint8_t *seed_in,
     put_prng(L, prng);
     S.dirty = true;
     up(S.d_pte, conj_vals_int, 8 * n);
-    seamd::CbdArgs ca{L.seed, L.ctr, L.i8[0], (uint32_t)(n / 16), 1};
-    LOWER_HIP(seamd::launch_sample_cbd(ca, nullptr));
+    LOWER_HIP(seamd::launch_sample_cbd(cbd_one(L, n), nullptr));
     LOWER_HIP(seamd::launch_add_small(S.d_pte, L.i8[0], n, nullptr));
     down(conj_vals_int, S.d_pte, 8 * n);   // host-synchronous: the sum is complete before anything on S.st reads it
     S.h_pte.assign(conj_vals_int, conj_vals_int + n);
@@ -1060,7 +1103,14 @@ void ckks_encode_encrypt_sym(const Parms *parms, const int64_t *conj_vals_int, c
                 const uint32_t pr = S.prime_of_step(k);
                 uint32_t *out = S.d_out + (size_t)pr * 3 * n, *stage = S.h_stage + (size_t)pr * 4 * n;
                 const uint32_t *a = S.d_rows + (size_t)r * n;
-                seamd::LowerSymArgs sa{S.d_key, S.d_pte, nullptr, a, out, out + n, out + 2 * n, (int)pr, 0, 0, 0};
+                seamd::LowerSymArgs sa{};
+                sa.s_small = S.d_key;
+                sa.pte     = S.d_pte;
+                sa.a       = a;
+                sa.c0      = out;
+                sa.ntt_pte = out + n;
+                sa.s_save  = out + 2 * n;
+                sa.j       = (int)pr;
                 LOWER_HIP(seamd::launch_lower_sym_prime(L.c().dp, L.c().dt, sa, 1, S.st));
                 LOWER_HIP(hipEventRecord(S.ev_kernel[pr], S.st));
                 LOWER_HIP(hipStreamWaitEvent(S.cp, S.ev_kernel[pr], 0));
@@ -1105,8 +1155,15 @@ void ckks_encode_encrypt_sym(const Parms *parms, const int64_t *conj_vals_int, c
         up(L.i8[0], ep_small, n);
     else
         up(L.i64, conj_vals_int, 8 * n);
-    seamd::LowerSymArgs sa{L.packed, ep_small ? nullptr : L.i64, ep_small ? L.i8[0] : nullptr, L.u32[0],
-                           L.u32[1], L.u32[2], L.u32[3], prime_of(parms), 0, 0, 0};
+    seamd::LowerSymArgs sa{};
+    sa.s_small = L.packed;
+    sa.pte     = ep_small ? nullptr : L.i64;
+    sa.ep      = ep_small ? L.i8[0] : nullptr;
+    sa.a       = L.u32[0];
+    sa.c0      = L.u32[1];
+    sa.ntt_pte = L.u32[2];
+    sa.s_save  = L.u32[3];
+    sa.j       = prime_of(parms);
     LOWER_HIP(seamd::launch_lower_sym_prime(L.c().dp, L.c().dt, sa, 1, nullptr));
     // deliveries in the reference's write order, so that aliased buffers end up the same
     down(c1, L.u32[0], 4 * n);
@@ -1167,10 +1224,12 @@ void ckks_asym_init(const Parms *parms, uint8_t *seed, SE_PRNG *prng, int64_t *c
     // u, then e0 (added to the plaintext) and e1 from the counters behind u (ckks_asym.c:188-201)
     put_prng(L, prng);
     up(L.i64, conj_vals_int, 8 * n);
-    seamd::TernaryArgs ta{L.seed, L.i8[0], L.ctr + 1, (uint32_t)n, 1, L.ctr};
-    LOWER_HIP(seamd::launch_sample_ternary(ta, nullptr));
+    LOWER_HIP(seamd::launch_sample_ternary(ternary_one(L, n), nullptr));
     int8_t *d_err = (int8_t *)L.u32[0];  // 2n bytes: e0 | e1
-    seamd::CbdArgs ca{L.seed, L.ctr + 1, d_err, (uint32_t)(2 * (n / 16)), 1};
+    seamd::CbdArgs ca = cbd_one(L, n);   // e0 | e1: twice the blocks, from the counter where u stopped
+    ca.ctr_base         = L.ctr + 1;
+    ca.out              = d_err;
+    ca.blocks_per_ct    = (uint32_t)(2 * (n / 16));
     LOWER_HIP(seamd::launch_sample_cbd(ca, nullptr));
     LOWER_HIP(seamd::launch_add_small(L.i64, d_err, n, nullptr));
     std::vector<int8_t> codes(n);
@@ -1202,8 +1261,18 @@ void ckks_encode_encrypt_asym(const Parms *parms, const int64_t *conj_vals_int, 
     up(L.i64, conj_vals_int, 8 * n);
     up(L.u32[0], pk_c0, 4 * n);
     up(L.u32[1], pk_c1, 4 * n);
-    seamd::LowerAsymArgs aa{L.packed, L.i8[0], L.i64, L.u32[0], L.u32[1], L.u32[2], L.u32[3], L.u32[4],
-                            ntt_u_save ? L.u32[5] : nullptr, ntt_e1_save ? L.u32[6] : nullptr, prime_of(parms)};
+    seamd::LowerAsymArgs aa{};
+    aa.u_small     = L.packed;
+    aa.e1          = L.i8[0];
+    aa.pte         = L.i64;
+    aa.pk0         = L.u32[0];
+    aa.pk1         = L.u32[1];
+    aa.c0          = L.u32[2];
+    aa.c1          = L.u32[3];
+    aa.ntt_pte     = L.u32[4];
+    aa.ntt_u_save  = ntt_u_save ? L.u32[5] : nullptr;
+    aa.ntt_e1_save = ntt_e1_save ? L.u32[6] : nullptr;
+    aa.j           = prime_of(parms);
     LOWER_HIP(seamd::launch_lower_asym_prime(L.c().dp, L.c().dt, aa, 1, nullptr));
     if (ntt_roots) roots_generic(parms, ntt_roots, false);
     if (ntt_u_save) down(ntt_u_save, L.u32[5], 4 * n);

@@ -281,7 +281,8 @@ def test_int64_boundary(env, shape):
     ctx.close()
 
 
-@pytest.mark.parametrize("shape", [(4096, 3), (16384, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(1024, 1), (2048, 1), (4096, 3), (8192, 6), (16384, 6)],
+                         ids=lambda s: f"{s[0]}x{s[1]}")
 def test_keyed_equals_unkeyed(env, shape):
     """Test 5: record b under ring key idx[b] equals the unkeyed entry with that key installed, on all four outputs;
     an index == K gives status 2 and zero outputs; no ring is SE_ERR_NO_KEY."""

@@ -75,7 +75,7 @@ def test_reference_style_sym_caller_matches_golden(env, golden, tmp_path, shape)
         assert [int(x) for x in polys[j, 0, :8]] + [int(x) for x in polys[j, 0, -8:]] == g["c0_ends"][j]
 
 
-@pytest.mark.parametrize("shape", [(1024, 1), (4096, 3), (16384, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(1024, 1), (2048, 1), (4096, 3), (16384, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_reference_style_asym_caller_matches_golden(env, golden, tmp_path, shape):
     """tests/c/lower_asym_caller.c: gen_pk per prime, ckks_asym_init, ckks_encode_encrypt_asym."""
     from oracle.pyoracle import Oracle

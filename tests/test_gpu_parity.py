@@ -279,7 +279,8 @@ def test_sample_uniform_wave_form_equals_lane_form(env, shape):
         ctx.close()
 
 
-@pytest.mark.parametrize("shape,B", [((1024, 1), 70), ((4096, 3), 131), ((8192, 6), 33), ((16384, 6), 70)],
+@pytest.mark.parametrize("shape,B", [((1024, 1), 70), ((2048, 1), 33), ((4096, 3), 131), ((8192, 6), 33),
+                                     ((16384, 6), 70)],
                          ids=lambda v: str(v))
 def test_staged_sampler_pipeline(env, shape, B):
     """The staged form of the symmetric pipeline (one ciphertext per LANE PAIR for the bulk squeeze --
