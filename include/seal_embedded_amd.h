@@ -353,6 +353,57 @@ int se_amd_ct_lincomb_device(se_amd_ctx *ctx,
         uint8_t *d_status /* [G], optional */, void *stream);
 /* test hook: partial sums a long row is split into (0 = automatic) */
 int se_amd_set_lincomb_split(se_amd_ctx *ctx, uint32_t splits);
+/* ---- real-valued weights: rescale, plaintext products, level-aware decrypt ----------------------
+ * "Level L" is a slab [B][L][n] of uint32 residues under the primes q_0 .. q_{L-1}, NTT form and bit-reversed order
+ * as every encryption entry writes it, 1 <= L <= np of the context.  The default chains are prefixes of one another,
+ * so a level-L record is an ordinary ciphertext of the parameter set (n, L).  The three device entries below take
+ * device pointers, are asynchronous on `stream`, allocate no scratch and -- except the decrypt -- need no key.
+ *
+ * Rescale: level L = primes (2 <= L <= np) in, level L - 1 out ([B][L-1][n]); divides the CKKS scale by q_{L-1}.
+ * With delta = INTT_{L-1}(in[b][L-1]), coefficients lifted to the centred representative in (-q_{L-1}/2, q_{L-1}/2],
+ *     out[b][j] = ( in[b][j] - NTT_j(delta mod q_j) ) . q_{L-1}^-1  mod q_j,   canonical,   j < L - 1:
+ * the exact quotient (c - delta) / q_{L-1}, i.e. c / q_{L-1} rounded to nearest (the moduli are odd: no ties) -- SEAL's
+ * rescale_to_next on NTT-form data.  The map is defined on arbitrary residue slabs and is applied identically to each
+ * slab; the second pair is optional (d_in1 = d_out1 = NULL).  Outputs must not overlap inputs (not checked).
+ * SE_ERR_INVALD_ARGUMENT: NULL d_in0 or d_out0; d_in1 and d_out1 not both set or both NULL; primes outside [2, np]; a
+ * slab pointer that is not 16-byte aligned; B at or above 2^31.  B = 0 is a successful no-op. */
+int se_amd_ct_rescale_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
+                             size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1 /* NULL iff d_in1 NULL */,
+                             void *stream);
+/* Slot-wise product with encoded plaintexts, on level-`primes` slabs (1 <= primes <= np), both slabs alike:
+ *     out[b][j][i] = in[b][j][i] . pt[p(b)][j][i]  mod q_j,   canonical,   j < primes.
+ * d_pt is [P][pt_primes][n], the layout se_amd_encode_ntt_device writes (NTT(m mod q_j)); pt_primes >= primes and only
+ * the first `primes` rows of a plaintext are read.  d_pt_idx [B] uint32 gives p(b); with d_pt_idx = NULL, P = 1 means
+ * one plaintext for every record and P = B means p(b) = b.  A record with p(b) >= P gets status 2 and all-zero rows;
+ * nothing is read out of bounds and other records are unaffected.  d_status [B] is optional (1, or 2).
+ * The scales of plaintext and ciphertext multiply: the result is at scale^2 until it is rescaled.
+ * d_out0 == d_in0 (and d_out1 == d_in1) exactly is allowed: the map is element-wise.  Any other overlap is not.
+ * SE_ERR_INVALD_ARGUMENT: NULL d_in0, d_out0 or d_pt; d_in1 and d_out1 not both set or both NULL; primes outside
+ * [1, np]; pt_primes < primes; d_pt_idx NULL with P neither 1 nor B; B or P at or above 2^32; a slab or plaintext
+ * pointer that is not 16-byte aligned.  B = 0 is a successful no-op. */
+int se_amd_ct_mul_plain_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
+                               size_t B, size_t primes, const uint32_t *d_pt, size_t P, size_t pt_primes,
+                               const uint32_t *d_pt_idx /* [B] or NULL */, uint32_t *d_out0,
+                               uint32_t *d_out1 /* NULL iff d_in1 NULL */, uint8_t *d_status /* [B], optional */,
+                               void *stream);
+/* se_amd_decrypt_full[_keyed]_device on level-`primes` records (d_c0 / d_c1 [B][primes][n], 1 <= primes <= np),
+ * decoded with the caller's `scale` (finite, > 0) in place of the context's: the recombination runs over
+ * Q_primes = q_0 ... q_{primes-1}.  Range: exact while every |y| < min(2^63, Q_primes / 2).  Outputs, status values,
+ * SE_ERR_NO_KEY and the other argument errors are those of the full entries; additionally SE_ERR_INVALD_ARGUMENT for
+ * primes outside [1, np] and for a scale that is not finite and positive.  With primes = np and scale =
+ * se_amd_scale(ctx) this IS the full entry.
+ * Scale bookkeeping: after a weighted sum with weights round(w . 2^s) the scale is scale . 2^s, after a plaintext
+ * product scale^2, and a rescale from level L divides it by q_{L-1}. */
+int se_amd_decrypt_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                double scale, int64_t *d_pte, float *d_values, double *d_values_f64,
+                                uint8_t *d_status, void *stream);
+int se_amd_decrypt_level_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                      size_t primes, double scale, const uint32_t *d_key_idx, int64_t *d_pte,
+                                      float *d_values, double *d_values_f64, uint8_t *d_status, void *stream);
+/* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
+ * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
+ * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */
+int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup);
 /* Host-only: the recombination constants the full-modulus decrypt uses, for inspection and CPU-side checks:
  * inv[j] = (q_0 ... q_{j-1})^-1 mod q_j and inv_shoup[j] = floor(inv[j] * 2^32 / q_j) for j = 1 .. np-1 (entry 0 is
  * 0).  inv_shoup may be NULL.  SE_ERR_INVALD_ARGUMENT for an unsupported (degree, nprimes). */

@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_encrypt_asym_keyed_device", "se_amd_decrypt_decode_keyed_device",
     "se_amd_decrypt_full_device", "se_amd_decrypt_full_keyed_device", "se_amd_crt_constants",
     "se_amd_ct_lincomb_device", "se_amd_set_lincomb_split",
+    "se_amd_ct_rescale_device", "se_amd_ct_mul_plain_device", "se_amd_decrypt_level_device",
+    "se_amd_decrypt_level_keyed_device", "se_amd_rescale_constants",
 )
 
 
@@ -143,6 +145,11 @@ def lib():
     L.se_amd_crt_constants.argtypes = [sz, sz, vp, vp]
     L.se_amd_ct_lincomb_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.se_amd_set_lincomb_split.argtypes = [vp, u32]
+    L.se_amd_ct_rescale_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    L.se_amd_ct_mul_plain_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.se_amd_decrypt_level_device.argtypes = [vp, vp, vp, sz, sz, C.c_double, vp, vp, vp, vp, vp]
+    L.se_amd_decrypt_level_keyed_device.argtypes = [vp, vp, vp, sz, sz, C.c_double, vp, vp, vp, vp, vp, vp]
+    L.se_amd_rescale_constants.argtypes = [sz, sz, vp, vp]
     _lib = L
     return L
 
@@ -187,6 +194,16 @@ def crt_constants(n, nprimes):
     import numpy as np
     inv = np.zeros(nprimes, np.uint32); sh = np.zeros(nprimes, np.uint32)
     _check(lib().se_amd_crt_constants(n, nprimes, _ptr(inv), _ptr(sh)), "se_amd_crt_constants")
+    return inv, sh
+
+
+def rescale_constants(n, primes):
+    """Constants of the rescale from level `primes` (host only): (inv, inv_shoup) uint32 [primes - 1],
+    inv[j] = q_{primes-1}^-1 mod q_j."""
+    import numpy as np
+    m = max(int(primes) - 1, 1)
+    inv = np.zeros(m, np.uint32); sh = np.zeros(m, np.uint32)
+    _check(lib().se_amd_rescale_constants(n, primes, _ptr(inv), _ptr(sh)), "se_amd_rescale_constants")
     return inv, sh
 
 
@@ -478,6 +495,42 @@ class Context:
     def set_lincomb_split(self, S):
         """Test hook: slices a row of ct_lincomb is cut into (0 = automatic); every value gives the same bits."""
         _check(self.L.se_amd_set_lincomb_split(self.h, S), "se_amd_set_lincomb_split")
+
+    def ct_rescale(self, in0, out0, in1=None, out1=None, primes=None):
+        """Key-free rescale of one or two slabs [B][primes][n] -> [B][primes-1][n] (out rows of B records, packed):
+        the exact quotient (c - delta) / q_last, delta = c mod q_last centred.  primes defaults to in0.shape[1]."""
+        B = in0.shape[0]
+        if primes is None:
+            primes = in0.shape[1]
+        _check(self.L.se_amd_ct_rescale_device(self.h, _ptr(in0), _ptr(in1), B, primes, _ptr(out0), _ptr(out1),
+                                               _stream_ptr()), "se_amd_ct_rescale_device")
+
+    def ct_mul_plain(self, in0, pt, out0, in1=None, out1=None, pt_idx=None, primes=None, status=None):
+        """Key-free slot-wise product of one or two slabs [B][primes][n] with encoded plaintexts pt [P][pt_primes][n]
+        (encode_ntt's layout): record b times plaintext pt_idx[b], or with pt_idx=None the one plaintext (P = 1) or
+        plaintext b (P = B).  status uint8 [B]: 2 and zero rows for an index >= P.  out may be the input itself."""
+        B = in0.shape[0]
+        if primes is None:
+            primes = in0.shape[1]
+        _check(self.L.se_amd_ct_mul_plain_device(self.h, _ptr(in0), _ptr(in1), B, primes, _ptr(pt), pt.shape[0],
+                                                 pt.shape[1], _ptr(pt_idx), _ptr(out0), _ptr(out1), _ptr(status),
+                                                 _stream_ptr()), "se_amd_ct_mul_plain_device")
+
+    def decrypt_level(self, c0, c1, primes, scale, pte=None, values=None, values_f64=None, status=None):
+        """decrypt_full on records of `primes` <= np primes [B][primes][n], decoded with `scale`."""
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt_level_device(self.h, _ptr(c0), _ptr(c1), B, primes, scale, _ptr(pte),
+                                                  _ptr(values), _ptr(values_f64), _ptr(status), _stream_ptr()),
+               "se_amd_decrypt_level_device")
+
+    def decrypt_level_keyed(self, c0, c1, key_idx, primes, scale, pte=None, values=None, values_f64=None,
+                            status=None):
+        """decrypt_level with ciphertext b under secret-ring key key_idx[b]; status 2 and zero outputs for an
+        index >= K."""
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt_level_keyed_device(self.h, _ptr(c0), _ptr(c1), B, primes, scale, _ptr(key_idx),
+                                                        _ptr(pte), _ptr(values), _ptr(values_f64), _ptr(status),
+                                                        _stream_ptr()), "se_amd_decrypt_level_keyed_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

@@ -1,8 +1,11 @@
-// ct_ops.hip -- key-free operations on resident ciphertext slabs: weighted sums of records (se_amd_ct_lincomb_device).
+// ct_ops.hip -- key-free operations on resident ciphertext slabs: weighted sums of records (se_amd_ct_lincomb_device),
+// slot-wise products with encoded plaintexts (se_amd_ct_mul_plain_device) and the rescale that drops the last prime
+// (se_amd_ct_rescale_device, at the end of the file).
 //
-// A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records is element-wise arithmetic
-// mod q_j: no transform, no key, no table.  Unlike the rest of the tree these kernels are bound by HBM, not by VALU
-// issue: every input row is read once per use and every output row written once.
+// A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
+// plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
+// the tree these two are bound by HBM, not by VALU issue: every input row is read once per use and every output row
+// written once.
 //
 // Access shape.  A row is np * n residues; n is a multiple of 1024, so a 256-thread workgroup that owns 1024
 // consecutive residues (one lane = 4 residues = one 16-byte load per input row) lies inside ONE prime: q_j and its
@@ -13,6 +16,7 @@
 #include "kernel_args.h"
 #include "launch.h"
 #include "modarith.cuh"
+#include "transform.cuh"
 
 namespace seamd {
 namespace {
@@ -225,6 +229,133 @@ hipError_t launch_ct_lincomb(const DevParams &P, const LincombArgs &args, uint32
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------
+// Slot-wise product with an encoded plaintext: out[b][j][i] = in[b][j][i] . pt[p(b)][j][i] mod q_j.  Streaming, in the
+// shape of k_ct_lincomb: a 256-thread workgroup owns 1024 consecutive residues of a record -- inside one prime, so q_j
+// and its Barrett constants are scalar -- and walks the records blockIdx.y, blockIdx.y + gridDim.y, ...; p(b) is
+// workgroup-uniform (a scalar load).  One 16-byte load per operand, one 16-byte store; 64-bit row offsets.  Every lane
+// reads its own 16 bytes of `in` before it writes the same 16 bytes of `out`, so out == in is allowed (no __restrict__
+// on the pair).  The product of two words is below 2^64 whatever the words are, and barrett64 is exact there.
+// grid (primes n / 1024 * slabs, min(B, 65 535)).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kLcThreads) void k_ct_mul_plain(const DevParams P, const MulPlainArgs A)
+{
+    const size_t row      = (size_t)A.primes << P.logn;
+    const size_t pt_row   = (size_t)A.pt_primes << P.logn;
+    const uint32_t chunks = (uint32_t)(row >> kLcTileLog);
+    const uint32_t slab   = blockIdx.x / chunks;
+    const uint32_t chunk  = blockIdx.x - slab * chunks;
+    const uint32_t j      = (chunk << kLcTileLog) >> P.logn;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const uint32_t *in = slab ? A.in1 : A.in0;
+    uint32_t *out      = slab ? A.out1 : A.out0;
+    const uint32_t *__restrict__ pt = A.pt;
+    const size_t off = ((size_t)chunk << kLcTileLog) + 4 * threadIdx.x;   // the same offset inside a plaintext: j < primes
+
+    for (size_t b = blockIdx.y; b < A.B; b += gridDim.y)
+    {
+        const uint32_t p = A.pt_idx ? A.pt_idx[b] : (A.P == 1 ? 0u : (uint32_t)b);
+        const bool bad   = p >= A.P;   // nothing of such a record's plaintext is read
+        uint4 r          = make_uint4(0, 0, 0, 0);
+        if (!bad)
+        {
+            const uint4 a = load_row(in, b, row, off);
+            const uint4 m = load_row(pt, p, pt_row, off);
+            r.x           = barrett64((uint64_t)a.x * m.x, q, cr_hi, cr_lo);
+            r.y           = barrett64((uint64_t)a.y * m.y, q, cr_hi, cr_lo);
+            r.z           = barrett64((uint64_t)a.z * m.z, q, cr_hi, cr_lo);
+            r.w           = barrett64((uint64_t)a.w * m.w, q, cr_hi, cr_lo);
+        }
+        *reinterpret_cast<uint4 *>(out + b * row + off) = r;
+        if (A.status && blockIdx.x == 0 && threadIdx.x == 0) A.status[b] = bad ? 2 : 1;
+    }
+}
+
+hipError_t launch_ct_mul_plain(const DevParams &P, const MulPlainArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    const uint32_t chunks = (uint32_t)(((size_t)A.primes << P.logn) >> kLcTileLog);
+    const uint32_t slabs  = A.in1 ? 2 : 1;
+    const dim3 grid(chunks * slabs, A.B < 65535u ? A.B : 65535u);
+    return launch(k_ct_mul_plain, grid, dim3(kLcThreads), 0, st, P, A);
+}
+
+// ------------------------------------------------------------------------------------------
+// Rescale: level L -> level L - 1, the exact quotient (c - delta) / q_last with delta = c mod q_last centred, i.e.
+// c / q_last rounded to nearest (SEAL's rescale_to_next on NTT-form data).  One workgroup of n/16 threads per
+// (record, slab), the tiling of the rest of the tree:
+//   last row (quad loads, 1 KiB per wave instruction) -> quads_to_tile -> intt_tiles mod q_last -> . n^-1 -> centred
+//   lift: 16 signed values per thread, |delta| <= (q_last - 1)/2 < 2^29, kept in registers in tile layout LOGN-4;
+//   per lower prime j: delta mod q_j (|delta| < q_j: one conditional add) -> ntt_tiles, which STARTS in tile layout
+//   LOGN-4, so nothing is re-dealt between the inverse and the forward transforms -> tile_to_quads -> (c_j - NTT) .
+//   q_last^-1 (Shoup pair, RescaleParams) -> canonical -> quad store.
+// The input row of prime j is requested before its NTT and lands while it runs.  LDS is the exchange plane alone
+// (XformGeom::SLOTS words): the wave-local transposes run inside it (rows of 16 words, n words in all) while no
+// exchange is in flight -- every exchange ends in a barrier, and one workgroup barrier after each transpose keeps the
+// next transform's first exchange off the rows other waves are still reading.
+// The map is plain modular arithmetic on whatever words the slab holds (defined for residues in [0, q_j)); no word is
+// used as an address.  grid (B, slabs).
+// ------------------------------------------------------------------------------------------
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_rescale(const DevParams P, const DevTables T,
+                                                                      const RescaleParams R, const RescaleArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds       = reinterpret_cast<uint32_t *>(smem);
+    const int t         = threadIdx.x;
+    const size_t b      = blockIdx.x;
+    const uint32_t last = A.primes - 1;
+    const uint32_t *in  = (blockIdx.y ? A.in1 : A.in0) + b * A.primes * N;
+    uint32_t *out       = (blockIdx.y ? A.out1 : A.out0) + b * last * N;
+
+    int32_t delta[16];
+    {
+        const uint32_t q = P.q[last];
+        uint32_t x[16];
+        load_quads(x, in + (size_t)last * N, t);
+        quads_to_tile<16>(x, lds, t);
+        __syncthreads();
+        intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * last, q, lds, t);
+        const uint32_t inv_n = P.inv_n[last], inv_n_sh = P.inv_n_sh[last];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+            delta[e] = (int32_t)centred_lift(csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, q), q), q);
+    }
+    for (uint32_t j = 0; j < last; j++)
+    {
+        const uint32_t q = P.q[j], two_q = q << 1;
+        uint32_t c[16], x[16];
+        load_quads(c, in + (size_t)j * N, t);
+#pragma unroll
+        for (int e = 0; e < 16; e++) x[e] = (uint32_t)delta[e] + ((uint32_t)(delta[e] >> 31) & q);   // [0, q)
+        ntt_tiles<LOGN>(x, T.ntt_rw + 2 * xform_table_len(N) * j, q, lds, t);
+        tile_to_quads<16>(x, lds, t);
+        const uint32_t w = R.inv[j], wp = R.inv_sh[j];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            const uint32_t u = min(x[e], x[e] - two_q);                          // NTT output [0, 4q) -> [0, 2q)
+            x[e]             = csub(mul_shoup_lazy(c[e] + two_q - u, w, wp, q), q);  // c - u + 2q in (0, 3q)
+        }
+        store_quads(out + (size_t)j * N, x, t);
+        __syncthreads();
+    }
+}
+
+hipError_t launch_ct_rescale(const DevParams &P, const DevTables &T, const RescaleParams &R, const RescaleArgs &A,
+                             size_t B, hipStream_t st)
+{
+    if (B == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        return launch(k_ct_rescale<L>, dim3((unsigned)B, A.in1 ? 2 : 1), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, R, A);
+    });
 }
 
 }  // namespace seamd

@@ -64,9 +64,7 @@ __device__ __forceinline__ void load16_pairs(uint32_t (&w)[16], uint32_t (&wp)[1
     }
 }
 
-// quad-layout (transform.cuh, tile_to_quads) accessors: every instruction of a wave covers 1 KiB contiguous.
-// One base pointer per access (the thread's first quad) and compile-time offsets that land in the instructions'
-// immediate fields.
+// (the quad-layout accessors load_quads / store_quads live beside tile_to_quads in transform.cuh)
 //
 // opaque_index(): a thread index the compiler must treat as freshly computed where it is taken.  The fused
 // kernels address the same per-thread pieces (a, key pairs, c0 / c1, u, e1) again for every prime; seen as
@@ -96,25 +94,6 @@ __device__ __forceinline__ DevTables with_key(const DevTables &T, const KeyRing 
     Tk.pk0       = R.k0 + kb;
     Tk.pk1       = R.k1 + kb;
     return Tk;
-}
-
-__device__ __forceinline__ void load_quads(uint32_t (&v)[16], const uint32_t *poly, int t)
-{
-    const uint32_t *base = poly + quad_index(t, 0);
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-    {
-        const uint4 w = *reinterpret_cast<const uint4 *>(base + (i << 8));
-        v[4 * i] = w.x, v[4 * i + 1] = w.y, v[4 * i + 2] = w.z, v[4 * i + 3] = w.w;
-    }
-}
-
-__device__ __forceinline__ void store_quads(uint32_t *poly, const uint32_t (&v)[16], int t)
-{
-    uint32_t *base = poly + quad_index(t, 0);
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        *reinterpret_cast<uint4 *>(base + (i << 8)) = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
 }
 
 // interleaved (value, shoup) pairs of one polynomial's table, quad layout
@@ -1250,11 +1229,6 @@ hipError_t launch_decrypt_decode(const DevParams &P, const DevTables &T, const u
 // The decode tail is decrypt_decode_body's with the int64 in place of the single-prime lift (ckks_decode,
 // device/test/ckks_tests_common.c:72-115): same never-contracted FP64 operations, same root table.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t centred_lift(uint32_t x, uint32_t q)
-{
-    return (x > q / 2) ? -(int64_t)(q - x) : (int64_t)x;
-}
-
 template <int LOGN, bool KEYED>
 __device__ __forceinline__ void decrypt_full_body(const DevParams &P, const DevTables &T, const CrtParams &C,
                                                   const FullArgs &A, const KeyRing &R, unsigned char *smem)

@@ -142,6 +142,30 @@ struct LincombArgs
 // S slices per output row (1 <= S <= 65 535): S = 1 writes the outputs directly, S > 1 goes through part / flag and a
 // second launch that sums the S partial rows.  Every S gives the same bits (modular sums are exact).
 hipError_t launch_ct_lincomb(const DevParams &, const LincombArgs &, uint32_t S, hipStream_t);
+// Key-free rescale of one or two residue slabs (ct_ops.hip: k_ct_rescale): level `primes` -> level `primes` - 1,
+//   out[b][j] = (in[b][j] - NTT_j(centred(INTT_last(in[b][last])) mod q_j)) . q_last^-1  mod q_j,   last = primes - 1.
+struct RescaleArgs
+{
+    const uint32_t *in0, *in1;   // [B][primes][n]; in1 / out1 NULL: one slab
+    uint32_t *out0, *out1;       // [B][primes - 1][n]
+    uint32_t primes;             // 2 .. np
+};
+hipError_t launch_ct_rescale(const DevParams &, const DevTables &, const RescaleParams &, const RescaleArgs &, size_t B,
+                             hipStream_t);
+// Slot-wise product with encoded plaintexts (ct_ops.hip: k_ct_mul_plain), key-free:
+//   out[b][j][i] = in[b][j][i] . pt[p(b)][j][i]  mod q_j,   j < primes,   p(b) = pt_idx[b], or 0 (P = 1) or b (P = B).
+// Status 1, or 2 with all-zero rows for p(b) >= P.  out == in exactly is allowed.
+struct MulPlainArgs
+{
+    const uint32_t *in0, *in1;   // [B][primes][n]; in1 / out1 NULL: one slab
+    uint32_t *out0, *out1;       // [B][primes][n]
+    const uint32_t *pt;          // [P][pt_primes][n], the first `primes` rows of a plaintext are read
+    const uint32_t *pt_idx;      // [B] or NULL
+    uint8_t *status;             // [B], optional
+    uint32_t B, P;
+    uint32_t primes, pt_primes;
+};
+hipError_t launch_ct_mul_plain(const DevParams &, const MulPlainArgs &, hipStream_t);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

@@ -65,6 +65,12 @@ __device__ __forceinline__ uint32_t reduce_signed(int64_t x, uint32_t q, uint32_
     return x < 0 ? q - r : r;
 }
 
+// canonical residue -> its representative in (-q/2, q/2]  (q odd)
+__device__ __forceinline__ int64_t centred_lift(uint32_t x, uint32_t q)
+{
+    return (x > q / 2) ? -(int64_t)(q - x) : (int64_t)x;
+}
+
 // Harvey butterfly, inputs/outputs in [0,4q): (X, Y) -> (X + Y*w, X - Y*w)  (ntt.c:156-162).
 // `nw` is the NEGATED root (2^32 - w) and `wp` its Shoup companion floor(w 2^32 / q), so that
 // tn = h*q + y*nw = -(y*w - h*q) = -t (mod 2^32) with t in [0,2q), and both outputs are single adds:

@@ -150,6 +150,54 @@ __device__ __forceinline__ int quad_index(int t, int i)
     return ((t >> 6) << 10) + (i << 8) + ((t & 63) << 2);
 }
 
+// The way back: quad layout -> tile layout 0 (thread t owns coefficients 16t .. 16t+15), for a kernel whose INPUT row
+// feeds a transform that starts in tile layout 0 (intt_tiles).  Same region, same rows, accesses mirrored.
+template <int STRIDE>
+__device__ __forceinline__ void quads_to_tile(uint32_t (&x)[16], uint32_t *lds_region, int t)
+{
+    static_assert(STRIDE % 4 == 0 && STRIDE >= 16, "rows stay 16-byte aligned");
+    const int lane = t & 63;
+    uint32_t *w    = lds_region + (t >> 6) * (64 * STRIDE);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        const int q = 64 * i + lane;
+        *reinterpret_cast<uint4 *>(w + STRIDE * (q >> 2) + 4 * (q & 3)) =
+            make_uint4(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint4 *row = reinterpret_cast<const uint4 *>(w + STRIDE * lane);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        const uint4 v = row[c];
+        x[4 * c] = v.x, x[4 * c + 1] = v.y, x[4 * c + 2] = v.z, x[4 * c + 3] = v.w;
+    }
+}
+
+// Quad-layout accessors of one polynomial: every instruction of a wave covers 1 KiB contiguous.  One base pointer per
+// access (the thread's first quad) and compile-time offsets that land in the instructions' immediate fields.
+__device__ __forceinline__ void load_quads(uint32_t (&v)[16], const uint32_t *poly, int t)
+{
+    const uint32_t *base = poly + quad_index(t, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        const uint4 w = *reinterpret_cast<const uint4 *>(base + (i << 8));
+        v[4 * i] = w.x, v[4 * i + 1] = w.y, v[4 * i + 2] = w.z, v[4 * i + 3] = w.w;
+    }
+}
+
+__device__ __forceinline__ void store_quads(uint32_t *poly, const uint32_t (&v)[16], int t)
+{
+    uint32_t *base = poly + quad_index(t, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        *reinterpret_cast<uint4 *>(base + (i << 8)) = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+}
+
 // ------------------------------------------------------------------------------------------
 // Complex product (a + ib)(c + id) as the reference's build evaluates the C operator `*` on
 // `double complex` (fft.c:139, :205): Annex-G form x = ac - bd, y = ad + bc, one rounding per operation.

@@ -296,6 +296,57 @@ int se_amd_decrypt_full_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, cons
                                      as_stream(stream));
 }
 
+int se_amd_decrypt_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                double scale, int64_t *d_pte, float *d_values, double *d_values_f64,
+                                uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt_level(d_c0, d_c1, B, primes, scale, d_pte, d_values, d_values_f64, d_status,
+                                as_stream(stream));
+}
+
+int se_amd_decrypt_level_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                      size_t primes, double scale, const uint32_t *d_key_idx, int64_t *d_pte,
+                                      float *d_values, double *d_values_f64, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt_level_keyed(d_c0, d_c1, B, primes, scale, d_key_idx, d_pte, d_values, d_values_f64,
+                                      d_status, as_stream(stream));
+}
+
+int se_amd_ct_rescale_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes,
+                             uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_rescale(d_in0, d_in1, B, primes, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_mul_plain_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes,
+                               const uint32_t *d_pt, size_t P, size_t pt_primes, const uint32_t *d_pt_idx,
+                               uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mul_plain(d_in0, d_in1, B, primes, d_pt, P, pt_primes, d_pt_idx, d_out0, d_out1, d_status,
+                               as_stream(stream));
+}
+
+int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)
+{
+    seamd::HostParams hp;
+    if (!inv || primes < 2 || seamd::host_params_init(hp, degree, primes) != 0)
+    {
+        seamd::set_last_error("unsupported parameter set (degree, primes), or primes < 2");
+        return SE_ERR_INVALD_ARGUMENT;
+    }
+    const seamd::RescaleParams r = seamd::host_rescale_params(hp, primes);
+    for (size_t j = 0; j + 1 < primes; j++)
+    {
+        inv[j] = r.inv[j];
+        if (inv_shoup) inv_shoup[j] = r.inv_sh[j];
+    }
+    return SE_SUCCESS;
+}
+
 int se_amd_ct_lincomb_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t G,
                              const uint32_t *d_row_ptr, const uint32_t *d_idx, const int32_t *d_w, size_t nnz,
                              uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status, void *stream)

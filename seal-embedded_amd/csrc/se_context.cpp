@@ -1173,12 +1173,31 @@ int Context::decrypt_decode_keyed(const uint32_t *d_c0, const uint32_t *d_c1, si
 int Context::decrypt_full(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, int64_t *d_pte, float *d_values,
                           double *d_values_f64, uint8_t *d_status, hipStream_t st)
 {
+    return decrypt_level(d_c0, d_c1, B, hp.nprimes, hp.scale, d_pte, d_values, d_values_f64, d_status, st);
+}
+
+// The kernel takes its record stride and its scale from the by-value DevParams; the chain, the key rows and the Garner
+// constants of the first `primes` primes are those of the parameter set (n, primes).
+static bool level_params(const DevParams &dp, size_t np, size_t primes, double scale, DevParams &out)
+{
+    if (primes < 1 || primes > np || !(scale > 0) || scale == HUGE_VAL) return false;   // NaN fails scale > 0
+    out         = dp;
+    out.nprimes = (uint32_t)primes;
+    out.scale   = scale;
+    return true;
+}
+
+int Context::decrypt_level(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, double scale,
+                           int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st)
+{
     if (!have_sk)
     {
         set_last_error("decrypt needs the secret key (se_amd_set_secret_key)");
         return kErrNoKey;
     }
+    DevParams lp;
     if (!d_c0 || !d_c1 || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
+    if (!level_params(dp, hp.nprimes, primes, scale, lp)) return kErrInvalid;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     FullArgs fa{};
@@ -1188,7 +1207,7 @@ int Context::decrypt_full(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, 
     fa.values     = d_values;
     fa.values_f64 = d_values_f64;
     fa.status     = d_status;
-    SEAMD_HIP(launch_decrypt_full(dp, dt, crt, fa, B, st));
+    SEAMD_HIP(launch_decrypt_full(lp, dt, crt, fa, B, st));
     return 0;
 }
 
@@ -1198,13 +1217,23 @@ int Context::decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size
                                 int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status,
                                 hipStream_t st)
 {
+    return decrypt_level_keyed(d_c0, d_c1, B, hp.nprimes, hp.scale, d_key_idx, d_pte, d_values, d_values_f64, d_status,
+                               st);
+}
+
+int Context::decrypt_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, double scale,
+                                 const uint32_t *d_key_idx, int64_t *d_pte, float *d_values, double *d_values_f64,
+                                 uint8_t *d_status, hipStream_t st)
+{
     std::lock_guard<std::mutex> lk(mu);
     if (!ring_sk)
     {
         set_last_error("keyed decrypt needs a secret key ring (se_amd_set_secret_keyring)");
         return kErrNoKey;
     }
+    DevParams lp;
     if (!d_c0 || !d_c1 || !d_key_idx || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
+    if (!level_params(dp, hp.nprimes, primes, scale, lp)) return kErrInvalid;
     if (B == 0) return 0;
     KeyRejectArgs ra{};
     ra.status   = d_status;
@@ -1222,9 +1251,60 @@ int Context::decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size
     fa.values_f64 = d_values_f64;
     fa.status     = d_status;
     return keyed_call(d_key_idx, ring_sk, d_ring_sk, d_ring_sk, ra, B, st, [&](const KeyRing &ring) -> int {
-        SEAMD_HIP(launch_decrypt_full(dp, dt, crt, fa, B, st, &ring));
+        SEAMD_HIP(launch_decrypt_full(lp, dt, crt, fa, B, st, &ring));
         return 0;
     });
+}
+
+// Key-free, one launch, nothing of the context is written: level `primes` -> `primes` - 1 on one or two slabs.
+int Context::ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
+                        uint32_t *d_out1, hipStream_t st)
+{
+    if (!d_in0 || !d_out0 || !d_in1 != !d_out1) return kErrInvalid;
+    if (primes < 2 || primes > hp.nprimes || B > 0x7fffffffu) return kErrInvalid;
+    for (const void *p : {(const void *)d_in0, (const void *)d_in1, (const void *)d_out0, (const void *)d_out1})
+        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    RescaleArgs ra{};
+    ra.in0    = d_in0;
+    ra.in1    = d_in1;
+    ra.out0   = d_out0;
+    ra.out1   = d_out1;
+    ra.primes = (uint32_t)primes;
+    SEAMD_HIP(launch_ct_rescale(dp, dt, host_rescale_params(hp, primes), ra, B, st));
+    return 0;
+}
+
+// Key-free, one launch, nothing of the context is written.
+int Context::ct_mul_plain(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *d_pt,
+                          size_t P, size_t pt_primes, const uint32_t *d_pt_idx, uint32_t *d_out0, uint32_t *d_out1,
+                          uint8_t *d_status, hipStream_t st)
+{
+    constexpr size_t k32 = (size_t)1 << 32;
+    if (!d_in0 || !d_out0 || !d_pt || !d_in1 != !d_out1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes || pt_primes < primes || pt_primes >= k32) return kErrInvalid;
+    if (B >= k32 || P >= k32) return kErrInvalid;
+    if (!d_pt_idx && P != 1 && P != B) return kErrInvalid;
+    for (const void *p : {(const void *)d_in0, (const void *)d_in1, (const void *)d_out0, (const void *)d_out1,
+                          (const void *)d_pt})
+        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    MulPlainArgs ma{};
+    ma.in0       = d_in0;
+    ma.in1       = d_in1;
+    ma.out0      = d_out0;
+    ma.out1      = d_out1;
+    ma.pt        = d_pt;
+    ma.pt_idx    = d_pt_idx;
+    ma.status    = d_status;
+    ma.B         = (uint32_t)B;
+    ma.P         = (uint32_t)P;
+    ma.primes    = (uint32_t)primes;
+    ma.pt_primes = (uint32_t)pt_primes;
+    SEAMD_HIP(launch_ct_mul_plain(dp, ma, st));
+    return 0;
 }
 
 // Slices per output row of ct_lincomb.  A workgroup owns 1024 residues of one output row, so G rows give

@@ -171,6 +171,19 @@ struct Context
                      double *d_values_f64, uint8_t *d_status, hipStream_t st);
     int decrypt_full_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, const uint32_t *d_key_idx,
                            int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);
+    // the same on records of `primes` <= np primes, decoded with the caller's scale (the parameter set (n, primes) is
+    // a prefix of this one: same kernels, a DevParams copy with nprimes and scale replaced)
+    int decrypt_level(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, double scale, int64_t *d_pte,
+                      float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);
+    int decrypt_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, double scale,
+                            const uint32_t *d_key_idx, int64_t *d_pte, float *d_values, double *d_values_f64,
+                            uint8_t *d_status, hipStream_t st);
+    // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
+    int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
+                   uint32_t *d_out1, hipStream_t st);
+    int ct_mul_plain(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *d_pt,
+                     size_t P, size_t pt_primes, const uint32_t *d_pt_idx, uint32_t *d_out0, uint32_t *d_out1,
+                     uint8_t *d_status, hipStream_t st);
     // key-free weighted sums of records (kernels/kernel_args.h, LincombArgs)
     int ct_lincomb(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t G, const uint32_t *d_row_ptr,
                    const uint32_t *d_idx, const int32_t *d_w, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,

@@ -143,6 +143,20 @@ CrtParams host_crt_params(const HostParams &hp)
     return c;
 }
 
+RescaleParams host_rescale_params(const HostParams &hp, size_t primes)
+{
+    RescaleParams r;
+    memset(&r, 0, sizeof(r));
+    const uint32_t q_last = hp.q[primes - 1];
+    for (size_t j = 0; j + 1 < primes; j++)
+    {
+        const uint32_t inv = host_inv_mod(q_last % hp.q[j], hp.q[j]);
+        r.inv[j]           = inv;
+        r.inv_sh[j]        = (uint32_t)(((uint64_t)inv << 32) / hp.q[j]);
+    }
+    return r;
+}
+
 size_t bitrev(size_t x, size_t nbits)
 {
     size_t r = 0;

@@ -23,6 +23,8 @@ struct HostParams
 int host_params_init(HostParams &hp, size_t n, size_t nprimes);
 DevParams to_dev_params(const HostParams &hp);
 CrtParams host_crt_params(const HostParams &hp);  // Garner constants of the chain (exact integer arithmetic)
+// constants of the rescale from level `primes` (2 .. hp.nprimes): q_{primes-1}^-1 mod q_j, j < primes - 1
+RescaleParams host_rescale_params(const HostParams &hp, size_t primes);
 bool host_known_prime(uint32_t q);  // one of the tabulated 27-/30-bit primes (parameters.c:129-174)
 
 size_t bitrev(size_t x, size_t nbits);

@@ -35,6 +35,14 @@ struct CrtParams
     uint32_t inv_sh[kMaxPrimes];   // floor(inv * 2^32 / q_j)
 };
 
+// Constants of the key-free rescale (k_ct_rescale), passed BY VALUE to that kernel only.  For the level L the call drops
+// to L - 1 primes: inv[j] = q_{L-1}^-1 mod q_j and its Shoup companion, j < L - 1 (the other entries are 0).
+struct RescaleParams
+{
+    uint32_t inv[kMaxPrimes];
+    uint32_t inv_sh[kMaxPrimes];   // floor(inv * 2^32 / q_j)
+};
+
 // Device-resident read-only tables (pointers into one HBM slab owned by the context).
 struct DevTables
 {

@@ -1,0 +1,104 @@
+"""CPU-side checks of the rescale, the plaintext product and the level-aware decrypt: the entries are declared, exported
+and wrapped, the rescale constants are exact, the new ct_ops kernels compile for gfx950 without private memory, and the
+weighted-average example is plain C (no GPU needed)."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+ENTRIES = ("se_amd_ct_rescale_device", "se_amd_ct_mul_plain_device", "se_amd_decrypt_level_device",
+           "se_amd_decrypt_level_keyed_device", "se_amd_rescale_constants")
+METHODS = ("ct_rescale", "ct_mul_plain", "decrypt_level", "decrypt_level_keyed")
+KERNELS = ("k_ct_mul_plain",) + tuple(f"k_ct_rescale<{logn}>" for logn in range(10, 15))
+SE_ERR_INVALD_ARGUMENT = -22
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import __graft_entry__ as ge
+    p = ge.load_package()
+    p.build_library()
+    return p
+
+
+def test_header_declares_the_entries():
+    text = open(os.path.join(ROOT, "include", "seal_embedded_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for nm in ENTRIES:
+        assert re.search(r"\bint\s+%s\s*\(" % nm, text), nm
+
+
+def test_library_exports_the_entries(pkg):
+    L = pkg.lib()
+    for nm in ENTRIES:
+        assert nm in pkg.EXPORTED_SYMBOLS
+        assert hasattr(L, nm), nm
+
+
+def test_context_has_the_methods(pkg):
+    for nm in METHODS:
+        assert callable(getattr(pkg.Context, nm, None)), nm
+
+
+@pytest.mark.parametrize("shape", [(4096, 2), (4096, 3), (8192, 6), (16384, 13)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_rescale_constants_are_exact(pkg, shape):
+    """inv[j] . q_last = 1 (mod q_j) and the Shoup companion is floor(inv . 2^32 / q_j), in Python ints; nothing is
+    written beyond the primes - 1 entries."""
+    n, primes = shape
+    q = [int(x) for x in pkg.host_tables(n, primes)["q"]]
+    inv = np.full(primes + 2, 0xABABABAB, np.uint32)
+    sh = np.full(primes + 2, 0xCDCDCDCD, np.uint32)
+    L = pkg.lib()
+    assert L.se_amd_rescale_constants(n, primes, inv.ctypes.data, sh.ctypes.data) == 0
+    for j in range(primes - 1):
+        assert 0 < int(inv[j]) < q[j]
+        assert int(inv[j]) * q[-1] % q[j] == 1, j
+        assert int(sh[j]) == (int(inv[j]) << 32) // q[j], j
+    assert (inv[primes - 1:] == 0xABABABAB).all() and (sh[primes - 1:] == 0xCDCDCDCD).all()
+    # the Shoup companion is optional, and the wrapper returns the same numbers
+    alone = np.zeros(primes - 1, np.uint32)
+    assert L.se_amd_rescale_constants(n, primes, alone.ctypes.data, None) == 0
+    assert (alone == inv[:primes - 1]).all()
+    wi, ws = pkg.rescale_constants(n, primes)
+    assert (wi == inv[:primes - 1]).all() and (ws == sh[:primes - 1]).all()
+
+
+def test_rescale_constants_reject_bad_arguments(pkg):
+    L = pkg.lib()
+    buf = np.zeros(16, np.uint32)
+    assert L.se_amd_rescale_constants(4096, 1, buf.ctypes.data, None) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_rescale_constants(4096, 0, buf.ctypes.data, None) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_rescale_constants(4096, 4, buf.ctypes.data, None) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_rescale_constants(1000, 2, buf.ctypes.data, None) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_rescale_constants(4096, 3, None, None) == SE_ERR_INVALD_ARGUMENT
+    assert not buf.any()
+
+
+def test_new_kernels_use_no_scratch():
+    """Every degree of the rescale kernel and the product kernel exists; the 16 signed values a rescale thread carries
+    across the prime loop, its transform tile and the input row all stay in registers."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), "ct_ops"],
+                         capture_output=True, text=True, timeout=1200).stdout
+    rows = {}
+    for line in out.splitlines()[1:]:
+        f = line.split()
+        if len(f) >= 6:
+            rows[" ".join(f[:-5]).replace("seamd::", "")] = (int(f[-5]), int(f[-3]), int(f[-2]))  # VGPR, scratch, occ
+    assert rows, out
+    for k in KERNELS:
+        assert k in rows, (k, sorted(rows))
+        vgpr, scratch, occ = rows[k]
+        print(f"{k}: {vgpr} VGPRs, {scratch} B scratch, {occ} waves/SIMD")
+        assert scratch == 0, (k, rows[k])
+
+
+def test_weighted_average_example_compiles_as_plain_c(tmp_path):
+    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-c",
+                    os.path.join(ROOT, "examples", "weighted_average_roundtrip.c"),
+                    "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
+                    "-o", str(tmp_path / "weighted_average_roundtrip.o")], check=True)
