@@ -7,15 +7,8 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import __graft_entry__ as ge
-    p = ge.load_package()
-    p.build_library()
-    return p
+from build_support import ROOT, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from gpu_support import check_host_tables
 
 
 def declared_functions():
@@ -95,13 +88,13 @@ int main(void)
     return !(f1 && f2 && f3 && f4 && f5);
 }
 """)
-    subprocess.check_call(["gcc", "-std=gnu11", *flags, "-c", str(src), "-o", str(tmp_path / "t.o")])
+    compat = ("-I" + os.path.join(inc, "compat"),)
+    compile_only(src, tmp_path, extra=compat)
     cxx = tmp_path / "t.cpp"
     cxx.write_text('#include "seal_embedded.h"\n#include "ckks_sym.h"\nint main(){ SE_PRNG p; prng_clear(&p); return 0; }\n')
     subprocess.check_call(["g++", "-std=c++17", *flags, "-c", str(cxx), "-o", str(tmp_path / "t2.o")])
     for name in ("lower_sym_caller", "lower_asym_caller"):
-        subprocess.check_call(["gcc", "-std=gnu11", *flags, "-c", os.path.join(ROOT, "tests", "c", name + ".c"),
-                               "-o", str(tmp_path / (name + ".o"))])
+        compile_only(os.path.join(ROOT, "tests", "c", name + ".c"), tmp_path, extra=compat)
 
 
 def test_header_cites_reference_interfaces():
@@ -212,40 +205,8 @@ def test_examples_compile_as_plain_c(tmp_path):
 
 @pytest.mark.parametrize("shape", [(1024, 1), (2048, 1), (4096, 3), (8192, 6), (16384, 13)])
 def test_host_tables_match_oracle_and_golden(pkg, shape):
-    """The setup-time tables the context uploads (host logic, no GPU): parameter set, index map,
-    libm IFFT roots (bit-exact doubles; digest pinned to the reference build host), NTT
-    roots + Shoup companions, inverse roots."""
-    import hashlib
-    import json
-    import numpy as np
-    from oracle.pyoracle import Oracle
-    n, npr = shape
-    t = pkg.host_tables(n, npr)
-    o = Oracle(n, npr)
-    assert [int(x) for x in t["q"]] == [int(o.p.q[j]) for j in range(npr)]
-    assert [(int(a), int(b)) for a, b in t["const_ratio"]] == \
-        [(int(o.p.cr_lo[j]), int(o.p.cr_hi[j])) for j in range(npr)]
-    for j in range(npr):
-        q = int(t["q"][j])
-        cr = (int(t["const_ratio"][j][1]) << 32) | int(t["const_ratio"][j][0])
-        assert cr == (1 << 64) // q
-    assert t["scale"] == o.p.scale
-    assert (t["index_map"] == o.map).all()
-    tw = o.twiddles()
-    assert t["ifft_w"].ravel().tobytes() == tw.tobytes()
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dig = json.load(open(os.path.join(root, "tests", "golden", "golden_digests.json")))["ifft_twiddle_sha256"]
-    assert hashlib.sha256(t["ifft_w"].astype("<f8").tobytes()).hexdigest() == dig[str(n)]
-    for j in range(npr):
-        q = int(t["q"][j])
-        r = t["ntt_rw"][j, :, 0].astype(np.uint64)
-        assert (r == o.ntt_roots(j)).all()
-        assert (t["ntt_rw"][j, :, 1].astype(np.uint64) == (r << np.uint64(32)) // np.uint64(q)).all()
-        ir = t["intt_rw"][j, :, 0].astype(np.uint64)
-        assert ((r * ir) % np.uint64(q) == 1).all()       # same bit-reversed slot: psi^i * psi^-i
-        assert (t["intt_rw"][j, :, 1].astype(np.uint64) == (ir << np.uint64(32)) // np.uint64(q)).all()
-    with pytest.raises(pkg.SealEmbeddedAmdError):
-        pkg.host_tables(3000, 1)
+    """Every setup-time table the context uploads (host logic, no GPU): gpu_support.check_host_tables."""
+    check_host_tables(pkg, shape)
 
 
 def _hot_path_has_no_scratch(root):
@@ -280,17 +241,8 @@ def test_hot_kernels_keep_their_register_budget():
     n <= 8192 and the split kernels do not spill, and at n = 4096 the symmetric / encode-only forms fit
     4 workgroups per CU (<= 128 VGPRs), the public-key form 3 (<= 168 VGPRs: round 4, global addresses formed per
     prime from an opaque thread index instead of being carried across the prime loop -- 206 VGPRs before)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "tools", "resource_usage.py"), "encode_encrypt"],
-                         capture_output=True, text=True, timeout=900).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 6:
-            rows[" ".join(f[:-5])] = (int(f[-5]), int(f[-3]), int(f[-2]))     # VGPRs, scratch bytes, waves/SIMD
-    assert len(rows) > 30, out
+    rows = resource_rows("encode_encrypt")
+    assert len(rows) > 30, rows
     for logn in (10, 11, 12, 13):
         for mode in (0, 1, 2):
             vgpr, scratch, occ = rows[f"k_encode_encrypt<{logn}, {mode}>"]
@@ -301,7 +253,7 @@ def test_hot_kernels_keep_their_register_budget():
                 assert scratch <= 96, (logn, mode, scratch)
             else:
                 assert scratch == 0, (logn, mode, scratch)
-    _hot_path_has_no_scratch(root)
+    _hot_path_has_no_scratch(ROOT)
     for mode in (0, 2):
         assert rows[f"k_encode_encrypt<12, {mode}>"][0] <= 128 and rows[f"k_encode_encrypt<12, {mode}>"][2] >= 4
     assert rows["k_encode_encrypt<12, 1>"][0] <= 168 and rows["k_encode_encrypt<12, 1>"][2] >= 3
@@ -312,13 +264,8 @@ def test_hot_kernels_keep_their_register_budget():
         assert rows[k][1] == 0, (k, rows[k])
     # the samplers: the batch form of the chain kernel at 160 VGPRs without spills (its per-lane-prime form must
     # not leak into it), the staged kernels light enough to sit beside a transform workgroup
-    out = subprocess.run([sys.executable, os.path.join(root, "tools", "resource_usage.py"), "samplers"],
-                         capture_output=True, text=True, timeout=900).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 6:
-            rows[" ".join(f[:-5]).replace("seamd::", "")] = (int(f[-5]), int(f[-3]), int(f[-2]))
+    rows = resource_rows("samplers")
+    assert rows, "tools/resource_usage.py gave no table for samplers"
     assert rows["k_sample_uniform<12, 512, false>"][0] <= 168 and rows["k_sample_uniform<12, 512, false>"][1] == 0
     assert rows["k_sample_uniform<14, 512, false>"][1] == 0
     for k, vg in (("k_bulk_pair<14>", 80), ("k_bulk_pair<12>", 80), ("k_candidates", 80), ("k_resolve_light<14>", 40),

@@ -2,47 +2,29 @@
 and wrapped, the rescale constants are exact, the new ct_ops kernels compile for gfx950 without private memory, and the
 weighted-average example is plain C (no GPU needed)."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from gpu_support import SE_ERR_INVALD_ARGUMENT
 
 ENTRIES = ("se_amd_ct_rescale_device", "se_amd_ct_mul_plain_device", "se_amd_decrypt_level_device",
            "se_amd_decrypt_level_keyed_device", "se_amd_rescale_constants")
 METHODS = ("ct_rescale", "ct_mul_plain", "decrypt_level", "decrypt_level_keyed")
 KERNELS = ("k_ct_mul_plain",) + tuple(f"k_ct_rescale<{logn}>" for logn in range(10, 15))
-SE_ERR_INVALD_ARGUMENT = -22
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import __graft_entry__ as ge
-    p = ge.load_package()
-    p.build_library()
-    return p
-
-
-def test_header_declares_the_entries():
-    text = open(os.path.join(ROOT, "include", "seal_embedded_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for nm in ENTRIES:
-        assert re.search(r"\bint\s+%s\s*\(" % nm, text), nm
+def test_header_declares_the_entries(pkg):
+    assert_entries(pkg, ENTRIES)
 
 
 def test_library_exports_the_entries(pkg):
-    L = pkg.lib()
-    for nm in ENTRIES:
-        assert nm in pkg.EXPORTED_SYMBOLS
-        assert hasattr(L, nm), nm
+    assert_entries(pkg, ENTRIES)
 
 
 def test_context_has_the_methods(pkg):
-    for nm in METHODS:
-        assert callable(getattr(pkg.Context, nm, None)), nm
+    assert_entries(pkg, (), methods=METHODS)
 
 
 @pytest.mark.parametrize("shape", [(4096, 2), (4096, 3), (8192, 6), (16384, 13)], ids=lambda s: f"{s[0]}x{s[1]}")
@@ -82,14 +64,8 @@ def test_rescale_constants_reject_bad_arguments(pkg):
 def test_new_kernels_use_no_scratch():
     """Every degree of the rescale kernel and the product kernel exists; the 16 signed values a rescale thread carries
     across the prime loop, its transform tile and the input row all stay in registers."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), "ct_ops"],
-                         capture_output=True, text=True, timeout=1200).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 6:
-            rows[" ".join(f[:-5]).replace("seamd::", "")] = (int(f[-5]), int(f[-3]), int(f[-2]))  # VGPR, scratch, occ
-    assert rows, out
+    rows = resource_rows("ct_ops")
+    assert rows, "tools/resource_usage.py gave no table for ct_ops"
     for k in KERNELS:
         assert k in rows, (k, sorted(rows))
         vgpr, scratch, occ = rows[k]
@@ -98,7 +74,4 @@ def test_new_kernels_use_no_scratch():
 
 
 def test_weighted_average_example_compiles_as_plain_c(tmp_path):
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-c",
-                    os.path.join(ROOT, "examples", "weighted_average_roundtrip.c"),
-                    "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
-                    "-o", str(tmp_path / "weighted_average_roundtrip.o")], check=True)
+    compile_only(os.path.join(ROOT, "examples", "weighted_average_roundtrip.c"), tmp_path, hip=True)

@@ -1,54 +1,29 @@
 """CPU-side checks of the full-modulus decrypt: the entries are declared and exported, the k_decrypt_full kernels exist
 for every degree within their scratch budgets, and the host's recombination constants are exact (no GPU needed)."""
 import os
-import re
-import subprocess
-import sys
 
 import pytest
 
 import vectors as V
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from gpu_support import SE_ERR_INVALD_ARGUMENT
 
 FULL_ENTRIES = ("se_amd_decrypt_full_device", "se_amd_decrypt_full_keyed_device")
 SHAPES = V.ALL_SHAPES + [(16384, 13), (4096, 2), (4096, 1), (8192, 3)]
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import __graft_entry__ as ge
-    p = ge.load_package()
-    p.build_library()
-    return p
-
-
-def test_header_declares_full_entries():
-    text = open(os.path.join(ROOT, "include", "seal_embedded_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for nm in FULL_ENTRIES:
-        assert re.search(r"\bint\s+%s\s*\(" % nm, text), nm
+def test_header_declares_full_entries(pkg):
+    assert_entries(pkg, FULL_ENTRIES)
 
 
 def test_library_exports_full_entries(pkg):
-    L = pkg.lib()
-    for nm in FULL_ENTRIES:
-        assert nm in pkg.EXPORTED_SYMBOLS
-        assert hasattr(L, nm), nm
-    ctx_cls = pkg.Context
-    assert hasattr(ctx_cls, "decrypt_full") and hasattr(ctx_cls, "decrypt_full_keyed")
+    assert_entries(pkg, FULL_ENTRIES, methods=("decrypt_full", "decrypt_full_keyed"))
 
 
 @pytest.fixture(scope="module")
 def rows():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), "encode_encrypt"],
-                         capture_output=True, text=True, timeout=1200).stdout
-    r = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 6:
-            r[" ".join(f[:-5]).replace("seamd::", "")] = (int(f[-5]), int(f[-3]), int(f[-2]))   # VGPR, scratch, occ
-    assert r, out
+    r = resource_rows("encode_encrypt")
+    assert r, "tools/resource_usage.py gave no table for encode_encrypt"
     return r
 
 
@@ -96,13 +71,10 @@ def test_crt_constants_reject_unsupported_shapes(pkg):
     import numpy as np
     L = pkg.lib()
     buf = np.zeros(16, np.uint32)
-    assert L.se_amd_crt_constants(4096, 4, buf.ctypes.data, None) == -22
-    assert L.se_amd_crt_constants(1000, 1, buf.ctypes.data, None) == -22
-    assert L.se_amd_crt_constants(4096, 3, None, None) == -22
+    assert L.se_amd_crt_constants(4096, 4, buf.ctypes.data, None) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_crt_constants(1000, 1, buf.ctypes.data, None) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_crt_constants(4096, 3, None, None) == SE_ERR_INVALD_ARGUMENT
 
 
 def test_roundtrip_example_compiles_as_plain_c(tmp_path):
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-c",
-                    os.path.join(ROOT, "examples", "batch_roundtrip.c"), "-I" + os.path.join(ROOT, "include"),
-                    "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-o", str(tmp_path / "batch_roundtrip.o")],
-                   check=True)
+    compile_only(os.path.join(ROOT, "examples", "batch_roundtrip.c"), tmp_path, hip=True)

@@ -7,43 +7,16 @@ import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, bits, decode_expect, dev_t, encrypt_sym, env, expectation,  # noqa: F401
+                         host_u32, ntt_secret, run_decrypt, stream_of)
 
 pytestmark = pytest.mark.gpu
 
-SE_ERR_INVALD_ARGUMENT = -22
 SENTINEL = 0x5A5A5A5A
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
 SPLITS = (0, 1, 2, 7, 64)      # 0 = the automatic choice; 64 is more slices than most rows have entries
 B_CONSTRUCTED = 40
 ALL_MAX = (3, 17)              # the records whose residues are all q_j - 1
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback exists)")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg, dev=torch.device("cuda:0"))
-
-
-def dev_t(env, a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return env["torch"].from_numpy(a).to(env["dev"])
-
-
-def host_u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
 # ---- the expectation -------------------------------------------------------------------------------------------------
@@ -264,7 +237,7 @@ def test_empty_batch_rows(env):
     out0 = torch.full((2, 1, 1024), SENTINEL, dtype=torch.int32, device=env["dev"])
     st = torch.full((2,), 77, dtype=torch.uint8, device=env["dev"])
     ptr, idx = dev_t(env, np.array([0, 0, 2], dtype=np.uint32)), dev_t(env, np.array([0, 1], dtype=np.uint32))
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = stream_of(env)
     p = lambda t: C.c_void_p(t.data_ptr())
     rc = ctx.L.se_amd_ct_lincomb_device(ctx.h, p(anchor), None, 0, 2, p(ptr), p(idx), None, 2, p(out0), None, p(st),
                                         stream)
@@ -291,7 +264,7 @@ def test_argument_errors(env, constructed):
     idx = dev_t(env, np.array([0, 1, 2, 3], dtype=np.uint32))
     w = dev_t(env, np.array([1, 2, 3, 4], dtype=np.int32))
     wd = dev_t(env, np.ones(G * B, dtype=np.int32))
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = stream_of(env)
     p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     z = C.c_void_p(None)
     f = L.se_amd_ct_lincomb_device
@@ -358,7 +331,6 @@ def test_offsets_beyond_4gib(env):
 
 # ---- end to end: encrypt, aggregate without a key, decrypt ----------------------------------------------------------
 def aggregate_and_decrypt(env, ctx, c0, c1, rows):
-    import test_gpu_decrypt_full as DF
     torch = env["torch"]
     G = len(rows)
     ptr, idx, w = csr(rows)
@@ -368,13 +340,7 @@ def aggregate_and_decrypt(env, ctx, c0, c1, rows):
     ctx.ct_lincomb(c0, s0, c1, s1, row_ptr=dev_t(env, ptr), idx=dev_t(env, idx), w=dev_t(env, w), status=st)
     torch.cuda.synchronize()
     assert bool((st == 1).all())
-    return DF.run_full(env, ctx, s0, s1)
-
-
-def decode_expect(o, pte):
-    """The decode of test_gpu_decrypt_full.expectation() on an int64 plaintext."""
-    res = o.fft((pte / o.scale).astype(np.complex128))
-    return np.ascontiguousarray(res.real[o.map[:o.n // 2].astype(np.int64)])
+    return run_decrypt(env, ctx, s0, s1)
 
 
 def weighted_rows(rng, G, B, wmax, longest):
@@ -408,14 +374,13 @@ def check_against_pte(env, ctx, o, c0, c1, pte, rows, bound):
 def test_end_to_end_symmetric(env, seeded):
     """Test 8: 4096 x 3, 24 records of bench_values, G = 5 rows of at most 24 entries, |w| <= 2^20.  Per coefficient
     |m + e| <= 25.5 . 2^25 + 21 < 2^30, so every sum is below 2^30 . 2^20 . 24 < 2^55 < min(2^63, Q/2)."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     torch = env["torch"]
     n, npr, B = 4096, 3, 24
     ctx = env["pkg"].Context(n, npr)
     ctx.set_secret_key(V.secret_key(n))
     vals = V.bench_values(B, n, first=40)
-    c0, c1, pte, st = DF.encrypt_sym(env, ctx, vals, first=40)
+    c0, c1, pte, st = encrypt_sym(env, ctx, vals, first=40)
     assert bool((st == 1).all())
     if seeded:
         ss, sd = V.bench_seeds(B, first=40)
@@ -435,13 +400,12 @@ def test_end_to_end_symmetric(env, seeded):
 def test_end_to_end_single_prime(env):
     """Test 9: 1024 x 1, 8 records of pattern 7, weights in [-4, 4]: |sum| <= 8 . 4 . (0.15 . 2^20 + 21) ~ 4.8 . 2^20,
     below Q / 2 ~ 2^26."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     n, npr, B = 1024, 1, 8
     ctx = env["pkg"].Context(n, npr)
     ctx.set_secret_key(V.secret_key(n))
     vals = np.stack([V.pattern_values(7, n, seed=7 + b) for b in range(B)]).astype(np.float32)
-    c0, c1, pte, st = DF.encrypt_sym(env, ctx, vals, first=60)
+    c0, c1, pte, st = encrypt_sym(env, ctx, vals, first=60)
     assert bool((st == 1).all())
     o = Oracle(n, npr)
     rng = np.random.default_rng(9)
@@ -456,7 +420,6 @@ def test_end_to_end_single_prime(env):
 def test_end_to_end_public_key(env):
     """Test 10: 4096 x 3, 16 records under one generated key pair: decrypt_full(sum w ct) == sum w y_b, y_b the
     oracle's decrypt, inverse NTT and CRT of each input record."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     torch = env["torch"]
     n, npr, B = 4096, 3, 16
@@ -473,9 +436,9 @@ def test_end_to_end_public_key(env):
     torch.cuda.synchronize()
     assert bool((st == 1).all())
     o = Oracle(n, npr)
-    s_hat = DF.ntt_secret(o, sk[0])
+    s_hat = ntt_secret(o, sk[0])
     h0, h1 = host_u32(c0), host_u32(c1)
-    y = [np.array(DF.expectation(o, h0[b], h1[b], s_hat)["y"], dtype=object) for b in range(B)]
+    y = [np.array(expectation(o, h0[b], h1[b], s_hat)["y"], dtype=object) for b in range(B)]
     rows = weighted_rows(np.random.default_rng(10), 4, B, 2 ** 20, 16)
     got = aggregate_and_decrypt(env, ctx, c0, c1, rows)
     for g, (idx, w) in enumerate(rows):

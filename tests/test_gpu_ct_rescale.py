@@ -5,7 +5,6 @@ integers, never from the code under test; every comparison is bit-exact except t
 |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below
 Oracle(n, L): the default chains are prefixes of one another."""
 import ctypes as C
-import os
 import re
 import subprocess
 
@@ -13,46 +12,14 @@ import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, build_example, dev_t,  # noqa: F401
+                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, same_bytes,
+                         stream_of)
 
 pytestmark = pytest.mark.gpu
 
-SE_ERR_INVALD_ARGUMENT = -22
-SE_ERR_NO_KEY = -1002
 SENTINEL = 0x5A5A5A5A
 WEIGHT_BITS = 30
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback exists)")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg, dev=torch.device("cuda:0"))
-
-
-def dev_t(env, a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return env["torch"].from_numpy(a).to(env["dev"])
-
-
-def host_u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
-def stream_of(env):
-    return C.c_void_p(env["torch"].cuda.current_stream().cuda_stream)
 
 
 # ---- expectations ----------------------------------------------------------------------------------------------------
@@ -79,19 +46,6 @@ def rescale_expect(o, slab):
     return out
 
 
-def level_expect(o, c0, c1, s_hat, scale):
-    """test_gpu_decrypt_full.expectation() on a record of o.np primes, decoded with `scale`."""
-    import test_gpu_decrypt_full as DF
-    pts = [o.intt(o.decrypt(c0[j], c1[j], s_hat[j], j), j) for j in range(o.np)]
-    y = DF.crt_centred(o, pts)
-    if not all(-2 ** 63 <= v < 2 ** 63 for v in y):
-        return dict(status=0, pte=None, y=y)
-    pte = np.array(y, dtype=np.int64)
-    res = o.fft((pte / scale).astype(np.complex128))
-    f64 = np.ascontiguousarray(res.real[o.map[:o.n // 2].astype(np.int64)])
-    return dict(status=1, pte=pte, y=y, values_f64=f64, values=f64.astype(np.float32))
-
-
 def run_rescale(env, ctx, in0, in1, primes):
     """One call; the outputs carry two extra rows behind the packed [B][primes-1][n] result, pre-filled with a
     sentinel that must survive.  -> out0, out1 | None (host uint32 [B][primes-1][n])."""
@@ -115,26 +69,6 @@ def run_rescale(env, ctx, in0, in1, primes):
         assert (h[words:] == SENTINEL).all(), "rows behind the result are not written"
         res.append(h[:words].reshape(B, primes - 1, n))
     return res
-
-
-def run_level(env, ctx, c0, c1, primes, scale, key_idx=None, want=("pte", "values", "values_f64", "status")):
-    torch = env["torch"]
-    B, n = c0.shape[0], ctx.n
-    out = dict(pte=torch.full((B, n), -7, dtype=torch.int64, device=env["dev"]),
-               values=torch.full((B, n // 2), -7.0, dtype=torch.float32, device=env["dev"]),
-               values_f64=torch.full((B, n // 2), -7.0, dtype=torch.float64, device=env["dev"]),
-               status=torch.full((B,), 77, dtype=torch.uint8, device=env["dev"]))
-    kw = {k: out[k] for k in want}
-    if key_idx is None:
-        ctx.decrypt_level(c0, c1, primes, scale, **kw)
-    else:
-        ctx.decrypt_level_keyed(c0, c1, key_idx, primes, scale, **kw)
-    torch.cuda.synchronize()
-    return out
-
-
-def same_bytes(a, b):
-    return a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
 # ---- test 1: the rescale on arbitrary slabs -------------------------------------------------------------------------
@@ -251,24 +185,23 @@ def test_rescale_exact_integer_identity(env, shape):
     """Test 2: with y, y' the oracle's centred CRT values of a symmetric ciphertext before and after the rescale and
     delta_i the oracle's centred INTT of the last-prime rows, q_last . y' + delta_0 + (delta_1 * s) == y as integers,
     for every coefficient.  No model of the rescale is involved."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     n, npr = shape
     B = 2
     ctx = env["pkg"].Context(n, npr)
     sk = V.secret_key(n)
     ctx.set_secret_key(sk)
-    c0, c1, _, st = DF.encrypt_sym(env, ctx, V.bench_values(B, n, first=3), first=3)
+    c0, c1, _, st = encrypt_sym(env, ctx, V.bench_values(B, n, first=3), first=3)
     assert bool((st == 1).all())
     r0, r1 = run_rescale(env, ctx, c0, c1, npr)
     o, lo = Oracle(n, npr), Oracle(n, npr - 1)
-    s_hat = DF.ntt_secret(o, sk)
+    s_hat = ntt_secret(o, sk)
     s_nat = ternary_natural(o, sk)
     h0, h1 = host_u32(c0), host_u32(c1)
     q_last = o.q[-1]
     for b in range(B):
-        y = np.array(DF.expectation(o, h0[b], h1[b], s_hat)["y"], dtype=object)
-        y2 = np.array(DF.expectation(lo, r0[b], r1[b], s_hat[:npr - 1])["y"], dtype=object)
+        y = np.array(expectation(o, h0[b], h1[b], s_hat)["y"], dtype=object)
+        y2 = np.array(expectation(lo, r0[b], r1[b], s_hat[:npr - 1])["y"], dtype=object)
         d0 = centred(o.intt(h0[b, npr - 1], npr - 1), q_last)
         d1 = centred(o.intt(h1[b, npr - 1], npr - 1), q_last)
         lhs = q_last * y2 + d0.astype(object) + negacyclic(d1, s_nat).astype(object)
@@ -280,7 +213,6 @@ def test_rescale_exact_integer_identity(env, shape):
 @pytest.fixture(scope="module")
 def level_cases(env):
     """Per shape, computed once: four records encrypted under one key, on a context that keeps the key installed."""
-    import test_gpu_decrypt_full as DF
     cache = {}
 
     def get(shape):
@@ -289,9 +221,9 @@ def level_cases(env):
             ctx = env["pkg"].Context(n, npr)
             sk = V.secret_key(n)
             ctx.set_secret_key(sk)
-            recs = [r for r in DF.records(n) if r[0] in ("bench", "pattern8x100", "1e6", "pattern4")]
+            recs = [r for r in records(n) if r[0] in ("bench", "pattern8x100", "1e6", "pattern4")]
             vals = np.stack([v for _, v in recs]).astype(np.float32)
-            c0, c1, _, st = DF.encrypt_sym(env, ctx, vals, first=11)
+            c0, c1, _, st = encrypt_sym(env, ctx, vals, first=11)
             assert bool((st == 1).all())
             cache[shape] = dict(ctx=ctx, sk=sk, c0=c0, c1=c1, B=len(recs))
         return cache[shape]
@@ -303,11 +235,10 @@ def level_cases(env):
 
 def test_level_full_is_decrypt_full(env, level_cases):
     """Test 3a: primes = np and the context's scale give the bytes of decrypt_full on every output."""
-    import test_gpu_decrypt_full as DF
     c = level_cases((4096, 3))
     ctx = c["ctx"]
-    full = DF.run_full(env, ctx, c["c0"], c["c1"])
-    got = run_level(env, ctx, c["c0"], c["c1"], 3, ctx.scale())
+    full = run_decrypt(env, ctx, c["c0"], c["c1"])
+    got = run_decrypt(env, ctx, c["c0"], c["c1"], 3, ctx.scale())
     assert bool((full["status"] == 1).all())
     for f in ("pte", "values", "values_f64", "status"):
         assert same_bytes(got[f], full[f]), f
@@ -317,7 +248,6 @@ def test_level_full_is_decrypt_full(env, level_cases):
 def test_level_below_is_the_smaller_parameter_set(env, level_cases, shape):
     """Test 3b: the first np - 1 rows of each record, re-packed, at primes = np - 1: the bytes of decrypt_full on
     Context(n, np - 1) with the same key."""
-    import test_gpu_decrypt_full as DF
     n, npr = shape
     c = level_cases(shape)
     ctx = c["ctx"]
@@ -325,8 +255,8 @@ def test_level_below_is_the_smaller_parameter_set(env, level_cases, shape):
     small = env["pkg"].Context(n, npr - 1)
     small.set_secret_key(c["sk"])
     assert small.scale() == ctx.scale()
-    ref = DF.run_full(env, small, l0, l1)
-    got = run_level(env, ctx, l0, l1, npr - 1, ctx.scale())
+    ref = run_decrypt(env, small, l0, l1)
+    got = run_decrypt(env, ctx, l0, l1, npr - 1, ctx.scale())
     assert bool((ref["status"] == 1).all())
     for f in ("pte", "values", "values_f64", "status"):
         assert same_bytes(got[f], ref[f]), f
@@ -340,27 +270,26 @@ def test_level_one_is_the_single_prime_entry(env, level_cases):
     ctx, n, B = c["ctx"], 4096, c["B"]
     ref = torch.zeros((B, n // 2), dtype=torch.float32, device=env["dev"])
     ctx.decrypt_decode(c["c0"], c["c1"], 0, None, None, ref)
-    got = run_level(env, ctx, c["c0"][:, :1].contiguous(), c["c1"][:, :1].contiguous(), 1, ctx.scale())
+    got = run_decrypt(env, ctx, c["c0"][:, :1].contiguous(), c["c1"][:, :1].contiguous(), 1, ctx.scale())
     assert bool((got["status"] == 1).all())
     assert torch.equal(got["values"].view(torch.int32), ref.view(torch.int32))
 
 
 def test_level_scale_is_the_callers(env, level_cases):
     """Test 3d: scale = 2 . se_amd_scale: values_f64 (and the rest) equal the oracle expectation at that scale."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     c = level_cases((4096, 3))
     ctx = c["ctx"]
     o = Oracle(4096, 3)
-    s_hat = DF.ntt_secret(o, c["sk"])
+    s_hat = ntt_secret(o, c["sk"])
     scale = 2.0 * ctx.scale()
-    got = run_level(env, ctx, c["c0"], c["c1"], 3, scale)
+    got = run_decrypt(env, ctx, c["c0"], c["c1"], 3, scale)
     h0, h1 = host_u32(c["c0"]), host_u32(c["c1"])
     for b in range(c["B"]):
-        e = level_expect(o, h0[b], h1[b], s_hat, scale)
+        e = expectation(o, h0[b], h1[b], s_hat, scale)
         assert e["status"] == 1
-        DF.assert_matches(got, b, e, b)
-        half = level_expect(o, h0[b], h1[b], s_hat, ctx.scale())
+        assert_matches(got, b, e, b)
+        half = expectation(o, h0[b], h1[b], s_hat, ctx.scale())
         assert (bits(half["values_f64"] * 0.5) == bits(e["values_f64"])).all()      # a power of two: exact
 
 
@@ -390,12 +319,12 @@ def test_level_keyed_twin(env):
     l0, l1 = c0[:, :2].contiguous(), c1[:, :2].contiguous()
     bad = idx.copy()
     bad[7] = K
-    got = run_level(env, ctx, l0, l1, 2, scale, key_idx=dev_t(env, bad))
+    got = run_decrypt(env, ctx, l0, l1, 2, scale, key_idx=dev_t(env, bad))
     for k in range(K):
         sel = np.nonzero((idx == k) & (bad < K))[0]
         ts = torch.from_numpy(sel).to(env["dev"])
         ctx.set_secret_key(sk[k])
-        ref = run_level(env, ctx, l0.index_select(0, ts).contiguous(), l1.index_select(0, ts).contiguous(), 2, scale)
+        ref = run_decrypt(env, ctx, l0.index_select(0, ts).contiguous(), l1.index_select(0, ts).contiguous(), 2, scale)
         assert bool((ref["status"] == 1).all())
         for f in ("pte", "values", "values_f64", "status"):
             assert same_bytes(got[f].index_select(0, ts), ref[f]), (k, f)
@@ -598,13 +527,12 @@ def test_mul_plain_arguments(env):
 def check_level_records(env, ctx, lo, r0, r1, s_hat, primes, scale, want):
     """decrypt_level on the rescaled records against the oracle expectation on the same records, bit for bit; the
     reference's 0.1 first on the expectation, then on the GPU result.  -> the largest error of the GPU result."""
-    import test_gpu_decrypt_full as DF
-    got = run_level(env, ctx, dev_t(env, r0), dev_t(env, r1), primes, scale)
+    got = run_decrypt(env, ctx, dev_t(env, r0), dev_t(env, r1), primes, scale)
     worst = 0.0
     for b in range(r0.shape[0]):
-        e = level_expect(lo, r0[b], r1[b], s_hat[:primes], scale)
+        e = expectation(lo, r0[b], r1[b], s_hat[:primes], scale)
         assert e["status"] == 1
-        DF.assert_matches(got, b, e, b)
+        assert_matches(got, b, e, b)
         err_e = float(np.abs(e["values"].astype(np.float64) - want[b]).max())
         err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want[b]).max())
         print(f"record {b}: max |values - expected| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
@@ -619,7 +547,6 @@ def test_weighted_sum_end_to_end(env):
     on the aggregator's sum, pte / values / values_f64 equal the oracle's on that record, status is 1 and the result is
     within the reference's 0.1 of sum_k (round(w_k . 2^30) / 2^30) . v_k (a CPU simulation of noise, encode rounding
     and rescale rounding puts the error at 1.5e-4 .. 2.0e-4 for this shape)."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     torch = env["torch"]
     n, npr, B = 4096, 3, 16
@@ -627,7 +554,7 @@ def test_weighted_sum_end_to_end(env):
     sk = V.secret_key(n)
     ctx.set_secret_key(sk)
     vals = V.bench_values(B, n, first=50)
-    c0, c1, _, st = DF.encrypt_sym(env, ctx, vals, first=50)
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=50)
     assert bool((st == 1).all())
     rng = np.random.default_rng(5)
     w = np.rint(rng.uniform(-1.0, 1.0, B) * 2.0 ** WEIGHT_BITS).astype(np.int64)
@@ -643,7 +570,7 @@ def test_weighted_sum_end_to_end(env):
     assert (r0 == rescale_expect(o, host_u32(s0))).all() and (r1 == rescale_expect(o, host_u32(s1))).all()
     scale = o.scale * 2.0 ** WEIGHT_BITS / o.q[npr - 1]
     want = [(w.astype(np.float64) / 2.0 ** WEIGHT_BITS) @ vals.astype(np.float64)]
-    worst = check_level_records(env, ctx, lo, r0, r1, DF.ntt_secret(o, sk), npr - 1, scale, want)
+    worst = check_level_records(env, ctx, lo, r0, r1, ntt_secret(o, sk), npr - 1, scale, want)
     assert worst < 0.1
     ctx.close()
 
@@ -654,7 +581,6 @@ def test_slotwise_product_end_to_end(env, shape):
     rescale -> decrypt_level(primes = np - 1, scale = Delta^2 / q_last), bit-exact against the oracle on the rescaled
     records and within the reference's 0.1 of v (.) w (the same simulation gives 4.3e-3 at n = 4096, 2.2e-2 at
     n = 16384)."""
-    import test_gpu_decrypt_full as DF
     from oracle.pyoracle import Oracle
     torch = env["torch"]
     n, npr = shape
@@ -663,7 +589,7 @@ def test_slotwise_product_end_to_end(env, shape):
     sk = V.secret_key(n)
     ctx.set_secret_key(sk)
     vals = V.bench_values(B, n, first=70)
-    c0, c1, _, st = DF.encrypt_sym(env, ctx, vals, first=70)
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=70)
     assert bool((st == 1).all())
     wv = np.random.default_rng(6 + n).uniform(-1.0, 1.0, (B, n // 2)).astype(np.float32)
     pt = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
@@ -686,7 +612,7 @@ def test_slotwise_product_end_to_end(env, shape):
     assert (r0 == rescale_expect(o, host_u32(m0))).all() and (r1 == rescale_expect(o, host_u32(m1))).all()
     scale = o.scale * o.scale / q[npr - 1]
     want = [vals[b].astype(np.float64) * wv[b].astype(np.float64) for b in range(B)]
-    worst = check_level_records(env, ctx, lo, r0, r1, DF.ntt_secret(o, sk), npr - 1, scale, want)
+    worst = check_level_records(env, ctx, lo, r0, r1, ntt_secret(o, sk), npr - 1, scale, want)
     assert worst < 0.1
     ctx.close()
 
@@ -695,13 +621,7 @@ def test_slotwise_product_end_to_end(env, shape):
 def test_weighted_average_example(env, tmp_path):
     """examples/weighted_average_roundtrip.c from plain gcc: real weights through lincomb, rescale and decrypt_level
     come back within the reference's 0.1."""
-    lib = os.path.join(ROOT, "seal-embedded_amd", "lib")
-    exe = tmp_path / "weighted_average_roundtrip"
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror",
-                    os.path.join(ROOT, "examples", "weighted_average_roundtrip.c"),
-                    "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-L" + lib,
-                    "-lseal_embedded_amd", "-L/opt/rocm/lib", "-lamdhip64", "-lm", "-Wl,-rpath," + lib,
-                    "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)], check=True)
+    exe = build_example("weighted_average_roundtrip", tmp_path, hip=True, extra=("-lm",))
     r = subprocess.run([str(exe), "4096", "3", "16"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     m = re.search(r"failed=0 B=16 .*max_abs_error=([0-9.e+-]+)", r.stdout)

@@ -3,125 +3,17 @@ Every expectation is built from the oracle's primitives (decrypt, intt, fft) and
 under test; every comparison is bit-exact except the reference's own acceptance criterion |values - input| < 0.1
 (device/test/ckks_tests_common.c:132)."""
 import ctypes as C
+import re
+import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, build_example, dev_t,  # noqa: F401
+                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, stream_of)
 
 pytestmark = pytest.mark.gpu
-
-SE_ERR_INVALD_ARGUMENT = -22
-SE_ERR_NO_KEY = -1002
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback exists)")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg, dev=torch.device("cuda:0"))
-
-
-def dev_t(env, a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return env["torch"].from_numpy(a).to(env["dev"])
-
-
-def host_u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
-# ---- the expectation -------------------------------------------------------------------------------------------------
-def crt_centred(o, pts):
-    """pts[j][k] = value mod q_j  ->  Python ints in (-Q/2, Q/2], Q = prod q_j."""
-    Q = 1
-    for q in o.q:
-        Q *= q
-    acc = np.zeros(o.n, dtype=object)
-    for j, q in enumerate(o.q):
-        M = Q // q
-        acc = acc + pts[j].astype(object) * (M * pow(M % q, -1, q))
-    acc = acc % Q
-    return [int(v) - Q if int(v) > Q // 2 else int(v) for v in acc]
-
-
-def ntt_secret(o, sk):
-    return [o.ntt(o.expand_ternary(sk, j), j) for j in range(o.np)]
-
-
-def expectation(o, c0, c1, s_hat):
-    """c0, c1 [np][n] uint32 -> dict(status, pte int64 | None, values_f64, values) from the oracle and Python ints."""
-    pts = [o.intt(o.decrypt(c0[j], c1[j], s_hat[j], j), j) for j in range(o.np)]
-    y = crt_centred(o, pts)
-    ok = all(-2 ** 63 <= v < 2 ** 63 for v in y)
-    if not ok:
-        return dict(status=0, pte=None, y=y)
-    pte = np.array(y, dtype=np.int64)
-    res = o.fft((pte / o.scale).astype(np.complex128))
-    f64 = np.ascontiguousarray(res.real[o.map[:o.n // 2].astype(np.int64)])
-    return dict(status=1, pte=pte, y=y, values_f64=f64, values=f64.astype(np.float32))
-
-
-def run_full(env, ctx, c0, c1, key_idx=None, want=("pte", "values", "values_f64", "status")):
-    torch = env["torch"]
-    B, n = c0.shape[0], ctx.n
-    out = dict(pte=torch.full((B, n), -7, dtype=torch.int64, device=env["dev"]),
-               values=torch.full((B, n // 2), -7.0, dtype=torch.float32, device=env["dev"]),
-               values_f64=torch.full((B, n // 2), -7.0, dtype=torch.float64, device=env["dev"]),
-               status=torch.full((B,), 77, dtype=torch.uint8, device=env["dev"]))
-    kw = {k: out[k] for k in want}
-    if key_idx is None:
-        ctx.decrypt_full(c0, c1, **kw)
-    else:
-        ctx.decrypt_full_keyed(c0, c1, key_idx, **kw)
-    torch.cuda.synchronize()
-    return out
-
-
-def assert_matches(got, b, exp, what):
-    assert int(got["status"][b]) == exp["status"], (what, "status")
-    if exp["status"] != 1:
-        return
-    assert (got["pte"][b].cpu().numpy() == exp["pte"]).all(), (what, "pte")
-    assert (bits(got["values_f64"][b].cpu().numpy()) == bits(exp["values_f64"])).all(), (what, "values_f64")
-    assert (bits(got["values"][b].cpu().numpy()) == bits(exp["values"])).all(), (what, "values")
-
-
-def records(n):
-    """The records of the issue's table plus the reference's small patterns."""
-    half = n // 2
-    return [("bench", V.bench_values(1, n)[0]),
-            ("pattern8x100", V.pattern_values(8, n) * np.float32(100)),
-            ("1e6", np.full(half, 1e6, dtype=np.float32)),
-            ("2.7e11", np.full(half, 2.7e11, dtype=np.float32)),
-            ("pattern4", V.pattern_values(4, n)),
-            ("survey", V.survey_values(n))]
-
-
-def encrypt_sym(env, ctx, vals, first=0):
-    torch = env["torch"]
-    B, n, npr = vals.shape[0], ctx.n, ctx.np
-    ss, sd = V.bench_seeds(B, first=first)
-    c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
-    c1 = torch.zeros_like(c0)
-    pte = torch.zeros((B, n), dtype=torch.int64, device=env["dev"])
-    st = torch.zeros(B, dtype=torch.uint8, device=env["dev"])
-    ctx.encrypt_sym(dev_t(env, vals), dev_t(env, ss), dev_t(env, sd), c0, c1, pte=pte, status=st)
-    torch.cuda.synchronize()
-    return c0, c1, pte, st
-
 
 SHAPES = V.ALL_SHAPES + [(16384, 13), (4096, 2)]
 
@@ -143,7 +35,7 @@ def sym_cases(env):
         vals = np.stack([v for _, v in recs]).astype(np.float32)
         c0, c1, enc_pte, enc_st = encrypt_sym(env, ctx, vals)
         assert bool((enc_st == 1).all()), "every record encodes (|m| < 2^63)"
-        got = run_full(env, ctx, c0, c1)
+        got = run_decrypt(env, ctx, c0, c1)
         o = Oracle(n, npr)
         s_hat = ntt_secret(o, sk)
         h0, h1 = host_u32(c0), host_u32(c1)
@@ -220,7 +112,7 @@ def test_oracle_parity_public_key(env, shape):
     ctx.encrypt_asym(dev_t(env, vals), dev_t(env, V.derive_seeds("full-enc", B)), c0, c1, status=st)
     torch.cuda.synchronize()
     assert bool((st == 1).all())
-    got = run_full(env, ctx, c0, c1)
+    got = run_decrypt(env, ctx, c0, c1)
     o = Oracle(n, npr)
     s_hat = ntt_secret(o, sk[0])
     h0, h1 = host_u32(c0), host_u32(c1)
@@ -243,7 +135,7 @@ def test_wrong_key_is_flagged(env):
     c0, c1, _, _ = encrypt_sym(env, ctx, V.bench_values(2, n))
     other = V.secret_key(n, seed=2)
     ctx.set_secret_key(other)
-    got = run_full(env, ctx, c0, c1)
+    got = run_decrypt(env, ctx, c0, c1)
     o = Oracle(n, npr)
     s_hat = ntt_secret(o, other)
     h0, h1 = host_u32(c0), host_u32(c1)
@@ -274,7 +166,7 @@ def test_int64_boundary(env, shape):
     for b, v in enumerate((v_out, v_in)):
         for j in range(npr):
             c0[b, j] = o.ntt(np.array([x % o.q[j] for x in v], dtype=np.uint32), j)
-    got = run_full(env, ctx, dev_t(env, c0), dev_t(env, np.zeros_like(c0)))
+    got = run_decrypt(env, ctx, dev_t(env, c0), dev_t(env, np.zeros_like(c0)))
     assert int(got["status"][0]) == 0
     assert int(got["status"][1]) == 1
     assert (got["pte"][1].cpu().numpy() == np.array(v_in, dtype=np.int64)).all()
@@ -311,12 +203,12 @@ def test_keyed_equals_unkeyed(env, shape):
     torch.cuda.synchronize()
     bad = idx.copy()
     bad[7] = K
-    got = run_full(env, ctx, c0, c1, key_idx=dev_t(env, bad))
+    got = run_decrypt(env, ctx, c0, c1, key_idx=dev_t(env, bad))
     for k in np.unique(idx):
         sel = np.nonzero((idx == k) & (bad < K))[0]
         ts = torch.from_numpy(sel).to(env["dev"])
         ctx.set_secret_key(sk[int(k)])
-        ref = run_full(env, ctx, c0.index_select(0, ts).contiguous(), c1.index_select(0, ts).contiguous())
+        ref = run_decrypt(env, ctx, c0.index_select(0, ts).contiguous(), c1.index_select(0, ts).contiguous())
         assert bool((ref["status"] == 1).all())
         for f in ("pte", "status"):
             assert torch.equal(got[f].index_select(0, ts), ref[f]), (int(k), f)
@@ -337,7 +229,7 @@ def test_optional_outputs_and_arguments(env):
     ctx = pkg.Context(n, npr)
     L = ctx.L
     z = C.c_void_p(None)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = stream_of(env)
     vals = V.bench_values(B, n, first=9)
     vals[2] *= 300.0
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
@@ -348,9 +240,9 @@ def test_optional_outputs_and_arguments(env):
     assert L.se_amd_decrypt_full_device(ctx.h, p(c0), p(c1), B, z, z, z, p(st), stream) == SE_ERR_NO_KEY
     ctx.set_secret_key(V.secret_key(n))
     c0, c1, _, _ = encrypt_sym(env, ctx, vals, first=9)
-    full = run_full(env, ctx, c0, c1)
+    full = run_decrypt(env, ctx, c0, c1)
     for f in ("pte", "values", "values_f64", "status"):
-        alone = run_full(env, ctx, c0, c1, want=(f,))
+        alone = run_decrypt(env, ctx, c0, c1, want=(f,))
         assert alone[f].cpu().numpy().tobytes() == full[f].cpu().numpy().tobytes(), f
         for g in ("pte", "values", "values_f64", "status"):
             if g != f:      # an output that was not requested is not written
@@ -410,16 +302,7 @@ def test_full_size(env):
 
 def test_roundtrip_example(env, tmp_path):
     """examples/batch_roundtrip.c from plain gcc: values around +-1000 come back within the reference's 0.1."""
-    import os
-    import re
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "seal-embedded_amd", "lib")
-    exe = tmp_path / "batch_roundtrip"
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror", os.path.join(root, "examples", "batch_roundtrip.c"),
-                    "-I" + os.path.join(root, "include"), "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-L" + lib,
-                    "-lseal_embedded_amd", "-L/opt/rocm/lib", "-lamdhip64", "-lm", "-Wl,-rpath," + lib,
-                    "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)], check=True)
+    exe = build_example("batch_roundtrip", tmp_path, hip=True, extra=("-lm",))
     r = subprocess.run([str(exe), "4096", "3", "16"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     m = re.search(r"failed=0 B=16 .*max_abs_error=([0-9.e+-]+)", r.stdout)

@@ -6,31 +6,9 @@ import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import dev_t, env, host_u32  # noqa: F401  (env is a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback exists)")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg, dev=torch.device("cuda:0"))
-
-
-def dev_t(env, a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)     # key indices: the kernels read the same 32-bit words
-    return env["torch"].from_numpy(a).to(env["dev"])
-
-
-def host_u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def make_keys(ctx, K, tag="ring"):

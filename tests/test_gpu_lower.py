@@ -6,42 +6,15 @@ Nothing here reads /root/reference.
 """
 import ctypes as C
 import hashlib
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import SEED_EP, SEED_PK, build_caller, env  # noqa: F401  (env is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-
-SEED_PK = hashlib.shake_256(b"golden-pk").digest(64)
-SEED_EP = hashlib.shake_256(b"golden-ep").digest(64)
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback exists)")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg)
-
-
-def _build_caller(name, tmp_path):
-    exe = tmp_path / name
-    lib = os.path.join(ROOT, "seal-embedded_amd", "lib")
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra", "-Werror",
-                    os.path.join(ROOT, "tests", "c", name + ".c"), "-I" + inc,
-                    "-I" + os.path.join(inc, "compat"), "-L" + lib, "-lseal_embedded_amd",
-                    "-Wl,-rpath," + lib, "-o", str(exe)], check=True)
-    return exe
 
 
 def _sha(a):
@@ -53,7 +26,7 @@ def test_reference_style_sym_caller_matches_golden(env, golden, tmp_path, shape)
     """tests/c/lower_sym_caller.c (reference API names only, gcc) -> per-prime c0, c1_save, s_save,
     the aliased c1 buffer, m + e and the final PRNG counter equal the compiled reference's."""
     n, npr = shape
-    exe = _build_caller("lower_sym_caller", tmp_path)
+    exe = build_caller("lower_sym_caller", tmp_path)
     data = tmp_path / "adapter_output_data"
     data.mkdir()
     V.secret_key(n).tofile(data / f"sk_{n}.dat")
@@ -80,7 +53,7 @@ def test_reference_style_asym_caller_matches_golden(env, golden, tmp_path, shape
     """tests/c/lower_asym_caller.c: gen_pk per prime, ckks_asym_init, ckks_encode_encrypt_asym."""
     from oracle.pyoracle import Oracle
     n, npr = shape
-    exe = _build_caller("lower_asym_caller", tmp_path)
+    exe = build_caller("lower_asym_caller", tmp_path)
     data = tmp_path / "adapter_output_data"
     data.mkdir()
     sk = V.secret_key(n)

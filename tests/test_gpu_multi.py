@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import build_example, gpu_env
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,11 +36,7 @@ def env():
         buses.add((pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id))
     if len(buses) < 2:
         pytest.skip(f"needs >= 2 distinct GPUs, this box shows {len(buses)}")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg, ndev=ndev)
+    return dict(gpu_env(), ndev=ndev)
 
 
 def _oracle_records(n, npr, B, first, sk, mode, pk=None):
@@ -116,9 +113,8 @@ def test_c_program_over_all_devices(env, tmp_path):
     the peer-gathered slab with a single-device pass (gather_verified=1), and the digest equals the oracle's."""
     from oracle import pyoracle
     from oracle.pyoracle import Oracle
-    import test_gpu_parity as P
     n, npr, B = 1024, 1, 16 * env["ndev"] + 5
-    exe = P._build_example("multi_device_encrypt", tmp_path, hip=True)
+    exe = build_example("multi_device_encrypt", tmp_path, hip=True)
     sk = V.secret_key(n)
     skf = tmp_path / "sk.dat"
     sk.tofile(skf)

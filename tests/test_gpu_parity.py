@@ -12,35 +12,12 @@ import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import (SEED_A, SEED_B, SEED_EP, SEED_PK, build_example, check_host_tables, dev_t, env,  # noqa: F401
+                         host_u32)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
-
-SEED_A = hashlib.shake_256(b"golden-share").digest(64)
-SEED_B = hashlib.shake_256(b"golden-secret").digest(64)
-SEED_PK = hashlib.shake_256(b"golden-pk").digest(64)
-SEED_EP = hashlib.shake_256(b"golden-ep").digest(64)
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback exists)")
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    from oracle import pyoracle
-    pyoracle.build(ref=False)
-    return dict(torch=torch, pkg=pkg, dev=torch.device("cuda:0"))
-
-
-def dev_t(env, a):
-    return env["torch"].from_numpy(np.ascontiguousarray(a)).to(env["dev"])
-
-
-def host_u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def seeds_np(B, tag):
@@ -66,9 +43,8 @@ def test_t8_root_tables_on_this_box(env, golden, n):
 
 def test_t8_host_tables_match_oracle_on_this_box(env):
     """The CPU-suite check of every setup-time table (tests/test_cabi.py) repeated where the product runs."""
-    import test_cabi
     for shape in [(1024, 1), (4096, 3), (16384, 13)]:
-        test_cabi.test_host_tables_match_oracle_and_golden(env["pkg"], shape)
+        check_host_tables(env["pkg"], shape)
 
 
 # --------------------------------------------------------------------------- PRNG / Keccak
@@ -1438,19 +1414,6 @@ def test_reference_api_callback_stream(env, golden, tmp_path):
 
 
 # --------------------------------------------------------------------------- C callers (examples/)
-def _build_example(name, tmp_path, hip=False):
-    import subprocess
-    exe = tmp_path / name
-    lib = os.path.join(ROOT, "seal-embedded_amd", "lib")
-    cmd = ["gcc", "-std=gnu11", "-Wall", "-Werror", os.path.join(ROOT, "examples", name + ".c"),
-           "-I" + os.path.join(ROOT, "include"), "-L" + lib, "-lseal_embedded_amd", "-Wl,-rpath," + lib, "-o", str(exe)]
-    if hip:   # a C caller that owns device memory: the HIP runtime's C API, still plain gcc
-        cmd += ["-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-L/opt/rocm/lib", "-lamdhip64",
-                "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True)
-    return exe
-
-
 def _key_dir(env, tmp_path, n, npr, asym):
     data = tmp_path / f"adapter_output_data_{n}_{int(asym)}"
     data.mkdir()
@@ -1474,7 +1437,7 @@ def test_c_caller_of_reference_api_reproduces_reference_digest(env, golden, tmp_
     digest the compiled reference produced for the same input (golden, made by make_golden.py)."""
     import subprocess
     n, npr = shape
-    exe = _build_example("api_digest", tmp_path)
+    exe = build_example("api_digest", tmp_path)
     data = _key_dir(env, tmp_path, n, npr, mode == "asym")
     e = dict(os.environ, SE_AMD_DATA_PATH=str(data), SE_AMD_REFERENCE_C1_ALIAS="1")
     out = subprocess.run([str(exe), str(n), str(npr), mode], env=e, check=True, capture_output=True,
@@ -1499,7 +1462,7 @@ def test_c_caller_of_batch_entry(env, tmp_path, devices):
     from oracle import pyoracle
     from oracle.pyoracle import Oracle
     n, npr, B = 1024, 1, 7
-    exe = _build_example("batch_encrypt", tmp_path)
+    exe = build_example("batch_encrypt", tmp_path)
     data = _key_dir(env, tmp_path, n, npr, False)
     e = dict(os.environ, SE_AMD_DATA_PATH=str(data))
     inject = None
@@ -1559,7 +1522,7 @@ def test_c_caller_of_multi_device_entry(env, tmp_path, devices, B):
     from oracle import pyoracle
     from oracle.pyoracle import Oracle
     n, npr = 1024, 1
-    exe = _build_example("multi_device_encrypt", tmp_path, hip=True)
+    exe = build_example("multi_device_encrypt", tmp_path, hip=True)
     sk = V.secret_key(n)
     skf = tmp_path / "sk.dat"
     sk.tofile(skf)

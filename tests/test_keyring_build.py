@@ -1,50 +1,25 @@
 """CPU-side checks of the key-ring feature: the five entries are declared and exported, and the keyed twins of the
 encryption / decrypt kernels keep the register budgets of the unkeyed kernels (no GPU needed)."""
-import os
-import re
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_support import assert_entries, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
 
 KEYRING_ENTRIES = ("se_amd_set_secret_keyring", "se_amd_set_public_keyring", "se_amd_encrypt_sym_keyed_device",
                    "se_amd_encrypt_asym_keyed_device", "se_amd_decrypt_decode_keyed_device")
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import __graft_entry__ as ge
-    p = ge.load_package()
-    p.build_library()
-    return p
-
-
-def test_header_declares_keyring_entries():
-    text = open(os.path.join(ROOT, "include", "seal_embedded_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for nm in KEYRING_ENTRIES:
-        assert re.search(r"\bint\s+%s\s*\(" % nm, text), nm
+def test_header_declares_keyring_entries(pkg):
+    assert_entries(pkg, KEYRING_ENTRIES)
 
 
 def test_library_exports_keyring_entries(pkg):
-    L = pkg.lib()
-    for nm in KEYRING_ENTRIES:
-        assert nm in pkg.EXPORTED_SYMBOLS
-        assert hasattr(L, nm), nm
+    assert_entries(pkg, KEYRING_ENTRIES)
 
 
 @pytest.fixture(scope="module")
 def rows():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), "encode_encrypt"],
-                         capture_output=True, text=True, timeout=1200).stdout
-    r = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 6:
-            r[" ".join(f[:-5]).replace("seamd::", "")] = (int(f[-5]), int(f[-3]), int(f[-2]))   # VGPR, scratch, occ
-    assert r, out
+    r = resource_rows("encode_encrypt")
+    assert r, "tools/resource_usage.py gave no table for encode_encrypt"
     return r
 
 

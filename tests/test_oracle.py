@@ -14,13 +14,10 @@ import numpy as np
 import pytest
 
 import vectors as V
+from gpu_support import SEED_A, SEED_B, SEED_EP, SEED_PK
 from oracle import pyoracle
 from oracle.pyoracle import Oracle
 
-SEED_A = hashlib.shake_256(b"golden-share").digest(64)
-SEED_B = hashlib.shake_256(b"golden-secret").digest(64)
-SEED_PK = hashlib.shake_256(b"golden-pk").digest(64)
-SEED_EP = hashlib.shake_256(b"golden-ep").digest(64)
 
 
 def ends(a, k=8):
