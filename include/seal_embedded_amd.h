@@ -400,6 +400,69 @@ int se_amd_decrypt_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uin
 int se_amd_decrypt_level_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
                                       size_t primes, double scale, const uint32_t *d_key_idx, int64_t *d_pte,
                                       float *d_values, double *d_values_f64, uint8_t *d_status, void *stream);
+/* ---- ciphertext products: tensor, relinearisation key, degree-2 decrypt ------------------------------
+ * Conventions are those of the level entries above: a level-L slab is uint32 [records][L][n], NTT form, bit-reversed
+ * order, residues in [0, q_j), 1 <= L <= np; device pointers are 16-byte aligned; the device entries are asynchronous on
+ * `stream`, allocate no scratch, and their outputs must not overlap their inputs (not checked).  A product of two
+ * ciphertexts at scale D is at scale D^2; relinearisation changes neither scale nor level; a rescale afterwards divides
+ * the scale by the prime it drops.
+ *
+ * Tensor product, key-free.  For pair p with x = record ia[p] of (d_a0, d_a1) [Ba][primes][n] and y = record ib[p] of
+ * (d_b0, d_b1) [Bb][primes][n], per prime j < primes and element, mod q_j and canonical:
+ *     out0 = x0 . y0,     out1 = x0 . y1 + x1 . y0,     out2 = x1 . y1          (each [P][primes][n]).
+ * (out0, out1, out2) decrypts as out0 + out1 s + out2 s^2 (se_amd_decrypt3_level_device) or is brought back to two slabs
+ * by se_amd_ct_relin_device.  d_ia / d_ib [P] uint32 on the device; with d_ia = d_ib = NULL, P must equal Ba and Bb and
+ * pair p is (p, p).  The a and b slabs may be the same pointers (squares, all pairs within one batch).  A pair with
+ * ia[p] >= Ba or ib[p] >= Bb gets status 2 and all-zero rows; nothing is read out of bounds and other pairs are
+ * unaffected.  d_status [P] is optional (1, or 2).
+ * SE_ERR_INVALD_ARGUMENT: a NULL slab pointer; only one of d_ia / d_ib NULL; both NULL with P != Ba or P != Bb; primes
+ * outside [1, np]; P, Ba or Bb at or above 2^32; a slab pointer that is not 16-byte aligned.  P = 0 is a successful
+ * no-op.  Nothing is written on an argument error. */
+int se_amd_ct_mul_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0,
+                         const uint32_t *d_b1, size_t Bb, size_t primes, size_t P,
+                         const uint32_t *d_ia /* [P] or NULL */, const uint32_t *d_ib /* [P] or NULL */,
+                         uint32_t *d_out0, uint32_t *d_out1, uint32_t *d_out2, uint8_t *d_status /* [P], optional */,
+                         void *stream);
+/* se_amd_decrypt_level[_keyed]_device on the degree-2 form: a third slab d_c2 after d_c1 and, per prime,
+ * d = c0 + s_hat . (c1 + s_hat . c2).  Everything after that is the level entry unchanged: INTT and recombination over
+ * Q_primes, status 0 or 1, decode with the caller's `scale`, the same optional outputs, SE_ERR_NO_KEY, the ring's status
+ * 2, the same argument errors (and a NULL d_c2).  With d_c2 pointing at an all-zero slab every output equals
+ * se_amd_decrypt_level_device byte for byte. */
+int se_amd_decrypt3_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2,
+                                 size_t B, size_t primes, double scale, int64_t *d_pte, float *d_values,
+                                 double *d_values_f64, uint8_t *d_status, void *stream);
+int se_amd_decrypt3_level_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1,
+                                       const uint32_t *d_c2, size_t B, size_t primes, double scale,
+                                       const uint32_t *d_key_idx, int64_t *d_pte, float *d_values,
+                                       double *d_values_f64, uint8_t *d_status, void *stream);
+/* Relinearisation key.  Digits are SE_AMD_RELIN_DIGIT_BITS = 15 bits, two per prime (30-bit digits would put the
+ * key-switch noise near the reference's 0.1 acceptance at the large parameter sets).  The key
+ * has R = 2 np rows; evk0 and evk1 are uint32 [R][np][n] each, NTT form.  Row r = 2j + t (j < np, t in {0, 1}) at prime
+ * i, mod q_i and canonical:
+ *     evk1[r][i] = a_{r,i}
+ *     evk0[r][i] = -a_{r,i} . s_hat_i + NTT_i(e_r mod q_i) + [i == j] . (2^(15 t) mod q_i) . s_hat_i^2.
+ * The diagonal term uses the CRT basis element of q_j (1 mod q_j, 0 mod the others), so ONE key serves every level L:
+ * the rows r < 2L and the columns i < L.
+ * se_amd_gen_relin_key (host pointers; a_seeds, e_seeds [R][64]): (evk0[r], evk1[r]) minus the diagonal term is exactly
+ * public key r of se_amd_gen_keys_batch with K = R, sk_in = this key replicated, pk_seeds = a_seeds and ep_seeds =
+ * e_seeds.  Keys installed in the context are not touched; a 2-bit code 3 in sk_packed is refused.
+ * se_amd_set_relin_key (host pointers): installs the key for se_amd_ct_relin_device; a word >= q_i is refused; replaces
+ * the previous key after the calls in flight finish.  The key is public material.  Device memory: 16 R np n bytes. */
+#define SE_AMD_RELIN_DIGIT_BITS 15
+int se_amd_gen_relin_key(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint8_t *a_seeds /*[R][64]*/,
+                         const uint8_t *e_seeds /*[R][64]*/, uint32_t *evk0, uint32_t *evk1 /*[R][np][n], host out*/);
+int se_amd_set_relin_key(se_amd_ctx *ctx, const uint32_t *evk0, const uint32_t *evk1);
+/* Relinearisation: level-`primes` slabs (d_d0, d_d1, d_d2) [B][primes][n] -> (d_out0, d_out1) of the same level.  Let
+ * D_{j,t} be the t-th 15-bit digit of each coefficient of the canonical natural-order INTT_j(d2[b][j]) (the n^-1 factor
+ * included), so that D_{j,0} + 2^15 D_{j,1} is that coefficient and every digit is already a residue of every prime.
+ * For i < primes, mod q_i and canonical:
+ *     out0[b][i] = d0[b][i] + sum_{j < primes, t} NTT_i(D_{j,t}) . evk0[2j + t][i]
+ *     out1[b][i] = d1[b][i] + sum_{j < primes, t} NTT_i(D_{j,t}) . evk1[2j + t][i].
+ * The map is defined on arbitrary residue slabs and arbitrary installed key words below q_i; it needs no secret key.
+ * SE_ERR_NO_KEY without an installed relinearisation key; SE_ERR_INVALD_ARGUMENT for a NULL slab pointer, primes
+ * outside [1, np], a slab pointer that is not 16-byte aligned, B at or above 2^32.  B = 0 is a successful no-op. */
+int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B,
+                           size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

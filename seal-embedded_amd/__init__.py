@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_ct_lincomb_device", "se_amd_set_lincomb_split",
     "se_amd_ct_rescale_device", "se_amd_ct_mul_plain_device", "se_amd_decrypt_level_device",
     "se_amd_decrypt_level_keyed_device", "se_amd_rescale_constants",
+    "se_amd_ct_mul_device", "se_amd_decrypt3_level_device", "se_amd_decrypt3_level_keyed_device",
+    "se_amd_gen_relin_key", "se_amd_set_relin_key", "se_amd_ct_relin_device",
 )
 
 
@@ -150,6 +152,12 @@ def lib():
     L.se_amd_decrypt_level_device.argtypes = [vp, vp, vp, sz, sz, C.c_double, vp, vp, vp, vp, vp]
     L.se_amd_decrypt_level_keyed_device.argtypes = [vp, vp, vp, sz, sz, C.c_double, vp, vp, vp, vp, vp, vp]
     L.se_amd_rescale_constants.argtypes = [sz, sz, vp, vp]
+    L.se_amd_ct_mul_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.se_amd_decrypt3_level_device.argtypes = [vp, vp, vp, vp, sz, sz, C.c_double, vp, vp, vp, vp, vp]
+    L.se_amd_decrypt3_level_keyed_device.argtypes = [vp, vp, vp, vp, sz, sz, C.c_double, vp, vp, vp, vp, vp, vp]
+    L.se_amd_gen_relin_key.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.se_amd_set_relin_key.argtypes = [vp, vp, vp]
+    L.se_amd_ct_relin_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -531,6 +539,64 @@ class Context:
         _check(self.L.se_amd_decrypt_level_keyed_device(self.h, _ptr(c0), _ptr(c1), B, primes, scale, _ptr(key_idx),
                                                         _ptr(pte), _ptr(values), _ptr(values_f64), _ptr(status),
                                                         _stream_ptr()), "se_amd_decrypt_level_keyed_device")
+
+    def ct_mul(self, a0, a1, b0, b1, out0, out1, out2, ia=None, ib=None, primes=None, status=None):
+        """Key-free tensor product: pair p = record ia[p] of (a0, a1) times record ib[p] of (b0, b1), slabs
+        [B][primes][n]; out0 = x0 y0, out1 = x0 y1 + x1 y0, out2 = x1 y1, each [P][primes][n].  ia = ib = None: pair p is
+        (p, p) and both sides hold P records.  status uint8 [P]: 2 and zero rows for an index out of range."""
+        if primes is None:
+            primes = a0.shape[1]
+        P = ia.numel() if ia is not None else a0.shape[0]
+        _check(self.L.se_amd_ct_mul_device(self.h, _ptr(a0), _ptr(a1), a0.shape[0], _ptr(b0), _ptr(b1), b0.shape[0],
+                                           primes, P, _ptr(ia), _ptr(ib), _ptr(out0), _ptr(out1), _ptr(out2),
+                                           _ptr(status), _stream_ptr()), "se_amd_ct_mul_device")
+
+    def decrypt3_level(self, c0, c1, c2, primes, scale, pte=None, values=None, values_f64=None, status=None):
+        """decrypt_level on the degree-2 form (c0, c1, c2): d = c0 + s (c1 + s c2) per prime."""
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt3_level_device(self.h, _ptr(c0), _ptr(c1), _ptr(c2), B, primes, scale, _ptr(pte),
+                                                   _ptr(values), _ptr(values_f64), _ptr(status), _stream_ptr()),
+               "se_amd_decrypt3_level_device")
+
+    def decrypt3_level_keyed(self, c0, c1, c2, key_idx, primes, scale, pte=None, values=None, values_f64=None,
+                             status=None):
+        """decrypt3_level with record b under secret-ring key key_idx[b]; status 2 and zero outputs for an
+        index >= K."""
+        B = c0.shape[0]
+        _check(self.L.se_amd_decrypt3_level_keyed_device(self.h, _ptr(c0), _ptr(c1), _ptr(c2), B, primes, scale,
+                                                         _ptr(key_idx), _ptr(pte), _ptr(values), _ptr(values_f64),
+                                                         _ptr(status), _stream_ptr()),
+               "se_amd_decrypt3_level_keyed_device")
+
+    def gen_relin_key(self, sk_packed, a_seeds, e_seeds):
+        """Relinearisation key of sk_packed from R = 2 np seed pairs [R][64]: (evk0, evk1) uint32 [R][np][n]."""
+        import numpy as np
+        R = 2 * self.np
+        sk = np.ascontiguousarray(sk_packed, dtype=np.uint8)
+        assert sk.size == self.n // 4
+        sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(R, 64)
+        se = np.ascontiguousarray(e_seeds, dtype=np.uint8).reshape(R, 64)
+        evk0 = np.zeros((R, self.np, self.n), dtype=np.uint32)
+        evk1 = np.zeros_like(evk0)
+        _check(self.L.se_amd_gen_relin_key(self.h, _ptr(sk), _ptr(sa), _ptr(se), _ptr(evk0), _ptr(evk1)),
+               "se_amd_gen_relin_key")
+        return evk0, evk1
+
+    def set_relin_key(self, evk0, evk1):
+        """evk0, evk1 [2 np][np][n] uint32 (as gen_relin_key returns them); a word >= q_i is refused."""
+        import numpy as np
+        evk0 = np.ascontiguousarray(evk0, dtype=np.uint32)
+        evk1 = np.ascontiguousarray(evk1, dtype=np.uint32)
+        assert evk0.size == 2 * self.np * self.np * self.n == evk1.size
+        _check(self.L.se_amd_set_relin_key(self.h, _ptr(evk0), _ptr(evk1)), "se_amd_set_relin_key")
+
+    def ct_relin(self, d0, d1, d2, out0, out1, primes=None):
+        """Relinearisation of the degree-2 form (d0, d1, d2) [B][primes][n] with the installed key -> (out0, out1) of
+        the same level; no secret key is needed."""
+        if primes is None:
+            primes = d0.shape[1]
+        _check(self.L.se_amd_ct_relin_device(self.h, _ptr(d0), _ptr(d1), _ptr(d2), d0.shape[0], primes, _ptr(out0),
+                                             _ptr(out1), _stream_ptr()), "se_amd_ct_relin_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

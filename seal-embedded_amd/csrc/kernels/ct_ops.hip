@@ -1,6 +1,7 @@
 // ct_ops.hip -- key-free operations on resident ciphertext slabs: weighted sums of records (se_amd_ct_lincomb_device),
 // slot-wise products with encoded plaintexts (se_amd_ct_mul_plain_device) and the rescale that drops the last prime
-// (se_amd_ct_rescale_device, at the end of the file).
+// (se_amd_ct_rescale_device), and the ciphertext products: the tensor (se_amd_ct_mul_device) and the relinearisation
+// that brings it back to two slabs (se_amd_ct_relin_device, at the end of the file, with the key plumbing).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -34,6 +35,8 @@ constexpr int kLcPeriod = 16;
 // the plain uint64 sum stays below 2^62: no reduction before the last one.  The sum of S <= 65 535 canonical partial
 // rows (k_ct_lincomb_sum) is below 2^46 the same way.
 static_assert(kLcPeriod % kLcFlight == 0, "a period is a whole number of load groups");
+// bits of a relinearisation digit (SE_AMD_RELIN_DIGIT_BITS): two digits cover a coefficient below 2^30
+constexpr int kRelinDigitBits = 15;
 
 struct Lane4
 {
@@ -283,6 +286,60 @@ hipError_t launch_ct_mul_plain(const DevParams &P, const MulPlainArgs &A, hipStr
 }
 
 // ------------------------------------------------------------------------------------------
+// Tensor product of two ciphertexts, the degree-2 form before relinearisation: for pair p with x = record ia[p] of
+// (a0, a1) and y = record ib[p] of (b0, b1),  out0 = x0 y0,  out1 = x0 y1 + x1 y0,  out2 = x1 y1  mod q_j, element-wise.
+// Streaming, in the shape of k_ct_mul_plain: a 256-thread workgroup owns 1024 consecutive residues of a pair -- inside
+// one prime, so q_j and its Barrett constants are scalar -- and walks the pairs blockIdx.y, blockIdx.y + gridDim.y, ...;
+// the two record indices are workgroup-uniform (scalar loads).  Four 16-byte loads and three 16-byte stores per lane,
+// 64-bit row offsets.  The a and b slabs may be the same memory (squares, all pairs within one batch): they are only
+// read, so no __restrict__ on them; the outputs overlap nothing.
+// Residues are below q < 2^30, so one product is at most (q - 1)^2 < 2^60 and the two products of out1 sum to less than
+// 2^61 < 2^64: ONE barrett64 (exact for every 64-bit input) for the sum.
+// grid (primes n / 1024, min(P, 65 535)).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kLcThreads) void k_ct_mul(const DevParams P, const MulArgs A)
+{
+    const size_t row     = (size_t)A.primes << P.logn;
+    const uint32_t chunk = blockIdx.x;
+    const uint32_t j     = (chunk << kLcTileLog) >> P.logn;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const size_t off = ((size_t)chunk << kLcTileLog) + 4 * threadIdx.x;
+
+    for (size_t p = blockIdx.y; p < A.P; p += gridDim.y)
+    {
+        const uint32_t ia = A.ia ? A.ia[p] : (uint32_t)p, ib = A.ib ? A.ib[p] : (uint32_t)p;
+        const bool bad    = ia >= A.Ba || ib >= A.Bb;   // nothing of such a pair's records is read
+        uint32_t r[3][4]  = {};
+        if (!bad)
+        {
+            const uint4 x0 = load_row(A.a0, ia, row, off), x1 = load_row(A.a1, ia, row, off);
+            const uint4 y0 = load_row(A.b0, ib, row, off), y1 = load_row(A.b1, ib, row, off);
+            const uint32_t u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
+            const uint32_t v0[4] = {y0.x, y0.y, y0.z, y0.w}, v1[4] = {y1.x, y1.y, y1.z, y1.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+            {
+                r[0][e] = barrett64((uint64_t)u0[e] * v0[e], q, cr_hi, cr_lo);
+                r[1][e] = barrett64((uint64_t)u0[e] * v1[e] + (uint64_t)u1[e] * v0[e], q, cr_hi, cr_lo);
+                r[2][e] = barrett64((uint64_t)u1[e] * v1[e], q, cr_hi, cr_lo);
+            }
+        }
+        *reinterpret_cast<uint4 *>(A.out0 + p * row + off) = make_uint4(r[0][0], r[0][1], r[0][2], r[0][3]);
+        *reinterpret_cast<uint4 *>(A.out1 + p * row + off) = make_uint4(r[1][0], r[1][1], r[1][2], r[1][3]);
+        *reinterpret_cast<uint4 *>(A.out2 + p * row + off) = make_uint4(r[2][0], r[2][1], r[2][2], r[2][3]);
+        if (A.status && blockIdx.x == 0 && threadIdx.x == 0) A.status[p] = bad ? 2 : 1;
+    }
+}
+
+hipError_t launch_ct_mul(const DevParams &P, const MulArgs &A, hipStream_t st)
+{
+    if (A.P == 0) return hipSuccess;
+    const uint32_t chunks = (uint32_t)(((size_t)A.primes << P.logn) >> kLcTileLog);
+    const dim3 grid(chunks, A.P < 65535u ? A.P : 65535u);
+    return launch(k_ct_mul, grid, dim3(kLcThreads), 0, st, P, A);
+}
+
+// ------------------------------------------------------------------------------------------
 // Rescale: level L -> level L - 1, the exact quotient (c - delta) / q_last with delta = c mod q_last centred, i.e.
 // c / q_last rounded to nearest (SEAL's rescale_to_next on NTT-form data).  One workgroup of n/16 threads per
 // (record, slab), the tiling of the rest of the tree:
@@ -356,6 +413,163 @@ hipError_t launch_ct_rescale(const DevParams &P, const DevTables &T, const Resca
         return launch(k_ct_rescale<L>, dim3((unsigned)B, A.in1 ? 2 : 1), dim3(G::THREADS),
                       (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, R, A);
     });
+}
+
+// ------------------------------------------------------------------------------------------
+// Relinearisation: (d0, d1, d2) of level L -> (out0, out1) of level L with the installed evaluation key,
+//   out0[b][i] = d0[b][i] + sum_{j < L, t < 2} NTT_i(D_{j,t}) . evk0[2j + t][i]  mod q_i   (out1: d1 and evk1),
+// D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients of INTT_j(d2[b][j]) (n^-1 included).
+// Baseline form, built from the pieces of k_ct_rescale: one workgroup of n/16 threads per (record, output prime i).
+// It walks j: row j of d2 (quad loads) -> quads_to_tile -> intt_tiles mod q_j -> . n^-1 -> canonical c < q_j < 2^30 in
+// tile layout LOGN-4; per digit t: c & 0x7FFF resp. c >> 15 (below 2^15 < q_i: a residue of every prime as it stands)
+// -> ntt_tiles mod q_i, which STARTS in that layout -> tile_to_quads -> multiply-accumulate against row 2j + t of both
+// key halves (quad loads of the word row and of its Shoup row).  L INTTs and 2 L NTTs per workgroup, L^2 and 2 L^2 per
+// record, no scratch: the row of d2 is transformed again by every output prime.
+// Lazy range of the accumulators.  Every prime is below 2^30.  A key word is w < q_i (set_relin_key refuses others) and
+// its companion is floor(w 2^32 / q_i), so mul_shoup_lazy(y, w, .) is in [0, 2 q_i) for ANY 32-bit y -- y is the lazy
+// NTT output in [0, 4 q_i).  An accumulator enters a step in [0, 2 q_i) (it starts at 0): the sum is below
+// 4 q_i < 2^32, and min(s, s - 2 q_i) brings it back into [0, 2 q_i).  So a 32-bit word per value carries any number of
+// terms; the one canonicalisation is in the epilogue, csub(csub(acc) + d) with d < q_i.
+// LDS is the exchange plane alone, used as in k_ct_rescale: the wave-local transposes run inside it while no exchange
+// is in flight, and one workgroup barrier after each keeps the next transform's first exchange off the rows other
+// waves are still reading.  No word of a slab or of the key is used as an address.
+// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// ------------------------------------------------------------------------------------------
+// The NTT mod q_i is the same for every j and digit, so with the plain thread index the compiler hoists its per-thread
+// root loads and LDS addresses out of both loops and carries them across the inverse transform (n = 16384, 128 VGPRs per
+// thread: 276 bytes of private memory).  Each transform takes an opaque copy of the index instead (opaque_index,
+// transform.cuh): 112 VGPRs there and nothing spilled.
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin(const DevParams P, const DevTables T,
+                                                                    const RelinArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
+    const uint32_t *k0 = A.evk + (size_t)i * 2 * N;   // column i of key row 0; a key row is np columns of 2 N words
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        for (uint32_t j = 0; j < A.primes; j++)
+        {
+            const int tj      = opaque_index(t);
+            const uint32_t qj = P.q[j];
+            uint32_t x[16];
+            load_quads(x, A.d2 + rec + (size_t)j * N, tj);
+            quads_to_tile<16>(x, lds, tj);
+            __syncthreads();
+            intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, qj, lds, tj);
+            const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
+#pragma unroll
+            for (int e = 0; e < 16; e++) x[e] = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
+            // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
+#pragma unroll 1
+            for (uint32_t dg = 0; dg < 2; dg++)
+            {
+                const int td = opaque_index(t);
+                uint32_t y[16];
+#pragma unroll
+                for (int e = 0; e < 16; e++) y[e] = (x[e] >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
+                ntt_tiles<LOGN>(y, rw, qi, lds, td);
+                tile_to_quads<16>(y, lds, td);
+                // key rows 2j + dg of both halves, a quad of words and of Shoup companions at a time
+                const uint32_t *key = k0 + (size_t)(2 * j + dg) * A.np * 2 * N + quad_index(td, 0);
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                {
+                    const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
+                    const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
+                    const uint4 w1 = *reinterpret_cast<const uint4 *>(key + A.half + (c << 8));
+                    const uint4 s1 = *reinterpret_cast<const uint4 *>(key + A.half + N + (c << 8));
+                    const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
+                    const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                    {
+                        const int e       = 4 * c + k;
+                        const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], qi);
+                        const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], qi);
+                        acc0[e]           = min(u0, u0 - two_qi);
+                        acc1[e]           = min(u1, u1 - two_qi);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        const size_t o = rec + (size_t)i * N;
+        uint32_t c[16];
+        load_quads(c, A.d0 + o, t);
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = csub(csub(acc0[e], qi) + c[e], qi);
+        store_quads(A.out0 + o, acc0, t);
+        load_quads(c, A.d1 + o, t);
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc1[e] = csub(csub(acc1[e], qi) + c[e], qi);
+        store_quads(A.out1 + o, acc1, t);
+    }
+}
+
+hipError_t launch_ct_relin(const DevParams &P, const DevTables &T, const RelinArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        return launch(k_ct_relin<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// The device copy of an evaluation key: every row [np][n] of key words becomes [np][2][n], the words of a column
+// followed by their Shoup companions floor(w 2^32 / q_i) (w < q_i was checked on the host).  One thread per word.
+__global__ __launch_bounds__(kLcThreads) void k_relin_key_rows(const DevParams P, const uint32_t *__restrict__ in,
+                                                            uint32_t *__restrict__ out, size_t words)
+{
+    const size_t k = (size_t)blockIdx.x * kLcThreads + threadIdx.x;
+    if (k >= words) return;
+    const size_t col   = k >> P.logn, c = k & (P.n - 1);
+    const uint32_t q   = P.q[col % P.nprimes], w = in[k];
+    out[((2 * col) << P.logn) + c]     = w;
+    out[((2 * col + 1) << P.logn) + c] = (uint32_t)(((uint64_t)w << 32) / q);
+}
+
+hipError_t launch_relin_key_rows(const DevParams &P, const uint32_t *in, uint32_t *out, size_t rows, hipStream_t st)
+{
+    const size_t words = (rows * P.nprimes) << P.logn;
+    if (words == 0) return hipSuccess;
+    return launch(k_relin_key_rows, dim3((unsigned)(words / kLcThreads)), dim3(kLcThreads), 0, st, P, in, out, words);
+}
+
+// The diagonal term of a relinearisation key on the [R][np][n] slab the public-key chain wrote:
+//   evk0[2j + t][j] += 2^(15 t) . s_hat^2  mod q_j,  t = 0, 1   (2^15 < q_j: the factor is its own residue).
+// s_hat^2 < q_j < 2^30 lives in a register only; s_hat^2 2^15 + evk0 < 2^46.  grid n / 256.
+__global__ __launch_bounds__(kLcThreads) void k_relin_diag(const DevParams P, uint32_t j,
+                                                        const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ evk0)
+{
+    const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const uint32_t s  = s_hat[c];
+    const uint64_t s2 = barrett64((uint64_t)s * s, q, cr_hi, cr_lo);
+#pragma unroll
+    for (uint32_t dg = 0; dg < 2; dg++)
+    {
+        uint32_t *p = evk0 + ((((size_t)(2 * j + dg)) * P.nprimes + j) << P.logn) + c;
+        *p          = barrett64((s2 << (kRelinDigitBits * dg)) + *p, q, cr_hi, cr_lo);
+    }
+}
+
+hipError_t launch_relin_diag(const DevParams &P, uint32_t j, const uint32_t *s_hat, uint32_t *evk0, hipStream_t st)
+{
+    return launch(k_relin_diag, dim3(P.n / kLcThreads), dim3(kLcThreads), 0, st, P, j, s_hat, evk0);
 }
 
 }  // namespace seamd

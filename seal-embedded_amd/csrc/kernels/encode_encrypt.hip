@@ -66,18 +66,6 @@ __device__ __forceinline__ void load16_pairs(uint32_t (&w)[16], uint32_t (&wp)[1
 
 // (the quad-layout accessors load_quads / store_quads live beside tile_to_quads in transform.cuh)
 //
-// opaque_index(): a thread index the compiler must treat as freshly computed where it is taken.  The fused
-// kernels address the same per-thread pieces (a, key pairs, c0 / c1, u, e1) again for every prime; seen as
-// loop-invariant, the 64-bit ADDRESS of every piece was formed ahead of the prime loop and carried -- or
-// spilled -- across it (public-key form: 206 VGPRs, of which 44 were such addresses; the one-transform-at-a-
-// time form spilled 22 of them).  Global addresses inside the prime loop are formed from an opaque copy of the
-// thread index taken per iteration: a few 64-bit adds per prime, and the registers are free.
-__device__ __forceinline__ int opaque_index(int t)
-{
-    __asm__ volatile("" : "+v"(t));
-    return t;
-}
-
 // Key rings (kernel_args.h, KeyRing): the keyed kernels read the key rows of record b from key idx[b] of the ring.  b is
 // workgroup-uniform (one plaintext per workgroup, or per half of the pair form), so the key's offset is one scalar word
 // (readfirstlane of the index) times the key stride: SGPRs only, and the per-prime offsets (kb) are the single key's.
@@ -1229,7 +1217,9 @@ hipError_t launch_decrypt_decode(const DevParams &P, const DevTables &T, const u
 // The decode tail is decrypt_decode_body's with the int64 in place of the single-prime lift (ckks_decode,
 // device/test/ckks_tests_common.c:72-115): same never-contracted FP64 operations, same root table.
 // ------------------------------------------------------------------------------------------
-template <int LOGN, bool KEYED>
+// DEG2: the degree-2 form a tensor product leaves (se_amd_ct_mul_device), d = c0 + s (c1 + s c2) per prime with the
+// third slab A.c2; everything after the per-prime d is the same code.
+template <int LOGN, bool KEYED, bool DEG2 = false>
 __device__ __forceinline__ void decrypt_full_body(const DevParams &P, const DevTables &T, const CrtParams &C,
                                                   const FullArgs &A, const KeyRing &R, unsigned char *smem)
 {
@@ -1254,9 +1244,22 @@ __device__ __forceinline__ void decrypt_full_body(const DevParams &P, const DevT
         uint32_t x[16];
         {
             uint32_t a[16], w[16], wp[16];
-            load16(x, A.c0 + rec);
-            load16(a, A.c1 + rec);
-            load16_pairs(w, wp, key, (size_t)j * N + 16 * t);
+            if constexpr (DEG2)
+            {
+                // c1 + s c2 first, in the registers of c0: the live set never exceeds the four tiles of the linear form
+                load16_pairs(w, wp, key, (size_t)j * N + 16 * t);
+                load16(x, A.c2 + rec);
+                load16(a, A.c1 + rec);
+#pragma unroll
+                for (int e = 0; e < 16; e++) a[e] = csub(csub(mul_shoup_lazy(x[e], w[e], wp[e], q), q) + a[e], q);
+                load16(x, A.c0 + rec);
+            }
+            else
+            {
+                load16(x, A.c0 + rec);
+                load16(a, A.c1 + rec);
+                load16_pairs(w, wp, key, (size_t)j * N + 16 * t);
+            }
 #pragma unroll
             for (int e = 0; e < 16; e++)
                 x[e] = csub(csub(mul_shoup_lazy(a[e], w[e], wp[e], q), q) + x[e], q);
@@ -1354,6 +1357,23 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt_full_keyed
     decrypt_full_body<LOGN, true>(P, T, C, A, R, smem);
 }
 
+// degree-2 twins (FullArgs::c2 set): d = c0 + s (c1 + s c2)
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt3_full(DevParams P, DevTables T, CrtParams C,
+                                                                         FullArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    decrypt_full_body<LOGN, false, true>(P, T, C, A, KeyRing{}, smem);
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_decrypt3_full_keyed(DevParams P, DevTables T,
+                                                                               CrtParams C, FullArgs A, KeyRing R)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    decrypt_full_body<LOGN, true, true>(P, T, C, A, R, smem);
+}
+
 hipError_t launch_decrypt_full(const DevParams &P, const DevTables &T, const CrtParams &C, const FullArgs &A, size_t B,
                                hipStream_t st, const KeyRing *ring)
 {
@@ -1365,6 +1385,11 @@ hipError_t launch_decrypt_full(const DevParams &P, const DevTables &T, const Crt
         const dim3 grid((unsigned)B), block(G::THREADS);
         // the INTT exchange takes SLOTS words; the FFT plane (SLOTS doubles) only when slots are decoded
         const size_t shmem = (size_t)G::SLOTS * ((A.values || A.values_f64) ? sizeof(double) : sizeof(uint32_t));
+        if (A.c2)
+        {
+            if (ring) return launch(k_decrypt3_full_keyed<L>, grid, block, shmem, st, P, T, C, A, *ring);
+            return launch(k_decrypt3_full<L>, grid, block, shmem, st, P, T, C, A);
+        }
         if (ring) return launch(k_decrypt_full_keyed<L>, grid, block, shmem, st, P, T, C, A, *ring);
         return launch(k_decrypt_full<L>, grid, block, shmem, st, P, T, C, A);
     });

@@ -117,6 +117,7 @@ struct FullArgs
     float *values;        // [B][n/2]  decoded slots
     double *values_f64;   // [B][n/2]  the same slots before the float conversion
     uint8_t *status;      // [B]       1 = every coefficient fits int64, else 0
+    const uint32_t *c2;   // [B][np][n] degree-2 form only (the decrypt3 kernels): d = c0 + s (c1 + s c2)
 };
 hipError_t launch_decrypt_full(const DevParams &, const DevTables &, const CrtParams &, const FullArgs &, size_t B,
                                hipStream_t, const KeyRing *ring = nullptr);
@@ -166,6 +167,43 @@ struct MulPlainArgs
     uint32_t primes, pt_primes;
 };
 hipError_t launch_ct_mul_plain(const DevParams &, const MulPlainArgs &, hipStream_t);
+// Tensor product of two ciphertexts (ct_ops.hip: k_ct_mul), key-free: pair p = record ia[p] of (a0, a1) times record
+// ib[p] of (b0, b1) (ia = ib = NULL: p, p), per prime j < primes and element, mod q_j:
+//   out0 = x0 y0,   out1 = x0 y1 + x1 y0,   out2 = x1 y1.
+// Status 1, or 2 with all-zero rows for ia[p] >= Ba or ib[p] >= Bb.  The a and b slabs may be the same memory.
+struct MulArgs
+{
+    const uint32_t *a0, *a1;     // [Ba][primes][n]
+    const uint32_t *b0, *b1;     // [Bb][primes][n]
+    const uint32_t *ia, *ib;     // [P] each, or both NULL
+    uint32_t *out0, *out1, *out2;   // [P][primes][n]
+    uint8_t *status;             // [P], optional
+    uint32_t P, Ba, Bb;
+    uint32_t primes;
+};
+hipError_t launch_ct_mul(const DevParams &, const MulArgs &, hipStream_t);
+// Relinearisation (ct_ops.hip: k_ct_relin): level-`primes` (d0, d1, d2) -> (out0, out1) of the same level with the
+// installed evaluation key.  evk is the device copy Context::set_relin_key builds: [2][R][np][2][n], R = 2 np rows of
+// the CONTEXT's np columns, each column a row of n key words followed by the row of their Shoup companions
+// floor(w 2^32 / q_i); evk1 starts `half` words behind evk0.
+//   out0[b][i] = d0[b][i] + sum_{j < primes, t < 2} NTT_i(D_{j,t}) . evk0[2j + t][i]   (out1: d1, evk1)   mod q_i,
+// D_{j,t} = the t-th 15-bit digit of the canonical coefficients of INTT_j(d2[b][j]).
+struct RelinArgs
+{
+    const uint32_t *d0, *d1, *d2;   // [B][primes][n]
+    uint32_t *out0, *out1;          // [B][primes][n]
+    const uint32_t *evk;
+    size_t half;                    // words of one key half: R np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes)
+    uint32_t primes;                // 1 .. np
+};
+hipError_t launch_ct_relin(const DevParams &, const DevTables &, const RelinArgs &, hipStream_t);
+// Relinearisation-key plumbing (ct_ops.hip).  relin_key_rows: `rows` rows [np][n] of key words (rows a multiple of np)
+// -> [rows][2][n] (words, Shoup companions).  relin_diag: evk0[2j + t][j] += 2^(15 t) . s_hat^2 mod q_j for t = 0, 1 on
+// an [R][np][n] slab, s_hat = the canonical NTT(s) mod q_j, [n].
+hipError_t launch_relin_key_rows(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, hipStream_t);
+hipError_t launch_relin_diag(const DevParams &, uint32_t j, const uint32_t *s_hat, uint32_t *evk0, hipStream_t);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

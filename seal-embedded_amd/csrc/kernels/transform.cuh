@@ -38,6 +38,18 @@ __device__ __forceinline__ void static_for(F &&f)
     }
 }
 
+// opaque_index(): a thread index the compiler must treat as freshly computed where it is taken.  The fused
+// kernels address the same per-thread pieces (a, key pairs, c0 / c1, u, e1) again for every prime; seen as
+// loop-invariant, the 64-bit ADDRESS of every piece was formed ahead of the prime loop and carried -- or
+// spilled -- across it (public-key form: 206 VGPRs, of which 44 were such addresses; the one-transform-at-a-
+// time form spilled 22 of them).  Global addresses inside the prime loop are formed from an opaque copy of the
+// thread index taken per iteration: a few 64-bit adds per prime, and the registers are free.
+__device__ __forceinline__ int opaque_index(int t)
+{
+    __asm__ volatile("" : "+v"(t));
+    return t;
+}
+
 // Point index held in slot e (0..15) of thread t for a pass whose 16-point tiles span bits
 // [C, C+4) of the index.
 template <int C>

@@ -330,6 +330,55 @@ int se_amd_ct_mul_plain_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uin
                                as_stream(stream));
 }
 
+int se_amd_ct_mul_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0,
+                         const uint32_t *d_b1, size_t Bb, size_t primes, size_t P, const uint32_t *d_ia,
+                         const uint32_t *d_ib, uint32_t *d_out0, uint32_t *d_out1, uint32_t *d_out2, uint8_t *d_status,
+                         void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mul(d_a0, d_a1, Ba, d_b0, d_b1, Bb, primes, P, d_ia, d_ib, d_out0, d_out1, d_out2, d_status,
+                         as_stream(stream));
+}
+
+int se_amd_decrypt3_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2,
+                                 size_t B, size_t primes, double scale, int64_t *d_pte, float *d_values,
+                                 double *d_values_f64, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt3_level(d_c0, d_c1, d_c2, B, primes, scale, d_pte, d_values, d_values_f64, d_status,
+                                 as_stream(stream));
+}
+
+int se_amd_decrypt3_level_keyed_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1,
+                                       const uint32_t *d_c2, size_t B, size_t primes, double scale,
+                                       const uint32_t *d_key_idx, int64_t *d_pte, float *d_values,
+                                       double *d_values_f64, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.decrypt3_level_keyed(d_c0, d_c1, d_c2, B, primes, scale, d_key_idx, d_pte, d_values, d_values_f64,
+                                       d_status, as_stream(stream));
+}
+
+int se_amd_gen_relin_key(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds,
+                         uint32_t *evk0, uint32_t *evk1)
+{
+    if (!ctx || !sk_packed || !a_seeds || !e_seeds || !evk0 || !evk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.gen_relin_key(sk_packed, a_seeds, e_seeds, evk0, evk1);
+}
+
+int se_amd_set_relin_key(se_amd_ctx *ctx, const uint32_t *evk0, const uint32_t *evk1)
+{
+    if (!ctx || !evk0 || !evk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_relin_key(evk0, evk1);
+}
+
+int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B,
+                           size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_relin(d_d0, d_d1, d_d2, B, primes, d_out0, d_out1, as_stream(stream));
+}
+
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)
 {
     seamd::HostParams hp;

@@ -507,6 +507,28 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
         return kErrInvalid;
     }
     std::lock_guard<std::mutex> lk(mu);
+    return gen_keys_chain(K, sk_in, sk_seeds, pk_seeds, ep_seeds, sk_out, pk0_out, pk1_out, false);
+}
+
+// Relinearisation key: the chain above with K = R = 2 np rows under ONE secret key, pk_seeds = a_seeds and ep_seeds =
+// e_seeds -- row r is public key r, (evk0[r], evk1[r]) = (-a_r s_hat + NTT(e_r), a_r) -- plus the diagonal term
+// 2^(15 t) s_hat^2 on column j of the rows r = 2j + t (kernels/ct_ops.hip, k_relin_diag).
+int Context::gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *evk0_out,
+                           uint32_t *evk1_out)
+{
+    for (size_t i = 0; i < hp.n / 4; i++)
+        if (sk_packed[i] & (sk_packed[i] >> 1) & 0x55u)
+        {
+            set_last_error("secret key holds an invalid 2-bit code (3)");
+            return kErrInvalid;
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    return gen_keys_chain(2 * hp.nprimes, sk_packed, nullptr, a_seeds, e_seeds, nullptr, evk0_out, evk1_out, true);
+}
+
+int Context::gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
+                            const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin)
+{
     SEAMD_HIP(hipSetDevice(device));
     int rc = ensure_scratch(K);
     if (rc) return rc;
@@ -515,8 +537,11 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
     DevBuf<uint8_t> seeds{Secret::yes}, keys{Secret::yes};
     DevBuf<int8_t> codes{Secret::yes}, ep{Secret::yes};
     DevBuf<uint32_t> pk0, pk1, tmp{Secret::yes};   // tmp: NTT(ep), secret as well
+    DevBuf<uint32_t> s_hat{Secret::yes};           // relin: NTT(s) mod the current prime, [K][n] (every row the same)
+    const size_t nkeys = relin ? 1 : K;            // secret keys behind the K rows
+    if (relin) SEAMD_HIP(s_hat.grow((size_t)K * n));
     SEAMD_HIP(seeds.grow(K * 192));
-    SEAMD_HIP(keys.grow(K * (n / 4)));
+    SEAMD_HIP(keys.grow(nkeys * (n / 4)));
     SEAMD_HIP(codes.grow((size_t)K * n));
     SEAMD_HIP(ep.grow((size_t)K * n));
     SEAMD_HIP(pk0.grow(slab));
@@ -527,7 +552,7 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
     SEAMD_HIP(hipMemcpy(d_pk_seeds, pk_seeds, K * 64, hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(d_ep_seeds, ep_seeds, K * 64, hipMemcpyHostToDevice));
     if (sk_in)
-        SEAMD_HIP(hipMemcpy(keys, sk_in, K * (n / 4), hipMemcpyHostToDevice));
+        SEAMD_HIP(hipMemcpy(keys, sk_in, nkeys * (n / 4), hipMemcpyHostToDevice));
     else
     {
         TernaryArgs ta{};
@@ -554,7 +579,8 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
     sa.s_small   = keys;
     sa.ep        = ep;
     sa.ntt_pte   = tmp;
-    sa.s_stride  = n / 4;
+    sa.s_stride  = relin ? 0 : n / 4;
+    sa.s_save    = relin ? s_hat.get() : nullptr;
     sa.a_stride  = np * n;
     sa.c0_stride = np * n;
     for (uint32_t j = 0; j < np; j++)
@@ -567,6 +593,7 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
         sa.c0 = pk0 + (size_t)j * n;
         sa.j  = (int)j;
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
+        if (relin) SEAMD_HIP(launch_relin_diag(dp, j, s_hat, pk0, nullptr));
     }
     SEAMD_HIP(hipDeviceSynchronize());
     if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys, K * (n / 4), hipMemcpyDeviceToHost));
@@ -1190,25 +1217,16 @@ static bool level_params(const DevParams &dp, size_t np, size_t primes, double s
 int Context::decrypt_level(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, double scale,
                            int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st)
 {
-    if (!have_sk)
-    {
-        set_last_error("decrypt needs the secret key (se_amd_set_secret_key)");
-        return kErrNoKey;
-    }
-    DevParams lp;
-    if (!d_c0 || !d_c1 || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
-    if (!level_params(dp, hp.nprimes, primes, scale, lp)) return kErrInvalid;
-    if (B == 0) return 0;
-    SEAMD_HIP(hipSetDevice(device));
-    FullArgs fa{};
-    fa.c0         = d_c0;
-    fa.c1         = d_c1;
-    fa.pte        = d_pte;
-    fa.values     = d_values;
-    fa.values_f64 = d_values_f64;
-    fa.status     = d_status;
-    SEAMD_HIP(launch_decrypt_full(lp, dt, crt, fa, B, st));
-    return 0;
+    return decrypt_level_impl(d_c0, d_c1, nullptr, false, B, primes, scale, nullptr, false, d_pte, d_values,
+                              d_values_f64, d_status, st);
+}
+
+int Context::decrypt3_level(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, size_t B, size_t primes,
+                            double scale, int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status,
+                            hipStream_t st)
+{
+    return decrypt_level_impl(d_c0, d_c1, d_c2, true, B, primes, scale, nullptr, false, d_pte, d_values, d_values_f64,
+                              d_status, st);
 }
 
 // An out-of-range index: the record is decrypted under the clamped index; its status then becomes 2 and its other
@@ -1225,16 +1243,52 @@ int Context::decrypt_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, siz
                                  const uint32_t *d_key_idx, int64_t *d_pte, float *d_values, double *d_values_f64,
                                  uint8_t *d_status, hipStream_t st)
 {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!ring_sk)
+    return decrypt_level_impl(d_c0, d_c1, nullptr, false, B, primes, scale, d_key_idx, true, d_pte, d_values,
+                              d_values_f64, d_status, st);
+}
+
+int Context::decrypt3_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, size_t B,
+                                  size_t primes, double scale, const uint32_t *d_key_idx, int64_t *d_pte,
+                                  float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st)
+{
+    return decrypt_level_impl(d_c0, d_c1, d_c2, true, B, primes, scale, d_key_idx, true, d_pte, d_values, d_values_f64,
+                              d_status, st);
+}
+
+// deg2: the third slab d_c2 is mandatory and the degree-2 kernels run (FullArgs::c2).  keyed: under the secret ring,
+// inside a call scope (the sanitised indices are context scratch); else one launch that writes nothing of the context.
+int Context::decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
+                                size_t primes, double scale, const uint32_t *d_key_idx, bool keyed, int64_t *d_pte,
+                                float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st)
+{
+    std::unique_lock<std::mutex> lk(mu, std::defer_lock);
+    if (keyed) lk.lock();
+    if (keyed ? !ring_sk : !have_sk)
     {
-        set_last_error("keyed decrypt needs a secret key ring (se_amd_set_secret_keyring)");
+        set_last_error(keyed ? "keyed decrypt needs a secret key ring (se_amd_set_secret_keyring)"
+                             : "decrypt needs the secret key (se_amd_set_secret_key)");
         return kErrNoKey;
     }
     DevParams lp;
-    if (!d_c0 || !d_c1 || !d_key_idx || (!d_pte && !d_values && !d_values_f64 && !d_status)) return kErrInvalid;
+    if (!d_c0 || !d_c1 || (deg2 && !d_c2) || (keyed && !d_key_idx) ||
+        (!d_pte && !d_values && !d_values_f64 && !d_status))
+        return kErrInvalid;
     if (!level_params(dp, hp.nprimes, primes, scale, lp)) return kErrInvalid;
     if (B == 0) return 0;
+    FullArgs fa{};
+    fa.c0         = d_c0;
+    fa.c1         = d_c1;
+    fa.c2         = deg2 ? d_c2 : nullptr;
+    fa.pte        = d_pte;
+    fa.values     = d_values;
+    fa.values_f64 = d_values_f64;
+    fa.status     = d_status;
+    if (!keyed)
+    {
+        SEAMD_HIP(hipSetDevice(device));
+        SEAMD_HIP(launch_decrypt_full(lp, dt, crt, fa, B, st));
+        return 0;
+    }
     KeyRejectArgs ra{};
     ra.status   = d_status;
     ra.rows[0]  = reinterpret_cast<uint32_t *>(d_pte);
@@ -1243,13 +1297,6 @@ int Context::decrypt_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, siz
     ra.words[0] = 2 * hp.n;
     ra.words[1] = hp.n / 2;
     ra.words[2] = hp.n;
-    FullArgs fa{};
-    fa.c0         = d_c0;
-    fa.c1         = d_c1;
-    fa.pte        = d_pte;
-    fa.values     = d_values;
-    fa.values_f64 = d_values_f64;
-    fa.status     = d_status;
     return keyed_call(d_key_idx, ring_sk, d_ring_sk, d_ring_sk, ra, B, st, [&](const KeyRing &ring) -> int {
         SEAMD_HIP(launch_decrypt_full(lp, dt, crt, fa, B, st, &ring));
         return 0;
@@ -1304,6 +1351,105 @@ int Context::ct_mul_plain(const uint32_t *d_in0, const uint32_t *d_in1, size_t B
     ma.primes    = (uint32_t)primes;
     ma.pt_primes = (uint32_t)pt_primes;
     SEAMD_HIP(launch_ct_mul_plain(dp, ma, st));
+    return 0;
+}
+
+// Key-free, one launch, nothing of the context is written.
+int Context::ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0, const uint32_t *d_b1,
+                    size_t Bb, size_t primes, size_t P, const uint32_t *d_ia, const uint32_t *d_ib, uint32_t *d_out0,
+                    uint32_t *d_out1, uint32_t *d_out2, uint8_t *d_status, hipStream_t st)
+{
+    constexpr size_t k32 = (size_t)1 << 32;
+    if (!d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_out0 || !d_out1 || !d_out2 || !d_ia != !d_ib) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes || P >= k32 || Ba >= k32 || Bb >= k32) return kErrInvalid;
+    if (!d_ia && (P != Ba || P != Bb)) return kErrInvalid;
+    for (const void *p : {(const void *)d_a0, (const void *)d_a1, (const void *)d_b0, (const void *)d_b1,
+                          (const void *)d_out0, (const void *)d_out1, (const void *)d_out2})
+        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (P == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    MulArgs ma{};
+    ma.a0     = d_a0;
+    ma.a1     = d_a1;
+    ma.b0     = d_b0;
+    ma.b1     = d_b1;
+    ma.ia     = d_ia;
+    ma.ib     = d_ib;
+    ma.out0   = d_out0;
+    ma.out1   = d_out1;
+    ma.out2   = d_out2;
+    ma.status = d_status;
+    ma.P      = (uint32_t)P;
+    ma.Ba     = (uint32_t)Ba;
+    ma.Bb     = (uint32_t)Bb;
+    ma.primes = (uint32_t)primes;
+    SEAMD_HIP(launch_ct_mul(dp, ma, st));
+    return 0;
+}
+
+// The key is public material: validated like a public key (a word >= q_i is refused), then every column gets its Shoup
+// companions on the device (launch_relin_key_rows).  Replaced only after every call already enqueued has finished.
+int Context::set_relin_key(const uint32_t *evk0, const uint32_t *evk1)
+{
+    const size_t n = hp.n, np = hp.nprimes, R = 2 * np, slab = R * np * n;
+    for (size_t r = 0; r < R; r++)
+        for (size_t i = 0; i < np; i++)
+        {
+            const uint32_t q   = hp.q[i];
+            const uint32_t *r0 = evk0 + (r * np + i) * n, *r1 = evk1 + (r * np + i) * n;
+            uint32_t bad       = 0;
+            for (size_t c = 0; c < n; c++) bad |= (uint32_t)(r0[c] >= q) | (uint32_t)(r1[c] >= q);
+            if (bad)
+            {
+                set_last_error("relinearisation key: row " + std::to_string(r) +
+                               " holds a word not reduced modulo its prime");
+                return kErrInvalid;
+            }
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    SEAMD_HIP(hipDeviceSynchronize());   // calls in flight may still read the old key
+    have_relin = false;
+    DevBuf<uint32_t> d_tmp;
+    SEAMD_HIP(d_tmp.grow(2 * slab));
+    SEAMD_HIP(d_evk.grow(4 * slab));
+    SEAMD_HIP(hipMemcpy(d_tmp, evk0, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SEAMD_HIP(hipMemcpy(d_tmp + slab, evk1, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SEAMD_HIP(launch_relin_key_rows(dp, d_tmp, d_evk, 2 * R, nullptr));
+    SEAMD_HIP(hipDeviceSynchronize());
+    have_relin = true;
+    return 0;
+}
+
+// One launch, no scratch, no secret key; reads the installed relinearisation key.
+int Context::ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B, size_t primes,
+                      uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!have_relin)
+    {
+        set_last_error("relinearisation needs an evaluation key (se_amd_set_relin_key)");
+        return kErrNoKey;
+    }
+    if (!d_d0 || !d_d1 || !d_d2 || !d_out0 || !d_out1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes || B >= ((size_t)1 << 32)) return kErrInvalid;
+    for (const void *p : {(const void *)d_d0, (const void *)d_d1, (const void *)d_d2, (const void *)d_out0,
+                          (const void *)d_out1})
+        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    RelinArgs ra{};
+    ra.d0     = d_d0;
+    ra.d1     = d_d1;
+    ra.d2     = d_d2;
+    ra.out0   = d_out0;
+    ra.out1   = d_out1;
+    ra.evk    = d_evk;
+    ra.half   = (size_t)2 * hp.nprimes * hp.nprimes * 2 * hp.n;
+    ra.B      = B;
+    ra.np     = (uint32_t)hp.nprimes;
+    ra.primes = (uint32_t)primes;
+    SEAMD_HIP(launch_ct_relin(dp, dt, ra, st));
     return 0;
 }
 

@@ -51,6 +51,10 @@ struct Context
     DevBuf<uint32_t> d_ring_sk{Secret::yes};   // [K][np][n][2] NTT(s) pairs
     DevBuf<uint32_t> d_ring_pk0, d_ring_pk1;   // [K][np][n][2]
     size_t ring_sk = 0, ring_pk = 0;           // keys in each ring (0 = no ring)
+    // relinearisation key (se_amd_set_relin_key; public material): [2][R][np][2][n], R = 2 np rows, every column a row
+    // of key words followed by the row of their Shoup companions (kernels/kernel_args.h, RelinArgs)
+    DevBuf<uint32_t> d_evk;
+    bool have_relin = false;
     DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
     DevBuf<uint32_t> d_kbad;                   // [1 + cap] count + records whose index was out of range
 
@@ -178,6 +182,23 @@ struct Context
     int decrypt_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, double scale,
                             const uint32_t *d_key_idx, int64_t *d_pte, float *d_values, double *d_values_f64,
                             uint8_t *d_status, hipStream_t st);
+    // degree-2 twins of the level entries: d = c0 + s (c1 + s c2) per prime, the rest unchanged
+    int decrypt3_level(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, size_t B, size_t primes,
+                       double scale, int64_t *d_pte, float *d_values, double *d_values_f64, uint8_t *d_status,
+                       hipStream_t st);
+    int decrypt3_level_keyed(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, size_t B, size_t primes,
+                             double scale, const uint32_t *d_key_idx, int64_t *d_pte, float *d_values,
+                             double *d_values_f64, uint8_t *d_status, hipStream_t st);
+    // ciphertext products: the key-free tensor (MulArgs), the relinearisation key (host pointers) and the
+    // relinearisation itself (RelinArgs); one launch each, no scratch
+    int ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0, const uint32_t *d_b1,
+               size_t Bb, size_t primes, size_t P, const uint32_t *d_ia, const uint32_t *d_ib, uint32_t *d_out0,
+               uint32_t *d_out1, uint32_t *d_out2, uint8_t *d_status, hipStream_t st);
+    int gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *evk0_out,
+                      uint32_t *evk1_out);
+    int set_relin_key(const uint32_t *evk0, const uint32_t *evk1);
+    int ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B, size_t primes,
+                 uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
     int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
                    uint32_t *d_out1, hipStream_t st);
@@ -217,6 +238,13 @@ struct Context
     void collect_events();
 
 private:
+    // the launch chain of gen_keys_batch; relin: ONE secret key (sk_in, n/4 bytes) shared by all K = 2 np rows and the
+    // diagonal term of a relinearisation key added to pk0.  The caller holds `mu`.
+    int gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
+                       const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin);
+    int decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
+                           size_t primes, double scale, const uint32_t *d_key_idx, bool keyed, int64_t *d_pte,
+                           float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);
     // the call protocol of the entries with scratch, and of the keyed ones on top of it (se_context.cpp)
     template <class Body>
     int call_scope(hipStream_t st, Body &&body);
