@@ -463,6 +463,61 @@ int se_amd_set_relin_key(se_amd_ctx *ctx, const uint32_t *evk0, const uint32_t *
  * outside [1, np], a slab pointer that is not 16-byte aligned, B at or above 2^32.  B = 0 is a successful no-op. */
 int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B,
                            size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
+/* ---- slot rotations: Galois elements, Galois keys, the automorphism fused with its key switch --------
+ * Conventions are those of the ciphertext products above (level-L slabs, 16-byte aligned device pointers, asynchronous
+ * device entry without scratch, outputs that do not overlap inputs).  A Galois element is an odd g, 1 <= g < 2n; sigma_g
+ * is the ring automorphism x(X) -> x(X^g).  On an NTT-form row in bit-reversed order it is a pure permutation,
+ *     sigma_g(x)[k] = x[src_g(k)],   src_g(k) = brev((((2 brev(k) + 1) g mod 2n) - 1) / 2),   brev over log2 n bits.
+ * With the encoder's index map (the orbit of 3), g = 3^s mod 2n rotates the slot vector LEFT by s:
+ * out_slot[k] = in_slot[(k + s) mod n/2]; a negative step rotates right; g = 2n - 1 conjugates (the real-valued slots
+ * of this encoder are unchanged by it).  A rotation changes neither scale nor level.
+ * Scale bookkeeping.  There is no special prime, so the key-switch term is the size of the relinearisation's (about
+ * 2.5e7 per coefficient at 4096 x 3): rotate at a raised scale and rescale afterwards.  A product before its rescale is
+ * already at scale^2; a fresh record is first lifted by se_amd_ct_lincomb_device with weight 2^30, which costs one level
+ * (INTEGRATION.md section 4h).
+ * Out of scope: hoisted rotations (one digit decomposition shared by many elements), a per-record element list,
+ * multi-GPU group entries, a special-prime (hybrid) key switch.
+ *
+ * se_amd_galois_element (host only, no context): *elt = 3^(step mod n/2) mod 2n, the step reduced into [0, n/2); step 0
+ * gives 1.  se_amd_galois_table (host only): src [n] uint16 with sigma_elt(x)[k] = x[src[k]]; element 1 gives the
+ * identity.  SE_ERR_INVALD_ARGUMENT for a degree that is not a power of two in [1024, 16384], a NULL output, an even
+ * element or one >= 2n. */
+int se_amd_galois_element(size_t degree, int64_t step, uint32_t *elt);
+int se_amd_galois_table(size_t degree, uint32_t elt, uint16_t *src /*[n]*/);
+/* Galois keys of G elements, 1 <= G <= SE_AMD_MAX_GALOIS_KEYS.  Each key has the shape of the relinearisation key: R =
+ * 2 np rows, the same 15-bit digits, gk0 and gk1 uint32 [G][R][np][n], NTT form.  For element elts[g], row r = 2j + t at
+ * prime i, mod q_i and canonical:
+ *     gk1[g][r][i] = a_{g,r,i}
+ *     gk0[g][r][i] = -a_{g,r,i} . s_hat_i + NTT_i(e_{g,r} mod q_i) + [i == j] . (2^(15 t) mod q_i) . sigma(s_hat)_i,
+ * sigma(s_hat)_i[k] = s_hat_i[src(k)].  As for the relinearisation key, one key serves every level L: rows r < 2L and
+ * columns i < L.
+ * se_amd_gen_galois_keys (host pointers; a_seeds, e_seeds [G][R][64]): (gk0[g][r], gk1[g][r]) minus the diagonal term is
+ * exactly public key r of se_amd_gen_keys_batch with K = R, sk_in = this key replicated, pk_seeds = the g-th block of
+ * a_seeds and ep_seeds = the g-th block of e_seeds.  Keys installed in the context are not touched.  Refused
+ * (SE_ERR_INVALD_ARGUMENT): a 2-bit code 3 in sk_packed, an even element, an element >= 2n, G = 0, G > 64, a NULL pointer.
+ * se_amd_set_galois_keys (host pointers): installs the keys of exactly these G elements for se_amd_ct_galois_device,
+ * replacing the whole installed set after the calls in flight finish.  Refused: a word >= q_i, an even element, an
+ * element >= 2n, an element listed twice, G = 0, G > 64; a refused install leaves the previous set in place.  The keys
+ * are public material.  Device memory: 16 R np n bytes per element, 16 G R np n = 32 G np^2 n bytes in all (4096 x 3:
+ * 1.1 MiB per element; 16384 x 13: 84.5 MiB per element). */
+#define SE_AMD_MAX_GALOIS_KEYS 64
+int se_amd_gen_galois_keys(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint32_t *elts, size_t G,
+                           const uint8_t *a_seeds /*[G][R][64]*/, const uint8_t *e_seeds /*[G][R][64]*/,
+                           uint32_t *gk0, uint32_t *gk1 /*[G][R][np][n], host out*/);
+int se_amd_set_galois_keys(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1);
+/* Rotation / conjugation: level-`primes` slabs (d_c0, d_c1) [B][primes][n] -> (d_out0, d_out1) of the same level under
+ * the same secret key.  Let p0 = sigma(c0) and p1 = sigma(c1), row-wise through src, and D_{j,t} the t-th 15-bit digit
+ * of each coefficient of the canonical natural-order INTT_j(p1[b][j]).  For i < primes, mod q_i and canonical:
+ *     out0[b][i] = p0[b][i] + sum_{j < primes, t} NTT_i(D_{j,t}) . gk0[g][2j + t][i]
+ *     out1[b][i] =            sum_{j < primes, t} NTT_i(D_{j,t}) . gk1[g][2j + t][i],
+ * g the installed key of `elt`: se_amd_ct_relin_device applied to (sigma(c0), 0, sigma(c1)) with gk[g] installed as the
+ * relinearisation key.  The map is defined on arbitrary residue slabs and arbitrary installed key words below q_i; it
+ * needs no secret key.
+ * SE_ERR_INVALD_ARGUMENT for a NULL slab pointer, primes outside [1, np], a slab pointer that is not 16-byte aligned, B
+ * at or above 2^32, an even `elt` or one >= 2n; SE_ERR_NO_KEY when no key is installed for `elt`.  B = 0 is a successful
+ * no-op.  Nothing is written on an error. */
+int se_amd_ct_galois_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                            uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

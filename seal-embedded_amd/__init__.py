@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_decrypt_level_keyed_device", "se_amd_rescale_constants",
     "se_amd_ct_mul_device", "se_amd_decrypt3_level_device", "se_amd_decrypt3_level_keyed_device",
     "se_amd_gen_relin_key", "se_amd_set_relin_key", "se_amd_ct_relin_device",
+    "se_amd_galois_element", "se_amd_galois_table", "se_amd_gen_galois_keys", "se_amd_set_galois_keys",
+    "se_amd_ct_galois_device",
 )
 
 
@@ -158,6 +160,11 @@ def lib():
     L.se_amd_gen_relin_key.argtypes = [vp, vp, vp, vp, vp, vp]
     L.se_amd_set_relin_key.argtypes = [vp, vp, vp]
     L.se_amd_ct_relin_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    L.se_amd_galois_element.argtypes = [sz, C.c_int64, vp]
+    L.se_amd_galois_table.argtypes = [sz, u32, vp]
+    L.se_amd_gen_galois_keys.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+    L.se_amd_set_galois_keys.argtypes = [vp, vp, sz, vp, vp]
+    L.se_amd_ct_galois_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp]
     _lib = L
     return L
 
@@ -213,6 +220,23 @@ def rescale_constants(n, primes):
     inv = np.zeros(m, np.uint32); sh = np.zeros(m, np.uint32)
     _check(lib().se_amd_rescale_constants(n, primes, _ptr(inv), _ptr(sh)), "se_amd_rescale_constants")
     return inv, sh
+
+
+def galois_element(n, step):
+    """The Galois element of a slot rotation (host only): 3^(step mod n/2) mod 2n.  It rotates the slot vector left by
+    `step` (np.roll(v, -step)); a negative step rotates right; step 0 gives 1."""
+    elt = C.c_uint32(0)
+    _check(lib().se_amd_galois_element(n, int(step), C.c_void_p(C.addressof(elt))), "se_amd_galois_element")
+    return int(elt.value)
+
+
+def galois_table(n, elt):
+    """The permutation of the automorphism x -> x^elt on an NTT-form row (host only): uint16 [n] with
+    sigma(x)[k] = x[src[k]]."""
+    import numpy as np
+    src = np.zeros(n, np.uint16)
+    _check(lib().se_amd_galois_table(n, int(elt), _ptr(src)), "se_amd_galois_table")
+    return src
 
 
 class Group:
@@ -597,6 +621,43 @@ class Context:
             primes = d0.shape[1]
         _check(self.L.se_amd_ct_relin_device(self.h, _ptr(d0), _ptr(d1), _ptr(d2), d0.shape[0], primes, _ptr(out0),
                                              _ptr(out1), _stream_ptr()), "se_amd_ct_relin_device")
+
+    def gen_galois_keys(self, sk_packed, elts, a_seeds, e_seeds):
+        """Galois keys of sk_packed for the elements `elts` (odd, below 2n) from G blocks of R = 2 np seed pairs
+        [G][R][64]: (gk0, gk1) uint32 [G][R][np][n]."""
+        import numpy as np
+        R = 2 * self.np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        G = el.size
+        sk = np.ascontiguousarray(sk_packed, dtype=np.uint8)
+        assert sk.size == self.n // 4
+        sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(G, R, 64)
+        se = np.ascontiguousarray(e_seeds, dtype=np.uint8).reshape(G, R, 64)
+        gk0 = np.zeros((G, R, self.np, self.n), dtype=np.uint32)
+        gk1 = np.zeros_like(gk0)
+        _check(self.L.se_amd_gen_galois_keys(self.h, _ptr(sk), _ptr(el), G, _ptr(sa), _ptr(se), _ptr(gk0), _ptr(gk1)),
+               "se_amd_gen_galois_keys")
+        return gk0, gk1
+
+    def set_galois_keys(self, elts, gk0, gk1):
+        """elts [G], gk0, gk1 [G][2 np][np][n] uint32 (as gen_galois_keys returns them): replaces the installed set; a
+        word >= q_i, an even or repeated element is refused and the previous set stays."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        gk0 = np.ascontiguousarray(gk0, dtype=np.uint32)
+        gk1 = np.ascontiguousarray(gk1, dtype=np.uint32)
+        assert gk0.size == el.size * 2 * self.np * self.np * self.n == gk1.size
+        _check(self.L.se_amd_set_galois_keys(self.h, _ptr(el), el.size, _ptr(gk0), _ptr(gk1)),
+               "se_amd_set_galois_keys")
+
+    def ct_galois(self, c0, c1, elt, out0, out1, primes=None):
+        """The automorphism x -> x^elt on the records (c0, c1) [B][primes][n] and its key switch with the installed
+        Galois key of `elt` -> (out0, out1) of the same level under the same key; no secret key is needed.
+        elt = galois_element(n, s) rotates the slots left by s."""
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_galois_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, int(elt), _ptr(out0),
+                                              _ptr(out1), _stream_ptr()), "se_amd_ct_galois_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

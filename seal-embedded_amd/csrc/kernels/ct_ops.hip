@@ -1,7 +1,8 @@
 // ct_ops.hip -- key-free operations on resident ciphertext slabs: weighted sums of records (se_amd_ct_lincomb_device),
 // slot-wise products with encoded plaintexts (se_amd_ct_mul_plain_device) and the rescale that drops the last prime
 // (se_amd_ct_rescale_device), and the ciphertext products: the tensor (se_amd_ct_mul_device) and the relinearisation
-// that brings it back to two slabs (se_amd_ct_relin_device, at the end of the file, with the key plumbing).
+// that brings it back to two slabs (se_amd_ct_relin_device, with the key plumbing), and the slot rotation: a ring
+// automorphism fused with its key switch (se_amd_ct_galois_device, at the end of the file).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -570,6 +571,180 @@ __global__ __launch_bounds__(kLcThreads) void k_relin_diag(const DevParams P, ui
 hipError_t launch_relin_diag(const DevParams &P, uint32_t j, const uint32_t *s_hat, uint32_t *evk0, hipStream_t st)
 {
     return launch(k_relin_diag, dim3(P.n / kLcThreads), dim3(kLcThreads), 0, st, P, j, s_hat, evk0);
+}
+
+// ------------------------------------------------------------------------------------------
+// Slot rotation / conjugation: the automorphism sigma_g : x -> x^g of the ring (g odd, below 2n) on both slabs of a
+// level-L record, and the key switch of sigma(c1) from sigma(s) back to s with the Galois key installed for g:
+//   out0[b][i] = sigma(c0)[b][i] + sum_{j < L, t < 2} NTT_i(D_{j,t}) . gk0[2j + t][i]  mod q_i   (out1: no addend, gk1),
+// D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients of sigma(INTT_j(c1[b][j])).  This is
+// k_ct_relin on (sigma(c0), 0, sigma(c1)) -- the same grid, thread shape, transforms, key layout and lazy ranges --
+// with sigma folded into the two places where a row is in flight anyway:
+//   c1: in the coefficient domain, where sigma sends coefficient k to position k g mod n with the sign (-1)^(k g div n).
+//       The INTT leaves thread t with the coefficients k = t + (n/16) e (tile layout LOGN-4); they are scattered to
+//       lds[k g mod n] and read back at lds[k], which is the layout the NTT starts in.  A wave's 64 lanes hold
+//       consecutive k, so their targets are g apart: g is odd, every 32-lane group of a ds_write_b32 covers the 32 banks
+//       once, and the read back is contiguous (tools/lds_conflicts.py: 0 conflict cycles for every element tried).  One
+//       LDS round trip and two barriers per input prime, against L INTTs and 2 L NTTs.  The negated coefficient is
+//       canonical: 0 stays 0, so the digits are those of the value in [0, q_j).
+//   c0: in the NTT domain, where sigma is a pure permutation of a bit-reversed row, sigma(x)[k] = x[src(k)] with
+//       src(k) = brev((((2 brev(k) + 1) g mod 2n) - 1) / 2).  The row of output prime i enters only the epilogue: it is
+//       staged into the plane with the quad loads (1 KiB per wave instruction), and every thread gathers its 16 words
+//       from lds[src(k)], src computed in registers (two v_bfrev, one multiply).  The gather is 2-way (g = 3, 3^5) to
+//       4-way (3^-1, n + 1, 2n - 1) bank-conflicted, 2 to 6 extra cycles on each of 16 ds_read_b32 per record and output
+//       prime (tools/lds_conflicts.py) -- beside 3 L transforms.  A dword gather of the row from global memory would
+//       touch 64 cache lines per wave instruction.
+// LDS stays the exchange plane alone (n <= XformGeom::SLOTS words for either use).  The only addresses formed from data
+// are formed from g, a launch argument the host has checked (odd, below 2n): every target is masked to [0, n), and no
+// word of a slab or of the key is used as an address.
+// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// ------------------------------------------------------------------------------------------
+template <int LOGN>
+__device__ __forceinline__ uint32_t galois_src(uint32_t k, uint32_t g)
+{
+    constexpr uint32_t N = 1u << LOGN;
+    const uint32_t r     = __brev(k) >> (32 - LOGN);
+    const uint32_t u     = ((2 * r + 1) * g) & (2 * N - 1);   // odd: (2r + 1) g < 2^30
+    return __brev(u >> 1) >> (32 - LOGN);
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois(const DevParams P, const DevTables T,
+                                                                     const GaloisArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t g   = A.elt;
+    const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
+    const uint32_t *k0 = A.gk + (size_t)i * 2 * N;   // column i of key row 0; a key row is np columns of 2 N words
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        for (uint32_t j = 0; j < A.primes; j++)
+        {
+            const int tj      = opaque_index(t);
+            const uint32_t qj = P.q[j];
+            uint32_t x[16];
+            load_quads(x, A.c1 + rec + (size_t)j * N, tj);
+            quads_to_tile<16>(x, lds, tj);
+            __syncthreads();
+            intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, qj, lds, tj);
+            const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
+            // sigma: coefficient k -> position k g mod n, negated when k g mod 2n >= n (k g < 2^29)
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+            {
+                const uint32_t c = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
+                const uint32_t u = (uint32_t)(tj + (N / 16) * e) * g;
+                lds[u & (N - 1)] = (u & N) && c ? qj - c : c;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 16; e++) x[e] = lds[tj + (N / 16) * e];
+            __syncthreads();
+            // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
+#pragma unroll 1
+            for (uint32_t dg = 0; dg < 2; dg++)
+            {
+                const int td = opaque_index(t);
+                uint32_t y[16];
+#pragma unroll
+                for (int e = 0; e < 16; e++) y[e] = (x[e] >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
+                ntt_tiles<LOGN>(y, rw, qi, lds, td);
+                tile_to_quads<16>(y, lds, td);
+                // key rows 2j + dg of both halves, a quad of words and of Shoup companions at a time
+                const uint32_t *key = k0 + (size_t)(2 * j + dg) * A.np * 2 * N + quad_index(td, 0);
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                {
+                    const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
+                    const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
+                    const uint4 w1 = *reinterpret_cast<const uint4 *>(key + A.half + (c << 8));
+                    const uint4 s1 = *reinterpret_cast<const uint4 *>(key + A.half + N + (c << 8));
+                    const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
+                    const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                    {
+                        const int e       = 4 * c + k;
+                        const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], qi);
+                        const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], qi);
+                        acc0[e]           = min(u0, u0 - two_qi);
+                        acc1[e]           = min(u1, u1 - two_qi);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // sigma(c0) row i: the row as it lies in memory goes into the plane, word k at lds[k]; gathered at src(k)
+        const int te   = opaque_index(t);
+        const size_t o = rec + (size_t)i * N;
+        const int k4   = quad_index(te, 0);
+        uint32_t c[16];
+        load_quads(c, A.c0 + o, te);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+            *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 16; e++) c[e] = lds[galois_src<LOGN>((uint32_t)(k4 + ((e >> 2) << 8) + (e & 3)), g)];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            acc0[e] = csub(csub(acc0[e], qi) + c[e], qi);
+            acc1[e] = csub(acc1[e], qi);
+        }
+        store_quads(A.out0 + o, acc0, te);
+        store_quads(A.out1 + o, acc1, te);
+        __syncthreads();   // the next record's first transpose writes the plane the gather reads
+    }
+}
+
+hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const GaloisArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        return launch(k_ct_galois<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// The diagonal term of the Galois key of element g on the [R][np][n] slab the public-key chain wrote:
+//   gk0[2j + t][j][k] += 2^(15 t) . s_hat[src_g(k)]  mod q_j,  t = 0, 1:   sigma_g(s) in NTT form, k_relin_diag with the
+// square replaced by the permuted key.  g is odd and below 2n (checked by the host).  grid n / 256.
+template <int LOGN>
+__global__ __launch_bounds__(kLcThreads) void k_galois_diag(const DevParams P, uint32_t j, uint32_t g,
+                                                         const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ gk0)
+{
+    const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const uint64_t s = s_hat[galois_src<LOGN>(c, g)];
+#pragma unroll
+    for (uint32_t dg = 0; dg < 2; dg++)
+    {
+        uint32_t *p = gk0 + ((((size_t)(2 * j + dg)) * P.nprimes + j) << LOGN) + c;
+        *p          = barrett64((s << (kRelinDigitBits * dg)) + *p, q, cr_hi, cr_lo);
+    }
+}
+
+hipError_t launch_galois_diag(const DevParams &P, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *gk0,
+                              hipStream_t st)
+{
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        return launch(k_galois_diag<L>, dim3(P.n / kLcThreads), dim3(kLcThreads), 0, st, P, j, elt, s_hat, gk0);
+    });
 }
 
 }  // namespace seamd

@@ -379,6 +379,72 @@ int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t
     return ctx->c.ct_relin(d_d0, d_d1, d_d2, B, primes, d_out0, d_out1, as_stream(stream));
 }
 
+static_assert(seamd::kMaxGaloisKeys == SE_AMD_MAX_GALOIS_KEYS, "the header's limit is the context's");
+
+static bool galois_degree(size_t degree)
+{
+    return degree >= 1024 && degree <= 16384 && (degree & (degree - 1)) == 0;
+}
+
+int se_amd_galois_element(size_t degree, int64_t step, uint32_t *elt)
+{
+    if (!elt || !galois_degree(degree))
+    {
+        seamd::set_last_error("Galois element: unsupported degree");
+        return SE_ERR_INVALD_ARGUMENT;
+    }
+    const int64_t half = (int64_t)degree / 2;
+    uint64_t s         = (uint64_t)(((step % half) + half) % half);
+    uint64_t g = 1, base = 3;
+    const uint64_t mask = 2 * degree - 1;
+    for (; s; s >>= 1, base = (base * base) & mask)
+        if (s & 1) g = (g * base) & mask;
+    *elt = (uint32_t)g;
+    return SE_SUCCESS;
+}
+
+int se_amd_galois_table(size_t degree, uint32_t elt, uint16_t *src)
+{
+    if (!src || !galois_degree(degree) || !(elt & 1) || elt >= 2 * degree)
+    {
+        seamd::set_last_error("Galois table: unsupported degree, or an element that is not odd and below 2n");
+        return SE_ERR_INVALD_ARGUMENT;
+    }
+    unsigned logn = 0;
+    while (((size_t)1 << logn) < degree) logn++;
+    auto brev = [logn](uint32_t v) {
+        uint32_t r = 0;
+        for (unsigned b = 0; b < logn; b++) r |= ((v >> b) & 1u) << (logn - 1 - b);
+        return r;
+    };
+    for (uint32_t k = 0; k < degree; k++)
+    {
+        const uint32_t u = (uint32_t)(((uint64_t)(2 * brev(k) + 1) * elt) & (2 * degree - 1));
+        src[k]           = (uint16_t)brev(u >> 1);
+    }
+    return SE_SUCCESS;
+}
+
+int se_amd_gen_galois_keys(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint32_t *elts, size_t G,
+                           const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *gk0, uint32_t *gk1)
+{
+    if (!ctx || !sk_packed || !elts || !a_seeds || !e_seeds || !gk0 || !gk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.gen_galois_keys(sk_packed, elts, G, a_seeds, e_seeds, gk0, gk1);
+}
+
+int se_amd_set_galois_keys(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1)
+{
+    if (!ctx || !elts || !gk0 || !gk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_galois_keys(elts, G, gk0, gk1);
+}
+
+int se_amd_ct_galois_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                            uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois(d_c0, d_c1, B, primes, elt, d_out0, d_out1, as_stream(stream));
+}
+
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)
 {
     seamd::HostParams hp;

@@ -527,7 +527,8 @@ int Context::gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, con
 }
 
 int Context::gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
-                            const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin)
+                            const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin,
+                            uint32_t galois_elt)
 {
     SEAMD_HIP(hipSetDevice(device));
     int rc = ensure_scratch(K);
@@ -593,7 +594,10 @@ int Context::gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
         sa.c0 = pk0 + (size_t)j * n;
         sa.j  = (int)j;
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
-        if (relin) SEAMD_HIP(launch_relin_diag(dp, j, s_hat, pk0, nullptr));
+        if (relin && galois_elt)
+            SEAMD_HIP(launch_galois_diag(dp, j, galois_elt, s_hat, pk0, nullptr));
+        else if (relin)
+            SEAMD_HIP(launch_relin_diag(dp, j, s_hat, pk0, nullptr));
     }
     SEAMD_HIP(hipDeviceSynchronize());
     if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys, K * (n / 4), hipMemcpyDeviceToHost));
@@ -1450,6 +1454,127 @@ int Context::ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t
     ra.np     = (uint32_t)hp.nprimes;
     ra.primes = (uint32_t)primes;
     SEAMD_HIP(launch_ct_relin(dp, dt, ra, st));
+    return 0;
+}
+
+// Galois keys: per element the chain of gen_relin_key on that element's block of seeds, with the diagonal term
+// 2^(15 t) sigma(s_hat) instead of 2^(15 t) s_hat^2 (kernels/ct_ops.hip, k_galois_diag).
+int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, size_t G, const uint8_t *a_seeds,
+                             const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out)
+{
+    if (G == 0 || G > kMaxGaloisKeys)
+    {
+        set_last_error("Galois keys: between 1 and 64 elements");
+        return kErrInvalid;
+    }
+    for (size_t g = 0; g < G; g++)
+        if (!(elts[g] & 1) || elts[g] >= 2 * hp.n)
+        {
+            set_last_error("Galois element " + std::to_string(elts[g]) + " is not odd and below 2n");
+            return kErrInvalid;
+        }
+    for (size_t i = 0; i < hp.n / 4; i++)
+        if (sk_packed[i] & (sk_packed[i] >> 1) & 0x55u)
+        {
+            set_last_error("secret key holds an invalid 2-bit code (3)");
+            return kErrInvalid;
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    const size_t R = 2 * hp.nprimes, slab = R * hp.nprimes * hp.n;
+    for (size_t g = 0; g < G; g++)
+    {
+        const int rc = gen_keys_chain(R, sk_packed, nullptr, a_seeds + g * R * 64, e_seeds + g * R * 64, nullptr,
+                                      gk0_out + g * slab, gk1_out + g * slab, true, elts[g]);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// Public material, validated like the relinearisation key; the whole installed set is replaced, and only after every
+// call already enqueued has finished.  Anything refused leaves the previous set in place: the new blocks are built
+// beside it and swapped in at the end.
+int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1)
+{
+    const size_t n = hp.n, np = hp.nprimes, R = 2 * np, slab = R * np * n;
+    if (G == 0 || G > kMaxGaloisKeys)
+    {
+        set_last_error("Galois keys: between 1 and 64 elements");
+        return kErrInvalid;
+    }
+    for (size_t g = 0; g < G; g++)
+    {
+        bool bad = !(elts[g] & 1) || elts[g] >= 2 * n;
+        for (size_t h = 0; h < g; h++) bad |= elts[h] == elts[g];
+        if (bad)
+        {
+            set_last_error("Galois element " + std::to_string(elts[g]) + " is even, not below 2n, or listed twice");
+            return kErrInvalid;
+        }
+    }
+    for (size_t g = 0; g < G; g++)
+        for (size_t r = 0; r < R; r++)
+            for (size_t i = 0; i < np; i++)
+            {
+                const uint32_t q   = hp.q[i];
+                const uint32_t *r0 = gk0 + ((g * R + r) * np + i) * n, *r1 = gk1 + ((g * R + r) * np + i) * n;
+                uint32_t bad       = 0;
+                for (size_t c = 0; c < n; c++) bad |= (uint32_t)(r0[c] >= q) | (uint32_t)(r1[c] >= q);
+                if (bad)
+                {
+                    set_last_error("Galois key of element " + std::to_string(elts[g]) + ": row " + std::to_string(r) +
+                                   " holds a word not reduced modulo its prime");
+                    return kErrInvalid;
+                }
+            }
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    DevBuf<uint32_t> d_tmp;
+    std::vector<DevBuf<uint32_t>> blocks(G);
+    SEAMD_HIP(d_tmp.grow(2 * slab));
+    for (size_t g = 0; g < G; g++)
+    {
+        SEAMD_HIP(blocks[g].grow(4 * slab));
+        SEAMD_HIP(hipMemcpy(d_tmp, gk0 + g * slab, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+        SEAMD_HIP(hipMemcpy(d_tmp + slab, gk1 + g * slab, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+        SEAMD_HIP(launch_relin_key_rows(dp, d_tmp, blocks[g], 2 * R, nullptr));
+        SEAMD_HIP(hipDeviceSynchronize());   // d_tmp is reused; after the last one: calls in flight have left the old set
+    }
+    galois_elts.assign(elts, elts + G);
+    d_gk = std::move(blocks);
+    return 0;
+}
+
+// One launch, no scratch, no secret key; reads the installed Galois key of `elt`.
+int Context::ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, uint32_t elt,
+                       uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!d_c0 || !d_c1 || !d_out0 || !d_out1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes || B >= ((size_t)1 << 32)) return kErrInvalid;
+    if (!(elt & 1) || elt >= 2 * hp.n) return kErrInvalid;
+    for (const void *p : {(const void *)d_c0, (const void *)d_c1, (const void *)d_out0, (const void *)d_out1})
+        if ((uintptr_t)p & 15) return kErrInvalid;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t g = 0;
+    while (g < galois_elts.size() && galois_elts[g] != elt) g++;
+    if (g == galois_elts.size())
+    {
+        set_last_error("no Galois key is installed for element " + std::to_string(elt) + " (se_amd_set_galois_keys)");
+        return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    GaloisArgs ga{};
+    ga.c0     = d_c0;
+    ga.c1     = d_c1;
+    ga.out0   = d_out0;
+    ga.out1   = d_out1;
+    ga.gk     = d_gk[g];
+    ga.half   = (size_t)2 * hp.nprimes * hp.nprimes * 2 * hp.n;
+    ga.B      = B;
+    ga.np     = (uint32_t)hp.nprimes;
+    ga.primes = (uint32_t)primes;
+    ga.elt    = elt;
+    SEAMD_HIP(launch_ct_galois(dp, dt, ga, st));
     return 0;
 }
 

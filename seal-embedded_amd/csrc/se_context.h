@@ -21,6 +21,8 @@ constexpr int kErrNoDevice = -19;    // SE_ERR_NO_DEVICE
 constexpr int kErrHip      = -1001;  // SE_ERR_HIP
 constexpr int kErrNoKey    = -1002;  // SE_ERR_NO_KEY
 
+constexpr size_t kMaxGaloisKeys = 64;  // elements of one installed set (SE_AMD_MAX_GALOIS_KEYS)
+
 constexpr int kStageCount = 6;  // cbd, uniform, ternary, encode_encrypt (fused), encode_rns, ntt_fuse
 
 struct HostPipe;
@@ -55,6 +57,10 @@ struct Context
     // of key words followed by the row of their Shoup companions (kernels/kernel_args.h, RelinArgs)
     DevBuf<uint32_t> d_evk;
     bool have_relin = false;
+    // Galois keys (se_amd_set_galois_keys; public material): the installed elements and one device block per element
+    // in the layout of d_evk
+    std::vector<uint32_t> galois_elts;
+    std::vector<DevBuf<uint32_t>> d_gk;
     DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
     DevBuf<uint32_t> d_kbad;                   // [1 + cap] count + records whose index was out of range
 
@@ -199,6 +205,13 @@ struct Context
     int set_relin_key(const uint32_t *evk0, const uint32_t *evk1);
     int ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B, size_t primes,
                  uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    // slot rotations: Galois keys of G elements (host pointers, [G][R][np][n] per half) and the automorphism fused
+    // with its key switch (GaloisArgs); one launch, no scratch
+    int gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, size_t G, const uint8_t *a_seeds,
+                        const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out);
+    int set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1);
+    int ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, uint32_t elt, uint32_t *d_out0,
+                  uint32_t *d_out1, hipStream_t st);
     // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
     int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
                    uint32_t *d_out1, hipStream_t st);
@@ -239,9 +252,11 @@ struct Context
 
 private:
     // the launch chain of gen_keys_batch; relin: ONE secret key (sk_in, n/4 bytes) shared by all K = 2 np rows and the
-    // diagonal term of a relinearisation key added to pk0.  The caller holds `mu`.
+    // diagonal term of a relinearisation key added to pk0 -- or, with galois_elt != 0, that of the Galois key of the
+    // element.  The caller holds `mu`.
     int gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
-                       const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin);
+                       const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin,
+                       uint32_t galois_elt = 0);
     int decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
                            size_t primes, double scale, const uint32_t *d_key_idx, bool keyed, int64_t *d_pte,
                            float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);

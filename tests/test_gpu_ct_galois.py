@@ -1,0 +1,540 @@
+"""Slot rotations (-m gpu): Galois keys (se_amd_gen_galois_keys, se_amd_set_galois_keys) and the automorphism fused with
+its key switch, se_amd_ct_galois_device.
+Every expectation is built from the oracle's primitives (ntt, intt, decrypt, fft, expand_ternary) and Python / NumPy
+integers, never from the code under test.  The automorphism of an expectation is its coefficient-domain definition
+x^k -> +-x^(k g mod n) pushed through o.intt and o.ntt, never se_amd_galois_table.  Every comparison is bit-exact except
+the reference's own acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
+Oracle(n, L - 1) is the oracle of the level below Oracle(n, L): the default chains are prefixes of one another."""
+import ctypes as C
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import vectors as V
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, build_example, crt_centred,  # noqa: F401
+                         dev_t, encrypt_sym, env, expectation, host_u32, ntt_secret, run_decrypt, stream_of)
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 0x5A5A5A5A
+DIGIT_BITS = 15
+DIGIT_MASK = (1 << DIGIT_BITS) - 1
+LIFT = 1 << 30
+
+
+# ---- helpers restated from the product tests (a test module imports from the support modules only) ------------------
+def centred(x, q):
+    """canonical residues -> int64 representatives in (-q/2, q/2]  (q odd)."""
+    x = x.astype(np.int64)
+    return np.where(x > q // 2, x - q, x)
+
+
+def negacyclic(a, s):
+    """a * s mod (x^n + 1) in int64 (the callers keep every sum below 2^62)."""
+    n = a.shape[0]
+    full = np.convolve(a, s)
+    res = full[:n].copy()
+    res[:n - 1] -= full[n:]
+    return res
+
+
+def rescale_expect(o, slab):
+    """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: out[j] = (in[j] - NTT_j(delta mod q_j)) . q_last^-1 mod q_j with
+    delta the centred INTT of the last row, from o.intt / o.ntt and uint64 arithmetic."""
+    B, L, n = slab.shape
+    q_last = o.q[L - 1]
+    out = np.zeros((B, L - 1, n), dtype=np.uint32)
+    for b in range(B):
+        delta = centred(o.intt(slab[b, L - 1], L - 1), q_last)
+        for j in range(L - 1):
+            q = o.q[j]
+            inv = pow(q_last, -1, q)
+            t = o.ntt((delta % q).astype(np.uint32), j).astype(np.uint64)
+            diff = (slab[b, j].astype(np.uint64) + np.uint64(q) - t) % np.uint64(q)
+            out[b, j] = ((diff * np.uint64(inv)) % np.uint64(q)).astype(np.uint32)
+    return out
+
+
+def sentinel_out(env, words, extra):
+    return env["torch"].full((words + extra,), SENTINEL, dtype=env["torch"].int32, device=env["dev"])
+
+
+def take(t, words, shape, what):
+    """Host copy of the first `words` words of a sentinel-backed output; the words behind them must be untouched."""
+    h = host_u32(t)
+    assert (h[words:] == SENTINEL).all(), f"{what}: words behind the result are written"
+    return h[:words].reshape(shape)
+
+
+def rand_slab(rng, q, count, n, primes=None):
+    primes = len(q) if primes is None else primes
+    return np.stack([rng.integers(0, q[j], (count, n), dtype=np.uint32) for j in range(primes)], axis=1)
+
+
+def unit_values(B, n, seed):
+    """float32 [B][n/2], uniform in [-1, 1]."""
+    return np.random.default_rng(seed).uniform(-1.0, 1.0, (B, n // 2)).astype(np.float32)
+
+
+def digits_of(o, rec, L):
+    """Record [L][n] -> the 2 L digit polynomials D_{j,t} (uint32, natural order), row r = 2j + t."""
+    out = []
+    for j in range(L):
+        c = o.intt(rec[j], j)
+        out += [c & np.uint32(DIGIT_MASK), c >> np.uint32(DIGIT_BITS)]
+    return out
+
+
+def relin_expect(o, d0, d1, d2, evk0, evk1):
+    """out_k[b][i] = d_k[b][i] + sum_r NTT_i(D_r) . evk_k[r][i] mod q_i, from o.intt / o.ntt and uint64 arithmetic (a
+    product is below 2^60, reduced before it is added)."""
+    B, L, n = d0.shape
+    out0, out1 = np.zeros_like(d0), np.zeros_like(d1)
+    for b in range(B):
+        D = digits_of(o, d2[b], L)
+        for i in range(L):
+            q = np.uint64(o.q[i])
+            acc0, acc1 = d0[b, i].astype(np.uint64), d1[b, i].astype(np.uint64)
+            for r, dig in enumerate(D):
+                f = o.ntt(dig, i).astype(np.uint64)
+                acc0 = (acc0 + (f * evk0[r, i].astype(np.uint64)) % q) % q
+                acc1 = (acc1 + (f * evk1[r, i].astype(np.uint64)) % q) % q
+            out0[b, i], out1[b, i] = acc0, acc1
+    return out0, out1
+
+
+# ---- the automorphism, in the coefficient domain --------------------------------------------------------------------
+def image(n, g):
+    """-> (pos, neg): coefficient k of x goes to position pos[k] of x(X^g), negated where neg[k]."""
+    u = (np.arange(n, dtype=np.int64) * g) % (2 * n)
+    return u % n, u >= n
+
+
+def sigma_coeff(a, g, q=None):
+    """x(X) -> x(X^g) on natural-order coefficients: residues mod q (uint32; a negated 0 stays 0), or with q = None
+    plain integers (int64 or object)."""
+    pos, neg = image(a.shape[0], g)
+    out = np.zeros_like(a)
+    if q is None:
+        out[pos] = np.where(neg, -a, a)
+    else:
+        out[pos] = np.where(neg, (q - a.astype(np.int64)) % q, a).astype(a.dtype)
+    return out
+
+
+def sigma_slab(o, slab, g):
+    """sigma on every NTT-form row of a slab [B][L][n] through o.intt / o.ntt."""
+    out = np.zeros_like(slab)
+    for b in range(slab.shape[0]):
+        for j in range(slab.shape[1]):
+            out[b, j] = o.ntt(sigma_coeff(o.intt(slab[b, j], j), g, o.q[j]), j)
+    return out
+
+
+def galois_expect(o, c0, c1, g, gk0, gk1):
+    """The definition: relin_expect on (sigma(c0), 0, sigma(c1)) with the key of the element."""
+    return relin_expect(o, sigma_slab(o, c0, g), np.zeros_like(c1), sigma_slab(o, c1, g), gk0, gk1)
+
+
+def run_galois(env, ctx, c0, c1, elt, primes):
+    """One call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois(c0, c1, elt, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "galois out0"), take(out1, words, (B, primes, n), "galois out1")
+
+
+def galois_seeds(npr, G, label):
+    return V.derive_seeds(label + "-a", G * 2 * npr), V.derive_seeds(label + "-e", G * 2 * npr)
+
+
+# ---- test 1: the definition on arbitrary slabs and key words --------------------------------------------------------
+def edge_row(o, j, rng, elts):
+    """NTT form of natural-order coefficients that hold both sides of the digit boundary, 0, 1 and q - 1, each of them
+    on at least one index whose image is negated and on one whose image is not, for every element of `elts`."""
+    n, q = o.n, o.q[j]
+    edges = np.array([0, 1, DIGIT_MASK, DIGIT_MASK + 1, DIGIT_MASK + 2, q - 1], dtype=np.uint32)
+    c = rng.integers(1, q, n, dtype=np.uint32)
+    for start in (0, n // 2, n - 13):           # twice, 7 apart: an even and an odd index for every value
+        c[start:start + 6] = c[start + 7:start + 13] = edges
+    for g in elts:
+        _, neg = image(n, g)
+        for v in edges:
+            at = c == v
+            assert (at & neg).any() and (at & ~neg).any(), (g, int(v))
+    row = o.ntt(c, j)
+    assert (o.intt(row, j) == c).all()
+    return row
+
+
+GALOIS_CASES = [((1024, 1), (1,), 3), ((4096, 3), (3, 2), 3), ((16384, 13), (13,), 2)]
+
+
+@pytest.mark.parametrize("shape,levels,B", GALOIS_CASES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_galois_arbitrary_slabs_and_key(env, shape, levels, B):
+    """Test 1: random residues for both slabs and for the installed keys of the elements 3 and n + 1 (n + 1 moves no
+    coefficient and negates every odd one); record 0 of c1 holds 0, 1, the digit boundaries and q - 1 on negated and on
+    kept positions, record 1 is all q_j - 1; against the definition.  A lower level uses the rows r < 2L and columns
+    i < L of the same keys; the sentinels behind the outputs survive.  No secret key is installed."""
+    from oracle.pyoracle import Oracle
+    n, npr = shape
+    R = 2 * npr
+    o = Oracle(n, npr)
+    ctx = env["pkg"].Context(n, npr)
+    q = o.q
+    rng = np.random.default_rng(37 * n + npr)
+    elts = [3, n + 1]
+    gk0 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in elts])
+    gk1 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in elts])
+    gk0[0, 0, 0, :4] = [0, 1, q[0] - 1, q[0] - 1]
+    ctx.set_galois_keys(elts, gk0, gk1)
+    for L in levels:
+        c0, c1 = rand_slab(rng, q, B, n, L), rand_slab(rng, q, B, n, L)
+        for j in range(L):
+            c1[0, j] = edge_row(o, j, rng, elts)
+        c0[1] = c1[1] = (np.array(q[:L], dtype=np.uint32) - 1)[:, None]
+        d0, d1 = dev_t(env, c0), dev_t(env, c1)
+        for k, g in enumerate(elts):
+            e0, e1 = galois_expect(o, c0, c1, g, gk0[k], gk1[k])
+            g0, g1 = run_galois(env, ctx, d0, d1, g, L)
+            assert (g0 == e0).all() and (g1 == e1).all(), (L, g)
+    ctx.close()
+
+
+# ---- test 2: the relinearisation twin -------------------------------------------------------------------------------
+def brev(v, bits):
+    r = np.zeros_like(v)
+    for b in range(bits):
+        r |= ((v >> b) & 1) << (bits - 1 - b)
+    return r
+
+
+def src_table(n, g):
+    """sigma_g(x)[k] = x[src[k]] on a bit-reversed NTT-form row, from the formula in Python."""
+    bits = n.bit_length() - 1
+    k = np.arange(n, dtype=np.int64)
+    return brev((((2 * brev(k, bits) + 1) * g) % (2 * n) - 1) // 2, bits)
+
+
+def test_galois_is_relin_of_the_permuted_record(env):
+    """Test 2: at 4096 x 3 the outputs have the bytes of ct_relin(sigma(c0), 0, sigma(c1)) with the element's key
+    installed as the relinearisation key; sigma is an index_select along the row."""
+    torch = env["torch"]
+    n, npr, B = 4096, 3, 3
+    R = 2 * npr
+    ctx = env["pkg"].Context(n, npr)
+    q = ctx.moduli()
+    rng = np.random.default_rng(4096 * 3 + 2)
+    elts = [pow(3, 7, 2 * n), 2 * n - 1]
+    gk0 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in elts])
+    gk1 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in elts])
+    ctx.set_galois_keys(elts, gk0, gk1)
+    c0, c1 = dev_t(env, rand_slab(rng, q, B, n)), dev_t(env, rand_slab(rng, q, B, n))
+    for k, g in enumerate(elts):
+        src = dev_t(env, src_table(n, g))
+        p0, p1 = c0.index_select(2, src).contiguous(), c1.index_select(2, src).contiguous()
+        ctx.set_relin_key(gk0[k], gk1[k])
+        r0, r1 = torch.full_like(c0, SENTINEL), torch.full_like(c0, SENTINEL)
+        ctx.ct_relin(p0, torch.zeros_like(p1), p1, r0, r1)
+        g0, g1 = run_galois(env, ctx, c0, c1, g, npr)
+        torch.cuda.synchronize()
+        assert (g0 == host_u32(r0)).all() and (g1 == host_u32(r1)).all(), g
+    ctx.close()
+
+
+# ---- test 3: key generation, installs and their refusals ------------------------------------------------------------
+def galois_diagonal(o, s_hat, g, j, t):
+    """(2^(15 t) mod q_j) . sigma(s_hat_j) mod q_j, uint64; sigma through the coefficient domain."""
+    q = o.q[j]
+    s = o.ntt(sigma_coeff(o.intt(s_hat[j], j), g, q), j).astype(np.uint64)
+    return (s * np.uint64(pow(2, DIGIT_BITS * t, q))) % np.uint64(q)
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_galois_key_generation(env, shape):
+    """Test 3: gen_galois_keys for {3, 3^-1, 2n - 1} equals gen_keys_batch(K = 2 np, this key replicated, the element's
+    block of seeds) plus the diagonal from the oracle's NTT(s) and sigma in Python; exactly the diagonal columns differ;
+    nothing installed in the context is touched.  ct_galois without a key, or for an element that is not installed, is
+    SE_ERR_NO_KEY; an install with a word == q_i, a duplicate or an even element is refused and the previous set still
+    works."""
+    from oracle.pyoracle import Oracle
+    torch = env["torch"]
+    pkg = env["pkg"]
+    n, npr = shape
+    R = 2 * npr
+    o = Oracle(n, npr)
+    ctx = pkg.Context(n, npr)
+    sk = V.secret_key(n, seed=3)
+    elts = [3, pow(3, -1, 2 * n), 2 * n - 1]
+    G = len(elts)
+    sa, se = galois_seeds(npr, G, "gk-keygen")
+    gk0, gk1 = ctx.gen_galois_keys(sk, elts, sa, se)
+    s_hat = ntt_secret(o, sk)
+    sa, se = np.asarray(sa).reshape(G, R, 64), np.asarray(se).reshape(G, R, 64)
+    for k, g in enumerate(elts):
+        _, pk0, pk1 = ctx.gen_keys_batch(sa[k], se[k], sk_in=np.tile(sk, (R, 1)))
+        exp0 = pk0.copy()
+        for j in range(npr):
+            for t in range(2):
+                exp0[2 * j + t, j] = (pk0[2 * j + t, j].astype(np.uint64) + galois_diagonal(o, s_hat, g, j, t)) % np.uint64(o.q[j])
+        assert (gk1[k] == pk1).all(), g
+        assert (gk0[k] == exp0).all(), g
+        assert (gk0[k] != pk0).any(axis=2).sum() == R, g      # exactly the diagonal columns changed
+    # the generator installed nothing: no secret key, no Galois key
+    B = 2
+    slab = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
+    st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
+    p = lambda x: C.c_void_p(x.data_ptr())
+    z = C.c_void_p(None)
+    assert ctx.L.se_amd_decrypt_level_device(ctx.h, p(slab), p(slab), B, npr, ctx.scale(), z, z, z, p(st),
+                                             stream_of(env)) == SE_ERR_NO_KEY
+    out0, out1 = torch.full_like(slab, SENTINEL), torch.full_like(slab, SENTINEL)
+    gal = lambda elt: ctx.L.se_amd_ct_galois_device(ctx.h, p(slab), p(slab), B, npr, elt, p(out0), p(out1),
+                                                    stream_of(env))
+    assert gal(3) == SE_ERR_NO_KEY
+    # a refused first install installs nothing
+    bad0 = gk0.copy()
+    bad0[0, 0, 0, 0] = o.q[0]
+    with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
+        ctx.set_galois_keys(elts, bad0, gk1)
+    assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
+    assert gal(3) == SE_ERR_NO_KEY
+    torch.cuda.synchronize()
+    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    # the first two elements are installed: the third is not there
+    ctx.set_galois_keys(elts[:2], gk0[:2], gk1[:2])
+    assert gal(elts[2]) == SE_ERR_NO_KEY and gal(5) == SE_ERR_NO_KEY
+    rng = np.random.default_rng(n + npr)
+    c0, c1 = rand_slab(rng, o.q, B, n), rand_slab(rng, o.q, B, n)
+    d0, d1 = dev_t(env, c0), dev_t(env, c1)
+    want = galois_expect(o, c0[:1], c1[:1], elts[1], gk0[1], gk1[1])
+
+    def previous_set_works():
+        g0, g1 = run_galois(env, ctx, d0, d1, elts[1], npr)
+        assert (g0[:1] == want[0]).all() and (g1[:1] == want[1]).all()
+        assert gal(elts[2]) == SE_ERR_NO_KEY
+
+    previous_set_works()
+    refused = []
+    for which, (k, r, i, c) in ((0, (0, 0, 0, 0)), (1, (G - 1, R - 1, npr - 1, n - 1))):
+        k0, k1 = gk0.copy(), gk1.copy()
+        (k0, k1)[which][k, r, i, c] = o.q[i]
+        refused.append((elts, k0, k1))                                   # a word == q_i
+    refused.append(([3, elts[1], 3], gk0, gk1))                          # a duplicate element
+    refused.append(([3, 4, elts[2]], gk0, gk1))                          # an even element
+    refused.append(([3, 2 * n + 1, elts[2]], gk0, gk1))                  # an element >= 2n
+    for el, k0, k1 in refused:
+        with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
+            ctx.set_galois_keys(el, k0, k1)
+        assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value), el
+        previous_set_works()
+    # a new install replaces the whole set
+    ctx.set_galois_keys(elts[2:], gk0[2:], gk1[2:])
+    assert gal(elts[1]) == SE_ERR_NO_KEY and gal(elts[2]) == 0
+    torch.cuda.synchronize()
+    assert int(torch.count_nonzero(out0)) == 0 and int(torch.count_nonzero(out1)) == 0    # zero slabs rotate to zero
+    # the generator's own refusals
+    bad_sk = sk.copy()
+    bad_sk[5] |= 0x03
+    for args in ((bad_sk, elts), (sk, [3, 6, 5]), (sk, [3, 2 * n + 1, 5])):
+        with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
+            ctx.gen_galois_keys(args[0], args[1], sa, se)
+        assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
+    f = ctx.L.se_amd_gen_galois_keys
+    el = np.array(elts, dtype=np.uint32)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    for Gbad in (0, 65):
+        assert f(ctx.h, hp(sk), hp(el), Gbad, hp(sa), hp(se), hp(gk0), hp(gk1)) == SE_ERR_INVALD_ARGUMENT
+        assert ctx.L.se_amd_set_galois_keys(ctx.h, hp(el), Gbad, hp(gk0), hp(gk1)) == SE_ERR_INVALD_ARGUMENT
+    assert gal(elts[2]) == 0
+    ctx.close()
+
+
+# ---- test 4: arguments ----------------------------------------------------------------------------------------------
+def test_galois_arguments(env):
+    """The argument errors return -22 and write nothing; B = 0 is a successful no-op; a level-2 call writes B . 2 . n
+    words and nothing behind them."""
+    torch = env["torch"]
+    n, npr, B = 4096, 3, 2
+    ctx = env["pkg"].Context(n, npr)
+    L, h = ctx.L, ctx.h
+    key = np.zeros((1, 2 * npr, npr, n), dtype=np.uint32)
+    ctx.set_galois_keys([3], key, key)
+    c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
+    c1 = torch.zeros_like(c0)
+    out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
+    out1 = torch.full_like(out0, SENTINEL)
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    z = C.c_void_p(None)
+    s = stream_of(env)
+    f = L.se_amd_ct_galois_device
+    bad_calls = [
+        (None, p(c0), p(c1), B, 3, 3, p(out0), p(out1), s),
+        (h, z, p(c1), B, 3, 3, p(out0), p(out1), s),                   # NULL mandatory pointers
+        (h, p(c0), z, B, 3, 3, p(out0), p(out1), s),
+        (h, p(c0), p(c1), B, 3, 3, z, p(out1), s),
+        (h, p(c0), p(c1), B, 3, 3, p(out0), z, s),
+        (h, p(c0), p(c1), B, 0, 3, p(out0), p(out1), s),               # primes outside [1, np]
+        (h, p(c0), p(c1), B, 4, 3, p(out0), p(out1), s),
+        (h, p(c0), p(c1), 2 ** 32, 3, 3, p(out0), p(out1), s),         # B >= 2^32
+        (h, p(c0, 4), p(c1), B, 3, 3, p(out0), p(out1), s),            # alignment, each slab
+        (h, p(c0), p(c1, 8), B, 3, 3, p(out0), p(out1), s),
+        (h, p(c0), p(c1), B, 3, 3, p(out0, 12), p(out1), s),
+        (h, p(c0), p(c1), B, 3, 3, p(out0), p(out1, 4), s),
+        (h, p(c0), p(c1), B, 3, 0, p(out0), p(out1), s),               # an even element, one >= 2n
+        (h, p(c0), p(c1), B, 3, 4, p(out0), p(out1), s),
+        (h, p(c0), p(c1), B, 3, 2 * n, p(out0), p(out1), s),
+        (h, p(c0), p(c1), B, 3, 2 * n + 3, p(out0), p(out1), s),
+    ]
+    for k, args in enumerate(bad_calls):
+        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
+    assert f(h, p(c0), p(c1), B, 3, 5, p(out0), p(out1), s) == SE_ERR_NO_KEY
+    assert f(h, p(c0), p(c1), 0, 3, 3, p(out0), p(out1), s) == 0
+    torch.cuda.synchronize()
+    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    assert f(h, p(c0), p(c1), B, 2, 3, p(out0), p(out1), s) == 0
+    torch.cuda.synchronize()
+    for o in (out0, out1):
+        flat = o.reshape(-1)
+        assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+    ctx.close()
+
+
+# ---- tests 5 and 6: a real key ---------------------------------------------------------------------------------------
+STEPS = (1, -3)
+
+
+@pytest.fixture(scope="module")
+def keyed_cases(env):
+    """Per shape, computed once: a context with a secret key and the Galois keys of the steps 1 and -3 installed, B = 4
+    fresh symmetric records with slot values in [-1, 1] and the same records lifted by 2^30 in the test's own
+    integers."""
+    from oracle.pyoracle import Oracle
+    cache = {}
+
+    def get(shape):
+        if shape in cache:
+            return cache[shape]
+        n, npr = shape
+        B = 4
+        o = Oracle(n, npr)
+        pkg = env["pkg"]
+        ctx = pkg.Context(n, npr)
+        sk = V.secret_key(n, seed=5)
+        ctx.set_secret_key(sk)
+        elts = [pkg.galois_element(n, s) for s in STEPS]
+        assert elts == [pow(3, s % (n // 2), 2 * n) for s in STEPS]
+        gk0, gk1 = ctx.gen_galois_keys(sk, elts, *galois_seeds(npr, len(elts), "gk-e2e"))
+        ctx.set_galois_keys(elts, gk0, gk1)
+        vals = unit_values(B, n, 3000 + n)
+        c0, c1, _, st = encrypt_sym(env, ctx, vals, first=200)
+        assert bool((st == 1).all())
+        qv = np.array(o.q, dtype=np.uint64)[None, :, None]
+        l0 = ((host_u32(c0).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
+        l1 = ((host_u32(c1).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
+        cache[shape] = dict(ctx=ctx, o=o, sk=sk, s_hat=ntt_secret(o, sk), elts=elts, gk0=gk0, gk1=gk1, vals=vals,
+                            fresh=(c0, c1), lifted=(l0, l1))
+        return cache[shape]
+
+    yield get
+    for c in cache.values():
+        c["ctx"].close()
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_galois_exact_key_switch_identity(env, keyed_cases, shape):
+    """Test 5: with y the oracle's centred decrypt of a lifted record, y' that of its rotation, D_r the digits of
+    sigma(c1) and e_r the key's errors recovered with the oracle (centred INTT of gk0 + gk1 . s_hat - diagonal),
+    y' - sigma(y) == sum_r negacyclic(D_r, e_r) as integers for every coefficient; sigma acts on the integers."""
+    c = keyed_cases(shape)
+    o, s_hat, npr, ctx = c["o"], c["s_hat"], c["o"].np, c["ctx"]
+    l0, l1 = (x[:2] for x in c["lifted"])
+    for k, g in enumerate(c["elts"]):
+        errs = []
+        for r in range(2 * npr):
+            per_prime = []
+            for i in (0, npr - 1):
+                q = np.uint64(o.q[i])
+                v = o.decrypt(c["gk0"][k, r, i], c["gk1"][k, r, i], s_hat[i], i).astype(np.uint64)
+                if i == r // 2:
+                    v = (v + q - galois_diagonal(o, s_hat, g, i, r % 2)) % q
+                per_prime.append(centred(o.intt(v.astype(np.uint32), i), o.q[i]))
+            assert (per_prime[0] == per_prime[1]).all() and np.abs(per_prime[0]).max() <= 64, r   # one small integer e_r
+            errs.append(per_prime[0])
+        g0, g1 = run_galois(env, ctx, dev_t(env, l0), dev_t(env, l1), g, npr)
+        p1 = sigma_slab(o, l1, g)
+        for b in range(2):
+            y = np.array(expectation(o, l0[b], l1[b], s_hat)["y"], dtype=object)
+            y2 = np.array(expectation(o, g0[b], g1[b], s_hat)["y"], dtype=object)
+            ks = np.zeros(o.n, dtype=np.int64)
+            for dig, er in zip(digits_of(o, p1[b], npr), errs):
+                ks += negacyclic(dig.astype(np.int64), er)         # n . 2^15 . 64 per term: far below 2^62
+            assert ((y2 - sigma_coeff(y, g)) == ks.astype(object)).all(), (g, b)
+            print(f"element {g}, record {b}: max |key-switch term| = {int(np.abs(ks).max())}")
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_rotation_end_to_end(env, keyed_cases, shape):
+    """Test 6: ct_lincomb with weight 2^30 -> ct_galois (step 1, then step -3 on a second pass) -> ct_rescale ->
+    decrypt_level(primes = np - 1, scale = Delta 2^30 / q_last) on B = 4 records with slot values in [-1, 1]: every
+    stage equals its definition, the final pte / values / values_f64 equal the oracle's on the final records bit for
+    bit, and the slots are within the reference's 0.1 of np.roll(vals, -s) (applied to the expectation first; a CPU
+    simulation of the same chain, tools/ct_galois_noise_sim.py, puts the error near 1e-4).  The worst error is
+    printed."""
+    from oracle.pyoracle import Oracle
+    torch = env["torch"]
+    c = keyed_cases(shape)
+    ctx, o = c["ctx"], c["o"]
+    n, npr = shape
+    lo = Oracle(n, npr - 1)
+    B = c["vals"].shape[0]
+    # the lift: one CSR row per record with the single weight 2^30
+    up0, up1 = sentinel_out(env, B * npr * n, 2 * n), sentinel_out(env, B * npr * n, 2 * n)
+    ctx.ct_lincomb(c["fresh"][0], up0, c["fresh"][1], up1, row_ptr=dev_t(env, np.arange(B + 1, dtype=np.uint32)),
+                   idx=dev_t(env, np.arange(B, dtype=np.uint32)), w=dev_t(env, np.full(B, LIFT, dtype=np.int32)))
+    torch.cuda.synchronize()
+    l0, l1 = take(up0, B * npr * n, (B, npr, n), "lift"), take(up1, B * npr * n, (B, npr, n), "lift")
+    assert (l0 == c["lifted"][0]).all() and (l1 == c["lifted"][1]).all()
+    scale = o.scale * LIFT / o.q[npr - 1]
+    for k, (s, g) in enumerate(zip(STEPS, c["elts"])):
+        g0, g1 = run_galois(env, ctx, dev_t(env, l0), dev_t(env, l1), g, npr)
+        e0, e1 = galois_expect(o, l0[:2], l1[:2], g, c["gk0"][k], c["gk1"][k])
+        assert (g0[:2] == e0).all() and (g1[:2] == e1).all(), s
+        for b in range(B):
+            big = max(abs(v) for v in expectation(o, g0[b], g1[b], c["s_hat"])["y"])
+            assert big < 2 ** 62, (s, b, big)
+        words = B * (npr - 1) * n
+        s0, s1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+        ctx.ct_rescale(dev_t(env, g0), s0, dev_t(env, g1), s1, primes=npr)
+        torch.cuda.synchronize()
+        f0, f1 = take(s0, words, (B, npr - 1, n), "rescale"), take(s1, words, (B, npr - 1, n), "rescale")
+        assert (f0 == rescale_expect(o, g0)).all() and (f1 == rescale_expect(o, g1)).all(), s
+        got = run_decrypt(env, ctx, dev_t(env, f0), dev_t(env, f1), npr - 1, scale)
+        worst = 0.0
+        for b in range(B):
+            e = expectation(lo, f0[b], f1[b], c["s_hat"][:npr - 1], scale)
+            assert e["status"] == 1
+            assert_matches(got, b, e, (s, b))
+            want = np.roll(c["vals"][b].astype(np.float64), -s)
+            err_e = float(np.abs(e["values"].astype(np.float64) - want).max())
+            err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want).max())
+            print(f"step {s}, record {b}: max |values - roll| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
+            assert err_e < 0.1 and err_g < 0.1, (s, b, err_e, err_g)
+            worst = max(worst, err_g)
+        print(f"{n} x {npr}, step {s}: worst error {worst:.3e}")
+        assert worst < 0.1
+
+
+# ---- test 7: the example --------------------------------------------------------------------------------------------
+def test_slot_sum_example(env, tmp_path):
+    """examples/slot_sum_roundtrip.c from plain gcc: packed dot products through the tensor, relin, four rotate-and-adds,
+    rescale and decrypt_level come back within the reference's 0.1."""
+    exe = build_example("slot_sum_roundtrip", tmp_path, hip=True, extra=("-lm",))
+    r = subprocess.run([str(exe), "4096", "3", "8"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"failed=0 B=8 .*max_abs_error=([0-9.e+-]+)", r.stdout)
+    assert m and float(m.group(1)) < 0.1, r.stdout

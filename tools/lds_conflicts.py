@@ -106,3 +106,20 @@ for stride in (16,20,24,28,36,40,44,52,68):
     w=sum(wr_conf([stride*l+4*c for l in range(64)]) for c in range(4))
     r=sum(rd_conf([stride*((64*i+l)>>2)+4*((64*i+l)&3) for l in range(64)]) for i in range(4))
     print(stride,'write',w,'read',r)
+
+
+# ---- k_ct_galois (ct_ops.hip): the coefficient-domain scatter of sigma(c1) and the NTT-domain gather of sigma(c0)
+print("k_ct_galois: extra cycles per workgroup; scatter = 16 x ds_write_b32 to (k g) mod n from tile layout logn-4, "
+      "gather = 16 x ds_read_b32 at src_g(k) from quad layout")
+def galois_src(k,g,logn):
+    n=1<<logn
+    return bitrev(((((2*bitrev(k,logn)+1)*g)%(2*n))-1)//2,logn)
+for logn in (10,12,14):
+    n=1<<logn; th=n//16
+    for name,g in (("3",3),("3^5",pow(3,5,2*n)),("3^-1",pow(3,-1,2*n)),("3^(n/4)",pow(3,n//4,2*n)),("n+1",n+1),("2n-1",2*n-1)):
+        sc=ga=0
+        for w in range(th//64):
+            for e in range(16):
+                sc+=conflicts([((64*w+l+th*e)*g)%n for l in range(64)],'w32')
+                ga+=conflicts([galois_src((w<<10)+((e>>2)<<8)+(l<<2)+(e&3),g,logn) for l in range(64)],'r32')
+        print(logn,name,'scatter',sc,'gather',ga,'of',16*(th//64),'instructions')
