@@ -592,26 +592,36 @@ class Context:
                                                          _ptr(status), _stream_ptr()),
                "se_amd_decrypt3_level_keyed_device")
 
-    def gen_relin_key(self, sk_packed, a_seeds, e_seeds):
-        """Relinearisation key of sk_packed from R = 2 np seed pairs [R][64]: (evk0, evk1) uint32 [R][np][n]."""
+    def _evk_gen_buffers(self, sk_packed, a_seeds, e_seeds, lead=()):
+        """What generating evaluation keys takes and fills: the packed key, the seed blocks lead + [R][64] and two
+        zeroed key halves lead + [R][np][n], R = 2 np."""
         import numpy as np
         R = 2 * self.np
         sk = np.ascontiguousarray(sk_packed, dtype=np.uint8)
         assert sk.size == self.n // 4
-        sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(R, 64)
-        se = np.ascontiguousarray(e_seeds, dtype=np.uint8).reshape(R, 64)
-        evk0 = np.zeros((R, self.np, self.n), dtype=np.uint32)
-        evk1 = np.zeros_like(evk0)
+        sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(*lead, R, 64)
+        se = np.ascontiguousarray(e_seeds, dtype=np.uint8).reshape(*lead, R, 64)
+        k0 = np.zeros((*lead, R, self.np, self.n), dtype=np.uint32)
+        return sk, sa, se, k0, np.zeros_like(k0)
+
+    def _evk_halves(self, k0, k1, count=1):
+        """The two halves of `count` evaluation keys as contiguous uint32, [count][2 np][np][n] words each."""
+        import numpy as np
+        k0 = np.ascontiguousarray(k0, dtype=np.uint32)
+        k1 = np.ascontiguousarray(k1, dtype=np.uint32)
+        assert k0.size == count * 2 * self.np * self.np * self.n == k1.size
+        return k0, k1
+
+    def gen_relin_key(self, sk_packed, a_seeds, e_seeds):
+        """Relinearisation key of sk_packed from R = 2 np seed pairs [R][64]: (evk0, evk1) uint32 [R][np][n]."""
+        sk, sa, se, evk0, evk1 = self._evk_gen_buffers(sk_packed, a_seeds, e_seeds)
         _check(self.L.se_amd_gen_relin_key(self.h, _ptr(sk), _ptr(sa), _ptr(se), _ptr(evk0), _ptr(evk1)),
                "se_amd_gen_relin_key")
         return evk0, evk1
 
     def set_relin_key(self, evk0, evk1):
         """evk0, evk1 [2 np][np][n] uint32 (as gen_relin_key returns them); a word >= q_i is refused."""
-        import numpy as np
-        evk0 = np.ascontiguousarray(evk0, dtype=np.uint32)
-        evk1 = np.ascontiguousarray(evk1, dtype=np.uint32)
-        assert evk0.size == 2 * self.np * self.np * self.n == evk1.size
+        evk0, evk1 = self._evk_halves(evk0, evk1)
         _check(self.L.se_amd_set_relin_key(self.h, _ptr(evk0), _ptr(evk1)), "se_amd_set_relin_key")
 
     def ct_relin(self, d0, d1, d2, out0, out1, primes=None):
@@ -626,15 +636,9 @@ class Context:
         """Galois keys of sk_packed for the elements `elts` (odd, below 2n) from G blocks of R = 2 np seed pairs
         [G][R][64]: (gk0, gk1) uint32 [G][R][np][n]."""
         import numpy as np
-        R = 2 * self.np
         el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
         G = el.size
-        sk = np.ascontiguousarray(sk_packed, dtype=np.uint8)
-        assert sk.size == self.n // 4
-        sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(G, R, 64)
-        se = np.ascontiguousarray(e_seeds, dtype=np.uint8).reshape(G, R, 64)
-        gk0 = np.zeros((G, R, self.np, self.n), dtype=np.uint32)
-        gk1 = np.zeros_like(gk0)
+        sk, sa, se, gk0, gk1 = self._evk_gen_buffers(sk_packed, a_seeds, e_seeds, lead=(G,))
         _check(self.L.se_amd_gen_galois_keys(self.h, _ptr(sk), _ptr(el), G, _ptr(sa), _ptr(se), _ptr(gk0), _ptr(gk1)),
                "se_amd_gen_galois_keys")
         return gk0, gk1
@@ -644,9 +648,7 @@ class Context:
         word >= q_i, an even or repeated element is refused and the previous set stays."""
         import numpy as np
         el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        gk0 = np.ascontiguousarray(gk0, dtype=np.uint32)
-        gk1 = np.ascontiguousarray(gk1, dtype=np.uint32)
-        assert gk0.size == el.size * 2 * self.np * self.np * self.n == gk1.size
+        gk0, gk1 = self._evk_halves(gk0, gk1, el.size)
         _check(self.L.se_amd_set_galois_keys(self.h, _ptr(el), el.size, _ptr(gk0), _ptr(gk1)),
                "se_amd_set_galois_keys")
 

@@ -417,29 +417,96 @@ hipError_t launch_ct_rescale(const DevParams &P, const DevTables &T, const Resca
 }
 
 // ------------------------------------------------------------------------------------------
-// Relinearisation: (d0, d1, d2) of level L -> (out0, out1) of level L with the installed evaluation key,
-//   out0[b][i] = d0[b][i] + sum_{j < L, t < 2} NTT_i(D_{j,t}) . evk0[2j + t][i]  mod q_i   (out1: d1 and evk1),
-// D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients of INTT_j(d2[b][j]) (n^-1 included).
-// Baseline form, built from the pieces of k_ct_rescale: one workgroup of n/16 threads per (record, output prime i).
-// It walks j: row j of d2 (quad loads) -> quads_to_tile -> intt_tiles mod q_j -> . n^-1 -> canonical c < q_j < 2^30 in
-// tile layout LOGN-4; per digit t: c & 0x7FFF resp. c >> 15 (below 2^15 < q_i: a residue of every prime as it stands)
-// -> ntt_tiles mod q_i, which STARTS in that layout -> tile_to_quads -> multiply-accumulate against row 2j + t of both
-// key halves (quad loads of the word row and of its Shoup row).  L INTTs and 2 L NTTs per workgroup, L^2 and 2 L^2 per
-// record, no scratch: the row of d2 is transformed again by every output prime.
-// Lazy range of the accumulators.  Every prime is below 2^30.  A key word is w < q_i (set_relin_key refuses others) and
+// The key switch under an evaluation key, shared by k_ct_relin and k_ct_galois: for one record and output prime i,
+//   acc0[i] = sum_{j < L, t < 2} NTT_i(D_{j,t}) . key0[2j + t][i]  mod q_i   (acc1: key1),
+// D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients c_j of an input row j.  Built from the
+// pieces of k_ct_rescale, one workgroup of n/16 threads per (record, output prime i), in two steps per input prime j:
+//   evk_row_coeffs: row j (quad loads) -> quads_to_tile -> intt_tiles mod q_j -> . n^-1 -> canonical c < q_j < 2^30 in
+//     tile layout LOGN-4 (the caller may permute the coefficients before the second step: k_ct_galois);
+//   evk_digits: per digit t, c & 0x7FFF resp. c >> 15 (below 2^15 < q_i: a residue of every prime as it stands)
+//     -> ntt_tiles mod q_i, which STARTS in that layout -> tile_to_quads -> multiply-accumulate against row 2j + t of
+//     both key halves (quad loads of the word row and of its Shoup row).
+// L INTTs and 2 L NTTs per workgroup, L^2 and 2 L^2 per record, no scratch: the input row is transformed again by every
+// output prime.
+// Lazy range of the accumulators.  Every prime is below 2^30.  A key word is w < q_i (the key setters refuse others) and
 // its companion is floor(w 2^32 / q_i), so mul_shoup_lazy(y, w, .) is in [0, 2 q_i) for ANY 32-bit y -- y is the lazy
 // NTT output in [0, 4 q_i).  An accumulator enters a step in [0, 2 q_i) (it starts at 0): the sum is below
 // 4 q_i < 2^32, and min(s, s - 2 q_i) brings it back into [0, 2 q_i).  So a 32-bit word per value carries any number of
-// terms; the one canonicalisation is in the epilogue, csub(csub(acc) + d) with d < q_i.
+// terms; the one canonicalisation is in the caller's epilogue, csub(acc) resp. csub(csub(acc) + d) with d < q_i.
 // LDS is the exchange plane alone, used as in k_ct_rescale: the wave-local transposes run inside it while no exchange
 // is in flight, and one workgroup barrier after each keeps the next transform's first exchange off the rows other
 // waves are still reading.  No word of a slab or of the key is used as an address.
-// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
-// ------------------------------------------------------------------------------------------
 // The NTT mod q_i is the same for every j and digit, so with the plain thread index the compiler hoists its per-thread
 // root loads and LDS addresses out of both loops and carries them across the inverse transform (n = 16384, 128 VGPRs per
 // thread: 276 bytes of private memory).  Each transform takes an opaque copy of the index instead (opaque_index,
-// transform.cuh): 112 VGPRs there and nothing spilled.
+// transform.cuh): the caller hands one to evk_row_coeffs, evk_digits takes its own per digit from the plain index.
+// ------------------------------------------------------------------------------------------
+template <int LOGN>
+__device__ __forceinline__ void evk_row_coeffs(uint32_t (&x)[16], const uint32_t *row, uint32_t j, const DevParams &P,
+                                               const DevTables &T, uint32_t *lds, int tj)
+{
+    constexpr int N   = XformGeom<LOGN>::N;
+    const uint32_t qj = P.q[j];
+    load_quads(x, row, tj);
+    quads_to_tile<16>(x, lds, tj);
+    __syncthreads();
+    intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, qj, lds, tj);
+    const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
+#pragma unroll
+    for (int e = 0; e < 16; e++) x[e] = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
+}
+
+// k0: column i of key row 0 (a key row is np columns of 2 N words); rw: the NTT roots of prime i.  A: RelinArgs or
+// GaloisArgs (key layout: half, np).
+template <int LOGN, class Args>
+__device__ __forceinline__ void evk_digits(const uint32_t (&x)[16], uint32_t (&acc0)[16], uint32_t (&acc1)[16],
+                                           const Args &A, const uint32_t *k0, uint32_t j, const uint32_t *rw,
+                                           uint32_t qi, uint32_t *lds, int t)
+{
+    constexpr int N       = XformGeom<LOGN>::N;
+    const uint32_t two_qi = qi << 1;
+    // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
+#pragma unroll 1
+    for (uint32_t dg = 0; dg < 2; dg++)
+    {
+        const int td = opaque_index(t);
+        uint32_t y[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) y[e] = (x[e] >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
+        ntt_tiles<LOGN>(y, rw, qi, lds, td);
+        tile_to_quads<16>(y, lds, td);
+        // key rows 2j + dg of both halves, a quad of words and of Shoup companions at a time
+        const uint32_t *key = k0 + (size_t)(2 * j + dg) * A.np * 2 * N + quad_index(td, 0);
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
+            const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
+            const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
+            const uint4 w1 = *reinterpret_cast<const uint4 *>(key + A.half + (c << 8));
+            const uint4 s1 = *reinterpret_cast<const uint4 *>(key + A.half + N + (c << 8));
+            const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
+            const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+            {
+                const int e       = 4 * c + k;
+                const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], qi);
+                const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], qi);
+                acc0[e]           = min(u0, u0 - two_qi);
+                acc1[e]           = min(u1, u1 - two_qi);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Relinearisation: (d0, d1, d2) of level L -> (out0, out1) of level L with the installed evaluation key,
+//   out0[b][i] = d0[b][i] + sum_{j < L, t < 2} NTT_i(D_{j,t}) . evk0[2j + t][i]  mod q_i   (out1: d1 and evk1),
+// D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients of INTT_j(d2[b][j]) (n^-1 included): the
+// key switch above on the rows of d2, and the two addends in the epilogue.
+// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// ------------------------------------------------------------------------------------------
 template <int LOGN>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin(const DevParams P, const DevTables T,
                                                                     const RelinArgs A)
@@ -450,9 +517,9 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin(const Dev
     uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
     const int t        = threadIdx.x;
     const uint32_t i   = blockIdx.y;
-    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t qi  = P.q[i];
     const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
-    const uint32_t *k0 = A.evk + (size_t)i * 2 * N;   // column i of key row 0; a key row is np columns of 2 N words
+    const uint32_t *k0 = A.key + (size_t)i * 2 * N;
 
     for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
     {
@@ -462,49 +529,9 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin(const Dev
         for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
         for (uint32_t j = 0; j < A.primes; j++)
         {
-            const int tj      = opaque_index(t);
-            const uint32_t qj = P.q[j];
             uint32_t x[16];
-            load_quads(x, A.d2 + rec + (size_t)j * N, tj);
-            quads_to_tile<16>(x, lds, tj);
-            __syncthreads();
-            intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, qj, lds, tj);
-            const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
-#pragma unroll
-            for (int e = 0; e < 16; e++) x[e] = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
-            // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
-#pragma unroll 1
-            for (uint32_t dg = 0; dg < 2; dg++)
-            {
-                const int td = opaque_index(t);
-                uint32_t y[16];
-#pragma unroll
-                for (int e = 0; e < 16; e++) y[e] = (x[e] >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
-                ntt_tiles<LOGN>(y, rw, qi, lds, td);
-                tile_to_quads<16>(y, lds, td);
-                // key rows 2j + dg of both halves, a quad of words and of Shoup companions at a time
-                const uint32_t *key = k0 + (size_t)(2 * j + dg) * A.np * 2 * N + quad_index(td, 0);
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                {
-                    const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
-                    const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
-                    const uint4 w1 = *reinterpret_cast<const uint4 *>(key + A.half + (c << 8));
-                    const uint4 s1 = *reinterpret_cast<const uint4 *>(key + A.half + N + (c << 8));
-                    const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
-                    const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                    {
-                        const int e       = 4 * c + k;
-                        const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], qi);
-                        const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], qi);
-                        acc0[e]           = min(u0, u0 - two_qi);
-                        acc1[e]           = min(u1, u1 - two_qi);
-                    }
-                }
-                __syncthreads();
-            }
+            evk_row_coeffs<LOGN>(x, A.d2 + rec + (size_t)j * N, j, P, T, lds, opaque_index(t));
+            evk_digits<LOGN>(x, acc0, acc1, A, k0, j, rw, qi, lds, t);
         }
         const size_t o = rec + (size_t)i * N;
         uint32_t c[16];
@@ -548,29 +575,6 @@ hipError_t launch_relin_key_rows(const DevParams &P, const uint32_t *in, uint32_
     const size_t words = (rows * P.nprimes) << P.logn;
     if (words == 0) return hipSuccess;
     return launch(k_relin_key_rows, dim3((unsigned)(words / kLcThreads)), dim3(kLcThreads), 0, st, P, in, out, words);
-}
-
-// The diagonal term of a relinearisation key on the [R][np][n] slab the public-key chain wrote:
-//   evk0[2j + t][j] += 2^(15 t) . s_hat^2  mod q_j,  t = 0, 1   (2^15 < q_j: the factor is its own residue).
-// s_hat^2 < q_j < 2^30 lives in a register only; s_hat^2 2^15 + evk0 < 2^46.  grid n / 256.
-__global__ __launch_bounds__(kLcThreads) void k_relin_diag(const DevParams P, uint32_t j,
-                                                        const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ evk0)
-{
-    const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
-    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
-    const uint32_t s  = s_hat[c];
-    const uint64_t s2 = barrett64((uint64_t)s * s, q, cr_hi, cr_lo);
-#pragma unroll
-    for (uint32_t dg = 0; dg < 2; dg++)
-    {
-        uint32_t *p = evk0 + ((((size_t)(2 * j + dg)) * P.nprimes + j) << P.logn) + c;
-        *p          = barrett64((s2 << (kRelinDigitBits * dg)) + *p, q, cr_hi, cr_lo);
-    }
-}
-
-hipError_t launch_relin_diag(const DevParams &P, uint32_t j, const uint32_t *s_hat, uint32_t *evk0, hipStream_t st)
-{
-    return launch(k_relin_diag, dim3(P.n / kLcThreads), dim3(kLcThreads), 0, st, P, j, s_hat, evk0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -618,10 +622,10 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois(const De
     uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
     const int t        = threadIdx.x;
     const uint32_t i   = blockIdx.y;
-    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t qi  = P.q[i];
     const uint32_t g   = A.elt;
     const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
-    const uint32_t *k0 = A.gk + (size_t)i * 2 * N;   // column i of key row 0; a key row is np columns of 2 N words
+    const uint32_t *k0 = A.key + (size_t)i * 2 * N;
 
     for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
     {
@@ -634,56 +638,19 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois(const De
             const int tj      = opaque_index(t);
             const uint32_t qj = P.q[j];
             uint32_t x[16];
-            load_quads(x, A.c1 + rec + (size_t)j * N, tj);
-            quads_to_tile<16>(x, lds, tj);
-            __syncthreads();
-            intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, qj, lds, tj);
-            const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
+            evk_row_coeffs<LOGN>(x, A.c1 + rec + (size_t)j * N, j, P, T, lds, tj);
             // sigma: coefficient k -> position k g mod n, negated when k g mod 2n >= n (k g < 2^29)
 #pragma unroll
             for (int e = 0; e < 16; e++)
             {
-                const uint32_t c = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
                 const uint32_t u = (uint32_t)(tj + (N / 16) * e) * g;
-                lds[u & (N - 1)] = (u & N) && c ? qj - c : c;
+                lds[u & (N - 1)] = (u & N) && x[e] ? qj - x[e] : x[e];
             }
             __syncthreads();
 #pragma unroll
             for (int e = 0; e < 16; e++) x[e] = lds[tj + (N / 16) * e];
             __syncthreads();
-            // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
-#pragma unroll 1
-            for (uint32_t dg = 0; dg < 2; dg++)
-            {
-                const int td = opaque_index(t);
-                uint32_t y[16];
-#pragma unroll
-                for (int e = 0; e < 16; e++) y[e] = (x[e] >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
-                ntt_tiles<LOGN>(y, rw, qi, lds, td);
-                tile_to_quads<16>(y, lds, td);
-                // key rows 2j + dg of both halves, a quad of words and of Shoup companions at a time
-                const uint32_t *key = k0 + (size_t)(2 * j + dg) * A.np * 2 * N + quad_index(td, 0);
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                {
-                    const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
-                    const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
-                    const uint4 w1 = *reinterpret_cast<const uint4 *>(key + A.half + (c << 8));
-                    const uint4 s1 = *reinterpret_cast<const uint4 *>(key + A.half + N + (c << 8));
-                    const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
-                    const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                    {
-                        const int e       = 4 * c + k;
-                        const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], qi);
-                        const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], qi);
-                        acc0[e]           = min(u0, u0 - two_qi);
-                        acc1[e]           = min(u1, u1 - two_qi);
-                    }
-                }
-                __syncthreads();
-            }
+            evk_digits<LOGN>(x, acc0, acc1, A, k0, j, rw, qi, lds, t);
         }
         // sigma(c0) row i: the row as it lies in memory goes into the plane, word k at lds[k]; gathered at src(k)
         const int te   = opaque_index(t);
@@ -720,30 +687,39 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
     });
 }
 
-// The diagonal term of the Galois key of element g on the [R][np][n] slab the public-key chain wrote:
-//   gk0[2j + t][j][k] += 2^(15 t) . s_hat[src_g(k)]  mod q_j,  t = 0, 1:   sigma_g(s) in NTT form, k_relin_diag with the
-// square replaced by the permuted key.  g is odd and below 2n (checked by the host).  grid n / 256.
-template <int LOGN>
-__global__ __launch_bounds__(kLcThreads) void k_galois_diag(const DevParams P, uint32_t j, uint32_t g,
-                                                         const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ gk0)
+// The diagonal term of an evaluation key on the [R][np][n] slab the public-key chain wrote:
+//   key0[2j + t][j][k] += 2^(15 t) . d[k]  mod q_j,  t = 0, 1   (2^15 < q_j: the factor is its own residue),
+// d = s_hat^2 for the relinearisation key (SIGMA false; g unused), d[k] = s_hat[src_g(k)] -- sigma_g(s) in NTT form --
+// for the Galois key of element g (SIGMA true; g is odd and below 2n, checked by the host).
+// d < q_j < 2^30 lives in a register only; d 2^15 + key0 < 2^46.  grid n / 256.
+template <int LOGN, bool SIGMA>
+__global__ __launch_bounds__(kLcThreads) void k_evk_diag(const DevParams P, uint32_t j, uint32_t g,
+                                                      const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ key0)
 {
     const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
     const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
-    const uint64_t s = s_hat[galois_src<LOGN>(c, g)];
+    uint64_t d;
+    if constexpr (SIGMA)
+        d = s_hat[galois_src<LOGN>(c, g)];
+    else
+        d = barrett64((uint64_t)s_hat[c] * s_hat[c], q, cr_hi, cr_lo);
 #pragma unroll
     for (uint32_t dg = 0; dg < 2; dg++)
     {
-        uint32_t *p = gk0 + ((((size_t)(2 * j + dg)) * P.nprimes + j) << LOGN) + c;
-        *p          = barrett64((s << (kRelinDigitBits * dg)) + *p, q, cr_hi, cr_lo);
+        uint32_t *p = key0 + ((((size_t)(2 * j + dg)) * P.nprimes + j) << LOGN) + c;
+        *p          = barrett64((d << (kRelinDigitBits * dg)) + *p, q, cr_hi, cr_lo);
     }
 }
 
-hipError_t launch_galois_diag(const DevParams &P, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *gk0,
-                              hipStream_t st)
+// elt 0: the relinearisation key's diagonal; else the Galois key's of that element
+hipError_t launch_evk_diag(const DevParams &P, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *key0,
+                           hipStream_t st)
 {
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
-        return launch(k_galois_diag<L>, dim3(P.n / kLcThreads), dim3(kLcThreads), 0, st, P, j, elt, s_hat, gk0);
+        const dim3 grid(P.n / kLcThreads), block(kLcThreads);
+        return elt ? launch(k_evk_diag<L, true>, grid, block, 0, st, P, j, elt, s_hat, key0)
+                   : launch(k_evk_diag<L, false>, grid, block, 0, st, P, j, elt, s_hat, key0);
     });
 }
 

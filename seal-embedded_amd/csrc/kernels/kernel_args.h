@@ -182,38 +182,34 @@ struct MulArgs
     uint32_t primes;
 };
 hipError_t launch_ct_mul(const DevParams &, const MulArgs &, hipStream_t);
-// Relinearisation (ct_ops.hip: k_ct_relin): level-`primes` (d0, d1, d2) -> (out0, out1) of the same level with the
-// installed evaluation key.  evk is the device copy Context::set_relin_key builds: [2][R][np][2][n], R = 2 np rows of
-// the CONTEXT's np columns, each column a row of n key words followed by the row of their Shoup companions
-// floor(w 2^32 / q_i); evk1 starts `half` words behind evk0.
-//   out0[b][i] = d0[b][i] + sum_{j < primes, t < 2} NTT_i(D_{j,t}) . evk0[2j + t][i]   (out1: d1, evk1)   mod q_i,
+// The key switch of ct_ops.hip, shared by k_ct_relin and k_ct_galois.  `key` is one device evaluation-key block, built
+// by Context::build_evk from the host's two halves: [2][R][np][2][n], R = 2 np rows of the CONTEXT's np columns, each
+// column a row of n key words followed by the row of their Shoup companions floor(w 2^32 / q_i); half 1 starts `half`
+// words behind half 0.  Both argument blocks name the fields the shared device code reads alike: key, half, np, primes,
+// B.
+// Relinearisation (k_ct_relin): level-`primes` (d0, d1, d2) -> (out0, out1) of the same level.
+//   out0[b][i] = d0[b][i] + sum_{j < primes, t < 2} NTT_i(D_{j,t}) . key0[2j + t][i]   (out1: d1, key1)   mod q_i,
 // D_{j,t} = the t-th 15-bit digit of the canonical coefficients of INTT_j(d2[b][j]).
 struct RelinArgs
 {
     const uint32_t *d0, *d1, *d2;   // [B][primes][n]
     uint32_t *out0, *out1;          // [B][primes][n]
-    const uint32_t *evk;
+    const uint32_t *key;
     size_t half;                    // words of one key half: R np 2 n
     size_t B;
     uint32_t np;                    // columns of a key row (the context's primes)
     uint32_t primes;                // 1 .. np
 };
 hipError_t launch_ct_relin(const DevParams &, const DevTables &, const RelinArgs &, hipStream_t);
-// Relinearisation-key plumbing (ct_ops.hip).  relin_key_rows: `rows` rows [np][n] of key words (rows a multiple of np)
-// -> [rows][2][n] (words, Shoup companions).  relin_diag: evk0[2j + t][j] += 2^(15 t) . s_hat^2 mod q_j for t = 0, 1 on
-// an [R][np][n] slab, s_hat = the canonical NTT(s) mod q_j, [n].
-hipError_t launch_relin_key_rows(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, hipStream_t);
-hipError_t launch_relin_diag(const DevParams &, uint32_t j, const uint32_t *s_hat, uint32_t *evk0, hipStream_t);
-// Slot rotation / conjugation (ct_ops.hip: k_ct_galois): the automorphism sigma : x -> x^elt on both slabs of a
-// level-`primes` record and the key switch of sigma(c1) with the Galois key of `elt` -- k_ct_relin on
-// (sigma(c0), 0, sigma(c1)).  gk is one element's device block in the layout of RelinArgs::evk.
-//   out0[b][i] = sigma(c0)[b][i] + sum_{j < primes, t < 2} NTT_i(D_{j,t}) . gk0[2j + t][i]   (out1: no addend, gk1),
+// Slot rotation / conjugation (k_ct_galois): the automorphism sigma : x -> x^elt on both slabs of a level-`primes`
+// record and the key switch of sigma(c1) with the Galois key of `elt` -- k_ct_relin on (sigma(c0), 0, sigma(c1)).
+//   out0[b][i] = sigma(c0)[b][i] + sum_{j < primes, t < 2} NTT_i(D_{j,t}) . key0[2j + t][i]   (out1: no addend, key1),
 // D_{j,t} = the t-th 15-bit digit of the canonical coefficients of sigma(INTT_j(c1[b][j])).
 struct GaloisArgs
 {
     const uint32_t *c0, *c1;        // [B][primes][n]
     uint32_t *out0, *out1;          // [B][primes][n]
-    const uint32_t *gk;
+    const uint32_t *key;
     size_t half;                    // words of one key half: R np 2 n
     size_t B;
     uint32_t np;                    // columns of a key row (the context's primes)
@@ -221,10 +217,13 @@ struct GaloisArgs
     uint32_t elt;                   // odd, below 2n (checked by the host: the kernel forms LDS addresses from it)
 };
 hipError_t launch_ct_galois(const DevParams &, const DevTables &, const GaloisArgs &, hipStream_t);
-// galois_diag: gk0[2j + t][j][k] += 2^(15 t) . s_hat[src_elt(k)] mod q_j for t = 0, 1 on an [R][np][n] slab (the
-// diagonal of a Galois key: sigma_elt(s) in NTT form instead of relin_diag's square).
-hipError_t launch_galois_diag(const DevParams &, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *gk0,
-                              hipStream_t);
+// Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words (rows a multiple of np) -> [rows][2][n]
+// (words, Shoup companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
+// slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =
+// s_hat[src_elt(k)], sigma_elt(s) in NTT form, else (the Galois key of elt).
+hipError_t launch_relin_key_rows(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, hipStream_t);
+hipError_t launch_evk_diag(const DevParams &, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *key0,
+                           hipStream_t);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

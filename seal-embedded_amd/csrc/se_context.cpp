@@ -31,6 +31,40 @@ int hip_fail(hipError_t e, const char *what)
     return kErrHip;
 }
 
+// ---- checks the key setters and the ct_* entries share --------------------------------------------------------------
+// Two [rows][np][n] slabs of residues, column i of a row modulo q_i: the first row of either that holds a word >= its
+// prime, or `rows` when every word is reduced.
+static size_t first_unreduced_row(const HostParams &hp, const uint32_t *s0, const uint32_t *s1, size_t rows)
+{
+    const size_t n = hp.n, np = hp.nprimes;
+    for (size_t r = 0; r < rows; r++)
+        for (size_t i = 0; i < np; i++)
+        {
+            const uint32_t q   = hp.q[i];
+            const uint32_t *r0 = s0 + (r * np + i) * n, *r1 = s1 + (r * np + i) * n;
+            uint32_t bad       = 0;
+            for (size_t c = 0; c < n; c++) bad |= (uint32_t)(r0[c] >= q) | (uint32_t)(r1[c] >= q);
+            if (bad) return r;
+        }
+    return rows;
+}
+
+// 2-bit packed secret keys: the first byte with both bits of some field set (code 3), or `bytes` when there is none.
+static size_t first_code3(const uint8_t *packed, size_t bytes)
+{
+    size_t i = 0;
+    while (i < bytes && !(packed[i] & (packed[i] >> 1) & 0x55u)) i++;
+    return i;
+}
+
+// every pointer 16-byte aligned (NULL is): the quad loads and stores of the ct_* kernels
+static bool aligned16(std::initializer_list<const void *> ptrs)
+{
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t)p;
+    return !(bits & 15);
+}
+
 Context::~Context()
 {
     // nothing may still use the scratch when the members wipe and free it (the auxiliary streams are non-blocking)
@@ -335,13 +369,11 @@ int Context::set_public_key(const uint32_t *pk0, const uint32_t *pk1)
 {
     const size_t n = hp.n, np = hp.nprimes;
     SEAMD_HIP(hipSetDevice(device));
-    for (size_t j = 0; j < np; j++)
-        for (size_t i = 0; i < n; i++)
-            if (pk0[j * n + i] >= hp.q[j] || pk1[j * n + i] >= hp.q[j])
-            {
-                set_last_error("public key coefficient not reduced modulo its prime");
-                return kErrInvalid;
-            }
+    if (first_unreduced_row(hp, pk0, pk1, 1) != 1)
+    {
+        set_last_error("public key coefficient not reduced modulo its prime");
+        return kErrInvalid;
+    }
     std::lock_guard<std::mutex> lk(mu);
     DevBuf<uint32_t> d_tmp;
     SEAMD_HIP(d_tmp.grow(2 * np * n));
@@ -371,13 +403,11 @@ int Context::set_secret_keyring(size_t K, const uint8_t *sk_packed)
         set_last_error("set_secret_keyring: K must be between 1 and 2^32 - 1");
         return kErrInvalid;
     }
-    // code 3 anywhere: a byte with both bits of some 2-bit field set
-    for (size_t i = 0; i < bytes; i++)
-        if (sk_packed[i] & (sk_packed[i] >> 1) & 0x55u)
-        {
-            set_last_error("secret key ring: key " + std::to_string(i / (n / 4)) + " holds an invalid 2-bit code (3)");
-            return kErrInvalid;
-        }
+    if (const size_t i = first_code3(sk_packed, bytes); i != bytes)
+    {
+        set_last_error("secret key ring: key " + std::to_string(i / (n / 4)) + " holds an invalid 2-bit code (3)");
+        return kErrInvalid;
+    }
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
     SEAMD_HIP(hipDeviceSynchronize());   // calls in flight may still read the old ring
@@ -404,20 +434,11 @@ int Context::set_public_keyring(size_t K, const uint32_t *pk0, const uint32_t *p
         set_last_error("set_public_keyring: K must be between 1 and 2^32 - 1");
         return kErrInvalid;
     }
-    for (size_t k = 0; k < K; k++)
-        for (size_t j = 0; j < np; j++)
-        {
-            const uint32_t q = hp.q[j];
-            const uint32_t *r0 = pk0 + (k * np + j) * n, *r1 = pk1 + (k * np + j) * n;
-            uint32_t bad = 0;
-            for (size_t i = 0; i < n; i++) bad |= (uint32_t)(r0[i] >= q) | (uint32_t)(r1[i] >= q);
-            if (bad)
-            {
-                set_last_error("public key ring: key " + std::to_string(k) +
-                               " holds a coefficient not reduced modulo its prime");
-                return kErrInvalid;
-            }
-        }
+    if (const size_t k = first_unreduced_row(hp, pk0, pk1, K); k != K)
+    {
+        set_last_error("public key ring: key " + std::to_string(k) + " holds a coefficient not reduced modulo its prime");
+        return kErrInvalid;
+    }
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
     SEAMD_HIP(hipDeviceSynchronize());   // calls in flight may still read the old ring
@@ -507,29 +528,34 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
         return kErrInvalid;
     }
     std::lock_guard<std::mutex> lk(mu);
-    return gen_keys_chain(K, sk_in, sk_seeds, pk_seeds, ep_seeds, sk_out, pk0_out, pk1_out, false);
+    return gen_keys_chain({KeyChain::kPairs}, K, sk_in, sk_seeds, pk_seeds, ep_seeds, sk_out, pk0_out, pk1_out);
 }
 
 // Relinearisation key: the chain above with K = R = 2 np rows under ONE secret key, pk_seeds = a_seeds and ep_seeds =
 // e_seeds -- row r is public key r, (evk0[r], evk1[r]) = (-a_r s_hat + NTT(e_r), a_r) -- plus the diagonal term
-// 2^(15 t) s_hat^2 on column j of the rows r = 2j + t (kernels/ct_ops.hip, k_relin_diag).
+// 2^(15 t) s_hat^2 on column j of the rows r = 2j + t (kernels/ct_ops.hip, k_evk_diag).
 int Context::gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *evk0_out,
                            uint32_t *evk1_out)
 {
-    for (size_t i = 0; i < hp.n / 4; i++)
-        if (sk_packed[i] & (sk_packed[i] >> 1) & 0x55u)
-        {
-            set_last_error("secret key holds an invalid 2-bit code (3)");
-            return kErrInvalid;
-        }
+    if (!evk_secret_ok(sk_packed)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    return gen_keys_chain(2 * hp.nprimes, sk_packed, nullptr, a_seeds, e_seeds, nullptr, evk0_out, evk1_out, true);
+    return gen_keys_chain({KeyChain::kRelin}, 2 * hp.nprimes, sk_packed, nullptr, a_seeds, e_seeds, nullptr, evk0_out,
+                          evk1_out);
 }
 
-int Context::gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
-                            const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin,
-                            uint32_t galois_elt)
+// the secret key of gen_relin_key / gen_galois_keys: n/4 bytes without code 3
+bool Context::evk_secret_ok(const uint8_t *sk_packed) const
 {
+    if (first_code3(sk_packed, hp.n / 4) == hp.n / 4) return true;
+    set_last_error("secret key holds an invalid 2-bit code (3)");
+    return false;
+}
+
+int Context::gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds,
+                            const uint8_t *pk_seeds, const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out,
+                            uint32_t *pk1_out)
+{
+    const bool relin = chain.kind != KeyChain::kPairs;   // evaluation-key rows: one secret key, a diagonal term
     SEAMD_HIP(hipSetDevice(device));
     int rc = ensure_scratch(K);
     if (rc) return rc;
@@ -538,7 +564,7 @@ int Context::gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
     DevBuf<uint8_t> seeds{Secret::yes}, keys{Secret::yes};
     DevBuf<int8_t> codes{Secret::yes}, ep{Secret::yes};
     DevBuf<uint32_t> pk0, pk1, tmp{Secret::yes};   // tmp: NTT(ep), secret as well
-    DevBuf<uint32_t> s_hat{Secret::yes};           // relin: NTT(s) mod the current prime, [K][n] (every row the same)
+    DevBuf<uint32_t> s_hat{Secret::yes};           // evaluation key: NTT(s) mod the current prime, [K][n] (every row the same)
     const size_t nkeys = relin ? 1 : K;            // secret keys behind the K rows
     if (relin) SEAMD_HIP(s_hat.grow((size_t)K * n));
     SEAMD_HIP(seeds.grow(K * 192));
@@ -594,10 +620,7 @@ int Context::gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
         sa.c0 = pk0 + (size_t)j * n;
         sa.j  = (int)j;
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
-        if (relin && galois_elt)
-            SEAMD_HIP(launch_galois_diag(dp, j, galois_elt, s_hat, pk0, nullptr));
-        else if (relin)
-            SEAMD_HIP(launch_relin_diag(dp, j, s_hat, pk0, nullptr));
+        if (relin) SEAMD_HIP(launch_evk_diag(dp, j, chain.kind == KeyChain::kGalois ? chain.elt : 0, s_hat, pk0, nullptr));
     }
     SEAMD_HIP(hipDeviceSynchronize());
     if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys, K * (n / 4), hipMemcpyDeviceToHost));
@@ -1313,8 +1336,7 @@ int Context::ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, 
 {
     if (!d_in0 || !d_out0 || !d_in1 != !d_out1) return kErrInvalid;
     if (primes < 2 || primes > hp.nprimes || B > 0x7fffffffu) return kErrInvalid;
-    for (const void *p : {(const void *)d_in0, (const void *)d_in1, (const void *)d_out0, (const void *)d_out1})
-        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (!aligned16({d_in0, d_in1, d_out0, d_out1})) return kErrInvalid;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     RescaleArgs ra{};
@@ -1337,9 +1359,7 @@ int Context::ct_mul_plain(const uint32_t *d_in0, const uint32_t *d_in1, size_t B
     if (primes < 1 || primes > hp.nprimes || pt_primes < primes || pt_primes >= k32) return kErrInvalid;
     if (B >= k32 || P >= k32) return kErrInvalid;
     if (!d_pt_idx && P != 1 && P != B) return kErrInvalid;
-    for (const void *p : {(const void *)d_in0, (const void *)d_in1, (const void *)d_out0, (const void *)d_out1,
-                          (const void *)d_pt})
-        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (!aligned16({d_in0, d_in1, d_out0, d_out1, d_pt})) return kErrInvalid;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     MulPlainArgs ma{};
@@ -1367,9 +1387,7 @@ int Context::ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const
     if (!d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_out0 || !d_out1 || !d_out2 || !d_ia != !d_ib) return kErrInvalid;
     if (primes < 1 || primes > hp.nprimes || P >= k32 || Ba >= k32 || Bb >= k32) return kErrInvalid;
     if (!d_ia && (P != Ba || P != Bb)) return kErrInvalid;
-    for (const void *p : {(const void *)d_a0, (const void *)d_a1, (const void *)d_b0, (const void *)d_b1,
-                          (const void *)d_out0, (const void *)d_out1, (const void *)d_out2})
-        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (!aligned16({d_a0, d_a1, d_b0, d_b1, d_out0, d_out1, d_out2})) return kErrInvalid;
     if (P == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     MulArgs ma{};
@@ -1391,37 +1409,53 @@ int Context::ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const
     return 0;
 }
 
-// The key is public material: validated like a public key (a word >= q_i is refused), then every column gets its Shoup
-// companions on the device (launch_relin_key_rows).  Replaced only after every call already enqueued has finished.
+// One device evaluation-key block [2][R][np][2][n] (kernels/kernel_args.h) from the host's halves k0, k1 [R][np][n]:
+// staged through `stage`, every column given its Shoup companions on the device (launch_relin_key_rows), and
+// synchronised -- `stage` may be reused, and every call enqueued before has finished.  The caller holds `mu`, has the
+// device current and has checked the words.
+int Context::build_evk(const uint32_t *k0, const uint32_t *k1, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block)
+{
+    const size_t R = 2 * hp.nprimes, slab = R * hp.nprimes * hp.n;
+    SEAMD_HIP(stage.grow(2 * slab));
+    SEAMD_HIP(block.grow(4 * slab));
+    SEAMD_HIP(hipMemcpy(stage, k0, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SEAMD_HIP(hipMemcpy(stage + slab, k1, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SEAMD_HIP(launch_relin_key_rows(dp, stage, block, 2 * R, nullptr));
+    SEAMD_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
+// What ct_relin and ct_galois check and fill alike: every slab pointer present and 16-byte aligned, the level and the
+// batch in range; then the fields of the argument block that describe the batch and the key layout.
+template <class Args>
+bool Context::evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes) const
+{
+    for (const void *p : slabs)
+        if (!p) return false;
+    if (primes < 1 || primes > hp.nprimes || B >= ((size_t)1 << 32) || !aligned16(slabs)) return false;
+    a.half   = (size_t)2 * hp.nprimes * hp.nprimes * 2 * hp.n;
+    a.B      = B;
+    a.np     = (uint32_t)hp.nprimes;
+    a.primes = (uint32_t)primes;
+    return true;
+}
+
+// Evaluation keys are public material: validated like a public key (a word >= q_i is refused), then built beside the
+// installed key and swapped in once every call already enqueued has finished (build_evk ends in a synchronisation).
+// Anything refused, or a HIP call that fails, leaves the previous key installed and usable.
 int Context::set_relin_key(const uint32_t *evk0, const uint32_t *evk1)
 {
-    const size_t n = hp.n, np = hp.nprimes, R = 2 * np, slab = R * np * n;
-    for (size_t r = 0; r < R; r++)
-        for (size_t i = 0; i < np; i++)
-        {
-            const uint32_t q   = hp.q[i];
-            const uint32_t *r0 = evk0 + (r * np + i) * n, *r1 = evk1 + (r * np + i) * n;
-            uint32_t bad       = 0;
-            for (size_t c = 0; c < n; c++) bad |= (uint32_t)(r0[c] >= q) | (uint32_t)(r1[c] >= q);
-            if (bad)
-            {
-                set_last_error("relinearisation key: row " + std::to_string(r) +
-                               " holds a word not reduced modulo its prime");
-                return kErrInvalid;
-            }
-        }
+    const size_t R = 2 * hp.nprimes;
+    if (const size_t r = first_unreduced_row(hp, evk0, evk1, R); r != R)
+    {
+        set_last_error("relinearisation key: row " + std::to_string(r) + " holds a word not reduced modulo its prime");
+        return kErrInvalid;
+    }
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
-    SEAMD_HIP(hipDeviceSynchronize());   // calls in flight may still read the old key
-    have_relin = false;
-    DevBuf<uint32_t> d_tmp;
-    SEAMD_HIP(d_tmp.grow(2 * slab));
-    SEAMD_HIP(d_evk.grow(4 * slab));
-    SEAMD_HIP(hipMemcpy(d_tmp, evk0, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
-    SEAMD_HIP(hipMemcpy(d_tmp + slab, evk1, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
-    SEAMD_HIP(launch_relin_key_rows(dp, d_tmp, d_evk, 2 * R, nullptr));
-    SEAMD_HIP(hipDeviceSynchronize());
-    have_relin = true;
+    DevBuf<uint32_t> stage, block;
+    if (int rc = build_evk(evk0, evk1, stage, block)) return rc;
+    d_evk = std::move(block);
     return 0;
 }
 
@@ -1430,35 +1464,27 @@ int Context::ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t
                       uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
-    if (!have_relin)
+    if (!d_evk)
     {
         set_last_error("relinearisation needs an evaluation key (se_amd_set_relin_key)");
         return kErrNoKey;
     }
-    if (!d_d0 || !d_d1 || !d_d2 || !d_out0 || !d_out1) return kErrInvalid;
-    if (primes < 1 || primes > hp.nprimes || B >= ((size_t)1 << 32)) return kErrInvalid;
-    for (const void *p : {(const void *)d_d0, (const void *)d_d1, (const void *)d_d2, (const void *)d_out0,
-                          (const void *)d_out1})
-        if ((uintptr_t)p & 15) return kErrInvalid;
+    RelinArgs ra{};
+    if (!evk_call_args(ra, {d_d0, d_d1, d_d2, d_out0, d_out1}, B, primes)) return kErrInvalid;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    RelinArgs ra{};
-    ra.d0     = d_d0;
-    ra.d1     = d_d1;
-    ra.d2     = d_d2;
-    ra.out0   = d_out0;
-    ra.out1   = d_out1;
-    ra.evk    = d_evk;
-    ra.half   = (size_t)2 * hp.nprimes * hp.nprimes * 2 * hp.n;
-    ra.B      = B;
-    ra.np     = (uint32_t)hp.nprimes;
-    ra.primes = (uint32_t)primes;
+    ra.d0   = d_d0;
+    ra.d1   = d_d1;
+    ra.d2   = d_d2;
+    ra.out0 = d_out0;
+    ra.out1 = d_out1;
+    ra.key  = d_evk;
     SEAMD_HIP(launch_ct_relin(dp, dt, ra, st));
     return 0;
 }
 
 // Galois keys: per element the chain of gen_relin_key on that element's block of seeds, with the diagonal term
-// 2^(15 t) sigma(s_hat) instead of 2^(15 t) s_hat^2 (kernels/ct_ops.hip, k_galois_diag).
+// 2^(15 t) sigma(s_hat) instead of 2^(15 t) s_hat^2 (kernels/ct_ops.hip, k_evk_diag).
 int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, size_t G, const uint8_t *a_seeds,
                              const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out)
 {
@@ -1473,26 +1499,19 @@ int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, siz
             set_last_error("Galois element " + std::to_string(elts[g]) + " is not odd and below 2n");
             return kErrInvalid;
         }
-    for (size_t i = 0; i < hp.n / 4; i++)
-        if (sk_packed[i] & (sk_packed[i] >> 1) & 0x55u)
-        {
-            set_last_error("secret key holds an invalid 2-bit code (3)");
-            return kErrInvalid;
-        }
+    if (!evk_secret_ok(sk_packed)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
     const size_t R = 2 * hp.nprimes, slab = R * hp.nprimes * hp.n;
     for (size_t g = 0; g < G; g++)
     {
-        const int rc = gen_keys_chain(R, sk_packed, nullptr, a_seeds + g * R * 64, e_seeds + g * R * 64, nullptr,
-                                      gk0_out + g * slab, gk1_out + g * slab, true, elts[g]);
+        const int rc = gen_keys_chain({KeyChain::kGalois, elts[g]}, R, sk_packed, nullptr, a_seeds + g * R * 64,
+                                      e_seeds + g * R * 64, nullptr, gk0_out + g * slab, gk1_out + g * slab);
         if (rc) return rc;
     }
     return 0;
 }
 
-// Public material, validated like the relinearisation key; the whole installed set is replaced, and only after every
-// call already enqueued has finished.  Anything refused leaves the previous set in place: the new blocks are built
-// beside it and swapped in at the end.
+// The whole installed set is replaced, by the rule of set_relin_key: one block per element, swapped in together.
 int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1)
 {
     const size_t n = hp.n, np = hp.nprimes, R = 2 * np, slab = R * np * n;
@@ -1511,34 +1530,18 @@ int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0
             return kErrInvalid;
         }
     }
-    for (size_t g = 0; g < G; g++)
-        for (size_t r = 0; r < R; r++)
-            for (size_t i = 0; i < np; i++)
-            {
-                const uint32_t q   = hp.q[i];
-                const uint32_t *r0 = gk0 + ((g * R + r) * np + i) * n, *r1 = gk1 + ((g * R + r) * np + i) * n;
-                uint32_t bad       = 0;
-                for (size_t c = 0; c < n; c++) bad |= (uint32_t)(r0[c] >= q) | (uint32_t)(r1[c] >= q);
-                if (bad)
-                {
-                    set_last_error("Galois key of element " + std::to_string(elts[g]) + ": row " + std::to_string(r) +
-                                   " holds a word not reduced modulo its prime");
-                    return kErrInvalid;
-                }
-            }
+    if (const size_t r = first_unreduced_row(hp, gk0, gk1, G * R); r != G * R)
+    {
+        set_last_error("Galois key of element " + std::to_string(elts[r / R]) + ": row " + std::to_string(r % R) +
+                       " holds a word not reduced modulo its prime");
+        return kErrInvalid;
+    }
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
-    DevBuf<uint32_t> d_tmp;
+    DevBuf<uint32_t> stage;
     std::vector<DevBuf<uint32_t>> blocks(G);
-    SEAMD_HIP(d_tmp.grow(2 * slab));
     for (size_t g = 0; g < G; g++)
-    {
-        SEAMD_HIP(blocks[g].grow(4 * slab));
-        SEAMD_HIP(hipMemcpy(d_tmp, gk0 + g * slab, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
-        SEAMD_HIP(hipMemcpy(d_tmp + slab, gk1 + g * slab, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
-        SEAMD_HIP(launch_relin_key_rows(dp, d_tmp, blocks[g], 2 * R, nullptr));
-        SEAMD_HIP(hipDeviceSynchronize());   // d_tmp is reused; after the last one: calls in flight have left the old set
-    }
+        if (int rc = build_evk(gk0 + g * slab, gk1 + g * slab, stage, blocks[g])) return rc;
     galois_elts.assign(elts, elts + G);
     d_gk = std::move(blocks);
     return 0;
@@ -1548,11 +1551,9 @@ int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0
 int Context::ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, uint32_t elt,
                        uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
 {
-    if (!d_c0 || !d_c1 || !d_out0 || !d_out1) return kErrInvalid;
-    if (primes < 1 || primes > hp.nprimes || B >= ((size_t)1 << 32)) return kErrInvalid;
+    GaloisArgs ga{};
+    if (!evk_call_args(ga, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
     if (!(elt & 1) || elt >= 2 * hp.n) return kErrInvalid;
-    for (const void *p : {(const void *)d_c0, (const void *)d_c1, (const void *)d_out0, (const void *)d_out1})
-        if ((uintptr_t)p & 15) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
     size_t g = 0;
     while (g < galois_elts.size() && galois_elts[g] != elt) g++;
@@ -1563,17 +1564,12 @@ int Context::ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, siz
     }
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    GaloisArgs ga{};
-    ga.c0     = d_c0;
-    ga.c1     = d_c1;
-    ga.out0   = d_out0;
-    ga.out1   = d_out1;
-    ga.gk     = d_gk[g];
-    ga.half   = (size_t)2 * hp.nprimes * hp.nprimes * 2 * hp.n;
-    ga.B      = B;
-    ga.np     = (uint32_t)hp.nprimes;
-    ga.primes = (uint32_t)primes;
-    ga.elt    = elt;
+    ga.c0   = d_c0;
+    ga.c1   = d_c1;
+    ga.out0 = d_out0;
+    ga.out1 = d_out1;
+    ga.key  = d_gk[g];
+    ga.elt  = elt;
     SEAMD_HIP(launch_ct_galois(dp, dt, ga, st));
     return 0;
 }
@@ -1611,8 +1607,7 @@ int Context::ct_lincomb(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, 
     if (!d_in0 || !d_out0 || !d_in1 != !d_out1 || !d_row_ptr != !d_idx) return kErrInvalid;
     if (B >= k32 || G >= k32 || nnz >= k32) return kErrInvalid;
     if (!d_row_ptr && nnz != G * B) return kErrInvalid;
-    for (const void *p : {(const void *)d_in0, (const void *)d_in1, (const void *)d_out0, (const void *)d_out1})
-        if ((uintptr_t)p & 15) return kErrInvalid;
+    if (!aligned16({d_in0, d_in1, d_out0, d_out1})) return kErrInvalid;
     if (G == 0) return 0;
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));

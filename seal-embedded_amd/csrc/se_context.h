@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -53,12 +54,10 @@ struct Context
     DevBuf<uint32_t> d_ring_sk{Secret::yes};   // [K][np][n][2] NTT(s) pairs
     DevBuf<uint32_t> d_ring_pk0, d_ring_pk1;   // [K][np][n][2]
     size_t ring_sk = 0, ring_pk = 0;           // keys in each ring (0 = no ring)
-    // relinearisation key (se_amd_set_relin_key; public material): [2][R][np][2][n], R = 2 np rows, every column a row
-    // of key words followed by the row of their Shoup companions (kernels/kernel_args.h, RelinArgs)
+    // evaluation keys (public material), each one device block [2][R][np][2][n] made by build_evk (layout:
+    // kernels/kernel_args.h): the relinearisation key (se_amd_set_relin_key; empty = none installed) and the Galois keys
+    // (se_amd_set_galois_keys): the installed elements and one block per element
     DevBuf<uint32_t> d_evk;
-    bool have_relin = false;
-    // Galois keys (se_amd_set_galois_keys; public material): the installed elements and one device block per element
-    // in the layout of d_evk
     std::vector<uint32_t> galois_elts;
     std::vector<DevBuf<uint32_t>> d_gk;
     DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
@@ -251,12 +250,22 @@ struct Context
     void collect_events();
 
 private:
-    // the launch chain of gen_keys_batch; relin: ONE secret key (sk_in, n/4 bytes) shared by all K = 2 np rows and the
-    // diagonal term of a relinearisation key added to pk0 -- or, with galois_elt != 0, that of the Galois key of the
-    // element.  The caller holds `mu`.
-    int gen_keys_chain(size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
-                       const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out, bool relin,
-                       uint32_t galois_elt = 0);
+    // What the K rows of a gen_keys_chain are: independent key pairs (gen_keys_batch), or the K = 2 np rows of an
+    // evaluation key under ONE secret key (sk_in, n/4 bytes) with its diagonal term added to pk0 -- that of the
+    // relinearisation key, or that of the Galois key of `elt`.
+    struct KeyChain
+    {
+        enum Kind { kPairs, kRelin, kGalois } kind;
+        uint32_t elt = 0;   // kGalois only
+    };
+    // the launch chain of gen_keys_batch.  The caller holds `mu`.
+    int gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
+                       const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out);
+    // shared by the two evaluation keys and their two calls (se_context.cpp)
+    bool evk_secret_ok(const uint8_t *sk_packed) const;
+    int build_evk(const uint32_t *k0, const uint32_t *k1, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block);
+    template <class Args>
+    bool evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes) const;
     int decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
                            size_t primes, double scale, const uint32_t *d_key_idx, bool keyed, int64_t *d_pte,
                            float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);

@@ -6,6 +6,9 @@ env, dev_t, ...`), never from another test module; a helper that a second module
 - SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY: the C ABI's error codes; SEED_A, SEED_B, SEED_PK, SEED_EP: the golden seeds.
 - the receiving side: records, encrypt_sym, ntt_secret, crt_centred, decode_expect, expectation (oracle + Python
   ints), run_decrypt (decrypt_full / decrypt_level and their keyed twins over sentinel-filled outputs), assert_matches.
+- ciphertext operations (tests/test_gpu_ct_*.py): SENTINEL, sentinel_out, take (outputs with guard words behind them);
+  DIGIT_BITS, DIGIT_MASK; centred, negacyclic, rand_slab, unit_values; the definitions the kernels are tested against,
+  rescale_expect, digits_of and relin_expect; keyed_cases, the module-scoped fixture of the end-to-end tests.
 - build_example, build_caller: plain-gcc programs of examples/ and tests/c/ linked against the product library.
 - check_host_tables: every setup-time table against the oracle and the golden digests (CPU suite and GPU box).
 """
@@ -24,6 +27,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SE_ERR_INVALD_ARGUMENT = -22
 SE_ERR_NO_KEY = -1002
+
+SENTINEL = 0x5A5A5A5A                 # fill of an output no call may have written
+DIGIT_BITS = 15                       # SE_AMD_RELIN_DIGIT_BITS
+DIGIT_MASK = (1 << DIGIT_BITS) - 1
 
 SEED_A = hashlib.shake_256(b"golden-share").digest(64)
 SEED_B = hashlib.shake_256(b"golden-secret").digest(64)
@@ -162,6 +169,113 @@ def encrypt_sym(env, ctx, vals, first=0):
     ctx.encrypt_sym(dev_t(env, vals), dev_t(env, ss), dev_t(env, sd), c0, c1, pte=pte, status=st)
     torch.cuda.synchronize()
     return c0, c1, pte, st
+
+
+# ---- ciphertext operations: guarded outputs, inputs and the definitions of rescale and key switch -------------------
+def sentinel_out(env, words, extra):
+    return env["torch"].full((words + extra,), SENTINEL, dtype=env["torch"].int32, device=env["dev"])
+
+
+def take(t, words, shape, what):
+    """Host copy of the first `words` words of a sentinel-backed output; the words behind them must be untouched."""
+    h = host_u32(t)
+    assert (h[words:] == SENTINEL).all(), f"{what}: words behind the result are written"
+    return h[:words].reshape(shape)
+
+
+def rand_slab(rng, q, count, n, primes=None):
+    primes = len(q) if primes is None else primes
+    return np.stack([rng.integers(0, q[j], (count, n), dtype=np.uint32) for j in range(primes)], axis=1)
+
+
+def unit_values(B, n, seed):
+    """float32 [B][n/2], uniform in [-1, 1]."""
+    return np.random.default_rng(seed).uniform(-1.0, 1.0, (B, n // 2)).astype(np.float32)
+
+
+def centred(x, q):
+    """canonical residues -> int64 representatives in (-q/2, q/2]  (q odd)."""
+    x = x.astype(np.int64)
+    return np.where(x > q // 2, x - q, x)
+
+
+def negacyclic(a, s):
+    """a * s mod (x^n + 1) in int64 (the callers keep every sum below 2^62)."""
+    n = a.shape[0]
+    full = np.convolve(a, s)
+    res = full[:n].copy()
+    res[:n - 1] -= full[n:]
+    return res
+
+
+def rescale_expect(o, slab):
+    """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: out[j] = (in[j] - NTT_j(delta mod q_j)) . q_last^-1 mod q_j with
+    delta the centred INTT of the last row, from o.intt / o.ntt and uint64 arithmetic."""
+    B, L, n = slab.shape
+    q_last = o.q[L - 1]
+    out = np.zeros((B, L - 1, n), dtype=np.uint32)
+    for b in range(B):
+        delta = centred(o.intt(slab[b, L - 1], L - 1), q_last)
+        for j in range(L - 1):
+            q = o.q[j]
+            inv = pow(q_last, -1, q)
+            t = o.ntt((delta % q).astype(np.uint32), j).astype(np.uint64)
+            diff = (slab[b, j].astype(np.uint64) + np.uint64(q) - t) % np.uint64(q)
+            out[b, j] = ((diff * np.uint64(inv)) % np.uint64(q)).astype(np.uint32)
+    return out
+
+
+def digits_of(o, rec, L):
+    """Record [L][n] -> the 2 L digit polynomials D_{j,t} (uint32, natural order), row r = 2j + t."""
+    out = []
+    for j in range(L):
+        c = o.intt(rec[j], j)
+        out += [c & np.uint32(DIGIT_MASK), c >> np.uint32(DIGIT_BITS)]
+    return out
+
+
+def relin_expect(o, d0, d1, d2, evk0, evk1):
+    """The definition of the key switch, which relinearisation and rotation are both tested against:
+    out_k[b][i] = d_k[b][i] + sum_r NTT_i(D_r) . evk_k[r][i] mod q_i, from o.intt / o.ntt and uint64 arithmetic (a
+    product is below 2^60, reduced before it is added)."""
+    B, L, n = d0.shape
+    out0, out1 = np.zeros_like(d0), np.zeros_like(d1)
+    for b in range(B):
+        D = digits_of(o, d2[b], L)
+        for i in range(L):
+            q = np.uint64(o.q[i])
+            acc0, acc1 = d0[b, i].astype(np.uint64), d1[b, i].astype(np.uint64)
+            for r, dig in enumerate(D):
+                f = o.ntt(dig, i).astype(np.uint64)
+                acc0 = (acc0 + (f * evk0[r, i].astype(np.uint64)) % q) % q
+                acc1 = (acc1 + (f * evk1[r, i].astype(np.uint64)) % q) % q
+            out0[b, i], out1[b, i] = acc0, acc1
+    return out0, out1
+
+
+@pytest.fixture(scope="module")
+def keyed_cases(env, request):
+    """keyed_cases(shape) -> the importing module's end-to-end case of that shape, computed once: a context of the shape
+    ("ctx") with the secret key V.secret_key(n, seed=5) installed ("sk", "s_hat" its NTT form from the oracle "o"), then
+    whatever the module's fill_keyed_case(env, case) adds to the dict -- its evaluation keys, records and results.  The
+    contexts are closed when the module is done."""
+    from oracle.pyoracle import Oracle
+    cache = {}
+
+    def get(shape):
+        if shape not in cache:
+            n, npr = shape
+            o = Oracle(n, npr)
+            ctx = env["pkg"].Context(n, npr)
+            sk = V.secret_key(n, seed=5)
+            ctx.set_secret_key(sk)
+            cache[shape] = case = dict(ctx=ctx, o=o, sk=sk, s_hat=ntt_secret(o, sk))
+            request.module.fill_keyed_case(env, case)
+        return cache[shape]
+
+    yield get
+    for c in cache.values():
+        c["ctx"].close()
 
 
 # ---- C callers ------------------------------------------------------------------------------------------------------

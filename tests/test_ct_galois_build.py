@@ -8,13 +8,19 @@ import numpy as np
 import pytest
 
 from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from vectors import sigma_coeff
 
 ENTRIES = ("se_amd_galois_element", "se_amd_galois_table", "se_amd_gen_galois_keys", "se_amd_set_galois_keys",
            "se_amd_ct_galois_device")
 METHODS = ("gen_galois_keys", "set_galois_keys", "ct_galois")
 DEGREES = (1024, 2048, 4096, 8192, 16384)
-GALOIS_KERNELS = tuple(f"{k}<{logn}>" for k in ("k_ct_galois", "k_galois_diag") for logn in range(10, 15))
+GALOIS_KERNELS = tuple(
+    f"{k}<{logn}{flag}>" for k, flag in (("k_ct_galois", ""), ("k_evk_diag", ", true")) for logn in range(10, 15))
 RELIN_KERNELS = tuple(f"k_ct_relin<{logn}>" for logn in range(10, 15))
+# Waves per SIMD of the two key-switch kernels before they shared their device code (tools/resource_usage.py ct_ops on
+# that commit: 106 / 107 / 107 / 109 / 114 VGPRs for k_ct_relin, 124 / 125 / 125 / 106 / 105 for k_ct_galois): the
+# floor the shared helpers must not cost a wave of.
+KEY_SWITCH_WAVES = {f"{k}<{logn}>": 4 for k in ("k_ct_relin", "k_ct_galois") for logn in range(10, 15)}
 
 
 def test_header_declares_and_library_exports_the_entries(pkg):
@@ -35,16 +41,6 @@ def test_galois_element_refuses_a_bad_degree(pkg):
     for n in (0, 512, 3000, 4097, 32768):
         with pytest.raises(pkg.SealEmbeddedAmdError):
             pkg.galois_element(n, 1)
-
-
-def sigma_coeff(a, g, q):
-    """x(X) -> x(X^g) on natural-order coefficients mod q: coefficient k goes to position k g mod n, negated when
-    k g mod 2n >= n."""
-    n = a.shape[0]
-    u = (np.arange(n, dtype=np.int64) * g) % (2 * n)
-    out = np.zeros_like(a)
-    out[u % n] = np.where(u >= n, (q - a.astype(np.int64)) % q, a).astype(a.dtype)
-    return out
 
 
 @pytest.mark.parametrize("shape", [(1024, 1), (4096, 3)], ids=lambda s: f"{s[0]}x{s[1]}")
@@ -78,7 +74,8 @@ def test_galois_table_identity_and_refusals(pkg):
 
 def test_ct_ops_kernels_use_no_scratch():
     """The fused automorphism + key switch and the Galois diagonal exist for every degree and stay in registers, and
-    so does every other kernel of the file -- the relinearisation kernel they were modelled on among them."""
+    so does every other kernel of the file -- the relinearisation kernel they share the key switch with among them; that
+    sharing costs neither of the two kernels a wave per SIMD at any degree."""
     rows = resource_rows("ct_ops")
     assert rows, "tools/resource_usage.py gave no table for ct_ops"
     for k in GALOIS_KERNELS + RELIN_KERNELS:
@@ -87,6 +84,9 @@ def test_ct_ops_kernels_use_no_scratch():
         print(f"{k}: {vgpr} VGPRs, {scratch} B scratch, {occ} waves/SIMD")
     for k, (_, scratch, _) in rows.items():
         assert scratch == 0, (k, scratch)
+    assert len(KEY_SWITCH_WAVES) == 10
+    for k, waves in KEY_SWITCH_WAVES.items():
+        assert rows[k][2] >= waves, (k, rows[k], waves)
 
 
 def test_slot_sum_example_compiles_as_plain_c(tmp_path):

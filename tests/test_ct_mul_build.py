@@ -9,7 +9,8 @@ from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows
 ENTRIES = ("se_amd_ct_mul_device", "se_amd_decrypt3_level_device", "se_amd_decrypt3_level_keyed_device",
            "se_amd_gen_relin_key", "se_amd_set_relin_key", "se_amd_ct_relin_device")
 METHODS = ("ct_mul", "decrypt3_level", "decrypt3_level_keyed", "gen_relin_key", "set_relin_key", "ct_relin")
-CT_KERNELS = ("k_ct_mul", "k_relin_key_rows", "k_relin_diag") + tuple(f"k_ct_relin<{logn}>" for logn in range(10, 15))
+CT_KERNELS = ("k_ct_mul", "k_relin_key_rows") + tuple(
+    f"{k}<{logn}{flag}>" for k, flag in (("k_ct_relin", ""), ("k_evk_diag", ", false")) for logn in range(10, 15))
 DECRYPT3_KERNELS = tuple(f"{k}<{logn}>" for k in ("k_decrypt3_full", "k_decrypt3_full_keyed") for logn in range(10, 15))
 
 

@@ -13,117 +13,18 @@ import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, build_example, crt_centred,  # noqa: F401
-                         dev_t, encrypt_sym, env, expectation, host_u32, ntt_secret, run_decrypt, stream_of)
+from gpu_support import (DIGIT_BITS, DIGIT_MASK, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches,  # noqa: F401
+                         build_example, centred, crt_centred, dev_t, digits_of, encrypt_sym, env, expectation, host_u32,
+                         keyed_cases, negacyclic, ntt_secret, rand_slab, relin_expect, rescale_expect, run_decrypt,
+                         sentinel_out, stream_of, take, unit_values)
+from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
-DIGIT_BITS = 15
-DIGIT_MASK = (1 << DIGIT_BITS) - 1
 LIFT = 1 << 30
 
 
-# ---- helpers restated from the product tests (a test module imports from the support modules only) ------------------
-def centred(x, q):
-    """canonical residues -> int64 representatives in (-q/2, q/2]  (q odd)."""
-    x = x.astype(np.int64)
-    return np.where(x > q // 2, x - q, x)
-
-
-def negacyclic(a, s):
-    """a * s mod (x^n + 1) in int64 (the callers keep every sum below 2^62)."""
-    n = a.shape[0]
-    full = np.convolve(a, s)
-    res = full[:n].copy()
-    res[:n - 1] -= full[n:]
-    return res
-
-
-def rescale_expect(o, slab):
-    """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: out[j] = (in[j] - NTT_j(delta mod q_j)) . q_last^-1 mod q_j with
-    delta the centred INTT of the last row, from o.intt / o.ntt and uint64 arithmetic."""
-    B, L, n = slab.shape
-    q_last = o.q[L - 1]
-    out = np.zeros((B, L - 1, n), dtype=np.uint32)
-    for b in range(B):
-        delta = centred(o.intt(slab[b, L - 1], L - 1), q_last)
-        for j in range(L - 1):
-            q = o.q[j]
-            inv = pow(q_last, -1, q)
-            t = o.ntt((delta % q).astype(np.uint32), j).astype(np.uint64)
-            diff = (slab[b, j].astype(np.uint64) + np.uint64(q) - t) % np.uint64(q)
-            out[b, j] = ((diff * np.uint64(inv)) % np.uint64(q)).astype(np.uint32)
-    return out
-
-
-def sentinel_out(env, words, extra):
-    return env["torch"].full((words + extra,), SENTINEL, dtype=env["torch"].int32, device=env["dev"])
-
-
-def take(t, words, shape, what):
-    """Host copy of the first `words` words of a sentinel-backed output; the words behind them must be untouched."""
-    h = host_u32(t)
-    assert (h[words:] == SENTINEL).all(), f"{what}: words behind the result are written"
-    return h[:words].reshape(shape)
-
-
-def rand_slab(rng, q, count, n, primes=None):
-    primes = len(q) if primes is None else primes
-    return np.stack([rng.integers(0, q[j], (count, n), dtype=np.uint32) for j in range(primes)], axis=1)
-
-
-def unit_values(B, n, seed):
-    """float32 [B][n/2], uniform in [-1, 1]."""
-    return np.random.default_rng(seed).uniform(-1.0, 1.0, (B, n // 2)).astype(np.float32)
-
-
-def digits_of(o, rec, L):
-    """Record [L][n] -> the 2 L digit polynomials D_{j,t} (uint32, natural order), row r = 2j + t."""
-    out = []
-    for j in range(L):
-        c = o.intt(rec[j], j)
-        out += [c & np.uint32(DIGIT_MASK), c >> np.uint32(DIGIT_BITS)]
-    return out
-
-
-def relin_expect(o, d0, d1, d2, evk0, evk1):
-    """out_k[b][i] = d_k[b][i] + sum_r NTT_i(D_r) . evk_k[r][i] mod q_i, from o.intt / o.ntt and uint64 arithmetic (a
-    product is below 2^60, reduced before it is added)."""
-    B, L, n = d0.shape
-    out0, out1 = np.zeros_like(d0), np.zeros_like(d1)
-    for b in range(B):
-        D = digits_of(o, d2[b], L)
-        for i in range(L):
-            q = np.uint64(o.q[i])
-            acc0, acc1 = d0[b, i].astype(np.uint64), d1[b, i].astype(np.uint64)
-            for r, dig in enumerate(D):
-                f = o.ntt(dig, i).astype(np.uint64)
-                acc0 = (acc0 + (f * evk0[r, i].astype(np.uint64)) % q) % q
-                acc1 = (acc1 + (f * evk1[r, i].astype(np.uint64)) % q) % q
-            out0[b, i], out1[b, i] = acc0, acc1
-    return out0, out1
-
-
-# ---- the automorphism, in the coefficient domain --------------------------------------------------------------------
-def image(n, g):
-    """-> (pos, neg): coefficient k of x goes to position pos[k] of x(X^g), negated where neg[k]."""
-    u = (np.arange(n, dtype=np.int64) * g) % (2 * n)
-    return u % n, u >= n
-
-
-def sigma_coeff(a, g, q=None):
-    """x(X) -> x(X^g) on natural-order coefficients: residues mod q (uint32; a negated 0 stays 0), or with q = None
-    plain integers (int64 or object)."""
-    pos, neg = image(a.shape[0], g)
-    out = np.zeros_like(a)
-    if q is None:
-        out[pos] = np.where(neg, -a, a)
-    else:
-        out[pos] = np.where(neg, (q - a.astype(np.int64)) % q, a).astype(a.dtype)
-    return out
-
-
+# ---- the automorphism, in the coefficient domain (vectors.sigma_coeff) on a slab ------------------------------------
 def sigma_slab(o, slab, g):
     """sigma on every NTT-form row of a slab [B][L][n] through o.intt / o.ntt."""
     out = np.zeros_like(slab)
@@ -162,7 +63,7 @@ def edge_row(o, j, rng, elts):
     for start in (0, n // 2, n - 13):           # twice, 7 apart: an even and an odd index for every value
         c[start:start + 6] = c[start + 7:start + 13] = edges
     for g in elts:
-        _, neg = image(n, g)
+        _, neg = V.galois_image(n, g)
         for v in edges:
             at = c == v
             assert (at & neg).any() and (at & ~neg).any(), (g, int(v))
@@ -408,41 +309,23 @@ def test_galois_arguments(env):
 STEPS = (1, -3)
 
 
-@pytest.fixture(scope="module")
-def keyed_cases(env):
-    """Per shape, computed once: a context with a secret key and the Galois keys of the steps 1 and -3 installed, B = 4
-    fresh symmetric records with slot values in [-1, 1] and the same records lifted by 2^30 in the test's own
-    integers."""
-    from oracle.pyoracle import Oracle
-    cache = {}
-
-    def get(shape):
-        if shape in cache:
-            return cache[shape]
-        n, npr = shape
-        B = 4
-        o = Oracle(n, npr)
-        pkg = env["pkg"]
-        ctx = pkg.Context(n, npr)
-        sk = V.secret_key(n, seed=5)
-        ctx.set_secret_key(sk)
-        elts = [pkg.galois_element(n, s) for s in STEPS]
-        assert elts == [pow(3, s % (n // 2), 2 * n) for s in STEPS]
-        gk0, gk1 = ctx.gen_galois_keys(sk, elts, *galois_seeds(npr, len(elts), "gk-e2e"))
-        ctx.set_galois_keys(elts, gk0, gk1)
-        vals = unit_values(B, n, 3000 + n)
-        c0, c1, _, st = encrypt_sym(env, ctx, vals, first=200)
-        assert bool((st == 1).all())
-        qv = np.array(o.q, dtype=np.uint64)[None, :, None]
-        l0 = ((host_u32(c0).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
-        l1 = ((host_u32(c1).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
-        cache[shape] = dict(ctx=ctx, o=o, sk=sk, s_hat=ntt_secret(o, sk), elts=elts, gk0=gk0, gk1=gk1, vals=vals,
-                            fresh=(c0, c1), lifted=(l0, l1))
-        return cache[shape]
-
-    yield get
-    for c in cache.values():
-        c["ctx"].close()
+def fill_keyed_case(env, case):
+    """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the Galois keys of the
+    steps 1 and -3, installed; B = 4 fresh symmetric records with slot values in [-1, 1] and the same records lifted by
+    2^30 in the test's own integers."""
+    ctx, o, sk, pkg = case["ctx"], case["o"], case["sk"], env["pkg"]
+    n, npr, B = ctx.n, ctx.np, 4
+    elts = [pkg.galois_element(n, s) for s in STEPS]
+    assert elts == [pow(3, s % (n // 2), 2 * n) for s in STEPS]
+    gk0, gk1 = ctx.gen_galois_keys(sk, elts, *galois_seeds(npr, len(elts), "gk-e2e"))
+    ctx.set_galois_keys(elts, gk0, gk1)
+    vals = unit_values(B, n, 3000 + n)
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=200)
+    assert bool((st == 1).all())
+    qv = np.array(o.q, dtype=np.uint64)[None, :, None]
+    l0 = ((host_u32(c0).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
+    l1 = ((host_u32(c1).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
+    case.update(elts=elts, gk0=gk0, gk1=gk1, vals=vals, fresh=(c0, c1), lifted=(l0, l1))
 
 
 @pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")

@@ -13,69 +13,12 @@ import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, build_example, crt_centred,  # noqa: F401
-                         decode_expect, dev_t, encrypt_sym, env, expectation, host_u32, ntt_secret, run_decrypt,
-                         same_bytes, stream_of)
+from gpu_support import (DIGIT_BITS, DIGIT_MASK, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches,  # noqa: F401
+                         build_example, centred, crt_centred, decode_expect, dev_t, digits_of, encrypt_sym, env,
+                         expectation, host_u32, keyed_cases, negacyclic, ntt_secret, rand_slab, relin_expect,
+                         rescale_expect, run_decrypt, same_bytes, sentinel_out, stream_of, take, unit_values)
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x5A5A5A5A
-DIGIT_BITS = 15
-DIGIT_MASK = (1 << DIGIT_BITS) - 1
-
-
-# ---- helpers restated from the rescale tests (a test module imports from the support modules only) ------------------
-def centred(x, q):
-    """canonical residues -> int64 representatives in (-q/2, q/2]  (q odd)."""
-    x = x.astype(np.int64)
-    return np.where(x > q // 2, x - q, x)
-
-
-def negacyclic(a, s):
-    """a * s mod (x^n + 1) in int64 (the callers keep every sum below 2^62)."""
-    n = a.shape[0]
-    full = np.convolve(a, s)
-    res = full[:n].copy()
-    res[:n - 1] -= full[n:]
-    return res
-
-
-def rescale_expect(o, slab):
-    """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: out[j] = (in[j] - NTT_j(delta mod q_j)) . q_last^-1 mod q_j with
-    delta the centred INTT of the last row, from o.intt / o.ntt and uint64 arithmetic."""
-    B, L, n = slab.shape
-    q_last = o.q[L - 1]
-    out = np.zeros((B, L - 1, n), dtype=np.uint32)
-    for b in range(B):
-        delta = centred(o.intt(slab[b, L - 1], L - 1), q_last)
-        for j in range(L - 1):
-            q = o.q[j]
-            inv = pow(q_last, -1, q)
-            t = o.ntt((delta % q).astype(np.uint32), j).astype(np.uint64)
-            diff = (slab[b, j].astype(np.uint64) + np.uint64(q) - t) % np.uint64(q)
-            out[b, j] = ((diff * np.uint64(inv)) % np.uint64(q)).astype(np.uint32)
-    return out
-
-
-def sentinel_out(env, words, extra):
-    return env["torch"].full((words + extra,), SENTINEL, dtype=env["torch"].int32, device=env["dev"])
-
-
-def take(t, words, shape, what):
-    """Host copy of the first `words` words of a sentinel-backed output; the words behind them must be untouched."""
-    h = host_u32(t)
-    assert (h[words:] == SENTINEL).all(), f"{what}: words behind the result are written"
-    return h[:words].reshape(shape)
-
-
-def rand_slab(rng, q, count, n, primes=None):
-    primes = len(q) if primes is None else primes
-    return np.stack([rng.integers(0, q[j], (count, n), dtype=np.uint32) for j in range(primes)], axis=1)
-
-
-def unit_values(B, n, seed):
-    """float32 [B][n/2], uniform in [-1, 1]."""
-    return np.random.default_rng(seed).uniform(-1.0, 1.0, (B, n // 2)).astype(np.float32)
 
 
 # ---- test 1: the tensor on arbitrary slabs --------------------------------------------------------------------------
@@ -447,33 +390,6 @@ def test_relin_key_generation(env, shape):
 
 
 # ---- test 4: the relinearisation on arbitrary slabs and key words ---------------------------------------------------
-def digits_of(o, d2_rec, L):
-    """Record [L][n] -> the 2 L digit polynomials D_{j,t} (uint32, natural order), row r = 2j + t."""
-    out = []
-    for j in range(L):
-        c = o.intt(d2_rec[j], j)
-        out += [c & np.uint32(DIGIT_MASK), c >> np.uint32(DIGIT_BITS)]
-    return out
-
-
-def relin_expect(o, d0, d1, d2, evk0, evk1):
-    """The definition: out_k[b][i] = d_k[b][i] + sum_r NTT_i(D_r) . evk_k[r][i] mod q_i, from o.intt / o.ntt and uint64
-    arithmetic (a product is below 2^60, reduced before it is added)."""
-    B, L, n = d0.shape
-    out0, out1 = np.zeros_like(d0), np.zeros_like(d1)
-    for b in range(B):
-        D = digits_of(o, d2[b], L)
-        for i in range(L):
-            q = np.uint64(o.q[i])
-            acc0, acc1 = d0[b, i].astype(np.uint64), d1[b, i].astype(np.uint64)
-            for r, dig in enumerate(D):
-                f = o.ntt(dig, i).astype(np.uint64)
-                acc0 = (acc0 + (f * evk0[r, i].astype(np.uint64)) % q) % q
-                acc1 = (acc1 + (f * evk1[r, i].astype(np.uint64)) % q) % q
-            out0[b, i], out1[b, i] = acc0, acc1
-    return out0, out1
-
-
 def run_relin(env, ctx, d0, d1, d2, primes):
     """One call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
     torch = env["torch"]
@@ -528,6 +444,30 @@ def test_relin_arbitrary_slabs_and_key(env, shape, levels):
     ctx.close()
 
 
+def test_refused_relin_key_leaves_the_installed_one(env):
+    """The replacement rule of the evaluation keys, on the relinearisation key (1024 x 1, B = 2): with key A installed,
+    a key with one word equal to q_0 is refused as an invalid argument, and ct_relin afterwards still gives the
+    definition under key A."""
+    from oracle.pyoracle import Oracle
+    pkg = env["pkg"]
+    n, npr, B = 1024, 1, 2
+    o = Oracle(n, npr)
+    ctx = pkg.Context(n, npr)
+    rng = np.random.default_rng(77)
+    evk0, evk1 = (np.stack([rand_slab(rng, o.q, 1, n)[0] for _ in range(2 * npr)]) for _ in range(2))
+    ctx.set_relin_key(evk0, evk1)
+    bad = evk1.copy()
+    bad[1, 0, n // 2] = o.q[0]
+    with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
+        ctx.set_relin_key(evk0, bad)
+    assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
+    d0, d1, d2 = (rand_slab(rng, o.q, B, n) for _ in range(3))
+    e0, e1 = relin_expect(o, d0, d1, d2, evk0, evk1)
+    g0, g1 = run_relin(env, ctx, dev_t(env, d0), dev_t(env, d1), dev_t(env, d2), npr)
+    assert (g0 == e0).all() and (g1 == e1).all()
+    ctx.close()
+
+
 def test_relin_arguments(env):
     """The argument errors return -22 and write nothing; B = 0 is a successful no-op."""
     torch = env["torch"]
@@ -574,38 +514,22 @@ def test_relin_arguments(env):
 
 
 # ---- tests 5 and 6: a real key ---------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def keyed_cases(env):
-    """Per shape, computed once: a context with a secret key and its relinearisation key installed, B = 4 records with
-    slot values in [-1, 1], the tensor of the pairs (b, b + 1 mod B) and its relinearisation."""
-    from oracle.pyoracle import Oracle
-    cache = {}
-
-    def get(shape):
-        if shape in cache:
-            return cache[shape]
-        n, npr = shape
-        B = 4
-        o = Oracle(n, npr)
-        ctx = env["pkg"].Context(n, npr)
-        sk = V.secret_key(n, seed=5)
-        ctx.set_secret_key(sk)
-        evk0, evk1 = ctx.gen_relin_key(sk, *relin_seeds(npr, "e2e"))
-        ctx.set_relin_key(evk0, evk1)
-        vals = unit_values(B, n, 2000 + n)
-        c0, c1, _, st = encrypt_sym(env, ctx, vals, first=160)
-        assert bool((st == 1).all())
-        ia, ib = list(range(B)), [(b + 1) % B for b in range(B)]
-        t, tst = run_tensor(env, ctx, c0, c1, c0, c1, ia, ib)
-        assert (tst == 1).all()
-        r0, r1 = run_relin(env, ctx, *(dev_t(env, t[k]) for k in range(3)), npr)
-        cache[shape] = dict(ctx=ctx, o=o, sk=sk, s_hat=ntt_secret(o, sk), evk0=evk0, evk1=evk1, vals=vals, ia=ia, ib=ib,
-                            tensor=t, relin=(r0, r1))
-        return cache[shape]
-
-    yield get
-    for c in cache.values():
-        c["ctx"].close()
+def fill_keyed_case(env, case):
+    """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the relinearisation key,
+    installed; B = 4 records with slot values in [-1, 1], the tensor of the pairs (b, b + 1 mod B) and its
+    relinearisation."""
+    ctx, sk = case["ctx"], case["sk"]
+    n, npr, B = ctx.n, ctx.np, 4
+    evk0, evk1 = ctx.gen_relin_key(sk, *relin_seeds(npr, "e2e"))
+    ctx.set_relin_key(evk0, evk1)
+    vals = unit_values(B, n, 2000 + n)
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=160)
+    assert bool((st == 1).all())
+    ia, ib = list(range(B)), [(b + 1) % B for b in range(B)]
+    t, tst = run_tensor(env, ctx, c0, c1, c0, c1, ia, ib)
+    assert (tst == 1).all()
+    r0, r1 = run_relin(env, ctx, *(dev_t(env, t[k]) for k in range(3)), npr)
+    case.update(evk0=evk0, evk1=evk1, vals=vals, ia=ia, ib=ib, tensor=t, relin=(r0, r1))
 
 
 @pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")

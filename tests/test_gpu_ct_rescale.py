@@ -12,40 +12,16 @@ import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, build_example, dev_t,  # noqa: F401
-                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, same_bytes,
-                         stream_of)
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, bits, build_example,  # noqa: F401
+                         centred, dev_t, encrypt_sym, env, expectation, host_u32, negacyclic, ntt_secret, records,
+                         rescale_expect, run_decrypt, same_bytes, stream_of)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 WEIGHT_BITS = 30
 
 
 # ---- expectations ----------------------------------------------------------------------------------------------------
-def centred(x, q):
-    """canonical residues -> int64 representatives in (-q/2, q/2]  (q odd)."""
-    x = x.astype(np.int64)
-    return np.where(x > q // 2, x - q, x)
-
-
-def rescale_expect(o, slab):
-    """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: the issue's map, from o.intt / o.ntt and uint64 arithmetic
-    (every intermediate is below 2^60).  o is an oracle with at least L primes."""
-    B, L, n = slab.shape
-    q_last = o.q[L - 1]
-    out = np.zeros((B, L - 1, n), dtype=np.uint32)
-    for b in range(B):
-        delta = centred(o.intt(slab[b, L - 1], L - 1), q_last)
-        for j in range(L - 1):
-            q = o.q[j]
-            inv = pow(q_last, -1, q)
-            t = o.ntt((delta % q).astype(np.uint32), j).astype(np.uint64)
-            diff = (slab[b, j].astype(np.uint64) + np.uint64(q) - t) % np.uint64(q)
-            out[b, j] = ((diff * np.uint64(inv)) % np.uint64(q)).astype(np.uint32)
-    return out
-
-
 def run_rescale(env, ctx, in0, in1, primes):
     """One call; the outputs carry two extra rows behind the packed [B][primes-1][n] result, pre-filled with a
     sentinel that must survive.  -> out0, out1 | None (host uint32 [B][primes-1][n])."""
@@ -169,15 +145,6 @@ def ternary_natural(o, sk):
     """The secret key as int64 coefficients in {-1, 0, 1}, natural order."""
     s = o.expand_ternary(sk, 0).astype(np.int64)
     return np.where(s == o.q[0] - 1, -1, s)
-
-
-def negacyclic(a, s):
-    """a * s mod (x^n + 1) in int64 (|a| < 2^29, s ternary, n <= 2^14: every sum is below 2^44)."""
-    n = a.shape[0]
-    full = np.convolve(a, s)
-    res = full[:n].copy()
-    res[:n - 1] -= full[n:]
-    return res
 
 
 @pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")

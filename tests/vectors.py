@@ -162,3 +162,21 @@ def nonfinite_values(case, n, seed=99):
 
 def sha256_hex(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def galois_image(n, g):
+    """-> (pos, neg): coefficient k of x goes to position pos[k] of x(X^g), negated where neg[k]."""
+    u = (np.arange(n, dtype=np.int64) * g) % (2 * n)
+    return u % n, u >= n
+
+
+def sigma_coeff(a, g, q=None):
+    """x(X) -> x(X^g) on natural-order coefficients: coefficient k goes to position k g mod n, negated when
+    k g mod 2n >= n.  Residues mod q (uint32; a negated 0 stays 0), or with q = None plain integers (int64 or object)."""
+    pos, neg = galois_image(a.shape[0], g)
+    out = np.zeros_like(a)
+    if q is None:
+        out[pos] = np.where(neg, -a, a)
+    else:
+        out[pos] = np.where(neg, (q - a.astype(np.int64)) % q, a).astype(a.dtype)
+    return out
