@@ -475,7 +475,7 @@ int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t
  * 2.5e7 per coefficient at 4096 x 3): rotate at a raised scale and rescale afterwards.  A product before its rescale is
  * already at scale^2; a fresh record is first lifted by se_amd_ct_lincomb_device with weight 2^30, which costs one level
  * (INTEGRATION.md section 4h).
- * Out of scope: hoisted rotations (one digit decomposition shared by many elements), a per-record element list,
+ * Out of scope: plaintext-weighted sums of rotations (the diagonal method), a per-record element list,
  * multi-GPU group entries, a special-prime (hybrid) key switch.
  *
  * se_amd_galois_element (host only, no context): *elt = 3^(step mod n/2) mod 2n, the step reduced into [0, n/2); step 0
@@ -518,6 +518,33 @@ int se_amd_set_galois_keys(se_amd_ctx *ctx, const uint32_t *elts, size_t G, cons
  * no-op.  Nothing is written on an error. */
 int se_amd_ct_galois_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                             uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, void *stream);
+/* Hoisted rotations: G rotations of every record from ONE digit decomposition of c1, under the Galois keys installed
+ * for se_amd_ct_galois_device as they are.  elts is a HOST pointer to G elements, 1 <= G <= SE_AMD_MAX_GALOIS_KEYS; an
+ * element may be listed twice.  Let D_{j,t} be the t-th 15-bit digit of each coefficient of the canonical natural-order
+ * INTT_j(c1[b][j]) -- of c1 itself, not of sigma(c1).  For element g (its installed key gk[g]), record b and i < primes,
+ * mod q_i and canonical:
+ *     rot0[g][b][i][k] = c0[b][i][src_g(k)] + sum_{j < primes, t} NTT_i(D_{j,t})[src_g(k)] . gk0[g][2j + t][i][k]
+ *     rot1[g][b][i][k] =                      sum_{j < primes, t} NTT_i(D_{j,t})[src_g(k)] . gk1[g][2j + t][i][k].
+ * sum_t 2^(15 t) sigma(D_{j,t}) = sigma(c1_j) mod q_j and sigma(D) has coefficients of magnitude below 2^15, so rot[g]
+ * decrypts to sigma_g of the input plus a key-switch term of the same bound as se_amd_ct_galois_device's.  It is NOT
+ * bit-identical to that entry: there the digits are those of sigma(c1), and a negated coefficient q - c has other digits
+ * than c.  The transforms (the dominant cost) are shared by the elements: an element costs a permutation and a
+ * multiply-accumulate.
+ * se_amd_ct_galois_many_device: d_out0, d_out1 are [G][B][primes][n], out[e] = rot[elts[e]].
+ * se_amd_ct_galois_sum_device: d_out0, d_out1 are [B][primes][n], out = add_input . (c0, c1) + sum_e rot[elts[e]] mod
+ * q_i; an element listed twice counts twice; add_input (0 or not) adds the record itself, the rotation by 0, which needs
+ * no key.  The transforms per record are those of ONE rotation whatever G is.
+ * Outputs must not overlap the inputs.  One asynchronous call each, no scratch, no host synchronisation.
+ * SE_ERR_INVALD_ARGUMENT for a NULL slab pointer, primes outside [1, np], a slab pointer that is not 16-byte aligned, B
+ * at or above 2^32 (the checks of se_amd_ct_galois_device), then for elts NULL, G = 0, G > 64, an even element or one
+ * >= 2n; SE_ERR_NO_KEY when an element has no installed key (the last-error text names it).  Nothing is launched or
+ * written on an error.  B = 0 is a successful no-op. */
+int se_amd_ct_galois_many_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                 const uint32_t *elts /*host, [G]*/, size_t G, uint32_t *d_out0, uint32_t *d_out1,
+                                 void *stream);
+int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                const uint32_t *elts /*host, [G]*/, size_t G, int add_input, uint32_t *d_out0,
+                                uint32_t *d_out1, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

@@ -68,7 +68,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_ct_mul_device", "se_amd_decrypt3_level_device", "se_amd_decrypt3_level_keyed_device",
     "se_amd_gen_relin_key", "se_amd_set_relin_key", "se_amd_ct_relin_device",
     "se_amd_galois_element", "se_amd_galois_table", "se_amd_gen_galois_keys", "se_amd_set_galois_keys",
-    "se_amd_ct_galois_device",
+    "se_amd_ct_galois_device", "se_amd_ct_galois_many_device", "se_amd_ct_galois_sum_device",
 )
 
 
@@ -165,6 +165,8 @@ def lib():
     L.se_amd_gen_galois_keys.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
     L.se_amd_set_galois_keys.argtypes = [vp, vp, sz, vp, vp]
     L.se_amd_ct_galois_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp]
+    L.se_amd_ct_galois_many_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
+    L.se_amd_ct_galois_sum_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -660,6 +662,31 @@ class Context:
             primes = c0.shape[1]
         _check(self.L.se_amd_ct_galois_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, int(elt), _ptr(out0),
                                               _ptr(out1), _stream_ptr()), "se_amd_ct_galois_device")
+
+    def ct_galois_many(self, c0, c1, elts, out0, out1, primes=None):
+        """Hoisted rotations: out[e] = the rotation of the records (c0, c1) [B][primes][n] by elts[e], for all G
+        elements from ONE digit decomposition of c1, with the installed Galois keys; out0, out1 are [G][B][primes][n].
+        Decrypts like ct_galois per element, but is not bit-identical to it (the digits are those of c1, permuted after
+        the transform)."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_galois_many_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el), el.size,
+                                                   _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_galois_many_device")
+
+    def ct_galois_sum(self, c0, c1, elts, out0, out1, add_input=False, primes=None):
+        """The sum of the hoisted rotations by elts[0 .. G) in one record, plus the record itself with add_input:
+        out0, out1 are [B][primes][n].  The transforms are those of one rotation whatever G is; an element listed twice
+        counts twice."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_galois_sum_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el), el.size,
+                                                  1 if add_input else 0, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_galois_sum_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

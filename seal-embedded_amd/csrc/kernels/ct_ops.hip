@@ -2,7 +2,8 @@
 // slot-wise products with encoded plaintexts (se_amd_ct_mul_plain_device) and the rescale that drops the last prime
 // (se_amd_ct_rescale_device), and the ciphertext products: the tensor (se_amd_ct_mul_device) and the relinearisation
 // that brings it back to two slabs (se_amd_ct_relin_device, with the key plumbing), and the slot rotation: a ring
-// automorphism fused with its key switch (se_amd_ct_galois_device, at the end of the file).
+// automorphism fused with its key switch (se_amd_ct_galois_device), and its hoisted form, many rotations of a record
+// from one digit decomposition (se_amd_ct_galois_many_device, se_amd_ct_galois_sum_device, at the end of the file).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -417,7 +418,8 @@ hipError_t launch_ct_rescale(const DevParams &P, const DevTables &T, const Resca
 }
 
 // ------------------------------------------------------------------------------------------
-// The key switch under an evaluation key, shared by k_ct_relin and k_ct_galois: for one record and output prime i,
+// The key switch under an evaluation key, shared by k_ct_relin and k_ct_galois (k_ct_galois_hoist takes the first step
+// and has its own second one): for one record and output prime i,
 //   acc0[i] = sum_{j < L, t < 2} NTT_i(D_{j,t}) . key0[2j + t][i]  mod q_i   (acc1: key1),
 // D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients c_j of an input row j.  Built from the
 // pieces of k_ct_rescale, one workgroup of n/16 threads per (record, output prime i), in two steps per input prime j:
@@ -684,6 +686,238 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
         using G         = XformGeom<L>;
         const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
         return launch(k_ct_galois<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Hoisted rotations: G rotations of a record from ONE digit decomposition of c1 (se_amd_ct_galois_many_device,
+// se_amd_ct_galois_sum_device).  k_ct_galois decomposes sigma(c1), so every element pays the L INTTs and 2 L NTTs of its
+// key switch again.  Here the digits D_{j,t} are those of c1 itself and sigma is applied to the TRANSFORMED digit, where
+// it is the permutation src_g of a bit-reversed row (galois_src above):
+//   rot0[g][b][i][k] = c0[b][i][src_g(k)] + sum_{j < L, t < 2} NTT_i(D_{j,t})[src_g(k)] . gk0_g[2j + t][i][k]  mod q_i,
+//   rot1[g][b][i][k] =                      sum_{j < L, t < 2} NTT_i(D_{j,t})[src_g(k)] . gk1_g[2j + t][i][k]  mod q_i.
+// sum_t 2^(15 t) sigma(D_{j,t}) = sigma(c1_j) mod q_j and sigma(D) has coefficients of magnitude below 2^15, so this is
+// a key switch under the SAME Galois keys; it is not bit-identical to k_ct_galois (a negated coefficient q - c has other
+// digits than c).  The third caller of evk_row_coeffs: the same grid, thread shape, roots, key layout and lazy
+// accumulator range as its two siblings (mul_shoup_lazy takes any 32-bit y: the argument above holds word for word).
+// Per input prime j: evk_row_coeffs once; per digit: ntt_tiles mod q_i, which ends in tile layout 0 -- thread t holds the
+// words 16 t .. 16 t + 15, lazy in [0, 4 q_i) -- with the plane free, so the thread parks them as they are, word k at
+// lds[k] (4 ds_write_b128; no tile_to_quads: the gather below re-deals).  One barrier; then, per element of the group,
+// every thread gathers the 16 words of its quads from lds[src_g(k)] and multiply-accumulates them against rows 2j + t of
+// both halves of that element's key block; one barrier before the next transform.  An element costs a gather and a
+// multiply-accumulate per digit; the transforms are shared.
+//   SUM: ONE accumulator pair serves all G elements (an element listed twice counts twice); the c0 row is staged once
+//     and gathered G times; with add_input the record itself (the rotation by 0, which needs no key) joins the sum.
+//     Transforms per record are those of a single rotation whatever G is.
+//   many: one accumulator pair (32 VGPRs) per element in flight, so the elements are taken in groups of kHoistGroup per
+//     pass over the digits: ceil(G / kHoistGroup) times the transforms of one rotation.  The last group may be short.
+// src_g(k) in registers: brev is additive over disjoint bit fields, so with r4 = brev(k4) of the thread's first quad and
+// the compile-time offset d of a word in the quads, (2 brev(k4 + d) + 1) g = (2 r4 + 1) g + 2 brev(d) g: one per-thread
+// product per element, a scalar product per word, then v_add, v_bfrev and the shift / mask to the LDS address.
+// The only addresses formed from data are formed from the elements, launch arguments the host has checked (odd, below
+// 2n): every target is masked to [0, n), and no word of a slab or of a key is used as an address.  The elements and
+// their key blocks are read from the argument block with a workgroup-uniform index (scalar loads).
+// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// ------------------------------------------------------------------------------------------
+constexpr int kHoistGroup = 2;   // elements in flight of the many form: the largest without scratch at every degree
+// n = 16384 is one workgroup of 16 waves, 4 per SIMD: 128 VGPRs at most, and two accumulator pairs beside the
+// coefficients of the input row and a transform in flight are 9 more than that.  There the many form parks the
+// coefficients in a second plane of n words behind the exchange plane while a digit is transformed: every thread reads
+// back the slots it wrote itself (lane-consecutive, no conflict, no barrier).  One workgroup per CU either way.
+template <int LOGN, bool SUM>
+constexpr bool kHoistPark = LOGN == 14 && !SUM;
+
+// src_g of the word whose (2 brev(k) + 1) g is u (any bits above 2n are dropped by the shift, the odd bit by the mask)
+template <int LOGN>
+__device__ __forceinline__ uint32_t galois_src_of(uint32_t u)
+{
+    return (__brev(u) >> (31 - LOGN)) & ((1u << LOGN) - 1);
+}
+
+// the 16 words of the thread's quads of sigma_g(row), row parked in the plane with word k at plane[k]; word 4 c + k of
+// the thread is k4 + (c << 8) + k.  u0 = (2 brev(k4) + 1) g < 2^30, the offsets add less than 2^30.
+template <int LOGN>
+__device__ __forceinline__ uint32_t hoist_word(const uint32_t *plane, uint32_t u0, uint32_t g, int c, int k)
+{
+    const uint32_t rd = __brev((uint32_t)((c << 8) + k)) >> (32 - LOGN);
+    return plane[galois_src_of<LOGN>(u0 + 2 * rd * g)];
+}
+
+// One element's share of one digit: acc += sigma_g(NTT_i(D))[k] . key[k] on both halves; `key` = the thread's first quad
+// of row 2j + t, column i of the element's block.
+template <int LOGN>
+__device__ __forceinline__ void hoist_mac(uint32_t (&acc0)[16], uint32_t (&acc1)[16], const uint32_t *plane,
+                                          const uint32_t *key, size_t half, uint32_t g, uint32_t r4, uint32_t qi)
+{
+    constexpr int N       = XformGeom<LOGN>::N;
+    const uint32_t two_qi = qi << 1;
+    const uint32_t u0     = (2 * r4 + 1) * g;
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
+        const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
+        const uint4 w1 = *reinterpret_cast<const uint4 *>(key + half + (c << 8));
+        const uint4 s1 = *reinterpret_cast<const uint4 *>(key + half + N + (c << 8));
+        const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
+        const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const int e       = 4 * c + k;
+            const uint32_t y  = hoist_word<LOGN>(plane, u0, g, c, k);
+            const uint32_t v0 = acc0[e] + mul_shoup_lazy(y, w0v[k], s0v[k], qi);
+            const uint32_t v1 = acc1[e] + mul_shoup_lazy(y, w1v[k], s1v[k], qi);
+            acc0[e]           = min(v0, v0 - two_qi);
+            acc1[e]           = min(v1, v1 - two_qi);
+        }
+    }
+}
+
+template <int LOGN, bool SUM>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_hoist(const DevParams P, const DevTables T,
+                                                                           const GaloisHoistArgs A)
+{
+    using G          = XformGeom<LOGN>;
+    constexpr int N  = G::N;
+    constexpr int GC = SUM ? 1 : kHoistGroup;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t qi  = P.q[i];
+    const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
+    const uint32_t r4  = __brev((uint32_t)quad_index(t, 0)) >> (32 - LOGN);
+    const uint32_t groups = SUM ? 1u : (A.G + GC - 1) / GC;
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        for (uint32_t grp = 0; grp < groups; grp++)
+        {
+            const uint32_t e0 = grp * GC;
+            uint32_t acc0[GC][16], acc1[GC][16];
+#pragma unroll
+            for (int u = 0; u < GC; u++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc0[u][e] = acc1[u][e] = 0;
+            for (uint32_t j = 0; j < A.primes; j++)
+            {
+                uint32_t x[16];
+                evk_row_coeffs<LOGN>(x, A.c1 + rec + (size_t)j * N, j, P, T, lds, opaque_index(t));
+                if constexpr (kHoistPark<LOGN, SUM>)
+                {
+                    uint32_t *park = lds + G::SLOTS + opaque_index(t);   // one base register, immediate offsets
+#pragma unroll
+                    for (int e = 0; e < 16; e++) park[G::THREADS * e] = x[e];
+                }
+                // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
+#pragma unroll 1
+                for (uint32_t dg = 0; dg < 2; dg++)
+                {
+                    const int td         = opaque_index(t);
+                    const uint32_t *park = lds + G::SLOTS + td;
+                    uint32_t y[16];
+#pragma unroll
+                    for (int e = 0; e < 16; e++)
+                    {
+                        const uint32_t xe = kHoistPark<LOGN, SUM> ? park[G::THREADS * e] : x[e];
+                        y[e]              = (xe >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
+                    }
+                    ntt_tiles<LOGN>(y, rw, qi, lds, td);
+#pragma unroll
+                    for (int c = 0; c < 4; c++)
+                        *reinterpret_cast<uint4 *>(lds + 16 * td + 4 * c) =
+                            make_uint4(y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]);
+                    __syncthreads();
+                    // the thread's first quad of row 2j + dg, column i of a key block
+                    const size_t ko = ((size_t)(2 * j + dg) * A.np + i) * 2 * N + quad_index(td, 0);
+                    if constexpr (SUM)
+                    {
+#pragma unroll 1
+                        for (uint32_t e = 0; e < A.G; e++)
+                            hoist_mac<LOGN>(acc0[0], acc1[0], lds, A.key[e] + ko, A.half, A.elt[e], r4, qi);
+                    }
+                    else
+                    {
+#pragma unroll
+                        for (int u = 0; u < GC; u++)
+                            if (e0 + u < A.G)
+                                hoist_mac<LOGN>(acc0[u], acc1[u], lds, A.key[e0 + u] + ko, A.half, A.elt[e0 + u], r4, qi);
+                    }
+                    __syncthreads();
+                }
+            }
+            // the c0 row of output prime i as it lies in memory goes into the plane, word k at lds[k]; gathered per element
+            const int te   = opaque_index(t);
+            const size_t o = rec + (size_t)i * N;
+            const int k4   = quad_index(te, 0);
+            uint32_t c[16];
+            load_quads(c, A.c0 + o, te);
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+                *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+            __syncthreads();
+            if constexpr (SUM)
+            {
+                // canonical sum of the G gathered rows, and of the row itself with add_input
+                if (!A.add_input)
+#pragma unroll
+                    for (int e = 0; e < 16; e++) c[e] = 0;
+#pragma unroll 1
+                for (uint32_t e = 0; e < A.G; e++)
+                {
+                    const uint32_t g = A.elt[e], u0 = (2 * r4 + 1) * g;
+#pragma unroll
+                    for (int w = 0; w < 16; w++) c[w] = csub(c[w] + hoist_word<LOGN>(lds, u0, g, w >> 2, w & 3), qi);
+                }
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc0[0][e] = csub(csub(acc0[0][e], qi) + c[e], qi);
+                store_quads(A.out0 + o, acc0[0], te);
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc1[0][e] = csub(acc1[0][e], qi);
+                if (A.add_input)
+                {
+                    load_quads(c, A.c1 + o, te);
+#pragma unroll
+                    for (int e = 0; e < 16; e++) acc1[0][e] = csub(acc1[0][e] + c[e], qi);
+                }
+                store_quads(A.out1 + o, acc1[0], te);
+            }
+            else
+            {
+#pragma unroll
+                for (int u = 0; u < GC; u++)
+                    if (e0 + u < A.G)
+                    {
+                        const uint32_t g = A.elt[e0 + u], u0 = (2 * r4 + 1) * g;
+                        const size_t og  = ((size_t)(e0 + u) * A.B + b) * A.primes * N + (size_t)i * N;
+#pragma unroll
+                        for (int e = 0; e < 16; e++)
+                        {
+                            acc0[u][e] = csub(csub(acc0[u][e], qi) + hoist_word<LOGN>(lds, u0, g, e >> 2, e & 3), qi);
+                            acc1[u][e] = csub(acc1[u][e], qi);
+                        }
+                        store_quads(A.out0 + og, acc0[u], te);
+                        store_quads(A.out1 + og, acc1[u], te);
+                    }
+            }
+            __syncthreads();   // the next pass's first transpose writes the plane the gather reads
+        }
+    }
+}
+
+hipError_t launch_ct_galois_hoist(const DevParams &P, const DevTables &T, const GaloisHoistArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t), park = (size_t)G::N * sizeof(uint32_t);
+        return A.sum ? launch(k_ct_galois_hoist<L, true>, grid, dim3(G::THREADS), plane, st, P, T, A)
+                     : launch(k_ct_galois_hoist<L, false>, grid, dim3(G::THREADS),
+                              plane + (kHoistPark<L, false> ? park : 0), st, P, T, A);
     });
 }
 

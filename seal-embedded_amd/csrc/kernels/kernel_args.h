@@ -217,6 +217,29 @@ struct GaloisArgs
     uint32_t elt;                   // odd, below 2n (checked by the host: the kernel forms LDS addresses from it)
 };
 hipError_t launch_ct_galois(const DevParams &, const DevTables &, const GaloisArgs &, hipStream_t);
+// Hoisted rotations (k_ct_galois_hoist): G rotations of every record from ONE digit decomposition of c1.  The digits
+// D_{j,t} are those of the canonical coefficients of INTT_j(c1[b][j]) itself; sigma is applied to the TRANSFORMED digits,
+// where it is the permutation src_g:
+//   rot0[g][b][i][k] = c0[b][i][src_g(k)] + sum_{j < primes, t < 2} NTT_i(D_{j,t})[src_g(k)] . key0_g[2j + t][i][k]
+//   rot1[g][b][i][k] =                      sum_{j < primes, t < 2} NTT_i(D_{j,t})[src_g(k)] . key1_g[2j + t][i][k].
+// Many form (sum = 0): out[e][b] = rot[elt[e]], outputs [G][B][primes][n].  Sum form (sum = 1): out[b] = add_input .
+// (c0, c1)[b] + sum_e rot[elt[e]], outputs [B][primes][n].  The elements and the key block of each travel in the
+// argument block (kernarg): no device table, no scratch.
+constexpr uint32_t kHoistMaxElts = 64;   // kMaxGaloisKeys (se_context.h)
+struct GaloisHoistArgs
+{
+    const uint32_t *c0, *c1;        // [B][primes][n]
+    uint32_t *out0, *out1;          // many: [G][B][primes][n]; sum: [B][primes][n]
+    size_t half;                    // words of one key half: R np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes)
+    uint32_t primes;                // 1 .. np
+    uint32_t G;                     // 1 .. kHoistMaxElts
+    uint32_t sum, add_input;        // 0 / 1 each; add_input only with sum
+    uint32_t elt[kHoistMaxElts];    // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kHoistMaxElts];   // the device key block of elt[e]
+};
+hipError_t launch_ct_galois_hoist(const DevParams &, const DevTables &, const GaloisHoistArgs &, hipStream_t);
 // Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words (rows a multiple of np) -> [rows][2][n]
 // (words, Shoup companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
 // slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =

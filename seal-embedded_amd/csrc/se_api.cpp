@@ -445,6 +445,22 @@ int se_amd_ct_galois_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_
     return ctx->c.ct_galois(d_c0, d_c1, B, primes, elt, d_out0, d_out1, as_stream(stream));
 }
 
+int se_amd_ct_galois_many_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                 const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois_hoist(d_c0, d_c1, B, primes, elts, G, false, false, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                const uint32_t *elts, size_t G, int add_input, uint32_t *d_out0, uint32_t *d_out1,
+                                void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois_hoist(d_c0, d_c1, B, primes, elts, G, true, add_input != 0, d_out0, d_out1,
+                                  as_stream(stream));
+}
+
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)
 {
     seamd::HostParams hp;

@@ -1574,6 +1574,54 @@ int Context::ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, siz
     return 0;
 }
 
+static_assert(kHoistMaxElts == kMaxGaloisKeys, "the argument block holds an installed set");
+
+// One launch, no scratch, no secret key, no host synchronisation; reads the installed Galois keys of elts[0 .. G).  The
+// checks of ct_galois in its order, the element check once per element; nothing is launched unless every element has a
+// key.  The key-block pointers travel in the argument block, so a call already enqueued keeps the blocks it was given.
+int Context::ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
+                             size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    GaloisHoistArgs ha{};
+    if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
+    if (!elts || G == 0 || G > kMaxGaloisKeys)
+    {
+        set_last_error("hoisted rotations: between 1 and 64 elements");
+        return kErrInvalid;
+    }
+    for (size_t e = 0; e < G; e++)
+        if (!(elts[e] & 1) || elts[e] >= 2 * hp.n)
+        {
+            set_last_error("Galois element " + std::to_string(elts[e]) + " is not odd and below 2n");
+            return kErrInvalid;
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t e = 0; e < G; e++)
+    {
+        size_t g = 0;
+        while (g < galois_elts.size() && galois_elts[g] != elts[e]) g++;
+        if (g == galois_elts.size())
+        {
+            set_last_error("no Galois key is installed for element " + std::to_string(elts[e]) +
+                           " (se_amd_set_galois_keys)");
+            return kErrNoKey;
+        }
+        ha.elt[e] = elts[e];
+        ha.key[e] = d_gk[g];
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    ha.c0        = d_c0;
+    ha.c1        = d_c1;
+    ha.out0      = d_out0;
+    ha.out1      = d_out1;
+    ha.G         = (uint32_t)G;
+    ha.sum       = sum;
+    ha.add_input = sum && add_input;
+    SEAMD_HIP(launch_ct_galois_hoist(dp, dt, ha, st));
+    return 0;
+}
+
 // Slices per output row of ct_lincomb.  A workgroup owns 1024 residues of one output row, so G rows give
 // G * slabs * row / 1024 workgroups: 24 for the whole-batch sum at 4096 x 3, on 256 compute units.  Rows are cut until
 // there are 8 workgroups (32 waves) per compute unit -- all resident at once, twice the 16 waves per CU at which a row

@@ -211,6 +211,11 @@ struct Context
     int set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1);
     int ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, uint32_t elt, uint32_t *d_out0,
                   uint32_t *d_out1, hipStream_t st);
+    // hoisted rotations (GaloisHoistArgs): G rotations of every record from one digit decomposition, each to its own
+    // output (sum false: outputs [G][B][primes][n]) or summed into one record, with the record itself when add_input
+    // (sum true: outputs [B][primes][n]); elts is a host pointer; one launch, no scratch
+    int ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
+                        size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
     int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
                    uint32_t *d_out1, hipStream_t st);

@@ -9,7 +9,12 @@ largest coefficient seen, and the slot errors against the rolled values of
   - a rotation of the fresh record at Delta (no lift),
   - lift by 2^30, one rotation (step 1), rescale,
   - lift by 2^30, four rotate-and-adds (steps 1, 2, 4, 8: every slot becomes the sum of 16), rescale,
-with the largest coefficient before each rescale.
+with the largest coefficient before each rescale; and the same for the hoisted form (se_amd_ct_galois_many_device /
+se_amd_ct_galois_sum_device), which decomposes c1 itself and permutes the transformed digits, so that
+  decrypt(rot0, rot1) = sigma(decrypt(c0, c1)) + sum_r sigma(D_r) * e_r  (D_r: digits of c1, sigma on the integers):
+  - its key-switch term for step 1,
+  - lift by 2^30, one hoisted rotation (step 1), rescale,
+  - lift by 2^30, the record plus its hoisted rotations by 1 .. 7 in one sum (every slot becomes the sum of 8), rescale.
   python tools/ct_galois_noise_sim.py [4096x3 8192x6 ...]"""
 import json
 import os
@@ -26,6 +31,7 @@ from ct_mul_noise_sim import DIGIT_BITS, ERR_SUPPORT, centred, crt_centred, deco
 
 LIFT = 1 << 30
 STEPS = (1, 2, 4, 8)
+WINDOW = tuple(range(1, 8))     # the hoisted sum of 8: the record and its rotations by 1 .. 7
 
 
 def sigma_coeff(a, g, q):
@@ -88,6 +94,44 @@ def galois(o, c0, c1, g, key):
     return out0, out1
 
 
+def src_table(n, g):
+    """sigma_g(x)[k] = x[src[k]] on a bit-reversed NTT-form row (se_amd_galois_table)."""
+    bits = n.bit_length() - 1
+
+    def brev(v):
+        r = np.zeros_like(v)
+        for b in range(bits):
+            r |= ((v >> b) & 1) << (bits - 1 - b)
+        return r
+
+    return brev((((2 * brev(np.arange(n, dtype=np.int64)) + 1) * g) % (2 * n) - 1) // 2)
+
+
+def galois_hoisted(o, c0, c1, elts, keys):
+    """The hoisted entries' definition on one record of L rows: the digits of c1 itself, transformed once per output
+    prime, then permuted by src_g and multiplied with the key of g, for every g of `elts`.  -> [(rot0, rot1)]."""
+    L = o.np
+    digs = []
+    for j in range(L):
+        c = o.intt(c1[j], j)
+        digs += [c & np.uint32((1 << DIGIT_BITS) - 1), c >> np.uint32(DIGIT_BITS)]
+    F = [[o.ntt(dig, i).astype(np.uint64) for dig in digs] for i in range(L)]
+    out = []
+    for g, (gk0, gk1) in zip(elts, keys):
+        src = src_table(o.n, g)
+        r0, r1 = [], []
+        for i in range(L):
+            q = np.uint64(o.q[i])
+            a0, a1 = c0[i][src].astype(np.uint64), np.zeros(o.n, dtype=np.uint64)
+            for r, f in enumerate(F[i]):
+                a0 = (a0 + (f[src] * gk0[r][i].astype(np.uint64)) % q) % q
+                a1 = (a1 + (f[src] * gk1[r][i].astype(np.uint64)) % q) % q
+            r0.append(a0.astype(np.uint32))
+            r1.append(a1.astype(np.uint32))
+        out.append((r0, r1))
+    return out
+
+
 def rescale(o, rows):
     L = len(rows)
     q_last = o.q[L - 1]
@@ -120,7 +164,7 @@ def simulate(n, L):
     ss, sd = V.bench_seeds(1, first=11)
     x = o.encrypt_sym(vals, ss[0].tobytes(), sd[0].tobytes(), sk)
     c0, c1 = [np.array(x["c0"][j]) for j in range(L)], [np.array(x["c1"][j]) for j in range(L)]
-    keys = {s: galois_key(o, sk, s_hat, pow(3, s, 2 * n), f"gsim-{s}") for s in STEPS}
+    keys = {s: galois_key(o, sk, s_hat, pow(3, s, 2 * n), f"gsim-{s}") for s in sorted(set(STEPS + WINDOW))}
     want1 = np.roll(vals.astype(np.float64), -1)
     g1 = pow(3, 1, 2 * n)
     # no lift: the key-switch term drowns a message at Delta
@@ -146,7 +190,25 @@ def simulate(n, L):
     big_sum = max(abs(int(v)) for v in value(o, a0, a1, s_hat))
     y = value(o, rescale(o, a0), rescale(o, a1), s_hat)
     err_sum = float(np.abs(decode(o, y, scale) - want).max())
-    return dict(n=n, primes=L, scale_bits=float(np.log2(o.scale)), q_last=q[last],
+    # the hoisted form: step 1 without a lift (its key-switch term), lifted and rescaled, and the sum of 8 in one pass
+    (h0, h1), = galois_hoisted(o, c0, c1, [g1], [keys[1]])
+    ks_h = value(o, h0, h1, s_hat) - sigma_int(y_in, g1)
+    (h0, h1), = galois_hoisted(o, l0, l1, [g1], [keys[1]])
+    big_h_one = max(abs(int(v)) for v in value(o, h0, h1, s_hat))
+    y = value(o, rescale(o, h0), rescale(o, h1), s_hat)
+    err_h_one = float(np.abs(decode(o, y, scale) - want1).max())
+    a0, a1 = l0, l1
+    want = vals.astype(np.float64)
+    for s, (h0, h1) in zip(WINDOW, galois_hoisted(o, l0, l1, [pow(3, s, 2 * n) for s in WINDOW], [keys[s] for s in WINDOW])):
+        a0, a1 = add_rows(o, a0, h0), add_rows(o, a1, h1)
+        want = want + np.roll(vals.astype(np.float64), -s)
+    big_h_sum = max(abs(int(v)) for v in value(o, a0, a1, s_hat))
+    y = value(o, rescale(o, a0), rescale(o, a1), s_hat)
+    err_h_sum = float(np.abs(decode(o, y, scale) - want).max())
+    hoisted = dict(key_switch_max=max(abs(int(v)) for v in ks_h),
+                   slot_error_lift_rotate_rescale=err_h_one, log2_max_coeff_one=float(np.log2(big_h_one)),
+                   slot_error_lift_sum_of_8_rescale=err_h_sum, log2_max_coeff_sum_of_8=float(np.log2(big_h_sum)))
+    return dict(n=n, primes=L, hoisted=hoisted, scale_bits=float(np.log2(o.scale)), q_last=q[last],
                 key_switch_bound=2 * L * n * ((1 << DIGIT_BITS) - 1) * ERR_SUPPORT,
                 key_switch_max=max(abs(int(v)) for v in ks),
                 slot_error_no_lift=err_plain,

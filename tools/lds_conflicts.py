@@ -123,3 +123,9 @@ for logn in (10,12,14):
                 sc+=conflicts([((64*w+l+th*e)*g)%n for l in range(64)],'w32')
                 ga+=conflicts([galois_src((w<<10)+((e>>2)<<8)+(l<<2)+(e&3),g,logn) for l in range(64)],'r32')
         print(logn,name,'scatter',sc,'gather',ga,'of',16*(th//64),'instructions')
+
+
+# ---- k_ct_galois_hoist (ct_ops.hip): every transformed digit is parked from tile layout 0 as it is, 4 x ds_write_b128 at
+# 16 t + 4 c (the unpadded row stride 16 of the table above), and gathered like sigma(c0) once per element
+print("k_ct_galois_hoist: extra cycles per wave to park one transformed digit (4 x ds_write_b128 at 16 t + 4 c):",
+      sum(wr_conf([16*l+4*c for l in range(64)]) for c in range(4)), "-- the gather per element and digit is k_ct_galois's above")
