@@ -545,6 +545,42 @@ int se_amd_ct_galois_many_device(se_amd_ctx *ctx, const uint32_t *d_c0, const ui
 int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                 const uint32_t *elts /*host, [G]*/, size_t G, int add_input, uint32_t *d_out0,
                                 uint32_t *d_out1, void *stream);
+/* Linear transforms: plaintext-weighted sums of hoisted rotations (the diagonal method),
+ *     y = d0 . x + sum_e d_e . rot_{elts[e]}(x)      slot-wise,
+ * an encrypted matrix-vector product by generalised diagonals, a convolution with arbitrary taps, the baby steps of a
+ * baby-step / giant-step product.  rot0 / rot1 are exactly those of the hoisted rotations above -- the digits of c1
+ * itself, the Galois keys installed when the plan was created, src_e = se_amd_galois_table(elts[e]) -- and the
+ * diagonals are plaintexts in the layout se_amd_encode_ntt_device writes.  For record b, i < primes, mod q_i, canonical:
+ *     out0[b][i][k] = d0[i][k] . c0[b][i][k] + sum_e d_e[i][k] . rot0[e][b][i][k]
+ *     out1[b][i][k] = d0[i][k] . c1[b][i][k] + sum_e d_e[i][k] . rot1[e][b][i][k]     (no d0 terms when d_diag0 is NULL)
+ * which fixes every bit: the result equals se_amd_ct_galois_many_device, then se_amd_ct_mul_plain_device per element,
+ * then the modular sum.  The scale is multiplied by the diagonals' scale, the level is unchanged; the key-switch term of
+ * element e is multiplied slot-wise by d_e, so relative to the result it is that of a rotation at the input's scale.
+ * The weight does not depend on the key row, so se_amd_lintrans_create folds d_e into a copy of the key block of
+ * elts[e] (words gk . d_e mod q_i with their Shoup companions) and a call costs ONE pass of the sum form, whatever G is,
+ * plus an epilogue: no [G][B][primes][n] scratch, no further passes over memory.
+ * se_amd_lintrans_create: elts is a HOST pointer to G odd elements below 2n, 1 <= G <= SE_AMD_MAX_GALOIS_KEYS, repeats
+ * allowed (each with its own diagonal); d_diag is DEVICE memory [G][pt_primes][n], d_diag0 DEVICE [pt_primes][n] or NULL
+ * (the weight of the record itself, the rotation by 0, which needs no key); pt_primes >= 1.  The plan serves the levels
+ * primes <= min(pt_primes, np).  Diagonal words are reduced mod q_i, so any 32-bit word is valid.  The call takes the
+ * context's lock, reads the diagonals and the installed key blocks and returns with everything complete (it
+ * synchronises): the plan is a SNAPSHOT, a later se_amd_set_galois_keys does not change it and the diagonals may be
+ * freed.  Device memory per plan: (G . 16 R np + (G + 1) . 8 np) n bytes, R = 2 np (4096 x 3, G = 7: 8.6 MiB;
+ * 16384 x 13, G = 7: 604.5 MiB -- 1.1 MiB resp. 84.5 MiB per element for the folded block, 96 KiB resp. 1.6 MiB per
+ * diagonal).  SE_ERR_INVALD_ARGUMENT for NULL elts / d_diag / out, G outside [1, 64], pt_primes = 0, an even element
+ * or one >= 2n, a diagonal pointer that is not 16-byte aligned; SE_ERR_NO_KEY when an element has no installed key
+ * (the last-error text names it).  A failed create leaves *out NULL and frees what it built.
+ * se_amd_lintrans_destroy: waits for the device, then frees; NULL is a no-op.  Destroy plans before their context.
+ * se_amd_ct_lintrans_device: d_out0, d_out1 are [B][primes][n].  One asynchronous launch, no scratch, no host
+ * synchronisation; outputs must not overlap the inputs.  SE_ERR_INVALD_ARGUMENT for the pointer, alignment, level and B
+ * checks of se_amd_ct_galois_device, then for a NULL plan, a plan of another context, or primes above the plan's
+ * levels.  Nothing is launched or written on an error.  B = 0 is a successful no-op. */
+typedef struct se_amd_lintrans se_amd_lintrans;
+int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts /*host, [G]*/, size_t G, const uint32_t *d_diag,
+                           const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out);
+void se_amd_lintrans_destroy(se_amd_lintrans *plan);
+int se_amd_ct_lintrans_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                              size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_gen_relin_key", "se_amd_set_relin_key", "se_amd_ct_relin_device",
     "se_amd_galois_element", "se_amd_galois_table", "se_amd_gen_galois_keys", "se_amd_set_galois_keys",
     "se_amd_ct_galois_device", "se_amd_ct_galois_many_device", "se_amd_ct_galois_sum_device",
+    "se_amd_lintrans_create", "se_amd_lintrans_destroy", "se_amd_ct_lintrans_device",
 )
 
 
@@ -167,6 +168,10 @@ def lib():
     L.se_amd_ct_galois_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp]
     L.se_amd_ct_galois_many_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
     L.se_amd_ct_galois_sum_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, i32, vp, vp, vp]
+    L.se_amd_lintrans_create.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(vp)]
+    L.se_amd_lintrans_destroy.argtypes = [vp]
+    L.se_amd_lintrans_destroy.restype = None
+    L.se_amd_ct_lintrans_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -315,6 +320,24 @@ class Group:
         _check(self.L.se_amd_encode_ntt_multi_device(
             self.h, C.c_size_t(B), self._arr(values), self._arr(out), self._arr(status), C.c_int(gather_root),
             _ptr(out_all)), "se_amd_encode_ntt_multi_device")
+
+
+class LintransPlan:
+    """Handle of se_amd_lintrans_create (Context.lintrans_plan)."""
+
+    def __init__(self, L, h):
+        self.L, self.h = L, h
+
+    def close(self):
+        if self.h:
+            self.L.se_amd_lintrans_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -687,6 +710,28 @@ class Context:
         _check(self.L.se_amd_ct_galois_sum_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el), el.size,
                                                   1 if add_input else 0, _ptr(out0), _ptr(out1), _stream_ptr()),
                "se_amd_ct_galois_sum_device")
+
+    def lintrans_plan(self, elts, diag, diag0=None, pt_primes=None):
+        """The plan of y = diag0 . x + sum_e diag[e] . rot_{elts[e]}(x): diag [G][pt_primes][n], diag0 [pt_primes][n] or
+        None, device tensors in the layout encode_ntt writes.  Folds the diagonals into the installed Galois keys of
+        `elts` (a snapshot; it synchronises) and returns an object with .close(); close it before the context."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if pt_primes is None:
+            pt_primes = diag.shape[1]
+        h = C.c_void_p()
+        _check(self.L.se_amd_lintrans_create(self.h, _ptr(el), el.size, _ptr(diag), _ptr(diag0), pt_primes,
+                                             C.byref(h)), "se_amd_lintrans_create")
+        return LintransPlan(self.L, h)
+
+    def ct_lintrans(self, plan, c0, c1, out0, out1, primes=None):
+        """One launch: the plan's weighted sum of hoisted rotations of the records (c0, c1) [B][primes][n] ->
+        (out0, out1) [B][primes][n]; the scale is multiplied by the diagonals' scale, the level is unchanged."""
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_lintrans_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
+                                                c0.shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_lintrans_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

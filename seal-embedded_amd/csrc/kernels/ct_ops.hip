@@ -3,7 +3,8 @@
 // (se_amd_ct_rescale_device), and the ciphertext products: the tensor (se_amd_ct_mul_device) and the relinearisation
 // that brings it back to two slabs (se_amd_ct_relin_device, with the key plumbing), and the slot rotation: a ring
 // automorphism fused with its key switch (se_amd_ct_galois_device), and its hoisted form, many rotations of a record
-// from one digit decomposition (se_amd_ct_galois_many_device, se_amd_ct_galois_sum_device, at the end of the file).
+// from one digit decomposition (se_amd_ct_galois_many_device, se_amd_ct_galois_sum_device, at the end of the file), and
+// the plaintext-weighted sum of hoisted rotations under a plan (se_amd_ct_lintrans_device, behind them).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -774,6 +775,66 @@ __device__ __forceinline__ void hoist_mac(uint32_t (&acc0)[16], uint32_t (&acc1)
     }
 }
 
+// The digit loop of a pass: for every input prime the coefficients of the c1 row, per digit its transform mod q_i parked
+// in the plane, and the share of every element of the pass (hoist_mac).  SUM: acc[0] serves all A.G elements; else
+// acc[u] is element e0 + u.  Args = GaloisHoistArgs, or LintransArgs (SUM, on folded key blocks).  Ends behind a barrier
+// with the plane free.
+template <int LOGN, bool SUM, int GC, class Args>
+__device__ __forceinline__ void hoist_digits(uint32_t (&acc0)[GC][16], uint32_t (&acc1)[GC][16], const Args &A,
+                                             size_t rec, uint32_t e0, uint32_t i, uint32_t qi, const uint32_t *rw,
+                                             uint32_t r4, const DevParams &P, const DevTables &T, uint32_t *lds, int t)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    for (uint32_t j = 0; j < A.primes; j++)
+    {
+        uint32_t x[16];
+        evk_row_coeffs<LOGN>(x, A.c1 + rec + (size_t)j * N, j, P, T, lds, opaque_index(t));
+        if constexpr (kHoistPark<LOGN, SUM>)
+        {
+            uint32_t *park = lds + G::SLOTS + opaque_index(t);   // one base register, immediate offsets
+#pragma unroll
+            for (int e = 0; e < 16; e++) park[G::THREADS * e] = x[e];
+        }
+        // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
+#pragma unroll 1
+        for (uint32_t dg = 0; dg < 2; dg++)
+        {
+            const int td         = opaque_index(t);
+            const uint32_t *park = lds + G::SLOTS + td;
+            uint32_t y[16];
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+            {
+                const uint32_t xe = kHoistPark<LOGN, SUM> ? park[G::THREADS * e] : x[e];
+                y[e]              = (xe >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
+            }
+            ntt_tiles<LOGN>(y, rw, qi, lds, td);
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                *reinterpret_cast<uint4 *>(lds + 16 * td + 4 * c) =
+                    make_uint4(y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]);
+            __syncthreads();
+            // the thread's first quad of row 2j + dg, column i of a key block
+            const size_t ko = ((size_t)(2 * j + dg) * A.np + i) * 2 * N + quad_index(td, 0);
+            if constexpr (SUM)
+            {
+#pragma unroll 1
+                for (uint32_t e = 0; e < A.G; e++)
+                    hoist_mac<LOGN>(acc0[0], acc1[0], lds, A.key[e] + ko, A.half, A.elt[e], r4, qi);
+            }
+            else
+            {
+#pragma unroll
+                for (int u = 0; u < GC; u++)
+                    if (e0 + u < A.G)
+                        hoist_mac<LOGN>(acc0[u], acc1[u], lds, A.key[e0 + u] + ko, A.half, A.elt[e0 + u], r4, qi);
+            }
+            __syncthreads();
+        }
+    }
+}
+
 template <int LOGN, bool SUM>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_hoist(const DevParams P, const DevTables T,
                                                                            const GaloisHoistArgs A)
@@ -801,53 +862,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_hoist(co
             for (int u = 0; u < GC; u++)
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc0[u][e] = acc1[u][e] = 0;
-            for (uint32_t j = 0; j < A.primes; j++)
-            {
-                uint32_t x[16];
-                evk_row_coeffs<LOGN>(x, A.c1 + rec + (size_t)j * N, j, P, T, lds, opaque_index(t));
-                if constexpr (kHoistPark<LOGN, SUM>)
-                {
-                    uint32_t *park = lds + G::SLOTS + opaque_index(t);   // one base register, immediate offsets
-#pragma unroll
-                    for (int e = 0; e < 16; e++) park[G::THREADS * e] = x[e];
-                }
-                // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
-#pragma unroll 1
-                for (uint32_t dg = 0; dg < 2; dg++)
-                {
-                    const int td         = opaque_index(t);
-                    const uint32_t *park = lds + G::SLOTS + td;
-                    uint32_t y[16];
-#pragma unroll
-                    for (int e = 0; e < 16; e++)
-                    {
-                        const uint32_t xe = kHoistPark<LOGN, SUM> ? park[G::THREADS * e] : x[e];
-                        y[e]              = (xe >> (kRelinDigitBits * dg)) & ((1u << kRelinDigitBits) - 1);
-                    }
-                    ntt_tiles<LOGN>(y, rw, qi, lds, td);
-#pragma unroll
-                    for (int c = 0; c < 4; c++)
-                        *reinterpret_cast<uint4 *>(lds + 16 * td + 4 * c) =
-                            make_uint4(y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]);
-                    __syncthreads();
-                    // the thread's first quad of row 2j + dg, column i of a key block
-                    const size_t ko = ((size_t)(2 * j + dg) * A.np + i) * 2 * N + quad_index(td, 0);
-                    if constexpr (SUM)
-                    {
-#pragma unroll 1
-                        for (uint32_t e = 0; e < A.G; e++)
-                            hoist_mac<LOGN>(acc0[0], acc1[0], lds, A.key[e] + ko, A.half, A.elt[e], r4, qi);
-                    }
-                    else
-                    {
-#pragma unroll
-                        for (int u = 0; u < GC; u++)
-                            if (e0 + u < A.G)
-                                hoist_mac<LOGN>(acc0[u], acc1[u], lds, A.key[e0 + u] + ko, A.half, A.elt[e0 + u], r4, qi);
-                    }
-                    __syncthreads();
-                }
-            }
+            hoist_digits<LOGN, SUM, GC>(acc0, acc1, A, rec, e0, i, qi, rw, r4, P, T, lds, t);
             // the c0 row of output prime i as it lies in memory goes into the plane, word k at lds[k]; gathered per element
             const int te   = opaque_index(t);
             const size_t o = rec + (size_t)i * N;
@@ -919,6 +934,156 @@ hipError_t launch_ct_galois_hoist(const DevParams &P, const DevTables &T, const 
                      : launch(k_ct_galois_hoist<L, false>, grid, dim3(G::THREADS),
                               plane + (kHoistPark<L, false> ? park : 0), st, P, T, A);
     });
+}
+
+// ------------------------------------------------------------------------------------------
+// Linear transform (se_amd_ct_lintrans_device): the diagonal method  out = d0 . (c0, c1) + sum_e d_e . rot[elt[e]]  with
+// the hoisted rotations above and one plaintext row d_e per entry.  The sum form keeps ONE accumulator pair because its
+// loop is digit outside, element inside; a weight applied after the digit sum would need a pair per element.  But d_e
+// does not depend on the key row:
+//   d_e[k] . sum_r F_r[src_e(k)] . gk_e[r][i][k]  =  sum_r F_r[src_e(k)] . (d_e[k] . gk_e[r][i][k])   mod q_i,
+// so the plan holds key blocks with d_e folded in (k_lintrans_fold below) and the digit loop is hoist_digits<SUM> as it
+// is: the same grid, thread shape, LDS plane and lazy ranges.  Only the c0 term carries d_e itself.  Epilogue, with the
+// c0 row parked in the plane: c = d0 . c0 (or 0), then per entry c += sigma_e(c0) . d_e, every product a Shoup product
+// in [0, 2 q_i) added to c in [0, 2 q_i) and brought back below 2 q_i; out0 = canon4(acc0 + c).  out1 = acc1 (+ d0 . c1).
+// mul_shoup_lazy takes any 32-bit word of a slab; the diagonal words are canonical (the fold kernel reduced them).
+// ------------------------------------------------------------------------------------------
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_lintrans(const DevParams P, const DevTables T,
+                                                                       const LintransArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
+    const uint32_t r4  = __brev((uint32_t)quad_index(t, 0)) >> (32 - LOGN);
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        uint32_t acc0[1][16], acc1[1][16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[0][e] = acc1[0][e] = 0;
+        hoist_digits<LOGN, true, 1>(acc0, acc1, A, rec, 0u, i, qi, rw, r4, P, T, lds, t);
+        const int te   = opaque_index(t);
+        const size_t o = rec + (size_t)i * N;
+        const int k4   = quad_index(te, 0);
+        // the thread's first quad of the (word, Shoup) rows of column i: entry e is e np 2 n further
+        const size_t dcol     = (size_t)i * 2 * N + k4;
+        const uint32_t *diag0 = A.diag0 ? A.diag0 + dcol : nullptr;
+        uint32_t c[16];
+        load_quads(c, A.c0 + o, te);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+            *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+        __syncthreads();
+        if (diag0)
+        {
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+            {
+                const uint4 w = *reinterpret_cast<const uint4 *>(diag0 + (m << 8));
+                const uint4 s = *reinterpret_cast<const uint4 *>(diag0 + N + (m << 8));
+                const uint32_t wv[4] = {w.x, w.y, w.z, w.w}, sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+                for (int k = 0; k < 4; k++) c[4 * m + k] = mul_shoup_lazy(c[4 * m + k], wv[k], sv[k], qi);
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int e = 0; e < 16; e++) c[e] = 0;
+        }
+#pragma unroll 1
+        for (uint32_t e = 0; e < A.G; e++)
+        {
+            const uint32_t g = A.elt[e], u0 = (2 * r4 + 1) * g;
+            const uint32_t *d = A.diag + (size_t)e * A.np * 2 * N + dcol;
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+            {
+                const uint4 w = *reinterpret_cast<const uint4 *>(d + (m << 8));
+                const uint4 s = *reinterpret_cast<const uint4 *>(d + N + (m << 8));
+                const uint32_t wv[4] = {w.x, w.y, w.z, w.w}, sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                {
+                    const uint32_t v = c[4 * m + k] + mul_shoup_lazy(hoist_word<LOGN>(lds, u0, g, m, k), wv[k], sv[k], qi);
+                    c[4 * m + k]     = min(v, v - two_qi);
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[0][e] = canon4(acc0[0][e] + c[e], qi, two_qi);
+        store_quads(A.out0 + o, acc0[0], te);
+        if (diag0)
+        {
+            load_quads(c, A.c1 + o, te);
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+            {
+                const uint4 w = *reinterpret_cast<const uint4 *>(diag0 + (m << 8));
+                const uint4 s = *reinterpret_cast<const uint4 *>(diag0 + N + (m << 8));
+                const uint32_t wv[4] = {w.x, w.y, w.z, w.w}, sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    acc1[0][4 * m + k] += mul_shoup_lazy(c[4 * m + k], wv[k], sv[k], qi);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc1[0][e] = canon4(acc1[0][e], qi, two_qi);
+        store_quads(A.out1 + o, acc1[0], te);
+        __syncthreads();   // the next record's first transpose writes the plane the gather reads
+    }
+}
+
+hipError_t launch_ct_lintrans(const DevParams &P, const DevTables &T, const LintransArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        return launch(k_ct_lintrans<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// Plan set-up: one thread per key word of an installed block [2][R][np][2][n], or per diagonal word when there is no
+// block (the weight of the record itself).  d = the diagonal word of the thread's column and position reduced mod q_i
+// (any 32-bit word is valid input; columns i >= pt have no diagonal and get 0); the thread of half 0, row 0 also writes
+// the (d, Shoup) pair of its position.
+__global__ __launch_bounds__(kLcThreads) void k_lintrans_fold(const DevParams P, const uint32_t *__restrict__ key_in,
+                                                           uint32_t *__restrict__ key_out,
+                                                           const uint32_t *__restrict__ diag_in,
+                                                           uint32_t *__restrict__ pair_out, uint32_t pt, size_t words)
+{
+    const size_t k = (size_t)blockIdx.x * kLcThreads + threadIdx.x;
+    if (k >= words) return;
+    const size_t col   = k >> P.logn, c = k & (P.n - 1);   // col = (half R + row) np + i
+    const uint32_t i   = (uint32_t)(col % P.nprimes);
+    const uint32_t q   = P.q[i];
+    const uint32_t d   = i < pt ? diag_in[((size_t)i << P.logn) + c] % q : 0;
+    if (col < P.nprimes)
+    {
+        pair_out[((2 * col) << P.logn) + c]     = d;
+        pair_out[((2 * col + 1) << P.logn) + c] = (uint32_t)(((uint64_t)d << 32) / q);
+    }
+    if (!key_in) return;
+    const uint32_t w = barrett64((uint64_t)key_in[((2 * col) << P.logn) + c] * d, q, P.cr_hi[i], P.cr_lo[i]);
+    key_out[((2 * col) << P.logn) + c]     = w;
+    key_out[((2 * col + 1) << P.logn) + c] = (uint32_t)(((uint64_t)w << 32) / q);
+}
+
+hipError_t launch_lintrans_fold(const DevParams &P, const uint32_t *key_in, uint32_t *key_out, const uint32_t *diag_in,
+                                uint32_t *pair_out, uint32_t pt, hipStream_t st)
+{
+    const size_t words = ((size_t)(key_in ? 4 * P.nprimes : 1) * P.nprimes) << P.logn;   // 2 halves of R = 2 np rows
+    return launch(k_lintrans_fold, dim3((unsigned)(words / kLcThreads)), dim3(kLcThreads), 0, st, P, key_in, key_out,
+                  diag_in, pair_out, pt, words);
 }
 
 // The diagonal term of an evaluation key on the [R][np][n] slab the public-key chain wrote:

@@ -240,6 +240,31 @@ struct GaloisHoistArgs
     const uint32_t *key[kHoistMaxElts];   // the device key block of elt[e]
 };
 hipError_t launch_ct_galois_hoist(const DevParams &, const DevTables &, const GaloisHoistArgs &, hipStream_t);
+// Linear transform (k_ct_lintrans): the sum form above with a plaintext weight per element, the diagonal method
+//   out0[b][i][k] = d0[i][k] c0[b][i][k] + sum_e d_e[i][k] rot0[elt[e]][b][i][k]   (out1: c1 and rot1)   mod q_i.
+// d_e does not depend on the key row, so it is folded into the key block when the plan is made (k_lintrans_fold):
+// key[e] holds gk . d_e mod q_i with its Shoup companions in the installed block's layout, and the digit loop is the sum
+// form's.  Only the epilogue carries weights: the (word, Shoup) rows diag[e][np][2][n], and diag0 [np][2][n] or NULL.
+struct LintransArgs
+{
+    const uint32_t *c0, *c1;        // [B][primes][n]
+    uint32_t *out0, *out1;          // [B][primes][n]
+    size_t half;                    // words of one key half: R np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes)
+    uint32_t primes;                // 1 .. the plan's levels
+    uint32_t G;                     // 1 .. kHoistMaxElts
+    const uint32_t *diag;           // [G][np][2][n]
+    const uint32_t *diag0;          // [np][2][n], or NULL: the record itself does not enter
+    uint32_t elt[kHoistMaxElts];    // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kHoistMaxElts];   // the folded key block of entry e
+};
+hipError_t launch_ct_lintrans(const DevParams &, const DevTables &, const LintransArgs &, hipStream_t);
+// Plan set-up (k_lintrans_fold), one entry per launch.  d = diag_in[i][k] mod q_i for columns i < pt, 0 beyond (any
+// 32-bit word is valid input).  pair_out [np][2][n] = (d, its Shoup companion); with key_in (an installed block
+// [2][R][np][2][n]), key_out = the block of the words key_in . d mod q_i and their companions.  key_in NULL: pairs only.
+hipError_t launch_lintrans_fold(const DevParams &, const uint32_t *key_in, uint32_t *key_out, const uint32_t *diag_in,
+                                uint32_t *pair_out, uint32_t pt, hipStream_t);
 // Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words (rows a multiple of np) -> [rows][2][n]
 // (words, Shoup companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
 // slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =

@@ -461,6 +461,38 @@ int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uin
                                   as_stream(stream));
 }
 
+int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *d_diag,
+                           const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !out) return SE_ERR_INVALD_ARGUMENT;
+    se_amd_lintrans *h = new (std::nothrow) se_amd_lintrans();
+    if (!h) return SE_ERR_NO_MEMORY;
+    const int rc = ctx->c.lintrans_create(elts, G, d_diag, d_diag0, pt_primes, h->p);
+    if (rc != 0)
+    {
+        delete h;   // the buffers of a plan half built went with the local it was built in
+        return rc;
+    }
+    *out = h;
+    return SE_SUCCESS;
+}
+
+void se_amd_lintrans_destroy(se_amd_lintrans *plan)
+{
+    if (!plan) return;
+    // the kernels of calls still enqueued read the plan's blocks: drain the device before they are freed
+    if (hipSetDevice(plan->p.device) == hipSuccess) (void)hipDeviceSynchronize();
+    delete plan;
+}
+
+int se_amd_ct_lintrans_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                              size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_lintrans(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, as_stream(stream));
+}
+
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)
 {
     seamd::HostParams hp;

@@ -1622,6 +1622,95 @@ int Context::ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t 
     return 0;
 }
 
+// The plan of a linear transform.  Argument checks first, then under `mu`: every element needs an installed key (the
+// blocks are read, not kept); one fold launch per entry and one for d0, then a synchronisation, so the caller's
+// diagonals and the installed blocks may go once this returns.  Anything refused leaves `plan` empty.
+int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_diag, const uint32_t *d_diag0,
+                             size_t pt_primes, LintransPlan &plan)
+{
+    const size_t n = hp.n, np = hp.nprimes;
+    if (!elts || !d_diag || G == 0 || G > kMaxGaloisKeys || pt_primes == 0 || !aligned16({d_diag, d_diag0}))
+    {
+        set_last_error("linear transform: between 1 and 64 elements, pt_primes >= 1, 16-byte aligned diagonals");
+        return kErrInvalid;
+    }
+    for (size_t e = 0; e < G; e++)
+        if (!(elts[e] & 1) || elts[e] >= 2 * n)
+        {
+            set_last_error("Galois element " + std::to_string(elts[e]) + " is not odd and below 2n");
+            return kErrInvalid;
+        }
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<size_t> at(G);
+    for (size_t e = 0; e < G; e++)
+    {
+        size_t g = 0;
+        while (g < galois_elts.size() && galois_elts[g] != elts[e]) g++;
+        if (g == galois_elts.size())
+        {
+            set_last_error("no Galois key is installed for element " + std::to_string(elts[e]) +
+                           " (se_amd_set_galois_keys)");
+            return kErrNoKey;
+        }
+        at[e] = g;
+    }
+    SEAMD_HIP(hipSetDevice(device));
+    const size_t levels = pt_primes < np ? pt_primes : np, pairs = np * 2 * n, block = 4 * np * pairs;
+    LintransPlan built;
+    built.keys.resize(G);
+    SEAMD_HIP(built.diag.grow((G + 1) * pairs));
+    for (size_t e = 0; e < G; e++)
+    {
+        SEAMD_HIP(built.keys[e].grow(block));
+        SEAMD_HIP(launch_lintrans_fold(dp, d_gk[at[e]], built.keys[e], d_diag + e * pt_primes * n,
+                                       built.diag + e * pairs, (uint32_t)levels, nullptr));
+    }
+    if (d_diag0)
+        SEAMD_HIP(launch_lintrans_fold(dp, nullptr, nullptr, d_diag0, built.diag + G * pairs, (uint32_t)levels, nullptr));
+    SEAMD_HIP(hipDeviceSynchronize());
+    built.owner  = this;
+    built.device = device;
+    built.levels = levels;
+    built.diag0  = d_diag0 != nullptr;
+    built.elts.assign(elts, elts + G);
+    plan = std::move(built);
+    return 0;
+}
+
+// One launch, no scratch, no host synchronisation, nothing of the context but its tables: the plan owns what the kernel
+// reads.  The checks of ct_galois first, then the plan's.
+int Context::ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                         uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    LintransArgs la{};
+    if (!evk_call_args(la, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
+    if (!plan || plan->owner != this || primes > plan->levels)
+    {
+        set_last_error(!plan ? "linear transform: no plan"
+                             : plan->owner != this ? "linear transform: the plan belongs to another context"
+                                                   : "linear transform: the plan's diagonals have fewer primes than the call");
+        return kErrInvalid;
+    }
+    if (B == 0) return 0;
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    const size_t G = plan->elts.size(), pairs = hp.nprimes * 2 * hp.n;
+    la.c0    = d_c0;
+    la.c1    = d_c1;
+    la.out0  = d_out0;
+    la.out1  = d_out1;
+    la.G     = (uint32_t)G;
+    la.diag  = plan->diag;
+    la.diag0 = plan->diag0 ? plan->diag + G * pairs : nullptr;
+    for (size_t e = 0; e < G; e++)
+    {
+        la.elt[e] = plan->elts[e];
+        la.key[e] = plan->keys[e];
+    }
+    SEAMD_HIP(launch_ct_lintrans(dp, dt, la, st));
+    return 0;
+}
+
 // Slices per output row of ct_lincomb.  A workgroup owns 1024 residues of one output row, so G rows give
 // G * slabs * row / 1024 workgroups: 24 for the whole-batch sum at 4096 x 3, on 256 compute units.  Rows are cut until
 // there are 8 workgroups (32 waves) per compute unit -- all resident at once, twice the 16 waves per CU at which a row

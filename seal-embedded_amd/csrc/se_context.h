@@ -27,6 +27,21 @@ constexpr size_t kMaxGaloisKeys = 64;  // elements of one installed set (SE_AMD_
 constexpr int kStageCount = 6;  // cbd, uniform, ternary, encode_encrypt (fused), encode_rns, ntt_fuse
 
 struct HostPipe;
+struct Context;
+
+// A linear transform y = d0 . x + sum_e d_e . rot_e(x) made ready (se_amd_lintrans_create): per entry the installed Galois
+// key block with the diagonal folded in, and the diagonals themselves as (word, Shoup) rows for the c0 term.  A snapshot:
+// nothing of it refers to the context's installed keys afterwards.  Freed with the device of `owner` current.
+struct LintransPlan
+{
+    const Context *owner = nullptr;   // compared, never dereferenced
+    int device           = 0;
+    size_t levels        = 0;       // min(pt_primes, np): the calls it serves have primes <= levels
+    bool diag0           = false;
+    std::vector<uint32_t> elts;
+    std::vector<DevBuf<uint32_t>> keys;   // per entry [2][R][np][2][n]
+    DevBuf<uint32_t> diag;                // [G + 1][np][2][n]; the last one is d0 (unused without diag0)
+};
 
 struct StageEvent
 {
@@ -216,6 +231,12 @@ struct Context
     // (sum true: outputs [B][primes][n]); elts is a host pointer; one launch, no scratch
     int ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
                         size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    // linear transforms (LintransArgs): the plan folds device diagonals [G][pt_primes][n] (+ d_diag0 [pt_primes][n] or
+    // NULL) into the installed Galois keys of elts (host) and synchronises; a call is one launch, no scratch
+    int lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_diag, const uint32_t *d_diag0,
+                        size_t pt_primes, LintransPlan &plan);
+    int ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                    uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
     int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
                    uint32_t *d_out1, hipStream_t st);
@@ -291,6 +312,10 @@ int hip_fail(hipError_t e, const char *what);
 struct se_amd_ctx
 {
     seamd::Context c;
+};
+struct se_amd_lintrans
+{
+    seamd::LintransPlan p;
 };
 
 #define SEAMD_HIP(call)                                             \

@@ -1,0 +1,492 @@
+"""Linear transforms (-m gpu): se_amd_lintrans_create / se_amd_ct_lintrans_device, plaintext-weighted sums of hoisted
+rotations (the diagonal method) under a plan that holds the diagonals folded into the Galois keys.
+Every expectation is written from the definition with the oracle's primitives (ntt, intt,
+decrypt, fft, expand_ternary, encode_ntt_batch), se_amd_galois_table -- a host-only entry pinned against the
+coefficient-domain automorphism by tests/test_ct_galois_build.py -- and Python / NumPy integers, never from the device
+code under test:
+    D_{j,t}          = digits_of(c1)                                  (of c1 itself, not of sigma(c1))
+    rot0[e][b][i][k] = c0[b][i][src_e(k)] + sum_r NTT_i(D_r)[src_e(k)] . gk0_e[r][i][k]   mod q_i
+    rot1[e][b][i][k] =                      sum_r NTT_i(D_r)[src_e(k)] . gk1_e[r][i][k]   mod q_i
+    out0[b][i][k]    = d0[i][k] . c0[b][i][k] + sum_e d_e[i][k] . rot0[e][b][i][k]        mod q_i   (out1: c1, rot1)
+with the keys installed when the plan was created, any 32-bit word of a diagonal standing for its residue.
+Every comparison is bit-exact except the reference's own acceptance criterion |values - expected| < 0.1
+(device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below Oracle(n, L)."""
+import ctypes as C
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import vectors as V
+from gpu_support import (DIGIT_MASK, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches,  # noqa: F401
+                         build_example, dev_t, digits_of, encrypt_sym, env, expectation, host_u32, keyed_cases,
+                         rand_slab, rescale_expect, run_decrypt, sentinel_out, stream_of, take)
+
+pytestmark = pytest.mark.gpu
+
+
+# ---- the definition ---------------------------------------------------------------------------------------------------
+def hoist_expect(pkg, o, c0, c1, elts, key_of, gk0, gk1):
+    """rot0, rot1 uint32 [G][B][L][n] for the call elements `elts`; key_of[g] is the row of g in gk0 / gk1
+    [keys][R][np][n].  uint64 arithmetic: a product is below 2^60 and is reduced before it is added."""
+    B, L, n = c0.shape
+    srcs = [pkg.galois_table(n, g).astype(np.int64) for g in elts]
+    out0 = np.zeros((len(elts), B, L, n), dtype=np.uint32)
+    out1 = np.zeros_like(out0)
+    for b in range(B):
+        D = digits_of(o, c1[b], L)
+        for i in range(L):
+            q = np.uint64(o.q[i])
+            F = [o.ntt(dig, i).astype(np.uint64) for dig in D]
+            for e, (g, src) in enumerate(zip(elts, srcs)):
+                k0, k1 = gk0[key_of[g]], gk1[key_of[g]]
+                acc0, acc1 = c0[b, i][src].astype(np.uint64), np.zeros(n, dtype=np.uint64)
+                for r, f in enumerate(F):
+                    acc0 = (acc0 + (f[src] * k0[r, i].astype(np.uint64)) % q) % q
+                    acc1 = (acc1 + (f[src] * k1[r, i].astype(np.uint64)) % q) % q
+                out0[e, b, i], out1[e, b, i] = acc0, acc1
+    return out0, out1
+
+
+def weighted_sum(o, rot, diag, c=None, diag0=None):
+    """sum_e (diag[e] mod q) . rot[e] (+ (diag0 mod q) . c) mod q_i: rot uint32 [G][B][L][n], diag [G][>= L][n] of any
+    32-bit words, c [B][L][n], diag0 [>= L][n].  A product of residues is below 2^60; reduced before it is added."""
+    G, B, L, n = rot.shape
+    qv = np.array(o.q[:L], dtype=np.uint64)[None, :, None]
+    acc = np.zeros((B, L, n), dtype=np.uint64)
+    for e in range(G):
+        acc = (acc + (rot[e].astype(np.uint64) * (diag[e, :L].astype(np.uint64)[None] % qv)) % qv) % qv
+    if diag0 is not None:
+        acc = (acc + (c.astype(np.uint64) * (diag0[:L].astype(np.uint64)[None] % qv)) % qv) % qv
+    return acc.astype(np.uint32)
+
+
+def lintrans_expect(o, rot, diag, c0, c1, diag0):
+    return weighted_sum(o, rot[0], diag, c0, diag0), weighted_sum(o, rot[1], diag, c1, diag0)
+
+
+def run_plan(env, ctx, plan, c0, c1, primes):
+    """One plan call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_lintrans(plan, c0, c1, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "lintrans out0"), take(out1, words, (B, primes, n), "lintrans out1")
+
+
+def run_many(env, ctx, c0, c1, elts, primes):
+    B, n, G = c0.shape[0], ctx.n, len(elts)
+    words = G * B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois_many(c0, c1, elts, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    shape = (G, B, primes, n)
+    return take(out0, words, shape, "many out0"), take(out1, words, shape, "many out1")
+
+
+# ---- tests 1 to 3: the definition on arbitrary slabs, keys and diagonals --------------------------------------------
+def edge_row(o, j, rng, elts):
+    """The edge row of the hoist tests: NTT form of natural-order coefficients that hold both sides of the digit
+    boundary, 0, 1 and q - 1, each on an index whose image is negated and on one whose image is kept, for every element
+    that keeps more than one index."""
+    n, q = o.n, o.q[j]
+    edges = np.array([0, 1, DIGIT_MASK, DIGIT_MASK + 1, DIGIT_MASK + 2, q - 1], dtype=np.uint32)
+    c = rng.integers(1, q, n, dtype=np.uint32)
+    for start in (0, n // 9, n // 5, n // 3, n // 2, n - 13):
+        c[start:start + 6] = c[start + 7:start + 13] = edges
+    for g in elts:
+        _, neg = V.galois_image(n, g)
+        for v in edges:
+            at = c == v
+            assert (at & neg).any(), (g, int(v))
+            assert (at & ~neg).any() or g == 2 * n - 1, (g, int(v))
+    assert c[0] == 0
+    row = o.ntt(c, j)
+    assert (o.intt(row, j) == c).all()
+    return row
+
+
+GALOIS_CASES = [((1024, 1), (1,), 3), ((4096, 3), (3, 2), 3), ((16384, 13), (13,), 2)]    # those of the rotation tests
+CASE_IDS = lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v)  # noqa: E731
+
+
+def call_elements(n, npr):
+    """4096 x 3: the seven of the hoist tests, 3^5 listed twice (it carries two different diagonals).  Elsewhere G = 3."""
+    if (n, npr) == (4096, 3):
+        elts = [3, pow(3, -1, 2 * n), pow(3, 5, 2 * n), n + 1, 2 * n - 1, 9, pow(3, 5, 2 * n)]
+        assert len(set(elts)) == len(elts) - 1
+        return elts
+    return [3, n + 1, 2 * n - 1]
+
+
+def random_keys(rng, q, count, n, npr):
+    R = 2 * npr
+    gk0 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in range(count)])
+    gk1 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in range(count)])
+    gk0[0, 0, 0, :4] = [0, 1, q[0] - 1, q[0] - 1]
+    return gk0, gk1
+
+
+def random_diagonals(rng, q, G, n):
+    """[G][np][n] random residues; the last prime row of the last diagonal holds arbitrary 32-bit words >= q_i; every
+    diagonal holds 0, 1, q - 1 at the positions 0, 1, 2 and n - 3 .. n - 1 of every prime row.  And a d0 [np][n]."""
+    npr = len(q)
+    diag = rand_slab(rng, q, G, n)
+    diag0 = rand_slab(rng, q, 1, n)[0]
+    diag[G - 1, npr - 1] = rng.integers(q[npr - 1], 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    diag[G - 1, npr - 1, 3:5] = [q[npr - 1], 0xFFFFFFFF]
+    diag0[0, 5] = 0xFFFFFFFF
+    for i in range(npr):
+        for d in list(diag) + [diag0]:
+            d[i, :3] = d[i, n - 3:] = [0, 1, q[i] - 1]
+    return diag, diag0
+
+
+@pytest.fixture(scope="module")
+def slab_cases(env):
+    """slab_cases(shape, levels, B) -> the context with random key words installed (no secret key), the diagonals, and
+    per level the slabs with the expectation of the hoisted rotations of every call element -- computed once and shared
+    by tests 1 to 3."""
+    from oracle.pyoracle import Oracle
+    cache = {}
+
+    def get(shape, levels, B):
+        if shape in cache:
+            return cache[shape]
+        n, npr = shape
+        o = Oracle(n, npr)
+        ctx = env["pkg"].Context(n, npr)
+        q = o.q
+        rng = np.random.default_rng(43 * n + npr)
+        elts = call_elements(n, npr)
+        keys = sorted(set(elts))
+        key_of = {g: k for k, g in enumerate(keys)}
+        gk0, gk1 = random_keys(rng, q, len(keys), n, npr)
+        ctx.set_galois_keys(keys, gk0, gk1)
+        diag, diag0 = random_diagonals(rng, q, len(elts), n)
+        per_level = {}
+        for L in levels:
+            c0, c1 = rand_slab(rng, q, B, n, L), rand_slab(rng, q, B, n, L)
+            for j in range(L):
+                c1[0, j] = edge_row(o, j, rng, elts)
+            c0[1] = c1[1] = (np.array(q[:L], dtype=np.uint32) - 1)[:, None]
+            rot = hoist_expect(env["pkg"], o, c0, c1, elts, key_of, gk0, gk1)
+            per_level[L] = dict(c0=c0, c1=c1, d0=dev_t(env, c0), d1=dev_t(env, c1), rot=rot)
+        cache[shape] = dict(ctx=ctx, o=o, elts=elts, keys=keys, key_of=key_of, gk=(gk0, gk1), diag=diag, diag0=diag0,
+                            t_diag=dev_t(env, diag), t_diag0=dev_t(env, diag0), levels=per_level)
+        return cache[shape]
+
+    yield get
+    for c in cache.values():
+        c["ctx"].close()
+
+
+@pytest.mark.parametrize("shape,levels,B", GALOIS_CASES, ids=CASE_IDS)
+def test_plan_call_matches_the_definition(env, slab_cases, shape, levels, B):
+    """Test 1: random residues for both slabs, the installed keys and the diagonals; one diagonal row of arbitrary 32-bit
+    words >= q_i, 0 / 1 / q - 1 at fixed positions of every diagonal; record 0 of c1 is the edge row of the hoist tests,
+    record 1 all q_j - 1.  With and without diag0, G = 1 and the full list (at 4096 x 3 one element twice with two
+    diagonals); the level-2 call runs on the plans built with pt_primes = 3; a plan with pt_primes = 2 refuses level 3.
+    Bit for bit, sentinels behind the outputs intact (run_plan)."""
+    case = slab_cases(shape, levels, B)
+    o, ctx, elts, n, npr = case["o"], case["ctx"], case["elts"], shape[0], shape[1]
+    for G in (1, len(elts)):
+        for with0 in (False, True):
+            plan = ctx.lintrans_plan(elts[:G], case["t_diag"][:G].contiguous(), case["t_diag0"] if with0 else None)
+            for L in levels:
+                lv = case["levels"][L]
+                want = lintrans_expect(o, (lv["rot"][0][:G], lv["rot"][1][:G]), case["diag"][:G], lv["c0"], lv["c1"],
+                                       case["diag0"] if with0 else None)
+                got = run_plan(env, ctx, plan, lv["d0"], lv["d1"], L)
+                assert (got[0] == want[0]).all(), (G, with0, L, "out0")
+                assert (got[1] == want[1]).all(), (G, with0, L, "out1")
+            plan.close()
+    if npr == 3:
+        lv = case["levels"][3]
+        short = ctx.lintrans_plan(elts, dev_t(env, case["diag"][:, :2]), dev_t(env, case["diag0"][:2]))
+        out0, out1 = sentinel_out(env, B * 3 * n, 0), sentinel_out(env, B * 3 * n, 0)
+        with pytest.raises(env["pkg"].SealEmbeddedAmdError, match="-22"):
+            ctx.ct_lintrans(short, lv["d0"], lv["d1"], out0, out1, primes=3)
+        env["torch"].cuda.synchronize()
+        assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+        l2 = case["levels"][2]
+        want = lintrans_expect(o, l2["rot"], case["diag"], l2["c0"], l2["c1"], case["diag0"])
+        got = run_plan(env, ctx, short, l2["d0"], l2["d1"], 2)
+        assert (got[0] == want[0]).all() and (got[1] == want[1]).all(), "pt_primes = 2 at level 2"
+        short.close()
+
+
+@pytest.mark.parametrize("shape,levels,B", GALOIS_CASES, ids=CASE_IDS)
+def test_plan_call_is_the_composition_on_the_device(env, slab_cases, shape, levels, B):
+    """Test 2: on the slabs of test 1, ONE many-form call, then one ct_mul_plain per element and one for diag0 (the
+    diagonals reduced mod q_i, which is what a plaintext holds), summed mod q_i in NumPy: equal to the plan call bit for
+    bit."""
+    torch = env["torch"]
+    case = slab_cases(shape, levels, B)
+    o, ctx, elts, n = case["o"], case["ctx"], case["elts"], shape[0]
+    G = len(elts)
+    qv = np.array(o.q, dtype=np.uint64)[:, None]
+    red = (case["diag"].astype(np.uint64) % qv[None]).astype(np.uint32)
+    red0 = (case["diag0"].astype(np.uint64) % qv).astype(np.uint32)
+    plan = ctx.lintrans_plan(elts, case["t_diag"], case["t_diag0"])
+    for L in levels:
+        lv = case["levels"][L]
+        m0, m1 = run_many(env, ctx, lv["d0"], lv["d1"], elts, L)
+        words = B * L * n
+        acc = [np.zeros((B, L, n), dtype=np.uint64), np.zeros((B, L, n), dtype=np.uint64)]
+        terms = [(dev_t(env, m0[e]), dev_t(env, m1[e]), red[e]) for e in range(G)] + [(lv["d0"], lv["d1"], red0)]
+        for in0, in1, pt in terms:
+            p0, p1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+            ctx.ct_mul_plain(in0, dev_t(env, pt[None]), p0, in1, p1, primes=L)
+            torch.cuda.synchronize()
+            acc[0] += take(p0, words, (B, L, n), "mul_plain out0")
+            acc[1] += take(p1, words, (B, L, n), "mul_plain out1")
+        got = run_plan(env, ctx, plan, lv["d0"], lv["d1"], L)
+        for h in (0, 1):
+            assert (got[h] == (acc[h] % qv[None, :L]).astype(np.uint32)).all(), (L, h)
+    plan.close()
+
+
+def test_plan_is_a_snapshot_of_the_keys(env, slab_cases):
+    """Test 3: a plan, then different random keys installed for the same elements: the old plan still returns the bits
+    of test 1, a new plan the expectation under the new keys, which differs.  Destroying both, then closing the
+    context (the fixture), is clean; the first keys are put back for the other tests."""
+    shape, levels, B = GALOIS_CASES[1]
+    case = slab_cases(shape, levels, B)
+    o, ctx, elts, n, npr = case["o"], case["ctx"], case["elts"], shape[0], shape[1]
+    lv = case["levels"][npr]
+    old = ctx.lintrans_plan(elts, case["t_diag"], case["t_diag0"])
+    want_old = lintrans_expect(o, lv["rot"], case["diag"], lv["c0"], lv["c1"], case["diag0"])
+    nk0, nk1 = random_keys(np.random.default_rng(77), o.q, len(case["keys"]), n, npr)
+    ctx.set_galois_keys(case["keys"], nk0, nk1)
+    try:
+        new = ctx.lintrans_plan(elts, case["t_diag"], case["t_diag0"])
+        rot_new = hoist_expect(env["pkg"], o, lv["c0"], lv["c1"], elts, case["key_of"], nk0, nk1)
+        want_new = lintrans_expect(o, rot_new, case["diag"], lv["c0"], lv["c1"], case["diag0"])
+        assert (want_new[0] != want_old[0]).any() and (want_new[1] != want_old[1]).any()
+        got_old = run_plan(env, ctx, old, lv["d0"], lv["d1"], npr)
+        got_new = run_plan(env, ctx, new, lv["d0"], lv["d1"], npr)
+        assert (got_old[0] == want_old[0]).all() and (got_old[1] == want_old[1]).all(), "the old plan changed"
+        assert (got_new[0] == want_new[0]).all() and (got_new[1] == want_new[1]).all(), "the new plan"
+        old.close()
+        new.close()
+        old.close()                                        # closing twice is a no-op
+    finally:
+        ctx.set_galois_keys(case["keys"], *case["gk"])
+
+
+# ---- test 4: arguments ----------------------------------------------------------------------------------------------
+def test_lintrans_arguments(env):
+    """Every documented error returns its code and leaves the sentinel-filled outputs untouched.  The call: the pointer,
+    alignment, level and B checks of se_amd_ct_galois_device, a NULL plan, a plan of another context, a level above the
+    plan's.  Create: NULL elts / d_diag / out, G = 0 and 65, pt_primes = 0, an even element, one >= 2n, a misaligned
+    diagonal -- the handle stays NULL --, an element without a key: SE_ERR_NO_KEY with the element named.  B = 0
+    succeeds and writes nothing; se_amd_lintrans_destroy(NULL) is safe."""
+    torch, pkg = env["torch"], env["pkg"]
+    n, npr, B = 4096, 3, 2
+    ctx, other = pkg.Context(n, npr), pkg.Context(n, npr)
+    L, h = ctx.L, ctx.h
+    key = np.zeros((2, 2 * npr, npr, n), dtype=np.uint32)
+    ctx.set_galois_keys([3, 9], key, key)
+    other.set_galois_keys([3, 9], key, key)
+    c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
+    c1 = torch.zeros_like(c0)
+    out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
+    out1 = torch.full_like(out0, SENTINEL)
+    diag = torch.ones((2, npr, n), dtype=torch.int32, device=env["dev"])
+    diag0 = torch.ones((npr, n), dtype=torch.int32, device=env["dev"])
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    z = C.c_void_p(None)
+    s = stream_of(env)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the G = 65 call
+    good, even, big, nokey = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 5)
+    P0, P1, O0, O1, E, D, D0 = p(c0), p(c1), p(out0), p(out1), hp(good), p(diag), p(diag0)
+
+    def create(ctx_h, elts, G, d, d0, pt, want_out=True):
+        handle = C.c_void_p(0xDEAD)                         # a failed create must overwrite it with NULL
+        rc = L.se_amd_lintrans_create(ctx_h, elts, G, d, d0, pt, C.byref(handle) if want_out else None)
+        return rc, handle
+
+    bad_creates = [
+        (None, E, 2, D, D0, npr),
+        (h, z, 2, D, D0, npr),                               # NULL elts, d_diag
+        (h, E, 2, z, D0, npr),
+        (h, E, 0, D, D0, npr),                               # G = 0, G = 65
+        (h, E, 65, D, D0, npr),
+        (h, E, 2, D, D0, 0),                                 # pt_primes = 0
+        (h, hp(even), 2, D, D0, npr),                        # an even element, one >= 2n
+        (h, hp(big), 2, D, D0, npr),
+        (h, E, 2, p(diag, 4), D0, npr),                      # alignment of either diagonal pointer
+        (h, E, 2, D, p(diag0, 8), npr),
+    ]
+    for k, args in enumerate(bad_creates):
+        rc, handle = create(*args)
+        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, (k, rc, handle.value)
+    assert create(h, E, 2, D, D0, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT       # NULL out
+    rc, handle = create(h, hp(nokey), 2, D, D0, npr)
+    assert rc == SE_ERR_NO_KEY and handle.value is None
+    assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
+    rc, plan = create(h, E, 2, D, D0, 2)                     # a plan of two levels, with diag0
+    assert rc == 0 and plan.value
+    rc, foreign = create(other.h, E, 2, D, D0, npr)
+    assert rc == 0 and foreign.value
+    rc, no0 = create(h, E, 1, D, z, 7)                       # no diag0; pt_primes above np serves np levels
+    assert rc == 0 and no0.value
+
+    def call(ctx_h, pl, a0, a1, Bv, primes, o0, o1):
+        return L.se_amd_ct_lintrans_device(ctx_h, pl, a0, a1, Bv, primes, o0, o1, s)
+
+    bad_calls = [
+        (None, plan, P0, P1, B, 2, O0, O1),
+        (h, plan, z, P1, B, 2, O0, O1),                      # NULL slab pointers
+        (h, plan, P0, z, B, 2, O0, O1),
+        (h, plan, P0, P1, B, 2, z, O1),
+        (h, plan, P0, P1, B, 2, O0, z),
+        (h, plan, P0, P1, B, 0, O0, O1),                     # primes outside [1, np]
+        (h, plan, P0, P1, B, 4, O0, O1),
+        (h, plan, P0, P1, 2 ** 32, 2, O0, O1),               # B >= 2^32
+        (h, plan, p(c0, 4), P1, B, 2, O0, O1),               # alignment, each slab
+        (h, plan, P0, p(c1, 8), B, 2, O0, O1),
+        (h, plan, P0, P1, B, 2, p(out0, 12), O1),
+        (h, plan, P0, P1, B, 2, O0, p(out1, 4)),
+        (h, z, P0, P1, B, 2, O0, O1),                        # no plan
+        (h, foreign, P0, P1, B, 2, O0, O1),                  # a plan of another context
+        (other.h, plan, P0, P1, B, 2, O0, O1),
+        (h, plan, P0, P1, B, 3, O0, O1),                     # a level above the plan's
+    ]
+    for k, args in enumerate(bad_calls):
+        assert call(*args) == SE_ERR_INVALD_ARGUMENT, k
+    assert call(h, plan, P0, P1, 0, 2, O0, O1) == 0
+    torch.cuda.synchronize()
+    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    # the plans work: zero keys and zero slabs give zero rows, at level 2 resp. 3
+    for pl, lv in ((plan, 2), (no0, 3)):
+        out0.fill_(SENTINEL)
+        out1.fill_(SENTINEL)
+        assert call(h, pl, P0, P1, B, lv, O0, O1) == 0
+        torch.cuda.synchronize()
+        for o in (out0, out1):
+            flat = o.reshape(-1)
+            assert int(torch.count_nonzero(flat[:B * lv * n])) == 0 and bool((flat[B * lv * n:] == SENTINEL).all())
+    L.se_amd_lintrans_destroy(None)
+    for pl in (plan, foreign, no0):
+        L.se_amd_lintrans_destroy(pl)
+    ctx.close()
+    other.close()
+
+
+# ---- test 5: end to end with a real key -------------------------------------------------------------------------------
+DIM = 8
+STEPS = tuple(range(1, DIM))
+LIFT = 1 << 18            # tools/ct_galois_noise_sim.py --lintrans: the example's bookkeeping
+DIAG_SHIFT = 256.0        # the diagonals are encoded from M / 2^8: their scale is Delta / 2^8
+
+
+def matrix():
+    """The example's fixed matrix: M[r][c] = ((7 r + 3 c + 1) mod 17 - 8) / 8, entries in [-1, 1]."""
+    r, c = np.meshgrid(np.arange(DIM), np.arange(DIM), indexing="ij")
+    return ((7 * r + 3 * c + 1) % 17 - 8) / 8.0
+
+
+def fill_keyed_case(env, case):
+    """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the Galois keys of the
+    steps 1 .. 7, installed; B = 4 fresh symmetric records holding 8-periodic slot values in [-1, 1]."""
+    ctx, sk, pkg = case["ctx"], case["sk"], env["pkg"]
+    n, npr, B = ctx.n, ctx.np, 4
+    elts = [pkg.galois_element(n, s) for s in STEPS]
+    assert elts == [pow(3, s, 2 * n) for s in STEPS]
+    a_seeds = V.derive_seeds("gk-lintrans-a", len(elts) * 2 * npr)
+    e_seeds = V.derive_seeds("gk-lintrans-e", len(elts) * 2 * npr)
+    gk0, gk1 = ctx.gen_galois_keys(sk, elts, a_seeds, e_seeds)
+    ctx.set_galois_keys(elts, gk0, gk1)
+    x8 = np.random.default_rng(5000 + n).uniform(-1.0, 1.0, (B, DIM))
+    vals = np.tile(x8, (1, n // 2 // DIM)).astype(np.float32)
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=300)
+    assert bool((st == 1).all())
+    case.update(elts=elts, key_of={g: k for k, g in enumerate(elts)}, gk0=gk0, gk1=gk1, vals=vals, fresh=(c0, c1))
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_matvec_end_to_end(env, keyed_cases, shape):
+    """Test 5: ct_lincomb with weight 2^18 -> ONE plan call (steps 1 .. 7 and diag0; the diagonals of M / 2^8 encoded on
+    the device) -> ct_rescale -> decrypt_level(primes = np - 1, scale = Delta 2^18 (Delta / 2^8) / q_last) on B = 4
+    records of 8-periodic slot values in [-1, 1].  Every stage equals its definition bit for bit (the encoded diagonals
+    equal the oracle's), the final pte / values / values_f64 equal the oracle's on the final records, every coefficient
+    before the rescale is below 2^62, and the slots of the expectation and of the GPU are within the reference's 0.1 of
+    M x.  The worst errors are printed."""
+    from oracle.pyoracle import Oracle
+    torch = env["torch"]
+    c = keyed_cases(shape)
+    ctx, o, pkg = c["ctx"], c["o"], env["pkg"]
+    n, npr = shape
+    lo = Oracle(n, npr - 1)
+    B = c["vals"].shape[0]
+    M = matrix()
+    # lift
+    up0, up1 = sentinel_out(env, B * npr * n, 2 * n), sentinel_out(env, B * npr * n, 2 * n)
+    ctx.ct_lincomb(c["fresh"][0], up0, c["fresh"][1], up1, row_ptr=dev_t(env, np.arange(B + 1, dtype=np.uint32)),
+                   idx=dev_t(env, np.arange(B, dtype=np.uint32)), w=dev_t(env, np.full(B, LIFT, dtype=np.int32)))
+    torch.cuda.synchronize()
+    l0, l1 = take(up0, B * npr * n, (B, npr, n), "lift"), take(up1, B * npr * n, (B, npr, n), "lift")
+    qv = np.array(o.q, dtype=np.uint64)[None, :, None]
+    assert (l0 == ((host_u32(c["fresh"][0]).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)).all()
+    assert (l1 == ((host_u32(c["fresh"][1]).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)).all()
+    # the diagonals: slot k of diagonal e = M[k mod 8][(k + e) mod 8] / 2^8, encoded on the device
+    k = np.arange(n // 2)
+    dvals = np.stack([M[k % DIM, (k + e) % DIM] / DIAG_SHIFT for e in range(DIM)]).astype(np.float32)
+    enc = sentinel_out(env, DIM * npr * n, 2 * n)
+    ctx.encode_ntt(dev_t(env, dvals), enc)
+    torch.cuda.synchronize()
+    ok, enc_want = o.encode_ntt_batch(dvals)
+    assert ok
+    diag = take(enc, DIM * npr * n, (DIM, npr, n), "encoded diagonals")
+    assert (diag == enc_want).all()
+    # one plan, one call
+    t_diag = dev_t(env, diag)
+    plan = ctx.lintrans_plan(c["elts"], t_diag[1:].contiguous(), t_diag[0].contiguous())
+    d0, d1 = dev_t(env, l0), dev_t(env, l1)
+    g0, g1 = run_plan(env, ctx, plan, d0, d1, npr)
+    plan.close()
+    rot = hoist_expect(pkg, o, l0, l1, c["elts"], c["key_of"], c["gk0"], c["gk1"])
+    want = lintrans_expect(o, rot, diag[1:], l0, l1, diag[0])
+    assert (g0 == want[0]).all() and (g1 == want[1]).all(), "plan call"
+    for b in range(B):
+        big = max(abs(v) for v in expectation(o, g0[b], g1[b], c["s_hat"])["y"])
+        print(f"record {b}: log2 of the largest coefficient before the rescale = {np.log2(float(big)):.2f}")
+        assert big < 2 ** 62, (b, big)
+    # rescale, decrypt one level lower
+    words = B * (npr - 1) * n
+    s0, s1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_rescale(dev_t(env, g0), s0, dev_t(env, g1), s1, primes=npr)
+    torch.cuda.synchronize()
+    f0, f1 = take(s0, words, (B, npr - 1, n), "rescale"), take(s1, words, (B, npr - 1, n), "rescale")
+    assert (f0 == rescale_expect(o, g0)).all() and (f1 == rescale_expect(o, g1)).all()
+    scale = o.scale * LIFT * (o.scale / DIAG_SHIFT) / o.q[npr - 1]
+    got = run_decrypt(env, ctx, dev_t(env, f0), dev_t(env, f1), npr - 1, scale)
+    v64 = c["vals"].astype(np.float64)
+    want_slots = np.tile(v64[:, :DIM] @ M.T, (1, n // 2 // DIM))
+    worst = 0.0
+    for b in range(B):
+        e = expectation(lo, f0[b], f1[b], c["s_hat"][:npr - 1], scale)
+        assert e["status"] == 1
+        assert_matches(got, b, e, ("matvec", b))
+        err_e = float(np.abs(e["values"].astype(np.float64) - want_slots[b]).max())
+        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want_slots[b]).max())
+        print(f"record {b}: max |values - M x| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
+        assert err_e < 0.1 and err_g < 0.1, (b, err_e, err_g)
+        worst = max(worst, err_g)
+    print(f"{n} x {npr}, M x by the diagonal method: worst error {worst:.3e}")
+
+
+# ---- test 6: the example --------------------------------------------------------------------------------------------
+def test_matvec_example(env, tmp_path):
+    """examples/matvec_roundtrip.c from plain gcc: the diagonals encoded and folded into a plan, lift, ONE
+    se_amd_ct_lintrans_device call, rescale and decrypt_level come back within the reference's 0.1 of M x."""
+    exe = build_example("matvec_roundtrip", tmp_path, hip=True, extra=("-lm",))
+    r = subprocess.run([str(exe), "4096", "3", "8"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"failed=0 B=8 .*max_abs_error=([0-9.e+-]+)", r.stdout)
+    assert m and float(m.group(1)) < 0.1, r.stdout

@@ -15,7 +15,14 @@ se_amd_ct_galois_sum_device), which decomposes c1 itself and permutes the transf
   - its key-switch term for step 1,
   - lift by 2^30, one hoisted rotation (step 1), rescale,
   - lift by 2^30, the record plus its hoisted rotations by 1 .. 7 in one sum (every slot becomes the sum of 8), rescale.
-  python tools/ct_galois_noise_sim.py [4096x3 8192x6 ...]"""
+  python tools/ct_galois_noise_sim.py [4096x3 8192x6 ...]
+With --lintrans: the weighted sum of examples/matvec_roundtrip.c (se_amd_ct_lintrans_device), y = M x on records that
+hold an 8-vector repeated through the slots, M a fixed 8 x 8 matrix with entries in [-1, 1], as the plaintext-weighted sum
+of the record and its hoisted rotations by 1 .. 7: diagonal e holds M[k mod 8][(k + e) mod 8] / 2^DIAG_SHIFT encoded at
+Delta, so its scale is Delta / 2^DIAG_SHIFT.  One JSON line per parameter set and per bookkeeping (lift bits, diagonal
+shift, rescales): the largest coefficient before the first rescale (it must stay below 2^62 for the int64 decrypt of
+the stage) and the worst slot error against M x after the rescales.
+  python tools/ct_galois_noise_sim.py --lintrans [4096x3 8192x6 ...]"""
 import json
 import os
 import sys
@@ -216,9 +223,73 @@ def simulate(n, L):
                 slot_error_lift_four_rotate_adds_rescale=err_sum, log2_max_coeff_four=float(np.log2(big_sum)))
 
 
+MATVEC_DIM = 8
+# (lift bits, diagonal shift, rescales): the example's choice first, then the neighbours that show why
+MATVEC_BOOKS = ((18, 8, 1), (30, 0, 2), (13, 8, 1), (18, 0, 1), (9, 0, 1))
+
+
+def matvec_matrix():
+    """The example's fixed matrix: M[r][c] = ((7 r + 3 c + 1) mod 17 - 8) / 8, entries in [-1, 1]."""
+    r, c = np.meshgrid(np.arange(MATVEC_DIM), np.arange(MATVEC_DIM), indexing="ij")
+    return ((7 * r + 3 * c + 1) % 17 - 8) / 8.0
+
+
+def mul_plain(o, rows, pt):
+    return [((rows[j].astype(np.uint64) * pt[j].astype(np.uint64)) % np.uint64(o.q[j])).astype(np.uint32)
+            for j in range(len(rows))]
+
+
+def simulate_lintrans(n, L, books=MATVEC_BOOKS):
+    """-> one dict per bookkeeping.  The keys, the record and the hoisted rotations of a lift are shared."""
+    o = pyoracle.Oracle(n, L)
+    q = o.q
+    sk = V.secret_key(n, seed=5)
+    s_hat = [o.ntt(o.expand_ternary(sk, j), j) for j in range(L)]
+    rng = np.random.default_rng(8 * n + L)
+    x8 = rng.uniform(-1.0, 1.0, MATVEC_DIM)
+    vals = np.tile(x8, n // 2 // MATVEC_DIM).astype(np.float32)
+    M = matvec_matrix()
+    want = np.tile(M @ vals[:MATVEC_DIM].astype(np.float64), n // 2 // MATVEC_DIM)
+    ss, sd = V.bench_seeds(1, first=13)
+    x = o.encrypt_sym(vals, ss[0].tobytes(), sd[0].tobytes(), sk)
+    c0, c1 = [np.array(x["c0"][j]) for j in range(L)], [np.array(x["c1"][j]) for j in range(L)]
+    steps = tuple(range(1, MATVEC_DIM))
+    elts = [pow(3, s, 2 * n) for s in steps]
+    keys = [galois_key(o, sk, s_hat, g, f"gsim-{s}") for s, g in zip(steps, elts)]
+    k = np.arange(n // 2)
+    out = []
+    for lift_bits, shift, rescales in books:
+        lift = lambda rows: [((rows[j].astype(np.uint64) << np.uint64(lift_bits)) % np.uint64(q[j])).astype(np.uint32)
+                             for j in range(L)]
+        l0, l1 = lift(c0), lift(c1)
+        rots = [(l0, l1)] + galois_hoisted(o, l0, l1, elts, keys)
+        a0 = a1 = None
+        for e, (r0, r1) in enumerate(rots):
+            d = (M[k % MATVEC_DIM, (k + e) % MATVEC_DIM] / float(1 << shift)).astype(np.float32)
+            ok, pt = o.encode_ntt_batch(d[None, :])
+            assert ok
+            t0, t1 = mul_plain(o, r0, pt[0]), mul_plain(o, r1, pt[0])
+            a0, a1 = (t0, t1) if a0 is None else (add_rows(o, a0, t0), add_rows(o, a1, t1))
+        big = max(abs(int(v)) for v in value(o, a0, a1, s_hat))
+        scale = o.scale * float(1 << lift_bits) * o.scale / float(1 << shift)
+        for r in range(rescales):
+            scale /= q[L - 1 - r]
+            a0, a1 = rescale(o, a0), rescale(o, a1)
+        err = float(np.abs(decode(o, value(o, a0, a1, s_hat), scale) - want).max())
+        out.append(dict(n=n, primes=L, lift_bits=lift_bits, diag_shift=shift, rescales=rescales,
+                        log2_max_coeff_before_rescale=float(np.log2(float(big))), fits_int64_stage=big < 2 ** 62,
+                        log2_final_scale=float(np.log2(scale)), slot_error=err))
+    return out
+
+
 if __name__ == "__main__":
     pyoracle.build(ref=False)
-    shapes = sys.argv[1:] or ["4096x3", "8192x6"]
+    args = [a for a in sys.argv[1:] if a != "--lintrans"]
+    shapes = args or ["4096x3", "8192x6"]
     for sh in shapes:
         n, L = (int(v) for v in sh.split("x"))
-        print(json.dumps(simulate(n, L)), flush=True)
+        if "--lintrans" in sys.argv[1:]:
+            for row in simulate_lintrans(n, L):
+                print(json.dumps(row), flush=True)
+        else:
+            print(json.dumps(simulate(n, L)), flush=True)
