@@ -471,12 +471,13 @@ int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t
  * With the encoder's index map (the orbit of 3), g = 3^s mod 2n rotates the slot vector LEFT by s:
  * out_slot[k] = in_slot[(k + s) mod n/2]; a negative step rotates right; g = 2n - 1 conjugates (the real-valued slots
  * of this encoder are unchanged by it).  A rotation changes neither scale nor level.
- * Scale bookkeeping.  There is no special prime, so the key-switch term is the size of the relinearisation's (about
- * 2.5e7 per coefficient at 4096 x 3): rotate at a raised scale and rescale afterwards.  A product before its rescale is
- * already at scale^2; a fresh record is first lifted by se_amd_ct_lincomb_device with weight 2^30, which costs one level
- * (INTEGRATION.md section 4h).
+ * Scale bookkeeping.  This entry's digit key has no special prime, so the key-switch term is the size of the
+ * relinearisation's (about 2.5e7 per coefficient at 4096 x 3): rotate at a raised scale and rescale afterwards.  A
+ * product before its rescale is already at scale^2; a fresh record is first lifted by se_amd_ct_lincomb_device with
+ * weight 2^30, which costs one level -- or rotated at its own scale by the special-prime
+ * entry further down, se_amd_ct_galois_sp_device, which reserves the last prime for the key instead.
  * Out of scope: plaintext-weighted sums of rotations (the diagonal method), a per-record element list,
- * multi-GPU group entries, a special-prime (hybrid) key switch.
+ * multi-GPU group entries.
  *
  * se_amd_galois_element (host only, no context): *elt = 3^(step mod n/2) mod 2n, the step reduced into [0, n/2); step 0
  * gives 1.  se_amd_galois_table (host only): src [n] uint16 with sigma_elt(x)[k] = x[src[k]]; element 1 gives the
@@ -581,6 +582,64 @@ int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts /*host, [G]*/, 
 void se_amd_lintrans_destroy(se_amd_lintrans *plan);
 int se_amd_ct_lintrans_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0, const uint32_t *d_c1,
                               size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
+/* ---- special-prime (hybrid) key switch: relinearise and rotate at the record's own scale ------------
+ * The digit keys above add a term of about 2.5e7 per coefficient (4096 x 3), the size of a fresh message at scale 2^25,
+ * so every caller lifts, switches and rescales: one level per rotation.  These entries reserve the LAST prime of the
+ * context for the key instead, P = q_p with p = np - 1 (the largest prime of every default chain), as SEAL's key
+ * switching does.  Data levels are 1 <= L <= np - 1; np >= 2 is required (the n = 1024 and 2048 contexts have one prime:
+ * SE_ERR_INVALD_ARGUMENT from every entry of this block but se_amd_ct_drop_primes_device).  The key-switch term is
+ * divided by P on the way out: a few hundred per coefficient, 6e-4 in the slots at 4096 x 3 with scale 2^25
+ * (tools/ct_keyswitch_sp_noise_sim.py).  A key switch changes neither scale nor level, and needs no lift and no rescale.
+ * Conventions are those of the digit twins: level-L slabs, 16-byte aligned device pointers, one asynchronous launch
+ * without scratch, outputs that do not overlap inputs, nothing written on an error.  centred(x, q) is the representative
+ * in (-q/2, q/2], the convention of the rescale's delta.
+ * Key (the relinearisation key and a Galois key share one shape): R' = np - 1 rows, one per data prime, np columns; k0
+ * and k1 are uint32 [R'][np][n], NTT form.  Row j at prime i, mod q_i and canonical:
+ *     k1[j][i] = a_{j,i}
+ *     k0[j][i] = -a_{j,i} . s_hat_i + NTT_i(e_j mod q_i) + [i == j] . (P mod q_j) . target_j,
+ * target_j = s_hat_j^2 (relinearisation) or sigma(s_hat)_j (Galois key of an element).  The diagonal is P times the CRT
+ * basis element of q_j over Q P, which is 0 mod P: column p has no diagonal, and ONE key serves every level L <= np - 1
+ * (rows j < L, columns i < L and column p).  Minus its diagonal, row j is exactly public key j of se_amd_gen_keys_batch
+ * with K = R', sk_in = this key replicated, pk_seeds = a_seeds and ep_seeds = e_seeds ([R'][64]; Galois: [G][R'][64]).
+ * The gen / set entries take host pointers and refuse what their digit twins refuse (a 2-bit code 3, a word >= q_i, an
+ * even, too large or repeated element, G = 0, G > SE_AMD_MAX_GALOIS_KEYS); an install is built beside the previous
+ * one, swapped in at the end, and the previous block is freed after the calls in flight; a refused install leaves the
+ * previous one usable.  The special-prime keys are installed sets of their own: neither install touches the digit
+ * keys, and an installed digit key does not serve the entries of this block.  Device memory per key: 16 R' np n =
+ * 16 (np - 1) np n bytes, half of a digit key (4096 x 3: 384 KiB; 16384 x 13: 39 MiB).
+ * Key switch of a level-L row polynomial d:
+ *     D_j     = centred(INTT_j(d[j]), q_j), j < L               natural order, n^-1 included: |D_j| < q_j / 2 < P / 2
+ *     acc_k[i] = sum_{j < L} NTT_i(D_j mod q_i) . k_k[j][i]     k in {0, 1}, i in {0 .. L-1, p}; for i = j the factor is d[j]
+ *     delta_k = centred(INTT_p(acc_k[p]), P)
+ *     ks_k[i] = (acc_k[i] - NTT_i(delta_k mod q_i)) . P^-1      mod q_i, i < L: the rescale's map with P dropped, the
+ *                                                               constants of se_amd_rescale_constants(degree, np, ...)
+ * se_amd_ct_relin_sp_device: (d0, d1, d2) -> out0 = d0 + ks_0, out1 = d1 + ks_1 with d = d2.
+ * se_amd_ct_galois_sp_device: (c0, c1), element elt -> out0 = sigma(c0) + ks_0, out1 = ks_1 with d = sigma(c1): the
+ * relinearisation entry on (sigma(c0), 0, sigma(c1)) with the Galois key installed as the relinearisation key.
+ * Both maps are defined on arbitrary residue slabs and arbitrary installed key words below q_i; no secret key is needed.
+ * SE_ERR_INVALD_ARGUMENT for the digit twins' argument errors, np = 1, primes outside [1, np - 1]; SE_ERR_NO_KEY when no
+ * special-prime key is installed, or none for elt.  B = 0 is a successful no-op.
+ * se_amd_ct_drop_primes_device: rows 0 .. primes_out - 1 of every record, [B][primes_in][n] -> [B][primes_out][n], 1 <=
+ * primes_out <= primes_in <= np; d_in1 and d_out1 both NULL: one slab.  A pitched asynchronous device copy, no kernel.
+ * A fresh record is at level np and the entries above need level np - 1 at most; dropping a prime changes neither
+ * message nor scale.  SE_ERR_INVALD_ARGUMENT for a NULL or misaligned slab, one of d_in1 / d_out1 alone, levels out of
+ * range, B at or above 2^32.
+ * Out of scope: hoisted, sum and linear-transform forms on the special-prime key, several special primes, custom
+ * chains, host-pointer and multi-device forms. */
+int se_amd_gen_relin_key_sp(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint8_t *a_seeds /*[R'][64]*/,
+                            const uint8_t *e_seeds /*[R'][64]*/, uint32_t *evk0, uint32_t *evk1 /*[R'][np][n], host out*/);
+int se_amd_set_relin_key_sp(se_amd_ctx *ctx, const uint32_t *evk0, const uint32_t *evk1);
+int se_amd_gen_galois_keys_sp(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint32_t *elts, size_t G,
+                              const uint8_t *a_seeds /*[G][R'][64]*/, const uint8_t *e_seeds /*[G][R'][64]*/,
+                              uint32_t *gk0, uint32_t *gk1 /*[G][R'][np][n], host out*/);
+int se_amd_set_galois_keys_sp(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1);
+int se_amd_ct_relin_sp_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B,
+                              size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
+int se_amd_ct_galois_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                               uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, void *stream);
+int se_amd_ct_drop_primes_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
+                                 size_t B, size_t primes_in, size_t primes_out, uint32_t *d_out0,
+                                 uint32_t *d_out1 /* NULL with d_in1 */, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

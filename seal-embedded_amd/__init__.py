@@ -70,6 +70,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_galois_element", "se_amd_galois_table", "se_amd_gen_galois_keys", "se_amd_set_galois_keys",
     "se_amd_ct_galois_device", "se_amd_ct_galois_many_device", "se_amd_ct_galois_sum_device",
     "se_amd_lintrans_create", "se_amd_lintrans_destroy", "se_amd_ct_lintrans_device",
+    "se_amd_gen_relin_key_sp", "se_amd_set_relin_key_sp", "se_amd_gen_galois_keys_sp", "se_amd_set_galois_keys_sp",
+    "se_amd_ct_relin_sp_device", "se_amd_ct_galois_sp_device", "se_amd_ct_drop_primes_device",
 )
 
 
@@ -166,6 +168,13 @@ def lib():
     L.se_amd_gen_galois_keys.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
     L.se_amd_set_galois_keys.argtypes = [vp, vp, sz, vp, vp]
     L.se_amd_ct_galois_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp]
+    L.se_amd_gen_relin_key_sp.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.se_amd_set_relin_key_sp.argtypes = [vp, vp, vp]
+    L.se_amd_gen_galois_keys_sp.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+    L.se_amd_set_galois_keys_sp.argtypes = [vp, vp, sz, vp, vp]
+    L.se_amd_ct_relin_sp_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    L.se_amd_ct_galois_sp_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp]
+    L.se_amd_ct_drop_primes_device.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
     L.se_amd_ct_galois_many_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
     L.se_amd_ct_galois_sum_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, i32, vp, vp, vp]
     L.se_amd_lintrans_create.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(vp)]
@@ -617,11 +626,11 @@ class Context:
                                                          _ptr(status), _stream_ptr()),
                "se_amd_decrypt3_level_keyed_device")
 
-    def _evk_gen_buffers(self, sk_packed, a_seeds, e_seeds, lead=()):
+    def _evk_gen_buffers(self, sk_packed, a_seeds, e_seeds, lead=(), R=None):
         """What generating evaluation keys takes and fills: the packed key, the seed blocks lead + [R][64] and two
-        zeroed key halves lead + [R][np][n], R = 2 np."""
+        zeroed key halves lead + [R][np][n], R = 2 np (a special-prime key: R = np - 1)."""
         import numpy as np
-        R = 2 * self.np
+        R = 2 * self.np if R is None else R
         sk = np.ascontiguousarray(sk_packed, dtype=np.uint8)
         assert sk.size == self.n // 4
         sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(*lead, R, 64)
@@ -629,12 +638,14 @@ class Context:
         k0 = np.zeros((*lead, R, self.np, self.n), dtype=np.uint32)
         return sk, sa, se, k0, np.zeros_like(k0)
 
-    def _evk_halves(self, k0, k1, count=1):
-        """The two halves of `count` evaluation keys as contiguous uint32, [count][2 np][np][n] words each."""
+    def _evk_halves(self, k0, k1, count=1, R=None):
+        """The two halves of `count` evaluation keys as contiguous uint32, [count][R][np][n] words each, R = 2 np (a
+        special-prime key: R = np - 1)."""
         import numpy as np
+        R = 2 * self.np if R is None else R
         k0 = np.ascontiguousarray(k0, dtype=np.uint32)
         k1 = np.ascontiguousarray(k1, dtype=np.uint32)
-        assert k0.size == count * 2 * self.np * self.np * self.n == k1.size
+        assert k0.size == count * R * self.np * self.n == k1.size
         return k0, k1
 
     def gen_relin_key(self, sk_packed, a_seeds, e_seeds):
@@ -685,6 +696,68 @@ class Context:
             primes = c0.shape[1]
         _check(self.L.se_amd_ct_galois_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, int(elt), _ptr(out0),
                                               _ptr(out1), _stream_ptr()), "se_amd_ct_galois_device")
+
+    # ---- special-prime (hybrid) key switch: the last prime of the context belongs to the key, records have at most
+    # np - 1 primes; keys of R' = np - 1 rows, installed sets of their own beside the digit keys
+    def gen_relin_key_sp(self, sk_packed, a_seeds, e_seeds):
+        """Special-prime relinearisation key of sk_packed from R' = np - 1 seed pairs [R'][64]: (evk0, evk1) uint32
+        [R'][np][n]."""
+        sk, sa, se, evk0, evk1 = self._evk_gen_buffers(sk_packed, a_seeds, e_seeds, R=max(self.np - 1, 1))
+        _check(self.L.se_amd_gen_relin_key_sp(self.h, _ptr(sk), _ptr(sa), _ptr(se), _ptr(evk0), _ptr(evk1)),
+               "se_amd_gen_relin_key_sp")
+        return evk0, evk1
+
+    def set_relin_key_sp(self, evk0, evk1):
+        """evk0, evk1 [np - 1][np][n] uint32 (as gen_relin_key_sp returns them); a word >= q_i is refused."""
+        evk0, evk1 = self._evk_halves(evk0, evk1, R=max(self.np - 1, 1))
+        _check(self.L.se_amd_set_relin_key_sp(self.h, _ptr(evk0), _ptr(evk1)), "se_amd_set_relin_key_sp")
+
+    def ct_relin_sp(self, d0, d1, d2, out0, out1, primes=None):
+        """Relinearisation of (d0, d1, d2) [B][primes][n], primes <= np - 1, with the installed special-prime key ->
+        (out0, out1) of the same level and scale: the key-switch term is divided by the last prime of the context."""
+        if primes is None:
+            primes = d0.shape[1]
+        _check(self.L.se_amd_ct_relin_sp_device(self.h, _ptr(d0), _ptr(d1), _ptr(d2), d0.shape[0], primes, _ptr(out0),
+                                                _ptr(out1), _stream_ptr()), "se_amd_ct_relin_sp_device")
+
+    def gen_galois_keys_sp(self, sk_packed, elts, a_seeds, e_seeds):
+        """Special-prime Galois keys of sk_packed for `elts` from G blocks of R' = np - 1 seed pairs [G][R'][64]: (gk0,
+        gk1) uint32 [G][R'][np][n]."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        G = el.size
+        sk, sa, se, gk0, gk1 = self._evk_gen_buffers(sk_packed, a_seeds, e_seeds, lead=(G,), R=max(self.np - 1, 1))
+        _check(self.L.se_amd_gen_galois_keys_sp(self.h, _ptr(sk), _ptr(el), G, _ptr(sa), _ptr(se), _ptr(gk0),
+                                                _ptr(gk1)), "se_amd_gen_galois_keys_sp")
+        return gk0, gk1
+
+    def set_galois_keys_sp(self, elts, gk0, gk1):
+        """elts [G], gk0, gk1 [G][np - 1][np][n] uint32: replaces the installed special-prime set (the digit set is not
+        touched); refusals as set_galois_keys."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        gk0, gk1 = self._evk_halves(gk0, gk1, el.size, R=max(self.np - 1, 1))
+        _check(self.L.se_amd_set_galois_keys_sp(self.h, _ptr(el), el.size, _ptr(gk0), _ptr(gk1)),
+               "se_amd_set_galois_keys_sp")
+
+    def ct_galois_sp(self, c0, c1, elt, out0, out1, primes=None):
+        """ct_galois with the installed special-prime Galois key of `elt` on records (c0, c1) [B][primes][n], primes <=
+        np - 1: a rotation at the record's own scale, no lift and no rescale."""
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_galois_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, int(elt),
+                                                 _ptr(out0), _ptr(out1), _stream_ptr()), "se_amd_ct_galois_sp_device")
+
+    def ct_drop_primes(self, in0, out0, in1=None, out1=None, primes_in=None, primes_out=None):
+        """Rows 0 .. primes_out-1 of every record of one or two slabs [B][primes_in][n] -> [B][primes_out][n] (a device
+        copy); primes_in defaults to in0.shape[1], primes_out to primes_in - 1."""
+        if primes_in is None:
+            primes_in = in0.shape[1]
+        if primes_out is None:
+            primes_out = primes_in - 1
+        _check(self.L.se_amd_ct_drop_primes_device(self.h, _ptr(in0), _ptr(in1), in0.shape[0], primes_in, primes_out,
+                                                   _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_drop_primes_device")
 
     def ct_galois_many(self, c0, c1, elts, out0, out1, primes=None):
         """Hoisted rotations: out[e] = the rotation of the records (c0, c1) [B][primes][n] by elts[e], for all G

@@ -4,7 +4,9 @@
 // that brings it back to two slabs (se_amd_ct_relin_device, with the key plumbing), and the slot rotation: a ring
 // automorphism fused with its key switch (se_amd_ct_galois_device), and its hoisted form, many rotations of a record
 // from one digit decomposition (se_amd_ct_galois_many_device, se_amd_ct_galois_sum_device, at the end of the file), and
-// the plaintext-weighted sum of hoisted rotations under a plan (se_amd_ct_lintrans_device, behind them).
+// the plaintext-weighted sum of hoisted rotations under a plan (se_amd_ct_lintrans_device, behind them), and the
+// special-prime key switch that relinearises and rotates at the record's own scale (se_amd_ct_relin_sp_device,
+// se_amd_ct_galois_sp_device, behind k_ct_galois).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -560,8 +562,9 @@ hipError_t launch_ct_relin(const DevParams &P, const DevTables &T, const RelinAr
     });
 }
 
-// The device copy of an evaluation key: every row [np][n] of key words becomes [np][2][n], the words of a column
-// followed by their Shoup companions floor(w 2^32 / q_i) (w < q_i was checked on the host).  One thread per word.
+// The device copy of an evaluation key of any number of rows (2 np of a digit key, np - 1 of a special-prime key, both
+// halves in one call): every row [np][n] of key words becomes [np][2][n], the words of a column followed by their Shoup
+// companions floor(w 2^32 / q_i) (w < q_i was checked on the host).  One thread per word.
 __global__ __launch_bounds__(kLcThreads) void k_relin_key_rows(const DevParams P, const uint32_t *__restrict__ in,
                                                             uint32_t *__restrict__ out, size_t words)
 {
@@ -687,6 +690,254 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
         using G         = XformGeom<L>;
         const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
         return launch(k_ct_galois<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Special-prime (hybrid) key switch: se_amd_ct_relin_sp_device and se_amd_ct_galois_sp_device.  The digit key switch above
+// adds sum_r D_r e_r with 15-bit digits D_r: about 2.5e7 per coefficient at 4096 x 3, the size of a fresh message.  Here
+// the last prime of the CONTEXT, P = q_p with p = np - 1, is reserved for the key: a level-L record (L <= np - 1) is
+// switched over the L + 1 primes E = {0 .. L-1, p} with ONE digit per data prime, the whole centred coefficient
+//   D_j = centred(INTT_j(d[j]), q_j),   |D_j| < q_j / 2,
+// under a key whose diagonal carries the factor P, and the result is divided by P, rounded, as k_ct_rescale divides by the
+// last prime: the term sum_j D_j e_j (about 2^29 n^(1/2) sigma) is divided by P ~ 2^30 on the way out.
+//   acc_k[i] = sum_{j < L} NTT_i(D_j mod q_i) . key_k[j][i]           i in E   (for i = j the factor is d[j] itself)
+//   delta_k  = centred(INTT_p(acc_k[p]), P)
+//   ks_k[i]  = (acc_k[i] - NTT_i(delta_k mod q_i)) . P^-1   mod q_i   i < L    (RescaleParams of level np)
+// Relinearisation: d = d2, out_k = d_k + ks_k.  Rotation: d = sigma(c1), out0 = sigma(c0) + ks_0, out1 = ks_1.
+// The geometry of k_ct_relin: one workgroup of n/16 threads per (record, output prime i < L), LDS the exchange plane
+// alone, no scratch, no global temporary.  A workgroup makes two passes over the input rows with the same code
+// (sp_row_mac), first modulo P against key column p, then modulo q_i against key column i:
+//   pass 0, per j: evk_row_coeffs (the INTT mod q_j of the digit kernels) [-> sigma, the LDS scatter of k_ct_galois] ->
+//     centre and reduce mod P (one conditional add: |D_j| < q_j / 2 < every prime of the chain) -> ntt_tiles mod P ->
+//     tile_to_quads -> multiply-accumulate against row j, column p of both key halves;
+//   between the passes, per half: quads_to_tile -> intt_tiles mod P -> . n^-1 -> centred delta reduced mod q_i (|delta| <
+//     P / 2 < q_i: one conditional add) -> ntt_tiles mod q_i -> tile_to_quads -> the accumulator of pass 1 starts at
+//     2 q_i - NTT(delta), lazy in (0, 2 q_i];
+//   pass 1, per j != i: the coefficients AGAIN -> reduce mod q_i -> ntt_tiles mod q_i -> multiply-accumulate against
+//     column i; row i enters as it lies in memory (rotation: gathered through src_g, as sigma(c0) is);
+//   epilogue: . P^-1 (Shoup pair), + d_k resp. the sigma(c0) gather of k_ct_galois, canonical.
+// 2 L - 1 INTTs and 2 L - 1 NTTs of rows, and 2 + 2 for the two deltas: 4 L + 2 transforms per workgroup against 3 L of
+// the digit kernels.  Keeping the L centred rows of pass 0 instead would save L - 1 INTTs and cost 16 (L - 1) registers
+// per thread or a global temporary; the live set here is two accumulator tiles and one row, below that of evk_digits
+// (two accumulators, the coefficients AND a digit).
+// Lazy ranges.  A key word is below q (the setters refuse others), so mul_shoup_lazy(y, w, .) is in [0, 2 q) for any
+// 32-bit y and an accumulator in [0, 2 q] plus one product is below 4 q < 2^32; min(s, s - 2 q) brings it below 2 q.
+// The accumulators of pass 0 enter intt_tiles in [0, 2 P), which is its input range.
+// Addresses: as in k_ct_galois the only addresses formed from data are formed from the element, which the host has
+// checked (odd, below 2n), and every target is masked to [0, n); no word of a slab or of a key is used as an address.
+// Key block [2][R'][np][2][n], R' = np - 1 rows (one per data prime) of the context's np columns, Shoup companions behind
+// every column (k_relin_key_rows): row j, column c of half h at key + h half + (j np + c) 2 n.
+// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// ------------------------------------------------------------------------------------------
+// acc_k += y . key_k[row][column] on both halves, y in quad layout; `key` = the thread's first quad of that column in
+// half 0.  The body of evk_digits' multiply-accumulate.
+template <int LOGN>
+__device__ __forceinline__ void sp_mac(uint32_t (&acc0)[16], uint32_t (&acc1)[16], const uint32_t (&y)[16],
+                                       const uint32_t *key, size_t half, uint32_t q)
+{
+    constexpr int N      = XformGeom<LOGN>::N;
+    const uint32_t two_q = q << 1;
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
+        const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
+        const uint4 w1 = *reinterpret_cast<const uint4 *>(key + half + (c << 8));
+        const uint4 s1 = *reinterpret_cast<const uint4 *>(key + half + N + (c << 8));
+        const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
+        const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const int e       = 4 * c + k;
+            const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], q);
+            const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], q);
+            acc0[e]           = min(u0, u0 - two_q);
+            acc1[e]           = min(u1, u1 - two_q);
+        }
+    }
+}
+
+// The row `row` of a record as it lies in memory, in quad layout; GALOIS: sigma_g of it, word k = row[src_g(k)], through
+// the plane (which must be free; ends with the plane read but not yet released: the caller's next barrier releases it).
+template <int LOGN, bool GALOIS>
+__device__ __forceinline__ void sp_ntt_row(uint32_t (&c)[16], const uint32_t *row, uint32_t g, uint32_t *lds, int te)
+{
+    load_quads(c, row, te);
+    if constexpr (GALOIS)
+    {
+        const int k4 = quad_index(te, 0);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+            *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 16; e++) c[e] = lds[galois_src<LOGN>((uint32_t)(k4 + ((e >> 2) << 8) + (e & 3)), g)];
+    }
+}
+
+// NTT_c(D_j mod q) in quad layout, q = q_c the prime of key column c and rw its roots: the centred coefficients of input
+// row j (GALOIS: of sigma_g of it) reduced mod q and transformed.  Ends with the plane in use by the wave-local
+// transpose: the caller's barrier after the multiply-accumulate releases it.
+template <int LOGN, bool GALOIS>
+__device__ __forceinline__ void sp_row_digit(uint32_t (&x)[16], const uint32_t *row, uint32_t j, uint32_t g, uint32_t q,
+                                             const uint32_t *rw, const DevParams &P, const DevTables &T, uint32_t *lds,
+                                             int t)
+{
+    constexpr int N   = XformGeom<LOGN>::N;
+    const int tj      = opaque_index(t);
+    const uint32_t qj = P.q[j], hj = qj >> 1, up = q - qj;   // up: mod 2^32 where q < q_j
+    evk_row_coeffs<LOGN>(x, row, j, P, T, lds, tj);
+    if constexpr (GALOIS)
+    {
+        // sigma: coefficient k -> position k g mod n, negated when k g mod 2n >= n (k g < 2^29); 0 stays 0
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            const uint32_t u = (uint32_t)(tj + (N / 16) * e) * g;
+            lds[u & (N - 1)] = (u & N) && x[e] ? qj - x[e] : x[e];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 16; e++) x[e] = lds[tj + (N / 16) * e];
+        __syncthreads();
+    }
+    // centred: c > (q_j - 1) / 2 stands for c - q_j, whose residue mod q is c - q_j + q, in (0, q) for every pair of
+    // primes of the chains (they lie within 1 % of one another); c <= (q_j - 1) / 2 is its own residue
+#pragma unroll
+    for (int e = 0; e < 16; e++) x[e] += x[e] > hj ? up : 0u;
+    const int td = opaque_index(t);
+    ntt_tiles<LOGN>(x, rw, q, lds, td);
+    tile_to_quads<16>(x, lds, td);
+}
+
+template <int LOGN, bool GALOIS>
+__device__ __forceinline__ void ct_key_switch_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
+                                                 const KeySwitchSpArgs &A, uint32_t *lds)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t sp  = A.np - 1;
+    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t g   = A.elt;
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        // pass 0: modulo P against key column p; pass 1: modulo q_i against key column i.  One body for both.
+#pragma unroll 1
+        for (uint32_t pass = 0; pass < 2; pass++)
+        {
+            const uint32_t col = pass ? i : sp;
+            const uint32_t q   = P.q[col];
+            const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * col;
+            for (uint32_t j = 0; j < A.primes; j++)
+            {
+                uint32_t y[16];
+                if (pass && j == i)
+                    sp_ntt_row<LOGN, GALOIS>(y, A.sw + rec + (size_t)i * N, g, lds, opaque_index(t));
+                else
+                    sp_row_digit<LOGN, GALOIS>(y, A.sw + rec + (size_t)j * N, j, g, q, rw, P, T, lds, t);
+                const uint32_t *key = A.key + ((size_t)j * A.np + col) * 2 * N + quad_index(opaque_index(t), 0);
+                sp_mac<LOGN>(acc0, acc1, y, key, A.half, q);
+                __syncthreads();
+            }
+            if (pass == 0)
+            {
+                // delta_k = centred(INTT_p(acc_k)), and the accumulator of pass 1 starts at -NTT_i(delta_k mod q_i).
+                // The two halves take the same code: not unrolled, the halves change places after each turn.
+                const uint32_t *rwi  = T.ntt_rw + 2 * xform_table_len(N) * i;
+                const uint32_t inv_n = P.inv_n[sp], inv_n_sh = P.inv_n_sh[sp], hp = q >> 1, down = qi - q;
+#pragma unroll 1
+                for (uint32_t k = 0; k < 2; k++)
+                {
+                    const int td = opaque_index(t);
+                    quads_to_tile<16>(acc0, lds, td);
+                    __syncthreads();
+                    intt_tiles<LOGN>(acc0, T.intt_rw + (size_t)2 * N * sp, q, lds, td);
+#pragma unroll
+                    for (int e = 0; e < 16; e++)
+                    {
+                        const uint32_t v = csub(mul_shoup_lazy(acc0[e], inv_n, inv_n_sh, q), q);
+                        acc0[e]          = v + (v > hp ? down : 0u);   // delta mod q_i in [0, q_i): |delta| < P / 2 < q_i
+                    }
+                    const int tn = opaque_index(t);
+                    ntt_tiles<LOGN>(acc0, rwi, qi, lds, tn);
+                    tile_to_quads<16>(acc0, lds, tn);
+#pragma unroll
+                    for (int e = 0; e < 16; e++)
+                    {
+                        const uint32_t u = min(acc0[e], acc0[e] - two_qi);   // NTT output [0, 4q) -> [0, 2q)
+                        const uint32_t o = acc1[e];
+                        acc1[e]          = two_qi - u;                       // (0, 2q]
+                        acc0[e]          = o;
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+        // ks_k = acc_k . P^-1, then the addends
+        const int te   = opaque_index(t);
+        const size_t o = rec + (size_t)i * N;
+        const uint32_t w = R.inv[i], wp = R.inv_sh[i];
+        uint32_t c[16];
+        sp_ntt_row<LOGN, GALOIS>(c, A.a0 + o, g, lds, te);
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = csub(csub(mul_shoup_lazy(acc0[e], w, wp, qi), qi) + c[e], qi);
+        store_quads(A.out0 + o, acc0, te);
+        if constexpr (GALOIS)
+        {
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc1[e] = csub(mul_shoup_lazy(acc1[e], w, wp, qi), qi);
+        }
+        else
+        {
+            load_quads(c, A.a1 + o, te);
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc1[e] = csub(csub(mul_shoup_lazy(acc1[e], w, wp, qi), qi) + c[e], qi);
+        }
+        store_quads(A.out1 + o, acc1, te);
+        __syncthreads();   // the next record's first transpose writes the plane the gather reads
+    }
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin_sp(const DevParams P, const DevTables T,
+                                                                       const RescaleParams R, const KeySwitchSpArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ct_key_switch_sp<LOGN, false>(P, T, R, A, reinterpret_cast<uint32_t *>(smem));
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_sp(const DevParams P, const DevTables T,
+                                                                        const RescaleParams R, const KeySwitchSpArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ct_key_switch_sp<LOGN, true>(P, T, R, A, reinterpret_cast<uint32_t *>(smem));
+}
+
+// elt 0: the relinearisation; else the rotation by that element.  Contexts with a special prime have np >= 2, which
+// the default chains give from n = 4096 on: the kernels exist for LOGN 12 .. 14 only, a smaller degree is an error (the
+// host refuses np = 1 before it gets here) and the two unreachable cases of the dispatch name the LOGN = 12 kernels.
+hipError_t launch_ct_key_switch_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
+                                   const KeySwitchSpArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
+        return A.elt ? launch(k_ct_galois_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
+                     : launch(k_ct_relin_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
     });
 }
 
@@ -1092,16 +1343,22 @@ hipError_t launch_lintrans_fold(const DevParams &P, const uint32_t *key_in, uint
 // for the Galois key of element g (SIGMA true; g is odd and below 2n, checked by the host).
 // d < q_j < 2^30 lives in a register only; d 2^15 + key0 < 2^46.  grid n / 256.
 template <int LOGN, bool SIGMA>
+__device__ __forceinline__ uint64_t evk_diag_target(const DevParams &P, uint32_t j, uint32_t g, uint32_t c,
+                                                    const uint32_t *__restrict__ s_hat)
+{
+    if constexpr (SIGMA)
+        return s_hat[galois_src<LOGN>(c, g)];
+    else
+        return barrett64((uint64_t)s_hat[c] * s_hat[c], P.q[j], P.cr_hi[j], P.cr_lo[j]);
+}
+
+template <int LOGN, bool SIGMA>
 __global__ __launch_bounds__(kLcThreads) void k_evk_diag(const DevParams P, uint32_t j, uint32_t g,
                                                       const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ key0)
 {
     const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
     const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
-    uint64_t d;
-    if constexpr (SIGMA)
-        d = s_hat[galois_src<LOGN>(c, g)];
-    else
-        d = barrett64((uint64_t)s_hat[c] * s_hat[c], q, cr_hi, cr_lo);
+    const uint64_t d = evk_diag_target<LOGN, SIGMA>(P, j, g, c, s_hat);
 #pragma unroll
     for (uint32_t dg = 0; dg < 2; dg++)
     {
@@ -1110,13 +1367,29 @@ __global__ __launch_bounds__(kLcThreads) void k_evk_diag(const DevParams P, uint
     }
 }
 
-// elt 0: the relinearisation key's diagonal; else the Galois key's of that element
-hipError_t launch_evk_diag(const DevParams &P, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *key0,
+// The special-prime key's diagonal on its [np - 1][np][n] slab: key0[j][j][k] += (P mod q_j) . d[k] mod q_j for a data
+// prime j < np - 1, P = q_{np-1} and d as above.  (P mod q_j) d + key0 < 2^60 + 2^30.
+template <int LOGN, bool SIGMA>
+__global__ __launch_bounds__(kLcThreads) void k_evk_diag_sp(const DevParams P, uint32_t j, uint32_t g,
+                                                         const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ key0)
+{
+    const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const uint64_t d = evk_diag_target<LOGN, SIGMA>(P, j, g, c, s_hat);
+    uint32_t *p      = key0 + (((size_t)j * P.nprimes + j) << LOGN) + c;
+    *p               = barrett64(d * (P.q[P.nprimes - 1] % q) + *p, q, cr_hi, cr_lo);
+}
+
+// elt 0: the relinearisation key's diagonal; else the Galois key's of that element.  sp: the special-prime key's rows
+hipError_t launch_evk_diag(const DevParams &P, uint32_t j, uint32_t elt, bool sp, const uint32_t *s_hat, uint32_t *key0,
                            hipStream_t st)
 {
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
         const dim3 grid(P.n / kLcThreads), block(kLcThreads);
+        if (sp)
+            return elt ? launch(k_evk_diag_sp<L, true>, grid, block, 0, st, P, j, elt, s_hat, key0)
+                       : launch(k_evk_diag_sp<L, false>, grid, block, 0, st, P, j, elt, s_hat, key0);
         return elt ? launch(k_evk_diag<L, true>, grid, block, 0, st, P, j, elt, s_hat, key0)
                    : launch(k_evk_diag<L, false>, grid, block, 0, st, P, j, elt, s_hat, key0);
     });

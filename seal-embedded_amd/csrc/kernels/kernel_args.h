@@ -217,6 +217,26 @@ struct GaloisArgs
     uint32_t elt;                   // odd, below 2n (checked by the host: the kernel forms LDS addresses from it)
 };
 hipError_t launch_ct_galois(const DevParams &, const DevTables &, const GaloisArgs &, hipStream_t);
+// Special-prime key switch (k_ct_relin_sp, k_ct_galois_sp): the last prime of the context, P = q_{np-1}, belongs to the
+// key, records have `primes` <= np - 1 rows.  `key` is a device block [2][R'][np][2][n] of R' = np - 1 rows (build_evk).
+// With D_j = centred(INTT_j(sw[b][j])) (sw = d2, or sigma(c1) for a rotation) and E = {0 .. primes-1, np-1}:
+//   acc_k[i] = sum_{j < primes} NTT_i(D_j mod q_i) . key_k[j][i],  i in E;   delta_k = centred(INTT_p(acc_k[p]), P);
+//   out_k[b][i] = a_k[b][i] + (acc_k[i] - NTT_i(delta_k mod q_i)) . P^-1   mod q_i,  i < primes,
+// a0 = d0 resp. sigma(c0), a1 = d1 resp. 0.  The constants P^-1 mod q_i are the RescaleParams of level np.
+struct KeySwitchSpArgs
+{
+    const uint32_t *a0, *a1;        // [B][primes][n]: d0, d1; rotation: c0, a1 unused
+    const uint32_t *sw;             // [B][primes][n]: d2; rotation: c1
+    uint32_t *out0, *out1;          // [B][primes][n]
+    const uint32_t *key;
+    size_t half;                    // words of one key half: R' np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
+    uint32_t primes;                // 1 .. np - 1
+    uint32_t elt;                   // 0: relinearisation; else odd, below 2n (checked by the host: LDS addresses)
+};
+hipError_t launch_ct_key_switch_sp(const DevParams &, const DevTables &, const RescaleParams &, const KeySwitchSpArgs &,
+                                   hipStream_t);
 // Hoisted rotations (k_ct_galois_hoist): G rotations of every record from ONE digit decomposition of c1.  The digits
 // D_{j,t} are those of the canonical coefficients of INTT_j(c1[b][j]) itself; sigma is applied to the TRANSFORMED digits,
 // where it is the permutation src_g:
@@ -265,13 +285,14 @@ hipError_t launch_ct_lintrans(const DevParams &, const DevTables &, const Lintra
 // [2][R][np][2][n]), key_out = the block of the words key_in . d mod q_i and their companions.  key_in NULL: pairs only.
 hipError_t launch_lintrans_fold(const DevParams &, const uint32_t *key_in, uint32_t *key_out, const uint32_t *diag_in,
                                 uint32_t *pair_out, uint32_t pt, hipStream_t);
-// Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words (rows a multiple of np) -> [rows][2][n]
-// (words, Shoup companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
+// Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words -> [rows][np][2][n] (words, Shoup
+// companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
 // slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =
-// s_hat[src_elt(k)], sigma_elt(s) in NTT form, else (the Galois key of elt).
+// s_hat[src_elt(k)], sigma_elt(s) in NTT form, else (the Galois key of elt).  sp: the special-prime key's slab
+// [np - 1][np][n] instead, key0[j][j][k] += (q_{np-1} mod q_j) . d[k] for j < np - 1.
 hipError_t launch_relin_key_rows(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, hipStream_t);
-hipError_t launch_evk_diag(const DevParams &, uint32_t j, uint32_t elt, const uint32_t *s_hat, uint32_t *key0,
-                           hipStream_t);
+hipError_t launch_evk_diag(const DevParams &, uint32_t j, uint32_t elt, bool sp, const uint32_t *s_hat,
+                           uint32_t *key0, hipStream_t);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

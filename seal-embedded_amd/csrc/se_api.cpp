@@ -445,6 +445,53 @@ int se_amd_ct_galois_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_
     return ctx->c.ct_galois(d_c0, d_c1, B, primes, elt, d_out0, d_out1, as_stream(stream));
 }
 
+int se_amd_gen_relin_key_sp(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds,
+                            uint32_t *evk0, uint32_t *evk1)
+{
+    if (!ctx || !sk_packed || !a_seeds || !e_seeds || !evk0 || !evk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.gen_relin_key(sk_packed, a_seeds, e_seeds, evk0, evk1, true);
+}
+
+int se_amd_set_relin_key_sp(se_amd_ctx *ctx, const uint32_t *evk0, const uint32_t *evk1)
+{
+    if (!ctx || !evk0 || !evk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_relin_key(evk0, evk1, true);
+}
+
+int se_amd_gen_galois_keys_sp(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint32_t *elts, size_t G,
+                              const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *gk0, uint32_t *gk1)
+{
+    if (!ctx || !sk_packed || !elts || !a_seeds || !e_seeds || !gk0 || !gk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.gen_galois_keys(sk_packed, elts, G, a_seeds, e_seeds, gk0, gk1, true);
+}
+
+int se_amd_set_galois_keys_sp(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1)
+{
+    if (!ctx || !elts || !gk0 || !gk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_galois_keys(elts, G, gk0, gk1, true);
+}
+
+int se_amd_ct_relin_sp_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2,
+                              size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_key_switch_sp(d_d0, d_d1, d_d2, B, primes, 0, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_galois_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                               uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx || !(elt & 1)) return SE_ERR_INVALD_ARGUMENT;   // the shared call takes element 0 for the relinearisation
+    return ctx->c.ct_key_switch_sp(d_c0, nullptr, d_c1, B, primes, elt, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_drop_primes_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B,
+                                 size_t primes_in, size_t primes_out, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_drop_primes(d_in0, d_in1, B, primes_in, primes_out, d_out0, d_out1, as_stream(stream));
+}
+
 int se_amd_ct_galois_many_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                  const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, void *stream)
 {

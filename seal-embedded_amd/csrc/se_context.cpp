@@ -534,13 +534,23 @@ int Context::gen_keys_batch(size_t K, const uint8_t *sk_in, const uint8_t *sk_se
 // Relinearisation key: the chain above with K = R = 2 np rows under ONE secret key, pk_seeds = a_seeds and ep_seeds =
 // e_seeds -- row r is public key r, (evk0[r], evk1[r]) = (-a_r s_hat + NTT(e_r), a_r) -- plus the diagonal term
 // 2^(15 t) s_hat^2 on column j of the rows r = 2j + t (kernels/ct_ops.hip, k_evk_diag).
+// The special-prime key (sp): K = R' = np - 1 rows, the diagonal (q_{np-1} mod q_j) s_hat^2 on column j of row j.
 int Context::gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *evk0_out,
-                           uint32_t *evk1_out)
+                           uint32_t *evk1_out, bool sp)
 {
+    if (sp && !special_prime_ok()) return kErrInvalid;
     if (!evk_secret_ok(sk_packed)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    return gen_keys_chain({KeyChain::kRelin}, 2 * hp.nprimes, sk_packed, nullptr, a_seeds, e_seeds, nullptr, evk0_out,
-                          evk1_out);
+    return gen_keys_chain({KeyChain::kRelin, 0, sp}, evk_rows(sp), sk_packed, nullptr, a_seeds, e_seeds, nullptr,
+                          evk0_out, evk1_out);
+}
+
+// the special-prime entries need a prime to reserve: np >= 2 (the default chains of n = 1024 and 2048 have one prime)
+bool Context::special_prime_ok() const
+{
+    if (hp.nprimes >= 2) return true;
+    set_last_error("the special-prime key switch needs a context of at least two primes");
+    return false;
 }
 
 // the secret key of gen_relin_key / gen_galois_keys: n/4 bytes without code 3
@@ -620,7 +630,9 @@ int Context::gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, cons
         sa.c0 = pk0 + (size_t)j * n;
         sa.j  = (int)j;
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
-        if (relin) SEAMD_HIP(launch_evk_diag(dp, j, chain.kind == KeyChain::kGalois ? chain.elt : 0, s_hat, pk0, nullptr));
+        if (relin && (!chain.sp || j + 1 < np))   // the special prime's own column has no diagonal
+            SEAMD_HIP(launch_evk_diag(dp, j, chain.kind == KeyChain::kGalois ? chain.elt : 0, chain.sp, s_hat, pk0,
+                                      nullptr));
     }
     SEAMD_HIP(hipDeviceSynchronize());
     if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys, K * (n / 4), hipMemcpyDeviceToHost));
@@ -1409,13 +1421,15 @@ int Context::ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const
     return 0;
 }
 
-// One device evaluation-key block [2][R][np][2][n] (kernels/kernel_args.h) from the host's halves k0, k1 [R][np][n]:
+// One device evaluation-key block [2][R][np][2][n] (kernels/kernel_args.h) from the host's halves k0, k1 [R][np][n],
+// R = 2 np rows of a digit key or np - 1 of a special-prime key:
 // staged through `stage`, every column given its Shoup companions on the device (launch_relin_key_rows), and
 // synchronised -- `stage` may be reused, and every call enqueued before has finished.  The caller holds `mu`, has the
 // device current and has checked the words.
-int Context::build_evk(const uint32_t *k0, const uint32_t *k1, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block)
+int Context::build_evk(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage,
+                       DevBuf<uint32_t> &block)
 {
-    const size_t R = 2 * hp.nprimes, slab = R * hp.nprimes * hp.n;
+    const size_t slab = R * hp.nprimes * hp.n;
     SEAMD_HIP(stage.grow(2 * slab));
     SEAMD_HIP(block.grow(4 * slab));
     SEAMD_HIP(hipMemcpy(stage, k0, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -1443,9 +1457,10 @@ bool Context::evk_call_args(Args &a, std::initializer_list<const void *> slabs, 
 // Evaluation keys are public material: validated like a public key (a word >= q_i is refused), then built beside the
 // installed key and swapped in once every call already enqueued has finished (build_evk ends in a synchronisation).
 // Anything refused, or a HIP call that fails, leaves the previous key installed and usable.
-int Context::set_relin_key(const uint32_t *evk0, const uint32_t *evk1)
+int Context::set_relin_key(const uint32_t *evk0, const uint32_t *evk1, bool sp)
 {
-    const size_t R = 2 * hp.nprimes;
+    if (sp && !special_prime_ok()) return kErrInvalid;
+    const size_t R = evk_rows(sp);
     if (const size_t r = first_unreduced_row(hp, evk0, evk1, R); r != R)
     {
         set_last_error("relinearisation key: row " + std::to_string(r) + " holds a word not reduced modulo its prime");
@@ -1454,8 +1469,8 @@ int Context::set_relin_key(const uint32_t *evk0, const uint32_t *evk1)
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
     DevBuf<uint32_t> stage, block;
-    if (int rc = build_evk(evk0, evk1, stage, block)) return rc;
-    d_evk = std::move(block);
+    if (int rc = build_evk(evk0, evk1, R, stage, block)) return rc;
+    (sp ? d_evk_sp : d_evk) = std::move(block);
     return 0;
 }
 
@@ -1486,8 +1501,9 @@ int Context::ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t
 // Galois keys: per element the chain of gen_relin_key on that element's block of seeds, with the diagonal term
 // 2^(15 t) sigma(s_hat) instead of 2^(15 t) s_hat^2 (kernels/ct_ops.hip, k_evk_diag).
 int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, size_t G, const uint8_t *a_seeds,
-                             const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out)
+                             const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out, bool sp)
 {
+    if (sp && !special_prime_ok()) return kErrInvalid;
     if (G == 0 || G > kMaxGaloisKeys)
     {
         set_last_error("Galois keys: between 1 and 64 elements");
@@ -1501,10 +1517,10 @@ int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, siz
         }
     if (!evk_secret_ok(sk_packed)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    const size_t R = 2 * hp.nprimes, slab = R * hp.nprimes * hp.n;
+    const size_t R = evk_rows(sp), slab = R * hp.nprimes * hp.n;
     for (size_t g = 0; g < G; g++)
     {
-        const int rc = gen_keys_chain({KeyChain::kGalois, elts[g]}, R, sk_packed, nullptr, a_seeds + g * R * 64,
+        const int rc = gen_keys_chain({KeyChain::kGalois, elts[g], sp}, R, sk_packed, nullptr, a_seeds + g * R * 64,
                                       e_seeds + g * R * 64, nullptr, gk0_out + g * slab, gk1_out + g * slab);
         if (rc) return rc;
     }
@@ -1512,9 +1528,10 @@ int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, siz
 }
 
 // The whole installed set is replaced, by the rule of set_relin_key: one block per element, swapped in together.
-int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1)
+int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1, bool sp)
 {
-    const size_t n = hp.n, np = hp.nprimes, R = 2 * np, slab = R * np * n;
+    if (sp && !special_prime_ok()) return kErrInvalid;
+    const size_t n = hp.n, np = hp.nprimes, R = evk_rows(sp), slab = R * np * n;
     if (G == 0 || G > kMaxGaloisKeys)
     {
         set_last_error("Galois keys: between 1 and 64 elements");
@@ -1541,9 +1558,71 @@ int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0
     DevBuf<uint32_t> stage;
     std::vector<DevBuf<uint32_t>> blocks(G);
     for (size_t g = 0; g < G; g++)
-        if (int rc = build_evk(gk0 + g * slab, gk1 + g * slab, stage, blocks[g])) return rc;
-    galois_elts.assign(elts, elts + G);
-    d_gk = std::move(blocks);
+        if (int rc = build_evk(gk0 + g * slab, gk1 + g * slab, R, stage, blocks[g])) return rc;
+    (sp ? galois_sp_elts : galois_elts).assign(elts, elts + G);
+    (sp ? d_gk_sp : d_gk) = std::move(blocks);
+    return 0;
+}
+
+// One launch, no scratch, no secret key; reads the installed special-prime key: the relinearisation key (elt 0) or the
+// Galois key of `elt`.  The digit keys do not serve it.  The checks of ct_relin / ct_galois in their order, with the
+// level in [1, np - 1].
+int Context::ct_key_switch_sp(const uint32_t *d_a0, const uint32_t *d_a1, const uint32_t *d_sw, size_t B, size_t primes,
+                              uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    const bool rot = elt != 0;
+    for (const void *p : {(const void *)d_a0, (const void *)d_sw, (const void *)d_out0, (const void *)d_out1})
+        if (!p) return kErrInvalid;
+    if (!rot && !d_a1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes - 1 || B >= ((size_t)1 << 32)) return kErrInvalid;
+    if (!aligned16({d_a0, d_a1, d_sw, d_out0, d_out1})) return kErrInvalid;
+    if (rot && (!(elt & 1) || elt >= 2 * hp.n)) return kErrInvalid;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint32_t *key = nullptr;
+    if (!rot)
+        key = d_evk_sp;
+    else
+        for (size_t g = 0; g < galois_sp_elts.size(); g++)
+            if (galois_sp_elts[g] == elt) key = d_gk_sp[g];
+    if (!key)
+    {
+        set_last_error(rot ? "no special-prime Galois key is installed for element " + std::to_string(elt) +
+                                 " (se_amd_set_galois_keys_sp)"
+                           : std::string("no special-prime relinearisation key is installed (se_amd_set_relin_key_sp)"));
+        return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    KeySwitchSpArgs ka{};
+    ka.a0     = d_a0;
+    ka.a1     = d_a1;
+    ka.sw     = d_sw;
+    ka.out0   = d_out0;
+    ka.out1   = d_out1;
+    ka.key    = key;
+    ka.half   = (hp.nprimes - 1) * hp.nprimes * 2 * hp.n;
+    ka.B      = B;
+    ka.np     = (uint32_t)hp.nprimes;
+    ka.primes = (uint32_t)primes;
+    ka.elt    = elt;
+    SEAMD_HIP(launch_ct_key_switch_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ka, st));
+    return 0;
+}
+
+// Rows 0 .. primes_out-1 of every record: [B][primes_in][n] -> [B][primes_out][n], one pitched asynchronous device copy
+// per slab, no kernel.  Dropping primes changes neither message nor scale.
+int Context::ct_drop_primes(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes_in, size_t primes_out,
+                            uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!d_in0 || !d_out0 || !d_in1 != !d_out1) return kErrInvalid;
+    if (primes_out < 1 || primes_out > primes_in || primes_in > hp.nprimes || B >= ((size_t)1 << 32)) return kErrInvalid;
+    if (!aligned16({d_in0, d_in1, d_out0, d_out1})) return kErrInvalid;
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    const size_t in_row = primes_in * hp.n * sizeof(uint32_t), out_row = primes_out * hp.n * sizeof(uint32_t);
+    SEAMD_HIP(hipMemcpy2DAsync(d_out0, out_row, d_in0, in_row, out_row, B, hipMemcpyDeviceToDevice, st));
+    if (d_in1) SEAMD_HIP(hipMemcpy2DAsync(d_out1, out_row, d_in1, in_row, out_row, B, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 

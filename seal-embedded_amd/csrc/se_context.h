@@ -74,6 +74,11 @@ struct Context
     // (se_amd_set_galois_keys): the installed elements and one block per element
     DevBuf<uint32_t> d_evk;
     std::vector<uint32_t> galois_elts;
+    // the special-prime keys (se_amd_set_relin_key_sp, se_amd_set_galois_keys_sp): the same layout with R' = np - 1
+    // rows, installed sets of their own beside the digit keys
+    DevBuf<uint32_t> d_evk_sp;
+    std::vector<uint32_t> galois_sp_elts;
+    std::vector<DevBuf<uint32_t>> d_gk_sp;
     std::vector<DevBuf<uint32_t>> d_gk;
     DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
     DevBuf<uint32_t> d_kbad;                   // [1 + cap] count + records whose index was out of range
@@ -214,18 +219,26 @@ struct Context
     int ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0, const uint32_t *d_b1,
                size_t Bb, size_t primes, size_t P, const uint32_t *d_ia, const uint32_t *d_ib, uint32_t *d_out0,
                uint32_t *d_out1, uint32_t *d_out2, uint8_t *d_status, hipStream_t st);
+    // sp (here and on the Galois keys): the special-prime key of R' = np - 1 rows instead of the digit key of 2 np
     int gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *evk0_out,
-                      uint32_t *evk1_out);
-    int set_relin_key(const uint32_t *evk0, const uint32_t *evk1);
+                      uint32_t *evk1_out, bool sp = false);
+    int set_relin_key(const uint32_t *evk0, const uint32_t *evk1, bool sp = false);
     int ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t *d_d2, size_t B, size_t primes,
                  uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // slot rotations: Galois keys of G elements (host pointers, [G][R][np][n] per half) and the automorphism fused
     // with its key switch (GaloisArgs); one launch, no scratch
     int gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, size_t G, const uint8_t *a_seeds,
-                        const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out);
-    int set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1);
+                        const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out, bool sp = false);
+    int set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0, const uint32_t *gk1, bool sp = false);
     int ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, uint32_t elt, uint32_t *d_out0,
                   uint32_t *d_out1, hipStream_t st);
+    // special-prime key switch (KeySwitchSpArgs) on level-`primes` records, primes <= np - 1: the relinearisation of
+    // (a0, a1, sw) = (d0, d1, d2) with elt 0, else the rotation of (a0, sw) = (c0, c1) by elt (a1 unused); one launch, no
+    // scratch.  ct_drop_primes: rows 0 .. primes_out-1 of every record of one or two slabs, a pitched device copy
+    int ct_key_switch_sp(const uint32_t *d_a0, const uint32_t *d_a1, const uint32_t *d_sw, size_t B, size_t primes,
+                         uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    int ct_drop_primes(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes_in, size_t primes_out,
+                       uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // hoisted rotations (GaloisHoistArgs): G rotations of every record from one digit decomposition, each to its own
     // output (sum false: outputs [G][B][primes][n]) or summed into one record, with the record itself when add_input
     // (sum true: outputs [B][primes][n]); elts is a host pointer; one launch, no scratch
@@ -278,18 +291,22 @@ struct Context
 private:
     // What the K rows of a gen_keys_chain are: independent key pairs (gen_keys_batch), or the K = 2 np rows of an
     // evaluation key under ONE secret key (sk_in, n/4 bytes) with its diagonal term added to pk0 -- that of the
-    // relinearisation key, or that of the Galois key of `elt`.
+    // relinearisation key, or that of the Galois key of `elt`.  sp: the K = np - 1 rows of a special-prime key, whose
+    // diagonal carries q_{np-1} mod q_j on row j instead of the digit weights on rows 2j, 2j + 1.
     struct KeyChain
     {
         enum Kind { kPairs, kRelin, kGalois } kind;
         uint32_t elt = 0;   // kGalois only
+        bool sp      = false;
     };
     // the launch chain of gen_keys_batch.  The caller holds `mu`.
     int gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
                        const uint8_t *ep_seeds, uint8_t *sk_out, uint32_t *pk0_out, uint32_t *pk1_out);
     // shared by the two evaluation keys and their two calls (se_context.cpp)
     bool evk_secret_ok(const uint8_t *sk_packed) const;
-    int build_evk(const uint32_t *k0, const uint32_t *k1, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block);
+    size_t evk_rows(bool sp) const { return sp ? hp.nprimes - 1 : 2 * hp.nprimes; }
+    bool special_prime_ok() const;
+    int build_evk(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block);
     template <class Args>
     bool evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes) const;
     int decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
