@@ -461,6 +461,53 @@ __device__ __forceinline__ void evk_row_coeffs(uint32_t (&x)[16], const uint32_t
     for (int e = 0; e < 16; e++) x[e] = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
 }
 
+// One quad of a (word, Shoup) row pair, the layout of every key column and plan diagonal (kernel_args.h): the words
+// p[256 m .. 256 m + 3] and their companions N further.
+template <int N>
+__device__ __forceinline__ void load_pair_quad(const uint32_t *p, int m, uint32_t (&w)[4], uint32_t (&s)[4])
+{
+    const uint4 a = *reinterpret_cast<const uint4 *>(p + (m << 8));
+    const uint4 b = *reinterpret_cast<const uint4 *>(p + N + (m << 8));
+    w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w;
+    s[0] = b.x, s[1] = b.y, s[2] = b.z, s[3] = b.w;
+}
+
+// THE multiply-accumulate of every key switch of this file: acc_h += y . key_h[row][column] on both halves h, lazy as
+// described above.  `key` = the thread's first quad of that column in half 0; word(c, k) = the 32-bit y of word 4c + k
+// of the thread's quads (any value: see the range argument).
+template <int LOGN, class Word>
+__device__ __forceinline__ void evk_mac(uint32_t (&acc0)[16], uint32_t (&acc1)[16], const uint32_t *key, size_t half,
+                                        uint32_t q, Word word)
+{
+    constexpr int N      = XformGeom<LOGN>::N;
+    const uint32_t two_q = q << 1;
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        uint32_t w0[4], s0[4], w1[4], s1[4];
+        load_pair_quad<N>(key, c, w0, s0);
+        load_pair_quad<N>(key + half, c, w1, s1);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const int e       = 4 * c + k;
+            const uint32_t y  = word(c, k);
+            const uint32_t u0 = acc0[e] + mul_shoup_lazy(y, w0[k], s0[k], q);
+            const uint32_t u1 = acc1[e] + mul_shoup_lazy(y, w1[k], s1[k], q);
+            acc0[e]           = min(u0, u0 - two_q);
+            acc1[e]           = min(u1, u1 - two_q);
+        }
+    }
+}
+
+// the same on y in quad layout in registers
+template <int LOGN>
+__device__ __forceinline__ void evk_mac(uint32_t (&acc0)[16], uint32_t (&acc1)[16], const uint32_t (&y)[16],
+                                        const uint32_t *key, size_t half, uint32_t q)
+{
+    evk_mac<LOGN>(acc0, acc1, key, half, q, [&](int c, int k) { return y[4 * c + k]; });
+}
+
 // k0: column i of key row 0 (a key row is np columns of 2 N words); rw: the NTT roots of prime i.  A: RelinArgs or
 // GaloisArgs (key layout: half, np).
 template <int LOGN, class Args>
@@ -468,8 +515,7 @@ __device__ __forceinline__ void evk_digits(const uint32_t (&x)[16], uint32_t (&a
                                            const Args &A, const uint32_t *k0, uint32_t j, const uint32_t *rw,
                                            uint32_t qi, uint32_t *lds, int t)
 {
-    constexpr int N       = XformGeom<LOGN>::N;
-    const uint32_t two_qi = qi << 1;
+    constexpr int N = XformGeom<LOGN>::N;
     // the two digits take the same code with a shift of 0 resp. 15: not unrolled, one NTT body in the kernel
 #pragma unroll 1
     for (uint32_t dg = 0; dg < 2; dg++)
@@ -482,25 +528,7 @@ __device__ __forceinline__ void evk_digits(const uint32_t (&x)[16], uint32_t (&a
         tile_to_quads<16>(y, lds, td);
         // key rows 2j + dg of both halves, a quad of words and of Shoup companions at a time
         const uint32_t *key = k0 + (size_t)(2 * j + dg) * A.np * 2 * N + quad_index(td, 0);
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-        {
-            const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
-            const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
-            const uint4 w1 = *reinterpret_cast<const uint4 *>(key + A.half + (c << 8));
-            const uint4 s1 = *reinterpret_cast<const uint4 *>(key + A.half + N + (c << 8));
-            const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
-            const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-            {
-                const int e       = 4 * c + k;
-                const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], qi);
-                const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], qi);
-                acc0[e]           = min(u0, u0 - two_qi);
-                acc1[e]           = min(u1, u1 - two_qi);
-            }
-        }
+        evk_mac<LOGN>(acc0, acc1, y, key, A.half, qi);
         __syncthreads();
     }
 }
@@ -510,7 +538,7 @@ __device__ __forceinline__ void evk_digits(const uint32_t (&x)[16], uint32_t (&a
 //   out0[b][i] = d0[b][i] + sum_{j < L, t < 2} NTT_i(D_{j,t}) . evk0[2j + t][i]  mod q_i   (out1: d1 and evk1),
 // D_{j,t} = the t-th 15-bit digit of the canonical natural-order coefficients of INTT_j(d2[b][j]) (n^-1 included): the
 // key switch above on the rows of d2, and the two addends in the epilogue.
-// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// grid evk_grid(B, L).
 // ------------------------------------------------------------------------------------------
 template <int LOGN>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin(const DevParams P, const DevTables T,
@@ -551,14 +579,21 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_relin(const Dev
     }
 }
 
+// The grid of every key-switch kernel: (min(B, 2^31 - 1), primes); a workgroup walks the records blockIdx.x,
+// blockIdx.x + gridDim.x, ...
+static dim3 evk_grid(size_t B, uint32_t primes)
+{
+    return dim3((unsigned)(B < 0x7fffffffu ? B : 0x7fffffffu), primes);
+}
+
 hipError_t launch_ct_relin(const DevParams &P, const DevTables &T, const RelinArgs &A, hipStream_t st)
 {
     if (A.B == 0) return hipSuccess;
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
         using G         = XformGeom<L>;
-        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
-        return launch(k_ct_relin<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+        return launch(k_ct_relin<L>, evk_grid(A.B, A.primes), dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st,
+                      P, T, A);
     });
 }
 
@@ -607,8 +642,17 @@ hipError_t launch_relin_key_rows(const DevParams &P, const uint32_t *in, uint32_
 // LDS stays the exchange plane alone (n <= XformGeom::SLOTS words for either use).  The only addresses formed from data
 // are formed from g, a launch argument the host has checked (odd, below 2n): every target is masked to [0, n), and no
 // word of a slab or of the key is used as an address.
-// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// grid evk_grid(B, L).
 // ------------------------------------------------------------------------------------------
+// src_g of the word whose (2 brev(k) + 1) g is u (any bits above 2n are dropped by the shift, the odd bit by the mask):
+// the form of the hoisted kernels.  galois_src below keeps its own: as galois_src_of((2 brev(k) + 1) g), with the scatter
+// shared too, k_ct_galois_sp<12> ran 10.597 ms against the parent's 10.566 (spread of the parent's rounds 0.025).
+template <int LOGN>
+__device__ __forceinline__ uint32_t galois_src_of(uint32_t u)
+{
+    return (__brev(u) >> (31 - LOGN)) & ((1u << LOGN) - 1);
+}
+
 template <int LOGN>
 __device__ __forceinline__ uint32_t galois_src(uint32_t k, uint32_t g)
 {
@@ -616,6 +660,38 @@ __device__ __forceinline__ uint32_t galois_src(uint32_t k, uint32_t g)
     const uint32_t r     = __brev(k) >> (32 - LOGN);
     const uint32_t u     = ((2 * r + 1) * g) & (2 * N - 1);   // odd: (2r + 1) g < 2^30
     return __brev(u >> 1) >> (32 - LOGN);
+}
+
+// A row in quad layout (load_quads) parked in the plane as it lies in memory, word k at lds[k]: four ds_write_b128.  k4 =
+// the thread's first quad (quad_index(t, 0)); word 4 m + k of the thread is k4 + (m << 8) + k.
+__device__ __forceinline__ void park_row_quads(const uint32_t (&c)[16], uint32_t *lds, int k4)
+{
+#pragma unroll
+    for (int m = 0; m < 4; m++)
+        *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+}
+
+// The thread's 16 words of sigma_g of a parked row: word k = lds[src_g(k)].
+template <int LOGN>
+__device__ __forceinline__ void gather_row(uint32_t (&c)[16], const uint32_t *lds, int k4, uint32_t g)
+{
+#pragma unroll
+    for (int e = 0; e < 16; e++) c[e] = lds[galois_src<LOGN>((uint32_t)(k4 + ((e >> 2) << 8) + (e & 3)), g)];
+}
+
+// The row `row` of a record as it lies in memory, in quad layout; GALOIS: sigma_g of it, word k = row[src_g(k)], through
+// the plane (which must be free; ends with the plane read but not yet released: the caller's next barrier releases it).
+template <int LOGN, bool GALOIS>
+__device__ __forceinline__ void load_row_sigma(uint32_t (&c)[16], const uint32_t *row, uint32_t g, uint32_t *lds, int te)
+{
+    load_quads(c, row, te);
+    if constexpr (GALOIS)
+    {
+        const int k4 = quad_index(te, 0);
+        park_row_quads(c, lds, k4);
+        __syncthreads();
+        gather_row<LOGN>(c, lds, k4, g);
+    }
 }
 
 template <int LOGN>
@@ -645,7 +721,8 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois(const De
             const uint32_t qj = P.q[j];
             uint32_t x[16];
             evk_row_coeffs<LOGN>(x, A.c1 + rec + (size_t)j * N, j, P, T, lds, tj);
-            // sigma: coefficient k -> position k g mod n, negated when k g mod 2n >= n (k g < 2^29)
+            // sigma: coefficient k -> position k g mod n, negated when k g mod 2n >= n (k g < 2^29); 0 stays 0.  This
+            // and sp_row_digit keep a copy each: as one inlined helper the scatter costs both kernels 24 - 28 instructions
 #pragma unroll
             for (int e = 0; e < 16; e++)
             {
@@ -658,18 +735,14 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois(const De
             __syncthreads();
             evk_digits<LOGN>(x, acc0, acc1, A, k0, j, rw, qi, lds, t);
         }
-        // sigma(c0) row i: the row as it lies in memory goes into the plane, word k at lds[k]; gathered at src(k)
         const int te   = opaque_index(t);
         const size_t o = rec + (size_t)i * N;
         const int k4   = quad_index(te, 0);
         uint32_t c[16];
         load_quads(c, A.c0 + o, te);
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-            *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+        park_row_quads(c, lds, k4);   // sigma(c0) row i
         __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; e++) c[e] = lds[galois_src<LOGN>((uint32_t)(k4 + ((e >> 2) << 8) + (e & 3)), g)];
+        gather_row<LOGN>(c, lds, k4, g);
 #pragma unroll
         for (int e = 0; e < 16; e++)
         {
@@ -688,8 +761,8 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
         using G         = XformGeom<L>;
-        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
-        return launch(k_ct_galois<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+        return launch(k_ct_galois<L>, evk_grid(A.B, A.primes), dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st,
+                      P, T, A);
     });
 }
 
@@ -707,7 +780,7 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
 // Relinearisation: d = d2, out_k = d_k + ks_k.  Rotation: d = sigma(c1), out0 = sigma(c0) + ks_0, out1 = ks_1.
 // The geometry of k_ct_relin: one workgroup of n/16 threads per (record, output prime i < L), LDS the exchange plane
 // alone, no scratch, no global temporary.  A workgroup makes two passes over the input rows with the same code
-// (sp_row_mac), first modulo P against key column p, then modulo q_i against key column i:
+// (sp_row_digit, evk_mac), first modulo P against key column p, then modulo q_i against key column i:
 //   pass 0, per j: evk_row_coeffs (the INTT mod q_j of the digit kernels) [-> sigma, the LDS scatter of k_ct_galois] ->
 //     centre and reduce mod P (one conditional add: |D_j| < q_j / 2 < every prime of the chain) -> ntt_tiles mod P ->
 //     tile_to_quads -> multiply-accumulate against row j, column p of both key halves;
@@ -715,68 +788,20 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
 //     P / 2 < q_i: one conditional add) -> ntt_tiles mod q_i -> tile_to_quads -> the accumulator of pass 1 starts at
 //     2 q_i - NTT(delta), lazy in (0, 2 q_i];
 //   pass 1, per j != i: the coefficients AGAIN -> reduce mod q_i -> ntt_tiles mod q_i -> multiply-accumulate against
-//     column i; row i enters as it lies in memory (rotation: gathered through src_g, as sigma(c0) is);
-//   epilogue: . P^-1 (Shoup pair), + d_k resp. the sigma(c0) gather of k_ct_galois, canonical.
+//     column i; row i enters as it lies in memory (rotation: load_row_sigma, as sigma(c0) does);
+//   epilogue: . P^-1 (Shoup pair), + d_k resp. sigma(c0), canonical.
 // 2 L - 1 INTTs and 2 L - 1 NTTs of rows, and 2 + 2 for the two deltas: 4 L + 2 transforms per workgroup against 3 L of
 // the digit kernels.  Keeping the L centred rows of pass 0 instead would save L - 1 INTTs and cost 16 (L - 1) registers
 // per thread or a global temporary; the live set here is two accumulator tiles and one row, below that of evk_digits
 // (two accumulators, the coefficients AND a digit).
-// Lazy ranges.  A key word is below q (the setters refuse others), so mul_shoup_lazy(y, w, .) is in [0, 2 q) for any
-// 32-bit y and an accumulator in [0, 2 q] plus one product is below 4 q < 2^32; min(s, s - 2 q) brings it below 2 q.
-// The accumulators of pass 0 enter intt_tiles in [0, 2 P), which is its input range.
-// Addresses: as in k_ct_galois the only addresses formed from data are formed from the element, which the host has
-// checked (odd, below 2n), and every target is masked to [0, n); no word of a slab or of a key is used as an address.
+// Lazy ranges: those of evk_mac (above evk_row_coeffs), with an accumulator entering in [0, 2 q] instead of [0, 2 q):
+// plus one product it is still below 4 q < 2^32.  The accumulators of pass 0 enter intt_tiles in [0, 2 P), which is its
+// input range.
+// Addresses: as in k_ct_galois (formed from the checked element only, masked to [0, n)).
 // Key block [2][R'][np][2][n], R' = np - 1 rows (one per data prime) of the context's np columns, Shoup companions behind
 // every column (k_relin_key_rows): row j, column c of half h at key + h half + (j np + c) 2 n.
-// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// grid evk_grid(B, L).
 // ------------------------------------------------------------------------------------------
-// acc_k += y . key_k[row][column] on both halves, y in quad layout; `key` = the thread's first quad of that column in
-// half 0.  The body of evk_digits' multiply-accumulate.
-template <int LOGN>
-__device__ __forceinline__ void sp_mac(uint32_t (&acc0)[16], uint32_t (&acc1)[16], const uint32_t (&y)[16],
-                                       const uint32_t *key, size_t half, uint32_t q)
-{
-    constexpr int N      = XformGeom<LOGN>::N;
-    const uint32_t two_q = q << 1;
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-    {
-        const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
-        const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
-        const uint4 w1 = *reinterpret_cast<const uint4 *>(key + half + (c << 8));
-        const uint4 s1 = *reinterpret_cast<const uint4 *>(key + half + N + (c << 8));
-        const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
-        const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-        {
-            const int e       = 4 * c + k;
-            const uint32_t u0 = acc0[e] + mul_shoup_lazy(y[e], w0v[k], s0v[k], q);
-            const uint32_t u1 = acc1[e] + mul_shoup_lazy(y[e], w1v[k], s1v[k], q);
-            acc0[e]           = min(u0, u0 - two_q);
-            acc1[e]           = min(u1, u1 - two_q);
-        }
-    }
-}
-
-// The row `row` of a record as it lies in memory, in quad layout; GALOIS: sigma_g of it, word k = row[src_g(k)], through
-// the plane (which must be free; ends with the plane read but not yet released: the caller's next barrier releases it).
-template <int LOGN, bool GALOIS>
-__device__ __forceinline__ void sp_ntt_row(uint32_t (&c)[16], const uint32_t *row, uint32_t g, uint32_t *lds, int te)
-{
-    load_quads(c, row, te);
-    if constexpr (GALOIS)
-    {
-        const int k4 = quad_index(te, 0);
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-            *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; e++) c[e] = lds[galois_src<LOGN>((uint32_t)(k4 + ((e >> 2) << 8) + (e & 3)), g)];
-    }
-}
-
 // NTT_c(D_j mod q) in quad layout, q = q_c the prime of key column c and rw its roots: the centred coefficients of input
 // row j (GALOIS: of sigma_g of it) reduced mod q and transformed.  Ends with the plane in use by the wave-local
 // transpose: the caller's barrier after the multiply-accumulate releases it.
@@ -785,13 +810,13 @@ __device__ __forceinline__ void sp_row_digit(uint32_t (&x)[16], const uint32_t *
                                              const uint32_t *rw, const DevParams &P, const DevTables &T, uint32_t *lds,
                                              int t)
 {
-    constexpr int N   = XformGeom<LOGN>::N;
     const int tj      = opaque_index(t);
     const uint32_t qj = P.q[j], hj = qj >> 1, up = q - qj;   // up: mod 2^32 where q < q_j
     evk_row_coeffs<LOGN>(x, row, j, P, T, lds, tj);
+    constexpr int N = XformGeom<LOGN>::N;
     if constexpr (GALOIS)
     {
-        // sigma: coefficient k -> position k g mod n, negated when k g mod 2n >= n (k g < 2^29); 0 stays 0
+        // sigma, the scatter of k_ct_galois (its own copy: see there)
 #pragma unroll
         for (int e = 0; e < 16; e++)
         {
@@ -841,11 +866,11 @@ __device__ __forceinline__ void ct_key_switch_sp(const DevParams &P, const DevTa
             {
                 uint32_t y[16];
                 if (pass && j == i)
-                    sp_ntt_row<LOGN, GALOIS>(y, A.sw + rec + (size_t)i * N, g, lds, opaque_index(t));
+                    load_row_sigma<LOGN, GALOIS>(y, A.sw + rec + (size_t)i * N, g, lds, opaque_index(t));
                 else
                     sp_row_digit<LOGN, GALOIS>(y, A.sw + rec + (size_t)j * N, j, g, q, rw, P, T, lds, t);
                 const uint32_t *key = A.key + ((size_t)j * A.np + col) * 2 * N + quad_index(opaque_index(t), 0);
-                sp_mac<LOGN>(acc0, acc1, y, key, A.half, q);
+                evk_mac<LOGN>(acc0, acc1, y, key, A.half, q);
                 __syncthreads();
             }
             if (pass == 0)
@@ -887,7 +912,7 @@ __device__ __forceinline__ void ct_key_switch_sp(const DevParams &P, const DevTa
         const size_t o = rec + (size_t)i * N;
         const uint32_t w = R.inv[i], wp = R.inv_sh[i];
         uint32_t c[16];
-        sp_ntt_row<LOGN, GALOIS>(c, A.a0 + o, g, lds, te);
+        load_row_sigma<LOGN, GALOIS>(c, A.a0 + o, g, lds, te);
 #pragma unroll
         for (int e = 0; e < 16; e++) acc0[e] = csub(csub(mul_shoup_lazy(acc0[e], w, wp, qi), qi) + c[e], qi);
         store_quads(A.out0 + o, acc0, te);
@@ -934,7 +959,7 @@ hipError_t launch_ct_key_switch_sp(const DevParams &P, const DevTables &T, const
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
         using G         = XformGeom<L>;
-        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        const dim3 grid    = evk_grid(A.B, A.primes);
         const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
         return A.elt ? launch(k_ct_galois_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
                      : launch(k_ct_relin_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
@@ -966,10 +991,9 @@ hipError_t launch_ct_key_switch_sp(const DevParams &P, const DevTables &T, const
 // src_g(k) in registers: brev is additive over disjoint bit fields, so with r4 = brev(k4) of the thread's first quad and
 // the compile-time offset d of a word in the quads, (2 brev(k4 + d) + 1) g = (2 r4 + 1) g + 2 brev(d) g: one per-thread
 // product per element, a scalar product per word, then v_add, v_bfrev and the shift / mask to the LDS address.
-// The only addresses formed from data are formed from the elements, launch arguments the host has checked (odd, below
-// 2n): every target is masked to [0, n), and no word of a slab or of a key is used as an address.  The elements and
-// their key blocks are read from the argument block with a workgroup-uniform index (scalar loads).
-// grid (min(B, 2^31 - 1), L); a workgroup walks the records blockIdx.x, blockIdx.x + gridDim.x, ...
+// Addresses: as in k_ct_galois, per element.  The elements and their key blocks are read from the argument block with a
+// workgroup-uniform index (scalar loads).
+// grid evk_grid(B, L).
 // ------------------------------------------------------------------------------------------
 constexpr int kHoistGroup = 2;   // elements in flight of the many form: the largest without scratch at every degree
 // n = 16384 is one workgroup of 16 waves, 4 per SIMD: 128 VGPRs at most, and two accumulator pairs beside the
@@ -978,13 +1002,6 @@ constexpr int kHoistGroup = 2;   // elements in flight of the many form: the lar
 // back the slots it wrote itself (lane-consecutive, no conflict, no barrier).  One workgroup per CU either way.
 template <int LOGN, bool SUM>
 constexpr bool kHoistPark = LOGN == 14 && !SUM;
-
-// src_g of the word whose (2 brev(k) + 1) g is u (any bits above 2n are dropped by the shift, the odd bit by the mask)
-template <int LOGN>
-__device__ __forceinline__ uint32_t galois_src_of(uint32_t u)
-{
-    return (__brev(u) >> (31 - LOGN)) & ((1u << LOGN) - 1);
-}
 
 // the 16 words of the thread's quads of sigma_g(row), row parked in the plane with word k at plane[k]; word 4 c + k of
 // the thread is k4 + (c << 8) + k.  u0 = (2 brev(k4) + 1) g < 2^30, the offsets add less than 2^30.
@@ -995,35 +1012,14 @@ __device__ __forceinline__ uint32_t hoist_word(const uint32_t *plane, uint32_t u
     return plane[galois_src_of<LOGN>(u0 + 2 * rd * g)];
 }
 
-// One element's share of one digit: acc += sigma_g(NTT_i(D))[k] . key[k] on both halves; `key` = the thread's first quad
-// of row 2j + t, column i of the element's block.
+// One element's share of one digit: acc += sigma_g(NTT_i(D))[k] . key[k] on both halves (evk_mac on gathered words);
+// `key` = the thread's first quad of row 2j + t, column i of the element's block.
 template <int LOGN>
 __device__ __forceinline__ void hoist_mac(uint32_t (&acc0)[16], uint32_t (&acc1)[16], const uint32_t *plane,
                                           const uint32_t *key, size_t half, uint32_t g, uint32_t r4, uint32_t qi)
 {
-    constexpr int N       = XformGeom<LOGN>::N;
-    const uint32_t two_qi = qi << 1;
-    const uint32_t u0     = (2 * r4 + 1) * g;
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-    {
-        const uint4 w0 = *reinterpret_cast<const uint4 *>(key + (c << 8));
-        const uint4 s0 = *reinterpret_cast<const uint4 *>(key + N + (c << 8));
-        const uint4 w1 = *reinterpret_cast<const uint4 *>(key + half + (c << 8));
-        const uint4 s1 = *reinterpret_cast<const uint4 *>(key + half + N + (c << 8));
-        const uint32_t w0v[4] = {w0.x, w0.y, w0.z, w0.w}, s0v[4] = {s0.x, s0.y, s0.z, s0.w};
-        const uint32_t w1v[4] = {w1.x, w1.y, w1.z, w1.w}, s1v[4] = {s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-        {
-            const int e       = 4 * c + k;
-            const uint32_t y  = hoist_word<LOGN>(plane, u0, g, c, k);
-            const uint32_t v0 = acc0[e] + mul_shoup_lazy(y, w0v[k], s0v[k], qi);
-            const uint32_t v1 = acc1[e] + mul_shoup_lazy(y, w1v[k], s1v[k], qi);
-            acc0[e]           = min(v0, v0 - two_qi);
-            acc1[e]           = min(v1, v1 - two_qi);
-        }
-    }
+    evk_mac<LOGN>(acc0, acc1, key, half, qi,
+                  [=](int c, int k) { return hoist_word<LOGN>(plane, (2 * r4 + 1) * g, g, c, k); });
 }
 
 // The digit loop of a pass: for every input prime the coefficients of the c1 row, per digit its transform mod q_i parked
@@ -1120,9 +1116,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_hoist(co
             const int k4   = quad_index(te, 0);
             uint32_t c[16];
             load_quads(c, A.c0 + o, te);
-#pragma unroll
-            for (int m = 0; m < 4; m++)
-                *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+            park_row_quads(c, lds, k4);
             __syncthreads();
             if constexpr (SUM)
             {
@@ -1179,7 +1173,7 @@ hipError_t launch_ct_galois_hoist(const DevParams &P, const DevTables &T, const 
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
         using G         = XformGeom<L>;
-        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
+        const dim3 grid    = evk_grid(A.B, A.primes);
         const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t), park = (size_t)G::N * sizeof(uint32_t);
         return A.sum ? launch(k_ct_galois_hoist<L, true>, grid, dim3(G::THREADS), plane, st, P, T, A)
                      : launch(k_ct_galois_hoist<L, false>, grid, dim3(G::THREADS),
@@ -1228,18 +1222,15 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_lintrans(const 
         const uint32_t *diag0 = A.diag0 ? A.diag0 + dcol : nullptr;
         uint32_t c[16];
         load_quads(c, A.c0 + o, te);
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-            *reinterpret_cast<uint4 *>(lds + k4 + (m << 8)) = make_uint4(c[4 * m], c[4 * m + 1], c[4 * m + 2], c[4 * m + 3]);
+        park_row_quads(c, lds, k4);
         __syncthreads();
         if (diag0)
         {
 #pragma unroll
             for (int m = 0; m < 4; m++)
             {
-                const uint4 w = *reinterpret_cast<const uint4 *>(diag0 + (m << 8));
-                const uint4 s = *reinterpret_cast<const uint4 *>(diag0 + N + (m << 8));
-                const uint32_t wv[4] = {w.x, w.y, w.z, w.w}, sv[4] = {s.x, s.y, s.z, s.w};
+                uint32_t wv[4], sv[4];
+                load_pair_quad<N>(diag0, m, wv, sv);
 #pragma unroll
                 for (int k = 0; k < 4; k++) c[4 * m + k] = mul_shoup_lazy(c[4 * m + k], wv[k], sv[k], qi);
             }
@@ -1257,9 +1248,8 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_lintrans(const 
 #pragma unroll
             for (int m = 0; m < 4; m++)
             {
-                const uint4 w = *reinterpret_cast<const uint4 *>(d + (m << 8));
-                const uint4 s = *reinterpret_cast<const uint4 *>(d + N + (m << 8));
-                const uint32_t wv[4] = {w.x, w.y, w.z, w.w}, sv[4] = {s.x, s.y, s.z, s.w};
+                uint32_t wv[4], sv[4];
+                load_pair_quad<N>(d, m, wv, sv);
 #pragma unroll
                 for (int k = 0; k < 4; k++)
                 {
@@ -1277,9 +1267,8 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_lintrans(const 
 #pragma unroll
             for (int m = 0; m < 4; m++)
             {
-                const uint4 w = *reinterpret_cast<const uint4 *>(diag0 + (m << 8));
-                const uint4 s = *reinterpret_cast<const uint4 *>(diag0 + N + (m << 8));
-                const uint32_t wv[4] = {w.x, w.y, w.z, w.w}, sv[4] = {s.x, s.y, s.z, s.w};
+                uint32_t wv[4], sv[4];
+                load_pair_quad<N>(diag0, m, wv, sv);
 #pragma unroll
                 for (int k = 0; k < 4; k++)
                     acc1[0][4 * m + k] += mul_shoup_lazy(c[4 * m + k], wv[k], sv[k], qi);
@@ -1298,8 +1287,7 @@ hipError_t launch_ct_lintrans(const DevParams &P, const DevTables &T, const Lint
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
         using G         = XformGeom<L>;
-        const dim3 grid((unsigned)(A.B < 0x7fffffffu ? A.B : 0x7fffffffu), A.primes);
-        return launch(k_ct_lintrans<L>, grid, dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+        return launch(k_ct_lintrans<L>, evk_grid(A.B, A.primes), dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
     });
 }
 

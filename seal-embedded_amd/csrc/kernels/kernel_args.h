@@ -182,11 +182,12 @@ struct MulArgs
     uint32_t primes;
 };
 hipError_t launch_ct_mul(const DevParams &, const MulArgs &, hipStream_t);
-// The key switch of ct_ops.hip, shared by k_ct_relin and k_ct_galois.  `key` is one device evaluation-key block, built
+// The key switch of ct_ops.hip, shared by every kernel from here to LintransArgs (evk_row_coeffs, evk_digits, evk_mac;
+// grid evk_grid(B, primes)).  `key` is one device evaluation-key block, built
 // by Context::build_evk from the host's two halves: [2][R][np][2][n], R = 2 np rows of the CONTEXT's np columns, each
 // column a row of n key words followed by the row of their Shoup companions floor(w 2^32 / q_i); half 1 starts `half`
-// words behind half 0.  Both argument blocks name the fields the shared device code reads alike: key, half, np, primes,
-// B.
+// words behind half 0.  Every argument block names the fields the shared device code reads alike: key, half, np,
+// primes, B.
 // Relinearisation (k_ct_relin): level-`primes` (d0, d1, d2) -> (out0, out1) of the same level.
 //   out0[b][i] = d0[b][i] + sum_{j < primes, t < 2} NTT_i(D_{j,t}) . key0[2j + t][i]   (out1: d1, key1)   mod q_i,
 // D_{j,t} = the t-th 15-bit digit of the canonical coefficients of INTT_j(d2[b][j]).
@@ -245,7 +246,7 @@ hipError_t launch_ct_key_switch_sp(const DevParams &, const DevTables &, const R
 // Many form (sum = 0): out[e][b] = rot[elt[e]], outputs [G][B][primes][n].  Sum form (sum = 1): out[b] = add_input .
 // (c0, c1)[b] + sum_e rot[elt[e]], outputs [B][primes][n].  The elements and the key block of each travel in the
 // argument block (kernarg): no device table, no scratch.
-constexpr uint32_t kHoistMaxElts = 64;   // kMaxGaloisKeys (se_context.h)
+constexpr uint32_t kMaxGaloisKeys = 64;   // elements of one installed set, and of one call (SE_AMD_MAX_GALOIS_KEYS)
 struct GaloisHoistArgs
 {
     const uint32_t *c0, *c1;        // [B][primes][n]
@@ -254,10 +255,10 @@ struct GaloisHoistArgs
     size_t B;
     uint32_t np;                    // columns of a key row (the context's primes)
     uint32_t primes;                // 1 .. np
-    uint32_t G;                     // 1 .. kHoistMaxElts
+    uint32_t G;                     // 1 .. kMaxGaloisKeys
     uint32_t sum, add_input;        // 0 / 1 each; add_input only with sum
-    uint32_t elt[kHoistMaxElts];    // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kHoistMaxElts];   // the device key block of elt[e]
+    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kMaxGaloisKeys];   // the device key block of elt[e]
 };
 hipError_t launch_ct_galois_hoist(const DevParams &, const DevTables &, const GaloisHoistArgs &, hipStream_t);
 // Linear transform (k_ct_lintrans): the sum form above with a plaintext weight per element, the diagonal method
@@ -273,11 +274,11 @@ struct LintransArgs
     size_t B;
     uint32_t np;                    // columns of a key row (the context's primes)
     uint32_t primes;                // 1 .. the plan's levels
-    uint32_t G;                     // 1 .. kHoistMaxElts
+    uint32_t G;                     // 1 .. kMaxGaloisKeys
     const uint32_t *diag;           // [G][np][2][n]
     const uint32_t *diag0;          // [np][2][n], or NULL: the record itself does not enter
-    uint32_t elt[kHoistMaxElts];    // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kHoistMaxElts];   // the folded key block of entry e
+    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kMaxGaloisKeys];   // the folded key block of entry e
 };
 hipError_t launch_ct_lintrans(const DevParams &, const DevTables &, const LintransArgs &, hipStream_t);
 // Plan set-up (k_lintrans_fold), one entry per launch.  d = diag_in[i][k] mod q_i for columns i < pt, 0 beyond (any

@@ -1439,19 +1439,61 @@ int Context::build_evk(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<
     return 0;
 }
 
-// What ct_relin and ct_galois check and fill alike: every slab pointer present and 16-byte aligned, the level and the
-// batch in range; then the fields of the argument block that describe the batch and the key layout.
+// What every key-switch call checks and fills alike: every slab pointer present and 16-byte aligned, the level and the
+// batch in range; then the fields of the argument block that describe the batch and the key layout.  sp: a
+// special-prime key, whose records have at most np - 1 primes and whose halves have np - 1 rows.
 template <class Args>
-bool Context::evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes) const
+bool Context::evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes, bool sp) const
 {
     for (const void *p : slabs)
         if (!p) return false;
-    if (primes < 1 || primes > hp.nprimes || B >= ((size_t)1 << 32) || !aligned16(slabs)) return false;
-    a.half   = (size_t)2 * hp.nprimes * hp.nprimes * 2 * hp.n;
+    if (primes < 1 || primes > hp.nprimes - sp || B >= ((size_t)1 << 32) || !aligned16(slabs)) return false;
+    a.half   = evk_rows(sp) * hp.nprimes * 2 * hp.n;
     a.B      = B;
     a.np     = (uint32_t)hp.nprimes;
     a.primes = (uint32_t)primes;
     return true;
+}
+
+const uint32_t *EvalKeys::find(uint32_t elt) const
+{
+    for (size_t g = 0; g < elts.size(); g++)
+        if (elts[g] == elt) return galois[g];
+    return nullptr;
+}
+
+// The elements of a call: 1 .. kMaxGaloisKeys of them (else the last error is `count_msg`), each one a Galois element;
+// distinct: and none listed twice (an installed set).
+bool Context::galois_elts_ok(const uint32_t *elts, size_t G, const char *count_msg, bool distinct) const
+{
+    if (!elts || G == 0 || G > kMaxGaloisKeys)
+    {
+        set_last_error(count_msg);
+        return false;
+    }
+    for (size_t g = 0; g < G; g++)
+    {
+        bool bad = !galois_elt_ok(elts[g]);
+        for (size_t h = 0; distinct && h < g; h++) bad |= elts[h] == elts[g];
+        if (bad)
+        {
+            set_last_error("Galois element " + std::to_string(elts[g]) +
+                           (distinct ? " is even, not below 2n, or listed twice" : " is not odd and below 2n"));
+            return false;
+        }
+    }
+    return true;
+}
+
+// The installed block of `elt` in a family; without one NULL and the last error set: the caller returns kErrNoKey.  The
+// caller holds `mu`.
+const uint32_t *Context::galois_key(bool sp, uint32_t elt) const
+{
+    const uint32_t *key = evk[sp].find(elt);
+    if (!key)
+        set_last_error(std::string("no ") + (sp ? "special-prime " : "") + "Galois key is installed for element " +
+                       std::to_string(elt) + (sp ? " (se_amd_set_galois_keys_sp)" : " (se_amd_set_galois_keys)"));
+    return key;
 }
 
 // Evaluation keys are public material: validated like a public key (a word >= q_i is refused), then built beside the
@@ -1470,7 +1512,7 @@ int Context::set_relin_key(const uint32_t *evk0, const uint32_t *evk1, bool sp)
     SEAMD_HIP(hipSetDevice(device));
     DevBuf<uint32_t> stage, block;
     if (int rc = build_evk(evk0, evk1, R, stage, block)) return rc;
-    (sp ? d_evk_sp : d_evk) = std::move(block);
+    evk[sp].relin = std::move(block);
     return 0;
 }
 
@@ -1479,7 +1521,7 @@ int Context::ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t
                       uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
-    if (!d_evk)
+    if (!evk[0].relin)
     {
         set_last_error("relinearisation needs an evaluation key (se_amd_set_relin_key)");
         return kErrNoKey;
@@ -1493,7 +1535,7 @@ int Context::ct_relin(const uint32_t *d_d0, const uint32_t *d_d1, const uint32_t
     ra.d2   = d_d2;
     ra.out0 = d_out0;
     ra.out1 = d_out1;
-    ra.key  = d_evk;
+    ra.key  = evk[0].relin;
     SEAMD_HIP(launch_ct_relin(dp, dt, ra, st));
     return 0;
 }
@@ -1504,17 +1546,7 @@ int Context::gen_galois_keys(const uint8_t *sk_packed, const uint32_t *elts, siz
                              const uint8_t *e_seeds, uint32_t *gk0_out, uint32_t *gk1_out, bool sp)
 {
     if (sp && !special_prime_ok()) return kErrInvalid;
-    if (G == 0 || G > kMaxGaloisKeys)
-    {
-        set_last_error("Galois keys: between 1 and 64 elements");
-        return kErrInvalid;
-    }
-    for (size_t g = 0; g < G; g++)
-        if (!(elts[g] & 1) || elts[g] >= 2 * hp.n)
-        {
-            set_last_error("Galois element " + std::to_string(elts[g]) + " is not odd and below 2n");
-            return kErrInvalid;
-        }
+    if (!galois_elts_ok(elts, G, "Galois keys: between 1 and 64 elements")) return kErrInvalid;
     if (!evk_secret_ok(sk_packed)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
     const size_t R = evk_rows(sp), slab = R * hp.nprimes * hp.n;
@@ -1532,21 +1564,7 @@ int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0
 {
     if (sp && !special_prime_ok()) return kErrInvalid;
     const size_t n = hp.n, np = hp.nprimes, R = evk_rows(sp), slab = R * np * n;
-    if (G == 0 || G > kMaxGaloisKeys)
-    {
-        set_last_error("Galois keys: between 1 and 64 elements");
-        return kErrInvalid;
-    }
-    for (size_t g = 0; g < G; g++)
-    {
-        bool bad = !(elts[g] & 1) || elts[g] >= 2 * n;
-        for (size_t h = 0; h < g; h++) bad |= elts[h] == elts[g];
-        if (bad)
-        {
-            set_last_error("Galois element " + std::to_string(elts[g]) + " is even, not below 2n, or listed twice");
-            return kErrInvalid;
-        }
-    }
+    if (!galois_elts_ok(elts, G, "Galois keys: between 1 and 64 elements", true)) return kErrInvalid;
     if (const size_t r = first_unreduced_row(hp, gk0, gk1, G * R); r != G * R)
     {
         set_last_error("Galois key of element " + std::to_string(elts[r / R]) + ": row " + std::to_string(r % R) +
@@ -1559,53 +1577,39 @@ int Context::set_galois_keys(const uint32_t *elts, size_t G, const uint32_t *gk0
     std::vector<DevBuf<uint32_t>> blocks(G);
     for (size_t g = 0; g < G; g++)
         if (int rc = build_evk(gk0 + g * slab, gk1 + g * slab, R, stage, blocks[g])) return rc;
-    (sp ? galois_sp_elts : galois_elts).assign(elts, elts + G);
-    (sp ? d_gk_sp : d_gk) = std::move(blocks);
+    evk[sp].elts.assign(elts, elts + G);
+    evk[sp].galois = std::move(blocks);
     return 0;
 }
 
 // One launch, no scratch, no secret key; reads the installed special-prime key: the relinearisation key (elt 0) or the
-// Galois key of `elt`.  The digit keys do not serve it.  The checks of ct_relin / ct_galois in their order, with the
-// level in [1, np - 1].
+// Galois key of `elt`.  The digit keys do not serve it.  The checks of ct_galois in their order, with the level in
+// [1, np - 1].
 int Context::ct_key_switch_sp(const uint32_t *d_a0, const uint32_t *d_a1, const uint32_t *d_sw, size_t B, size_t primes,
                               uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
 {
     if (!special_prime_ok()) return kErrInvalid;
     const bool rot = elt != 0;
-    for (const void *p : {(const void *)d_a0, (const void *)d_sw, (const void *)d_out0, (const void *)d_out1})
-        if (!p) return kErrInvalid;
-    if (!rot && !d_a1) return kErrInvalid;
-    if (primes < 1 || primes > hp.nprimes - 1 || B >= ((size_t)1 << 32)) return kErrInvalid;
-    if (!aligned16({d_a0, d_a1, d_sw, d_out0, d_out1})) return kErrInvalid;
-    if (rot && (!(elt & 1) || elt >= 2 * hp.n)) return kErrInvalid;
+    KeySwitchSpArgs ka{};
+    // a rotation has no a1: a0 stands in its place
+    if (!evk_call_args(ka, {d_a0, rot ? d_a0 : d_a1, d_sw, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
+    if (rot && !galois_elt_ok(elt)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    const uint32_t *key = nullptr;
-    if (!rot)
-        key = d_evk_sp;
-    else
-        for (size_t g = 0; g < galois_sp_elts.size(); g++)
-            if (galois_sp_elts[g] == elt) key = d_gk_sp[g];
+    const uint32_t *key = rot ? galois_key(true, elt) : (const uint32_t *)evk[1].relin;
     if (!key)
     {
-        set_last_error(rot ? "no special-prime Galois key is installed for element " + std::to_string(elt) +
-                                 " (se_amd_set_galois_keys_sp)"
-                           : std::string("no special-prime relinearisation key is installed (se_amd_set_relin_key_sp)"));
+        if (!rot) set_last_error("no special-prime relinearisation key is installed (se_amd_set_relin_key_sp)");
         return kErrNoKey;
     }
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    KeySwitchSpArgs ka{};
-    ka.a0     = d_a0;
-    ka.a1     = d_a1;
-    ka.sw     = d_sw;
-    ka.out0   = d_out0;
-    ka.out1   = d_out1;
-    ka.key    = key;
-    ka.half   = (hp.nprimes - 1) * hp.nprimes * 2 * hp.n;
-    ka.B      = B;
-    ka.np     = (uint32_t)hp.nprimes;
-    ka.primes = (uint32_t)primes;
-    ka.elt    = elt;
+    ka.a0   = d_a0;
+    ka.a1   = d_a1;
+    ka.sw   = d_sw;
+    ka.out0 = d_out0;
+    ka.out1 = d_out1;
+    ka.key  = key;
+    ka.elt  = elt;
     SEAMD_HIP(launch_ct_key_switch_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ka, st));
     return 0;
 }
@@ -1632,28 +1636,21 @@ int Context::ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, siz
 {
     GaloisArgs ga{};
     if (!evk_call_args(ga, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
-    if (!(elt & 1) || elt >= 2 * hp.n) return kErrInvalid;
+    if (!galois_elt_ok(elt)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    size_t g = 0;
-    while (g < galois_elts.size() && galois_elts[g] != elt) g++;
-    if (g == galois_elts.size())
-    {
-        set_last_error("no Galois key is installed for element " + std::to_string(elt) + " (se_amd_set_galois_keys)");
-        return kErrNoKey;
-    }
+    const uint32_t *key = galois_key(false, elt);
+    if (!key) return kErrNoKey;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     ga.c0   = d_c0;
     ga.c1   = d_c1;
     ga.out0 = d_out0;
     ga.out1 = d_out1;
-    ga.key  = d_gk[g];
+    ga.key  = key;
     ga.elt  = elt;
     SEAMD_HIP(launch_ct_galois(dp, dt, ga, st));
     return 0;
 }
-
-static_assert(kHoistMaxElts == kMaxGaloisKeys, "the argument block holds an installed set");
 
 // One launch, no scratch, no secret key, no host synchronisation; reads the installed Galois keys of elts[0 .. G).  The
 // checks of ct_galois in its order, the element check once per element; nothing is launched unless every element has a
@@ -1663,30 +1660,13 @@ int Context::ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t 
 {
     GaloisHoistArgs ha{};
     if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
-    if (!elts || G == 0 || G > kMaxGaloisKeys)
-    {
-        set_last_error("hoisted rotations: between 1 and 64 elements");
-        return kErrInvalid;
-    }
-    for (size_t e = 0; e < G; e++)
-        if (!(elts[e] & 1) || elts[e] >= 2 * hp.n)
-        {
-            set_last_error("Galois element " + std::to_string(elts[e]) + " is not odd and below 2n");
-            return kErrInvalid;
-        }
+    if (!galois_elts_ok(elts, G, "hoisted rotations: between 1 and 64 elements")) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
     for (size_t e = 0; e < G; e++)
     {
-        size_t g = 0;
-        while (g < galois_elts.size() && galois_elts[g] != elts[e]) g++;
-        if (g == galois_elts.size())
-        {
-            set_last_error("no Galois key is installed for element " + std::to_string(elts[e]) +
-                           " (se_amd_set_galois_keys)");
-            return kErrNoKey;
-        }
         ha.elt[e] = elts[e];
-        ha.key[e] = d_gk[g];
+        ha.key[e] = galois_key(false, elts[e]);
+        if (!ha.key[e]) return kErrNoKey;
     }
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
@@ -1708,30 +1688,19 @@ int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_d
                              size_t pt_primes, LintransPlan &plan)
 {
     const size_t n = hp.n, np = hp.nprimes;
-    if (!elts || !d_diag || G == 0 || G > kMaxGaloisKeys || pt_primes == 0 || !aligned16({d_diag, d_diag0}))
+    const char *args_msg = "linear transform: between 1 and 64 elements, pt_primes >= 1, 16-byte aligned diagonals";
+    if (!d_diag || pt_primes == 0 || !aligned16({d_diag, d_diag0}))
     {
-        set_last_error("linear transform: between 1 and 64 elements, pt_primes >= 1, 16-byte aligned diagonals");
+        set_last_error(args_msg);
         return kErrInvalid;
     }
-    for (size_t e = 0; e < G; e++)
-        if (!(elts[e] & 1) || elts[e] >= 2 * n)
-        {
-            set_last_error("Galois element " + std::to_string(elts[e]) + " is not odd and below 2n");
-            return kErrInvalid;
-        }
+    if (!galois_elts_ok(elts, G, args_msg)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    std::vector<size_t> at(G);
+    std::vector<const uint32_t *> from(G);
     for (size_t e = 0; e < G; e++)
     {
-        size_t g = 0;
-        while (g < galois_elts.size() && galois_elts[g] != elts[e]) g++;
-        if (g == galois_elts.size())
-        {
-            set_last_error("no Galois key is installed for element " + std::to_string(elts[e]) +
-                           " (se_amd_set_galois_keys)");
-            return kErrNoKey;
-        }
-        at[e] = g;
+        from[e] = galois_key(false, elts[e]);
+        if (!from[e]) return kErrNoKey;
     }
     SEAMD_HIP(hipSetDevice(device));
     const size_t levels = pt_primes < np ? pt_primes : np, pairs = np * 2 * n, block = 4 * np * pairs;
@@ -1741,7 +1710,7 @@ int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_d
     for (size_t e = 0; e < G; e++)
     {
         SEAMD_HIP(built.keys[e].grow(block));
-        SEAMD_HIP(launch_lintrans_fold(dp, d_gk[at[e]], built.keys[e], d_diag + e * pt_primes * n,
+        SEAMD_HIP(launch_lintrans_fold(dp, from[e], built.keys[e], d_diag + e * pt_primes * n,
                                        built.diag + e * pairs, (uint32_t)levels, nullptr));
     }
     if (d_diag0)

@@ -22,8 +22,6 @@ constexpr int kErrNoDevice = -19;    // SE_ERR_NO_DEVICE
 constexpr int kErrHip      = -1001;  // SE_ERR_HIP
 constexpr int kErrNoKey    = -1002;  // SE_ERR_NO_KEY
 
-constexpr size_t kMaxGaloisKeys = 64;  // elements of one installed set (SE_AMD_MAX_GALOIS_KEYS)
-
 constexpr int kStageCount = 6;  // cbd, uniform, ternary, encode_encrypt (fused), encode_rns, ntt_fuse
 
 struct HostPipe;
@@ -41,6 +39,17 @@ struct LintransPlan
     std::vector<uint32_t> elts;
     std::vector<DevBuf<uint32_t>> keys;   // per entry [2][R][np][2][n]
     DevBuf<uint32_t> diag;                // [G + 1][np][2][n]; the last one is d0 (unused without diag0)
+};
+
+// One installed family of evaluation keys (public material): digit keys (R = 2 np rows; se_amd_set_relin_key,
+// se_amd_set_galois_keys) or special-prime keys (R = np - 1; the _sp setters).  Every key is one device block
+// [2][R][np][2][n] made by build_evk (layout: kernels/kernel_args.h).
+struct EvalKeys
+{
+    DevBuf<uint32_t> relin;                 // the relinearisation key; empty = none installed
+    std::vector<uint32_t> elts;             // the installed Galois elements
+    std::vector<DevBuf<uint32_t>> galois;   // one block per element of elts
+    const uint32_t *find(uint32_t elt) const;   // the block of elt, or nullptr
 };
 
 struct StageEvent
@@ -69,17 +78,7 @@ struct Context
     DevBuf<uint32_t> d_ring_sk{Secret::yes};   // [K][np][n][2] NTT(s) pairs
     DevBuf<uint32_t> d_ring_pk0, d_ring_pk1;   // [K][np][n][2]
     size_t ring_sk = 0, ring_pk = 0;           // keys in each ring (0 = no ring)
-    // evaluation keys (public material), each one device block [2][R][np][2][n] made by build_evk (layout:
-    // kernels/kernel_args.h): the relinearisation key (se_amd_set_relin_key; empty = none installed) and the Galois keys
-    // (se_amd_set_galois_keys): the installed elements and one block per element
-    DevBuf<uint32_t> d_evk;
-    std::vector<uint32_t> galois_elts;
-    // the special-prime keys (se_amd_set_relin_key_sp, se_amd_set_galois_keys_sp): the same layout with R' = np - 1
-    // rows, installed sets of their own beside the digit keys
-    DevBuf<uint32_t> d_evk_sp;
-    std::vector<uint32_t> galois_sp_elts;
-    std::vector<DevBuf<uint32_t>> d_gk_sp;
-    std::vector<DevBuf<uint32_t>> d_gk;
+    EvalKeys evk[2];                           // the installed evaluation keys: [0] digit, [1] special-prime (index: sp)
     DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
     DevBuf<uint32_t> d_kbad;                   // [1 + cap] count + records whose index was out of range
 
@@ -308,7 +307,10 @@ private:
     bool special_prime_ok() const;
     int build_evk(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block);
     template <class Args>
-    bool evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes) const;
+    bool evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes, bool sp = false) const;
+    bool galois_elt_ok(uint32_t elt) const { return (elt & 1) && elt < 2 * hp.n; }   // odd and below 2n
+    bool galois_elts_ok(const uint32_t *elts, size_t G, const char *count_msg, bool distinct = false) const;
+    const uint32_t *galois_key(bool sp, uint32_t elt) const;
     int decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
                            size_t primes, double scale, const uint32_t *d_key_idx, bool keyed, int64_t *d_pte,
                            float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);
