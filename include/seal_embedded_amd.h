@@ -574,8 +574,9 @@ int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uin
  * se_amd_lintrans_destroy: waits for the device, then frees; NULL is a no-op.  Destroy plans before their context.
  * se_amd_ct_lintrans_device: d_out0, d_out1 are [B][primes][n].  One asynchronous launch, no scratch, no host
  * synchronisation; outputs must not overlap the inputs.  SE_ERR_INVALD_ARGUMENT for the pointer, alignment, level and B
- * checks of se_amd_ct_galois_device, then for a NULL plan, a plan of another context, or primes above the plan's
- * levels.  Nothing is launched or written on an error.  B = 0 is a successful no-op. */
+ * checks of se_amd_ct_galois_device, then for a NULL plan, a plan of another context, a special-prime plan
+ * (se_amd_lintrans_create_sp), or primes above the plan's levels.  Nothing is launched or written on an error.  B = 0
+ * is a successful no-op. */
 typedef struct se_amd_lintrans se_amd_lintrans;
 int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts /*host, [G]*/, size_t G, const uint32_t *d_diag,
                            const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out);
@@ -624,8 +625,8 @@ int se_amd_ct_lintrans_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, cons
  * A fresh record is at level np and the entries above need level np - 1 at most; dropping a prime changes neither
  * message nor scale.  SE_ERR_INVALD_ARGUMENT for a NULL or misaligned slab, one of d_in1 / d_out1 alone, levels out of
  * range, B at or above 2^32.
- * Out of scope: hoisted, sum and linear-transform forms on the special-prime key, several special primes, custom
- * chains, host-pointer and multi-device forms. */
+ * The sum and linear-transform forms on this key are the next block.  Out of scope: the hoisted many form on the
+ * special-prime key, several special primes, custom chains, host-pointer and multi-device forms. */
 int se_amd_gen_relin_key_sp(se_amd_ctx *ctx, const uint8_t *sk_packed, const uint8_t *a_seeds /*[R'][64]*/,
                             const uint8_t *e_seeds /*[R'][64]*/, uint32_t *evk0, uint32_t *evk1 /*[R'][np][n], host out*/);
 int se_amd_set_relin_key_sp(se_amd_ctx *ctx, const uint32_t *evk0, const uint32_t *evk1);
@@ -640,6 +641,53 @@ int se_amd_ct_galois_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint
 int se_amd_ct_drop_primes_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
                                  size_t B, size_t primes_in, size_t primes_out, uint32_t *d_out0,
                                  uint32_t *d_out1 /* NULL with d_in1 */, void *stream);
+/* ---- special-prime hoisted rotations: the sum form and linear transforms at the record's own scale ----
+ * The sum of G rotations (se_amd_ct_galois_sum_sp_device) and the plaintext-weighted sum of G rotations
+ * (se_amd_ct_lintrans_sp_device) on the special-prime Galois keys, with ONE decomposition of c1 and ONE division by P per
+ * record whatever G is ("double hoisting"): a moving sum or a diagonal-method matrix-vector product on FRESH records, with
+ * no lift and no level spent on the key switch.  Notation is that of the block above: p = np - 1, P = q_p, records at
+ * level 1 <= L <= np - 1, E = {0 .. L-1, p}, centred(x, q) in (-q/2, q/2], src_e = se_amd_galois_table(elts[e]), (k0^e,
+ * k1^e) the installed special-prime Galois key of elts[e].  The digits are taken from c1 ITSELF, once, and sigma is
+ * applied to the transformed digit as a permutation:
+ *     D_j         = centred(INTT_j(c1[b][j]), q_j)                     j < L, natural order
+ *     F_{j,i}     = NTT_i(D_j mod q_i)                                 i in E   (F_{j,j} is c1[b][j] as it lies)
+ *     ACC_k[i][x] = sum_e w_e[i][x] . sum_{j<L} F_{j,i}[src_e(x)] . k_k^e[j][i][x]     mod q_i, i in E, k in {0, 1}
+ *     delta_k     = centred(INTT_p(ACC_k[p]), P)
+ *     ks_k[i]     = (ACC_k[i] - NTT_i(delta_k mod q_i)) . P^-1         mod q_i, i < L (se_amd_rescale_constants(degree, np, ..))
+ *     out0[i][x]  = ks_0[i][x] + w_0[i][x] . c0[b][i][x] + sum_e w_e[i][x] . c0[b][i][src_e(x)]
+ *     out1[i][x]  = ks_1[i][x] + w_0[i][x] . c1[b][i][x]
+ * all canonical; an element listed twice counts twice.  Sum form: w_e = 1 and w_0 = add_input ? 1 : 0.  Linear transform:
+ * w_e = d_e mod q_i, the e-th diagonal INCLUDING its row at prime p, which enters ACC_k[p]; w_0 = d_0, no w_0 terms when
+ * d_diag0 is NULL.  The record's own term and the c0 terms are added after the division by P: they are exact.
+ * Two facts.  (1) Centring commutes with sigma -- a negated coefficient q - c centres to -centred(c) -- so sigma(D_j) is
+ * the digit of sigma(c1), and the sum form with G = 1, add_input = 0 is BIT-IDENTICAL to se_amd_ct_galois_sp_device (the
+ * digit twin se_amd_ct_galois_sum_device has no such property: see there).  (2) G >= 2 does NOT equal the sum of G single
+ * calls: that sum carries G roundings delta^e, this form carries centred(sum_e delta^e mod P), and the two differ
+ * wherever |sum_e delta^e| > P/2 -- about a quarter of the coefficients at G = 2 on random data.  One rounding instead of
+ * G; a workgroup's transforms stay at 4 L + 2 whatever G is.
+ * Conventions are those of the digit twins and of se_amd_ct_galois_sp_device: level-`primes` slabs [B][primes][n], 16-byte
+ * aligned; one asynchronous launch, no scratch, no host synchronisation in the device entries; outputs do not overlap
+ * inputs; nothing is written on an error; B = 0 is a successful no-op.  SE_ERR_INVALD_ARGUMENT for the argument errors of
+ * se_amd_ct_galois_sum_device / se_amd_ct_lintrans_device, np = 1, primes outside [1, np - 1]; SE_ERR_NO_KEY when an
+ * element has no installed SPECIAL-PRIME key (installed digit keys do not serve these entries; the last-error text names
+ * the element).
+ * se_amd_lintrans_create_sp: as se_amd_lintrans_create, on the installed special-prime blocks.  pt_primes MUST equal np:
+ * the diagonals' row at the special prime is folded into key column p (anything else: SE_ERR_INVALD_ARGUMENT).  The plan
+ * serves the levels 1 .. np - 1.  It is a snapshot: the words k . d_e mod q_c with their Shoup companions for every column
+ * c, p included, and the (word, Shoup) rows of the diagonals; (G . 16 (np - 1) np + (G + 1) . 8 np) n bytes of device
+ * memory (4096 x 3, G = 7: 3.4 MiB; 16384 x 13, G = 7: 286 MiB).  se_amd_lintrans_destroy serves both kinds of plan.
+ * A plan has a kind: se_amd_ct_lintrans_device refuses a special-prime plan and se_amd_ct_lintrans_sp_device refuses a
+ * digit plan, both with SE_ERR_INVALD_ARGUMENT and nothing written.
+ * Out of scope: the MANY form on the special-prime key (each output needs its own delta and its own division by P, so
+ * hoisting would save only the shared pass transforms), baby-step / giant-step plans, several special primes, custom
+ * chains, host-pointer and multi-device forms. */
+int se_amd_ct_galois_sum_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                   const uint32_t *elts /*host, [G]*/, size_t G, int add_input, uint32_t *d_out0,
+                                   uint32_t *d_out1, void *stream);
+int se_amd_lintrans_create_sp(se_amd_ctx *ctx, const uint32_t *elts /*host, [G]*/, size_t G, const uint32_t *d_diag,
+                              const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out);
+int se_amd_ct_lintrans_sp_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                                 size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_lintrans_create", "se_amd_lintrans_destroy", "se_amd_ct_lintrans_device",
     "se_amd_gen_relin_key_sp", "se_amd_set_relin_key_sp", "se_amd_gen_galois_keys_sp", "se_amd_set_galois_keys_sp",
     "se_amd_ct_relin_sp_device", "se_amd_ct_galois_sp_device", "se_amd_ct_drop_primes_device",
+    "se_amd_ct_galois_sum_sp_device", "se_amd_lintrans_create_sp", "se_amd_ct_lintrans_sp_device",
 )
 
 
@@ -181,6 +182,9 @@ def lib():
     L.se_amd_lintrans_destroy.argtypes = [vp]
     L.se_amd_lintrans_destroy.restype = None
     L.se_amd_ct_lintrans_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    L.se_amd_ct_galois_sum_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, i32, vp, vp, vp]
+    L.se_amd_lintrans_create_sp.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(vp)]
+    L.se_amd_ct_lintrans_sp_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -805,6 +809,42 @@ class Context:
         _check(self.L.se_amd_ct_lintrans_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
                                                 c0.shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
                "se_amd_ct_lintrans_device")
+
+    def ct_galois_sum_sp(self, c0, c1, elts, out0, out1, add_input=False, primes=None):
+        """ct_galois_sum with the installed special-prime Galois keys on records (c0, c1) [B][primes][n], primes <=
+        np - 1: the sum of the rotations by elts[0 .. G), plus the record itself with add_input, at the record's own
+        scale from ONE decomposition and ONE division by the special prime.  One element without add_input gives the
+        bits of ct_galois_sp; several carry one rounding instead of one each."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_galois_sum_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el),
+                                                     el.size, 1 if add_input else 0, _ptr(out0), _ptr(out1),
+                                                     _stream_ptr()), "se_amd_ct_galois_sum_sp_device")
+
+    def lintrans_plan_sp(self, elts, diag, diag0=None, pt_primes=None):
+        """lintrans_plan on the installed special-prime Galois keys: diag [G][np][n], diag0 [np][n] or None -- the
+        diagonals need ALL np rows, the one at the special prime is folded into the key.  The plan serves ct_lintrans_sp
+        at the levels 1 .. np - 1."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if pt_primes is None:
+            pt_primes = diag.shape[1]
+        h = C.c_void_p()
+        _check(self.L.se_amd_lintrans_create_sp(self.h, _ptr(el), el.size, _ptr(diag), _ptr(diag0), pt_primes,
+                                                C.byref(h)), "se_amd_lintrans_create_sp")
+        return LintransPlan(self.L, h)
+
+    def ct_lintrans_sp(self, plan, c0, c1, out0, out1, primes=None):
+        """One launch: the special-prime plan's weighted sum of rotations of the records (c0, c1) [B][primes][n],
+        primes <= np - 1 -> (out0, out1) [B][primes][n]; the scale is multiplied by the diagonals' scale, the level is
+        unchanged and no lift is needed."""
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_lintrans_sp_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
+                                                   c0.shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_lintrans_sp_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

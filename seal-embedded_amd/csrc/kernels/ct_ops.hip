@@ -837,6 +837,46 @@ __device__ __forceinline__ void sp_row_digit(uint32_t (&x)[16], const uint32_t *
     tile_to_quads<16>(x, lds, td);
 }
 
+// Between the passes of every special-prime kernel (ct_key_switch_sp, ct_hoist_sp): the accumulators hold acc_k[p] in
+// quad layout, lazy in [0, 2 P); delta_k = centred(INTT_p(acc_k)), and the accumulator of pass 1 starts at
+// -NTT_i(delta_k mod q_i), lazy in (0, 2 q_i].  The two halves take the same code: not unrolled, the halves change
+// places after each turn.  Ends behind a barrier with the plane free.
+template <int LOGN>
+__device__ __forceinline__ void sp_delta(uint32_t (&acc0)[16], uint32_t (&acc1)[16], uint32_t i, uint32_t sp,
+                                         const DevParams &P, const DevTables &T, uint32_t *lds, int t)
+{
+    constexpr int N      = XformGeom<LOGN>::N;
+    const uint32_t q     = P.q[sp], qi = P.q[i], two_qi = qi << 1;
+    const uint32_t *rwi  = T.ntt_rw + 2 * xform_table_len(N) * i;
+    const uint32_t inv_n = P.inv_n[sp], inv_n_sh = P.inv_n_sh[sp], hp = q >> 1, down = qi - q;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 2; k++)
+    {
+        const int td = opaque_index(t);
+        quads_to_tile<16>(acc0, lds, td);
+        __syncthreads();
+        intt_tiles<LOGN>(acc0, T.intt_rw + (size_t)2 * N * sp, q, lds, td);
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            const uint32_t v = csub(mul_shoup_lazy(acc0[e], inv_n, inv_n_sh, q), q);
+            acc0[e]          = v + (v > hp ? down : 0u);   // delta mod q_i in [0, q_i): |delta| < P / 2 < q_i
+        }
+        const int tn = opaque_index(t);
+        ntt_tiles<LOGN>(acc0, rwi, qi, lds, tn);
+        tile_to_quads<16>(acc0, lds, tn);
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            const uint32_t u = min(acc0[e], acc0[e] - two_qi);   // NTT output [0, 4q) -> [0, 2q)
+            const uint32_t o = acc1[e];
+            acc1[e]          = two_qi - u;                       // (0, 2q]
+            acc0[e]          = o;
+        }
+        __syncthreads();
+    }
+}
+
 template <int LOGN, bool GALOIS>
 __device__ __forceinline__ void ct_key_switch_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
                                                  const KeySwitchSpArgs &A, uint32_t *lds)
@@ -846,7 +886,7 @@ __device__ __forceinline__ void ct_key_switch_sp(const DevParams &P, const DevTa
     const int t        = threadIdx.x;
     const uint32_t i   = blockIdx.y;
     const uint32_t sp  = A.np - 1;
-    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t qi  = P.q[i];
     const uint32_t g   = A.elt;
 
     for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
@@ -873,39 +913,7 @@ __device__ __forceinline__ void ct_key_switch_sp(const DevParams &P, const DevTa
                 evk_mac<LOGN>(acc0, acc1, y, key, A.half, q);
                 __syncthreads();
             }
-            if (pass == 0)
-            {
-                // delta_k = centred(INTT_p(acc_k)), and the accumulator of pass 1 starts at -NTT_i(delta_k mod q_i).
-                // The two halves take the same code: not unrolled, the halves change places after each turn.
-                const uint32_t *rwi  = T.ntt_rw + 2 * xform_table_len(N) * i;
-                const uint32_t inv_n = P.inv_n[sp], inv_n_sh = P.inv_n_sh[sp], hp = q >> 1, down = qi - q;
-#pragma unroll 1
-                for (uint32_t k = 0; k < 2; k++)
-                {
-                    const int td = opaque_index(t);
-                    quads_to_tile<16>(acc0, lds, td);
-                    __syncthreads();
-                    intt_tiles<LOGN>(acc0, T.intt_rw + (size_t)2 * N * sp, q, lds, td);
-#pragma unroll
-                    for (int e = 0; e < 16; e++)
-                    {
-                        const uint32_t v = csub(mul_shoup_lazy(acc0[e], inv_n, inv_n_sh, q), q);
-                        acc0[e]          = v + (v > hp ? down : 0u);   // delta mod q_i in [0, q_i): |delta| < P / 2 < q_i
-                    }
-                    const int tn = opaque_index(t);
-                    ntt_tiles<LOGN>(acc0, rwi, qi, lds, tn);
-                    tile_to_quads<16>(acc0, lds, tn);
-#pragma unroll
-                    for (int e = 0; e < 16; e++)
-                    {
-                        const uint32_t u = min(acc0[e], acc0[e] - two_qi);   // NTT output [0, 4q) -> [0, 2q)
-                        const uint32_t o = acc1[e];
-                        acc1[e]          = two_qi - u;                       // (0, 2q]
-                        acc0[e]          = o;
-                    }
-                    __syncthreads();
-                }
-            }
+            if (pass == 0) sp_delta<LOGN>(acc0, acc1, i, sp, P, T, lds, t);
         }
         // ks_k = acc_k . P^-1, then the addends
         const int te   = opaque_index(t);
@@ -1291,8 +1299,245 @@ hipError_t launch_ct_lintrans(const DevParams &P, const DevTables &T, const Lint
     });
 }
 
-// Plan set-up: one thread per key word of an installed block [2][R][np][2][n], or per diagonal word when there is no
-// block (the weight of the record itself).  d = the diagonal word of the thread's column and position reduced mod q_i
+// ------------------------------------------------------------------------------------------
+// Hoisted rotations on the special-prime key ("double hoisting"): se_amd_ct_galois_sum_sp_device and
+// se_amd_ct_lintrans_sp_device.  The sum of G rotations, plain or weighted by plaintext diagonals, of a level-L record
+// (L <= np - 1) at its own scale, from ONE decomposition of c1 and ONE division by P whatever G is.  With the notation of
+// the special-prime block (p = np - 1, P = q_p, E = {0 .. L-1, p}) and src_e the permutation of element e:
+//   D_j         = centred(INTT_j(c1[b][j]), q_j)                                          (the digits of c1 ITSELF)
+//   F_{j,i}     = NTT_i(D_j mod q_i),  i in E                                              (F_{j,j} = c1[b][j] as it lies)
+//   acc_k[i][x] = sum_e sum_{j < L} F_{j,i}[src_e(x)] . key_k^e[j][i][x]   mod q_i,  i in E
+//   delta_k     = centred(INTT_p(acc_k[p]), P);   ks_k[i] = (acc_k[i] - NTT_i(delta_k mod q_i)) . P^-1   mod q_i,  i < L
+//   sum form:   out0 = ks_0 + add_input . c0 + sum_e sigma_e(c0),   out1 = ks_1 + add_input . c1
+//   weighted:   key^e = the plan's block with d_e folded in on EVERY column, p included (k_lintrans_fold), and
+//               out0 = ks_0 + d_0 . c0 + sum_e d_e . sigma_e(c0),   out1 = ks_1 + d_0 . c1      (d_0 terms only with diag0).
+// Centring commutes with sigma (q - c centres to -centred(c)), so sigma(D_j) IS the digit of sigma(c1): one element
+// without add_input gives the bits of k_ct_galois_sp.  G >= 2 carries one rounding centred(sum_e delta^e mod P) where G
+// calls carry G.
+// The body is ct_key_switch_sp's two passes crossed with the park-and-gather of hoist_digits<SUM>: the same grid, one
+// workgroup of n/16 threads per (record, output prime i < L), LDS the exchange plane alone, ONE accumulator pair.
+//   pass 0 (mod P, key column p), per j: sp_park_digit = evk_row_coeffs -> centre and reduce mod P -> ntt_tiles mod P,
+//     which ends in tile layout 0 with the plane free -> parked as it lies, word k at lds[k] (no tile_to_quads) -> barrier
+//     -> per element hoist_mac against row j, column p of that element's block -> barrier;
+//   between the passes: sp_delta, once per half;
+//   pass 1 (mod q_i, column i): the same per j != i; row i enters as it lies in memory (park_row_quads);
+//   epilogue: . P^-1, then the c0 row parked once and gathered G times (weighted: by the diagonal pairs, the epilogue of
+//     k_ct_lintrans), then the terms of the record itself.  They are added after the division: exact.
+// Transforms per workgroup: those of ct_key_switch_sp, 4 L + 2, whatever G is; an element costs a gather and a
+// multiply-accumulate per row and pass.
+// Lazy ranges: those of evk_mac.  An accumulator takes G L products in pass 0 and is brought back into [0, 2 P) after each,
+// so it enters intt_tiles (sp_delta) in [0, 2 P), its input range; it starts pass 1 in (0, 2 q_i], plus one product is
+// below 4 q_i < 2^32, and after the first product it is in [0, 2 q_i) again.  The parked words are the lazy NTT output in
+// [0, 4 q), resp. any 32-bit word of the slab for row i: mul_shoup_lazy takes any 32-bit y.
+// Addresses: as in k_ct_galois_hoist (formed from the checked elements only, masked to [0, n)).
+// grid evk_grid(B, L).
+// ------------------------------------------------------------------------------------------
+// NTT_c(D_j mod q) parked in the plane as ntt_tiles leaves it, word k at lds[k] (the staging of hoist_digits): the centred
+// coefficients of input row j reduced mod q = q_c, rw the roots of column c; td = the opaque index of the transform and of
+// the park.  The 16 words live here only: written into the row loop, merged with the words of the row that enters as it
+// lies, k_ct_galois_sum_sp<14> spilled 36 - 48 bytes per lane and <12> took 129 VGPRs.  The caller's barrier publishes the
+// plane.
+template <int LOGN>
+__device__ __forceinline__ void sp_park_digit(const uint32_t *row, uint32_t j, uint32_t q, const uint32_t *rw,
+                                              const DevParams &P, const DevTables &T, uint32_t *lds, int td, int t)
+{
+    uint32_t y[16];
+    const uint32_t qj = P.q[j], hj = qj >> 1, up = q - qj;   // up: mod 2^32 where q < q_j
+    evk_row_coeffs<LOGN>(y, row, j, P, T, lds, opaque_index(t));
+#pragma unroll
+    for (int e = 0; e < 16; e++) y[e] += y[e] > hj ? up : 0u;
+    ntt_tiles<LOGN>(y, rw, q, lds, td);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        *reinterpret_cast<uint4 *>(lds + 16 * td + 4 * c) = make_uint4(y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]);
+}
+
+template <int LOGN, bool WEIGHTED>
+__device__ __forceinline__ void ct_hoist_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
+                                            const HoistSpArgs &A, uint32_t *lds)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t sp  = A.np - 1;
+    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        // pass 0: modulo P against key column p; pass 1: modulo q_i against key column i.  One body for both.
+#pragma unroll 1
+        for (uint32_t pass = 0; pass < 2; pass++)
+        {
+            const uint32_t col = pass ? i : sp;
+            const uint32_t q   = P.q[col];
+            const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * col;
+            for (uint32_t j = 0; j < A.primes; j++)
+            {
+                const int td = opaque_index(t);
+                if (pass && j == i)
+                {
+                    uint32_t y[16];
+                    load_quads(y, A.c1 + rec + (size_t)i * N, td);
+                    park_row_quads(y, lds, quad_index(td, 0));
+                }
+                else
+                    sp_park_digit<LOGN>(A.c1 + rec + (size_t)j * N, j, q, rw, P, T, lds, td, t);
+                __syncthreads();
+                // the thread's first quad of row j, column col of a key block, and brev of that quad for the gathers: from
+                // the opaque index, so that nothing but the accumulators lives across sp_delta
+                const size_t ko   = ((size_t)j * A.np + col) * 2 * N + quad_index(td, 0);
+                const uint32_t r4 = __brev((uint32_t)quad_index(td, 0)) >> (32 - LOGN);
+#pragma unroll 1
+                for (uint32_t e = 0; e < A.G; e++)
+                    hoist_mac<LOGN>(acc0, acc1, lds, A.key[e] + ko, A.half, A.elt[e], r4, q);
+                __syncthreads();
+            }
+            if (pass == 0) sp_delta<LOGN>(acc0, acc1, i, sp, P, T, lds, t);
+        }
+        // ks_k = acc_k . P^-1 (lazy, [0, 2 q_i)), then the addends; the c0 row of output prime i goes into the plane
+        const int te   = opaque_index(t);
+        const size_t o = rec + (size_t)i * N;
+        const int k4   = quad_index(te, 0);
+        const uint32_t r4 = __brev((uint32_t)k4) >> (32 - LOGN);
+        const uint32_t w = R.inv[i], wp = R.inv_sh[i];
+        uint32_t c[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            acc0[e] = mul_shoup_lazy(acc0[e], w, wp, qi);
+            acc1[e] = mul_shoup_lazy(acc1[e], w, wp, qi);
+        }
+        if constexpr (!WEIGHTED)
+        {
+            // out1 first: its accumulator is gone before the gathers begin
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc1[e] = csub(acc1[e], qi);
+            if (A.add_input)
+            {
+                load_quads(c, A.c1 + o, te);
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc1[e] = csub(acc1[e] + c[e], qi);
+            }
+            store_quads(A.out1 + o, acc1, te);
+        }
+        load_quads(c, A.c0 + o, te);
+        park_row_quads(c, lds, k4);
+        __syncthreads();
+        if constexpr (WEIGHTED)
+        {
+            // the thread's first quad of the (word, Shoup) rows of column i: entry e is e np 2 n further
+            const size_t dcol     = (size_t)i * 2 * N + k4;
+            const uint32_t *diag0 = A.diag0 ? A.diag0 + dcol : nullptr;
+            if (diag0)
+            {
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                {
+                    uint32_t wv[4], sv[4];
+                    load_pair_quad<N>(diag0, m, wv, sv);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) c[4 * m + k] = mul_shoup_lazy(c[4 * m + k], wv[k], sv[k], qi);
+                }
+            }
+            else
+            {
+#pragma unroll
+                for (int e = 0; e < 16; e++) c[e] = 0;
+            }
+#pragma unroll 1
+            for (uint32_t e = 0; e < A.G; e++)
+            {
+                const uint32_t g = A.elt[e], u0 = (2 * r4 + 1) * g;
+                const uint32_t *d = A.diag + (size_t)e * A.np * 2 * N + dcol;
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                {
+                    uint32_t wv[4], sv[4];
+                    load_pair_quad<N>(d, m, wv, sv);
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                    {
+                        const uint32_t v = c[4 * m + k] + mul_shoup_lazy(hoist_word<LOGN>(lds, u0, g, m, k), wv[k], sv[k], qi);
+                        c[4 * m + k]     = min(v, v - two_qi);
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc0[e] = canon4(acc0[e] + c[e], qi, two_qi);
+            store_quads(A.out0 + o, acc0, te);
+            if (diag0)
+            {
+                load_quads(c, A.c1 + o, te);
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                {
+                    uint32_t wv[4], sv[4];
+                    load_pair_quad<N>(diag0, m, wv, sv);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) acc1[4 * m + k] += mul_shoup_lazy(c[4 * m + k], wv[k], sv[k], qi);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc1[e] = canon4(acc1[e], qi, two_qi);
+            store_quads(A.out1 + o, acc1, te);
+        }
+        else
+        {
+            // the canonical ks_0 takes the G gathered rows one by one, and the row itself with add_input
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc0[e] = csub(csub(acc0[e], qi) + (A.add_input ? c[e] : 0u), qi);
+#pragma unroll 1
+            for (uint32_t e = 0; e < A.G; e++)
+            {
+                const uint32_t g = A.elt[e], u0 = (2 * r4 + 1) * g;
+#pragma unroll
+                for (int k = 0; k < 16; k++) acc0[k] = csub(acc0[k] + hoist_word<LOGN>(lds, u0, g, k >> 2, k & 3), qi);
+            }
+            store_quads(A.out0 + o, acc0, te);
+        }
+        __syncthreads();   // the next record's first transpose writes the plane the gather reads
+    }
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_sum_sp(const DevParams P, const DevTables T,
+                                                                            const RescaleParams R, const HoistSpArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ct_hoist_sp<LOGN, false>(P, T, R, A, reinterpret_cast<uint32_t *>(smem));
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_lintrans_sp(const DevParams P, const DevTables T,
+                                                                          const RescaleParams R, const HoistSpArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ct_hoist_sp<LOGN, true>(P, T, R, A, reinterpret_cast<uint32_t *>(smem));
+}
+
+// LOGN 12 .. 14 only, by the rule of launch_ct_key_switch_sp.
+hipError_t launch_ct_hoist_sp(const DevParams &P, const DevTables &T, const RescaleParams &R, const HoistSpArgs &A,
+                              hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid    = evk_grid(A.B, A.primes);
+        const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
+        return A.weighted ? launch(k_ct_lintrans_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
+                          : launch(k_ct_galois_sum_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
+    });
+}
+
+// Plan set-up: one thread per key word of an installed block [2][R][np][2][n] (R = 2 np rows of a digit key, np - 1 of a
+// special-prime key), or per diagonal word when there is no block (the weight of the record itself).  d = the diagonal word of the thread's column and position reduced mod q_i
 // (any 32-bit word is valid input; columns i >= pt have no diagonal and get 0); the thread of half 0, row 0 also writes
 // the (d, Shoup) pair of its position.
 __global__ __launch_bounds__(kLcThreads) void k_lintrans_fold(const DevParams P, const uint32_t *__restrict__ key_in,
@@ -1317,10 +1562,11 @@ __global__ __launch_bounds__(kLcThreads) void k_lintrans_fold(const DevParams P,
     key_out[((2 * col + 1) << P.logn) + c] = (uint32_t)(((uint64_t)w << 32) / q);
 }
 
-hipError_t launch_lintrans_fold(const DevParams &P, const uint32_t *key_in, uint32_t *key_out, const uint32_t *diag_in,
-                                uint32_t *pair_out, uint32_t pt, hipStream_t st)
+hipError_t launch_lintrans_fold(const DevParams &P, const uint32_t *key_in, uint32_t *key_out, size_t rows,
+                                const uint32_t *diag_in, uint32_t *pair_out, uint32_t pt, hipStream_t st)
 {
-    const size_t words = ((size_t)(key_in ? 4 * P.nprimes : 1) * P.nprimes) << P.logn;   // 2 halves of R = 2 np rows
+    // 2 halves of `rows` rows (2 np of a digit block, np - 1 of a special-prime block: at least one row of np columns)
+    const size_t words = ((size_t)(key_in ? 2 * rows : 1) * P.nprimes) << P.logn;
     return launch(k_lintrans_fold, dim3((unsigned)(words / kLcThreads)), dim3(kLcThreads), 0, st, P, key_in, key_out,
                   diag_in, pair_out, pt, words);
 }

@@ -182,7 +182,7 @@ struct MulArgs
     uint32_t primes;
 };
 hipError_t launch_ct_mul(const DevParams &, const MulArgs &, hipStream_t);
-// The key switch of ct_ops.hip, shared by every kernel from here to LintransArgs (evk_row_coeffs, evk_digits, evk_mac;
+// The key switch of ct_ops.hip, shared by every kernel from here to HoistSpArgs (evk_row_coeffs, evk_digits, evk_mac;
 // grid evk_grid(B, primes)).  `key` is one device evaluation-key block, built
 // by Context::build_evk from the host's two halves: [2][R][np][2][n], R = 2 np rows of the CONTEXT's np columns, each
 // column a row of n key words followed by the row of their Shoup companions floor(w 2^32 / q_i); half 1 starts `half`
@@ -281,11 +281,40 @@ struct LintransArgs
     const uint32_t *key[kMaxGaloisKeys];   // the folded key block of entry e
 };
 hipError_t launch_ct_lintrans(const DevParams &, const DevTables &, const LintransArgs &, hipStream_t);
+// Hoisted rotations on the special-prime key (k_ct_galois_sum_sp, k_ct_lintrans_sp): the sum form and the linear
+// transform above on blocks [2][R'][np][2][n] of R' = np - 1 rows, records of `primes` <= np - 1 rows.  With D_j =
+// centred(INTT_j(c1[b][j])), E = {0 .. primes-1, np-1} and src_e the permutation of elt[e]:
+//   acc_k[i][x] = sum_e sum_{j < primes} NTT_i(D_j mod q_i)[src_e(x)] . key_k[e][j][i][x],  i in E;
+//   delta_k = centred(INTT_p(acc_k[p]), P);   ks_k[i] = (acc_k[i] - NTT_i(delta_k mod q_i)) . P^-1   mod q_i,  i < primes;
+//   sum form (weighted = 0): out0 = ks_0 + add_input . c0 + sum_e sigma_e(c0),  out1 = ks_1 + add_input . c1, key[e] the
+//     installed special-prime blocks;
+//   weighted: out0 = ks_0 + d0 . c0 + sum_e d_e . sigma_e(c0),  out1 = ks_1 + d0 . c1, key[e] the plan's blocks with d_e
+//     folded in on every column (np - 1 included), diag / diag0 as in LintransArgs.
+// One decomposition and one division by P per record whatever G is.  The constants P^-1 mod q_i are the RescaleParams of
+// level np.
+struct HoistSpArgs
+{
+    const uint32_t *c0, *c1;        // [B][primes][n]
+    uint32_t *out0, *out1;          // [B][primes][n]
+    size_t half;                    // words of one key half: R' np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
+    uint32_t primes;                // 1 .. np - 1
+    uint32_t G;                     // 1 .. kMaxGaloisKeys
+    uint32_t weighted, add_input;   // 0 / 1 each; add_input only without weighted
+    const uint32_t *diag;           // weighted: [G][np][2][n]
+    const uint32_t *diag0;          // weighted: [np][2][n], or NULL: the record itself does not enter
+    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kMaxGaloisKeys];   // the key block of entry e
+};
+hipError_t launch_ct_hoist_sp(const DevParams &, const DevTables &, const RescaleParams &, const HoistSpArgs &,
+                              hipStream_t);
 // Plan set-up (k_lintrans_fold), one entry per launch.  d = diag_in[i][k] mod q_i for columns i < pt, 0 beyond (any
 // 32-bit word is valid input).  pair_out [np][2][n] = (d, its Shoup companion); with key_in (an installed block
-// [2][R][np][2][n]), key_out = the block of the words key_in . d mod q_i and their companions.  key_in NULL: pairs only.
-hipError_t launch_lintrans_fold(const DevParams &, const uint32_t *key_in, uint32_t *key_out, const uint32_t *diag_in,
-                                uint32_t *pair_out, uint32_t pt, hipStream_t);
+// [2][rows][np][2][n]), key_out = the block of the words key_in . d mod q_i and their companions.  key_in NULL: pairs
+// only.
+hipError_t launch_lintrans_fold(const DevParams &, const uint32_t *key_in, uint32_t *key_out, size_t rows,
+                                const uint32_t *diag_in, uint32_t *pair_out, uint32_t pt, hipStream_t);
 // Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words -> [rows][np][2][n] (words, Shoup
 // companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
 // slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =

@@ -508,14 +508,15 @@ int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uin
                                   as_stream(stream));
 }
 
-int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *d_diag,
-                           const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out)
+// both kinds of plan: sp = on the special-prime keys
+static int lintrans_create(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *d_diag,
+                           const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out, bool sp)
 {
     if (out) *out = nullptr;
     if (!ctx || !out) return SE_ERR_INVALD_ARGUMENT;
     se_amd_lintrans *h = new (std::nothrow) se_amd_lintrans();
     if (!h) return SE_ERR_NO_MEMORY;
-    const int rc = ctx->c.lintrans_create(elts, G, d_diag, d_diag0, pt_primes, h->p);
+    const int rc = ctx->c.lintrans_create(elts, G, d_diag, d_diag0, pt_primes, h->p, sp);
     if (rc != 0)
     {
         delete h;   // the buffers of a plan half built went with the local it was built in
@@ -523,6 +524,18 @@ int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts, size_t G, cons
     }
     *out = h;
     return SE_SUCCESS;
+}
+
+int se_amd_lintrans_create(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *d_diag,
+                           const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out)
+{
+    return lintrans_create(ctx, elts, G, d_diag, d_diag0, pt_primes, out, false);
+}
+
+int se_amd_lintrans_create_sp(se_amd_ctx *ctx, const uint32_t *elts, size_t G, const uint32_t *d_diag,
+                              const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out)
+{
+    return lintrans_create(ctx, elts, G, d_diag, d_diag0, pt_primes, out, true);
 }
 
 void se_amd_lintrans_destroy(se_amd_lintrans *plan)
@@ -538,6 +551,22 @@ int se_amd_ct_lintrans_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, cons
 {
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
     return ctx->c.ct_lintrans(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_galois_sum_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                   const uint32_t *elts, size_t G, int add_input, uint32_t *d_out0, uint32_t *d_out1,
+                                   void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois_sum_sp(d_c0, d_c1, B, primes, elts, G, add_input != 0, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_lintrans_sp_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0,
+                                 const uint32_t *d_c1, size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1,
+                                 void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_lintrans(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, as_stream(stream), true);
 }
 
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)

@@ -1681,15 +1681,49 @@ int Context::ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t 
     return 0;
 }
 
+// The sum form on the special-prime key: ct_galois_hoist's checks in its order behind those of ct_key_switch_sp (a
+// context of one prime, the level in [1, np - 1]); reads the installed special-prime Galois keys, the digit keys do not
+// serve it.  One launch, no scratch, no host synchronisation.
+int Context::ct_galois_sum_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
+                              size_t G, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    HoistSpArgs ha{};
+    if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
+    if (!galois_elts_ok(elts, G, "hoisted rotations: between 1 and 64 elements")) return kErrInvalid;
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t e = 0; e < G; e++)
+    {
+        ha.elt[e] = elts[e];
+        ha.key[e] = galois_key(true, elts[e]);
+        if (!ha.key[e]) return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    ha.c0        = d_c0;
+    ha.c1        = d_c1;
+    ha.out0      = d_out0;
+    ha.out1      = d_out1;
+    ha.G         = (uint32_t)G;
+    ha.add_input = add_input;
+    SEAMD_HIP(launch_ct_hoist_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ha, st));
+    return 0;
+}
+
 // The plan of a linear transform.  Argument checks first, then under `mu`: every element needs an installed key (the
 // blocks are read, not kept); one fold launch per entry and one for d0, then a synchronisation, so the caller's
 // diagonals and the installed blocks may go once this returns.  Anything refused leaves `plan` empty.
+// sp: on the special-prime keys.  The diagonals must have all np rows -- the row at the special prime is folded into key
+// column np - 1 -- and the plan serves the levels 1 .. np - 1.
 int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_diag, const uint32_t *d_diag0,
-                             size_t pt_primes, LintransPlan &plan)
+                             size_t pt_primes, LintransPlan &plan, bool sp)
 {
+    if (sp && !special_prime_ok()) return kErrInvalid;
     const size_t n = hp.n, np = hp.nprimes;
-    const char *args_msg = "linear transform: between 1 and 64 elements, pt_primes >= 1, 16-byte aligned diagonals";
-    if (!d_diag || pt_primes == 0 || !aligned16({d_diag, d_diag0}))
+    const char *args_msg = sp ? "special-prime linear transform: between 1 and 64 elements, pt_primes = the context's "
+                                "primes, 16-byte aligned diagonals"
+                              : "linear transform: between 1 and 64 elements, pt_primes >= 1, 16-byte aligned diagonals";
+    if (!d_diag || pt_primes == 0 || (sp && pt_primes != np) || !aligned16({d_diag, d_diag0}))
     {
         set_last_error(args_msg);
         return kErrInvalid;
@@ -1699,26 +1733,28 @@ int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_d
     std::vector<const uint32_t *> from(G);
     for (size_t e = 0; e < G; e++)
     {
-        from[e] = galois_key(false, elts[e]);
+        from[e] = galois_key(sp, elts[e]);
         if (!from[e]) return kErrNoKey;
     }
     SEAMD_HIP(hipSetDevice(device));
-    const size_t levels = pt_primes < np ? pt_primes : np, pairs = np * 2 * n, block = 4 * np * pairs;
+    // the diagonal columns that are folded: all of a special-prime plan's, the first pt_primes of a digit plan's
+    const size_t cols = pt_primes < np ? pt_primes : np, pairs = np * 2 * n, R = evk_rows(sp), block = 2 * R * pairs;
     LintransPlan built;
     built.keys.resize(G);
     SEAMD_HIP(built.diag.grow((G + 1) * pairs));
     for (size_t e = 0; e < G; e++)
     {
         SEAMD_HIP(built.keys[e].grow(block));
-        SEAMD_HIP(launch_lintrans_fold(dp, from[e], built.keys[e], d_diag + e * pt_primes * n,
-                                       built.diag + e * pairs, (uint32_t)levels, nullptr));
+        SEAMD_HIP(launch_lintrans_fold(dp, from[e], built.keys[e], R, d_diag + e * pt_primes * n,
+                                       built.diag + e * pairs, (uint32_t)cols, nullptr));
     }
     if (d_diag0)
-        SEAMD_HIP(launch_lintrans_fold(dp, nullptr, nullptr, d_diag0, built.diag + G * pairs, (uint32_t)levels, nullptr));
+        SEAMD_HIP(launch_lintrans_fold(dp, nullptr, nullptr, R, d_diag0, built.diag + G * pairs, (uint32_t)cols, nullptr));
     SEAMD_HIP(hipDeviceSynchronize());
     built.owner  = this;
     built.device = device;
-    built.levels = levels;
+    built.levels = sp ? np - 1 : cols;
+    built.sp     = sp;
     built.diag0  = d_diag0 != nullptr;
     built.elts.assign(elts, elts + G);
     plan = std::move(built);
@@ -1726,30 +1762,57 @@ int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_d
 }
 
 // One launch, no scratch, no host synchronisation, nothing of the context but its tables: the plan owns what the kernel
-// reads.  The checks of ct_galois first, then the plan's.
+// reads.  The checks of ct_galois first (sp: of ct_key_switch_sp), then the plan's: a plan serves the entry of its kind.
 int Context::ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
-                         uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+                         uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp)
 {
+    if (sp && !special_prime_ok()) return kErrInvalid;
     LintransArgs la{};
-    if (!evk_call_args(la, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
-    if (!plan || plan->owner != this || primes > plan->levels)
+    HoistSpArgs ha{};
+    if (!(sp ? evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes, true)
+             : evk_call_args(la, {d_c0, d_c1, d_out0, d_out1}, B, primes)))
+        return kErrInvalid;
+    if (!plan || plan->owner != this || plan->sp != sp || primes > plan->levels)
     {
         set_last_error(!plan ? "linear transform: no plan"
-                             : plan->owner != this ? "linear transform: the plan belongs to another context"
-                                                   : "linear transform: the plan's diagonals have fewer primes than the call");
+                       : plan->owner != this ? "linear transform: the plan belongs to another context"
+                       : plan->sp != sp ? (sp ? "linear transform: a digit-key plan (se_amd_lintrans_create) does not serve "
+                                                "the special-prime entry"
+                                              : "linear transform: a special-prime plan (se_amd_lintrans_create_sp) does "
+                                                "not serve the digit-key entry")
+                                        : "linear transform: the plan's diagonals have fewer primes than the call");
         return kErrInvalid;
     }
     if (B == 0) return 0;
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
     const size_t G = plan->elts.size(), pairs = hp.nprimes * 2 * hp.n;
+    const uint32_t *diag0 = plan->diag0 ? plan->diag + G * pairs : nullptr;
+    if (sp)
+    {
+        ha.c0       = d_c0;
+        ha.c1       = d_c1;
+        ha.out0     = d_out0;
+        ha.out1     = d_out1;
+        ha.G        = (uint32_t)G;
+        ha.weighted = 1;
+        ha.diag     = plan->diag;
+        ha.diag0    = diag0;
+        for (size_t e = 0; e < G; e++)
+        {
+            ha.elt[e] = plan->elts[e];
+            ha.key[e] = plan->keys[e];
+        }
+        SEAMD_HIP(launch_ct_hoist_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ha, st));
+        return 0;
+    }
     la.c0    = d_c0;
     la.c1    = d_c1;
     la.out0  = d_out0;
     la.out1  = d_out1;
     la.G     = (uint32_t)G;
     la.diag  = plan->diag;
-    la.diag0 = plan->diag0 ? plan->diag + G * pairs : nullptr;
+    la.diag0 = diag0;
     for (size_t e = 0; e < G; e++)
     {
         la.elt[e] = plan->elts[e];

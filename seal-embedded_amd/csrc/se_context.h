@@ -34,10 +34,12 @@ struct LintransPlan
 {
     const Context *owner = nullptr;   // compared, never dereferenced
     int device           = 0;
-    size_t levels        = 0;       // min(pt_primes, np): the calls it serves have primes <= levels
+    size_t levels        = 0;       // min(pt_primes, np), np - 1 of a special-prime plan: the calls it serves have
+                                    // primes <= levels
+    bool sp              = false;   // made from the special-prime keys (se_amd_lintrans_create_sp): R = np - 1 rows
     bool diag0           = false;
     std::vector<uint32_t> elts;
-    std::vector<DevBuf<uint32_t>> keys;   // per entry [2][R][np][2][n]
+    std::vector<DevBuf<uint32_t>> keys;   // per entry [2][R][np][2][n], R = 2 np or np - 1 (sp)
     DevBuf<uint32_t> diag;                // [G + 1][np][2][n]; the last one is d0 (unused without diag0)
 };
 
@@ -245,10 +247,14 @@ struct Context
                         size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // linear transforms (LintransArgs): the plan folds device diagonals [G][pt_primes][n] (+ d_diag0 [pt_primes][n] or
     // NULL) into the installed Galois keys of elts (host) and synchronises; a call is one launch, no scratch
+    // sp: on the special-prime keys (pt_primes = np, levels 1 .. np - 1; HoistSpArgs); a plan serves the calls of its kind
     int lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_diag, const uint32_t *d_diag0,
-                        size_t pt_primes, LintransPlan &plan);
+                        size_t pt_primes, LintransPlan &plan, bool sp = false);
     int ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
-                    uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+                    uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp = false);
+    // the sum form on the special-prime Galois keys (HoistSpArgs): one decomposition and one division by P whatever G is
+    int ct_galois_sum_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
+                         size_t G, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
     int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
                    uint32_t *d_out1, hipStream_t st);

@@ -1,0 +1,676 @@
+"""Hoisted rotations on the special-prime key (-m gpu): se_amd_ct_galois_sum_sp_device, se_amd_lintrans_create_sp and
+se_amd_ct_lintrans_sp_device.
+Every expectation is the definition in tests/keyswitch_sp_hoist_support.py (and, for the single entry, in
+tests/keyswitch_sp_support.py): the oracle's primitives and Python / NumPy integers, never the code under test.  Every
+comparison is bit-exact except the reference's own acceptance criterion |values - expected| < 0.1.
+Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
+import ctypes as C
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import vectors as V
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, build_example, dev_t,  # noqa: F401
+                         encrypt_sym, env, expectation, host_u32, keyed_cases, rand_slab, rescale_expect, run_decrypt,
+                         sentinel_out, stream_of, take, unit_values)
+from keyswitch_sp_hoist_support import hoist_sp_expect, src_table, sum_of_single_calls
+from keyswitch_sp_support import add_mod, centred, key_errors, key_switch_sp, negacyclic, sigma_rows
+from vectors import sigma_coeff
+
+pytestmark = pytest.mark.gpu
+
+
+def run_sum_sp(env, ctx, c0, c1, elts, primes, add_input):
+    """One call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois_sum_sp(c0, c1, elts, out0, out1, add_input=add_input, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "sum_sp out0"), take(out1, words, (B, primes, n), "sum_sp out1")
+
+
+def run_lintrans_sp(env, ctx, plan, c0, c1, primes):
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_lintrans_sp(plan, c0, c1, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "lintrans_sp out0"), take(out1, words, (B, primes, n), "lintrans_sp out1")
+
+
+def run_galois_sp(env, ctx, c0, c1, elt, primes):
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois_sp(c0, c1, elt, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "galois_sp out0"), take(out1, words, (B, primes, n), "galois_sp out1")
+
+
+def rand_key(rng, q, n):
+    """One key half [np - 1][np][n] of random words below q_i."""
+    return np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(len(q) - 1)])
+
+
+def edge_row(o, j, rng, elts):
+    """NTT form of natural-order coefficients that hold 0, 1, both sides of the centring boundary and q - 1, each of
+    them on at least one index whose image is negated and on one whose image is not, for every element of `elts`."""
+    n, q = o.n, o.q[j]
+    edges = np.array([0, 1, (q - 1) // 2, (q + 1) // 2, q - 1], dtype=np.uint32)
+    c = rng.integers(2, q - 1, n, dtype=np.uint32)
+    for start in (0, n // 2, n - 13):           # twice, 7 apart: an even and an odd index for every value
+        c[start:start + 5] = c[start + 7:start + 12] = edges
+    for g in elts:
+        _, neg = V.galois_image(n, g)
+        for v in edges:
+            at = c == v
+            assert (at & neg).any() and (at & ~neg).any(), (g, int(v))
+    row = o.ntt(c, j)
+    assert (o.intt(row, j) == c).all()
+    return row
+
+
+SP_CASES = [((4096, 3), (2, 1), 3), ((4096, 2), (1,), 3), ((16384, 13), (12,), 2)]
+CASE_IDS = lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v)  # noqa: E731
+
+
+@pytest.fixture(scope="module")
+def slab_cases(env):
+    """slab_cases(shape, B) -> per shape, computed once and shared by tests 1 and 4: a context without a secret key, random
+    special-prime Galois keys of its elements installed (key words 0, 1 and q - 1 on a data column and on column p), and
+    per level the slabs: record 0 of c1 holds the edge rows, record 1 is all q_j - 1."""
+    from oracle.pyoracle import Oracle
+    cache = {}
+
+    def get(shape, levels, B):
+        if shape in cache:
+            return cache[shape]
+        n, npr = shape
+        p = npr - 1
+        o = Oracle(n, npr)
+        ctx = env["pkg"].Context(n, npr)
+        q = o.q
+        rng = np.random.default_rng(43 * n + npr)
+        elts = [3, n + 1] if n > 4096 else [3, n + 1, 1, 2 * n - 1]
+        gk0 = np.stack([rand_key(rng, q, n) for _ in elts])
+        gk1 = np.stack([rand_key(rng, q, n) for _ in elts])
+        for k in (gk0[0], gk1[1]):
+            k[0, 0, :4] = [0, 1, q[0] - 1, q[0] - 1]
+            k[0, p, :4] = [0, 1, q[p] - 1, q[p] - 1]
+        ctx.set_galois_keys_sp(elts, gk0, gk1)
+        slabs = {}
+        for L in levels:
+            c0, c1 = rand_slab(rng, q, B, n, L), rand_slab(rng, q, B, n, L)
+            for j in range(L):
+                c1[0, j] = edge_row(o, j, rng, [3, n + 1])     # 1 negates nothing, 2n - 1 everything but index 0
+            c0[1] = c1[1] = (np.array(q[:L], dtype=np.uint32) - 1)[:, None]
+            slabs[L] = (c0, c1)
+        cache[shape] = dict(o=o, ctx=ctx, elts=elts, keys={g: (gk0[k], gk1[k]) for k, g in enumerate(elts)},
+                            slabs=slabs, rng=rng)
+        return cache[shape]
+
+    yield get
+    for c in cache.values():
+        c["ctx"].close()
+
+
+# ---- test 1: the definition on arbitrary slabs and key words --------------------------------------------------------
+@pytest.mark.parametrize("shape,levels,B", SP_CASES, ids=CASE_IDS)
+def test_sum_sp_arbitrary_slabs_and_keys(env, slab_cases, shape, levels, B):
+    """Test 1: random residues for the slabs and for the installed keys; the element lists [3], [3, n + 1, 3] (a repeat
+    counts twice) and [1, 2n - 1], each with add_input 0 and 1, against the definition (at 16384 x 13 the one list
+    [3, n + 1, 3] with add_input).  A lower level uses rows j < L, columns i < L and column p of the same keys; the
+    sentinels survive.  No secret key is installed."""
+    case = slab_cases(shape, levels, B)
+    n, npr = shape
+    o, ctx = case["o"], case["ctx"]
+    runs = [([3, n + 1, 3], 1)] if n > 4096 else [(el, a) for el in ([3], [3, n + 1, 3], [1, 2 * n - 1]) for a in (0, 1)]
+    for L in levels:
+        c0, c1 = case["slabs"][L]
+        d0, d1 = dev_t(env, c0), dev_t(env, c1)
+        for elts, add in runs:
+            e0, e1, _ = hoist_sp_expect(o, c0, c1, elts, [case["keys"][g] for g in elts], w0=1 if add else None)
+            g0, g1 = run_sum_sp(env, ctx, d0, d1, elts, L, bool(add))
+            assert (g0 == e0).all() and (g1 == e1).all(), (L, elts, add)
+
+
+# ---- test 2: one element is the single entry ------------------------------------------------------------------------
+def test_sum_sp_of_one_element_has_the_bytes_of_galois_sp(env):
+    """Test 2: at 4096 x 3, L = 2, B = 3, for the elements 3^7 mod 2n and 2n - 1 the sum form with G = 1 and no
+    add_input has the bytes of ct_galois_sp (centring commutes with sigma); with add_input it is that plus the record,
+    mod q_i."""
+    n, npr, L, B = 4096, 3, 2, 3
+    ctx = env["pkg"].Context(n, npr)
+    q = ctx.moduli()
+    rng = np.random.default_rng(4096 * 3 + 7)
+    elts = [pow(3, 7, 2 * n), 2 * n - 1]
+    ctx.set_galois_keys_sp(elts, np.stack([rand_key(rng, q, n) for _ in elts]),
+                           np.stack([rand_key(rng, q, n) for _ in elts]))
+    c0, c1 = rand_slab(rng, q, B, n, L), rand_slab(rng, q, B, n, L)
+    d0, d1 = dev_t(env, c0), dev_t(env, c1)
+    qv = np.array(q[:L], dtype=np.uint64)[None, :, None]
+    for g in elts:
+        s0, s1 = run_galois_sp(env, ctx, d0, d1, g, L)
+        h0, h1 = run_sum_sp(env, ctx, d0, d1, [g], L, False)
+        assert (h0 == s0).all() and (h1 == s1).all(), g
+        a0, a1 = run_sum_sp(env, ctx, d0, d1, [g], L, True)
+        assert (a0 == ((s0.astype(np.uint64) + c0) % qv)).all() and (a1 == ((s1.astype(np.uint64) + c1) % qv)).all(), g
+    ctx.close()
+
+
+# ---- test 3: one rounding, not G ------------------------------------------------------------------------------------
+def test_sum_sp_rounds_once(env):
+    """Test 3, the delta boundary at 4096 x 3, L = 2, elements 1 and 3: column p of both rows of half 0 of both keys is the
+    NTT of the constant 1 (all ones), so the single delta_0 of element e is centred(sigma_e(D_0 + D_1) mod P) and the
+    hoisted delta_0 is centred(sigma_1(S) + sigma_3(S) mod P), S = D_0 + D_1.  S is built so that on chosen coefficients x
+    the two single values a = S[x] and b = sigma_3(S)[x] each lie inside (-P/2, P/2] while a + b is (P - 1)/2,
+    (P + 1)/2, -(P - 1)/2, -(P + 1)/2, P - 1, -(P - 1) and 0: at and across the boundary on both sides.  Everywhere
+    else |S| < P/8, so no other coefficient wraps.  The construction is confirmed on the CPU expectation first; then
+    the GPU equals the definition, the sum of two ct_galois_sp outputs equals the sum of the single expectations, and the
+    two differ exactly where the expectations do."""
+    from oracle.pyoracle import Oracle
+    n, npr, L, B = 4096, 3, 2, 1
+    o = Oracle(n, npr)
+    q, p = o.q, npr - 1
+    P = q[p]
+    ctx = env["pkg"].Context(n, npr)
+    rng = np.random.default_rng(79)
+    elts = [1, 3]
+    keys = []
+    for _ in elts:
+        k0, k1 = rand_key(rng, q, n), rand_key(rng, q, n)
+        k0[0, p] = k0[1, p] = 1
+        keys.append((k0, k1))
+    assert (o.ntt(np.eye(1, n, 0, dtype=np.uint32)[0], p) == 1).all()
+    ctx.set_galois_keys_sp(elts, np.stack([k[0] for k in keys]), np.stack([k[1] for k in keys]))
+    targets = np.array([(P - 1) // 2, (P + 1) // 2, -(P - 1) // 2, -(P + 1) // 2, P - 1, -(P - 1), 0], dtype=np.int64)
+    wrapped = np.array([(P - 1) // 2, -(P - 1) // 2, -(P - 1) // 2, (P - 1) // 2, -1, 1, 0], dtype=np.int64)
+    assert (wrapped == centred(targets % P, P)).all()
+    pos, neg = V.galois_image(n, 3)
+    inv = np.empty(n, dtype=np.int64)
+    inv[pos] = np.arange(n)
+    xs = np.arange(5, 5 + 16 * len(targets), 16)            # the chosen coefficients, and their preimages under sigma_3
+    ks = inv[xs]
+    assert len(set(xs) | set(ks)) == 2 * len(targets)
+    S = rng.integers(-(P // 16), P // 16, n, dtype=np.int64)
+    a = targets // 2
+    b = targets - a
+    S[xs] = a
+    S[ks] = np.where(neg[ks], -b, b)
+    D0 = S // 2
+    D1 = S - D0
+    assert np.abs(D0).max() <= (q[0] - 1) // 2 and np.abs(D1).max() <= (q[1] - 1) // 2
+    c1 = np.stack([o.ntt((D % q[j]).astype(np.uint32), j) for j, D in enumerate((D0, D1))])[None]
+    c0 = rand_slab(rng, q, B, n, L)
+    # the construction, on the expectations
+    e0, e1, info = hoist_sp_expect(o, c0, c1, elts, keys)
+    assert (info[0]["D"][0] == D0).all() and (info[0]["D"][1] == D1).all()
+    single = [key_switch_sp(o, sigma_rows(o, c1[0], g), *key)["delta"][0] for g, key in zip(elts, keys)]
+    assert (single[0] == S).all() and (single[1] == sigma_coeff(S, 3)).all()       # no single delta wraps anywhere
+    assert (single[0][xs] == a).all() and (single[1][xs] == b).all()
+    assert (info[0]["delta"][0][xs] == wrapped).all()
+    total = single[0] + single[1]
+    assert (info[0]["delta"][0] == centred(total % P, P)).all()
+    crossing = np.abs(total) > P // 2
+    assert crossing[xs].tolist() == [False, True, False, True, True, True, False]
+    s0, s1 = sum_of_single_calls(o, c0, c1, elts, keys)
+    assert (e0 != s0).any()
+    # the GPU
+    d0, d1 = dev_t(env, c0), dev_t(env, c1)
+    g0, g1 = run_sum_sp(env, ctx, d0, d1, elts, L, False)
+    assert (g0 == e0).all() and (g1 == e1).all()
+    t0, t1 = np.zeros_like(c0), np.zeros_like(c1)
+    for g in elts:
+        r0, r1 = run_galois_sp(env, ctx, d0, d1, g, L)
+        t0[0], t1[0] = add_mod(o, t0[0], r0[0]), add_mod(o, t1[0], r1[0])
+    assert (t0 == s0).all() and (t1 == s1).all()
+    assert ((g0 != t0) == (e0 != s0)).all() and ((g1 != t1) == (e1 != s1)).all()
+    print(f"{int(crossing.sum())} coefficients cross the boundary; {int((e0 != s0).sum())} words of out0 differ")
+    ctx.close()
+
+
+# ---- test 4: the linear transform -----------------------------------------------------------------------------------
+def edge_diagonals(rng, q, G, n):
+    """[G][np][n] arbitrary 32-bit words: random, with 0, 1, q_i - 1, q_i and 2^32 - 1 on every row, the row at the
+    special prime among them."""
+    d = rng.integers(0, 2 ** 32, (G, len(q), n), dtype=np.uint32)
+    for i, qi in enumerate(q):
+        d[:, i, 3:8] = [0, 1, qi - 1, qi, 2 ** 32 - 1]
+        d[:, i, n - 5:] = [2 ** 32 - 1, qi, qi - 1, 1, 0]
+    return d
+
+
+@pytest.mark.parametrize("shape,levels,B", SP_CASES, ids=CASE_IDS)
+def test_lintrans_sp_matches_the_definition(env, slab_cases, shape, levels, B):
+    """Test 4: on the slabs and keys of test 1 (B = 2 at 16384 x 13), elements [3, n + 1, 3], diagonals of arbitrary
+    32-bit words with 0, 1, q_i - 1, q_i and 2^32 - 1 on data rows and on row p, with and without diag0, against the
+    definition; one plan serves every level of the case.  All-ones diagonals with diag0 all ones or absent give the
+    bytes of the sum form with add_input 1 or 0."""
+    torch = env["torch"]
+    case = slab_cases(shape, levels, B)
+    n, npr = shape
+    o, ctx = case["o"], case["ctx"]
+    elts = [3, n + 1, 3]
+    keys = [case["keys"][g] for g in elts]
+    diag = edge_diagonals(case["rng"], o.q, len(elts) + 1, n)
+    t_diag = dev_t(env, diag)
+    ones = torch.ones((len(elts) + 1, npr, n), dtype=torch.int32, device=env["dev"])
+    for with0 in (True, False):
+        plan = ctx.lintrans_plan_sp(elts, t_diag[1:].contiguous(), t_diag[0].contiguous() if with0 else None)
+        unit = ctx.lintrans_plan_sp(elts, ones[1:].contiguous(), ones[0].contiguous() if with0 else None)
+        for L in levels:
+            c0, c1 = case["slabs"][L]
+            d0, d1 = dev_t(env, c0), dev_t(env, c1)
+            e0, e1, _ = hoist_sp_expect(o, c0, c1, elts, keys, diag[1:], diag[0] if with0 else None)
+            g0, g1 = run_lintrans_sp(env, ctx, plan, d0, d1, L)
+            assert (g0 == e0).all() and (g1 == e1).all(), (L, with0)
+            u0, u1 = run_lintrans_sp(env, ctx, unit, d0, d1, L)
+            s0, s1 = run_sum_sp(env, ctx, d0, d1, elts, L, with0)
+            assert (u0 == s0).all() and (u1 == s1).all(), (L, with0)
+        plan.close()
+        unit.close()
+
+
+def test_lintrans_sp_plan_is_a_snapshot(env, slab_cases):
+    """Test 4: after set_galois_keys_sp with other words and after the diagonals are freed, a plan gives the bytes it
+    gave before; a plan made now gives others.  The shared keys are put back."""
+    shape, levels, B = SP_CASES[0]
+    case = slab_cases(shape, levels, B)
+    n, npr = shape
+    o, ctx = case["o"], case["ctx"]
+    elts, L = [3, n + 1], 2
+    c0, c1 = case["slabs"][L]
+    d0, d1 = dev_t(env, c0), dev_t(env, c1)
+    diag = edge_diagonals(np.random.default_rng(5), o.q, 3, n)
+    t_diag = dev_t(env, diag)
+    old = ctx.lintrans_plan_sp(elts, t_diag[1:].contiguous(), t_diag[0].contiguous())
+    before = run_lintrans_sp(env, ctx, old, d0, d1, L)
+    del t_diag
+    env["torch"].cuda.empty_cache()
+    rng = np.random.default_rng(6)
+    installed = list(case["keys"])
+    try:
+        ctx.set_galois_keys_sp(elts, np.stack([rand_key(rng, o.q, n) for _ in elts]),
+                               np.stack([rand_key(rng, o.q, n) for _ in elts]))
+        after = run_lintrans_sp(env, ctx, old, d0, d1, L)
+        assert (after[0] == before[0]).all() and (after[1] == before[1]).all()
+        t_diag = dev_t(env, diag)
+        new = ctx.lintrans_plan_sp(elts, t_diag[1:].contiguous(), t_diag[0].contiguous())
+        other = run_lintrans_sp(env, ctx, new, d0, d1, L)
+        assert (other[0] != before[0]).any() and (other[1] != before[1]).any()
+        new.close()
+    finally:
+        ctx.set_galois_keys_sp(installed, np.stack([case["keys"][g][0] for g in installed]),
+                               np.stack([case["keys"][g][1] for g in installed]))
+        old.close()
+
+
+# ---- tests 5 and 8: a real key --------------------------------------------------------------------------------------
+DIM = 8
+WINDOW = tuple(range(1, DIM))          # the moving sum and the matrix use the steps 1 .. 7
+IDENTITY_STEPS = (1, -3)
+
+
+def matrix():
+    """The example's fixed matrix: M[r][c] = ((7 r + 3 c + 1) mod 17 - 8) / 8, entries in [-1, 1]."""
+    r, c = np.meshgrid(np.arange(DIM), np.arange(DIM), indexing="ij")
+    return ((7 * r + 3 * c + 1) % 17 - 8) / 8.0
+
+
+def fill_keyed_case(env, case):
+    """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the special-prime Galois
+    keys of the steps 1 .. 7 and -3, installed; B = 4 fresh symmetric records with slot values in [-1, 1] and B = 4 with
+    8-periodic slot values, both dropped to np - 1 primes by ct_drop_primes (equal to the slices)."""
+    ctx, sk, pkg, torch = case["ctx"], case["sk"], env["pkg"], env["torch"]
+    n, npr, B = ctx.n, ctx.np, 4
+    L = npr - 1
+    steps = WINDOW + (-3,)
+    elts = [pkg.galois_element(n, s) for s in steps]
+    assert elts == [pow(3, s % (n // 2), 2 * n) for s in steps]
+    G = len(elts)
+    gk0, gk1 = ctx.gen_galois_keys_sp(sk, elts, V.derive_seeds("sp-hoist-gk-a", G * L), V.derive_seeds("sp-hoist-gk-e", G * L))
+    ctx.set_galois_keys_sp(elts, gk0, gk1)
+    x8 = np.random.default_rng(7000 + n).uniform(-1.0, 1.0, (B, DIM))
+    sets = dict(unit=unit_values(B, n, 6000 + n), tiled=np.tile(x8, (1, n // 2 // DIM)).astype(np.float32))
+    dropped = {}
+    for k, (name, vals) in enumerate(sets.items()):
+        c0, c1, _, st = encrypt_sym(env, ctx, vals, first=400 + 16 * k)
+        assert bool((st == 1).all())
+        words = B * L * n
+        o0, o1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+        ctx.ct_drop_primes(c0, o0, c1, o1, primes_in=npr, primes_out=L)
+        torch.cuda.synchronize()
+        l0, l1 = take(o0, words, (B, L, n), "drop"), take(o1, words, (B, L, n), "drop")
+        assert (l0 == host_u32(c0)[:, :L]).all() and (l1 == host_u32(c1)[:, :L]).all()
+        dropped[name] = (l0, l1)
+    case.update(key_of={s: (elts[k], (gk0[k], gk1[k])) for k, s in enumerate(steps)}, vals=sets, dropped=dropped)
+
+
+KEYED_SHAPES = [(4096, 3), (8192, 6)]
+SHAPE_IDS = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
+
+
+@pytest.mark.parametrize("shape", KEYED_SHAPES, ids=SHAPE_IDS)
+def test_sum_sp_exact_identity_with_a_real_key(env, keyed_cases, shape):
+    """Test 5, at L = np - 1 on two fresh dropped records, steps {1, -3}, add_input: with y, y' the oracle's centred
+    decrypts of the input and the output, D_j the centred digits of c1, e_{e,j} the errors of element e's key recovered
+    with the oracle, delta_k of the definition and T = sum_e sum_j negacyclic(sigma_e(D_j), e_{e,j}):
+    T - delta_0 - negacyclic(delta_1, s) is divisible by P in every coefficient and y' - y - sum_e sigma_e(y) equals the
+    quotient as integers.  The largest coefficient of the quotient is printed."""
+    from oracle.pyoracle import Oracle
+    c = keyed_cases(shape)
+    o, s_hat, ctx = c["o"], c["s_hat"], c["ctx"]
+    n, npr = shape
+    L = npr - 1
+    P = o.q[npr - 1]
+    lo = Oracle(n, L)
+    s_nat = centred(o.expand_ternary(c["sk"], 0), o.q[0])
+    l0, l1 = (x[:2] for x in c["dropped"]["unit"])
+    elts = [c["key_of"][s][0] for s in IDENTITY_STEPS]
+    keys = [c["key_of"][s][1] for s in IDENTITY_STEPS]
+    errs = [key_errors(o, k0, k1, s_hat, sigma_rows(o, np.stack(s_hat[:L]), g)) for g, (k0, k1) in zip(elts, keys)]
+    g0, g1 = run_sum_sp(env, ctx, dev_t(env, l0), dev_t(env, l1), elts, L, True)
+    e0, e1, info = hoist_sp_expect(o, l0, l1, elts, keys, w0=1)
+    assert (g0 == e0).all() and (g1 == e1).all()
+    for b in range(2):
+        y = np.array(expectation(lo, l0[b], l1[b], s_hat[:L])["y"], dtype=object)
+        y2 = np.array(expectation(lo, g0[b], g1[b], s_hat[:L])["y"], dtype=object)
+        T = np.zeros(n, dtype=np.int64)
+        rotated = y.copy()
+        for g, err in zip(elts, errs):
+            rotated = rotated + sigma_coeff(y, g)
+            for Dj, ej in zip(info[b]["D"], err):
+                T += negacyclic(sigma_coeff(Dj, g), ej)                     # below n . 2^29 . 64 < 2^49 per term
+        num = T - info[b]["delta"][0] - negacyclic(info[b]["delta"][1], s_nat)
+        assert (num % P == 0).all(), b
+        quo = num // P
+        assert ((y2 - rotated) == quo.astype(object)).all(), b
+        print(f"{n} x {npr}, record {b}: max |key-switch term of the sum of two rotations| = {int(np.abs(quo).max())}")
+
+
+@pytest.mark.parametrize("shape", KEYED_SHAPES, ids=SHAPE_IDS)
+def test_moving_sum_end_to_end_at_the_fresh_scale(env, keyed_cases, shape):
+    """Test 8 (a): encrypt -> ct_drop_primes -> ONE ct_galois_sum_sp (steps 1 .. 7, add_input) -> decrypt_level(np - 1,
+    Delta) on B = 4 records with slot values in [-1, 1]: the stage equals its definition, the decode equals the oracle's
+    on the output records bit for bit, and the slots are within the reference's 0.1 of the rolled sum, asserted on the
+    expectation first (tools/ct_keyswitch_sp_noise_sim.py admits both shapes).  The worst error is printed."""
+    from oracle.pyoracle import Oracle
+    c = keyed_cases(shape)
+    ctx, o = c["ctx"], c["o"]
+    n, npr = shape
+    L = npr - 1
+    lo = Oracle(n, L)
+    vals = c["vals"]["unit"]
+    B = vals.shape[0]
+    l0, l1 = c["dropped"]["unit"]
+    elts = [c["key_of"][s][0] for s in WINDOW]
+    keys = [c["key_of"][s][1] for s in WINDOW]
+    g0, g1 = run_sum_sp(env, ctx, dev_t(env, l0), dev_t(env, l1), elts, L, True)
+    e0, e1, _ = hoist_sp_expect(o, l0, l1, elts, keys, w0=1)
+    assert (g0 == e0).all() and (g1 == e1).all()
+    got = run_decrypt(env, ctx, dev_t(env, g0), dev_t(env, g1), L, o.scale)
+    worst = 0.0
+    for b in range(B):
+        e = expectation(lo, g0[b], g1[b], c["s_hat"][:L], o.scale)
+        assert e["status"] == 1
+        assert_matches(got, b, e, ("moving sum", b))
+        want = sum(np.roll(vals[b].astype(np.float64), -s) for s in (0,) + WINDOW)
+        err_e = float(np.abs(e["values"].astype(np.float64) - want).max())
+        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want).max())
+        print(f"record {b}: max |values - moving sum| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
+        assert err_e < 0.1 and err_g < 0.1, (b, err_e, err_g)
+        worst = max(worst, err_g)
+    print(f"{n} x {npr}, moving sum of 8 at the fresh scale: worst error {worst:.3e}")
+
+
+@pytest.mark.parametrize("shape", KEYED_SHAPES, ids=SHAPE_IDS)
+def test_matvec_end_to_end_without_a_lift(env, keyed_cases, shape):
+    """Test 8 (b): encode_ntt of the eight diagonals of M at Delta -> lintrans_plan_sp -> ONE ct_lintrans_sp on fresh
+    dropped records -> ct_rescale -> decrypt_level(np - 2, Delta^2 / q_{np-2}) on B = 4 records of 8-periodic slot values
+    in [-1, 1]: every stage equals its definition (the encoded diagonals equal the oracle's), the decode equals the
+    oracle's bit for bit, and the slots are within the reference's 0.1 of M x, on the expectation first.  The worst error
+    is printed."""
+    from oracle.pyoracle import Oracle
+    torch = env["torch"]
+    c = keyed_cases(shape)
+    ctx, o = c["ctx"], c["o"]
+    n, npr = shape
+    L = npr - 1
+    lo, lo1 = Oracle(n, L), Oracle(n, L - 1)
+    vals = c["vals"]["tiled"]
+    B = vals.shape[0]
+    l0, l1 = c["dropped"]["tiled"]
+    elts = [c["key_of"][s][0] for s in WINDOW]
+    keys = [c["key_of"][s][1] for s in WINDOW]
+    M = matrix()
+    k = np.arange(n // 2)
+    dvals = np.stack([M[k % DIM, (k + e) % DIM] for e in range(DIM)]).astype(np.float32)
+    enc = sentinel_out(env, DIM * npr * n, 2 * n)
+    ctx.encode_ntt(dev_t(env, dvals), enc)
+    torch.cuda.synchronize()
+    ok, enc_want = o.encode_ntt_batch(dvals)
+    assert ok
+    diag = take(enc, DIM * npr * n, (DIM, npr, n), "encoded diagonals")
+    assert (diag == enc_want).all()
+    t_diag = dev_t(env, diag)
+    plan = ctx.lintrans_plan_sp(elts, t_diag[1:].contiguous(), t_diag[0].contiguous())
+    g0, g1 = run_lintrans_sp(env, ctx, plan, dev_t(env, l0), dev_t(env, l1), L)
+    plan.close()
+    e0, e1, _ = hoist_sp_expect(o, l0, l1, elts, keys, diag[1:], diag[0])
+    assert (g0 == e0).all() and (g1 == e1).all(), "plan call"
+    words = B * (L - 1) * n
+    s0, s1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_rescale(dev_t(env, g0), s0, dev_t(env, g1), s1, primes=L)
+    torch.cuda.synchronize()
+    f0, f1 = take(s0, words, (B, L - 1, n), "rescale"), take(s1, words, (B, L - 1, n), "rescale")
+    assert (f0 == rescale_expect(lo, g0)).all() and (f1 == rescale_expect(lo, g1)).all()
+    scale = o.scale * o.scale / o.q[L - 1]
+    got = run_decrypt(env, ctx, dev_t(env, f0), dev_t(env, f1), L - 1, scale)
+    want_slots = np.tile(vals.astype(np.float64)[:, :DIM] @ M.T, (1, n // 2 // DIM))
+    worst = 0.0
+    for b in range(B):
+        e = expectation(lo1, f0[b], f1[b], c["s_hat"][:L - 1], scale)
+        assert e["status"] == 1
+        assert_matches(got, b, e, ("matvec", b))
+        err_e = float(np.abs(e["values"].astype(np.float64) - want_slots[b]).max())
+        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want_slots[b]).max())
+        print(f"record {b}: max |values - M x| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
+        assert err_e < 0.1 and err_g < 0.1, (b, err_e, err_g)
+        worst = max(worst, err_g)
+    print(f"{n} x {npr}, M x on fresh records: worst error {worst:.3e}")
+
+
+# ---- tests 6 and 7: installs, kinds and arguments -------------------------------------------------------------------
+def test_sp_hoist_installs_and_kinds(env):
+    """Test 6: with only digit keys installed the sum entry and lintrans_create_sp are SE_ERR_NO_KEY (*out stays NULL);
+    an element missing from the special-prime set is SE_ERR_NO_KEY with the element named; a digit plan passed to the new
+    execute entry and a special-prime plan passed to se_amd_ct_lintrans_device are -22, as is a plan of another context,
+    and the sentinels are intact; se_amd_lintrans_destroy(NULL) is a no-op."""
+    torch, pkg = env["torch"], env["pkg"]
+    n, npr, B = 4096, 3, 2
+    ctx, other = pkg.Context(n, npr), pkg.Context(n, npr)
+    L, h = ctx.L, ctx.h
+    c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
+    c1 = torch.zeros_like(c0)
+    out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
+    out1 = torch.full_like(out0, SENTINEL)
+    diag = torch.ones((2, npr, n), dtype=torch.int32, device=env["dev"])
+    diag0 = torch.ones((npr, n), dtype=torch.int32, device=env["dev"])
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    z = C.c_void_p(None)
+    s = stream_of(env)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    good, nokey = np.array([3, 9], dtype=np.uint32), np.array([3, 5], dtype=np.uint32)
+
+    def create(f, ctx_h, elts, G, d, d0, pt):
+        handle = C.c_void_p(0xDEAD)                         # a failed create must overwrite it with NULL
+        return f(ctx_h, hp(elts), G, d, d0, pt, C.byref(handle)), handle
+
+    fs = L.se_amd_ct_galois_sum_sp_device
+    dkey = np.zeros((2, 2 * npr, npr, n), dtype=np.uint32)
+    ctx.set_galois_keys([3, 9], dkey, dkey)
+    assert fs(h, p(c0), p(c1), B, 2, hp(good), 2, 1, p(out0), p(out1), s) == SE_ERR_NO_KEY
+    rc, handle = create(L.se_amd_lintrans_create_sp, h, good, 2, p(diag), p(diag0), npr)
+    assert rc == SE_ERR_NO_KEY and handle.value is None
+    key = np.zeros((2, npr - 1, npr, n), dtype=np.uint32)
+    ctx.set_galois_keys_sp([3, 9], key, key)
+    other.set_galois_keys_sp([3, 9], key, key)
+    assert fs(h, p(c0), p(c1), B, 2, hp(nokey), 2, 1, p(out0), p(out1), s) == SE_ERR_NO_KEY
+    assert "special-prime" in L.se_amd_last_error().decode() and "element 5" in L.se_amd_last_error().decode()
+    rc, handle = create(L.se_amd_lintrans_create_sp, h, nokey, 2, p(diag), p(diag0), npr)
+    assert rc == SE_ERR_NO_KEY and handle.value is None
+    assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
+    rc, digit = create(L.se_amd_lintrans_create, h, good, 2, p(diag), p(diag0), npr)
+    assert rc == 0 and digit.value
+    rc, sp = create(L.se_amd_lintrans_create_sp, h, good, 2, p(diag), p(diag0), npr)
+    assert rc == 0 and sp.value
+    rc, foreign = create(L.se_amd_lintrans_create_sp, other.h, good, 2, p(diag), p(diag0), npr)
+    assert rc == 0 and foreign.value
+    fd, fp = L.se_amd_ct_lintrans_device, L.se_amd_ct_lintrans_sp_device
+    assert fp(h, digit, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
+    assert fd(h, sp, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
+    assert fp(h, foreign, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
+    assert fp(other.h, sp, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
+    torch.cuda.synchronize()
+    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    # each plan serves the entry of its kind: zero keys and zero slabs give zero rows
+    for f, pl in ((fd, digit), (fp, sp)):
+        out0.fill_(SENTINEL)
+        out1.fill_(SENTINEL)
+        assert f(h, pl, p(c0), p(c1), B, 2, p(out0), p(out1), s) == 0
+        torch.cuda.synchronize()
+        for o in (out0, out1):
+            flat = o.reshape(-1)
+            assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+    L.se_amd_lintrans_destroy(None)
+    for pl in (digit, sp, foreign):
+        L.se_amd_lintrans_destroy(pl)
+    ctx.close()
+    other.close()
+
+
+def test_sp_hoist_arguments(env):
+    """Test 7: every argument error returns -22 and writes nothing: NULL pointers, each alignment, B = 2^32, primes 0, np
+    and np + 1, elts NULL, G = 0 and 65, an even element, an element >= 2n, pt_primes other than np, and all three
+    entries on a context of one prime.  B = 0 returns 0; a level-1 call writes B . n words and nothing behind them."""
+    torch, pkg = env["torch"], env["pkg"]
+    n, npr, B = 4096, 3, 2
+    ctx = pkg.Context(n, npr)
+    L, h = ctx.L, ctx.h
+    key = np.zeros((2, npr - 1, npr, n), dtype=np.uint32)
+    ctx.set_galois_keys_sp([3, 9], key, key)
+    c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
+    c1 = torch.zeros_like(c0)
+    out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
+    out1 = torch.full_like(out0, SENTINEL)
+    diag = torch.ones((2, npr, n), dtype=torch.int32, device=env["dev"])
+    diag0 = torch.ones((npr, n), dtype=torch.int32, device=env["dev"])
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    z = C.c_void_p(None)
+    s = stream_of(env)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the G = 65 call
+    good, even, big = el(3, 9), el(3, 4), el(3, 2 * n + 1)
+    P0, P1, O0, O1, E, D, D0 = p(c0), p(c1), p(out0), p(out1), hp(good), p(diag), p(diag0)
+    fs, fc, fp = L.se_amd_ct_galois_sum_sp_device, L.se_amd_lintrans_create_sp, L.se_amd_ct_lintrans_sp_device
+    bad_sums = [
+        (None, P0, P1, B, 2, E, 2, 1, O0, O1, s),
+        (h, z, P1, B, 2, E, 2, 1, O0, O1, s),                        # NULL mandatory pointers
+        (h, P0, z, B, 2, E, 2, 1, O0, O1, s),
+        (h, P0, P1, B, 2, E, 2, 1, z, O1, s),
+        (h, P0, P1, B, 2, E, 2, 1, O0, z, s),
+        (h, P0, P1, B, 0, E, 2, 1, O0, O1, s),                       # primes outside [1, np - 1]
+        (h, P0, P1, B, npr, E, 2, 1, O0, O1, s),                     # primes = np: the special prime is not data
+        (h, P0, P1, B, npr + 1, E, 2, 1, O0, O1, s),
+        (h, P0, P1, 2 ** 32, 2, E, 2, 1, O0, O1, s),                 # B >= 2^32
+        (h, p(c0, 4), P1, B, 2, E, 2, 1, O0, O1, s),                 # alignment, each slab
+        (h, P0, p(c1, 8), B, 2, E, 2, 1, O0, O1, s),
+        (h, P0, P1, B, 2, E, 2, 1, p(out0, 12), O1, s),
+        (h, P0, P1, B, 2, E, 2, 1, O0, p(out1, 4), s),
+        (h, P0, P1, B, 2, z, 2, 1, O0, O1, s),                       # elts NULL, G = 0, G = 65
+        (h, P0, P1, B, 2, E, 0, 1, O0, O1, s),
+        (h, P0, P1, B, 2, E, 65, 1, O0, O1, s),
+        (h, P0, P1, B, 2, hp(even), 2, 1, O0, O1, s),                # an even element, one >= 2n
+        (h, P0, P1, B, 2, hp(big), 2, 1, O0, O1, s),
+    ]
+    for k, args in enumerate(bad_sums):
+        assert fs(*args) == SE_ERR_INVALD_ARGUMENT, k
+
+    def create(ctx_h, elts, G, d, d0, pt, want_out=True, f=fc):
+        handle = C.c_void_p(0xDEAD)
+        return f(ctx_h, elts, G, d, d0, pt, C.byref(handle) if want_out else None), handle
+
+    bad_creates = [
+        (None, E, 2, D, D0, npr),
+        (h, z, 2, D, D0, npr),                               # NULL elts, d_diag
+        (h, E, 2, z, D0, npr),
+        (h, E, 0, D, D0, npr),                               # G = 0, G = 65
+        (h, E, 65, D, D0, npr),
+        (h, E, 2, D, D0, 0),                                 # pt_primes must be np
+        (h, E, 2, D, D0, npr - 1),
+        (h, E, 2, D, D0, npr + 1),
+        (h, hp(even), 2, D, D0, npr),                        # an even element, one >= 2n
+        (h, hp(big), 2, D, D0, npr),
+        (h, E, 2, p(diag, 4), D0, npr),                      # alignment of either diagonal pointer
+        (h, E, 2, D, p(diag0, 8), npr),
+    ]
+    for k, args in enumerate(bad_creates):
+        rc, handle = create(*args)
+        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, (k, rc, handle.value)
+    assert create(h, E, 2, D, D0, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT       # NULL out
+    rc, plan = create(h, E, 2, D, D0, npr)
+    assert rc == 0 and plan.value
+    bad_calls = [
+        (None, plan, P0, P1, B, 2, O0, O1, s),
+        (h, plan, z, P1, B, 2, O0, O1, s),                   # NULL slab pointers
+        (h, plan, P0, z, B, 2, O0, O1, s),
+        (h, plan, P0, P1, B, 2, z, O1, s),
+        (h, plan, P0, P1, B, 2, O0, z, s),
+        (h, plan, P0, P1, B, 0, O0, O1, s),                  # primes outside [1, np - 1]
+        (h, plan, P0, P1, B, npr, O0, O1, s),
+        (h, plan, P0, P1, B, npr + 1, O0, O1, s),
+        (h, plan, P0, P1, 2 ** 32, 2, O0, O1, s),            # B >= 2^32
+        (h, plan, p(c0, 4), P1, B, 2, O0, O1, s),            # alignment, each slab
+        (h, plan, P0, p(c1, 8), B, 2, O0, O1, s),
+        (h, plan, P0, P1, B, 2, p(out0, 12), O1, s),
+        (h, plan, P0, P1, B, 2, O0, p(out1, 4), s),
+        (h, z, P0, P1, B, 2, O0, O1, s),                     # no plan
+    ]
+    for k, args in enumerate(bad_calls):
+        assert fp(*args) == SE_ERR_INVALD_ARGUMENT, k
+    assert fs(h, P0, P1, 0, 2, E, 2, 1, O0, O1, s) == 0
+    assert fp(h, plan, P0, P1, 0, 2, O0, O1, s) == 0
+    # a context of one prime has no prime to reserve
+    one = pkg.Context(1024, 1)
+    assert one.L.se_amd_ct_galois_sum_sp_device(one.h, P0, P1, B, 1, E, 2, 1, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
+    rc, handle = create(one.h, E, 2, D, D0, 1, f=one.L.se_amd_lintrans_create_sp)
+    assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None
+    assert one.L.se_amd_ct_lintrans_sp_device(one.h, plan, P0, P1, B, 1, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
+    one.close()
+    torch.cuda.synchronize()
+    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    for call in (lambda: fs(h, P0, P1, B, 1, E, 2, 1, O0, O1, s), lambda: fp(h, plan, P0, P1, B, 1, O0, O1, s)):
+        out0.fill_(SENTINEL)
+        out1.fill_(SENTINEL)
+        assert call() == 0
+        torch.cuda.synchronize()
+        for o in (out0, out1):
+            flat = o.reshape(-1)
+            assert int(torch.count_nonzero(flat[:B * n])) == 0 and bool((flat[B * n:] == SENTINEL).all())
+    L.se_amd_lintrans_destroy(plan)
+    ctx.close()
+
+
+# ---- test 9: the example --------------------------------------------------------------------------------------------
+def test_matvec_fresh_example(env, tmp_path):
+    """examples/matvec_fresh_roundtrip.c from plain gcc: encrypt, drop to np - 1, the diagonals of M encoded at Delta and
+    folded into a special-prime plan, ONE se_amd_ct_lintrans_sp_device call, rescale and decrypt_level come back within the
+    reference's 0.1 of M x."""
+    exe = build_example("matvec_fresh_roundtrip", tmp_path, hip=True, extra=("-lm",))
+    r = subprocess.run([str(exe), "4096", "3", "8"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"failed=0 B=8 .*max_abs_error=([0-9.e+-]+)", r.stdout)
+    assert m and float(m.group(1)) < 0.1, r.stdout
