@@ -549,7 +549,8 @@ int se_amd_ct_galois_sum_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uin
 /* Linear transforms: plaintext-weighted sums of hoisted rotations (the diagonal method),
  *     y = d0 . x + sum_e d_e . rot_{elts[e]}(x)      slot-wise,
  * an encrypted matrix-vector product by generalised diagonals, a convolution with arbitrary taps, the baby steps of a
- * baby-step / giant-step product.  rot0 / rot1 are exactly those of the hoisted rotations above -- the digits of c1
+ * baby-step / giant-step product (the plan for that product, which reaches beyond 64 diagonals, is se_amd_bsgs_create
+ * further down).  rot0 / rot1 are exactly those of the hoisted rotations above -- the digits of c1
  * itself, the Galois keys installed when the plan was created, src_e = se_amd_galois_table(elts[e]) -- and the
  * diagonals are plaintexts in the layout se_amd_encode_ntt_device writes.  For record b, i < primes, mod q_i, canonical:
  *     out0[b][i][k] = d0[i][k] . c0[b][i][k] + sum_e d_e[i][k] . rot0[e][b][i][k]
@@ -679,8 +680,8 @@ int se_amd_ct_drop_primes_device(se_amd_ctx *ctx, const uint32_t *d_in0, const u
  * A plan has a kind: se_amd_ct_lintrans_device refuses a special-prime plan and se_amd_ct_lintrans_sp_device refuses a
  * digit plan, both with SE_ERR_INVALD_ARGUMENT and nothing written.
  * Out of scope: the MANY form on the special-prime key (each output needs its own delta and its own division by P, so
- * hoisting would save only the shared pass transforms), baby-step / giant-step plans, several special primes, custom
- * chains, host-pointer and multi-device forms. */
+ * hoisting would save only the shared pass transforms), baby-step / giant-step plans on this key (the digit-key family
+ * has them: se_amd_bsgs_create below), several special primes, custom chains, host-pointer and multi-device forms. */
 int se_amd_ct_galois_sum_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                    const uint32_t *elts /*host, [G]*/, size_t G, int add_input, uint32_t *d_out0,
                                    uint32_t *d_out1, void *stream);
@@ -688,6 +689,76 @@ int se_amd_lintrans_create_sp(se_amd_ctx *ctx, const uint32_t *elts /*host, [G]*
                               const uint32_t *d_diag0, size_t pt_primes, se_amd_lintrans **out);
 int se_amd_ct_lintrans_sp_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0, const uint32_t *d_c1,
                                  size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
+/* ---- baby-step / giant-step linear transforms on the digit Galois keys ----------------------------------
+ * A linear-transform plan above costs one Galois key and one folded key block per diagonal, so it ends at
+ * SE_AMD_MAX_GALOIS_KEYS = 64 diagonals.  With the diagonals indexed by a product of elements,
+ *     y = sum_{g < n2, b < n1} d[g][b] . rot_{giant[g] . baby[b] mod 2n}(x)       slot-wise,
+ * n1 + n2 - 2 keys serve n1 . n2 diagonals (64 as 8 x 8: 14 keys instead of 63; 2048 as 32 x 64: 94 keys), and a plan
+ * holds diagonals only.  The digit-key family only (se_amd_set_galois_keys, 15-bit digits), every degree and level its
+ * entries serve.  Conventions are theirs: level-`primes` slabs [records][primes][n] in NTT form, bit-reversed order,
+ * canonical residues; 16-byte aligned device pointers; asynchronous on `stream`; outputs do not overlap inputs; nothing
+ * is launched or written on an error; B = 0 is a successful no-op; errors through se_amd_last_error.
+ * se_amd_ct_mul_plain_sum_device: a plaintext-weighted sum over a stack of E batches, key-free, one launch.
+ *     in  (d_in0, d_in1)   [E][B][primes][n]          d_in1 and d_out1 both NULL: one slab
+ *     pt  d_pt             [Gout][E][pt_primes][n]    the layout se_amd_encode_ntt_device writes; pt_primes >= primes
+ *     out (d_out0, d_out1) [Gout][B][primes][n]
+ *     out[g][b][i][k] = sum_{e < E} (pt[g][e][i][k] mod q_i) . in[e][b][i][k]     mod q_i, canonical.
+ * 1 <= E <= 64 and 1 <= Gout <= 64.  Any 32-bit plaintext word stands for its residue, as in
+ * se_amd_ct_mul_plain_device; every bit is fixed: the result equals se_amd_ct_mul_plain_device per (g, e) followed by the
+ * modular sum, and is exact for every input (E = 64 with all words at q_i - 1 included).  SE_ERR_INVALD_ARGUMENT for the
+ * argument errors of se_amd_ct_mul_plain_device (a NULL d_in0 / d_out0 / d_pt, one of d_in1 / d_out1 alone, primes outside
+ * [1, np], pt_primes < primes, B at or above 2^32, a pointer that is not 16-byte aligned), E or Gout outside [1, 64],
+ * E . B or Gout . B at or above 2^32.
+ * se_amd_ct_galois_accum_device: rotate G DIFFERENT ciphertexts and add, one launch, no scratch.
+ *     in (d_in0, d_in1) [G][B][primes][n];  elts HOST [G], 1 <= G <= 64, odd, below 2n, repeats allowed
+ *     out[b] = sum_{g < G} rho_g(in[g][b])     mod q_i, canonical, [B][primes][n]
+ * rho_g is the map of se_amd_ct_galois_device with elts[g] (the digits of sigma(c1), the installed digit key), and the
+ * identity when elts[g] == 1, which needs no key.  The output equals, bit for bit, the modular sum of G
+ * se_amd_ct_galois_device outputs.  SE_ERR_INVALD_ARGUMENT for the argument errors of se_amd_ct_galois_many_device, and
+ * for G . B at or above 2^32; SE_ERR_NO_KEY when an element other than 1 has no installed key (the last-error text names
+ * it).
+ * The plan.  se_amd_bsgs_create: baby HOST [n1], giant HOST [n2], 1 <= n1, n2 <= 64, elements odd and below 2n, no
+ * element twice within a list (SE_ERR_INVALD_ARGUMENT); element 1 may appear once in each list and needs no key.  d_diag
+ * is DEVICE memory [n2][n1][pt_primes][n], pt_primes >= 1: d[g][b] is the diagonal of the COMPOSITE element giant[g] .
+ * baby[b] mod 2n, unrotated, as a flat plan would take it.  The plan serves primes <= min(pt_primes, np).  Create stores
+ *     d'[g][b][i][k] = d[g][b][i][src_{giant[g]^-1 mod 2n}(k)],      src from se_amd_galois_table:
+ * on an NTT-form row a plaintext rotation is that permutation and src_a o src_{a^-1} is the identity, so
+ * sigma_gamma(d' . z) = d . sigma_gamma(z).  The plan is a snapshot of the diagonals ONLY: create synchronises, the
+ * diagonals may be freed afterwards, and no key is read.  Plan memory: n1 . n2 . pt_primes . n words (no Shoup
+ * companions: the step that reads them is bound by memory traffic, which they would double).  A failed create leaves
+ * *out NULL.  se_amd_bsgs_destroy waits for the device, then frees; NULL is a no-op; destroy plans before their context.
+ * se_amd_ct_bsgs_device is fixed bit for bit as
+ *     rot[b]   = (c0, c1) if baby[b] == 1, else the se_amd_ct_galois_many_device output for baby[b]  (digits of c1 itself)
+ *     inner[g] = sum_b d'[g][b] . rot[b]                          se_amd_ct_mul_plain_sum_device
+ *     out      = sum_g rho_g(inner[g])                            se_amd_ct_galois_accum_device, elements giant[g]
+ * Keys are read from the context at CALL time: SE_ERR_NO_KEY names the element without a key, and a later
+ * se_amd_set_galois_keys takes effect on the next call.  The scale is multiplied by the diagonals' scale, the level is
+ * unchanged; the result carries the key-switch term of a baby step weighted by a diagonal and that of a giant step on top.
+ * Workspace: the caller's, used in stream order; no context scratch, no hidden allocation, no host synchronisation.  One
+ * record needs 2 . (n1 + n2) . primes . n . 4 bytes (both halves of the rot and of the inner stack);
+ * se_amd_bsgs_workspace_bytes returns records times that (0 for a NULL plan).  The call takes Bc = min(B, workspace_bytes
+ * / per-record) and walks the batch in chunks of Bc records: the chunk is copied into the identity slot of rot (if 1 is
+ * listed), the many form fills the other slots, then the two steps above, the second straight into the chunk's output
+ * rows.  Every chunk size gives the same bits.  SE_ERR_INVALD_ARGUMENT for the pointer, alignment, level and B checks of
+ * se_amd_ct_galois_device, a NULL plan, a plan of another context, primes above the plan's levels, a NULL workspace, one
+ * that is not 16-byte aligned or one below one record.
+ * Out of scope: the special-prime family (it has no many form for the baby steps), a one-division giant sum, sparse
+ * diagonal masks, multi-device and host-pointer forms. */
+int se_amd_ct_mul_plain_sum_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
+                                   size_t E, size_t B, size_t primes, const uint32_t *d_pt, size_t Gout, size_t pt_primes,
+                                   uint32_t *d_out0, uint32_t *d_out1 /* NULL with d_in1 */, void *stream);
+int se_amd_ct_galois_accum_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes,
+                                  const uint32_t *elts /*host, [G]*/, size_t G, uint32_t *d_out0, uint32_t *d_out1,
+                                  void *stream);
+typedef struct se_amd_bsgs se_amd_bsgs;
+int se_amd_bsgs_create(se_amd_ctx *ctx, const uint32_t *baby /*host, [n1]*/, size_t n1, const uint32_t *giant /*host, [n2]*/,
+                       size_t n2, const uint32_t *d_diag /*device, [n2][n1][pt_primes][n]*/, size_t pt_primes,
+                       se_amd_bsgs **out);
+void se_amd_bsgs_destroy(se_amd_bsgs *plan);
+size_t se_amd_bsgs_workspace_bytes(const se_amd_bsgs *plan, size_t records, size_t primes);
+int se_amd_ct_bsgs_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                          size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes,
+                          void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_gen_relin_key_sp", "se_amd_set_relin_key_sp", "se_amd_gen_galois_keys_sp", "se_amd_set_galois_keys_sp",
     "se_amd_ct_relin_sp_device", "se_amd_ct_galois_sp_device", "se_amd_ct_drop_primes_device",
     "se_amd_ct_galois_sum_sp_device", "se_amd_lintrans_create_sp", "se_amd_ct_lintrans_sp_device",
+    "se_amd_ct_mul_plain_sum_device", "se_amd_ct_galois_accum_device", "se_amd_bsgs_create", "se_amd_bsgs_destroy",
+    "se_amd_bsgs_workspace_bytes", "se_amd_ct_bsgs_device",
 )
 
 
@@ -185,6 +187,14 @@ def lib():
     L.se_amd_ct_galois_sum_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, i32, vp, vp, vp]
     L.se_amd_lintrans_create_sp.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(vp)]
     L.se_amd_ct_lintrans_sp_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    L.se_amd_ct_mul_plain_sum_device.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, sz, vp, vp, vp]
+    L.se_amd_ct_galois_accum_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
+    L.se_amd_bsgs_create.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp)]
+    L.se_amd_bsgs_destroy.argtypes = [vp]
+    L.se_amd_bsgs_destroy.restype = None
+    L.se_amd_bsgs_workspace_bytes.argtypes = [vp, sz, sz]
+    L.se_amd_bsgs_workspace_bytes.restype = sz
+    L.se_amd_ct_bsgs_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp]
     _lib = L
     return L
 
@@ -257,6 +267,24 @@ def galois_table(n, elt):
     src = np.zeros(n, np.uint16)
     _check(lib().se_amd_galois_table(n, int(elt), _ptr(src)), "se_amd_galois_table")
     return src
+
+
+class BsgsPlan:
+    """Handle of se_amd_bsgs_create (Context.bsgs_plan)."""
+
+    def __init__(self, L, h):
+        self.L, self.h = L, h
+
+    def close(self):
+        if self.h:
+            self.L.se_amd_bsgs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Group:
@@ -845,6 +873,61 @@ class Context:
         _check(self.L.se_amd_ct_lintrans_sp_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
                                                    c0.shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
                "se_amd_ct_lintrans_sp_device")
+
+    # ---- baby-step / giant-step linear transforms on the digit Galois keys
+    def ct_mul_plain_sum(self, in0, pt, out0, in1=None, out1=None, primes=None):
+        """Key-free weighted sum over a stack: in [E][B][primes][n] (one slab or two), pt [Gout][E][pt_primes][n] in
+        encode_ntt's layout, out [Gout][B][primes][n]; out[g][b] = sum_e pt[g][e] . in[e][b] mod q_i, canonical.  Any
+        32-bit plaintext word stands for its residue."""
+        E, B = in0.shape[0], in0.shape[1]
+        if primes is None:
+            primes = in0.shape[2]
+        _check(self.L.se_amd_ct_mul_plain_sum_device(self.h, _ptr(in0), _ptr(in1), E, B, primes, _ptr(pt), pt.shape[0],
+                                                     pt.shape[2], _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_mul_plain_sum_device")
+
+    def ct_galois_accum(self, in0, in1, elts, out0, out1, primes=None):
+        """Rotate G different records and add: in [G][B][primes][n], out[b] = sum_g ct_galois(in[g][b], elts[g]) mod q_i
+        with the installed Galois keys, [B][primes][n]; element 1 is the identity and needs no key.  Bit-identical to
+        the modular sum of G ct_galois outputs."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = in0.shape[2]
+        _check(self.L.se_amd_ct_galois_accum_device(self.h, _ptr(in0), _ptr(in1), in0.shape[1], primes, _ptr(el),
+                                                    el.size, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_galois_accum_device")
+
+    def bsgs_plan(self, baby, giant, diag, pt_primes=None):
+        """The plan of y = sum_{g,b} diag[g][b] . rot_{giant[g] baby[b] mod 2n}(x): diag [n2][n1][pt_primes][n], a device
+        tensor in the layout encode_ntt writes, the diagonal of the COMPOSITE element unrotated.  A snapshot of the
+        diagonals only (it synchronises); keys are read at call time.  Returns an object with .close(); close it before
+        the context."""
+        import numpy as np
+        bs = np.ascontiguousarray(baby, dtype=np.uint32).reshape(-1)
+        gs = np.ascontiguousarray(giant, dtype=np.uint32).reshape(-1)
+        if pt_primes is None:
+            pt_primes = diag.shape[2]
+        h = C.c_void_p()
+        _check(self.L.se_amd_bsgs_create(self.h, _ptr(bs), bs.size, _ptr(gs), gs.size, _ptr(diag), pt_primes,
+                                         C.byref(h)), "se_amd_bsgs_create")
+        return BsgsPlan(self.L, h)
+
+    def bsgs_workspace_bytes(self, plan, records, primes):
+        """Bytes of workspace ct_bsgs needs to take `records` records of level `primes` in one chunk."""
+        return int(self.L.se_amd_bsgs_workspace_bytes(plan.h if plan is not None else None, records, primes))
+
+    def ct_bsgs(self, plan, c0, c1, out0, out1, workspace, primes=None, workspace_bytes=None):
+        """The plan's transform of the records (c0, c1) [B][primes][n] -> (out0, out1) [B][primes][n]: the many form for
+        the baby steps, ct_mul_plain_sum, ct_galois_accum for the giant steps, in chunks of what `workspace` (a device
+        tensor, 16-byte aligned) holds.  Every chunk size gives the same bits."""
+        if primes is None:
+            primes = c0.shape[1]
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+        _check(self.L.se_amd_ct_bsgs_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
+                                            c0.shape[0], primes, _ptr(out0), _ptr(out1), _ptr(workspace),
+                                            workspace_bytes, _stream_ptr()), "se_amd_ct_bsgs_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

@@ -6,7 +6,9 @@
 // from one digit decomposition (se_amd_ct_galois_many_device, se_amd_ct_galois_sum_device, at the end of the file), and
 // the plaintext-weighted sum of hoisted rotations under a plan (se_amd_ct_lintrans_device, behind them), and the
 // special-prime key switch that relinearises and rotates at the record's own scale (se_amd_ct_relin_sp_device,
-// se_amd_ct_galois_sp_device, behind k_ct_galois).
+// se_amd_ct_galois_sp_device, behind k_ct_galois), and the two device steps of a baby-step / giant-step transform: the
+// plaintext-weighted sum over a stack of batches and the rotate-and-accumulate over different records
+// (se_amd_ct_mul_plain_sum_device, se_amd_ct_galois_accum_device, se_amd_ct_bsgs_device, behind the special-prime hoist).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -59,6 +61,13 @@ struct Lane4
         a[1] += (uint64_t)v.y * w;
         a[2] += (uint64_t)v.z * w;
         a[3] += (uint64_t)v.w * w;
+    }
+    __device__ __forceinline__ void mad4(const uint4 &v, const uint4 &w)
+    {
+        a[0] += (uint64_t)v.x * w.x;
+        a[1] += (uint64_t)v.y * w.y;
+        a[2] += (uint64_t)v.z * w.z;
+        a[3] += (uint64_t)v.w * w.w;
     }
     __device__ __forceinline__ void reduce(uint32_t q, uint32_t cr_hi, uint32_t cr_lo)
     {
@@ -1533,6 +1542,239 @@ hipError_t launch_ct_hoist_sp(const DevParams &P, const DevTables &T, const Resc
         const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
         return A.weighted ? launch(k_ct_lintrans_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
                           : launch(k_ct_galois_sum_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Baby-step / giant-step linear transforms (se_amd_ct_bsgs_device): y = sum_{g, b} d[g][b] . rot_{giant[g] baby[b]}(x) as
+//   rot[b] = the hoisted MANY form above (the record itself for element 1),
+//   inner[g] = sum_b d'[g][b] . rot[b]                      k_ct_mul_plain_sum
+//   out = sum_g rho_{giant[g]}(inner[g])                    k_ct_galois_accum
+// with d' the diagonals pre-rotated by giant[g]^-1 when the plan is made (k_bsgs_permute).  n1 + n2 - 2 Galois keys serve
+// n1 n2 diagonals.
+//
+// k_ct_mul_plain_sum: out[g][b] = sum_{e < E} pt[g][e] . in[e][b], element-wise and bound by HBM like k_ct_mul_plain,
+// whose access shape it has: a 256-thread workgroup owns 1024 consecutive residues -- inside one prime, q_i and its Barrett
+// constants scalar -- of kSumTile consecutive records of ONE output g, and walks e.  Per e: one plaintext quad, reduced mod
+// q_i once (barrett64 takes any 64-bit word) and used by the kSumTile records, and kSumTile input quads, all requested
+// before the first product.  The input quads do not depend on g: the Gout workgroups that read the same input rows follow
+// one another on ONE XCD (the block order in the kernel), so all but the first find them in that die's L2; with g simply
+// running first in blockIdx.x they sat on eight dies and the weighted sum of 64 diagonals took 16.1 ms instead of 9.8
+// (4096 x 3, 16 384 records).
+// Lazy range.  The reduced plaintext word is below q_i < 2^30 and an input word is ANY 32-bit word, so one product is below
+// 2^62; the accumulator enters a period canonical (below 2^30) and takes kSumPeriod = 3 products:
+//   2^30 + 3 . 2^62 < 2^64; a fourth would not fit.  (64 products of (q - 1)^2 ~ 2^60 pass 2^64: the saturation case.)
+// Row offsets are 64-bit; E B and Gout B are below 2^32 (checked by the host).  grid (Gout . primes n / 1024 . slabs,
+// min(ceil(B / kSumTile), 65 535)).
+// ------------------------------------------------------------------------------------------
+constexpr int kSumTile   = 4;
+constexpr int kSumPeriod = 3;
+constexpr uint32_t kXcds = 8;   // accelerator dies of an MI355X; workgroups are dealt to them round-robin
+
+__global__ __launch_bounds__(kLcThreads) void k_ct_mul_plain_sum(const DevParams P, const MulPlainSumArgs A)
+{
+    const size_t row      = (size_t)A.primes << P.logn;
+    const size_t pt_row   = (size_t)A.pt_primes << P.logn;
+    const uint32_t chunks = (uint32_t)(row >> kLcTileLog);
+    // blockIdx.x -> (g, row tile).  Consecutive workgroups go to consecutive XCDs, each with an L2 of its own: where the
+    // row tiles divide by kXcds, workgroup 8 v + k (all on XCD k) takes g = v mod Gout of row tile 8 (v / Gout) + k, so the
+    // Gout readers of one input tile follow one another on ONE XCD.  Elsewhere g simply runs first.
+    const uint32_t tiles_x = chunks * (A.in1 ? 2u : 1u);
+    const bool by_xcd      = tiles_x % kXcds == 0;
+    const uint32_t v       = by_xcd ? blockIdx.x / kXcds : blockIdx.x;
+    const uint32_t g       = v % A.Gout;
+    const uint32_t rest    = by_xcd ? v / A.Gout * kXcds + blockIdx.x % kXcds : v / A.Gout;
+    const uint32_t slab   = rest / chunks;
+    const uint32_t chunk  = rest - slab * chunks;
+    const uint32_t j      = (chunk << kLcTileLog) >> P.logn;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const uint32_t *__restrict__ in = slab ? A.in1 : A.in0;
+    const uint32_t *__restrict__ pt = A.pt;
+    uint32_t *__restrict__ out      = slab ? A.out1 : A.out0;
+    const size_t off   = ((size_t)chunk << kLcTileLog) + 4 * threadIdx.x;   // the same offset inside a plaintext
+    const size_t tiles = ((size_t)A.B + kSumTile - 1) / kSumTile;
+
+    for (size_t tile = blockIdx.y; tile < tiles; tile += gridDim.y)
+    {
+        const size_t b0 = tile * kSumTile;
+        // a record past the end of the last tile reads the last record again and is not stored
+        size_t rec[kSumTile];
+#pragma unroll
+        for (int r = 0; r < kSumTile; r++) rec[r] = b0 + r < A.B ? b0 + r : (size_t)A.B - 1;
+        Lane4 acc[kSumTile];
+        int pending = 0;
+        for (uint32_t e = 0; e < A.E; e++)
+        {
+            uint4 m = load_row(pt, (size_t)g * A.E + e, pt_row, off);
+            uint4 v[kSumTile];
+#pragma unroll
+            for (int r = 0; r < kSumTile; r++) v[r] = load_row(in, (size_t)e * A.B + rec[r], row, off);
+            m.x = barrett64((uint64_t)m.x, q, cr_hi, cr_lo);
+            m.y = barrett64((uint64_t)m.y, q, cr_hi, cr_lo);
+            m.z = barrett64((uint64_t)m.z, q, cr_hi, cr_lo);
+            m.w = barrett64((uint64_t)m.w, q, cr_hi, cr_lo);
+#pragma unroll
+            for (int r = 0; r < kSumTile; r++) acc[r].mad4(v[r], m);
+            if (++pending == kSumPeriod)
+            {
+#pragma unroll
+                for (int r = 0; r < kSumTile; r++) acc[r].reduce(q, cr_hi, cr_lo);
+                pending = 0;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kSumTile; r++)
+        {
+            if (pending) acc[r].reduce(q, cr_hi, cr_lo);
+            if (b0 + r < A.B) *reinterpret_cast<uint4 *>(out + ((size_t)g * A.B + b0 + r) * row + off) = acc[r].get();
+        }
+    }
+}
+
+hipError_t launch_ct_mul_plain_sum(const DevParams &P, const MulPlainSumArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    const uint32_t chunks = (uint32_t)(((size_t)A.primes << P.logn) >> kLcTileLog);
+    const uint32_t slabs  = A.in1 ? 2 : 1;
+    const uint32_t tiles  = (A.B - 1) / kSumTile + 1;
+    const dim3 grid(A.Gout * chunks * slabs, tiles < 65535u ? tiles : 65535u);
+    return launch(k_ct_mul_plain_sum, grid, dim3(kLcThreads), 0, st, P, A);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_ct_galois_accum: out[b] = sum_g rho_g(in[g][b]), rho_g = k_ct_galois's map with elt[g] and its installed key -- the
+// giant steps of a baby-step / giant-step product, G rotations of G DIFFERENT records into one.  It is k_ct_galois with the
+// element loop inside the record loop: the same grid, thread shape, transforms (3 L per keyed element), key layout and lazy
+// ranges, LDS the exchange plane alone.  ONE accumulator pair lives across the G elements: evk_mac leaves it in
+// [0, 2 q_i) after every product, whichever key block the product came from, so the digits of element g + 1 accumulate on
+// top of those of element g and the one canonicalisation is the epilogue's.  sigma(c0) of element g joins the same pair: the
+// row of output prime i is parked in the plane (free behind evk_digits' last barrier), gathered through src_g as in
+// k_ct_galois, and added to acc0 -- a canonical word d < q_i on an accumulator in [0, 2 q_i) is below 3 q_i < 2^32, and
+// min(s, s - 2 q_i) brings it back.  The sum is modular and every step exact, so the result has the bits of the modular sum
+// of G k_ct_galois outputs in any order.  Element 1 is the identity: no key switch, both rows are added as they lie.
+// Addresses: as in k_ct_galois (formed from the checked elements only, masked to [0, n)).
+// grid evk_grid(B, L).
+// ------------------------------------------------------------------------------------------
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum(const DevParams P, const DevTables T,
+                                                                           const GaloisAccumArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t qi  = P.q[i], two_qi = qi << 1;
+    const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * i;
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+#pragma unroll 1
+        for (uint32_t s = 0; s < A.G; s++)
+        {
+            const uint32_t g = A.elt[s];
+            const size_t rec = ((size_t)s * A.B + b) * A.primes * N;
+            if (g != 1)
+            {
+                const uint32_t *k0 = A.key[s] + (size_t)i * 2 * N;
+                for (uint32_t j = 0; j < A.primes; j++)
+                {
+                    const int tj      = opaque_index(t);
+                    const uint32_t qj = P.q[j];
+                    uint32_t x[16];
+                    evk_row_coeffs<LOGN>(x, A.in1 + rec + (size_t)j * N, j, P, T, lds, tj);
+                    // sigma, the scatter of k_ct_galois (its own copy: see there)
+#pragma unroll
+                    for (int e = 0; e < 16; e++)
+                    {
+                        const uint32_t u = (uint32_t)(tj + (N / 16) * e) * g;
+                        lds[u & (N - 1)] = (u & N) && x[e] ? qj - x[e] : x[e];
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int e = 0; e < 16; e++) x[e] = lds[tj + (N / 16) * e];
+                    __syncthreads();
+                    evk_digits<LOGN>(x, acc0, acc1, A, k0, j, rw, qi, lds, t);
+                }
+            }
+            const int te   = opaque_index(t);
+            const size_t o = rec + (size_t)i * N;
+            uint32_t c[16];
+            load_quads(c, A.in0 + o, te);
+            if (g != 1)
+            {
+                const int k4 = quad_index(te, 0);
+                park_row_quads(c, lds, k4);   // sigma(c0) row i
+                __syncthreads();
+                gather_row<LOGN>(c, lds, k4, g);
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+            {
+                const uint32_t u = acc0[e] + c[e];
+                acc0[e]          = min(u, u - two_qi);
+            }
+            if (g != 1)
+                __syncthreads();   // the next transpose writes the plane the gather reads
+            else
+            {
+                load_quads(c, A.in1 + o, te);
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                {
+                    const uint32_t u = acc1[e] + c[e];
+                    acc1[e]          = min(u, u - two_qi);
+                }
+            }
+        }
+        const int te   = opaque_index(t);
+        const size_t o = b * A.primes * N + (size_t)i * N;
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            acc0[e] = csub(acc0[e], qi);
+            acc1[e] = csub(acc1[e], qi);
+        }
+        store_quads(A.out0 + o, acc0, te);
+        store_quads(A.out1 + o, acc1, te);
+    }
+}
+
+hipError_t launch_ct_galois_accum(const DevParams &P, const DevTables &T, const GaloisAccumArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        using G         = XformGeom<L>;
+        return launch(k_ct_galois_accum<L>, evk_grid(A.B, A.primes), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// Plan set-up of se_amd_bsgs_create: out[r][k] = in[r][src_elt(k)], one thread per word.
+template <int LOGN>
+__global__ __launch_bounds__(kLcThreads) void k_bsgs_permute(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                          uint32_t elt, size_t words)
+{
+    const size_t w = (size_t)blockIdx.x * kLcThreads + threadIdx.x;
+    if (w >= words) return;
+    const uint32_t k = (uint32_t)(w & ((1u << LOGN) - 1));
+    out[w]           = in[w - k + galois_src<LOGN>(k, elt)];
+}
+
+hipError_t launch_bsgs_permute(const DevParams &P, const uint32_t *in, uint32_t *out, size_t rows, uint32_t elt,
+                               hipStream_t st)
+{
+    const size_t words = rows << P.logn;
+    if (words == 0) return hipSuccess;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        return launch(k_bsgs_permute<L>, dim3((unsigned)(words / kLcThreads)), dim3(kLcThreads), 0, st, in, out, elt,
+                      words);
     });
 }
 

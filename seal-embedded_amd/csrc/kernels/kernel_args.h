@@ -315,6 +315,41 @@ hipError_t launch_ct_hoist_sp(const DevParams &, const DevTables &, const Rescal
 // only.
 hipError_t launch_lintrans_fold(const DevParams &, const uint32_t *key_in, uint32_t *key_out, size_t rows,
                                 const uint32_t *diag_in, uint32_t *pair_out, uint32_t pt, hipStream_t);
+// Baby-step / giant-step linear transforms (se_amd_ct_bsgs_device): the two device steps behind the many form, and the
+// plan's set-up.
+// Weighted sum over a stack (k_ct_mul_plain_sum), key-free:
+//   out[g][b][i][k] = sum_{e < E} (pt[g][e][i][k] mod q_i) . in[e][b][i][k]   mod q_i, canonical,
+// in [E][B][primes][n], pt [Gout][E][pt_primes][n] (any 32-bit word stands for its residue), out [Gout][B][primes][n].
+struct MulPlainSumArgs
+{
+    const uint32_t *in0, *in1;      // [E][B][primes][n]; in1 NULL: one slab
+    const uint32_t *pt;             // [Gout][E][pt_primes][n]
+    uint32_t *out0, *out1;          // [Gout][B][primes][n]
+    uint32_t B;
+    uint32_t E, Gout;               // 1 .. kMaxGaloisKeys each; E B and Gout B below 2^32
+    uint32_t primes, pt_primes;     // pt_primes >= primes
+};
+hipError_t launch_ct_mul_plain_sum(const DevParams &, const MulPlainSumArgs &, hipStream_t);
+// Rotate different ciphertexts and add (k_ct_galois_accum): out[b] = sum_{g < G} rho_g(in[g][b]) mod q_i, canonical, rho_g
+// the map of GaloisArgs with elt[g] and key[g]; elt[g] == 1 is the identity (key[g] unused).  The elements and the key
+// block of each travel in the argument block, as in GaloisHoistArgs.
+struct GaloisAccumArgs
+{
+    const uint32_t *in0, *in1;      // [G][B][primes][n]
+    uint32_t *out0, *out1;          // [B][primes][n]
+    size_t half;                    // words of one key half: R np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes)
+    uint32_t primes;                // 1 .. np
+    uint32_t G;                     // 1 .. kMaxGaloisKeys; G B below 2^32
+    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kMaxGaloisKeys];   // the device key block of elt[g]; NULL where elt[g] == 1
+};
+hipError_t launch_ct_galois_accum(const DevParams &, const DevTables &, const GaloisAccumArgs &, hipStream_t);
+// Plan set-up: out[r][k] = in[r][src_elt(k)] on `rows` rows of n words, src the permutation of the automorphism of `elt`
+// (odd, below 2n, checked by the host) on a bit-reversed NTT-form row.
+hipError_t launch_bsgs_permute(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, uint32_t elt,
+                               hipStream_t);
 // Evaluation-key plumbing.  relin_key_rows: `rows` rows [np][n] of key words -> [rows][np][2][n] (words, Shoup
 // companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
 // slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =

@@ -569,6 +569,61 @@ int se_amd_ct_lintrans_sp_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, c
     return ctx->c.ct_lintrans(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, as_stream(stream), true);
 }
 
+int se_amd_ct_mul_plain_sum_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B,
+                                   size_t primes, const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0,
+                                   uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mul_plain_sum(d_in0, d_in1, E, B, primes, d_pt, Gout, pt_primes, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_galois_accum_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes,
+                                  const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois_accum(d_in0, d_in1, B, primes, elts, G, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_bsgs_create(se_amd_ctx *ctx, const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2,
+                       const uint32_t *d_diag, size_t pt_primes, se_amd_bsgs **out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !out) return SE_ERR_INVALD_ARGUMENT;
+    se_amd_bsgs *h = new (std::nothrow) se_amd_bsgs();
+    if (!h) return SE_ERR_NO_MEMORY;
+    const int rc = ctx->c.bsgs_create(baby, n1, giant, n2, d_diag, pt_primes, h->p);
+    if (rc != 0)
+    {
+        delete h;   // the buffer of a plan half built went with the local it was built in
+        return rc;
+    }
+    *out = h;
+    return SE_SUCCESS;
+}
+
+void se_amd_bsgs_destroy(se_amd_bsgs *plan)
+{
+    if (!plan) return;
+    // the kernels of calls still enqueued read the plan's diagonals: drain the device before they are freed
+    if (hipSetDevice(plan->p.device) == hipSuccess) (void)hipDeviceSynchronize();
+    delete plan;
+}
+
+size_t se_amd_bsgs_workspace_bytes(const se_amd_bsgs *plan, size_t records, size_t primes)
+{
+    if (!plan) return 0;
+    return records * 2 * (plan->p.baby.size() + plan->p.giant.size()) * primes * plan->p.n * sizeof(uint32_t);
+}
+
+int se_amd_ct_bsgs_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                          size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes,
+                          void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_bsgs(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, d_workspace, workspace_bytes,
+                          as_stream(stream));
+}
+
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)
 {
     seamd::HostParams hp;

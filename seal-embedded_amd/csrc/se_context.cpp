@@ -12,6 +12,7 @@
 #include "se_context.h"
 #include "se_hostpipe.h"
 
+#include <algorithm>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1819,6 +1820,205 @@ int Context::ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const u
         la.key[e] = plan->keys[e];
     }
     SEAMD_HIP(launch_ct_lintrans(dp, dt, la, st));
+    return 0;
+}
+
+// Key-free, one launch, nothing of the context is written.  The checks of ct_mul_plain, then the stack's.
+int Context::ct_mul_plain_sum(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
+                              const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0, uint32_t *d_out1,
+                              hipStream_t st)
+{
+    constexpr size_t k32 = (size_t)1 << 32;
+    if (!d_in0 || !d_out0 || !d_pt || !d_in1 != !d_out1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes || pt_primes < primes || pt_primes >= k32) return kErrInvalid;
+    if (B >= k32 || !aligned16({d_in0, d_in1, d_out0, d_out1, d_pt})) return kErrInvalid;
+    if (E < 1 || E > kMaxGaloisKeys || Gout < 1 || Gout > kMaxGaloisKeys || E * B >= k32 || Gout * B >= k32)
+    {
+        set_last_error("weighted sum over a stack: E and Gout between 1 and 64, E B and Gout B below 2^32");
+        return kErrInvalid;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    MulPlainSumArgs ma{};
+    ma.in0       = d_in0;
+    ma.in1       = d_in1;
+    ma.pt        = d_pt;
+    ma.out0      = d_out0;
+    ma.out1      = d_out1;
+    ma.B         = (uint32_t)B;
+    ma.E         = (uint32_t)E;
+    ma.Gout      = (uint32_t)Gout;
+    ma.primes    = (uint32_t)primes;
+    ma.pt_primes = (uint32_t)pt_primes;
+    SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
+    return 0;
+}
+
+// One launch, no scratch, no secret key, no host synchronisation; reads the installed Galois keys of the elements other
+// than 1.  The checks of ct_galois_hoist in its order, then G B; nothing is launched unless every such element has a key.
+int Context::ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
+                             size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    GaloisAccumArgs aa{};
+    if (!evk_call_args(aa, {d_in0, d_in1, d_out0, d_out1}, B, primes)) return kErrInvalid;
+    if (!galois_elts_ok(elts, G, "rotate and accumulate: between 1 and 64 elements")) return kErrInvalid;
+    if (G * B >= ((size_t)1 << 32))
+    {
+        set_last_error("rotate and accumulate: G B must stay below 2^32");
+        return kErrInvalid;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t g = 0; g < G; g++)
+    {
+        aa.elt[g] = elts[g];
+        aa.key[g] = elts[g] == 1 ? nullptr : galois_key(false, elts[g]);
+        if (elts[g] != 1 && !aa.key[g]) return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    aa.in0  = d_in0;
+    aa.in1  = d_in1;
+    aa.out0 = d_out0;
+    aa.out1 = d_out1;
+    aa.G    = (uint32_t)G;
+    SEAMD_HIP(launch_ct_galois_accum(dp, dt, aa, st));
+    return 0;
+}
+
+// The plan of a baby-step / giant-step transform: argument checks, then one permutation launch per giant step -- row
+// (g, b) of the caller's diagonals by giant[g]^-1, written to the slot of baby[b] with element 1 moved to the front --
+// and a synchronisation, so the caller's diagonals may go once this returns.  No key is read.  Anything refused leaves
+// `plan` empty.
+int Context::bsgs_create(const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2, const uint32_t *d_diag,
+                         size_t pt_primes, BsgsPlan &plan)
+{
+    const char *args_msg = "baby-step / giant-step plan: between 1 and 64 distinct elements in each list, pt_primes >= 1, "
+                           "16-byte aligned diagonals";
+    if (!d_diag || pt_primes == 0 || pt_primes >= ((size_t)1 << 32) || !aligned16({d_diag}))
+    {
+        set_last_error(args_msg);
+        return kErrInvalid;
+    }
+    if (!galois_elts_ok(baby, n1, args_msg, true) || !galois_elts_ok(giant, n2, args_msg, true)) return kErrInvalid;
+    const size_t n = hp.n, np = hp.nprimes, rows = n1 * pt_primes;
+    BsgsPlan built;
+    // the slot of every baby step: element 1 first, the others in their order behind it
+    std::vector<size_t> slot(n1);
+    const size_t one = std::find(baby, baby + n1, 1u) - baby;
+    for (size_t b = 0, next = one < n1 ? 1 : 0; b < n1; b++) slot[b] = b == one ? 0 : next++;
+    built.baby.resize(n1);
+    for (size_t b = 0; b < n1; b++) built.baby[slot[b]] = baby[b];
+    built.giant.assign(giant, giant + n2);
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    SEAMD_HIP(built.diag.grow(n2 * rows * n));
+    for (size_t g = 0; g < n2; g++)
+    {
+        // giant[g]^-1 mod 2n by Newton's iteration: x = a is the inverse mod 8 of an odd a, every step doubles the bits
+        uint32_t inv = giant[g];
+        for (int it = 0; it < 4; it++) inv *= 2 - giant[g] * inv;
+        inv &= (uint32_t)(2 * n - 1);
+        for (size_t b = 0; b < n1; b++)
+            SEAMD_HIP(launch_bsgs_permute(dp, d_diag + (g * n1 + b) * pt_primes * n,
+                                          built.diag + (g * n1 + slot[b]) * pt_primes * n, pt_primes, inv, nullptr));
+    }
+    SEAMD_HIP(hipDeviceSynchronize());
+    built.owner     = this;
+    built.device    = device;
+    built.n         = n;
+    built.levels    = pt_primes < np ? pt_primes : np;
+    built.pt_primes = pt_primes;
+    plan            = std::move(built);
+    return 0;
+}
+
+// The checks of ct_galois first, then the plan's and the workspace's, then under `mu` the keys of every element other
+// than 1 (read from the context NOW: a plan holds none).  The batch is walked in chunks of Bc = min(B, workspace records);
+// a chunk of c records uses the workspace as rot0 | rot1 | inner0 | inner1, stacks [n1][c] resp. [n2][c] of level-`primes`
+// rows at offsets fixed by Bc.  Everything is enqueued on `st`: no context scratch, no allocation, no synchronisation.
+int Context::ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                     uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st)
+{
+    GaloisHoistArgs ha{};
+    GaloisAccumArgs aa{};
+    if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes) ||
+        !evk_call_args(aa, {d_c0, d_c1, d_out0, d_out1}, B, primes))
+        return kErrInvalid;
+    if (!plan || plan->owner != this || primes > plan->levels)
+    {
+        set_last_error(!plan ? "baby-step / giant-step transform: no plan"
+                       : plan->owner != this ? "baby-step / giant-step transform: the plan belongs to another context"
+                                             : "baby-step / giant-step transform: the plan's diagonals have fewer primes "
+                                               "than the call");
+        return kErrInvalid;
+    }
+    const size_t n1 = plan->baby.size(), n2 = plan->giant.size(), row = primes * hp.n;
+    const size_t per = 2 * (n1 + n2) * row * sizeof(uint32_t);
+    if (!d_workspace || !aligned16({d_workspace}) || workspace_bytes < per)
+    {
+        set_last_error("baby-step / giant-step transform: the workspace must be 16-byte aligned and hold at least one "
+                       "record (se_amd_bsgs_workspace_bytes)");
+        return kErrInvalid;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    const bool own   = plan->baby[0] == 1;   // the record itself is baby step 0
+    const size_t many = n1 - own;
+    for (size_t e = 0; e < many; e++)
+    {
+        ha.elt[e] = plan->baby[own + e];
+        ha.key[e] = galois_key(false, ha.elt[e]);
+        if (!ha.key[e]) return kErrNoKey;
+    }
+    for (size_t g = 0; g < n2; g++)
+    {
+        aa.elt[g] = plan->giant[g];
+        aa.key[g] = aa.elt[g] == 1 ? nullptr : galois_key(false, aa.elt[g]);
+        if (aa.elt[g] != 1 && !aa.key[g]) return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    const size_t Bc = std::min(B, workspace_bytes / per);
+    uint32_t *rot0 = static_cast<uint32_t *>(d_workspace), *rot1 = rot0 + n1 * Bc * row;
+    uint32_t *inner0 = rot1 + n1 * Bc * row, *inner1 = inner0 + n2 * Bc * row;
+    ha.G = (uint32_t)many;
+    aa.G = (uint32_t)n2;
+    MulPlainSumArgs ma{};
+    ma.in0       = rot0;
+    ma.in1       = rot1;
+    ma.pt        = plan->diag;
+    ma.out0      = inner0;
+    ma.out1      = inner1;
+    ma.E         = (uint32_t)n1;
+    ma.Gout      = (uint32_t)n2;
+    ma.primes    = (uint32_t)primes;
+    ma.pt_primes = (uint32_t)plan->pt_primes;
+    aa.in0       = inner0;
+    aa.in1       = inner1;
+    for (size_t b0 = 0; b0 < B; b0 += Bc)
+    {
+        const size_t c = std::min(Bc, B - b0), bytes = c * row * sizeof(uint32_t);
+        const uint32_t *c0 = d_c0 + b0 * row, *c1 = d_c1 + b0 * row;
+        if (own)
+        {
+            SEAMD_HIP(hipMemcpyAsync(rot0, c0, bytes, hipMemcpyDeviceToDevice, st));
+            SEAMD_HIP(hipMemcpyAsync(rot1, c1, bytes, hipMemcpyDeviceToDevice, st));
+        }
+        if (many)
+        {
+            ha.c0   = c0;
+            ha.c1   = c1;
+            ha.out0 = rot0 + own * c * row;
+            ha.out1 = rot1 + own * c * row;
+            ha.B    = c;
+            SEAMD_HIP(launch_ct_galois_hoist(dp, dt, ha, st));
+        }
+        ma.B = (uint32_t)c;
+        SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
+        aa.B    = c;
+        aa.out0 = d_out0 + b0 * row;
+        aa.out1 = d_out1 + b0 * row;
+        SEAMD_HIP(launch_ct_galois_accum(dp, dt, aa, st));
+    }
     return 0;
 }
 

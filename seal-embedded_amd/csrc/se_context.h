@@ -43,6 +43,21 @@ struct LintransPlan
     DevBuf<uint32_t> diag;                // [G + 1][np][2][n]; the last one is d0 (unused without diag0)
 };
 
+// A baby-step / giant-step linear transform made ready (se_amd_bsgs_create): the diagonals alone, pre-rotated by the
+// inverse of their giant step, in the layout k_ct_mul_plain_sum reads.  It holds no key material: the Galois keys are
+// looked up in the context at call time.  Element 1, where listed, stands FIRST in `baby` (the modular sum does not
+// depend on the order), so the keyed baby steps are one contiguous stack for the many form.
+struct BsgsPlan
+{
+    const Context *owner = nullptr;   // compared, never dereferenced
+    int device           = 0;
+    size_t n             = 0;
+    size_t levels        = 0;       // min(pt_primes, np): the calls it serves have primes <= levels
+    size_t pt_primes     = 0;
+    std::vector<uint32_t> baby, giant;   // baby: element 1 first where listed
+    DevBuf<uint32_t> diag;               // [n2][n1][pt_primes][n], row (g, b) permuted by giant[g]^-1
+};
+
 // One installed family of evaluation keys (public material): digit keys (R = 2 np rows; se_amd_set_relin_key,
 // se_amd_set_galois_keys) or special-prime keys (R = np - 1; the _sp setters).  Every key is one device block
 // [2][R][np][2][n] made by build_evk (layout: kernels/kernel_args.h).
@@ -252,6 +267,19 @@ struct Context
                         size_t pt_primes, LintransPlan &plan, bool sp = false);
     int ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                     uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp = false);
+    // baby-step / giant-step linear transforms: the weighted sum over a stack (MulPlainSumArgs, key-free), the rotate-and-
+    // accumulate of G different records (GaloisAccumArgs, elts a host pointer, element 1 needs no key), one launch each;
+    // the plan (device diagonals [n2][n1][pt_primes][n], host element lists; synchronises) and its call, which walks the
+    // batch in chunks of what the caller's workspace holds: copies, the many form, the two entries above, all on `st`
+    int ct_mul_plain_sum(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
+                         const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0, uint32_t *d_out1,
+                         hipStream_t st);
+    int ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
+                        size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    int bsgs_create(const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2, const uint32_t *d_diag,
+                    size_t pt_primes, BsgsPlan &plan);
+    int ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st);
     // the sum form on the special-prime Galois keys (HoistSpArgs): one decomposition and one division by P whatever G is
     int ct_galois_sum_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
                          size_t G, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
@@ -341,6 +369,10 @@ struct se_amd_ctx
 struct se_amd_lintrans
 {
     seamd::LintransPlan p;
+};
+struct se_amd_bsgs
+{
+    seamd::BsgsPlan p;
 };
 
 #define SEAMD_HIP(call)                                             \

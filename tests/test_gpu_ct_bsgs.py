@@ -1,0 +1,612 @@
+"""Baby-step / giant-step linear transforms (-m gpu): se_amd_ct_mul_plain_sum_device, se_amd_ct_galois_accum_device and the
+plan se_amd_bsgs_create / se_amd_ct_bsgs_device on the digit Galois keys.
+Every expectation is written from the definitions of include/seal_embedded_amd.h (tests/bsgs_support.py) with the
+oracle's primitives, se_amd_galois_table and NumPy / Python integers, never from the device code under test; the
+device-against-device tests are second anchors beside them.  Every comparison is bit-exact except the reference's own
+acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).  Every output has two rows of
+sentinels behind it, and so has the workspace of a plan call."""
+import ctypes as C
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import vectors as V
+from bsgs_support import (CASE_IDS, GALOIS_CASES, accum_expect, bsgs_expect, edge_row, hoist_expect, inverse_element,
+                          permute_diagonals, random_keys, random_plaintexts, stack_sum_expect, stack_sum_python)
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, build_example,  # noqa: F401
+                         dev_t, encrypt_sym, env, expectation, host_u32, keyed_cases, rand_slab, rescale_expect,
+                         run_decrypt, sentinel_out, stream_of, take)
+
+pytestmark = pytest.mark.gpu
+
+
+# ---- one call each, outputs backed by sentinels ---------------------------------------------------------------------
+def run_sum(env, ctx, in0, in1, pt, primes):
+    E, B, n, Gout = in0.shape[0], in0.shape[1], ctx.n, pt.shape[0]
+    words = Gout * B * primes * n
+    out0 = sentinel_out(env, words, 2 * n)
+    out1 = sentinel_out(env, words, 2 * n) if in1 is not None else None
+    ctx.ct_mul_plain_sum(in0, pt, out0, in1, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    shape = (Gout, B, primes, n)
+    return take(out0, words, shape, "sum out0"), (take(out1, words, shape, "sum out1") if in1 is not None else None)
+
+
+def run_accum(env, ctx, in0, in1, elts, primes):
+    B, n = in0.shape[1], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois_accum(in0, in1, elts, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "accum out0"), take(out1, words, (B, primes, n), "accum out1")
+
+
+def run_galois(env, ctx, c0, c1, elt, primes):
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois(c0, c1, elt, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, (B, primes, n), "galois out0"), take(out1, words, (B, primes, n), "galois out1")
+
+
+def run_many(env, ctx, c0, c1, elts, primes):
+    B, n, G = c0.shape[0], ctx.n, len(elts)
+    words = G * B * primes * n
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_galois_many(c0, c1, elts, out0, out1, primes=primes)
+    env["torch"].cuda.synchronize()
+    shape = (G, B, primes, n)
+    return take(out0, words, shape, "many out0"), take(out1, words, shape, "many out1")
+
+
+def run_bsgs(env, ctx, plan, c0, c1, primes, records):
+    """One plan call with a workspace for `records` records; the words behind the workspace must stay untouched."""
+    B, n = c0.shape[0], ctx.n
+    words = B * primes * n
+    ws_bytes = ctx.bsgs_workspace_bytes(plan, records, primes)
+    assert ws_bytes % 4 == 0
+    ws = sentinel_out(env, ws_bytes // 4, 2 * n)
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_bsgs(plan, c0, c1, out0, out1, ws, primes=primes, workspace_bytes=ws_bytes)
+    env["torch"].cuda.synchronize()
+    assert (host_u32(ws)[ws_bytes // 4:] == SENTINEL).all(), "words behind the workspace are written"
+    return take(out0, words, (B, primes, n), "bsgs out0"), take(out1, words, (B, primes, n), "bsgs out1")
+
+
+# ---- test 1: the weighted sum over a stack ----------------------------------------------------------------------------
+# (shape, levels, E, Gout, B): the issue's two, and a stack of two record tiles (the last one short) whose E is not a
+# multiple of the reduction period
+SUM_CASES = [((1024, 1), (1,), 3, 2, 3), ((4096, 3), (3, 2), 3, 2, 3), ((1024, 1), (1,), 4, 1, 5)]
+
+
+@pytest.mark.parametrize("shape,levels,E,Gout,B", SUM_CASES, ids=CASE_IDS)
+def test_mul_plain_sum_matches_the_definition(env, shape, levels, E, Gout, B):
+    """Random residues in both stacks, record 1 of every batch all q_i - 1; plaintexts [Gout][E][np][n] with 0, 1, q - 1 at
+    fixed positions of every row and one row of arbitrary words >= q_i (q_i and 0xFFFFFFFF among them).  Two slabs and
+    one; at 4096 x 3 the level-2 call reads the same plaintexts (pt_primes = 3).  One row is also checked in Python
+    integers."""
+    from oracle.pyoracle import Oracle
+    n, npr = shape
+    o = Oracle(n, npr)
+    ctx = env["pkg"].Context(n, npr)
+    rng = np.random.default_rng(51 * n + 7 * E + B)
+    pt = random_plaintexts(rng, o.q, (Gout, E), n)
+    t_pt = dev_t(env, pt)
+    for L in levels:
+        s0, s1 = [rand_slab(rng, o.q, E * B, n, L).reshape(E, B, L, n) for _ in range(2)]
+        s0[:, 1] = s1[:, 1] = (np.array(o.q[:L], dtype=np.uint32) - 1)[:, None]
+        want0, want1 = stack_sum_expect(o, s0, pt), stack_sum_expect(o, s1, pt)
+        last = L - 1
+        assert want0[Gout - 1, 0, last].tolist() == stack_sum_python(int(o.q[last]), s0[:, 0, last], pt[Gout - 1, :, last])
+        d0, d1 = dev_t(env, s0), dev_t(env, s1)
+        got0, got1 = run_sum(env, ctx, d0, d1, t_pt, L)
+        assert (got0 == want0).all() and (got1 == want1).all(), (L, "two slabs")
+        one, none = run_sum(env, ctx, d1, None, t_pt, L)
+        assert none is None and (one == want1).all(), (L, "one slab")
+    ctx.close()
+
+
+@pytest.mark.parametrize("shape", [(1024, 1), (4096, 3)], ids=CASE_IDS)
+def test_mul_plain_sum_saturation(env, shape):
+    """E = 64, Gout = 1, B = 1, every input word and every plaintext word q_i - 1: the result is 64 (q_i - 1)^2 mod q_i =
+    64 in every word.  At 1024 x 1 (the 27-bit prime) the sixty-four products still fit 64 bits; at 4096 x 3 the primes
+    are close to 2^30, one product is close to 2^60 and the unreduced sum passes 2^64.  With plaintext words 0xFFFFFFFF
+    (reduced before they are used) the same stack gives 64 (q_i - 1) (2^32 - 1) mod q_i."""
+    from oracle.pyoracle import Oracle
+    n, npr = shape
+    E = 64
+    ctx = env["pkg"].Context(n, npr)
+    q = [int(v) for v in Oracle(n, npr).q]
+    assert all((E * (v - 1) ** 2) % v == 64 for v in q)
+    assert npr == 1 or any(E * (v - 1) ** 2 >= 2 ** 64 for v in q)
+    top = np.array(q, dtype=np.uint32)[:, None] - 1
+    stack = np.broadcast_to(top, (E, 1, npr, n)).copy()
+    pt = np.broadcast_to(top, (1, E, npr, n)).copy()
+    got0, got1 = run_sum(env, ctx, dev_t(env, stack), dev_t(env, stack), dev_t(env, pt), npr)
+    assert (got0 == 64).all() and (got1 == 64).all()
+    pt[:] = 0xFFFFFFFF
+    want = np.array([(E * (v - 1) * (0xFFFFFFFF % v)) % v for v in q], dtype=np.uint32)[None, None, :, None]
+    got0, _ = run_sum(env, ctx, dev_t(env, stack), None, dev_t(env, pt), npr)
+    assert (got0 == want).all()
+    ctx.close()
+
+
+# ---- tests 2 and 3 share contexts with random key words installed -----------------------------------------------------
+def key_elements(n):
+    return [3, 9, inverse_element(n, 3), n + 1, 2 * n - 1]
+
+
+@pytest.fixture(scope="module")
+def key_cases(env):
+    """key_cases(shape) -> a context with random key words installed for key_elements(n) (no secret key), its oracle and
+    the keys."""
+    from oracle.pyoracle import Oracle
+    cache = {}
+
+    def get(shape):
+        if shape not in cache:
+            n, npr = shape
+            o = Oracle(n, npr)
+            ctx = env["pkg"].Context(n, npr)
+            rng = np.random.default_rng(47 * n + npr)
+            keys = key_elements(n)
+            gk0, gk1 = random_keys(rng, o.q, len(keys), n, npr)
+            ctx.set_galois_keys(keys, gk0, gk1)
+            cache[shape] = dict(ctx=ctx, o=o, keys=keys, key_of={g: k for k, g in enumerate(keys)}, gk=(gk0, gk1), rng=rng)
+        return cache[shape]
+
+    yield get
+    for c in cache.values():
+        c["ctx"].close()
+
+
+def stack_inputs(case, elts, G, B, L):
+    """in0, in1 [G][B][L][n] of random residues; record 0 of every in1 batch is the edge row of the digit boundaries,
+    record 1 all q_j - 1."""
+    o, rng = case["o"], case["rng"]
+    n = o.n
+    in0 = rand_slab(rng, o.q, G * B, n, L).reshape(G, B, L, n)
+    in1 = rand_slab(rng, o.q, G * B, n, L).reshape(G, B, L, n)
+    for s in range(G):
+        for j in range(L):
+            in1[s, 0, j] = edge_row(o, j, rng, elts)
+    in0[:, 1] = in1[:, 1] = (np.array(o.q[:L], dtype=np.uint32) - 1)[:, None]
+    return in0, in1
+
+
+@pytest.mark.parametrize("shape,levels,B", GALOIS_CASES, ids=CASE_IDS)
+def test_galois_accum_matches_the_sum_of_rotations(env, key_cases, shape, levels, B):
+    """G = 3 different batches with element 1 in the middle, against the modular sum of the rotation expectations (the
+    definition of se_amd_ct_galois_device on arbitrary slabs and arbitrary key words); at 4096 x 3 also G = 4 with one
+    element listed twice.  G = 1 with a keyed element equals se_amd_ct_galois_device on the same input, device against
+    device."""
+    case = key_cases(shape)
+    o, ctx, n = case["o"], case["ctx"], shape[0]
+    lists = [[3, 1, n + 1]] + ([[9, 3, 2 * n - 1, 3]] if shape == (4096, 3) else [])
+    for L in levels:
+        for elts in lists:
+            in0, in1 = stack_inputs(case, elts, len(elts), B, L)
+            want = accum_expect(o, in0, in1, elts, case["key_of"], *case["gk"])
+            d0, d1 = dev_t(env, in0), dev_t(env, in1)
+            got = run_accum(env, ctx, d0, d1, elts, L)
+            assert (got[0] == want[0]).all() and (got[1] == want[1]).all(), (L, elts)
+        one = run_accum(env, ctx, d0[:1].contiguous(), d1[:1].contiguous(), elts[:1], L)
+        ref = run_galois(env, ctx, d0[0].contiguous(), d1[0].contiguous(), elts[0], L)
+        assert (one[0] == ref[0]).all() and (one[1] == ref[1]).all(), (L, "G = 1 against ct_galois")
+
+
+PLAN_CASES = [((4096, 3), (3, 2), 3), ((1024, 1), (1,), 3)]
+
+
+@pytest.fixture(scope="module")
+def plan_cases(env, key_cases):
+    """plan_cases(shape, levels, B) -> key_cases(shape) plus the 3 x 3 plan lists, random diagonals [3][3][np][n] and per
+    level the records with their expectation under the installed keys, computed once."""
+    cache = {}
+
+    def get(shape, levels, B):
+        if shape in cache:
+            return cache[shape]
+        case = key_cases(shape)
+        o, n = case["o"], shape[0]
+        baby, giant = [1, 3, 2 * n - 1], [1, 9, inverse_element(n, 3)]
+        diag = random_plaintexts(case["rng"], o.q, (3, 3), n)
+        per_level = {}
+        for L in levels:
+            c0, c1 = rand_slab(case["rng"], o.q, B, n, L), rand_slab(case["rng"], o.q, B, n, L)
+            for j in range(L):
+                c1[0, j] = edge_row(o, j, case["rng"], baby)
+            c0[1] = c1[1] = (np.array(o.q[:L], dtype=np.uint32) - 1)[:, None]
+            want = bsgs_expect(env["pkg"], o, c0, c1, baby, giant, diag, case["key_of"], *case["gk"])
+            per_level[L] = dict(c0=c0, c1=c1, d0=dev_t(env, c0), d1=dev_t(env, c1), want=want)
+        cache[shape] = dict(case, baby=baby, giant=giant, diag=diag, t_diag=dev_t(env, diag), levels=per_level)
+        return cache[shape]
+
+    return get
+
+
+@pytest.mark.parametrize("shape,levels,B", PLAN_CASES, ids=CASE_IDS)
+def test_plan_matches_the_three_step_definition(env, plan_cases, shape, levels, B):
+    """n1 = 3 (1, 3, 2n - 1), n2 = 3 (1, 9, 3^-1), random keys and diagonals (one row of words >= q_i), B = 3: against
+    many form -> weighted sum with the pre-rotated diagonals -> sum of giant rotations, bit for bit; the level-2 call runs
+    on the plan built with pt_primes = 3.  A workspace for 2 records (two chunks, the last one short), for 1 and for B
+    records give identical bits."""
+    pc = plan_cases(shape, levels, B)
+    ctx = pc["ctx"]
+    plan = ctx.bsgs_plan(pc["baby"], pc["giant"], pc["t_diag"])
+    for L in levels:
+        lv = pc["levels"][L]
+        whole = run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], L, B)
+        assert (whole[0] == lv["want"][0]).all() and (whole[1] == lv["want"][1]).all(), (L, "one chunk")
+        for records in (2, 1):
+            got = run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], L, records)
+            assert (got[0] == whole[0]).all() and (got[1] == whole[1]).all(), (L, records)
+    plan.close()
+    plan.close()                                           # closing twice is a no-op
+
+
+@pytest.mark.parametrize("shape,levels,B", PLAN_CASES, ids=CASE_IDS)
+def test_plan_without_the_identity(env, plan_cases, shape, levels, B):
+    """Element 1 in neither list: baby (3, 2n - 1), giant (9, 3^-1), the matching 2 x 2 block of the diagonals."""
+    pc = plan_cases(shape, levels, B)
+    ctx, o = pc["ctx"], pc["o"]
+    baby, giant = pc["baby"][1:], pc["giant"][1:]
+    diag = np.ascontiguousarray(pc["diag"][1:, 1:])
+    plan = ctx.bsgs_plan(baby, giant, dev_t(env, diag))
+    L = levels[0]
+    lv = pc["levels"][L]
+    want = bsgs_expect(env["pkg"], o, lv["c0"], lv["c1"], baby, giant, diag, pc["key_of"], *pc["gk"])
+    got = run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], L, 2)
+    assert (got[0] == want[0]).all() and (got[1] == want[1]).all()
+    plan.close()
+
+
+@pytest.mark.parametrize("shape,levels,B", PLAN_CASES, ids=CASE_IDS)
+def test_plan_is_the_composition_on_the_device(env, plan_cases, shape, levels, B):
+    """Device against device: ct_galois_many for the keyed baby steps (the record itself in the slot of element 1) ->
+    ct_mul_plain_sum on the host-permuted diagonals -> ct_galois_accum, called separately, equal the plan call."""
+    torch = env["torch"]
+    pc = plan_cases(shape, levels, B)
+    ctx, n = pc["ctx"], shape[0]
+    t_perm = dev_t(env, permute_diagonals(env["pkg"], n, pc["diag"], pc["giant"]))
+    plan = ctx.bsgs_plan(pc["baby"], pc["giant"], pc["t_diag"])
+    for L in levels:
+        lv = pc["levels"][L]
+        m0, m1 = run_many(env, ctx, lv["d0"], lv["d1"], pc["baby"][1:], L)
+        rot0 = torch.cat([lv["d0"][None], dev_t(env, m0)]).contiguous()
+        rot1 = torch.cat([lv["d1"][None], dev_t(env, m1)]).contiguous()
+        i0, i1 = run_sum(env, ctx, rot0, rot1, t_perm, L)
+        want = run_accum(env, ctx, dev_t(env, i0), dev_t(env, i1), pc["giant"], L)
+        got = run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], L, B)
+        assert (got[0] == want[0]).all() and (got[1] == want[1]).all(), L
+    plan.close()
+
+
+def test_plan_reads_the_keys_at_call_time(env, plan_cases):
+    """After a re-install of the Galois keys the SAME plan gives the bits of the new keys, which differ; with a giant
+    step's key gone it returns SE_ERR_NO_KEY and names the element.  The first keys are put back for the other tests."""
+    shape, levels, B = PLAN_CASES[1]
+    pc = plan_cases(shape, levels, B)
+    ctx, o, n, npr = pc["ctx"], pc["o"], shape[0], shape[1]
+    lv = pc["levels"][npr]
+    plan = ctx.bsgs_plan(pc["baby"], pc["giant"], pc["t_diag"])
+    nk0, nk1 = random_keys(np.random.default_rng(79), o.q, len(pc["keys"]), n, npr)
+    ctx.set_galois_keys(pc["keys"], nk0, nk1)
+    try:
+        want = bsgs_expect(env["pkg"], o, lv["c0"], lv["c1"], pc["baby"], pc["giant"], pc["diag"], pc["key_of"], nk0, nk1)
+        assert (want[0] != lv["want"][0]).any() and (want[1] != lv["want"][1]).any()
+        got = run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], npr, B)
+        assert (got[0] == want[0]).all() and (got[1] == want[1]).all(), "the new keys"
+        ctx.set_galois_keys(pc["keys"][:1] + pc["keys"][2:], np.delete(nk0, 1, 0), np.delete(nk1, 1, 0))   # 9 is gone
+        with pytest.raises(env["pkg"].SealEmbeddedAmdError, match="-1002") as err:
+            run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], npr, B)
+        assert "element 9" in str(err.value), str(err.value)
+    finally:
+        ctx.set_galois_keys(pc["keys"], *pc["gk"])
+    got = run_bsgs(env, ctx, plan, lv["d0"], lv["d1"], npr, B)
+    assert (got[0] == lv["want"][0]).all() and (got[1] == lv["want"][1]).all(), "the first keys again"
+    plan.close()
+
+
+# ---- test 4: arguments ------------------------------------------------------------------------------------------------
+def test_bsgs_arguments(env):
+    """Every documented error returns its code and leaves the sentinel-filled outputs untouched; B = 0 succeeds and writes
+    nothing; SE_ERR_NO_KEY names the missing element, for the accumulate entry and for the plan at call time; a repeat
+    in a plan list is refused with *out NULL; se_amd_bsgs_destroy(NULL) is safe and se_amd_bsgs_workspace_bytes is
+    records . 2 (n1 + n2) primes n 4."""
+    torch, pkg = env["torch"], env["pkg"]
+    n, npr, B = 4096, 3, 2
+    ctx, other = pkg.Context(n, npr), pkg.Context(n, npr)
+    L, h = ctx.L, ctx.h
+    key = np.zeros((2, 2 * npr, npr, n), dtype=np.uint32)
+    ctx.set_galois_keys([3, 9], key, key)
+    other.set_galois_keys([3, 9], key, key)
+    dev = env["dev"]
+    stack0 = torch.zeros((2, B, npr, n), dtype=torch.int32, device=dev)
+    stack1 = torch.zeros_like(stack0)
+    out0 = torch.full((2, B, npr, n), SENTINEL, dtype=torch.int32, device=dev)
+    out1 = torch.full_like(out0, SENTINEL)
+    pt = torch.ones((2, 2, npr, n), dtype=torch.int32, device=dev)
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    z = C.c_void_p(None)
+    s = stream_of(env)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the 65-element calls
+    good, even, big, nokey, twice, ident = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 5), el(3, 3), el(1, 3)
+    I0, I1, O0, O1, PT, E = p(stack0), p(stack1), p(out0), p(out1), p(pt), hp(good)
+
+    def untouched():
+        torch.cuda.synchronize()
+        assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+
+    # -- entry 1: (ctx, in0, in1, E, B, primes, pt, Gout, pt_primes, out0, out1)
+    def msum(*a):
+        return L.se_amd_ct_mul_plain_sum_device(*a, s)
+
+    bad = [
+        (None, I0, I1, 2, B, npr, PT, 2, npr, O0, O1),
+        (h, z, I1, 2, B, npr, PT, 2, npr, O0, O1),                 # NULL in0, out0, pt
+        (h, I0, I1, 2, B, npr, PT, 2, npr, z, O1),
+        (h, I0, I1, 2, B, npr, z, 2, npr, O0, O1),
+        (h, I0, z, 2, B, npr, PT, 2, npr, O0, O1),                 # one of in1 / out1 alone
+        (h, I0, I1, 2, B, npr, PT, 2, npr, O0, z),
+        (h, I0, I1, 2, B, 0, PT, 2, npr, O0, O1),                  # primes outside [1, np]
+        (h, I0, I1, 2, B, npr + 1, PT, 2, npr + 1, O0, O1),
+        (h, I0, I1, 2, B, npr, PT, 2, npr - 1, O0, O1),            # pt_primes < primes
+        (h, I0, I1, 2, 2 ** 32, npr, PT, 2, npr, O0, O1),          # B >= 2^32
+        (h, p(stack0, 4), I1, 2, B, npr, PT, 2, npr, O0, O1),      # alignment, each pointer
+        (h, I0, p(stack1, 8), 2, B, npr, PT, 2, npr, O0, O1),
+        (h, I0, I1, 2, B, npr, p(pt, 12), 2, npr, O0, O1),
+        (h, I0, I1, 2, B, npr, PT, 2, npr, p(out0, 4), O1),
+        (h, I0, I1, 2, B, npr, PT, 2, npr, O0, p(out1, 8)),
+        (h, I0, I1, 0, B, npr, PT, 2, npr, O0, O1),                # E, Gout outside [1, 64]
+        (h, I0, I1, 65, B, npr, PT, 2, npr, O0, O1),
+        (h, I0, I1, 2, B, npr, PT, 0, npr, O0, O1),
+        (h, I0, I1, 2, B, npr, PT, 65, npr, O0, O1),
+        (h, I0, I1, 2, 2 ** 31, npr, PT, 1, npr, O0, O1),          # E B, Gout B at or above 2^32
+        (h, I0, I1, 1, 2 ** 31, npr, PT, 2, npr, O0, O1),
+    ]
+    for k, a in enumerate(bad):
+        assert msum(*a) == SE_ERR_INVALD_ARGUMENT, ("sum", k)
+    assert msum(h, I0, I1, 2, 0, npr, PT, 2, npr, O0, O1) == 0
+    untouched()
+
+    # -- entry 2: (ctx, in0, in1, B, primes, elts, G, out0, out1)
+    def accum(*a):
+        return L.se_amd_ct_galois_accum_device(*a, s)
+
+    bad = [
+        (None, I0, I1, B, npr, E, 2, O0, O1),
+        (h, z, I1, B, npr, E, 2, O0, O1),                          # NULL slab pointers
+        (h, I0, z, B, npr, E, 2, O0, O1),
+        (h, I0, I1, B, npr, E, 2, z, O1),
+        (h, I0, I1, B, npr, E, 2, O0, z),
+        (h, I0, I1, B, 0, E, 2, O0, O1),                           # primes outside [1, np]
+        (h, I0, I1, B, npr + 1, E, 2, O0, O1),
+        (h, I0, I1, 2 ** 32, npr, E, 2, O0, O1),                   # B >= 2^32
+        (h, p(stack0, 4), I1, B, npr, E, 2, O0, O1),               # alignment, each slab
+        (h, I0, p(stack1, 8), B, npr, E, 2, O0, O1),
+        (h, I0, I1, B, npr, E, 2, p(out0, 12), O1),
+        (h, I0, I1, B, npr, E, 2, O0, p(out1, 4)),
+        (h, I0, I1, B, npr, z, 2, O0, O1),                         # elts NULL, G = 0, G = 65
+        (h, I0, I1, B, npr, E, 0, O0, O1),
+        (h, I0, I1, B, npr, E, 65, O0, O1),
+        (h, I0, I1, B, npr, hp(even), 2, O0, O1),                  # an even element, one >= 2n
+        (h, I0, I1, B, npr, hp(big), 2, O0, O1),
+        (h, I0, I1, 2 ** 31, npr, E, 2, O0, O1),                   # G B at or above 2^32
+    ]
+    for k, a in enumerate(bad):
+        assert accum(*a) == SE_ERR_INVALD_ARGUMENT, ("accum", k)
+    assert accum(h, I0, I1, B, npr, hp(nokey), 2, O0, O1) == SE_ERR_NO_KEY
+    assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
+    assert accum(h, I0, I1, 0, npr, E, 2, O0, O1) == 0
+    untouched()
+    # element 1 needs no key; a repeat is allowed: zero keys and zero slabs give zero rows
+    for elts in (ident, twice):
+        assert accum(h, I0, I1, B, npr, hp(elts), 2, O0, O1) == 0
+        torch.cuda.synchronize()
+        for o in (out0, out1):
+            flat = o.reshape(-1)
+            assert int(torch.count_nonzero(flat[:B * npr * n])) == 0 and bool((flat[B * npr * n:] == SENTINEL).all())
+        out0.fill_(SENTINEL)
+        out1.fill_(SENTINEL)
+
+    # -- create: (ctx, baby, n1, giant, n2, d_diag, pt_primes, out)
+    def create(ctx_h, baby, n1, giant, n2, d, ptp, want_out=True):
+        handle = C.c_void_p(0xDEAD)                         # a failed create must overwrite it with NULL
+        rc = L.se_amd_bsgs_create(ctx_h, baby, n1, giant, n2, d, ptp, C.byref(handle) if want_out else None)
+        return rc, handle
+
+    G1 = hp(ident)
+    bad = [
+        (None, E, 2, G1, 2, PT, npr),
+        (h, z, 2, G1, 2, PT, npr),                                 # NULL lists, NULL diagonals
+        (h, E, 2, z, 2, PT, npr),
+        (h, E, 2, G1, 2, z, npr),
+        (h, E, 0, G1, 2, PT, npr),                                 # n1, n2 outside [1, 64]
+        (h, E, 65, G1, 2, PT, npr),
+        (h, E, 2, G1, 0, PT, npr),
+        (h, E, 2, G1, 65, PT, npr),
+        (h, E, 2, G1, 2, PT, 0),                                   # pt_primes = 0
+        (h, hp(even), 2, G1, 2, PT, npr),                          # an even element, one >= 2n, in either list
+        (h, E, 2, hp(big), 2, PT, npr),
+        (h, E, 2, G1, 2, p(pt, 4), npr),                           # alignment
+        (h, hp(twice), 2, G1, 2, PT, npr),                         # a repeat within a list
+        (h, E, 2, hp(twice), 2, PT, npr),
+    ]
+    for k, a in enumerate(bad):
+        rc, handle = create(*a)
+        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, ("create", k, rc, handle.value)
+    assert create(h, E, 2, G1, 2, PT, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT     # NULL out
+    rc, plan = create(h, E, 2, G1, 2, PT, 2)                # baby (3, 9), giant (1, 3), two levels
+    assert rc == 0 and plan.value
+    rc, foreign = create(other.h, E, 2, G1, 2, PT, npr)
+    assert rc == 0 and foreign.value
+    rc, unkeyed = create(h, hp(nokey), 2, G1, 2, PT, npr)   # create reads no key: element 5 is found at call time
+    assert rc == 0 and unkeyed.value
+    L.se_amd_bsgs_workspace_bytes.restype = C.c_size_t
+    per = 2 * (2 + 2) * 2 * n * 4
+    assert L.se_amd_bsgs_workspace_bytes(plan, 5, 2) == 5 * per and L.se_amd_bsgs_workspace_bytes(None, 5, 2) == 0
+
+    # -- the call: (ctx, plan, c0, c1, B, primes, out0, out1, workspace, bytes)
+    ws = torch.full((B * per // 4 + 4,), SENTINEL, dtype=torch.int32, device=dev)
+    W, WB = p(ws), B * per
+
+    def call(*a):
+        return L.se_amd_ct_bsgs_device(*a, s)
+
+    bad = [
+        (None, plan, I0, I1, B, 2, O0, O1, W, WB),
+        (h, plan, z, I1, B, 2, O0, O1, W, WB),                     # NULL slab pointers
+        (h, plan, I0, z, B, 2, O0, O1, W, WB),
+        (h, plan, I0, I1, B, 2, z, O1, W, WB),
+        (h, plan, I0, I1, B, 2, O0, z, W, WB),
+        (h, plan, I0, I1, B, 0, O0, O1, W, WB),                    # primes outside [1, np]
+        (h, plan, I0, I1, B, 4, O0, O1, W, WB),
+        (h, plan, I0, I1, 2 ** 32, 2, O0, O1, W, WB),              # B >= 2^32
+        (h, plan, p(stack0, 4), I1, B, 2, O0, O1, W, WB),          # alignment, each slab
+        (h, plan, I0, p(stack1, 8), B, 2, O0, O1, W, WB),
+        (h, plan, I0, I1, B, 2, p(out0, 12), O1, W, WB),
+        (h, plan, I0, I1, B, 2, O0, p(out1, 4), W, WB),
+        (h, z, I0, I1, B, 2, O0, O1, W, WB),                       # no plan, a plan of another context
+        (h, foreign, I0, I1, B, 2, O0, O1, W, WB),
+        (other.h, plan, I0, I1, B, 2, O0, O1, W, WB),
+        (h, plan, I0, I1, B, 3, O0, O1, W, WB),                    # a level above the plan's
+        (h, plan, I0, I1, B, 2, O0, O1, z, WB),                    # the workspace: NULL, misaligned, below one record
+        (h, plan, I0, I1, B, 2, O0, O1, p(ws, 8), WB - 8),
+        (h, plan, I0, I1, B, 2, O0, O1, W, per - 16),
+    ]
+    for k, a in enumerate(bad):
+        assert call(*a) == SE_ERR_INVALD_ARGUMENT, ("call", k)
+    assert call(h, unkeyed, I0, I1, B, 2, O0, O1, W, WB) == SE_ERR_NO_KEY
+    assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
+    assert call(h, plan, I0, I1, 0, 2, O0, O1, W, WB) == 0
+    untouched()
+    assert bool((ws == SENTINEL).all()), "an error or a no-op wrote the workspace"
+    # the plan works: zero keys and zero slabs give zero rows at level 2, one record per chunk
+    assert call(h, plan, I0, I1, B, 2, O0, O1, W, per) == 0
+    torch.cuda.synchronize()
+    for o in (out0, out1):
+        flat = o.reshape(-1)
+        assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+    assert bool((ws[per // 4:] == SENTINEL).all()), "words behind one record of workspace are written"
+    L.se_amd_bsgs_destroy(None)
+    for pl in (plan, foreign, unkeyed):
+        L.se_amd_bsgs_destroy(pl)
+    ctx.close()
+    other.close()
+
+
+# ---- test 5: end to end with a real key -------------------------------------------------------------------------------
+DIM = 16
+N1 = N2 = 4
+LIFT = 1 << 18            # the bookkeeping of examples/matvec_roundtrip.c (tools/ct_galois_noise_sim.py --lintrans)
+DIAG_SHIFT = 256.0        # the diagonals are encoded from M / 2^8: their scale is Delta / 2^8
+
+
+def matrix():
+    """The example's fixed matrix: M[r][c] = ((7 r + 3 c + 1) mod 17 - 8) / 16, entries in [-1/2, 1/2]: sixteen of them
+    against x in [-1, 1] keep |M x| <= 8, the bound of the 8 x 8 example."""
+    r, c = np.meshgrid(np.arange(DIM), np.arange(DIM), indexing="ij")
+    return ((7 * r + 3 * c + 1) % 17 - 8) / 16.0
+
+
+def fill_keyed_case(env, case):
+    """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the Galois keys of the steps
+    1 .. 15, installed (the flat plan needs all fifteen, the baby-step / giant-step plan six of them); B = 4 fresh
+    symmetric records holding 16-periodic slot values in [-1, 1]."""
+    ctx, sk, pkg = case["ctx"], case["sk"], env["pkg"]
+    n, npr, B = ctx.n, ctx.np, 4
+    elts = [pkg.galois_element(n, s) for s in range(1, DIM)]
+    assert elts == [pow(3, s, 2 * n) for s in range(1, DIM)]
+    a_seeds = V.derive_seeds("gk-bsgs-a", len(elts) * 2 * npr)
+    e_seeds = V.derive_seeds("gk-bsgs-e", len(elts) * 2 * npr)
+    gk0, gk1 = ctx.gen_galois_keys(sk, elts, a_seeds, e_seeds)
+    ctx.set_galois_keys(elts, gk0, gk1)
+    x16 = np.random.default_rng(6000 + n).uniform(-1.0, 1.0, (B, DIM))
+    vals = np.tile(x16, (1, n // 2 // DIM)).astype(np.float32)
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=400)
+    assert bool((st == 1).all())
+    case.update(elts=elts, key_of={g: k for k, g in enumerate(elts)}, gk0=gk0, gk1=gk1, vals=vals, fresh=(c0, c1))
+
+
+def test_matvec_bsgs_end_to_end(env, keyed_cases):
+    """4096 x 3, B = 4: ct_lincomb with weight 2^18 -> ONE se_amd_ct_bsgs_device call (baby steps 0 .. 3, giant steps 0, 4,
+    8, 12: six keys; the sixteen diagonals of M / 2^8 encoded on the device) -> ct_rescale -> decrypt_level(primes = 2,
+    scale = Delta 2^18 (Delta / 2^8) / q_last).  The plan call equals its definition bit for bit, every coefficient
+    before the rescale is below 2^62, and every slot is within the reference's 0.1 of M x.  The flat 15-key lintrans plan
+    runs on the same records; both largest errors are printed."""
+    torch = env["torch"]
+    shape = (4096, 3)
+    c = keyed_cases(shape)
+    ctx, o, pkg = c["ctx"], c["o"], env["pkg"]
+    n, npr = shape
+    B = c["vals"].shape[0]
+    M = matrix()
+    up0, up1 = sentinel_out(env, B * npr * n, 2 * n), sentinel_out(env, B * npr * n, 2 * n)
+    ctx.ct_lincomb(c["fresh"][0], up0, c["fresh"][1], up1, row_ptr=dev_t(env, np.arange(B + 1, dtype=np.uint32)),
+                   idx=dev_t(env, np.arange(B, dtype=np.uint32)), w=dev_t(env, np.full(B, LIFT, dtype=np.int32)))
+    torch.cuda.synchronize()
+    l0, l1 = take(up0, B * npr * n, (B, npr, n), "lift"), take(up1, B * npr * n, (B, npr, n), "lift")
+    # the diagonals: slot k of diagonal e = M[k mod 16][(k + e) mod 16] / 2^8, encoded on the device
+    k = np.arange(n // 2)
+    dvals = np.stack([M[k % DIM, (k + e) % DIM] / DIAG_SHIFT for e in range(DIM)]).astype(np.float32)
+    enc = sentinel_out(env, DIM * npr * n, 2 * n)
+    ctx.encode_ntt(dev_t(env, dvals), enc)
+    torch.cuda.synchronize()
+    diag = take(enc, DIM * npr * n, (DIM, npr, n), "encoded diagonals")
+    t_diag = dev_t(env, diag)
+    d0, d1 = dev_t(env, l0), dev_t(env, l1)
+    # baby steps 0 .. 3, giant steps 0, 4, 8, 12: d[g][b] is diagonal 4 g + b, as the flat plan takes it
+    baby = [pkg.galois_element(n, b) for b in range(N1)]
+    giant = [pkg.galois_element(n, N1 * g) for g in range(N2)]
+    assert baby[0] == giant[0] == 1 and len(set(baby + giant)) == N1 + N2 - 1
+    assert all((gg * bb) % (2 * n) == pkg.galois_element(n, N1 * g + b)
+               for g, gg in enumerate(giant) for b, bb in enumerate(baby))
+    plan = ctx.bsgs_plan(baby, giant, t_diag.reshape(N2, N1, npr, n))
+    b0, b1 = run_bsgs(env, ctx, plan, d0, d1, npr, 3)          # two chunks, the last one short
+    plan.close()
+    want = bsgs_expect(pkg, o, l0, l1, baby, giant, diag.reshape(N2, N1, npr, n), c["key_of"], c["gk0"], c["gk1"])
+    assert (b0 == want[0]).all() and (b1 == want[1]).all(), "plan call"
+    flat = ctx.lintrans_plan(c["elts"], t_diag[1:].contiguous(), t_diag[0].contiguous())
+    words = B * npr * n
+    f0, f1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    ctx.ct_lintrans(flat, d0, d1, f0, f1, primes=npr)
+    torch.cuda.synchronize()
+    flat.close()
+    f0, f1 = take(f0, words, (B, npr, n), "flat out0"), take(f1, words, (B, npr, n), "flat out1")
+    for b in range(B):
+        big = max(abs(v) for v in expectation(o, b0[b], b1[b], c["s_hat"])["y"])
+        print(f"record {b}: log2 of the largest coefficient before the rescale = {np.log2(float(big)):.2f}")
+        assert big < 2 ** 62, (b, big)
+    scale = o.scale * LIFT * (o.scale / DIAG_SHIFT) / o.q[npr - 1]
+    v64 = c["vals"].astype(np.float64)
+    want_slots = np.tile(v64[:, :DIM] @ M.T, (1, n // 2 // DIM))
+    worst = {}
+    for name, (g0, g1) in (("bsgs", (b0, b1)), ("flat", (f0, f1))):
+        low = B * (npr - 1) * n
+        s0, s1 = sentinel_out(env, low, 2 * n), sentinel_out(env, low, 2 * n)
+        ctx.ct_rescale(dev_t(env, g0), s0, dev_t(env, g1), s1, primes=npr)
+        torch.cuda.synchronize()
+        r0, r1 = take(s0, low, (B, npr - 1, n), "rescale"), take(s1, low, (B, npr - 1, n), "rescale")
+        got = run_decrypt(env, ctx, dev_t(env, r0), dev_t(env, r1), npr - 1, scale)
+        assert bool((got["status"] == 1).all()), name
+        err = np.abs(got["values"].cpu().numpy().astype(np.float64) - want_slots)
+        worst[name] = float(err.max())
+        print(f"{name}: max |values - M x| over {B} records = {worst[name]:.3e}")
+        assert worst[name] < 0.1, (name, worst[name])
+    print(f"{n} x {npr}, 16 x 16 M x: worst error {worst['bsgs']:.3e} (4 x 4 baby-step / giant-step, 6 keys), "
+          f"{worst['flat']:.3e} (flat plan, 15 keys)")
+
+
+def test_matvec_bsgs_example(env, tmp_path):
+    """examples/matvec_bsgs_roundtrip.c from plain gcc: six Galois keys, the sixteen diagonals in a 4 x 4 plan, lift, ONE
+    se_amd_ct_bsgs_device call, rescale and decrypt_level come back within the reference's 0.1 of M x."""
+    exe = build_example("matvec_bsgs_roundtrip", tmp_path, hip=True, extra=("-lm",))
+    r = subprocess.run([str(exe), "4096", "3", "4"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"failed=0 B=4 .*max_abs_error=([0-9.e+-]+)", r.stdout)
+    assert m and float(m.group(1)) < 0.1, r.stdout
