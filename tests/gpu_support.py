@@ -1,27 +1,33 @@
-"""What the GPU test modules (tests/test_gpu_*.py) share.  Tests import helpers from here (`from gpu_support import
-env, dev_t, ...`), never from another test module; a helper that a second module needs moves here.
+"""Device plumbing that the GPU test modules (tests/test_gpu_*.py) share.  Tests import helpers from here (`from
+gpu_support import env, dev_t, ...`) and the host model from ct_model, never from another test module; a helper that a
+second module needs moves here (device code) or to ct_model (definitions and inputs).  Nothing of ct_model is re-exported.
 
 - env: the module-scoped fixture (torch, the loaded package, cuda:0); gpu_env() is the same setup as a plain function.
 - dev_t, host_u32, bits, stream_of, same_bytes: host <-> device and bit-pattern conveniences.
 - SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY: the C ABI's error codes; SEED_A, SEED_B, SEED_PK, SEED_EP: the golden seeds.
-- the receiving side: records, encrypt_sym, ntt_secret, crt_centred, decode_expect, expectation (oracle + Python
-  ints), run_decrypt (decrypt_full / decrypt_level and their keyed twins over sentinel-filled outputs), assert_matches.
-- ciphertext operations (tests/test_gpu_ct_*.py): SENTINEL, sentinel_out, take (outputs with guard words behind them);
-  DIGIT_BITS, DIGIT_MASK; centred, negacyclic, rand_slab, unit_values; the definitions the kernels are tested against,
-  rescale_expect, digits_of and relin_expect; keyed_cases, the module-scoped fixture of the end-to-end tests.
-- build_example, build_caller: plain-gcc programs of examples/ and tests/c/ linked against the product library.
+- the receiving side: records, encrypt_sym, fresh_records, ntt_secret, decode_expect, expectation (oracle + Python ints),
+  run_decrypt (decrypt_full / decrypt_level and their keyed twins over sentinel-filled outputs), assert_matches,
+  check_level_decrypt.
+- ciphertext operations (tests/test_gpu_ct_*.py): SENTINEL, sentinel_out, take (outputs with guard words behind them); one
+  runner per entry (run_relin, run_galois, run_many, run_sum, run_plan and the special-prime run_relin_sp,
+  run_galois_sp), each one call with two rows of sentinels behind each output; keyed_cases, the module-scoped fixture of
+  the end-to-end tests, with step_elements, install_galois_keys, lift_records, rescale_records and encode_diagonals, the
+  blocks those tests repeat.
+- build_example, build_caller, run_example: plain-gcc programs of examples/ and tests/c/ linked against the product library.
 - check_host_tables: every setup-time table against the oracle and the golden digests (CPU suite and GPU box).
 """
 import ctypes as C
 import hashlib
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
+from ct_model import crt_centred, galois_seeds, lift_expect, rescale_expect
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,8 +35,6 @@ SE_ERR_INVALD_ARGUMENT = -22
 SE_ERR_NO_KEY = -1002
 
 SENTINEL = 0x5A5A5A5A                 # fill of an output no call may have written
-DIGIT_BITS = 15                       # SE_AMD_RELIN_DIGIT_BITS
-DIGIT_MASK = (1 << DIGIT_BITS) - 1
 
 SEED_A = hashlib.shake_256(b"golden-share").digest(64)
 SEED_B = hashlib.shake_256(b"golden-secret").digest(64)
@@ -81,19 +85,6 @@ def same_bytes(a, b):
 
 
 # ---- the receiving side: expectations from the oracle's primitives and Python integers ------------------------------
-def crt_centred(o, pts):
-    """pts[j][k] = value mod q_j  ->  Python ints in (-Q/2, Q/2], Q = prod q_j."""
-    Q = 1
-    for q in o.q:
-        Q *= q
-    acc = np.zeros(o.n, dtype=object)
-    for j, q in enumerate(o.q):
-        M = Q // q
-        acc = acc + pts[j].astype(object) * (M * pow(M % q, -1, q))
-    acc = acc % Q
-    return [int(v) - Q if int(v) > Q // 2 else int(v) for v in acc]
-
-
 def ntt_secret(o, sk):
     return [o.ntt(o.expand_ternary(sk, j), j) for j in range(o.np)]
 
@@ -108,7 +99,7 @@ def expectation(o, c0, c1, s_hat, scale=None):
     """c0, c1 [np][n] uint32 -> dict(status, pte int64 | None, y, values_f64, values) from the oracle and Python ints,
     on a record of o.np primes, decoded with `scale` (default: the oracle's)."""
     pts = [o.intt(o.decrypt(c0[j], c1[j], s_hat[j], j), j) for j in range(o.np)]
-    y = crt_centred(o, pts)
+    y = crt_centred(o.q, pts)
     if not all(-2 ** 63 <= v < 2 ** 63 for v in y):
         return dict(status=0, pte=None, y=y)
     pte = np.array(y, dtype=np.int64)
@@ -171,7 +162,7 @@ def encrypt_sym(env, ctx, vals, first=0):
     return c0, c1, pte, st
 
 
-# ---- ciphertext operations: guarded outputs, inputs and the definitions of rescale and key switch -------------------
+# ---- ciphertext operations: guarded outputs, one runner per entry, the blocks of the end-to-end tests ----------------
 def sentinel_out(env, words, extra):
     return env["torch"].full((words + extra,), SENTINEL, dtype=env["torch"].int32, device=env["dev"])
 
@@ -183,9 +174,54 @@ def take(t, words, shape, what):
     return h[:words].reshape(shape)
 
 
-def rand_slab(rng, q, count, n, primes=None):
-    primes = len(q) if primes is None else primes
-    return np.stack([rng.integers(0, q[j], (count, n), dtype=np.uint32) for j in range(primes)], axis=1)
+def guarded_pair(env, n, shape, what, call):
+    """call(out0, out1) on two outputs of `shape` words with two rows of sentinels behind each -> their host copies (take:
+    the sentinels must have survived)."""
+    words = int(np.prod(shape))
+    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
+    call(out0, out1)
+    env["torch"].cuda.synchronize()
+    return take(out0, words, shape, what + " out0"), take(out1, words, shape, what + " out1")
+
+
+def run_relin(env, ctx, d0, d1, d2, primes):
+    """One ct_relin call on device slabs [B][primes][n]."""
+    return guarded_pair(env, ctx.n, (d0.shape[0], primes, ctx.n), "relin",
+                        lambda a, b: ctx.ct_relin(d0, d1, d2, a, b, primes=primes))
+
+
+def run_relin_sp(env, ctx, d0, d1, d2, primes):
+    return guarded_pair(env, ctx.n, (d0.shape[0], primes, ctx.n), "relin_sp",
+                        lambda a, b: ctx.ct_relin_sp(d0, d1, d2, a, b, primes=primes))
+
+
+def run_galois(env, ctx, c0, c1, elt, primes):
+    """One ct_galois call on device slabs [B][primes][n]."""
+    return guarded_pair(env, ctx.n, (c0.shape[0], primes, ctx.n), "galois",
+                        lambda a, b: ctx.ct_galois(c0, c1, elt, a, b, primes=primes))
+
+
+def run_galois_sp(env, ctx, c0, c1, elt, primes):
+    return guarded_pair(env, ctx.n, (c0.shape[0], primes, ctx.n), "galois_sp",
+                        lambda a, b: ctx.ct_galois_sp(c0, c1, elt, a, b, primes=primes))
+
+
+def run_many(env, ctx, c0, c1, elts, primes):
+    """One many-form call on device slabs [B][primes][n] -> [G][B][primes][n] each."""
+    return guarded_pair(env, ctx.n, (len(elts), c0.shape[0], primes, ctx.n), "many",
+                        lambda a, b: ctx.ct_galois_many(c0, c1, elts, a, b, primes=primes))
+
+
+def run_sum(env, ctx, c0, c1, elts, primes, add_input):
+    """One sum-form call (ct_galois_sum) on device slabs [B][primes][n]."""
+    return guarded_pair(env, ctx.n, (c0.shape[0], primes, ctx.n), "sum",
+                        lambda a, b: ctx.ct_galois_sum(c0, c1, elts, a, b, add_input=add_input, primes=primes))
+
+
+def run_plan(env, ctx, plan, c0, c1, primes):
+    """One ct_lintrans call of a flat plan on device slabs [B][primes][n]."""
+    return guarded_pair(env, ctx.n, (c0.shape[0], primes, ctx.n), "lintrans",
+                        lambda a, b: ctx.ct_lintrans(plan, c0, c1, a, b, primes=primes))
 
 
 def unit_values(B, n, seed):
@@ -193,64 +229,103 @@ def unit_values(B, n, seed):
     return np.random.default_rng(seed).uniform(-1.0, 1.0, (B, n // 2)).astype(np.float32)
 
 
-def centred(x, q):
-    """canonical residues -> int64 representatives in (-q/2, q/2]  (q odd)."""
-    x = x.astype(np.int64)
-    return np.where(x > q // 2, x - q, x)
+def periodic_values(B, n, dim, seed):
+    """float32 [B][n/2]: per record a dim-vector uniform in [-1, 1], repeated through the slots."""
+    x = np.random.default_rng(seed).uniform(-1.0, 1.0, (B, dim))
+    return np.tile(x, (1, n // 2 // dim)).astype(np.float32)
 
 
-def negacyclic(a, s):
-    """a * s mod (x^n + 1) in int64 (the callers keep every sum below 2^62)."""
-    n = a.shape[0]
-    full = np.convolve(a, s)
-    res = full[:n].copy()
-    res[:n - 1] -= full[n:]
-    return res
+def fresh_records(env, ctx, vals, first):
+    """vals encrypted under the installed secret key with the bench seeds from `first` on; every record must encode."""
+    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=first)
+    assert bool((st == 1).all())
+    return c0, c1
 
 
-def rescale_expect(o, slab):
-    """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: out[j] = (in[j] - NTT_j(delta mod q_j)) . q_last^-1 mod q_j with
-    delta the centred INTT of the last row, from o.intt / o.ntt and uint64 arithmetic."""
-    B, L, n = slab.shape
-    q_last = o.q[L - 1]
-    out = np.zeros((B, L - 1, n), dtype=np.uint32)
-    for b in range(B):
-        delta = centred(o.intt(slab[b, L - 1], L - 1), q_last)
-        for j in range(L - 1):
-            q = o.q[j]
-            inv = pow(q_last, -1, q)
-            t = o.ntt((delta % q).astype(np.uint32), j).astype(np.uint64)
-            diff = (slab[b, j].astype(np.uint64) + np.uint64(q) - t) % np.uint64(q)
-            out[b, j] = ((diff * np.uint64(inv)) % np.uint64(q)).astype(np.uint32)
-    return out
+def step_elements(env, n, steps):
+    """The Galois elements of the slot rotations by `steps` from the package, which must be 3^step mod 2n."""
+    elts = [env["pkg"].galois_element(n, s) for s in steps]
+    assert elts == [pow(3, s % (n // 2), 2 * n) for s in steps]
+    return elts
 
 
-def digits_of(o, rec, L):
-    """Record [L][n] -> the 2 L digit polynomials D_{j,t} (uint32, natural order), row r = 2j + t."""
-    out = []
-    for j in range(L):
-        c = o.intt(rec[j], j)
-        out += [c & np.uint32(DIGIT_MASK), c >> np.uint32(DIGIT_BITS)]
-    return out
+def install_galois_keys(case, elts, label, sp=False):
+    """Generate the Galois keys of `elts` under the case's secret key from the seeds derive_seeds(label + "-a" / "-e")
+    and install them: digit keys, or with sp the special-prime keys.  -> gk0, gk1."""
+    ctx = case["ctx"]
+    gen, install = (ctx.gen_galois_keys_sp, ctx.set_galois_keys_sp) if sp else (ctx.gen_galois_keys, ctx.set_galois_keys)
+    gk0, gk1 = gen(case["sk"], elts, *galois_seeds(ctx.np, len(elts), label, sp))
+    install(elts, gk0, gk1)
+    return gk0, gk1
 
 
-def relin_expect(o, d0, d1, d2, evk0, evk1):
-    """The definition of the key switch, which relinearisation and rotation are both tested against:
-    out_k[b][i] = d_k[b][i] + sum_r NTT_i(D_r) . evk_k[r][i] mod q_i, from o.intt / o.ntt and uint64 arithmetic (a
-    product is below 2^60, reduced before it is added)."""
-    B, L, n = d0.shape
-    out0, out1 = np.zeros_like(d0), np.zeros_like(d1)
-    for b in range(B):
-        D = digits_of(o, d2[b], L)
-        for i in range(L):
-            q = np.uint64(o.q[i])
-            acc0, acc1 = d0[b, i].astype(np.uint64), d1[b, i].astype(np.uint64)
-            for r, dig in enumerate(D):
-                f = o.ntt(dig, i).astype(np.uint64)
-                acc0 = (acc0 + (f * evk0[r, i].astype(np.uint64)) % q) % q
-                acc1 = (acc1 + (f * evk1[r, i].astype(np.uint64)) % q) % q
-            out0[b, i], out1[b, i] = acc0, acc1
-    return out0, out1
+def drop_records(env, ctx, c0, c1, L):
+    """ct_drop_primes of full records to L primes, which must equal the slices -> host l0, l1 [B][L][n]."""
+    l0, l1 = guarded_pair(env, ctx.n, (c0.shape[0], L, ctx.n), "drop",
+                          lambda a, b: ctx.ct_drop_primes(c0, a, c1, b, primes_in=ctx.np, primes_out=L))
+    assert (l0 == host_u32(c0)[:, :L]).all() and (l1 == host_u32(c1)[:, :L]).all()
+    return l0, l1
+
+
+def lift_records(env, ctx, o, fresh, weight):
+    """The lift: ct_lincomb with one CSR row per record holding the single weight; equal to the product in the test's
+    own integers -> host l0, l1 [B][np][n]."""
+    c0, c1 = fresh
+    B = c0.shape[0]
+    l0, l1 = guarded_pair(env, ctx.n, (B, ctx.np, ctx.n), "lift", lambda a, b: ctx.ct_lincomb(
+        c0, a, c1, b, row_ptr=dev_t(env, np.arange(B + 1, dtype=np.uint32)), idx=dev_t(env, np.arange(B, dtype=np.uint32)),
+        w=dev_t(env, np.full(B, weight, dtype=np.int32))))
+    assert (l0 == lift_expect(o, host_u32(c0), weight)).all() and (l1 == lift_expect(o, host_u32(c1), weight)).all()
+    return l0, l1
+
+
+def encode_diagonals(env, ctx, o, dvals):
+    """encode_ntt of float32 [dim][n/2] on the device, equal to the oracle's encoding -> host uint32 [dim][np][n]."""
+    dim, npr, n = dvals.shape[0], ctx.np, ctx.n
+    enc = sentinel_out(env, dim * npr * n, 2 * n)
+    ctx.encode_ntt(dev_t(env, dvals), enc)
+    env["torch"].cuda.synchronize()
+    ok, enc_want = o.encode_ntt_batch(dvals)
+    assert ok
+    diag = take(enc, dim * npr * n, (dim, npr, n), "encoded diagonals")
+    assert (diag == enc_want).all()
+    return diag
+
+
+def check_headroom(o, g0, g1, s_hat, what):
+    """Every coefficient of the records' centred decrypt is below 2^62, the room the int64 stages need."""
+    for b in range(g0.shape[0]):
+        big = max(abs(v) for v in expectation(o, g0[b], g1[b], s_hat)["y"])
+        print(f"{what}, record {b}: log2 of the largest coefficient = {np.log2(float(big)):.2f}")
+        assert big < 2 ** 62, (what, b, big)
+
+
+def rescale_records(env, ctx, o, g0, g1, primes, what="rescale"):
+    """ct_rescale of host records [B][primes][n], equal to rescale_expect -> host f0, f1 [B][primes - 1][n]."""
+    f0, f1 = guarded_pair(env, ctx.n, (g0.shape[0], primes - 1, ctx.n), "rescale",
+                          lambda a, b: ctx.ct_rescale(dev_t(env, g0), a, dev_t(env, g1), b, primes=primes))
+    assert (f0 == rescale_expect(o, g0)).all() and (f1 == rescale_expect(o, g1)).all(), what
+    return f0, f1
+
+
+def check_level_decrypt(env, ctx, lo, r0, r1, s_hat, primes, scale, want, what="decrypt"):
+    """decrypt_level on host records [B][primes][n] against the oracle expectation (lo: the oracle of that level) on the
+    same records, bit for bit; the reference's 0.1 against want[b] first on the expectation, then on the GPU result.
+    -> the largest error of the GPU result, printed."""
+    got = run_decrypt(env, ctx, dev_t(env, r0), dev_t(env, r1), primes, scale)
+    worst = 0.0
+    for b in range(r0.shape[0]):
+        e = expectation(lo, r0[b], r1[b], s_hat[:primes], scale)
+        assert e["status"] == 1
+        assert_matches(got, b, e, (what, b))
+        err_e = float(np.abs(e["values"].astype(np.float64) - want[b]).max())
+        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want[b]).max())
+        print(f"{what}, record {b}: max |values - expected| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
+        assert err_e < 0.1 and err_g < 0.1, (what, b, err_e, err_g)
+        worst = max(worst, err_g)
+    print(f"{ctx.n} x {ctx.np}, {what}: worst error {worst:.3e}")
+    assert worst < 0.1
+    return worst
 
 
 @pytest.fixture(scope="module")
@@ -292,6 +367,16 @@ def build_example(name, tmp_path, hip=False, extra=()):
     flags = ["-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-L/opt/rocm/lib", "-lamdhip64",
              "-Wl,-rpath,/opt/rocm/lib"] if hip else []
     return _link(os.path.join(ROOT, "examples", name + ".c"), tmp_path / name, flags + list(extra))
+
+
+def run_example(name, tmp_path, args, bound=0.1):
+    """Build examples/<name>.c (a HIP-owning C caller, with -lm), run it with `args` = n, np, B, ...: it must exit 0 and
+    report failed=0 for its B records with a largest absolute error below `bound`, the reference's 0.1."""
+    exe = build_example(name, tmp_path, hip=True, extra=("-lm",))
+    r = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"failed=0 B=%s .*max_abs_error=([0-9.e+-]+)" % args[2], r.stdout)
+    assert m and float(m.group(1)) < bound, r.stdout
 
 
 def build_caller(name, tmp_path):

@@ -7,8 +7,8 @@ import re
 
 import numpy as np
 
-from bsgs_support import inverse_element, src_of
 from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from ct_model import inverse_element
 
 ENTRIES = ("se_amd_ct_mul_plain_sum_device", "se_amd_ct_galois_accum_device", "se_amd_bsgs_create",
            "se_amd_ct_bsgs_device")                                   # declared `int name(`
@@ -78,7 +78,7 @@ def test_a_diagonal_pre_rotated_by_the_inverse_commutes_with_the_giant_step(pkg)
     edges = [0, 1, q - 1]
     for gamma in (3, n + 1, 2 * n - 1, inverse_element(n, 3)):
         inv = inverse_element(n, gamma)
-        src, src_inv = src_of(pkg, n, gamma), src_of(pkg, n, inv)
+        src, src_inv = (pkg.galois_table(n, g).astype(np.int64) for g in (gamma, inv))
         assert sorted(src.tolist()) == list(range(n))
         assert (src[src_inv] == np.arange(n)).all() and (src_inv[src] == np.arange(n)).all(), gamma
         d = [int(v) for v in rng.integers(0, q, n)]

@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from ct_model import edge_row, galois_sp_expect, hoist_sp_expect, sum_of_single_calls
 
 ENTRIES = ("se_amd_ct_galois_sum_sp_device", "se_amd_lintrans_create_sp", "se_amd_ct_lintrans_sp_device")
 METHODS = ("ct_galois_sum_sp", "lintrans_plan_sp", "ct_lintrans_sp")
@@ -50,18 +51,13 @@ def test_matvec_fresh_example_compiles_as_plain_c(tmp_path):
 
 
 def test_model_one_element_is_the_single_entry_and_two_are_not_two_calls():
-    """The definition (tests/keyswitch_sp_hoist_support.py) at 4096 x 3, L = 2, one record whose c1 rows hold 0, 1,
+    """The definition (hoist_sp_expect of tests/ct_model.py) at 4096 x 3, L = 2, one record whose c1 rows hold 0, 1,
     (q - 1)/2, (q + 1)/2 and q - 1 on negated and on kept positions, random key words: with one element it equals the
     definition of se_amd_ct_galois_sp_device bit for bit (centring commutes with sigma), for both elements; with the
     elements {3, n + 1} it differs from the sum of the two single key switches in at least one word of each half (one
     rounding, not two).  All-ones weights with an all-ones diag0 give the sum form with add_input."""
     from oracle import pyoracle
     pyoracle.build(ref=False)
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import vectors as V
-    from keyswitch_sp_support import galois_sp_expect
-    from keyswitch_sp_hoist_support import hoist_sp_expect, sum_of_single_calls
     n, npr, L = 4096, 3, 2
     o = pyoracle.Oracle(n, npr)
     q = o.q
@@ -70,18 +66,7 @@ def test_model_one_element_is_the_single_entry_and_two_are_not_two_calls():
     keys = [tuple(np.stack([np.stack([rng.integers(0, q[i], n, dtype=np.uint32) for i in range(npr)])
                             for _ in range(npr - 1)]) for _ in range(2)) for _ in elts]
     c0 = np.stack([rng.integers(0, q[j], n, dtype=np.uint32) for j in range(L)])[None]
-    rows = []
-    for j in range(L):
-        edges = np.array([0, 1, (q[j] - 1) // 2, (q[j] + 1) // 2, q[j] - 1], dtype=np.uint32)
-        c = rng.integers(2, q[j] - 1, n, dtype=np.uint32)
-        for start in (0, n // 2, n - 13):
-            c[start:start + 5] = c[start + 7:start + 12] = edges
-        for g in elts:
-            _, neg = V.galois_image(n, g)
-            for v in edges:
-                assert ((c == v) & neg).any() and ((c == v) & ~neg).any(), (g, int(v))
-        rows.append(o.ntt(c, j))
-    c1 = np.stack(rows)[None]
+    c1 = np.stack([edge_row(o, j, rng, elts, edges="centring") for j in range(L)])[None]
     for g, key in zip(elts, keys):
         h0, h1, info = hoist_sp_expect(o, c0, c1, [g], [key])
         e0, e1 = galois_sp_expect(o, c0, c1, g, *key)

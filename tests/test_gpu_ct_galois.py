@@ -6,17 +6,17 @@ x^k -> +-x^(k g mod n) pushed through o.intt and o.ntt, never se_amd_galois_tabl
 the reference's own acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
 Oracle(n, L - 1) is the oracle of the level below Oracle(n, L): the default chains are prefixes of one another."""
 import ctypes as C
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (DIGIT_BITS, DIGIT_MASK, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches,  # noqa: F401
-                         build_example, centred, crt_centred, dev_t, digits_of, encrypt_sym, env, expectation, host_u32,
-                         keyed_cases, negacyclic, ntt_secret, rand_slab, relin_expect, rescale_expect, run_decrypt,
-                         sentinel_out, stream_of, take, unit_values)
+from ct_model import (CASE_IDS, GALOIS_CASES, SHAPE_IDS, digit_key_errors, digits_of, edge_row, galois_diagonal,
+                      galois_expect, galois_seeds, lift_expect, negacyclic, rand_slab, random_keys, sigma_slab, src_table)
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_headroom, check_level_decrypt,  # noqa: F401
+                         dev_t, env, expectation, fresh_records, host_u32, install_galois_keys, keyed_cases,
+                         lift_records, ntt_secret, rescale_records, run_example, run_galois, step_elements, stream_of,
+                         unit_values)
 from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
@@ -24,58 +24,8 @@ pytestmark = pytest.mark.gpu
 LIFT = 1 << 30
 
 
-# ---- the automorphism, in the coefficient domain (vectors.sigma_coeff) on a slab ------------------------------------
-def sigma_slab(o, slab, g):
-    """sigma on every NTT-form row of a slab [B][L][n] through o.intt / o.ntt."""
-    out = np.zeros_like(slab)
-    for b in range(slab.shape[0]):
-        for j in range(slab.shape[1]):
-            out[b, j] = o.ntt(sigma_coeff(o.intt(slab[b, j], j), g, o.q[j]), j)
-    return out
-
-
-def galois_expect(o, c0, c1, g, gk0, gk1):
-    """The definition: relin_expect on (sigma(c0), 0, sigma(c1)) with the key of the element."""
-    return relin_expect(o, sigma_slab(o, c0, g), np.zeros_like(c1), sigma_slab(o, c1, g), gk0, gk1)
-
-
-def run_galois(env, ctx, c0, c1, elt, primes):
-    """One call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
-    B, n = c0.shape[0], ctx.n
-    words = B * primes * n
-    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_galois(c0, c1, elt, out0, out1, primes=primes)
-    env["torch"].cuda.synchronize()
-    return take(out0, words, (B, primes, n), "galois out0"), take(out1, words, (B, primes, n), "galois out1")
-
-
-def galois_seeds(npr, G, label):
-    return V.derive_seeds(label + "-a", G * 2 * npr), V.derive_seeds(label + "-e", G * 2 * npr)
-
-
 # ---- test 1: the definition on arbitrary slabs and key words --------------------------------------------------------
-def edge_row(o, j, rng, elts):
-    """NTT form of natural-order coefficients that hold both sides of the digit boundary, 0, 1 and q - 1, each of them
-    on at least one index whose image is negated and on one whose image is not, for every element of `elts`."""
-    n, q = o.n, o.q[j]
-    edges = np.array([0, 1, DIGIT_MASK, DIGIT_MASK + 1, DIGIT_MASK + 2, q - 1], dtype=np.uint32)
-    c = rng.integers(1, q, n, dtype=np.uint32)
-    for start in (0, n // 2, n - 13):           # twice, 7 apart: an even and an odd index for every value
-        c[start:start + 6] = c[start + 7:start + 13] = edges
-    for g in elts:
-        _, neg = V.galois_image(n, g)
-        for v in edges:
-            at = c == v
-            assert (at & neg).any() and (at & ~neg).any(), (g, int(v))
-    row = o.ntt(c, j)
-    assert (o.intt(row, j) == c).all()
-    return row
-
-
-GALOIS_CASES = [((1024, 1), (1,), 3), ((4096, 3), (3, 2), 3), ((16384, 13), (13,), 2)]
-
-
-@pytest.mark.parametrize("shape,levels,B", GALOIS_CASES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+@pytest.mark.parametrize("shape,levels,B", GALOIS_CASES, ids=CASE_IDS)
 def test_galois_arbitrary_slabs_and_key(env, shape, levels, B):
     """Test 1: random residues for both slabs and for the installed keys of the elements 3 and n + 1 (n + 1 moves no
     coefficient and negates every odd one); record 0 of c1 holds 0, 1, the digit boundaries and q - 1 on negated and on
@@ -83,15 +33,12 @@ def test_galois_arbitrary_slabs_and_key(env, shape, levels, B):
     i < L of the same keys; the sentinels behind the outputs survive.  No secret key is installed."""
     from oracle.pyoracle import Oracle
     n, npr = shape
-    R = 2 * npr
     o = Oracle(n, npr)
     ctx = env["pkg"].Context(n, npr)
     q = o.q
     rng = np.random.default_rng(37 * n + npr)
     elts = [3, n + 1]
-    gk0 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in elts])
-    gk1 = np.stack([np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(R)]) for _ in elts])
-    gk0[0, 0, 0, :4] = [0, 1, q[0] - 1, q[0] - 1]
+    gk0, gk1 = random_keys(rng, q, len(elts), n, npr)
     ctx.set_galois_keys(elts, gk0, gk1)
     for L in levels:
         c0, c1 = rand_slab(rng, q, B, n, L), rand_slab(rng, q, B, n, L)
@@ -107,20 +54,6 @@ def test_galois_arbitrary_slabs_and_key(env, shape, levels, B):
 
 
 # ---- test 2: the relinearisation twin -------------------------------------------------------------------------------
-def brev(v, bits):
-    r = np.zeros_like(v)
-    for b in range(bits):
-        r |= ((v >> b) & 1) << (bits - 1 - b)
-    return r
-
-
-def src_table(n, g):
-    """sigma_g(x)[k] = x[src[k]] on a bit-reversed NTT-form row, from the formula in Python."""
-    bits = n.bit_length() - 1
-    k = np.arange(n, dtype=np.int64)
-    return brev((((2 * brev(k, bits) + 1) * g) % (2 * n) - 1) // 2, bits)
-
-
 def test_galois_is_relin_of_the_permuted_record(env):
     """Test 2: at 4096 x 3 the outputs have the bytes of ct_relin(sigma(c0), 0, sigma(c1)) with the element's key
     installed as the relinearisation key; sigma is an index_select along the row."""
@@ -148,14 +81,7 @@ def test_galois_is_relin_of_the_permuted_record(env):
 
 
 # ---- test 3: key generation, installs and their refusals ------------------------------------------------------------
-def galois_diagonal(o, s_hat, g, j, t):
-    """(2^(15 t) mod q_j) . sigma(s_hat_j) mod q_j, uint64; sigma through the coefficient domain."""
-    q = o.q[j]
-    s = o.ntt(sigma_coeff(o.intt(s_hat[j], j), g, q), j).astype(np.uint64)
-    return (s * np.uint64(pow(2, DIGIT_BITS * t, q))) % np.uint64(q)
-
-
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_galois_key_generation(env, shape):
     """Test 3: gen_galois_keys for {3, 3^-1, 2n - 1} equals gen_keys_batch(K = 2 np, this key replicated, the element's
     block of seeds) plus the diagonal from the oracle's NTT(s) and sigma in Python; exactly the diagonal columns differ;
@@ -313,22 +239,17 @@ def fill_keyed_case(env, case):
     """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the Galois keys of the
     steps 1 and -3, installed; B = 4 fresh symmetric records with slot values in [-1, 1] and the same records lifted by
     2^30 in the test's own integers."""
-    ctx, o, sk, pkg = case["ctx"], case["o"], case["sk"], env["pkg"]
-    n, npr, B = ctx.n, ctx.np, 4
-    elts = [pkg.galois_element(n, s) for s in STEPS]
-    assert elts == [pow(3, s % (n // 2), 2 * n) for s in STEPS]
-    gk0, gk1 = ctx.gen_galois_keys(sk, elts, *galois_seeds(npr, len(elts), "gk-e2e"))
-    ctx.set_galois_keys(elts, gk0, gk1)
-    vals = unit_values(B, n, 3000 + n)
-    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=200)
-    assert bool((st == 1).all())
-    qv = np.array(o.q, dtype=np.uint64)[None, :, None]
-    l0 = ((host_u32(c0).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
-    l1 = ((host_u32(c1).astype(np.uint64) * np.uint64(LIFT)) % qv).astype(np.uint32)
-    case.update(elts=elts, gk0=gk0, gk1=gk1, vals=vals, fresh=(c0, c1), lifted=(l0, l1))
+    ctx, o = case["ctx"], case["o"]
+    n = ctx.n
+    elts = step_elements(env, n, STEPS)
+    gk0, gk1 = install_galois_keys(case, elts, "gk-e2e")
+    vals = unit_values(4, n, 3000 + n)
+    c0, c1 = fresh_records(env, ctx, vals, 200)
+    case.update(elts=elts, gk0=gk0, gk1=gk1, vals=vals, fresh=(c0, c1),
+                lifted=(lift_expect(o, host_u32(c0), LIFT), lift_expect(o, host_u32(c1), LIFT)))
 
 
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_galois_exact_key_switch_identity(env, keyed_cases, shape):
     """Test 5: with y the oracle's centred decrypt of a lifted record, y' that of its rotation, D_r the digits of
     sigma(c1) and e_r the key's errors recovered with the oracle (centred INTT of gk0 + gk1 . s_hat - diagonal),
@@ -337,17 +258,7 @@ def test_galois_exact_key_switch_identity(env, keyed_cases, shape):
     o, s_hat, npr, ctx = c["o"], c["s_hat"], c["o"].np, c["ctx"]
     l0, l1 = (x[:2] for x in c["lifted"])
     for k, g in enumerate(c["elts"]):
-        errs = []
-        for r in range(2 * npr):
-            per_prime = []
-            for i in (0, npr - 1):
-                q = np.uint64(o.q[i])
-                v = o.decrypt(c["gk0"][k, r, i], c["gk1"][k, r, i], s_hat[i], i).astype(np.uint64)
-                if i == r // 2:
-                    v = (v + q - galois_diagonal(o, s_hat, g, i, r % 2)) % q
-                per_prime.append(centred(o.intt(v.astype(np.uint32), i), o.q[i]))
-            assert (per_prime[0] == per_prime[1]).all() and np.abs(per_prime[0]).max() <= 64, r   # one small integer e_r
-            errs.append(per_prime[0])
+        errs = digit_key_errors(o, c["gk0"][k], c["gk1"][k], s_hat, lambda j, t: galois_diagonal(o, s_hat, g, j, t))
         g0, g1 = run_galois(env, ctx, dev_t(env, l0), dev_t(env, l1), g, npr)
         p1 = sigma_slab(o, l1, g)
         for b in range(2):
@@ -360,7 +271,7 @@ def test_galois_exact_key_switch_identity(env, keyed_cases, shape):
             print(f"element {g}, record {b}: max |key-switch term| = {int(np.abs(ks).max())}")
 
 
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_rotation_end_to_end(env, keyed_cases, shape):
     """Test 6: ct_lincomb with weight 2^30 -> ct_galois (step 1, then step -3 on a second pass) -> ct_rescale ->
     decrypt_level(primes = np - 1, scale = Delta 2^30 / q_last) on B = 4 records with slot values in [-1, 1]: every
@@ -369,55 +280,25 @@ def test_rotation_end_to_end(env, keyed_cases, shape):
     simulation of the same chain, tools/ct_galois_noise_sim.py, puts the error near 1e-4).  The worst error is
     printed."""
     from oracle.pyoracle import Oracle
-    torch = env["torch"]
     c = keyed_cases(shape)
     ctx, o = c["ctx"], c["o"]
     n, npr = shape
     lo = Oracle(n, npr - 1)
-    B = c["vals"].shape[0]
-    # the lift: one CSR row per record with the single weight 2^30
-    up0, up1 = sentinel_out(env, B * npr * n, 2 * n), sentinel_out(env, B * npr * n, 2 * n)
-    ctx.ct_lincomb(c["fresh"][0], up0, c["fresh"][1], up1, row_ptr=dev_t(env, np.arange(B + 1, dtype=np.uint32)),
-                   idx=dev_t(env, np.arange(B, dtype=np.uint32)), w=dev_t(env, np.full(B, LIFT, dtype=np.int32)))
-    torch.cuda.synchronize()
-    l0, l1 = take(up0, B * npr * n, (B, npr, n), "lift"), take(up1, B * npr * n, (B, npr, n), "lift")
+    l0, l1 = lift_records(env, ctx, o, c["fresh"], LIFT)
     assert (l0 == c["lifted"][0]).all() and (l1 == c["lifted"][1]).all()
     scale = o.scale * LIFT / o.q[npr - 1]
     for k, (s, g) in enumerate(zip(STEPS, c["elts"])):
         g0, g1 = run_galois(env, ctx, dev_t(env, l0), dev_t(env, l1), g, npr)
         e0, e1 = galois_expect(o, l0[:2], l1[:2], g, c["gk0"][k], c["gk1"][k])
         assert (g0[:2] == e0).all() and (g1[:2] == e1).all(), s
-        for b in range(B):
-            big = max(abs(v) for v in expectation(o, g0[b], g1[b], c["s_hat"])["y"])
-            assert big < 2 ** 62, (s, b, big)
-        words = B * (npr - 1) * n
-        s0, s1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-        ctx.ct_rescale(dev_t(env, g0), s0, dev_t(env, g1), s1, primes=npr)
-        torch.cuda.synchronize()
-        f0, f1 = take(s0, words, (B, npr - 1, n), "rescale"), take(s1, words, (B, npr - 1, n), "rescale")
-        assert (f0 == rescale_expect(o, g0)).all() and (f1 == rescale_expect(o, g1)).all(), s
-        got = run_decrypt(env, ctx, dev_t(env, f0), dev_t(env, f1), npr - 1, scale)
-        worst = 0.0
-        for b in range(B):
-            e = expectation(lo, f0[b], f1[b], c["s_hat"][:npr - 1], scale)
-            assert e["status"] == 1
-            assert_matches(got, b, e, (s, b))
-            want = np.roll(c["vals"][b].astype(np.float64), -s)
-            err_e = float(np.abs(e["values"].astype(np.float64) - want).max())
-            err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want).max())
-            print(f"step {s}, record {b}: max |values - roll| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
-            assert err_e < 0.1 and err_g < 0.1, (s, b, err_e, err_g)
-            worst = max(worst, err_g)
-        print(f"{n} x {npr}, step {s}: worst error {worst:.3e}")
-        assert worst < 0.1
+        check_headroom(o, g0, g1, c["s_hat"], f"step {s}")
+        f0, f1 = rescale_records(env, ctx, o, g0, g1, npr, s)
+        want = np.roll(c["vals"].astype(np.float64), -s, axis=1)
+        check_level_decrypt(env, ctx, lo, f0, f1, c["s_hat"], npr - 1, scale, want, f"step {s}")
 
 
 # ---- test 7: the example --------------------------------------------------------------------------------------------
 def test_slot_sum_example(env, tmp_path):
     """examples/slot_sum_roundtrip.c from plain gcc: packed dot products through the tensor, relin, four rotate-and-adds,
     rescale and decrypt_level come back within the reference's 0.1."""
-    exe = build_example("slot_sum_roundtrip", tmp_path, hip=True, extra=("-lm",))
-    r = subprocess.run([str(exe), "4096", "3", "8"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search(r"failed=0 B=8 .*max_abs_error=([0-9.e+-]+)", r.stdout)
-    assert m and float(m.group(1)) < 0.1, r.stdout
+    run_example("slot_sum_roundtrip", tmp_path, ("4096", "3", "8"))

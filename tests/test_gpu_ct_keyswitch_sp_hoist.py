@@ -1,80 +1,36 @@
 """Hoisted rotations on the special-prime key (-m gpu): se_amd_ct_galois_sum_sp_device, se_amd_lintrans_create_sp and
 se_amd_ct_lintrans_sp_device.
-Every expectation is the definition in tests/keyswitch_sp_hoist_support.py (and, for the single entry, in
-tests/keyswitch_sp_support.py): the oracle's primitives and Python / NumPy integers, never the code under test.  Every
-comparison is bit-exact except the reference's own acceptance criterion |values - expected| < 0.1.
+Every expectation is the definition in tests/ct_model.py (hoist_sp_expect and, for the single entry, galois_sp_expect):
+the oracle's primitives and Python / NumPy integers, never the code under test.  Every comparison is bit-exact except
+the reference's own acceptance criterion |values - expected| < 0.1.
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
 import ctypes as C
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, build_example, dev_t,  # noqa: F401
-                         encrypt_sym, env, expectation, host_u32, keyed_cases, rand_slab, rescale_expect, run_decrypt,
-                         sentinel_out, stream_of, take, unit_values)
-from keyswitch_sp_hoist_support import hoist_sp_expect, src_table, sum_of_single_calls
-from keyswitch_sp_support import add_mod, centred, key_errors, key_switch_sp, negacyclic, sigma_rows
+from ct_model import (CASE_IDS, SHAPE_IDS, SP_CASES, add_mod, centred, edge_diagonals, edge_row, hoist_sp_expect,
+                      key_errors, key_switch_sp, matrix, matrix_diagonals, negacyclic, rand_key, rand_slab, sigma_rows,
+                      sum_of_single_calls)
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
+                         encode_diagonals, env, expectation, fresh_records, guarded_pair, install_galois_keys,
+                         keyed_cases, periodic_values, rescale_records, run_example, run_galois_sp, step_elements,
+                         stream_of, unit_values)
 from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
 
 
 def run_sum_sp(env, ctx, c0, c1, elts, primes, add_input):
-    """One call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
-    B, n = c0.shape[0], ctx.n
-    words = B * primes * n
-    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_galois_sum_sp(c0, c1, elts, out0, out1, add_input=add_input, primes=primes)
-    env["torch"].cuda.synchronize()
-    return take(out0, words, (B, primes, n), "sum_sp out0"), take(out1, words, (B, primes, n), "sum_sp out1")
+    """One ct_galois_sum_sp call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
+    return guarded_pair(env, ctx.n, (c0.shape[0], primes, ctx.n), "sum_sp",
+                        lambda a, b: ctx.ct_galois_sum_sp(c0, c1, elts, a, b, add_input=add_input, primes=primes))
 
 
 def run_lintrans_sp(env, ctx, plan, c0, c1, primes):
-    B, n = c0.shape[0], ctx.n
-    words = B * primes * n
-    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_lintrans_sp(plan, c0, c1, out0, out1, primes=primes)
-    env["torch"].cuda.synchronize()
-    return take(out0, words, (B, primes, n), "lintrans_sp out0"), take(out1, words, (B, primes, n), "lintrans_sp out1")
-
-
-def run_galois_sp(env, ctx, c0, c1, elt, primes):
-    B, n = c0.shape[0], ctx.n
-    words = B * primes * n
-    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_galois_sp(c0, c1, elt, out0, out1, primes=primes)
-    env["torch"].cuda.synchronize()
-    return take(out0, words, (B, primes, n), "galois_sp out0"), take(out1, words, (B, primes, n), "galois_sp out1")
-
-
-def rand_key(rng, q, n):
-    """One key half [np - 1][np][n] of random words below q_i."""
-    return np.stack([rand_slab(rng, q, 1, n)[0] for _ in range(len(q) - 1)])
-
-
-def edge_row(o, j, rng, elts):
-    """NTT form of natural-order coefficients that hold 0, 1, both sides of the centring boundary and q - 1, each of
-    them on at least one index whose image is negated and on one whose image is not, for every element of `elts`."""
-    n, q = o.n, o.q[j]
-    edges = np.array([0, 1, (q - 1) // 2, (q + 1) // 2, q - 1], dtype=np.uint32)
-    c = rng.integers(2, q - 1, n, dtype=np.uint32)
-    for start in (0, n // 2, n - 13):           # twice, 7 apart: an even and an odd index for every value
-        c[start:start + 5] = c[start + 7:start + 12] = edges
-    for g in elts:
-        _, neg = V.galois_image(n, g)
-        for v in edges:
-            at = c == v
-            assert (at & neg).any() and (at & ~neg).any(), (g, int(v))
-    row = o.ntt(c, j)
-    assert (o.intt(row, j) == c).all()
-    return row
-
-
-SP_CASES = [((4096, 3), (2, 1), 3), ((4096, 2), (1,), 3), ((16384, 13), (12,), 2)]
-CASE_IDS = lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v)  # noqa: E731
+    return guarded_pair(env, ctx.n, (c0.shape[0], primes, ctx.n), "lintrans_sp",
+                        lambda a, b: ctx.ct_lintrans_sp(plan, c0, c1, a, b, primes=primes))
 
 
 @pytest.fixture(scope="module")
@@ -105,7 +61,7 @@ def slab_cases(env):
         for L in levels:
             c0, c1 = rand_slab(rng, q, B, n, L), rand_slab(rng, q, B, n, L)
             for j in range(L):
-                c1[0, j] = edge_row(o, j, rng, [3, n + 1])     # 1 negates nothing, 2n - 1 everything but index 0
+                c1[0, j] = edge_row(o, j, rng, [3, n + 1], edges="centring")     # 1 negates nothing, 2n - 1 everything but index 0
             c0[1] = c1[1] = (np.array(q[:L], dtype=np.uint32) - 1)[:, None]
             slabs[L] = (c0, c1)
         cache[shape] = dict(o=o, ctx=ctx, elts=elts, keys={g: (gk0[k], gk1[k]) for k, g in enumerate(elts)},
@@ -233,16 +189,6 @@ def test_sum_sp_rounds_once(env):
 
 
 # ---- test 4: the linear transform -----------------------------------------------------------------------------------
-def edge_diagonals(rng, q, G, n):
-    """[G][np][n] arbitrary 32-bit words: random, with 0, 1, q_i - 1, q_i and 2^32 - 1 on every row, the row at the
-    special prime among them."""
-    d = rng.integers(0, 2 ** 32, (G, len(q), n), dtype=np.uint32)
-    for i, qi in enumerate(q):
-        d[:, i, 3:8] = [0, 1, qi - 1, qi, 2 ** 32 - 1]
-        d[:, i, n - 5:] = [2 ** 32 - 1, qi, qi - 1, 1, 0]
-    return d
-
-
 @pytest.mark.parametrize("shape,levels,B", SP_CASES, ids=CASE_IDS)
 def test_lintrans_sp_matches_the_definition(env, slab_cases, shape, levels, B):
     """Test 4: on the slabs and keys of test 1 (B = 2 at 16384 x 13), elements [3, n + 1, 3], diagonals of arbitrary
@@ -314,43 +260,24 @@ WINDOW = tuple(range(1, DIM))          # the moving sum and the matrix use the s
 IDENTITY_STEPS = (1, -3)
 
 
-def matrix():
-    """The example's fixed matrix: M[r][c] = ((7 r + 3 c + 1) mod 17 - 8) / 8, entries in [-1, 1]."""
-    r, c = np.meshgrid(np.arange(DIM), np.arange(DIM), indexing="ij")
-    return ((7 * r + 3 * c + 1) % 17 - 8) / 8.0
-
-
 def fill_keyed_case(env, case):
     """What keyed_cases (gpu_support) holds per shape beside the context and its secret key: the special-prime Galois
     keys of the steps 1 .. 7 and -3, installed; B = 4 fresh symmetric records with slot values in [-1, 1] and B = 4 with
     8-periodic slot values, both dropped to np - 1 primes by ct_drop_primes (equal to the slices)."""
-    ctx, sk, pkg, torch = case["ctx"], case["sk"], env["pkg"], env["torch"]
+    ctx = case["ctx"]
     n, npr, B = ctx.n, ctx.np, 4
-    L = npr - 1
     steps = WINDOW + (-3,)
-    elts = [pkg.galois_element(n, s) for s in steps]
-    assert elts == [pow(3, s % (n // 2), 2 * n) for s in steps]
-    G = len(elts)
-    gk0, gk1 = ctx.gen_galois_keys_sp(sk, elts, V.derive_seeds("sp-hoist-gk-a", G * L), V.derive_seeds("sp-hoist-gk-e", G * L))
-    ctx.set_galois_keys_sp(elts, gk0, gk1)
-    x8 = np.random.default_rng(7000 + n).uniform(-1.0, 1.0, (B, DIM))
-    sets = dict(unit=unit_values(B, n, 6000 + n), tiled=np.tile(x8, (1, n // 2 // DIM)).astype(np.float32))
+    elts = step_elements(env, n, steps)
+    gk0, gk1 = install_galois_keys(case, elts, "sp-hoist-gk", sp=True)
+    sets = dict(unit=unit_values(B, n, 6000 + n), tiled=periodic_values(B, n, DIM, 7000 + n))
     dropped = {}
     for k, (name, vals) in enumerate(sets.items()):
-        c0, c1, _, st = encrypt_sym(env, ctx, vals, first=400 + 16 * k)
-        assert bool((st == 1).all())
-        words = B * L * n
-        o0, o1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-        ctx.ct_drop_primes(c0, o0, c1, o1, primes_in=npr, primes_out=L)
-        torch.cuda.synchronize()
-        l0, l1 = take(o0, words, (B, L, n), "drop"), take(o1, words, (B, L, n), "drop")
-        assert (l0 == host_u32(c0)[:, :L]).all() and (l1 == host_u32(c1)[:, :L]).all()
-        dropped[name] = (l0, l1)
+        c0, c1 = fresh_records(env, ctx, vals, 400 + 16 * k)
+        dropped[name] = drop_records(env, ctx, c0, c1, npr - 1)
     case.update(key_of={s: (elts[k], (gk0[k], gk1[k])) for k, s in enumerate(steps)}, vals=sets, dropped=dropped)
 
 
 KEYED_SHAPES = [(4096, 3), (8192, 6)]
-SHAPE_IDS = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
 
 
 @pytest.mark.parametrize("shape", KEYED_SHAPES, ids=SHAPE_IDS)
@@ -404,26 +331,14 @@ def test_moving_sum_end_to_end_at_the_fresh_scale(env, keyed_cases, shape):
     L = npr - 1
     lo = Oracle(n, L)
     vals = c["vals"]["unit"]
-    B = vals.shape[0]
     l0, l1 = c["dropped"]["unit"]
     elts = [c["key_of"][s][0] for s in WINDOW]
     keys = [c["key_of"][s][1] for s in WINDOW]
     g0, g1 = run_sum_sp(env, ctx, dev_t(env, l0), dev_t(env, l1), elts, L, True)
     e0, e1, _ = hoist_sp_expect(o, l0, l1, elts, keys, w0=1)
     assert (g0 == e0).all() and (g1 == e1).all()
-    got = run_decrypt(env, ctx, dev_t(env, g0), dev_t(env, g1), L, o.scale)
-    worst = 0.0
-    for b in range(B):
-        e = expectation(lo, g0[b], g1[b], c["s_hat"][:L], o.scale)
-        assert e["status"] == 1
-        assert_matches(got, b, e, ("moving sum", b))
-        want = sum(np.roll(vals[b].astype(np.float64), -s) for s in (0,) + WINDOW)
-        err_e = float(np.abs(e["values"].astype(np.float64) - want).max())
-        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want).max())
-        print(f"record {b}: max |values - moving sum| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
-        assert err_e < 0.1 and err_g < 0.1, (b, err_e, err_g)
-        worst = max(worst, err_g)
-    print(f"{n} x {npr}, moving sum of 8 at the fresh scale: worst error {worst:.3e}")
+    want = sum(np.roll(vals.astype(np.float64), -s, axis=1) for s in (0,) + WINDOW)
+    check_level_decrypt(env, ctx, lo, g0, g1, c["s_hat"], L, o.scale, want, "moving sum of 8 at the fresh scale")
 
 
 @pytest.mark.parametrize("shape", KEYED_SHAPES, ids=SHAPE_IDS)
@@ -434,53 +349,27 @@ def test_matvec_end_to_end_without_a_lift(env, keyed_cases, shape):
     oracle's bit for bit, and the slots are within the reference's 0.1 of M x, on the expectation first.  The worst error
     is printed."""
     from oracle.pyoracle import Oracle
-    torch = env["torch"]
     c = keyed_cases(shape)
     ctx, o = c["ctx"], c["o"]
     n, npr = shape
     L = npr - 1
     lo, lo1 = Oracle(n, L), Oracle(n, L - 1)
     vals = c["vals"]["tiled"]
-    B = vals.shape[0]
     l0, l1 = c["dropped"]["tiled"]
     elts = [c["key_of"][s][0] for s in WINDOW]
     keys = [c["key_of"][s][1] for s in WINDOW]
-    M = matrix()
-    k = np.arange(n // 2)
-    dvals = np.stack([M[k % DIM, (k + e) % DIM] for e in range(DIM)]).astype(np.float32)
-    enc = sentinel_out(env, DIM * npr * n, 2 * n)
-    ctx.encode_ntt(dev_t(env, dvals), enc)
-    torch.cuda.synchronize()
-    ok, enc_want = o.encode_ntt_batch(dvals)
-    assert ok
-    diag = take(enc, DIM * npr * n, (DIM, npr, n), "encoded diagonals")
-    assert (diag == enc_want).all()
+    M = matrix(DIM)
+    diag = encode_diagonals(env, ctx, o, matrix_diagonals(M, n))
     t_diag = dev_t(env, diag)
     plan = ctx.lintrans_plan_sp(elts, t_diag[1:].contiguous(), t_diag[0].contiguous())
     g0, g1 = run_lintrans_sp(env, ctx, plan, dev_t(env, l0), dev_t(env, l1), L)
     plan.close()
     e0, e1, _ = hoist_sp_expect(o, l0, l1, elts, keys, diag[1:], diag[0])
     assert (g0 == e0).all() and (g1 == e1).all(), "plan call"
-    words = B * (L - 1) * n
-    s0, s1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_rescale(dev_t(env, g0), s0, dev_t(env, g1), s1, primes=L)
-    torch.cuda.synchronize()
-    f0, f1 = take(s0, words, (B, L - 1, n), "rescale"), take(s1, words, (B, L - 1, n), "rescale")
-    assert (f0 == rescale_expect(lo, g0)).all() and (f1 == rescale_expect(lo, g1)).all()
+    f0, f1 = rescale_records(env, ctx, lo, g0, g1, L)
     scale = o.scale * o.scale / o.q[L - 1]
-    got = run_decrypt(env, ctx, dev_t(env, f0), dev_t(env, f1), L - 1, scale)
     want_slots = np.tile(vals.astype(np.float64)[:, :DIM] @ M.T, (1, n // 2 // DIM))
-    worst = 0.0
-    for b in range(B):
-        e = expectation(lo1, f0[b], f1[b], c["s_hat"][:L - 1], scale)
-        assert e["status"] == 1
-        assert_matches(got, b, e, ("matvec", b))
-        err_e = float(np.abs(e["values"].astype(np.float64) - want_slots[b]).max())
-        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want_slots[b]).max())
-        print(f"record {b}: max |values - M x| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
-        assert err_e < 0.1 and err_g < 0.1, (b, err_e, err_g)
-        worst = max(worst, err_g)
-    print(f"{n} x {npr}, M x on fresh records: worst error {worst:.3e}")
+    check_level_decrypt(env, ctx, lo1, f0, f1, c["s_hat"], L - 1, scale, want_slots, "M x on fresh records")
 
 
 # ---- tests 6 and 7: installs, kinds and arguments -------------------------------------------------------------------
@@ -669,8 +558,4 @@ def test_matvec_fresh_example(env, tmp_path):
     """examples/matvec_fresh_roundtrip.c from plain gcc: encrypt, drop to np - 1, the diagonals of M encoded at Delta and
     folded into a special-prime plan, ONE se_amd_ct_lintrans_sp_device call, rescale and decrypt_level come back within the
     reference's 0.1 of M x."""
-    exe = build_example("matvec_fresh_roundtrip", tmp_path, hip=True, extra=("-lm",))
-    r = subprocess.run([str(exe), "4096", "3", "8"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search(r"failed=0 B=8 .*max_abs_error=([0-9.e+-]+)", r.stdout)
-    assert m and float(m.group(1)) < 0.1, r.stdout
+    run_example("matvec_fresh_roundtrip", tmp_path, ("4096", "3", "8"))

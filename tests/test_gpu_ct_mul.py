@@ -6,17 +6,17 @@ integers, never from the code under test; every comparison is bit-exact except t
 |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below
 Oracle(n, L): the default chains are prefixes of one another."""
 import ctypes as C
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (DIGIT_BITS, DIGIT_MASK, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches,  # noqa: F401
-                         build_example, centred, crt_centred, decode_expect, dev_t, digits_of, encrypt_sym, env,
-                         expectation, host_u32, keyed_cases, negacyclic, ntt_secret, rand_slab, relin_expect,
-                         rescale_expect, run_decrypt, same_bytes, sentinel_out, stream_of, take, unit_values)
+from ct_model import (DIGIT_MASK, SHAPE_IDS, crt_centred, digit_key_errors, digits_of, negacyclic, rand_slab,
+                      relin_diagonal, relin_expect)
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, check_level_decrypt,  # noqa: F401
+                         decode_expect, dev_t, encrypt_sym, env, expectation, fresh_records, keyed_cases, ntt_secret,
+                         rescale_records, run_decrypt, run_example, run_relin, same_bytes, sentinel_out, stream_of, take,
+                         unit_values)
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +54,7 @@ def run_tensor(env, ctx, a0, a1, b0, b1, ia=None, ib=None, primes=None):
     return np.stack([take(o, words, (P, L, n), "tensor") for o in outs]), st.cpu().numpy()
 
 
-@pytest.mark.parametrize("shape", [(1024, 1), (4096, 3), (16384, 13)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(1024, 1), (4096, 3), (16384, 13)], ids=SHAPE_IDS)
 def test_tensor_arbitrary_slabs(env, shape):
     """Test 1: Ba = 5, Bb = 3, record 3 of a and record 1 of b all q_j - 1.  Identity pairs (b padded to 5), an index list
     with a repeat, a = b for squares, primes = np - 1, and indices == Ba / 0xFFFFFFFF (status 2, zero rows, neighbours
@@ -239,7 +239,7 @@ def product_cases(env):
                 fa = o.ntt((m[a] % qj).astype(np.uint32), j).astype(np.uint64)
                 fb = o.ntt((m[b] % qj).astype(np.uint32), j).astype(np.uint64)
                 pts.append(o.intt(((fa * fb) % np.uint64(qj)).astype(np.uint32), j))
-            y = crt_centred(o, pts)
+            y = crt_centred(o.q, pts)
             assert max(abs(v) for v in y) < 2 ** 62, "shrink the value range: a product coefficient reaches 2^62"
             prods.append(np.array(y, dtype=np.int64))
         # the first product once more in plain integers (int64 convolution: every sum is below 2^62 by the assert)
@@ -252,7 +252,7 @@ def product_cases(env):
         c["ctx"].close()
 
 
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_decrypt3_exact_integer_identity(env, product_cases, shape):
     """Tests 2b and 2d: decrypt3_level(tensor(x, y), primes = np, scale = Delta^2).pte equals the negacyclic product of
     the two plaintexts m + e the encryptor reported, as integers; values_f64 / values equal the oracle's decode of that
@@ -330,14 +330,7 @@ def relin_seeds(npr, label):
     return V.derive_seeds(label + "-a", 2 * npr), V.derive_seeds(label + "-e", 2 * npr)
 
 
-def diagonal(o, s_hat, j, t):
-    """(2^(15 t) mod q_j) . s_hat_j^2 mod q_j, uint64 (every intermediate is below 2^60)."""
-    q = np.uint64(o.q[j])
-    s = s_hat[j].astype(np.uint64)
-    return (((s * s) % q) * np.uint64(pow(2, DIGIT_BITS * t, o.q[j]))) % q
-
-
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_relin_key_generation(env, shape):
     """Test 3: gen_relin_key equals gen_keys_batch(K = 2 np, this key replicated, the same seeds) plus the diagonal term
     computed from the oracle's NTT(s) in Python ints; the keys installed in the context are not touched; set_relin_key
@@ -357,7 +350,7 @@ def test_relin_key_generation(env, shape):
     exp0 = pk0.copy()
     for j in range(npr):
         for t in range(2):
-            exp0[2 * j + t, j] = (pk0[2 * j + t, j].astype(np.uint64) + diagonal(o, s_hat, j, t)) % np.uint64(o.q[j])
+            exp0[2 * j + t, j] = (pk0[2 * j + t, j].astype(np.uint64) + relin_diagonal(o, s_hat, j, t)) % np.uint64(o.q[j])
     assert (evk1 == pk1).all()
     assert (evk0 == exp0).all()
     assert (evk0 != pk0).any(axis=2).sum() == R            # exactly the diagonal columns changed
@@ -390,17 +383,6 @@ def test_relin_key_generation(env, shape):
 
 
 # ---- test 4: the relinearisation on arbitrary slabs and key words ---------------------------------------------------
-def run_relin(env, ctx, d0, d1, d2, primes):
-    """One call on device slabs [B][primes][n]; two rows of sentinels behind each output."""
-    torch = env["torch"]
-    B, n = d0.shape[0], ctx.n
-    words = B * primes * n
-    out0, out1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_relin(d0, d1, d2, out0, out1, primes=primes)
-    torch.cuda.synchronize()
-    return take(out0, words, (B, primes, n), "relin out0"), take(out1, words, (B, primes, n), "relin out1")
-
-
 def digit_edge_row(o, j, rng):
     """NTT form of natural-order coefficients that hold both sides of the digit boundary -- 0, 2^15 - 1, 2^15,
     2^15 + 1 -- and q - 1, beside random values."""
@@ -523,8 +505,7 @@ def fill_keyed_case(env, case):
     evk0, evk1 = ctx.gen_relin_key(sk, *relin_seeds(npr, "e2e"))
     ctx.set_relin_key(evk0, evk1)
     vals = unit_values(B, n, 2000 + n)
-    c0, c1, _, st = encrypt_sym(env, ctx, vals, first=160)
-    assert bool((st == 1).all())
+    c0, c1 = fresh_records(env, ctx, vals, 160)
     ia, ib = list(range(B)), [(b + 1) % B for b in range(B)]
     t, tst = run_tensor(env, ctx, c0, c1, c0, c1, ia, ib)
     assert (tst == 1).all()
@@ -532,29 +513,19 @@ def fill_keyed_case(env, case):
     case.update(evk0=evk0, evk1=evk1, vals=vals, ia=ia, ib=ib, tensor=t, relin=(r0, r1))
 
 
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_relin_exact_key_switch_identity(env, keyed_cases, shape):
     """Test 5: with y3 the oracle's centred degree-2 value of (d0, d1, d2), y2 the oracle expectation of the relinearised
     pair and e_r the key's errors recovered with the oracle (centred INTT of evk0 + evk1 . s_hat - diagonal),
     y2 - y3 == sum_r negacyclic(D_r, e_r) as integers, for every coefficient.  No model of the kernel enters."""
     c = keyed_cases(shape)
     o, s_hat, npr = c["o"], c["s_hat"], c["o"].np
-    errs = []
-    for r in range(2 * npr):
-        per_prime = []
-        for i in (0, npr - 1):
-            q = np.uint64(o.q[i])
-            v = o.decrypt(c["evk0"][r, i], c["evk1"][r, i], s_hat[i], i).astype(np.uint64)
-            if i == r // 2:
-                v = (v + q - diagonal(o, s_hat, i, r % 2)) % q
-            per_prime.append(centred(o.intt(v.astype(np.uint32), i), o.q[i]))
-        assert (per_prime[0] == per_prime[1]).all() and np.abs(per_prime[0]).max() <= 64, r    # one small integer e_r
-        errs.append(per_prime[0])
+    errs = digit_key_errors(o, c["evk0"], c["evk1"], s_hat, lambda j, t: relin_diagonal(o, s_hat, j, t))
     d0, d1, d2 = c["tensor"]
     for p in range(2):
         pts = [o.intt(o.decrypt(d0[p, j], o.decrypt(d1[p, j], d2[p, j], s_hat[j], j), s_hat[j], j), j)
                for j in range(npr)]
-        y3 = np.array(crt_centred(o, pts), dtype=object)
+        y3 = np.array(crt_centred(o.q, pts), dtype=object)
         e = expectation(o, c["relin"][0][p], c["relin"][1][p], s_hat)
         y2 = np.array(e["y"], dtype=object)
         D = digits_of(o, d2[p], npr)
@@ -565,7 +536,7 @@ def test_relin_exact_key_switch_identity(env, keyed_cases, shape):
         print(f"pair {p}: max |key-switch term| = {int(np.abs(ks).max())}")
 
 
-@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=SHAPE_IDS)
 def test_product_end_to_end(env, keyed_cases, shape):
     """Test 6: tensor -> relin -> rescale -> decrypt_level(primes = np - 1, scale = Delta^2 / q_last) on B = 4 pairs of
     records with slot values in [-1, 1]: every stage equals its definition, the final pte / values / values_f64 equal
@@ -581,37 +552,14 @@ def test_product_end_to_end(env, keyed_cases, shape):
     r0, r1 = c["relin"]
     e0, e1 = relin_expect(o, *(c["tensor"][k][:2] for k in range(3)), c["evk0"], c["evk1"])
     assert (r0[:2] == e0).all() and (r1[:2] == e1).all()
-    torch = env["torch"]
-    B = r0.shape[0]
-    words = B * (npr - 1) * n
-    s0, s1 = sentinel_out(env, words, 2 * n), sentinel_out(env, words, 2 * n)
-    ctx.ct_rescale(dev_t(env, r0), s0, dev_t(env, r1), s1, primes=npr)
-    torch.cuda.synchronize()
-    f0, f1 = take(s0, words, (B, npr - 1, n), "rescale"), take(s1, words, (B, npr - 1, n), "rescale")
-    assert (f0 == rescale_expect(o, r0)).all() and (f1 == rescale_expect(o, r1)).all()
+    f0, f1 = rescale_records(env, ctx, o, r0, r1, npr)
     scale = o.scale * o.scale / o.q[npr - 1]
-    got = run_decrypt(env, ctx, dev_t(env, f0), dev_t(env, f1), npr - 1, scale)
-    worst = 0.0
-    for b in range(B):
-        e = expectation(lo, f0[b], f1[b], c["s_hat"][:npr - 1], scale)
-        assert e["status"] == 1
-        assert_matches(got, b, e, b)
-        want = c["vals"][c["ia"][b]].astype(np.float64) * c["vals"][c["ib"][b]].astype(np.float64)
-        err_e = float(np.abs(e["values"].astype(np.float64) - want).max())
-        err_g = float(np.abs(got["values"][b].cpu().numpy().astype(np.float64) - want).max())
-        print(f"pair {b}: max |values - x.y| = {err_e:.3e} (expectation), {err_g:.3e} (GPU)")
-        assert err_e < 0.1 and err_g < 0.1, (b, err_e, err_g)
-        worst = max(worst, err_g)
-    print(f"{n} x {npr}: worst error {worst:.3e}")
-    assert worst < 0.1
+    v64 = c["vals"].astype(np.float64)
+    check_level_decrypt(env, ctx, lo, f0, f1, c["s_hat"], npr - 1, scale, v64[c["ia"]] * v64[c["ib"]], "x.y")
 
 
 # ---- test 7: the example --------------------------------------------------------------------------------------------
 def test_ct_product_example(env, tmp_path):
     """examples/ct_product_roundtrip.c from plain gcc: squares through the tensor, relin, a plain sum, rescale and
     decrypt_level come back within the reference's 0.1 of sum v^2."""
-    exe = build_example("ct_product_roundtrip", tmp_path, hip=True, extra=("-lm",))
-    r = subprocess.run([str(exe), "4096", "3", "16"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search(r"failed=0 B=16 .*max_abs_error=([0-9.e+-]+)", r.stdout)
-    assert m and float(m.group(1)) < 0.1, r.stdout
+    run_example("ct_product_roundtrip", tmp_path, ("4096", "3", "16"))

@@ -3,15 +3,13 @@ Every expectation is built from the oracle's primitives (decrypt, intt, fft) and
 under test; every comparison is bit-exact except the reference's own acceptance criterion |values - input| < 0.1
 (device/test/ckks_tests_common.c:132)."""
 import ctypes as C
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, build_example, dev_t,  # noqa: F401
-                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, stream_of)
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, dev_t, encrypt_sym, env,  # noqa: F401
+                         expectation, host_u32, ntt_secret, records, run_decrypt, run_example, stream_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -302,8 +300,4 @@ def test_full_size(env):
 
 def test_roundtrip_example(env, tmp_path):
     """examples/batch_roundtrip.c from plain gcc: values around +-1000 come back within the reference's 0.1."""
-    exe = build_example("batch_roundtrip", tmp_path, hip=True, extra=("-lm",))
-    r = subprocess.run([str(exe), "4096", "3", "16"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search(r"failed=0 B=16 .*max_abs_error=([0-9.e+-]+)", r.stdout)
-    assert m and float(m.group(1)) < 0.1, r.stdout
+    run_example("batch_roundtrip", tmp_path, ("4096", "3", "16"))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CPU simulation of the noise of a slot rotation: encrypt a record with slot values uniform in [-1, 1], apply the
 automorphism and its key switch with 15-bit digits as se_amd_ct_galois_device defines them, decrypt -- all with the
-oracle's primitives and Python / NumPy integers, no GPU.  The library has no special prime, so the key-switch term
+oracle's primitives and Python / NumPy integers (sigma on rows, the permutation table and the integer helpers are those of
+the tests' host model, tests/ct_model.py), no GPU.  The digit key switch has no special prime, so the key-switch term
   decrypt(out0, out1) = sigma(decrypt(c0, c1)) + sum_r D_r * e_r        (D_r: digits of sigma(c1), integers)
 is as large as the relinearisation's and a rotation belongs at a raised scale.  Prints one JSON line per parameter set:
 the bound 2 L n (2^15 - 1) E on a coefficient of the key-switch term (E = 21, the support of the error sampler), the
@@ -34,20 +35,12 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 from oracle import pyoracle  # noqa: E402
 import vectors as V  # noqa: E402
-from ct_mul_noise_sim import DIGIT_BITS, ERR_SUPPORT, centred, crt_centred, decode  # noqa: E402
+from ct_model import DIGIT_BITS, centred, crt_centred, sigma_rows, src_table  # noqa: E402
+from ct_mul_noise_sim import ERR_SUPPORT, decode  # noqa: E402
 
 LIFT = 1 << 30
 STEPS = (1, 2, 4, 8)
 WINDOW = tuple(range(1, 8))     # the hoisted sum of 8: the record and its rotations by 1 .. 7
-
-
-def sigma_coeff(a, g, q):
-    """x(X) -> x(X^g) on natural-order residues mod q: coefficient k goes to k g mod n, negated when k g mod 2n >= n."""
-    n = a.shape[0]
-    u = (np.arange(n, dtype=np.int64) * g) % (2 * n)
-    out = np.zeros_like(a)
-    out[u % n] = np.where(u >= n, (q - a.astype(np.int64)) % q, a).astype(a.dtype)
-    return out
 
 
 def sigma_int(y, g):
@@ -56,10 +49,6 @@ def sigma_int(y, g):
     out = np.zeros_like(y)
     out[u % n] = np.where(u >= n, -y, y)
     return out
-
-
-def sigma_rows(o, rows, g):
-    return [o.ntt(sigma_coeff(o.intt(rows[j], j), g, o.q[j]), j) for j in range(len(rows))]
 
 
 def galois_key(o, sk, s_hat, g, label):
@@ -99,19 +88,6 @@ def galois(o, c0, c1, g, key):
         out0.append(a0.astype(np.uint32))
         out1.append(a1.astype(np.uint32))
     return out0, out1
-
-
-def src_table(n, g):
-    """sigma_g(x)[k] = x[src[k]] on a bit-reversed NTT-form row (se_amd_galois_table)."""
-    bits = n.bit_length() - 1
-
-    def brev(v):
-        r = np.zeros_like(v)
-        for b in range(bits):
-            r |= ((v >> b) & 1) << (bits - 1 - b)
-        return r
-
-    return brev((((2 * brev(np.arange(n, dtype=np.int64)) + 1) * g) % (2 * n) - 1) // 2)
 
 
 def galois_hoisted(o, c0, c1, elts, keys):
@@ -155,7 +131,8 @@ def rescale(o, rows):
 def value(o, c0, c1, s_hat):
     """The centred integer c0 + c1 s over the primes of the rows."""
     L = len(c0)
-    return crt_centred(o.q[:L], [o.intt(o.decrypt(c0[j], c1[j], s_hat[j], j), j) for j in range(L)])
+    pts = [o.intt(o.decrypt(c0[j], c1[j], s_hat[j], j), j) for j in range(L)]
+    return np.array(crt_centred(o.q[:L], pts), dtype=object)
 
 
 def add_rows(o, a, b):

@@ -2,7 +2,7 @@
 """CPU simulation of the special-prime key switch (se_amd_ct_galois_sp_device, se_amd_ct_relin_sp_device): the last
 prime of the context, P, belongs to the key, a level-L record (L <= np - 1) is switched with one centred digit per data
 prime and the result is divided by P.  Everything is the oracle's primitives and Python / NumPy integers
-(tests/keyswitch_sp_support.py holds the definition), no GPU.
+(tests/ct_model.py holds the definition), no GPU.
   rotation: a fresh record dropped to level L, element 3 (one slot to the left), decoded at the fresh scale Delta with no
             lift and no rescale: the largest coefficient of the key-switch term y' - sigma(y) and the worst slot error
             against the rolled values;
@@ -12,8 +12,8 @@ prime and the result is divided by P.  Everything is the oracle's primitives and
 both with the centred digits of the definition and with canonical digits in [0, q_j) -- a digit of mean q/2 convolved
 with the key error is a random walk of that size, which is why the definition centres.  One JSON line per case, then
 the table.
-The hoisted forms (se_amd_ct_galois_sum_sp_device, se_amd_ct_lintrans_sp_device; tests/keyswitch_sp_hoist_support.py
-holds their definition), with --hoist:
+The hoisted forms (se_amd_ct_galois_sum_sp_device, se_amd_ct_lintrans_sp_device; hoist_sp_expect of tests/ct_model.py is
+their definition), with --hoist:
   moving_sum: a fresh record dropped to level L plus its rotations by the steps 1 .. G in ONE call, decoded at Delta;
   matvec:     the diagonal method on a dim x dim matrix with entries in [-1, 1], diagonals encoded at Delta, NO lift, one
               rescale, decoded at Delta^2 / q_{L-1};
@@ -30,10 +30,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 from oracle import pyoracle  # noqa: E402
 import vectors as V  # noqa: E402
-import keyswitch_sp_support as K  # noqa: E402
-import keyswitch_sp_hoist_support as H  # noqa: E402
+import ct_model as K  # noqa: E402
 from ct_galois_noise_sim import decode, matvec_matrix, mul_plain, rescale, sigma_int, value  # noqa: E402
-from ct_mul_noise_sim import crt_centred  # noqa: E402
 from ct_mul_noise_sim import mulmod  # noqa: E402
 
 DEFAULT = ("4096x3:2", "4096x3:1", "8192x6:5", "4096x2:1")
@@ -127,7 +125,7 @@ def moving_sum(n, npr, L, G):
     for st, g in zip(steps, elts):
         exact = exact + sigma_int(y_in, g)
         want = want + np.roll(vals.astype(np.float64), -st)
-    h0, h1, info = H.hoist_sp_expect(o, c0[None], c1[None], elts, keys, w0=1)
+    h0, h1, info = K.hoist_sp_expect(o, c0[None], c1[None], elts, keys, w0=1)
     s0, s1, r_single = c0, c1, np.zeros(n)
     for g, key in zip(elts, keys):
         r0, r1, delta = single_rotation(o, c0, c1, g, key)
@@ -170,9 +168,9 @@ def matvec(n, npr, L, dim=8):
         m = o.decrypt(c0[i], c1[i], s_hat[i], i).astype(np.uint64)
         acc = (diag[0, i].astype(np.uint64) * m) % np.uint64(q[i])
         for e, g in enumerate(elts):
-            acc = (acc + (diag[e + 1, i].astype(np.uint64) * m[H.src_table(n, g)]) % np.uint64(q[i])) % np.uint64(q[i])
+            acc = (acc + (diag[e + 1, i].astype(np.uint64) * m[K.src_table(n, g)]) % np.uint64(q[i])) % np.uint64(q[i])
         rows.append(o.intt(acc.astype(np.uint32), i))
-    exact = crt_centred(q[:L], rows)
+    exact = np.array(K.crt_centred(q[:L], rows), dtype=object)
     single0, single1 = np.stack(mul_plain(o, c0, diag[0])), np.stack(mul_plain(o, c1, diag[0]))
     r_single = np.zeros(n)
     for e, (g, key) in enumerate(zip(elts, keys)):
@@ -183,7 +181,7 @@ def matvec(n, npr, L, dim=8):
         full = np.convolve(rounding(o, delta, s_nat), d_nat)
         r_single = r_single + full[:n] - np.append(full[n:], 0.0)
     scale = o.scale * o.scale / q[L - 1]
-    h0, h1, info = H.hoist_sp_expect(o, c0[None], c1[None], elts, keys, diag[1:], diag[0])
+    h0, h1, info = K.hoist_sp_expect(o, c0[None], c1[None], elts, keys, diag[1:], diag[0])
     out = dict(rounding_rms=rms(rounding(o, info[0]["delta"], s_nat)), rounding_rms_single=rms(r_single))
     for name, (r0, r1) in (("", (h0[0], h1[0])), ("_single", (single0, single1))):
         out["key_switch_max" + name] = max(abs(int(v)) for v in value(o, list(r0), list(r1), s_hat) - exact)

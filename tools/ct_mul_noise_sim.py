@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CPU simulation of the noise of a ciphertext product: encrypt two records with slot values uniform in [-1, 1], tensor,
 relinearise with 15-bit digits, rescale, decrypt -- all with the oracle's primitives and Python / NumPy integers, no
-GPU.  Uses the exact identities the GPU tests assert:
+GPU; the integer helpers are those of the tests' host model, tests/ct_model.py.  Uses the exact identities the GPU tests
+assert:
   relin    decrypt(out0, out1) = decrypt3(d0, d1, d2) + sum_r D_r * e_r          (key-switch term, integers)
   rescale  q_last . y' + delta_0 + delta_1 * s = y                               (delta_k = centred last-prime rows)
 so only the last-prime column of the relinearised pair is formed.  Prints one JSON line per parameter set: the bound
@@ -20,34 +21,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from oracle import pyoracle  # noqa: E402
 import vectors as V  # noqa: E402
+from ct_model import DIGIT_BITS, centred, crt_centred, negacyclic  # noqa: E402
 
-DIGIT_BITS = 15
 ERR_SUPPORT = 21
-
-
-def centred(x, q):
-    x = x.astype(np.int64)
-    return np.where(x > q // 2, x - q, x)
-
-
-def negacyclic(a, s):
-    n = a.shape[0]
-    full = np.convolve(a, s)
-    res = full[:n].copy()
-    res[:n - 1] -= full[n:]
-    return res
-
-
-def crt_centred(q, pts):
-    Q = 1
-    for x in q:
-        Q *= x
-    acc = np.zeros(pts[0].shape[0], dtype=object)
-    for j, x in enumerate(q):
-        M = Q // x
-        acc = acc + pts[j].astype(object) * (M * pow(M % x, -1, x))
-    acc = acc % Q
-    return np.array([int(v) - Q if int(v) > Q // 2 else int(v) for v in acc], dtype=object)
 
 
 def decode(o, y, scale):
@@ -73,8 +49,8 @@ def simulate(n, L):
            np.uint64(q[j])).astype(np.uint32) for j in range(L)]
     d2 = [mulmod(x["c1"][j], y["c1"][j], q[j]) for j in range(L)]
     # the degree-2 value, as integers
-    y3 = crt_centred(q, [o.intt(o.decrypt(d0[j], o.decrypt(d1[j], d2[j], s_hat[j], j), s_hat[j], j), j)
-                         for j in range(L)])
+    y3 = np.array(crt_centred(q, [o.intt(o.decrypt(d0[j], o.decrypt(d1[j], d2[j], s_hat[j], j), s_hat[j], j), j)
+                                  for j in range(L)]), dtype=object)
     # digits, key rows (last-prime column only) and the key-switch term
     a_seeds, e_seeds = V.derive_seeds("sim-a", 2 * L), V.derive_seeds("sim-e", 2 * L)
     ks = np.zeros(n, dtype=np.int64)
