@@ -679,9 +679,8 @@ int se_amd_ct_drop_primes_device(se_amd_ctx *ctx, const uint32_t *d_in0, const u
  * memory (4096 x 3, G = 7: 3.4 MiB; 16384 x 13, G = 7: 286 MiB).  se_amd_lintrans_destroy serves both kinds of plan.
  * A plan has a kind: se_amd_ct_lintrans_device refuses a special-prime plan and se_amd_ct_lintrans_sp_device refuses a
  * digit plan, both with SE_ERR_INVALD_ARGUMENT and nothing written.
- * Out of scope: the MANY form on the special-prime key (each output needs its own delta and its own division by P, so
- * hoisting would save only the shared pass transforms), baby-step / giant-step plans on this key (the digit-key family
- * has them: se_amd_bsgs_create below), several special primes, custom chains, host-pointer and multi-device forms. */
+ * Beyond 64 diagonals: the baby-step / giant-step plans on this key (se_amd_bsgs_create_sp below), whose baby steps are
+ * the UNDIVIDED many form.  Out of scope: several special primes, custom chains, host-pointer and multi-device forms. */
 int se_amd_ct_galois_sum_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                    const uint32_t *elts /*host, [G]*/, size_t G, int add_input, uint32_t *d_out0,
                                    uint32_t *d_out1, void *stream);
@@ -742,8 +741,9 @@ int se_amd_ct_lintrans_sp_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, c
  * rows.  Every chunk size gives the same bits.  SE_ERR_INVALD_ARGUMENT for the pointer, alignment, level and B checks of
  * se_amd_ct_galois_device, a NULL plan, a plan of another context, primes above the plan's levels, a NULL workspace, one
  * that is not 16-byte aligned or one below one record.
- * Out of scope: the special-prime family (it has no many form for the baby steps), a one-division giant sum, sparse
- * diagonal masks, multi-device and host-pointer forms. */
+ * The special-prime family has its own plan kind (se_amd_bsgs_create_sp below); se_amd_ct_bsgs_device refuses such a
+ * plan with SE_ERR_INVALD_ARGUMENT and nothing written.  Out of scope: sparse diagonal masks, multi-device and
+ * host-pointer forms. */
 int se_amd_ct_mul_plain_sum_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
                                    size_t E, size_t B, size_t primes, const uint32_t *d_pt, size_t Gout, size_t pt_primes,
                                    uint32_t *d_out0, uint32_t *d_out1 /* NULL with d_in1 */, void *stream);
@@ -759,6 +759,72 @@ size_t se_amd_bsgs_workspace_bytes(const se_amd_bsgs *plan, size_t records, size
 int se_amd_ct_bsgs_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
                           size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes,
                           void *stream);
+/* ---- baby-step / giant-step linear transforms on the special-prime keys, division by P deferred ----------
+ * The plans above meet fresh records only after a lift; the special-prime linear transform ends at 64 diagonals.  Here
+ * the baby steps stay UNDIVIDED, as residues modulo q_0 .. q_{L-1}, P: the diagonals are multiplied in there, their row at
+ * P included, every giant step's inner sum is divided by P once and the giant steps share ONE more division: n2 + 1
+ * roundings for n1 . n2 diagonals, at the record's own scale, no lift, no level spent.  Notation of the special-prime
+ * block: p = np - 1, P = q_p, L = primes in [1, np - 1], E = {0 .. L-1, p}, centred(x, q) in (-q/2, q/2], src_e =
+ * se_amd_galois_table(elts[e]), (k0^e, k1^e) the installed SPECIAL-PRIME Galois key of elts[e] (an installed digit key
+ * does not serve).  An EXTENDED record is [L + 1][n] words per half: rows r < L modulo q_r, row L modulo P, NTT form,
+ * bit-reversed, canonical: "P times a ciphertext plus a key-switch sum", not decryptable until it is brought down.
+ * Conventions are those above: 16-byte aligned device pointers; asynchronous on `stream`; outputs do not overlap inputs;
+ * nothing is launched or written on an error; B = 0 (count = 0) is a successful no-op.  Every step is exact modular
+ * arithmetic or a centred rounding: every bit is fixed.  Every entry returns SE_ERR_INVALD_ARGUMENT on a one-prime
+ * context, for a NULL slab, primes outside [1, np - 1], a pointer that is not 16-byte aligned, B at or above 2^32.
+ * se_amd_ct_galois_many_ext_sp_device: (d_c0, d_c1) [B][L][n], elts HOST [G], 1 <= G <= 64, odd, below 2n -> (d_out0,
+ * d_out1) [G][B][L+1][n].  The digits are those of c1 itself, taken once:
+ *     D_j = centred(INTT_j(c1[b][j]), q_j), j < L;   F_{j,i} = NTT_i(D_j mod q_i), i in E   (F_{j,j} is c1[b][j] as it lies)
+ *     U^e_k[i][x] = sum_{j<L} F_{j,i}[src_e(x)] . k_k^e[j][i][x]   mod q_i
+ *     out0[e][b][r] = U^e_0[i_r] + [r < L] (P mod q_r) . c0[b][r][src_e(x)];   out1[e][b][r] = U^e_1[i_r]   (i_r = r, or p for r = L)
+ *     elts[e] == 1: out_k[e][b][r] = (P mod q_r) . c_k[b][r] for r < L, row L all zero; no key needed.
+ * G . B below 2^32.  SE_ERR_NO_KEY names the element other than 1 without a special-prime key.
+ * se_amd_ct_mul_plain_sum_ext_sp_device: se_amd_ct_mul_plain_sum_device on stacks of extended records, in [E][B][L+1][n],
+ * out [Gout][B][L+1][n]; row r < L uses q_r and plaintext row r, row L uses P and plaintext row p; plaintexts
+ * [Gout][E][np][n], ALL np rows, any 32-bit words.  At L = np - 1 it is bit for bit the plain entry with primes = np.
+ * se_amd_ct_mod_down_sp_device: [count][L+1][n] -> [count][L][n] on one slab (d_in1 = d_out1 = NULL) or two,
+ *     delta = centred(INTT_p(in[L]), P);   out[i] = (in[i] - NTT_i(delta mod q_i)) . P^-1 mod q_i,
+ * the rescale's map with P as the dropped prime and the constants of se_amd_rescale_constants(degree, np, ..).  At L =
+ * np - 1 it is bit for bit se_amd_ct_rescale_device with primes = np.  count at most 2^31 - 1.
+ * se_amd_ct_galois_accum_sp_device: the one-division giant sum of G DIFFERENT level-L ciphertexts (a^g, b^g) = in[g][b],
+ * in [G][B][L][n], out [B][L][n]:
+ *     keyed g (elts[g] != 1):  D^g_j = centred(INTT_j(sigma_g(b^g[j])), q_j)          (the digits of se_amd_ct_galois_sp_device)
+ *     ACC_k[i] = sum_{keyed g} sum_{j<L} NTT_i(D^g_j mod q_i) . k_k^g[j][i],  i in E
+ *     delta_k = centred(INTT_p(ACC_k[p]), P);   ks_k[i] = (ACC_k[i] - NTT_i(delta_k mod q_i)) . P^-1
+ *     out0[i] = ks_0[i] + sum_{keyed g} sigma_g(a^g)[i] + sum_{elts[g]==1} a^g[i];   out1[i] = ks_1[i] + sum_{elts[g]==1} b^g[i].
+ * With G = 1 it has the bytes of se_amd_ct_galois_sp_device; with G >= 2 it does NOT equal the sum of single calls: it
+ * rounds once.  G . B below 2^32; SE_ERR_NO_KEY as above.
+ * The plan.  se_amd_bsgs_create_sp takes the arguments of se_amd_bsgs_create and pre-rotates the same way, but pt_primes
+ * must equal np (the row at P enters the sum) and the plan serves the levels 1 .. np - 1.  It holds diagonals only; keys
+ * are read at CALL time.  A plan has a kind: each call entry refuses the other kind with SE_ERR_INVALD_ARGUMENT and
+ * writes nothing; se_amd_bsgs_destroy and se_amd_bsgs_workspace_bytes serve both.  se_amd_ct_bsgs_sp_device has the
+ * argument list of se_amd_ct_bsgs_device and is fixed bit for bit as
+ *     U[b] = many_ext(c; baby[b])                          [n1][Bc][L+1][n]
+ *     V[g] = sum_b d'[g][b] . U[b]   on the rows E          [n2][Bc][L+1][n]
+ *     W[g] = mod_down(V[g])                                 [n2][Bc][L][n]
+ *     out  = accum_sp(W; giant)                             scale Delta . Delta_d, level L.
+ * Workspace: the caller's, in stream order; no context scratch, no hidden allocation, no host synchronisation.  One record
+ * needs 2 . ((n1 + n2) . (L + 1) + n2 . L) . n . 4 bytes (both halves of U, V and W; W does not overlay U);
+ * se_amd_bsgs_workspace_bytes returns records times that.  The batch is walked in chunks of Bc = min(B, workspace_bytes /
+ * per-record) records and every chunk size gives the same bits. */
+int se_amd_ct_galois_many_ext_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                        size_t primes, const uint32_t *elts /*host, [G]*/, size_t G, uint32_t *d_out0,
+                                        uint32_t *d_out1, void *stream);
+int se_amd_ct_mul_plain_sum_ext_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
+                                          size_t E, size_t B, size_t primes, const uint32_t *d_pt, size_t Gout,
+                                          uint32_t *d_out0, uint32_t *d_out1 /* NULL with d_in1 */, void *stream);
+int se_amd_ct_mod_down_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1 /* NULL: one slab */,
+                                 size_t count, size_t primes, uint32_t *d_out0, uint32_t *d_out1 /* NULL with d_in1 */,
+                                 void *stream);
+int se_amd_ct_galois_accum_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B,
+                                     size_t primes, const uint32_t *elts /*host, [G]*/, size_t G, uint32_t *d_out0,
+                                     uint32_t *d_out1, void *stream);
+int se_amd_bsgs_create_sp(se_amd_ctx *ctx, const uint32_t *baby /*host, [n1]*/, size_t n1,
+                          const uint32_t *giant /*host, [n2]*/, size_t n2,
+                          const uint32_t *d_diag /*device, [n2][n1][np][n]*/, size_t pt_primes, se_amd_bsgs **out);
+int se_amd_ct_bsgs_sp_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                             size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

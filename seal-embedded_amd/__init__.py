@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_ct_galois_sum_sp_device", "se_amd_lintrans_create_sp", "se_amd_ct_lintrans_sp_device",
     "se_amd_ct_mul_plain_sum_device", "se_amd_ct_galois_accum_device", "se_amd_bsgs_create", "se_amd_bsgs_destroy",
     "se_amd_bsgs_workspace_bytes", "se_amd_ct_bsgs_device",
+    "se_amd_ct_galois_many_ext_sp_device", "se_amd_ct_mul_plain_sum_ext_sp_device", "se_amd_ct_mod_down_sp_device",
+    "se_amd_ct_galois_accum_sp_device", "se_amd_bsgs_create_sp", "se_amd_ct_bsgs_sp_device",
 )
 
 
@@ -195,6 +197,12 @@ def lib():
     L.se_amd_bsgs_workspace_bytes.argtypes = [vp, sz, sz]
     L.se_amd_bsgs_workspace_bytes.restype = sz
     L.se_amd_ct_bsgs_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp]
+    L.se_amd_ct_galois_many_ext_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
+    L.se_amd_ct_mul_plain_sum_ext_sp_device.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp]
+    L.se_amd_ct_mod_down_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    L.se_amd_ct_galois_accum_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
+    L.se_amd_bsgs_create_sp.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp)]
+    L.se_amd_ct_bsgs_sp_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp]
     _lib = L
     return L
 
@@ -928,6 +936,77 @@ class Context:
         _check(self.L.se_amd_ct_bsgs_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
                                             c0.shape[0], primes, _ptr(out0), _ptr(out1), _ptr(workspace),
                                             workspace_bytes, _stream_ptr()), "se_amd_ct_bsgs_device")
+
+    # ---- baby-step / giant-step linear transforms on the special-prime keys, division by P deferred
+    def ct_galois_many_ext_sp(self, c0, c1, elts, out0, out1, primes=None):
+        """The undivided baby steps: records (c0, c1) [B][L][n], L <= np - 1 -> extended records [G][B][L+1][n] (rows r <
+        L modulo q_r, row L modulo the special prime), out[e] = P times the rotation by elts[e] plus its key-switch sum,
+        from ONE decomposition of c1 under the installed special-prime keys.  Element 1 needs no key.  ct_mod_down_sp
+        of out[e] is ct_galois_sp by elts[e]."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_galois_many_ext_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el),
+                                                          el.size, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_galois_many_ext_sp_device")
+
+    def ct_mul_plain_sum_ext_sp(self, in0, pt, out0, in1=None, out1=None, primes=None):
+        """ct_mul_plain_sum on stacks of extended records: in [E][B][L+1][n], pt [Gout][E][np][n] (all np rows: row L of
+        a record meets the plaintext's row at the special prime), out [Gout][B][L+1][n].  primes = L."""
+        E, B = in0.shape[0], in0.shape[1]
+        if primes is None:
+            primes = in0.shape[2] - 1
+        _check(self.L.se_amd_ct_mul_plain_sum_ext_sp_device(self.h, _ptr(in0), _ptr(in1), E, B, primes, _ptr(pt),
+                                                            pt.shape[0], _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_mul_plain_sum_ext_sp_device")
+
+    def ct_mod_down_sp(self, in0, out0, in1=None, out1=None, primes=None, count=None):
+        """The division by the special prime, rounded: extended records [..][L+1][n] (one slab or two) -> [..][L][n].
+        count defaults to the product of the leading dimensions, primes = L to in0.shape[-2] - 1."""
+        if primes is None:
+            primes = in0.shape[-2] - 1
+        if count is None:
+            count = in0.numel() // (in0.shape[-2] * in0.shape[-1])
+        _check(self.L.se_amd_ct_mod_down_sp_device(self.h, _ptr(in0), _ptr(in1), count, primes, _ptr(out0), _ptr(out1),
+                                                   _stream_ptr()), "se_amd_ct_mod_down_sp_device")
+
+    def ct_galois_accum_sp(self, in0, in1, elts, out0, out1, primes=None):
+        """Rotate G different records under the special-prime keys and add, with ONE division by the special prime: in
+        [G][B][L][n] -> [B][L][n].  Element 1 is the identity.  G = 1 has the bytes of ct_galois_sp; G >= 2 rounds once
+        where G calls round G times."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = in0.shape[2]
+        _check(self.L.se_amd_ct_galois_accum_sp_device(self.h, _ptr(in0), _ptr(in1), in0.shape[1], primes, _ptr(el),
+                                                       el.size, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_galois_accum_sp_device")
+
+    def bsgs_plan_sp(self, baby, giant, diag, pt_primes=None):
+        """bsgs_plan for ct_bsgs_sp: diag [n2][n1][np][n] with ALL np rows.  Diagonals only; the special-prime keys are
+        read at call time.  The plan serves the levels 1 .. np - 1."""
+        import numpy as np
+        bs = np.ascontiguousarray(baby, dtype=np.uint32).reshape(-1)
+        gs = np.ascontiguousarray(giant, dtype=np.uint32).reshape(-1)
+        if pt_primes is None:
+            pt_primes = diag.shape[2]
+        h = C.c_void_p()
+        _check(self.L.se_amd_bsgs_create_sp(self.h, _ptr(bs), bs.size, _ptr(gs), gs.size, _ptr(diag), pt_primes,
+                                            C.byref(h)), "se_amd_bsgs_create_sp")
+        return BsgsPlan(self.L, h)
+
+    def ct_bsgs_sp(self, plan, c0, c1, out0, out1, workspace, primes=None, workspace_bytes=None):
+        """The special-prime plan's transform of fresh records (c0, c1) [B][L][n], L <= np - 1 -> [B][L][n] at the
+        record's scale times the diagonals': ct_galois_many_ext_sp, ct_mul_plain_sum_ext_sp, ct_mod_down_sp,
+        ct_galois_accum_sp in chunks of what `workspace` holds.  Every chunk size gives the same bits."""
+        if primes is None:
+            primes = c0.shape[1]
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+        _check(self.L.se_amd_ct_bsgs_sp_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
+                                               c0.shape[0], primes, _ptr(out0), _ptr(out1), _ptr(workspace),
+                                               workspace_bytes, _stream_ptr()), "se_amd_ct_bsgs_sp_device")
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

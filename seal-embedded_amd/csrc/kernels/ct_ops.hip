@@ -8,7 +8,10 @@
 // special-prime key switch that relinearises and rotates at the record's own scale (se_amd_ct_relin_sp_device,
 // se_amd_ct_galois_sp_device, behind k_ct_galois), and the two device steps of a baby-step / giant-step transform: the
 // plaintext-weighted sum over a stack of batches and the rotate-and-accumulate over different records
-// (se_amd_ct_mul_plain_sum_device, se_amd_ct_galois_accum_device, se_amd_ct_bsgs_device, behind the special-prime hoist).
+// (se_amd_ct_mul_plain_sum_device, se_amd_ct_galois_accum_device, se_amd_ct_bsgs_device, behind the special-prime hoist),
+// and the same transform on the special-prime keys with the division by P deferred: undivided baby steps, the division of
+// extended records and the one-division giant sum (se_amd_ct_galois_many_ext_sp_device, se_amd_ct_mod_down_sp_device,
+// se_amd_ct_galois_accum_sp_device, se_amd_ct_bsgs_sp_device, between the two).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -417,6 +420,60 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_rescale(const D
     }
 }
 
+// The division by the special prime of extended records (se_amd_ct_mod_down_sp_device): k_ct_rescale on records of L + 1
+// rows whose last row is modulo P = q_drop (A.drop = np - 1) instead of q_last; the lower rows, |delta| < P / 2 < q_j and
+// the constants R (level np) are the rescale's.  At L = np - 1 the row map is the identity and the bits are the rescale's.
+// A sibling with the body written out, not a shared inline: as one, k_ct_rescale<10> and <13> took one more register each
+// and <12> seven fewer, and the rows of the rescale are to stay as they are.
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_mod_down_sp(const DevParams P, const DevTables T,
+                                                                          const RescaleParams R, const RescaleArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds       = reinterpret_cast<uint32_t *>(smem);
+    const int t         = threadIdx.x;
+    const size_t b      = blockIdx.x;
+    const uint32_t last = A.primes - 1;
+    const uint32_t lp   = A.drop;   // the prime of row `last`
+    const uint32_t *in  = (blockIdx.y ? A.in1 : A.in0) + b * A.primes * N;
+    uint32_t *out       = (blockIdx.y ? A.out1 : A.out0) + b * last * N;
+
+    int32_t delta[16];
+    {
+        const uint32_t q = P.q[lp];
+        uint32_t x[16];
+        load_quads(x, in + (size_t)last * N, t);
+        quads_to_tile<16>(x, lds, t);
+        __syncthreads();
+        intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * lp, q, lds, t);
+        const uint32_t inv_n = P.inv_n[lp], inv_n_sh = P.inv_n_sh[lp];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+            delta[e] = (int32_t)centred_lift(csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, q), q), q);
+    }
+    for (uint32_t j = 0; j < last; j++)
+    {
+        const uint32_t q = P.q[j], two_q = q << 1;
+        uint32_t c[16], x[16];
+        load_quads(c, in + (size_t)j * N, t);
+#pragma unroll
+        for (int e = 0; e < 16; e++) x[e] = (uint32_t)delta[e] + ((uint32_t)(delta[e] >> 31) & q);   // [0, q)
+        ntt_tiles<LOGN>(x, T.ntt_rw + 2 * xform_table_len(N) * j, q, lds, t);
+        tile_to_quads<16>(x, lds, t);
+        const uint32_t w = R.inv[j], wp = R.inv_sh[j];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            const uint32_t u = min(x[e], x[e] - two_q);                          // NTT output [0, 4q) -> [0, 2q)
+            x[e]             = csub(mul_shoup_lazy(c[e] + two_q - u, w, wp, q), q);  // c - u + 2q in (0, 3q)
+        }
+        store_quads(out + (size_t)j * N, x, t);
+        __syncthreads();
+    }
+}
+
 hipError_t launch_ct_rescale(const DevParams &P, const DevTables &T, const RescaleParams &R, const RescaleArgs &A,
                              size_t B, hipStream_t st)
 {
@@ -425,6 +482,20 @@ hipError_t launch_ct_rescale(const DevParams &P, const DevTables &T, const Resca
         constexpr int L = decltype(l)::value;
         using G         = XformGeom<L>;
         return launch(k_ct_rescale<L>, dim3((unsigned)B, A.in1 ? 2 : 1), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, R, A);
+    });
+}
+
+// LOGN 12 .. 14 only, by the rule of launch_ct_key_switch_sp.
+hipError_t launch_ct_mod_down_sp(const DevParams &P, const DevTables &T, const RescaleParams &R, const RescaleArgs &A,
+                                 size_t B, hipStream_t st)
+{
+    if (B == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        return launch(k_ct_mod_down_sp<L>, dim3((unsigned)B, A.in1 ? 2 : 1), dim3(G::THREADS),
                       (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, R, A);
     });
 }
@@ -1546,6 +1617,251 @@ hipError_t launch_ct_hoist_sp(const DevParams &P, const DevTables &T, const Resc
 }
 
 // ------------------------------------------------------------------------------------------
+// Baby-step / giant-step transforms on the special-prime keys (se_amd_ct_bsgs_sp_device): the division by P is DEFERRED.
+// The baby steps leave extended records -- L + 1 rows, the last one modulo P: "P times the rotated ciphertext plus the
+// key-switch sum", undivided -- the diagonals are multiplied in on all L + 1 rows (k_ct_mul_plain_sum with the row map),
+// every giant step's inner sum is divided once (k_ct_mod_down_sp) and the giant steps share one more division
+// (k_ct_galois_accum_sp): n2 + 1 roundings for n1 n2 diagonals.
+//
+// k_ct_galois_many_ext_sp: out[e][b] = the undivided rotation of record b by elt[e], from ONE decomposition of c1 (the
+// digits D_j of ct_hoist_sp).  One workgroup of n/16 threads per (record, row r of the extended record); row r < L works
+// modulo q_r against key column r, row L modulo P against key column p = np - 1: ONE pass of ct_hoist_sp's two, no delta.
+//   per j < L: sp_park_digit (row j == r < L enters as it lies: park_row_quads) -> barrier -> per element of the group
+//     hoist_mac against row j, column i_r of that element's block -> barrier;
+//   epilogue, r < L: the c0 row parked once and gathered per element, (P mod q_r) . sigma_e(c0) by barrett64 (exact on any
+//     64-bit word) added to the canonical accumulator.  Element 1: no key, no product; out_k = (P mod q_r) . c_k, row L zero.
+// The elements are taken in groups of kManyExtGroup accumulator pairs per pass over the rows, as k_ct_galois_hoist<., false>
+// does: ceil(G / kManyExtGroup) times 2 (L - 1) transforms on a row r < L and 2 L on row L, 2 L^2 per record and group.
+// Lazy ranges: those of evk_mac -- an accumulator starts at 0 and is back in [0, 2 q) after every product, the parked words
+// are the lazy NTT output in [0, 4 q) resp. any 32-bit word of the slab; one csub canonicalises.  (P mod q_r) . c < 2^62.
+// Addresses: as in k_ct_galois_hoist (formed from the checked elements only, masked to [0, n)).
+// grid evk_grid(B, L + 1).
+// ------------------------------------------------------------------------------------------
+constexpr int kManyExtGroup = kHoistGroup;
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_many_ext_sp(const DevParams P, const DevTables T,
+                                                                                 const GaloisManyExtSpArgs A)
+{
+    using G          = XformGeom<LOGN>;
+    constexpr int N  = G::N;
+    constexpr int GC = kManyExtGroup;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t r   = blockIdx.y;                       // row of the extended record
+    const bool data    = r < A.primes;
+    const uint32_t col = data ? r : A.np - 1;              // its prime and key column
+    const uint32_t q = P.q[col], cr_hi = P.cr_hi[col], cr_lo = P.cr_lo[col];
+    const uint32_t pm  = data ? P.q[A.np - 1] % q : 0u;    // P mod q_r
+    const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * col;
+    const size_t rows  = (size_t)A.primes + 1;
+    const uint32_t groups = (A.G + GC - 1) / GC;
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        const size_t rec = b * A.primes * N;
+        for (uint32_t grp = 0; grp < groups; grp++)
+        {
+            const uint32_t e0 = grp * GC;
+            uint32_t acc0[GC][16], acc1[GC][16];
+#pragma unroll
+            for (int u = 0; u < GC; u++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc0[u][e] = acc1[u][e] = 0;
+            for (uint32_t j = 0; j < A.primes; j++)
+            {
+                const int td = opaque_index(t);
+                if (j == r)
+                {
+                    uint32_t y[16];
+                    load_quads(y, A.c1 + rec + (size_t)j * N, td);
+                    park_row_quads(y, lds, quad_index(td, 0));
+                }
+                else
+                    sp_park_digit<LOGN>(A.c1 + rec + (size_t)j * N, j, q, rw, P, T, lds, td, t);
+                __syncthreads();
+                const size_t ko   = ((size_t)j * A.np + col) * 2 * N + quad_index(td, 0);
+                const uint32_t r4 = __brev((uint32_t)quad_index(td, 0)) >> (32 - LOGN);
+#pragma unroll
+                for (int u = 0; u < GC; u++)
+                    if (e0 + u < A.G && A.elt[e0 + u] != 1)
+                        hoist_mac<LOGN>(acc0[u], acc1[u], lds, A.key[e0 + u] + ko, A.half, A.elt[e0 + u], r4, q);
+                __syncthreads();
+            }
+            const int te      = opaque_index(t);
+            const int k4      = quad_index(te, 0);
+            const uint32_t r4 = __brev((uint32_t)k4) >> (32 - LOGN);
+            if (data)
+            {
+                uint32_t c[16];
+                load_quads(c, A.c0 + rec + (size_t)r * N, te);
+                park_row_quads(c, lds, k4);
+                __syncthreads();
+            }
+#pragma unroll
+            for (int u = 0; u < GC; u++)
+                if (e0 + u < A.G)
+                {
+                    const uint32_t g = A.elt[e0 + u], u0 = (2 * r4 + 1) * g;
+                    const size_t og  = (((size_t)(e0 + u) * A.B + b) * rows + r) * N;
+#pragma unroll
+                    for (int e = 0; e < 16; e++)
+                    {
+                        acc0[u][e] = csub(acc0[u][e], q);
+                        acc1[u][e] = csub(acc1[u][e], q);
+                    }
+                    if (data)
+                    {
+#pragma unroll
+                        for (int e = 0; e < 16; e++)
+                        {
+                            const uint32_t w = hoist_word<LOGN>(lds, u0, g, e >> 2, e & 3);
+                            acc0[u][e] = csub(acc0[u][e] + barrett64((uint64_t)w * pm, q, cr_hi, cr_lo), q);
+                        }
+                        if (g == 1)
+                        {
+                            // the record itself: the accumulators are 0, out1 = (P mod q_r) . c1
+                            uint32_t c[16];
+                            load_quads(c, A.c1 + rec + (size_t)r * N, te);
+#pragma unroll
+                            for (int e = 0; e < 16; e++) acc1[u][e] = barrett64((uint64_t)c[e] * pm, q, cr_hi, cr_lo);
+                        }
+                    }
+                    store_quads(A.out0 + og, acc0[u], te);
+                    store_quads(A.out1 + og, acc1[u], te);
+                }
+            __syncthreads();   // the next pass's first transpose writes the plane the gather reads
+        }
+    }
+}
+
+// LOGN 12 .. 14 only, by the rule of launch_ct_key_switch_sp.
+hipError_t launch_ct_galois_many_ext_sp(const DevParams &P, const DevTables &T, const GaloisManyExtSpArgs &A,
+                                        hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        return launch(k_ct_galois_many_ext_sp<L>, evk_grid(A.B, A.primes + 1), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// k_ct_galois_accum_sp: the giant steps with ONE division by P.  G DIFFERENT level-L records (a^g, b^g) = in[g][b] are
+// rotated by elt[g] under the special-prime keys and added.  It is ct_key_switch_sp<., true> -- the same grid, thread shape,
+// two passes, sp_row_digit, evk_mac, sp_delta, lazy ranges -- with the element loop of k_ct_galois_accum inside each pass:
+// ONE accumulator pair takes the products of every keyed element (evk_mac leaves it in [0, 2 q) whichever block a product
+// came from), so there is one delta and one rounding centred(sum_g acc^g[p]) where G calls of k_ct_galois_sp round G times.
+// The exact addends -- sigma_g(a^g) of a keyed element (load_row_sigma), both rows of an element 1 as they lie -- join the
+// canonical ks_k AFTER the division.  Without a keyed element the accumulators stay 0, delta is 0 and ks is 0.
+// G (4 L - 2) + 4 transforms per workgroup for G keyed elements, against G (4 L + 2) of G single rotations.
+// Addresses: as in k_ct_galois (formed from the checked elements only, masked to [0, n)).
+// grid evk_grid(B, L).
+// ------------------------------------------------------------------------------------------
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum_sp(const DevParams P, const DevTables T,
+                                                                              const RescaleParams R,
+                                                                              const GaloisAccumSpArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t sp  = A.np - 1;
+    const uint32_t qi  = P.q[i];
+
+    for (size_t b = blockIdx.x; b < A.B; b += gridDim.x)
+    {
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        // pass 0: modulo P against key column p; pass 1: modulo q_i against key column i.  One body for both.
+#pragma unroll 1
+        for (uint32_t pass = 0; pass < 2; pass++)
+        {
+            const uint32_t col = pass ? i : sp;
+            const uint32_t q   = P.q[col];
+            const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * col;
+#pragma unroll 1
+            for (uint32_t s = 0; s < A.G; s++)
+            {
+                const uint32_t g = A.elt[s];
+                if (g == 1) continue;
+                const uint32_t *sw = A.in1 + ((size_t)s * A.B + b) * A.primes * N;
+                for (uint32_t j = 0; j < A.primes; j++)
+                {
+                    uint32_t y[16];
+                    if (pass && j == i)
+                        load_row_sigma<LOGN, true>(y, sw + (size_t)i * N, g, lds, opaque_index(t));
+                    else
+                        sp_row_digit<LOGN, true>(y, sw + (size_t)j * N, j, g, q, rw, P, T, lds, t);
+                    const uint32_t *key = A.key[s] + ((size_t)j * A.np + col) * 2 * N + quad_index(opaque_index(t), 0);
+                    evk_mac<LOGN>(acc0, acc1, y, key, A.half, q);
+                    __syncthreads();
+                }
+            }
+            if (pass == 0) sp_delta<LOGN>(acc0, acc1, i, sp, P, T, lds, t);
+        }
+        // ks_k = acc_k . P^-1, canonical; then the exact addends
+        const uint32_t w = R.inv[i], wp = R.inv_sh[i];
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+        {
+            acc0[e] = csub(mul_shoup_lazy(acc0[e], w, wp, qi), qi);
+            acc1[e] = csub(mul_shoup_lazy(acc1[e], w, wp, qi), qi);
+        }
+#pragma unroll 1
+        for (uint32_t s = 0; s < A.G; s++)
+        {
+            const uint32_t g = A.elt[s];
+            const int te     = opaque_index(t);
+            const size_t o   = (((size_t)s * A.B + b) * A.primes + i) * N;
+            uint32_t c[16];
+            if (g != 1)
+            {
+                load_row_sigma<LOGN, true>(c, A.in0 + o, g, lds, te);
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc0[e] = csub(acc0[e] + c[e], qi);
+                __syncthreads();   // the next park writes the plane the gather reads
+            }
+            else
+            {
+                load_quads(c, A.in0 + o, te);
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc0[e] = csub(acc0[e] + c[e], qi);
+                load_quads(c, A.in1 + o, te);
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc1[e] = csub(acc1[e] + c[e], qi);
+            }
+        }
+        const int te   = opaque_index(t);
+        const size_t o = (b * A.primes + i) * N;
+        store_quads(A.out0 + o, acc0, te);
+        store_quads(A.out1 + o, acc1, te);
+    }
+}
+
+// LOGN 12 .. 14 only, by the rule of launch_ct_key_switch_sp.
+hipError_t launch_ct_galois_accum_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
+                                     const GaloisAccumSpArgs &A, hipStream_t st)
+{
+    if (A.B == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        return launch(k_ct_galois_accum_sp<L>, evk_grid(A.B, A.primes), dim3(G::THREADS),
+                      (size_t)G::SLOTS * sizeof(uint32_t), st, P, T, R, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
 // Baby-step / giant-step linear transforms (se_amd_ct_bsgs_device): y = sum_{g, b} d[g][b] . rot_{giant[g] baby[b]}(x) as
 //   rot[b] = the hoisted MANY form above (the record itself for element 1),
 //   inner[g] = sum_b d'[g][b] . rot[b]                      k_ct_mul_plain_sum
@@ -1586,10 +1902,13 @@ __global__ __launch_bounds__(kLcThreads) void k_ct_mul_plain_sum(const DevParams
     const uint32_t rest    = by_xcd ? v / A.Gout * kXcds + blockIdx.x % kXcds : v / A.Gout;
     const uint32_t slab   = rest / chunks;
     const uint32_t chunk  = rest - slab * chunks;
-    const uint32_t j      = (chunk << kLcTileLog) >> P.logn;
+    // row -> prime: the identity but for the last row, which is modulo q_{last_prime} (the special prime on extended
+    // records) and meets that row of the plaintext: a shift of the plaintext's base, scalar like the rest
+    const uint32_t r      = (chunk << kLcTileLog) >> P.logn;
+    const uint32_t j      = r == A.primes - 1 ? A.last_prime : r;
     const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
     const uint32_t *__restrict__ in = slab ? A.in1 : A.in0;
-    const uint32_t *__restrict__ pt = A.pt;
+    const uint32_t *__restrict__ pt = A.pt + ((size_t)(j - r) << P.logn);
     uint32_t *__restrict__ out      = slab ? A.out1 : A.out0;
     const size_t off   = ((size_t)chunk << kLcTileLog) + 4 * threadIdx.x;   // the same offset inside a plaintext
     const size_t tiles = ((size_t)A.B + kSumTile - 1) / kSumTile;

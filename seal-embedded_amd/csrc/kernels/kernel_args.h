@@ -150,9 +150,15 @@ struct RescaleArgs
     const uint32_t *in0, *in1;   // [B][primes][n]; in1 / out1 NULL: one slab
     uint32_t *out0, *out1;       // [B][primes - 1][n]
     uint32_t primes;             // 2 .. np
+    uint32_t drop;               // mod-down only (k_ct_mod_down_sp): the prime of the last row, np - 1; rows j < primes - 1
+                                 // are modulo q_j either way
 };
 hipError_t launch_ct_rescale(const DevParams &, const DevTables &, const RescaleParams &, const RescaleArgs &, size_t B,
                              hipStream_t);
+// The same map with the special prime as the dropped one (k_ct_mod_down_sp): extended records [B][primes][n], primes =
+// L + 1 <= np, whose last row is modulo q_drop, drop = np - 1 -> [B][L][n]; RescaleParams of level np.
+hipError_t launch_ct_mod_down_sp(const DevParams &, const DevTables &, const RescaleParams &, const RescaleArgs &,
+                                 size_t B, hipStream_t);
 // Slot-wise product with encoded plaintexts (ct_ops.hip: k_ct_mul_plain), key-free:
 //   out[b][j][i] = in[b][j][i] . pt[p(b)][j][i]  mod q_j,   j < primes,   p(b) = pt_idx[b], or 0 (P = 1) or b (P = B).
 // Status 1, or 2 with all-zero rows for p(b) >= P.  out == in exactly is allowed.
@@ -328,6 +334,8 @@ struct MulPlainSumArgs
     uint32_t B;
     uint32_t E, Gout;               // 1 .. kMaxGaloisKeys each; E B and Gout B below 2^32
     uint32_t primes, pt_primes;     // pt_primes >= primes
+    uint32_t last_prime;            // the prime (and plaintext row) of row primes - 1: primes - 1 itself (the identity map),
+                                    // or np - 1 on extended records, whose last row is modulo the special prime
 };
 hipError_t launch_ct_mul_plain_sum(const DevParams &, const MulPlainSumArgs &, hipStream_t);
 // Rotate different ciphertexts and add (k_ct_galois_accum): out[b] = sum_{g < G} rho_g(in[g][b]) mod q_i, canonical, rho_g
@@ -346,6 +354,43 @@ struct GaloisAccumArgs
     const uint32_t *key[kMaxGaloisKeys];   // the device key block of elt[g]; NULL where elt[g] == 1
 };
 hipError_t launch_ct_galois_accum(const DevParams &, const DevTables &, const GaloisAccumArgs &, hipStream_t);
+// Baby steps on the special-prime keys, UNDIVIDED (k_ct_galois_many_ext_sp): G rotations of a level-`primes` record
+// (primes <= np - 1) as extended records of primes + 1 rows -- rows r < primes modulo q_r, row `primes` modulo P = q_{np-1}
+// -- from ONE decomposition of c1.  With D_j, F_{j,i}, E and src_e as in HoistSpArgs and i_r = r, or np - 1 for r = primes:
+//   out_k[e][b][r][x] = sum_{j < primes} F_{j,i_r}[src_e(x)] . key_k[e][j][i_r][x]  (+ (P mod q_r) . c0[b][r][src_e(x)] for
+//   k = 0, r < primes)   mod q_{i_r}, canonical.  elt[e] == 1: out_k = (P mod q_r) . c_k[b][r], row `primes` zero, no key.
+// "P times the rotated ciphertext plus the key-switch sum": k_ct_mod_down_sp of it is the rotation by elt[e].
+struct GaloisManyExtSpArgs
+{
+    const uint32_t *c0, *c1;        // [B][primes][n]
+    uint32_t *out0, *out1;          // [G][B][primes + 1][n]
+    size_t half;                    // words of one key half: R' np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
+    uint32_t primes;                // 1 .. np - 1
+    uint32_t G;                     // 1 .. kMaxGaloisKeys; G B below 2^32
+    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kMaxGaloisKeys];   // the special-prime key block of elt[e]; NULL where elt[e] == 1
+};
+hipError_t launch_ct_galois_many_ext_sp(const DevParams &, const DevTables &, const GaloisManyExtSpArgs &, hipStream_t);
+// Giant steps on the special-prime keys with ONE division (k_ct_galois_accum_sp): G different level-`primes` records
+// (a^g, b^g) = in[g][b] are rotated and added.  With D^g_j = centred(INTT_j(sigma_g(b^g[j])), q_j) for the keyed g (elt[g]
+// != 1):  acc_k[i] = sum_g sum_j NTT_i(D^g_j mod q_i) . key_k[g][j][i], i in E;  delta_k, ks_k as in KeySwitchSpArgs;
+//   out0 = ks_0 + sum_{keyed g} sigma_g(a^g) + sum_{elt[g] == 1} a^g,   out1 = ks_1 + sum_{elt[g] == 1} b^g.
+struct GaloisAccumSpArgs
+{
+    const uint32_t *in0, *in1;      // [G][B][primes][n]
+    uint32_t *out0, *out1;          // [B][primes][n]
+    size_t half;                    // words of one key half: R' np 2 n
+    size_t B;
+    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
+    uint32_t primes;                // 1 .. np - 1
+    uint32_t G;                     // 1 .. kMaxGaloisKeys; G B below 2^32
+    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
+    const uint32_t *key[kMaxGaloisKeys];   // the special-prime key block of elt[g]; NULL where elt[g] == 1
+};
+hipError_t launch_ct_galois_accum_sp(const DevParams &, const DevTables &, const RescaleParams &,
+                                     const GaloisAccumSpArgs &, hipStream_t);
 // Plan set-up: out[r][k] = in[r][src_elt(k)] on `rows` rows of n words, src the permutation of the automorphism of `elt`
 // (odd, below 2n, checked by the host) on a bit-reversed NTT-form row.
 hipError_t launch_bsgs_permute(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, uint32_t elt,

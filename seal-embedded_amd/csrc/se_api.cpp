@@ -584,14 +584,15 @@ int se_amd_ct_galois_accum_device(se_amd_ctx *ctx, const uint32_t *d_in0, const 
     return ctx->c.ct_galois_accum(d_in0, d_in1, B, primes, elts, G, d_out0, d_out1, as_stream(stream));
 }
 
-int se_amd_bsgs_create(se_amd_ctx *ctx, const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2,
-                       const uint32_t *d_diag, size_t pt_primes, se_amd_bsgs **out)
+// both kinds of plan: sp = for the special-prime entry
+static int bsgs_create(se_amd_ctx *ctx, const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2,
+                       const uint32_t *d_diag, size_t pt_primes, se_amd_bsgs **out, bool sp)
 {
     if (out) *out = nullptr;
     if (!ctx || !out) return SE_ERR_INVALD_ARGUMENT;
     se_amd_bsgs *h = new (std::nothrow) se_amd_bsgs();
     if (!h) return SE_ERR_NO_MEMORY;
-    const int rc = ctx->c.bsgs_create(baby, n1, giant, n2, d_diag, pt_primes, h->p);
+    const int rc = ctx->c.bsgs_create(baby, n1, giant, n2, d_diag, pt_primes, h->p, sp);
     if (rc != 0)
     {
         delete h;   // the buffer of a plan half built went with the local it was built in
@@ -599,6 +600,18 @@ int se_amd_bsgs_create(se_amd_ctx *ctx, const uint32_t *baby, size_t n1, const u
     }
     *out = h;
     return SE_SUCCESS;
+}
+
+int se_amd_bsgs_create(se_amd_ctx *ctx, const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2,
+                       const uint32_t *d_diag, size_t pt_primes, se_amd_bsgs **out)
+{
+    return bsgs_create(ctx, baby, n1, giant, n2, d_diag, pt_primes, out, false);
+}
+
+int se_amd_bsgs_create_sp(se_amd_ctx *ctx, const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2,
+                          const uint32_t *d_diag, size_t pt_primes, se_amd_bsgs **out)
+{
+    return bsgs_create(ctx, baby, n1, giant, n2, d_diag, pt_primes, out, true);
 }
 
 void se_amd_bsgs_destroy(se_amd_bsgs *plan)
@@ -612,6 +625,8 @@ void se_amd_bsgs_destroy(se_amd_bsgs *plan)
 size_t se_amd_bsgs_workspace_bytes(const se_amd_bsgs *plan, size_t records, size_t primes)
 {
     if (!plan) return 0;
+    if (plan->p.sp)
+        return records * seamd::Context::bsgs_sp_record_bytes(plan->p.baby.size(), plan->p.giant.size(), primes, plan->p.n);
     return records * 2 * (plan->p.baby.size() + plan->p.giant.size()) * primes * plan->p.n * sizeof(uint32_t);
 }
 
@@ -622,6 +637,46 @@ int se_amd_ct_bsgs_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
     return ctx->c.ct_bsgs(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, d_workspace, workspace_bytes,
                           as_stream(stream));
+}
+
+int se_amd_ct_galois_many_ext_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                        size_t primes, const uint32_t *elts, size_t G, uint32_t *d_out0,
+                                        uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois_many_ext_sp(d_c0, d_c1, B, primes, elts, G, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_mul_plain_sum_ext_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t E,
+                                          size_t B, size_t primes, const uint32_t *d_pt, size_t Gout, uint32_t *d_out0,
+                                          uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mul_plain_sum_ext_sp(d_in0, d_in1, E, B, primes, d_pt, Gout, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_mod_down_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t count,
+                                 size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mod_down_sp(d_in0, d_in1, count, primes, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_galois_accum_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t B,
+                                     size_t primes, const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1,
+                                     void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_galois_accum_sp(d_in0, d_in1, B, primes, elts, G, d_out0, d_out1, as_stream(stream));
+}
+
+int se_amd_ct_bsgs_sp_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                             size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *d_workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_bsgs_sp(plan ? &plan->p : nullptr, d_c0, d_c1, B, primes, d_out0, d_out1, d_workspace,
+                             workspace_bytes, as_stream(stream));
 }
 
 int se_amd_rescale_constants(size_t degree, size_t primes, uint32_t *inv, uint32_t *inv_shoup)

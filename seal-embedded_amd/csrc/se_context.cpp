@@ -1850,6 +1850,7 @@ int Context::ct_mul_plain_sum(const uint32_t *d_in0, const uint32_t *d_in1, size
     ma.Gout      = (uint32_t)Gout;
     ma.primes    = (uint32_t)primes;
     ma.pt_primes = (uint32_t)pt_primes;
+    ma.last_prime = (uint32_t)primes - 1;
     SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
     return 0;
 }
@@ -1889,12 +1890,18 @@ int Context::ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_
 // (g, b) of the caller's diagonals by giant[g]^-1, written to the slot of baby[b] with element 1 moved to the front --
 // and a synchronisation, so the caller's diagonals may go once this returns.  No key is read.  Anything refused leaves
 // `plan` empty.
+// sp: the plan of ct_bsgs_sp.  The diagonals must have all np rows -- the row at the special prime meets row L of the
+// extended records -- and the plan serves the levels 1 .. np - 1.
 int Context::bsgs_create(const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2, const uint32_t *d_diag,
-                         size_t pt_primes, BsgsPlan &plan)
+                         size_t pt_primes, BsgsPlan &plan, bool sp)
 {
-    const char *args_msg = "baby-step / giant-step plan: between 1 and 64 distinct elements in each list, pt_primes >= 1, "
-                           "16-byte aligned diagonals";
-    if (!d_diag || pt_primes == 0 || pt_primes >= ((size_t)1 << 32) || !aligned16({d_diag}))
+    if (sp && !special_prime_ok()) return kErrInvalid;
+    const char *args_msg = sp ? "special-prime baby-step / giant-step plan: between 1 and 64 distinct elements in each "
+                                "list, pt_primes = the context's primes, 16-byte aligned diagonals"
+                              : "baby-step / giant-step plan: between 1 and 64 distinct elements in each list, pt_primes "
+                                ">= 1, 16-byte aligned diagonals";
+    if (!d_diag || pt_primes == 0 || pt_primes >= ((size_t)1 << 32) || (sp && pt_primes != hp.nprimes) ||
+        !aligned16({d_diag}))
     {
         set_last_error(args_msg);
         return kErrInvalid;
@@ -1926,8 +1933,9 @@ int Context::bsgs_create(const uint32_t *baby, size_t n1, const uint32_t *giant,
     built.owner     = this;
     built.device    = device;
     built.n         = n;
-    built.levels    = pt_primes < np ? pt_primes : np;
+    built.levels    = sp ? np - 1 : pt_primes < np ? pt_primes : np;
     built.pt_primes = pt_primes;
+    built.sp        = sp;
     plan            = std::move(built);
     return 0;
 }
@@ -1944,12 +1952,14 @@ int Context::ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t 
     if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes) ||
         !evk_call_args(aa, {d_c0, d_c1, d_out0, d_out1}, B, primes))
         return kErrInvalid;
-    if (!plan || plan->owner != this || primes > plan->levels)
+    if (!plan || plan->owner != this || plan->sp || primes > plan->levels)
     {
         set_last_error(!plan ? "baby-step / giant-step transform: no plan"
                        : plan->owner != this ? "baby-step / giant-step transform: the plan belongs to another context"
-                                             : "baby-step / giant-step transform: the plan's diagonals have fewer primes "
-                                               "than the call");
+                       : plan->sp ? "baby-step / giant-step transform: a special-prime plan (se_amd_bsgs_create_sp) does "
+                                    "not serve the digit-key entry"
+                                  : "baby-step / giant-step transform: the plan's diagonals have fewer primes "
+                                    "than the call");
         return kErrInvalid;
     }
     const size_t n1 = plan->baby.size(), n2 = plan->giant.size(), row = primes * hp.n;
@@ -1992,6 +2002,7 @@ int Context::ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t 
     ma.Gout      = (uint32_t)n2;
     ma.primes    = (uint32_t)primes;
     ma.pt_primes = (uint32_t)plan->pt_primes;
+    ma.last_prime = (uint32_t)primes - 1;
     aa.in0       = inner0;
     aa.in1       = inner1;
     for (size_t b0 = 0; b0 < B; b0 += Bc)
@@ -2018,6 +2029,221 @@ int Context::ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t 
         aa.out0 = d_out0 + b0 * row;
         aa.out1 = d_out1 + b0 * row;
         SEAMD_HIP(launch_ct_galois_accum(dp, dt, aa, st));
+    }
+    return 0;
+}
+
+// The four steps of the special-prime baby-step / giant-step transform.  Each: the checks of ct_key_switch_sp in their
+// order (a context of one prime, the slabs, the level in [1, np - 1], alignment), then its own; one launch, no scratch, no
+// host synchronisation; the keyed ones read the installed special-prime Galois keys of the elements other than 1 (the
+// digit keys do not serve them) and launch nothing unless every such element has one.
+int Context::ct_galois_many_ext_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                   const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    GaloisManyExtSpArgs ma{};
+    if (!evk_call_args(ma, {d_c0, d_c1, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
+    if (!galois_elts_ok(elts, G, "undivided rotations: between 1 and 64 elements")) return kErrInvalid;
+    if (G * B >= ((size_t)1 << 32))
+    {
+        set_last_error("undivided rotations: G B must stay below 2^32");
+        return kErrInvalid;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t e = 0; e < G; e++)
+    {
+        ma.elt[e] = elts[e];
+        ma.key[e] = elts[e] == 1 ? nullptr : galois_key(true, elts[e]);
+        if (elts[e] != 1 && !ma.key[e]) return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    ma.c0   = d_c0;
+    ma.c1   = d_c1;
+    ma.out0 = d_out0;
+    ma.out1 = d_out1;
+    ma.G    = (uint32_t)G;
+    SEAMD_HIP(launch_ct_galois_many_ext_sp(dp, dt, ma, st));
+    return 0;
+}
+
+// ct_mul_plain_sum on stacks of extended records: primes + 1 rows, the last one modulo the special prime against row
+// np - 1 of the plaintexts, which have all np rows.
+int Context::ct_mul_plain_sum_ext_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
+                                     const uint32_t *d_pt, size_t Gout, uint32_t *d_out0, uint32_t *d_out1,
+                                     hipStream_t st)
+{
+    constexpr size_t k32 = (size_t)1 << 32;
+    if (!special_prime_ok()) return kErrInvalid;
+    if (!d_in0 || !d_out0 || !d_pt || !d_in1 != !d_out1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes - 1) return kErrInvalid;
+    if (B >= k32 || !aligned16({d_in0, d_in1, d_out0, d_out1, d_pt})) return kErrInvalid;
+    if (E < 1 || E > kMaxGaloisKeys || Gout < 1 || Gout > kMaxGaloisKeys || E * B >= k32 || Gout * B >= k32)
+    {
+        set_last_error("weighted sum over a stack: E and Gout between 1 and 64, E B and Gout B below 2^32");
+        return kErrInvalid;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    MulPlainSumArgs ma{};
+    ma.in0        = d_in0;
+    ma.in1        = d_in1;
+    ma.pt         = d_pt;
+    ma.out0       = d_out0;
+    ma.out1       = d_out1;
+    ma.B          = (uint32_t)B;
+    ma.E          = (uint32_t)E;
+    ma.Gout       = (uint32_t)Gout;
+    ma.primes     = (uint32_t)primes + 1;
+    ma.pt_primes  = (uint32_t)hp.nprimes;
+    ma.last_prime = (uint32_t)hp.nprimes - 1;
+    SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
+    return 0;
+}
+
+// The division by the special prime: `count` extended records of primes + 1 rows -> records of `primes` rows.
+int Context::ct_mod_down_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t count, size_t primes, uint32_t *d_out0,
+                            uint32_t *d_out1, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    if (!d_in0 || !d_out0 || !d_in1 != !d_out1) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes - 1 || count > 0x7fffffffu) return kErrInvalid;
+    if (!aligned16({d_in0, d_in1, d_out0, d_out1})) return kErrInvalid;
+    if (count == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    RescaleArgs ra{};
+    ra.in0    = d_in0;
+    ra.in1    = d_in1;
+    ra.out0   = d_out0;
+    ra.out1   = d_out1;
+    ra.primes = (uint32_t)primes + 1;
+    ra.drop   = (uint32_t)hp.nprimes - 1;
+    SEAMD_HIP(launch_ct_mod_down_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ra, count, st));
+    return 0;
+}
+
+int Context::ct_galois_accum_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes,
+                                const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    GaloisAccumSpArgs aa{};
+    if (!evk_call_args(aa, {d_in0, d_in1, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
+    if (!galois_elts_ok(elts, G, "rotate and accumulate: between 1 and 64 elements")) return kErrInvalid;
+    if (G * B >= ((size_t)1 << 32))
+    {
+        set_last_error("rotate and accumulate: G B must stay below 2^32");
+        return kErrInvalid;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t g = 0; g < G; g++)
+    {
+        aa.elt[g] = elts[g];
+        aa.key[g] = elts[g] == 1 ? nullptr : galois_key(true, elts[g]);
+        if (elts[g] != 1 && !aa.key[g]) return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    aa.in0  = d_in0;
+    aa.in1  = d_in1;
+    aa.out0 = d_out0;
+    aa.out1 = d_out1;
+    aa.G    = (uint32_t)G;
+    SEAMD_HIP(launch_ct_galois_accum_sp(dp, dt, host_rescale_params(hp, hp.nprimes), aa, st));
+    return 0;
+}
+
+// ct_bsgs on the special-prime keys.  The checks of ct_key_switch_sp first, then the plan's and the workspace's, then
+// under `mu` the special-prime keys of every element other than 1, read NOW.  The batch is walked in chunks of Bc =
+// min(B, workspace records); a chunk of c records uses the workspace as U0 | U1 | V0 | V1 | W0 | W1 -- stacks [n1][c] and
+// [n2][c] of extended records (primes + 1 rows) and [n2][c] of level-`primes` records -- at offsets fixed by Bc:
+//   U = many_ext(c; baby),  V[g] = sum_b d'[g][b] . U[b] on all primes + 1 rows,  W = mod_down(V),  out = accum_sp(W; giant).
+// Everything is enqueued on `st`: no context scratch, no allocation, no synchronisation.
+int Context::ct_bsgs_sp(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                        uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    GaloisManyExtSpArgs ua{};
+    GaloisAccumSpArgs aa{};
+    if (!evk_call_args(ua, {d_c0, d_c1, d_out0, d_out1}, B, primes, true) ||
+        !evk_call_args(aa, {d_c0, d_c1, d_out0, d_out1}, B, primes, true))
+        return kErrInvalid;
+    if (!plan || plan->owner != this || !plan->sp || primes > plan->levels)
+    {
+        set_last_error(!plan ? "baby-step / giant-step transform: no plan"
+                       : plan->owner != this ? "baby-step / giant-step transform: the plan belongs to another context"
+                       : !plan->sp ? "baby-step / giant-step transform: a digit-key plan (se_amd_bsgs_create) does not "
+                                     "serve the special-prime entry"
+                                   : "baby-step / giant-step transform: the level is above the plan's");
+        return kErrInvalid;
+    }
+    const size_t n1 = plan->baby.size(), n2 = plan->giant.size(), n = hp.n, np = hp.nprimes;
+    const size_t row = primes * n, xrow = (primes + 1) * n;
+    const size_t per = bsgs_sp_record_bytes(n1, n2, primes, n);
+    if (!d_workspace || !aligned16({d_workspace}) || workspace_bytes < per)
+    {
+        set_last_error("baby-step / giant-step transform: the workspace must be 16-byte aligned and hold at least one "
+                       "record (se_amd_bsgs_workspace_bytes)");
+        return kErrInvalid;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t e = 0; e < n1; e++)
+    {
+        ua.elt[e] = plan->baby[e];
+        ua.key[e] = ua.elt[e] == 1 ? nullptr : galois_key(true, ua.elt[e]);
+        if (ua.elt[e] != 1 && !ua.key[e]) return kErrNoKey;
+    }
+    for (size_t g = 0; g < n2; g++)
+    {
+        aa.elt[g] = plan->giant[g];
+        aa.key[g] = aa.elt[g] == 1 ? nullptr : galois_key(true, aa.elt[g]);
+        if (aa.elt[g] != 1 && !aa.key[g]) return kErrNoKey;
+    }
+    if (B == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    // a chunk's stacks are launch grids too: n1 c and n2 c stay below 2^31
+    const size_t Bc = std::min({B, workspace_bytes / per, (size_t)0x7fffffffu / std::max(n1, n2)});
+    uint32_t *u0 = static_cast<uint32_t *>(d_workspace), *u1 = u0 + n1 * Bc * xrow;
+    uint32_t *v0 = u1 + n1 * Bc * xrow, *v1 = v0 + n2 * Bc * xrow;
+    uint32_t *w0 = v1 + n2 * Bc * xrow, *w1 = w0 + n2 * Bc * row;
+    const RescaleParams rp = host_rescale_params(hp, np);
+    ua.G    = (uint32_t)n1;
+    ua.out0 = u0;
+    ua.out1 = u1;
+    aa.G    = (uint32_t)n2;
+    aa.in0  = w0;
+    aa.in1  = w1;
+    MulPlainSumArgs ma{};
+    ma.in0        = u0;
+    ma.in1        = u1;
+    ma.pt         = plan->diag;
+    ma.out0       = v0;
+    ma.out1       = v1;
+    ma.E          = (uint32_t)n1;
+    ma.Gout       = (uint32_t)n2;
+    ma.primes     = (uint32_t)primes + 1;
+    ma.pt_primes  = (uint32_t)np;
+    ma.last_prime = (uint32_t)np - 1;
+    RescaleArgs ra{};
+    ra.in0    = v0;
+    ra.in1    = v1;
+    ra.out0   = w0;
+    ra.out1   = w1;
+    ra.primes = (uint32_t)primes + 1;
+    ra.drop   = (uint32_t)np - 1;
+    for (size_t b0 = 0; b0 < B; b0 += Bc)
+    {
+        const size_t c = std::min(Bc, B - b0);
+        ua.c0 = d_c0 + b0 * row;
+        ua.c1 = d_c1 + b0 * row;
+        ua.B  = c;
+        SEAMD_HIP(launch_ct_galois_many_ext_sp(dp, dt, ua, st));
+        ma.B = (uint32_t)c;
+        SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
+        SEAMD_HIP(launch_ct_mod_down_sp(dp, dt, rp, ra, n2 * c, st));
+        aa.B    = c;
+        aa.out0 = d_out0 + b0 * row;
+        aa.out1 = d_out1 + b0 * row;
+        SEAMD_HIP(launch_ct_galois_accum_sp(dp, dt, rp, aa, st));
     }
     return 0;
 }

@@ -54,6 +54,7 @@ struct BsgsPlan
     size_t n             = 0;
     size_t levels        = 0;       // min(pt_primes, np): the calls it serves have primes <= levels
     size_t pt_primes     = 0;
+    bool sp              = false;   // made by se_amd_bsgs_create_sp: pt_primes = np, levels = np - 1, served by ct_bsgs_sp
     std::vector<uint32_t> baby, giant;   // baby: element 1 first where listed
     DevBuf<uint32_t> diag;               // [n2][n1][pt_primes][n], row (g, b) permuted by giant[g]^-1
 };
@@ -277,9 +278,27 @@ struct Context
     int ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
                         size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     int bsgs_create(const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2, const uint32_t *d_diag,
-                    size_t pt_primes, BsgsPlan &plan);
+                    size_t pt_primes, BsgsPlan &plan, bool sp = false);
     int ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                 uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st);
+    // the same on the special-prime keys with the division by P deferred: the four steps below, one launch each and
+    // useful on their own, and the call that chains them in the caller's workspace.  An extended record has primes + 1
+    // rows, the last one modulo the special prime (GaloisManyExtSpArgs)
+    int ct_galois_many_ext_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
+                              size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    int ct_mul_plain_sum_ext_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
+                                const uint32_t *d_pt, size_t Gout, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    int ct_mod_down_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t count, size_t primes, uint32_t *d_out0,
+                       uint32_t *d_out1, hipStream_t st);
+    int ct_galois_accum_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
+                           size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    int ct_bsgs_sp(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                   uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st);
+    static size_t bsgs_sp_record_bytes(size_t n1, size_t n2, size_t primes, size_t n)
+    {
+        // U [n1] and V [n2] of primes + 1 rows, W [n2] of primes rows, two halves each
+        return 2 * ((n1 + n2) * (primes + 1) + n2 * primes) * n * sizeof(uint32_t);
+    }
     // the sum form on the special-prime Galois keys (HoistSpArgs): one decomposition and one division by P whatever G is
     int ct_galois_sum_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
                          size_t G, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);

@@ -18,7 +18,12 @@ their definition), with --hoist:
   matvec:     the diagonal method on a dim x dim matrix with entries in [-1, 1], diagonals encoded at Delta, NO lift, one
               rescale, decoded at Delta^2 / q_{L-1};
 each with the same figures for G single key switches, each rounded on its own, then summed.
-  python tools/ct_keyswitch_sp_noise_sim.py [--hoist] [4096x3:2 4096x3:1 8192x6:5 4096x2:1 ...]      (n x np : L)"""
+The baby-step / giant-step plan with the division by P deferred (se_amd_ct_bsgs_sp_device; bsgs_sp_expect of
+tests/ct_model_bsgs_sp.py is its definition), with --bsgs:
+  matvec_bsgs: a 16 x 16 matrix with entries in [-1/2, 1/2] as a 4 x 4 plan (six keys), diagonals encoded at Delta, NO
+              lift, one rescale, decoded at Delta^2 / q_{L-1}: the worst slot error, and the largest coefficient of what
+              the plan adds to the exact weighted sum before the rescale (n2 + 1 = 5 roundings and the key errors).
+  python tools/ct_keyswitch_sp_noise_sim.py [--hoist | --bsgs] [4096x3:2 4096x3:1 8192x6:5 4096x2:1 ...]   (n x np : L)"""
 import json
 import os
 import sys
@@ -190,6 +195,51 @@ def matvec(n, npr, L, dim=8):
     return dict(op="matvec", n=n, primes=npr, level=L, G=dim - 1, log2_scale_after=float(np.log2(scale)), **out)
 
 
+def matvec_bsgs(n, npr, L, n1=4, n2=4):
+    """-> dict: M x for the 16 x 16 matrix of examples/matvec_bsgs_fresh_roundtrip.c on a fresh record at level L through
+    the 4 x 4 plan: baby steps 0 .. 3 undivided, the diagonals (encoded at Delta, all np rows) multiplied in, one division
+    per giant step 0, 4, 8, 12 and one for their sum, one rescale, decoded at Delta^2 / q_{L-1}."""
+    import ct_model_bsgs_sp as KB
+    assert L >= 2
+    dim = n1 * n2
+    o = pyoracle.Oracle(n, npr)
+    q = o.q
+    sk = V.secret_key(n, seed=5)
+    s_hat = np.stack([o.ntt(o.expand_ternary(sk, j), j) for j in range(npr)])
+    x16 = np.random.default_rng(16 * n + npr).uniform(-1.0, 1.0, dim)
+    vals = np.tile(x16, n // 2 // dim).astype(np.float32)
+    M = K.matrix(dim)
+    want = np.tile(M @ vals[:dim].astype(np.float64), n // 2 // dim)
+    ss, sd = V.bench_seeds(1, first=13)
+    x = o.encrypt_sym(vals, ss[0].tobytes(), sd[0].tobytes(), sk)
+    c0 = np.stack([np.array(x["c0"][j]) for j in range(L)])
+    c1 = np.stack([np.array(x["c1"][j]) for j in range(L)])
+    baby = [pow(3, b, 2 * n) for b in range(n1)]
+    giant = [pow(3, n1 * g, 2 * n) for g in range(n2)]
+    elts, keys = step_keys(o, sk, s_hat, [b for b in range(1, n1)] + [n1 * g for g in range(1, n2)])
+    ok, diag = o.encode_ntt_batch(K.matrix_diagonals(M, n))
+    assert ok
+    diag = np.stack([np.stack([np.array(d[j]) for j in range(npr)]) for d in diag])    # [dim][np][n], scale Delta
+    # the exact weighted sum: sum_e d_e . sigma_e(m) per prime on the decrypted record, recombined
+    rows = []
+    for i in range(L):
+        m = o.decrypt(c0[i], c1[i], s_hat[i], i).astype(np.uint64)
+        acc = np.zeros(n, dtype=np.uint64)
+        for e in range(dim):
+            src = K.src_table(n, pow(3, e, 2 * n))
+            acc = (acc + (diag[e, i].astype(np.uint64) * m[src]) % np.uint64(q[i])) % np.uint64(q[i])
+        rows.append(o.intt(acc.astype(np.uint32), i))
+    exact = np.array(K.crt_centred(q[:L], rows), dtype=object)
+    r0, r1 = KB.bsgs_sp_expect(K.src_table, o, c0[None], c1[None], baby, giant, diag.reshape(n2, n1, npr, n),
+                               dict(zip(elts, keys)))
+    scale = o.scale * o.scale / q[L - 1]
+    term = value(o, list(r0[0]), list(r1[0]), s_hat) - exact
+    y = value(o, rescale(o, list(r0[0])), rescale(o, list(r1[0])), s_hat)
+    return dict(op="matvec_bsgs", n=n, primes=npr, level=L, n1=n1, n2=n2, keys=len(elts),
+                log2_scale_after=float(np.log2(scale)), key_switch_max=max(abs(int(v)) for v in term),
+                slot_error=float(np.abs(decode(o, y, scale) - want).max()))
+
+
 def parse(arg):
     shape, L = arg.split(":")
     n, npr = (int(v) for v in shape.split("x"))
@@ -199,6 +249,10 @@ def parse(arg):
 if __name__ == "__main__":
     pyoracle.build(ref=False)
     rows = []
+    if "--bsgs" in sys.argv[1:]:
+        for arg in [a for a in sys.argv[1:] if a != "--bsgs"] or ("4096x3:2", "8192x6:5"):
+            print(json.dumps(matvec_bsgs(*parse(arg))), flush=True)
+        sys.exit(0)
     args = [a for a in sys.argv[1:] if a != "--hoist"]
     if "--hoist" in sys.argv[1:]:
         for arg in args or ("4096x3:2", "8192x6:5"):
