@@ -825,6 +825,72 @@ int se_amd_bsgs_create_sp(se_amd_ctx *ctx, const uint32_t *baby /*host, [n1]*/, 
 int se_amd_ct_bsgs_sp_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1,
                              size_t B, size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *d_workspace,
                              size_t workspace_bytes, void *stream);
+/* ---- switch-key rings: bring records of many keys under one key, and sum them ------------------------------
+ * The key rings above put one batch under K device keys, one key index per ciphertext; everything behind them -- sums
+ * (se_amd_ct_lincomb_device: "All records of a row must be under the same key"), products, rotations, plans -- works
+ * under ONE key.  A switching key closes the gap: a special-prime key whose diagonal hides P . s_from under s_to moves a
+ * record from key `from` to key `to` at the record's own scale, with no lift and no level spent, exactly as a Galois key
+ * does for sigma(s).  A ring holds K of them, chosen per record.  Notation is that of the special-prime block: p = np - 1,
+ * P = q_p, records at level 1 <= L <= np - 1, E = {0 .. L-1, p}, R' = np - 1, centred(x, q) in (-q/2, q/2]; conventions
+ * those of se_amd_ct_relin_sp_device: level-`primes` slabs [B][primes][n], 16-byte aligned; one asynchronous launch, no
+ * scratch, no host synchronisation; outputs do not overlap inputs; nothing is written on an argument error; B = 0 resp.
+ * G = 0 is a successful no-op; np >= 2.
+ * WHO RUNS THE GENERATOR.  se_amd_gen_switch_keys_sp needs BOTH secrets, every s_from_k and s_to.  It belongs to the
+ * authority that issued the device keys (the role of the reference's adapter), never to the evaluator: the evaluator
+ * receives wk0 / wk1, which are public material like every evaluation key, and installs them.  A public-key form, in which
+ * a device makes its own switching key from the target's public key, is out of scope.
+ * Key k of the ring has the shape of every special-prime key: wk0, wk1 uint32 [K][R'][np][n], NTT form, canonical,
+ *     wk1[k][j][i] = a_{k,j,i}
+ *     wk0[k][j][i] = -a_{k,j,i} . s_to_hat_i + NTT_i(e_{k,j}) + [i == j] . (P mod q_j) . s_from_k_hat_j.
+ * Minus its diagonal, row j of key k is exactly public key j of se_amd_gen_keys_batch with K = R', sk_in = sk_to replicated,
+ * pk_seeds = a_seeds[k] and ep_seeds = e_seeds[k].  Column p has no diagonal and one key serves every level.  The generator
+ * takes host pointers, installs nothing, keeps its device copies of secret material in wiped buffers, and refuses a 2-bit
+ * code 3 in any of the K + 1 secret keys, K = 0, NULL pointers and np = 1.
+ * se_amd_set_switch_keyring_sp validates every word < q_i (else SE_ERR_INVALD_ARGUMENT; also K = 0), builds the ring --
+ * per key the device block of the other special-prime keys, with Shoup companions, keys at a fixed stride -- BESIDE the
+ * installed ring and swaps it in at the end: a refused or failed install leaves the previous ring usable, and calls in
+ * flight finish on the old one.  The ring is an installed set of its own: it neither touches nor is served by the
+ * relinearisation key, the Galois keys, the digit keys or the secret / public rings.  Device memory: 16 (np - 1) np n bytes
+ * per key (4096 x 3: 384 KiB, so 512 keys take 192 MiB).
+ * se_amd_ct_switch_keyed_sp_device: for record b with k = d_key_idx[b], out0 = c0 + ks_0 and out1 = ks_1, ks the "key
+ * switch of a level-L row polynomial" above applied to d = c1[b] under ring key k: BIT-IDENTICAL to
+ * se_amd_ct_relin_sp_device(c0, 0, c1) with ring key k installed as the relinearisation key.  Defined on arbitrary residue
+ * slabs and key words; no secret key is needed.  k >= K never forms an address: the workgroup compares the index with K
+ * (wave-uniform), such a record gets all-zero outputs and status 2, the other records status 1 and are unaffected -- the
+ * ring's convention, without a sanitising pass and without scratch.
+ * se_amd_ct_switch_sum_keyed_sp_device: the CSR rows of se_amd_ct_lincomb_device, unweighted: row g takes the records b =
+ * d_idx[t], t in [d_row_ptr[g], d_row_ptr[g + 1]); a record listed twice counts twice.  ONE division by P per row:
+ *     D_{b,j}    = centred(INTT_j(c1[b][j]), q_j)                                               j < L
+ *     ACC_k[i]   = sum_{b in row} sum_{j<L} NTT_i(D_{b,j} mod q_i) . ring[key_idx[b]]_k[j][i]   i in E (for i = j the factor is
+ *                                                                                               c1[b][j] as it lies)
+ *     delta_k    = centred(INTT_p(ACC_k[p]), P)
+ *     out0[g][i] = (ACC_0[i] - NTT_i(delta_0 mod q_i)) . P^-1 + sum_{b in row} c0[b][i]         mod q_i, canonical
+ *     out1[g][i] = (ACC_1[i] - NTT_i(delta_1 mod q_i)) . P^-1
+ * The c0 terms are added after the division: they are exact.  Two facts.  (1) A row of one record is BIT-IDENTICAL to
+ * se_amd_ct_switch_keyed_sp_device on that record.  (2) A row of m >= 2 records is NOT the modular sum of m single
+ * switches: it carries centred(sum_b delta^b mod P) instead of m roundings delta^b, and differs wherever |sum_b delta^b| >
+ * P/2.  One rounding instead of m, and (4 L - 2) m + 4 transforms per output row and prime against (4 L + 2) m.
+ * Status (uint8 [G], optional): an empty row is all zero with status 1; a row with a record index >= B, a member whose key
+ * index is >= K, or a d_row_ptr pair that decreases or reaches beyond nnz is all zero in both slabs with status 2.  Nothing
+ * is read out of bounds, and the status is decided before anything of the row is written.
+ * The result is under s_to at the records' scale and level: it goes straight into se_amd_ct_lincomb_device, a plan or
+ * se_amd_decrypt_level_device.  A row runs on L workgroups whatever its length and is not sliced: sum a large batch in two
+ * tiers, switch-sum in groups (tens of records), then se_amd_ct_lincomb_device over the group sums, which are all under s_to.
+ * SE_ERR_NO_KEY without an installed switch ring; SE_ERR_INVALD_ARGUMENT for the argument errors of
+ * se_amd_ct_relin_sp_device, a NULL d_key_idx, and in the sum form a NULL d_row_ptr, a NULL d_idx with nnz > 0, G or nnz at
+ * or above 2^32.  Out of scope: slicing long rows, weighted rows, a public-key generator, several special primes, digit
+ * switching keys, host-pointer and multi-device forms, installing the ring from device pointers. */
+int se_amd_gen_switch_keys_sp(se_amd_ctx *ctx, size_t K, const uint8_t *sk_from /*[K][n/4]*/, const uint8_t *sk_to /*[n/4]*/,
+                              const uint8_t *a_seeds /*[K][R'][64]*/, const uint8_t *e_seeds /*[K][R'][64]*/,
+                              uint32_t *wk0, uint32_t *wk1 /*[K][R'][np][n], host out*/);
+int se_amd_set_switch_keyring_sp(se_amd_ctx *ctx, size_t K, const uint32_t *wk0, const uint32_t *wk1);
+int se_amd_ct_switch_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                     const uint32_t *d_key_idx /*[B]*/, uint32_t *d_out0, uint32_t *d_out1,
+                                     uint8_t *d_status /*[B], optional*/, void *stream);
+int se_amd_ct_switch_sum_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                         const uint32_t *d_key_idx /*[B]*/, size_t G, const uint32_t *d_row_ptr /*[G+1]*/,
+                                         const uint32_t *d_idx /*[nnz]*/, size_t nnz, uint32_t *d_out0, uint32_t *d_out1
+                                         /*[G][primes][n]*/, uint8_t *d_status /*[G], optional*/, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

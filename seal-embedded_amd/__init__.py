@@ -77,6 +77,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_bsgs_workspace_bytes", "se_amd_ct_bsgs_device",
     "se_amd_ct_galois_many_ext_sp_device", "se_amd_ct_mul_plain_sum_ext_sp_device", "se_amd_ct_mod_down_sp_device",
     "se_amd_ct_galois_accum_sp_device", "se_amd_bsgs_create_sp", "se_amd_ct_bsgs_sp_device",
+    "se_amd_gen_switch_keys_sp", "se_amd_set_switch_keyring_sp", "se_amd_ct_switch_keyed_sp_device",
+    "se_amd_ct_switch_sum_keyed_sp_device",
 )
 
 
@@ -203,6 +205,10 @@ def lib():
     L.se_amd_ct_galois_accum_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
     L.se_amd_bsgs_create_sp.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp)]
     L.se_amd_ct_bsgs_sp_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp]
+    L.se_amd_gen_switch_keys_sp.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    L.se_amd_set_switch_keyring_sp.argtypes = [vp, sz, vp, vp]
+    L.se_amd_ct_switch_keyed_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.se_amd_ct_switch_sum_keyed_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -798,6 +804,59 @@ class Context:
         _check(self.L.se_amd_ct_drop_primes_device(self.h, _ptr(in0), _ptr(in1), in0.shape[0], primes_in, primes_out,
                                                    _ptr(out0), _ptr(out1), _stream_ptr()),
                "se_amd_ct_drop_primes_device")
+
+    # ---- switch-key rings: K special-prime keys that hide P . s_from_k under s_to; record b is switched under ring key
+    # key_idx[b].  The generator needs both secrets (the authority that issued the keys); the ring is public material
+    def gen_switch_keys_sp(self, sk_from, sk_to, a_seeds, e_seeds):
+        """Switching keys from the K packed keys sk_from [K][n/4] to sk_to [n/4], from K blocks of R' = np - 1 seed pairs
+        [K][R'][64]: (wk0, wk1) uint32 [K][R'][np][n].  Installs nothing."""
+        import numpy as np
+        R = max(self.np - 1, 1)
+        skf = np.ascontiguousarray(sk_from, dtype=np.uint8).reshape(-1, self.n // 4)
+        K = skf.shape[0]
+        skt = np.ascontiguousarray(sk_to, dtype=np.uint8)
+        assert skt.size == self.n // 4
+        sa = np.ascontiguousarray(a_seeds, dtype=np.uint8).reshape(K, R, 64)
+        se = np.ascontiguousarray(e_seeds, dtype=np.uint8).reshape(K, R, 64)
+        wk0 = np.zeros((K, R, self.np, self.n), dtype=np.uint32)
+        wk1 = np.zeros_like(wk0)
+        _check(self.L.se_amd_gen_switch_keys_sp(self.h, K, _ptr(skf), _ptr(skt), _ptr(sa), _ptr(se), _ptr(wk0),
+                                                _ptr(wk1)), "se_amd_gen_switch_keys_sp")
+        return wk0, wk1
+
+    def set_switch_keyring_sp(self, wk0, wk1):
+        """wk0, wk1 [K][np - 1][np][n] uint32 (as gen_switch_keys_sp returns them): replaces the installed switch ring; a
+        word >= q_i is refused and the previous ring stays."""
+        import numpy as np
+        R = max(self.np - 1, 1)
+        wk0 = np.ascontiguousarray(wk0, dtype=np.uint32)
+        K = wk0.size // (R * self.np * self.n)
+        wk0, wk1 = self._evk_halves(wk0, wk1, K, R=R)
+        _check(self.L.se_amd_set_switch_keyring_sp(self.h, K, _ptr(wk0), _ptr(wk1)), "se_amd_set_switch_keyring_sp")
+
+    def ct_switch_keyed_sp(self, c0, c1, key_idx, out0, out1, primes=None, status=None):
+        """Record b of (c0, c1) [B][primes][n], primes <= np - 1, from the key of ring entry key_idx[b] to the ring's
+        target key, at the record's own scale: the bits of ct_relin_sp(c0, 0, c1) under that ring key.  status uint8 [B]:
+        2 and zero rows for an index >= K."""
+        if primes is None:
+            primes = c0.shape[1]
+        _check(self.L.se_amd_ct_switch_keyed_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(key_idx),
+                                                       _ptr(out0), _ptr(out1), _ptr(status), _stream_ptr()),
+               "se_amd_ct_switch_keyed_sp_device")
+
+    def ct_switch_sum_keyed_sp(self, c0, c1, key_idx, row_ptr, idx, out0, out1, primes=None, status=None):
+        """Switch and sum: output row g = the sum of the records idx[row_ptr[g] .. row_ptr[g + 1]) of (c0, c1)
+        [B][primes][n], each switched under ring key key_idx[b], with ONE division by the special prime per row; out0,
+        out1 are [G][primes][n].  A row of one record has the bits of ct_switch_keyed_sp.  status uint8 [G]: 2 and a
+        zero row for a record index >= B, a member's key index >= K or a bad row_ptr pair."""
+        if primes is None:
+            primes = c0.shape[1]
+        G = row_ptr.numel() - 1
+        nnz = idx.numel() if idx is not None else 0
+        _check(self.L.se_amd_ct_switch_sum_keyed_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes,
+                                                           _ptr(key_idx), G, _ptr(row_ptr), _ptr(idx), nnz, _ptr(out0),
+                                                           _ptr(out1), _ptr(status), _stream_ptr()),
+               "se_amd_ct_switch_sum_keyed_sp_device")
 
     def ct_galois_many(self, c0, c1, elts, out0, out1, primes=None):
         """Hoisted rotations: out[e] = the rotation of the records (c0, c1) [B][primes][n] by elts[e], for all G

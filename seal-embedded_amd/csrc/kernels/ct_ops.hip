@@ -11,7 +11,9 @@
 // (se_amd_ct_mul_plain_sum_device, se_amd_ct_galois_accum_device, se_amd_ct_bsgs_device, behind the special-prime hoist),
 // and the same transform on the special-prime keys with the division by P deferred: undivided baby steps, the division of
 // extended records and the one-division giant sum (se_amd_ct_galois_many_ext_sp_device, se_amd_ct_mod_down_sp_device,
-// se_amd_ct_galois_accum_sp_device, se_amd_ct_bsgs_sp_device, between the two).
+// se_amd_ct_galois_accum_sp_device, se_amd_ct_bsgs_sp_device, between the two), and the switch-key ring: the special-prime
+// key switch with the key chosen per record, alone or summed over CSR rows with one division by P per row
+// (se_amd_ct_switch_keyed_sp_device, se_amd_ct_switch_sum_keyed_sp_device, behind k_ct_galois_sp).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -1051,6 +1053,162 @@ hipError_t launch_ct_key_switch_sp(const DevParams &P, const DevTables &T, const
         const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
         return A.elt ? launch(k_ct_galois_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
                      : launch(k_ct_relin_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Switch-key ring: se_amd_ct_switch_keyed_sp_device and se_amd_ct_switch_sum_keyed_sp_device (SwitchSpArgs).  A ring
+// key hides P . s_from_k under s_to, so the special-prime key switch of c1[b] under ring key key_idx[b], plus c0[b],
+// is record b under s_to.  The sum form brings the records of a CSR row under s_to AND adds them, with the family's
+// newest motif: the undivided terms of the whole row are accumulated and divided by P once.
+// One body, ct_switch_sp, from the pieces of ct_key_switch_sp (sp_row_digit<LOGN, false>, evk_mac, sp_delta,
+// load_quads / store_quads) and in its geometry: one workgroup of n/16 threads per (output row, output prime i < L),
+// LDS the exchange plane alone, no scratch, no global temporary.  The single switch is the row {g} without the row tables.
+//   row:    the entries [lo, hi) and their validity, decided before anything of the row is written: every record index
+//           is compared with B and only then used to read key_idx, every key index is compared with K and only then
+//           used to form the key pointer ring + key_idx[b] . stride.  All of these depend on blockIdx and the loop
+//           counters alone: they are wave-uniform.  An invalid row (status 2) and an empty one (status 1) are all zero.
+//   pass 0: per record of the row and input row j: sp_row_digit mod P -> evk_mac against row j, column p of THAT
+//           record's key;   then sp_delta once for the row;
+//   pass 1: the records again against column i (row i of a record enters as it lies in memory);
+//   epilogue: . P^-1; out1 is finished and stored first, then the rows c0[b][i] of the records are added into the
+//           divided acc0 one at a time -- exact, canonical after every step, and no third accumulator tile.
+// Transforms per workgroup for a row of m records: (2 L - 1) m INTTs and as many NTTs, and 4 for the two deltas:
+// (4 L - 2) m + 4, against (4 L + 2) m for m single switches and a sum; the switched records never touch memory.
+// Lazy ranges: evk_mac's range argument (above evk_row_coeffs) does not depend on the number of terms -- a 32-bit word per
+// value carries any number of them -- so it covers a row of any length; pass 1 enters in (0, 2 q_i] as in
+// ct_key_switch_sp.  A row of one record runs the operations of k_ct_relin_sp on (c0, 0, c1) in their order: the same
+// bits.  A long row is not sliced: a whole-batch sum into one row runs on L workgroups (sum in groups, then
+// se_amd_ct_lincomb_device over the group sums).
+// grid evk_grid(rows, L).
+// ------------------------------------------------------------------------------------------
+template <int LOGN, bool SUM>
+__device__ __forceinline__ void ct_switch_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
+                                             const SwitchSpArgs &A, uint32_t *lds)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t sp  = A.np - 1;
+    const uint32_t qi  = P.q[i];
+    const size_t words = (size_t)A.primes * N;   // of a record
+    const uint32_t *__restrict__ idx  = A.idx;
+    const uint32_t *__restrict__ kidx = A.key_idx;
+    auto record_of = [&](uint32_t e) -> uint32_t {
+        if constexpr (SUM)
+            return idx[e];
+        else
+            return e;
+    };
+
+    for (size_t g = blockIdx.x; g < A.rows; g += gridDim.x)
+    {
+        uint32_t lo, hi;
+        bool bad = false;
+        if constexpr (SUM)
+        {
+            const uint32_t a = A.row_ptr[g], b = A.row_ptr[g + 1];
+            bad = a > b || b > A.nnz;
+            lo  = a;
+            hi  = bad ? a : b;
+        }
+        else
+        {
+            lo = (uint32_t)g;
+            hi = lo + 1;
+        }
+        for (uint32_t e = lo; e < hi && !bad; e++)
+        {
+            const uint32_t b = record_of(e);
+            bad              = b >= A.B || kidx[b] >= A.K;   // key_idx is read for a record that exists only
+        }
+        const int te   = opaque_index(t);
+        const size_t o = g * words + (size_t)i * N;
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        if (bad || lo == hi)
+        {
+            store_quads(A.out0 + o, acc0, te);
+            store_quads(A.out1 + o, acc1, te);
+            if (A.status && i == 0 && t == 0) A.status[g] = bad ? 2 : 1;
+            continue;
+        }
+        // pass 0: modulo P against key column p; pass 1: modulo q_i against key column i.  One body for both.
+#pragma unroll 1
+        for (uint32_t pass = 0; pass < 2; pass++)
+        {
+            const uint32_t col = pass ? i : sp;
+            const uint32_t q   = P.q[col];
+            const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * col;
+            for (uint32_t e = lo; e < hi; e++)
+            {
+                const uint32_t b   = record_of(e);
+                const uint32_t *sw = A.c1 + b * words;
+                const uint32_t *kc = A.ring + kidx[b] * A.stride + (size_t)col * 2 * N;   // column col of key row 0
+                for (uint32_t j = 0; j < A.primes; j++)
+                {
+                    uint32_t y[16];
+                    if (pass && j == i)
+                        load_quads(y, sw + (size_t)i * N, opaque_index(t));
+                    else
+                        sp_row_digit<LOGN, false>(y, sw + (size_t)j * N, j, 0, q, rw, P, T, lds, t);
+                    const uint32_t *key = kc + (size_t)j * A.np * 2 * N + quad_index(opaque_index(t), 0);
+                    evk_mac<LOGN>(acc0, acc1, y, key, A.half, q);
+                    __syncthreads();
+                }
+            }
+            if (pass == 0) sp_delta<LOGN>(acc0, acc1, i, sp, P, T, lds, t);
+        }
+        // ks_k = acc_k . P^-1; out1 leaves first, then the c0 rows join the divided acc0
+        const uint32_t w = R.inv[i], wp = R.inv_sh[i];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc1[e] = csub(mul_shoup_lazy(acc1[e], w, wp, qi), qi);
+        store_quads(A.out1 + o, acc1, te);
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = csub(mul_shoup_lazy(acc0[e], w, wp, qi), qi);
+        for (uint32_t e = lo; e < hi; e++)
+        {
+            uint32_t c[16];
+            load_quads(c, A.c0 + record_of(e) * words + (size_t)i * N, te);
+#pragma unroll
+            for (int k = 0; k < 16; k++) acc0[k] = csub(acc0[k] + c[k], qi);
+        }
+        store_quads(A.out0 + o, acc0, te);
+        if (A.status && i == 0 && t == 0) A.status[g] = 1;
+    }
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_switch_sp(const DevParams P, const DevTables T,
+                                                                        const RescaleParams R, const SwitchSpArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ct_switch_sp<LOGN, false>(P, T, R, A, reinterpret_cast<uint32_t *>(smem));
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_switch_sum_sp(const DevParams P, const DevTables T,
+                                                                            const RescaleParams R, const SwitchSpArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ct_switch_sp<LOGN, true>(P, T, R, A, reinterpret_cast<uint32_t *>(smem));
+}
+
+// row_ptr set: the sum form.  LOGN 12 .. 14, as launch_ct_key_switch_sp.
+hipError_t launch_ct_switch_sp(const DevParams &P, const DevTables &T, const RescaleParams &R, const SwitchSpArgs &A,
+                               hipStream_t st)
+{
+    if (A.rows == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        const dim3 grid    = evk_grid(A.rows, A.primes);
+        const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
+        return A.row_ptr ? launch(k_ct_switch_sum_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
+                         : launch(k_ct_switch_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
     });
 }
 
@@ -2135,14 +2293,21 @@ hipError_t launch_lintrans_fold(const DevParams &P, const uint32_t *key_in, uint
 // The diagonal term of an evaluation key on the [R][np][n] slab the public-key chain wrote:
 //   key0[2j + t][j][k] += 2^(15 t) . d[k]  mod q_j,  t = 0, 1   (2^15 < q_j: the factor is its own residue),
 // d = s_hat^2 for the relinearisation key (SIGMA false; g unused), d[k] = s_hat[src_g(k)] -- sigma_g(s) in NTT form --
-// for the Galois key of element g (SIGMA true; g is odd and below 2n, checked by the host).
+// for the Galois key of element g (SIGMA true; g is odd and below 2n, checked by the host).  The third target, d = the
+// row as it is, is a switching key's (special-prime rows only; g unused): the caller passes the canonical NTT form of
+// the OTHER secret key, the one the key hides.
 // d < q_j < 2^30 lives in a register only; d 2^15 + key0 < 2^46.  grid n / 256.
-template <int LOGN, bool SIGMA>
+enum DiagTarget { kDiagSquare, kDiagSigma, kDiagOther };
+template <bool SIGMA>
+constexpr DiagTarget kDiagOf = SIGMA ? kDiagSigma : kDiagSquare;
+template <int LOGN, DiagTarget TARGET>
 __device__ __forceinline__ uint64_t evk_diag_target(const DevParams &P, uint32_t j, uint32_t g, uint32_t c,
                                                     const uint32_t *__restrict__ s_hat)
 {
-    if constexpr (SIGMA)
+    if constexpr (TARGET == kDiagSigma)
         return s_hat[galois_src<LOGN>(c, g)];
+    else if constexpr (TARGET == kDiagOther)
+        return s_hat[c];
     else
         return barrett64((uint64_t)s_hat[c] * s_hat[c], P.q[j], P.cr_hi[j], P.cr_lo[j]);
 }
@@ -2153,7 +2318,7 @@ __global__ __launch_bounds__(kLcThreads) void k_evk_diag(const DevParams P, uint
 {
     const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
     const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
-    const uint64_t d = evk_diag_target<LOGN, SIGMA>(P, j, g, c, s_hat);
+    const uint64_t d = evk_diag_target<LOGN, kDiagOf<SIGMA>>(P, j, g, c, s_hat);
 #pragma unroll
     for (uint32_t dg = 0; dg < 2; dg++)
     {
@@ -2164,24 +2329,43 @@ __global__ __launch_bounds__(kLcThreads) void k_evk_diag(const DevParams P, uint
 
 // The special-prime key's diagonal on its [np - 1][np][n] slab: key0[j][j][k] += (P mod q_j) . d[k] mod q_j for a data
 // prime j < np - 1, P = q_{np-1} and d as above.  (P mod q_j) d + key0 < 2^60 + 2^30.
-template <int LOGN, bool SIGMA>
-__global__ __launch_bounds__(kLcThreads) void k_evk_diag_sp(const DevParams P, uint32_t j, uint32_t g,
-                                                         const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ key0)
+template <int LOGN, DiagTarget TARGET>
+__device__ __forceinline__ void evk_diag_sp(const DevParams &P, uint32_t j, uint32_t g,
+                                            const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ key0)
 {
     const uint32_t c = blockIdx.x * kLcThreads + threadIdx.x;
     const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
-    const uint64_t d = evk_diag_target<LOGN, SIGMA>(P, j, g, c, s_hat);
+    const uint64_t d = evk_diag_target<LOGN, TARGET>(P, j, g, c, s_hat);
     uint32_t *p      = key0 + (((size_t)j * P.nprimes + j) << LOGN) + c;
     *p               = barrett64(d * (P.q[P.nprimes - 1] % q) + *p, q, cr_hi, cr_lo);
 }
 
-// elt 0: the relinearisation key's diagonal; else the Galois key's of that element.  sp: the special-prime key's rows
-hipError_t launch_evk_diag(const DevParams &P, uint32_t j, uint32_t elt, bool sp, const uint32_t *s_hat, uint32_t *key0,
-                           hipStream_t st)
+template <int LOGN, bool SIGMA>
+__global__ __launch_bounds__(kLcThreads) void k_evk_diag_sp(const DevParams P, uint32_t j, uint32_t g,
+                                                         const uint32_t *__restrict__ s_hat, uint32_t *__restrict__ key0)
 {
+    evk_diag_sp<LOGN, kDiagOf<SIGMA>>(P, j, g, s_hat, key0);
+}
+
+// a switching key's diagonal: key0[j][j][k] += (P mod q_j) . s_from_hat[k], s_from_hat the NTT form mod q_j of the key it hides
+template <int LOGN>
+__global__ __launch_bounds__(kLcThreads) void k_evk_diag_switch_sp(const DevParams P, uint32_t j,
+                                                                const uint32_t *__restrict__ s_from_hat,
+                                                                uint32_t *__restrict__ key0)
+{
+    evk_diag_sp<LOGN, kDiagOther>(P, j, 0, s_from_hat, key0);
+}
+
+// elt 0: the relinearisation key's diagonal; else the Galois key's of that element.  sp: the special-prime key's rows.
+// other: a switching key's diagonal (special-prime rows only), s_hat = the NTT form of the key it hides.
+hipError_t launch_evk_diag(const DevParams &P, uint32_t j, uint32_t elt, bool sp, const uint32_t *s_hat, uint32_t *key0,
+                           hipStream_t st, bool other)
+{
+    if (other && !sp) return hipErrorInvalidValue;
     return for_logn(P.logn, [&](auto l) {
         constexpr int L = decltype(l)::value;
         const dim3 grid(P.n / kLcThreads), block(kLcThreads);
+        if (other) return launch(k_evk_diag_switch_sp<L>, grid, block, 0, st, P, j, s_hat, key0);
         if (sp)
             return elt ? launch(k_evk_diag_sp<L, true>, grid, block, 0, st, P, j, elt, s_hat, key0)
                        : launch(k_evk_diag_sp<L, false>, grid, block, 0, st, P, j, elt, s_hat, key0);

@@ -244,6 +244,32 @@ struct KeySwitchSpArgs
 };
 hipError_t launch_ct_key_switch_sp(const DevParams &, const DevTables &, const RescaleParams &, const KeySwitchSpArgs &,
                                    hipStream_t);
+// Switch-key ring (k_ct_switch_sp, k_ct_switch_sum_sp): `ring` holds K key blocks of the layout above, `stride` words
+// apart; record b is switched under block key_idx[b].  An output row takes the records idx[row_ptr[g] .. row_ptr[g + 1])
+// (the sum form, CSR rows as LincombArgs, unweighted), or the one record g (row_ptr = idx = NULL, rows = B).  With
+// D_{b,j} = centred(INTT_j(c1[b][j])) and E as above:
+//   acc_k[i] = sum_{b in row} sum_{j < primes} NTT_i(D_{b,j} mod q_i) . ring[key_idx[b]]_k[j][i],  i in E;
+//   delta_k = centred(INTT_p(acc_k[p]), P);   ks_k[i] = (acc_k[i] - NTT_i(delta_k mod q_i)) . P^-1   mod q_i;
+//   out0[g][i] = ks_0[i] + sum_{b in row} c0[b][i],   out1[g][i] = ks_1[i]:   one division by P per row.
+// status[g] (optional): 1; 2 with an all-zero row in both slabs for a record index >= B, a member's key index >= K or a
+// row_ptr pair that decreases or passes nnz.  An empty row is all zero with status 1.
+struct SwitchSpArgs
+{
+    const uint32_t *c0, *c1;        // [B][primes][n]
+    uint32_t *out0, *out1;          // [rows][primes][n]
+    const uint32_t *ring;
+    const uint32_t *key_idx;        // [B]
+    const uint32_t *row_ptr, *idx;  // [rows + 1], [nnz]; both NULL: row g is the record g
+    uint8_t *status;                // [rows], optional
+    size_t half;                    // words of one key half: R' np 2 n
+    size_t stride;                  // words from one key block to the next: 2 half
+    size_t B, rows, nnz;            // each below 2^32
+    uint32_t K;                     // keys in the ring
+    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
+    uint32_t primes;                // 1 .. np - 1
+};
+hipError_t launch_ct_switch_sp(const DevParams &, const DevTables &, const RescaleParams &, const SwitchSpArgs &,
+                               hipStream_t);
 // Hoisted rotations (k_ct_galois_hoist): G rotations of every record from ONE digit decomposition of c1.  The digits
 // D_{j,t} are those of the canonical coefficients of INTT_j(c1[b][j]) itself; sigma is applied to the TRANSFORMED digits,
 // where it is the permutation src_g:
@@ -399,10 +425,11 @@ hipError_t launch_bsgs_permute(const DevParams &, const uint32_t *in, uint32_t *
 // companions).  evk_diag: key0[2j + t][j][k] += 2^(15 t) . d[k] mod q_j for t = 0, 1 on an [R][np][n]
 // slab, s_hat = the canonical NTT(s) mod q_j, [n]: d = s_hat^2 with elt 0 (the relinearisation key), d[k] =
 // s_hat[src_elt(k)], sigma_elt(s) in NTT form, else (the Galois key of elt).  sp: the special-prime key's slab
-// [np - 1][np][n] instead, key0[j][j][k] += (q_{np-1} mod q_j) . d[k] for j < np - 1.
+// [np - 1][np][n] instead, key0[j][j][k] += (q_{np-1} mod q_j) . d[k] for j < np - 1.  other (sp only): a switching key,
+// d = s_hat as it is, the caller passing the canonical NTT form of the secret key the switching key hides.
 hipError_t launch_relin_key_rows(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, hipStream_t);
 hipError_t launch_evk_diag(const DevParams &, uint32_t j, uint32_t elt, bool sp, const uint32_t *s_hat,
-                           uint32_t *key0, hipStream_t);
+                           uint32_t *key0, hipStream_t, bool other = false);
 // key-ring install and the sanitising / rejecting passes of a keyed call (encode_encrypt.hip)
 //   ring_secret_ntt : K packed secret keys [K][n/4] -> (NTT(s) mod q_j, Shoup) pairs of prime j of each ring key
 //   ring_pairs      : K public-key slabs [K][np][n] (NTT form) -> [K][np][n][2] (value, Shoup)

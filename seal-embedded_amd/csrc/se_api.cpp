@@ -492,6 +492,38 @@ int se_amd_ct_drop_primes_device(se_amd_ctx *ctx, const uint32_t *d_in0, const u
     return ctx->c.ct_drop_primes(d_in0, d_in1, B, primes_in, primes_out, d_out0, d_out1, as_stream(stream));
 }
 
+int se_amd_gen_switch_keys_sp(se_amd_ctx *ctx, size_t K, const uint8_t *sk_from, const uint8_t *sk_to,
+                              const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *wk0, uint32_t *wk1)
+{
+    if (!ctx || !sk_from || !sk_to || !a_seeds || !e_seeds || !wk0 || !wk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.gen_switch_keys(K, sk_from, sk_to, a_seeds, e_seeds, wk0, wk1);
+}
+
+int se_amd_set_switch_keyring_sp(se_amd_ctx *ctx, size_t K, const uint32_t *wk0, const uint32_t *wk1)
+{
+    if (!ctx || !wk0 || !wk1) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.set_switch_keyring(K, wk0, wk1);
+}
+
+int se_amd_ct_switch_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                     const uint32_t *d_key_idx, uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status,
+                                     void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_switch_keyed_sp(d_c0, d_c1, B, primes, d_key_idx, false, 0, nullptr, nullptr, 0, d_out0, d_out1,
+                                     d_status, as_stream(stream));
+}
+
+int se_amd_ct_switch_sum_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
+                                         size_t primes, const uint32_t *d_key_idx, size_t G, const uint32_t *d_row_ptr,
+                                         const uint32_t *d_idx, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                                         uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_switch_keyed_sp(d_c0, d_c1, B, primes, d_key_idx, true, G, d_row_ptr, d_idx, nnz, d_out0, d_out1,
+                                     d_status, as_stream(stream));
+}
+
 int se_amd_ct_galois_many_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                  const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, void *stream)
 {

@@ -578,6 +578,17 @@ int Context::gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, cons
     DevBuf<uint32_t> s_hat{Secret::yes};           // evaluation key: NTT(s) mod the current prime, [K][n] (every row the same)
     const size_t nkeys = relin ? 1 : K;            // secret keys behind the K rows
     if (relin) SEAMD_HIP(s_hat.grow((size_t)K * n));
+    // switching key: the packed key it hides, its NTT form mod the current prime [n] and the two rows the chain step that
+    // makes it writes beside (a public-key row under that key: secret as well)
+    const bool other = chain.kind == KeyChain::kSwitch;
+    DevBuf<uint8_t> other_key{Secret::yes};
+    DevBuf<uint32_t> other_hat{Secret::yes};
+    if (other)
+    {
+        SEAMD_HIP(other_key.grow(n / 4));
+        SEAMD_HIP(other_hat.grow((size_t)3 * n));
+        SEAMD_HIP(hipMemcpy(other_key, chain.other, n / 4, hipMemcpyHostToDevice));
+    }
     SEAMD_HIP(seeds.grow(K * 192));
     SEAMD_HIP(keys.grow(nkeys * (n / 4)));
     SEAMD_HIP(codes.grow((size_t)K * n));
@@ -631,9 +642,21 @@ int Context::gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, cons
         sa.c0 = pk0 + (size_t)j * n;
         sa.j  = (int)j;
         SEAMD_HIP(launch_lower_sym_prime(dp, dt, sa, K, nullptr));
-        if (relin && (!chain.sp || j + 1 < np))   // the special prime's own column has no diagonal
-            SEAMD_HIP(launch_evk_diag(dp, j, chain.kind == KeyChain::kGalois ? chain.elt : 0, chain.sp, s_hat, pk0,
-                                      nullptr));
+        if (!relin || (chain.sp && j + 1 == np)) continue;   // the special prime's own column has no diagonal
+        if (other)
+        {
+            // NTT_j of the hidden key, made the way s_save makes s_hat: the same step on one polynomial
+            LowerSymArgs oa = sa;
+            oa.s_small   = other_key;
+            oa.s_stride  = 0;
+            oa.s_save    = other_hat;
+            oa.c0        = other_hat + n;
+            oa.ntt_pte   = other_hat + (size_t)2 * n;
+            oa.c0_stride = 0;
+            SEAMD_HIP(launch_lower_sym_prime(dp, dt, oa, 1, nullptr));
+        }
+        SEAMD_HIP(launch_evk_diag(dp, j, chain.kind == KeyChain::kGalois ? chain.elt : 0, chain.sp,
+                                  other ? other_hat.get() : s_hat.get(), pk0, nullptr, other));
     }
     SEAMD_HIP(hipDeviceSynchronize());
     if (sk_out) SEAMD_HIP(hipMemcpy(sk_out, keys, K * (n / 4), hipMemcpyDeviceToHost));
@@ -1430,9 +1453,15 @@ int Context::ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const
 int Context::build_evk(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage,
                        DevBuf<uint32_t> &block)
 {
+    SEAMD_HIP(block.grow(4 * R * hp.nprimes * hp.n));
+    return build_evk_at(k0, k1, R, stage, block);
+}
+
+// the same into 4 R np n words the caller owns: one block of a ring
+int Context::build_evk_at(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage, uint32_t *block)
+{
     const size_t slab = R * hp.nprimes * hp.n;
     SEAMD_HIP(stage.grow(2 * slab));
-    SEAMD_HIP(block.grow(4 * slab));
     SEAMD_HIP(hipMemcpy(stage, k0, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
     SEAMD_HIP(hipMemcpy(stage + slab, k1, slab * sizeof(uint32_t), hipMemcpyHostToDevice));
     SEAMD_HIP(launch_relin_key_rows(dp, stage, block, 2 * R, nullptr));
@@ -1612,6 +1641,100 @@ int Context::ct_key_switch_sp(const uint32_t *d_a0, const uint32_t *d_a1, const 
     ka.key  = key;
     ka.elt  = elt;
     SEAMD_HIP(launch_ct_key_switch_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ka, st));
+    return 0;
+}
+
+// Switching keys: per key k the chain of gen_relin_key's special-prime form under sk_to on that key's block of seeds,
+// with the diagonal (q_{np-1} mod q_j) . NTT_j(s_from_k) instead of s_hat^2: row j hides P . s_from_k under s_to.  Needs
+// BOTH secrets -- it belongs to whoever issued the device keys -- and installs nothing.
+int Context::gen_switch_keys(size_t K, const uint8_t *sk_from, const uint8_t *sk_to, const uint8_t *a_seeds,
+                             const uint8_t *e_seeds, uint32_t *wk0_out, uint32_t *wk1_out)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    if (K == 0)
+    {
+        set_last_error("switching keys: at least one source key");
+        return kErrInvalid;
+    }
+    if (!evk_secret_ok(sk_to)) return kErrInvalid;
+    for (size_t k = 0; k < K; k++)
+        if (!evk_secret_ok(sk_from + k * (hp.n / 4))) return kErrInvalid;
+    std::lock_guard<std::mutex> lk(mu);
+    const size_t R = evk_rows(true), slab = R * hp.nprimes * hp.n;
+    for (size_t k = 0; k < K; k++)
+    {
+        const int rc = gen_keys_chain({KeyChain::kSwitch, 0, true, sk_from + k * (hp.n / 4)}, R, sk_to, nullptr,
+                                      a_seeds + k * R * 64, e_seeds + k * R * 64, nullptr, wk0_out + k * slab,
+                                      wk1_out + k * slab);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// The ring is public material, validated and built by the rule of set_relin_key: beside the installed ring, every
+// block by build_evk_at (which ends in a synchronisation: calls already enqueued have finished on the old ring), and
+// swapped in at the end.  Anything refused, or a HIP call that fails, leaves the previous ring installed and usable.
+int Context::set_switch_keyring(size_t K, const uint32_t *wk0, const uint32_t *wk1)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    if (K == 0 || K >= ((size_t)1 << 32))
+    {
+        set_last_error("switch-key ring: between 1 and 2^32 - 1 keys");
+        return kErrInvalid;
+    }
+    const size_t R = evk_rows(true), slab = R * hp.nprimes * hp.n;
+    if (const size_t r = first_unreduced_row(hp, wk0, wk1, K * R); r != K * R)
+    {
+        set_last_error("switch-key ring: key " + std::to_string(r / R) + ", row " + std::to_string(r % R) +
+                       " holds a word not reduced modulo its prime");
+        return kErrInvalid;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    SEAMD_HIP(hipSetDevice(device));
+    DevBuf<uint32_t> stage, ring;
+    SEAMD_HIP(ring.grow(K * 4 * slab));
+    for (size_t k = 0; k < K; k++)
+        if (int rc = build_evk_at(wk0 + k * slab, wk1 + k * slab, R, stage, ring + k * 4 * slab)) return rc;
+    d_switch_ring = std::move(ring);
+    switch_keys   = K;
+    return 0;
+}
+
+// One launch, no scratch, no secret key, no host synchronisation; reads the installed switch-key ring.  The key indices
+// are compared with K inside the kernel (status 2), never sanitised on the way.  sum: the CSR rows of ct_lincomb.
+int Context::ct_switch_keyed_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                                const uint32_t *d_key_idx, bool sum, size_t G, const uint32_t *d_row_ptr,
+                                const uint32_t *d_idx, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                                uint8_t *d_status, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    constexpr size_t k32 = (size_t)1 << 32;
+    SwitchSpArgs sa{};
+    if (!evk_call_args(sa, {d_c0, d_c1, d_out0, d_out1}, B, primes, true) || !d_key_idx) return kErrInvalid;
+    if (sum &&(!d_row_ptr || (!d_idx && nnz) || G >= k32 || nnz >= k32)) return kErrInvalid;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!switch_keys)
+    {
+        set_last_error("no switch-key ring is installed (se_amd_set_switch_keyring_sp)");
+        return kErrNoKey;
+    }
+    const size_t rows = sum ? G : B;
+    if (rows == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    sa.c0      = d_c0;
+    sa.c1      = d_c1;
+    sa.out0    = d_out0;
+    sa.out1    = d_out1;
+    sa.ring    = d_switch_ring;
+    sa.key_idx = d_key_idx;
+    sa.row_ptr = sum ? d_row_ptr : nullptr;
+    sa.idx     = sum ? d_idx : nullptr;
+    sa.status  = d_status;
+    sa.stride  = 2 * sa.half;
+    sa.rows    = rows;
+    sa.nnz     = nnz;
+    sa.K       = (uint32_t)switch_keys;
+    SEAMD_HIP(launch_ct_switch_sp(dp, dt, host_rescale_params(hp, hp.nprimes), sa, st));
     return 0;
 }
 

@@ -97,6 +97,10 @@ struct Context
     DevBuf<uint32_t> d_ring_pk0, d_ring_pk1;   // [K][np][n][2]
     size_t ring_sk = 0, ring_pk = 0;           // keys in each ring (0 = no ring)
     EvalKeys evk[2];                           // the installed evaluation keys: [0] digit, [1] special-prime (index: sp)
+    // the switch-key ring (se_amd_set_switch_keyring_sp): K special-prime key blocks [2][np - 1][np][2][n] back to back,
+    // an installed set of its own (public material); record b of a switch call uses block key_idx[b]
+    DevBuf<uint32_t> d_switch_ring;
+    size_t switch_keys = 0;                    // keys in the ring (0 = no ring)
     DevBuf<uint32_t> d_kidx;                   // [cap] key index of each record, clamped below K (keyed calls)
     DevBuf<uint32_t> d_kbad;                   // [1 + cap] count + records whose index was out of range
 
@@ -256,6 +260,17 @@ struct Context
                          uint32_t elt, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     int ct_drop_primes(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes_in, size_t primes_out,
                        uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+    // switch-key ring: K special-prime keys that hide P . s_from_k under s_to (host pointers, [K][np - 1][np][n] per
+    // half; the generator needs both secrets and installs nothing), the ring built beside the installed one, and the
+    // switch of record b under ring key key_idx[b] (SwitchSpArgs): one record per output row, or with d_row_ptr the CSR
+    // rows summed with one division by P per row; one launch, no scratch, no sanitising pass
+    int gen_switch_keys(size_t K, const uint8_t *sk_from, const uint8_t *sk_to, const uint8_t *a_seeds,
+                        const uint8_t *e_seeds, uint32_t *wk0_out, uint32_t *wk1_out);
+    int set_switch_keyring(size_t K, const uint32_t *wk0, const uint32_t *wk1);
+    int ct_switch_keyed_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                           const uint32_t *d_key_idx, bool sum, size_t G, const uint32_t *d_row_ptr,
+                           const uint32_t *d_idx, size_t nnz, uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status,
+                           hipStream_t st);
     // hoisted rotations (GaloisHoistArgs): G rotations of every record from one digit decomposition, each to its own
     // output (sum false: outputs [G][B][primes][n]) or summed into one record, with the record itself when add_input
     // (sum true: outputs [B][primes][n]); elts is a host pointer; one launch, no scratch
@@ -344,12 +359,15 @@ private:
     // What the K rows of a gen_keys_chain are: independent key pairs (gen_keys_batch), or the K = 2 np rows of an
     // evaluation key under ONE secret key (sk_in, n/4 bytes) with its diagonal term added to pk0 -- that of the
     // relinearisation key, or that of the Galois key of `elt`.  sp: the K = np - 1 rows of a special-prime key, whose
-    // diagonal carries q_{np-1} mod q_j on row j instead of the digit weights on rows 2j, 2j + 1.
+    // diagonal carries q_{np-1} mod q_j on row j instead of the digit weights on rows 2j, 2j + 1.  kSwitch (sp only): the
+    // rows are under sk_in and the diagonal is (q_{np-1} mod q_j) . NTT_j(other), `other` the packed secret key the
+    // switching key hides (host pointer, n/4 bytes).
     struct KeyChain
     {
-        enum Kind { kPairs, kRelin, kGalois } kind;
+        enum Kind { kPairs, kRelin, kGalois, kSwitch } kind;
         uint32_t elt = 0;   // kGalois only
         bool sp      = false;
+        const uint8_t *other = nullptr;   // kSwitch only
     };
     // the launch chain of gen_keys_batch.  The caller holds `mu`.
     int gen_keys_chain(KeyChain chain, size_t K, const uint8_t *sk_in, const uint8_t *sk_seeds, const uint8_t *pk_seeds,
@@ -359,6 +377,7 @@ private:
     size_t evk_rows(bool sp) const { return sp ? hp.nprimes - 1 : 2 * hp.nprimes; }
     bool special_prime_ok() const;
     int build_evk(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage, DevBuf<uint32_t> &block);
+    int build_evk_at(const uint32_t *k0, const uint32_t *k1, size_t R, DevBuf<uint32_t> &stage, uint32_t *block);
     template <class Args>
     bool evk_call_args(Args &a, std::initializer_list<const void *> slabs, size_t B, size_t primes, bool sp = false) const;
     bool galois_elt_ok(uint32_t elt) const { return (elt & 1) && elt < 2 * hp.n; }   // odd and below 2n
