@@ -6,7 +6,7 @@ second module needs moves here (device code) or to ct_model (definitions and inp
 - dev_t, host_u32, bits, stream_of, same_bytes: host <-> device and bit-pattern conveniences.
 - SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY: the C ABI's error codes; SEED_A, SEED_B, SEED_PK, SEED_EP: the golden seeds.
 - the receiving side: records, encrypt_sym, fresh_records, ntt_secret, decode_expect, expectation (oracle + Python ints),
-  run_decrypt (decrypt_full / decrypt_level and their keyed twins over sentinel-filled outputs), assert_matches,
+  run_decrypt (decrypt_full / decrypt_level / decrypt3_level and their keyed twins over filled outputs), assert_matches,
   check_level_decrypt.
 - ciphertext operations (tests/test_gpu_ct_*.py): SENTINEL, sentinel_out, take (outputs with guard words behind them); one
   runner per entry (run_relin, run_galois, run_many, run_sum, run_plan and the special-prime run_relin_sp,
@@ -108,10 +108,10 @@ def expectation(o, c0, c1, s_hat, scale=None):
 
 
 def run_decrypt(env, ctx, c0, c1, primes=None, scale=None, key_idx=None,
-                want=("pte", "values", "values_f64", "status")):
-    """decrypt_full[_keyed], or with `primes` or `scale` (the other defaults to the context's) decrypt_level[_keyed], into
-    outputs pre-filled with -7 (status: 77).  -> all four outputs whatever `want` selects: one that was not requested
-    must keep its fill."""
+                want=("pte", "values", "values_f64", "status"), c2=None):
+    """decrypt_full[_keyed], or with `primes` or `scale` (the other defaults to the context's) decrypt_level[_keyed], or
+    with a third slab `c2` decrypt3_level[_keyed], into outputs pre-filled with -7 (status: 77).  -> all four outputs
+    whatever `want` selects: one that was not requested must keep its fill."""
     torch = env["torch"]
     B, n = c0.shape[0], ctx.n
     out = dict(pte=torch.full((B, n), -7, dtype=torch.int64, device=env["dev"]),
@@ -120,7 +120,10 @@ def run_decrypt(env, ctx, c0, c1, primes=None, scale=None, key_idx=None,
                status=torch.full((B,), 77, dtype=torch.uint8, device=env["dev"]))
     kw = {k: out[k] for k in want}
     keyed = () if key_idx is None else (key_idx,)
-    if primes is None and scale is None:
+    if c2 is not None:
+        (ctx.decrypt3_level if key_idx is None else ctx.decrypt3_level_keyed)(
+            c0, c1, c2, *keyed, ctx.np if primes is None else primes, ctx.scale() if scale is None else scale, **kw)
+    elif primes is None and scale is None:
         (ctx.decrypt_full if key_idx is None else ctx.decrypt_full_keyed)(c0, c1, *keyed, **kw)
     else:
         (ctx.decrypt_level if key_idx is None else ctx.decrypt_level_keyed)(

@@ -1,15 +1,19 @@
 """Full-modulus decrypt and decode (-m gpu): se_amd_decrypt_full_device recombines all primes of a ciphertext on the GPU.
 Every expectation is built from the oracle's primitives (decrypt, intt, fft) and Python integers, never from the code
 under test; every comparison is bit-exact except the reference's own acceptance criterion |values - input| < 0.1
-(device/test/ckks_tests_common.c:132)."""
+(device/test/ckks_tests_common.c:132).  The constructed records at the end (tests/recv_model.py) are planted Python integers,
+one for every branch of the recombination: the record's own integers are the expectation."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, dev_t, encrypt_sym, env,  # noqa: F401
-                         expectation, host_u32, ntt_secret, records, run_decrypt, run_example, stream_of)
+from ct_model import CASE_IDS
+from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, decode_expect, dev_t,  # noqa: F401
+                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, run_example, stream_of)
+from recv_model import SHAPES as RECV_SHAPES
+from recv_model import ciphertext_of, expect_at_level, in_range_vectors, out_of_range_vectors
 
 pytestmark = pytest.mark.gpu
 
@@ -301,3 +305,169 @@ def test_full_size(env):
 def test_roundtrip_example(env, tmp_path):
     """examples/batch_roundtrip.c from plain gcc: values around +-1000 come back within the reference's 0.1."""
     run_example("batch_roundtrip", tmp_path, ("4096", "3", "16"))
+
+
+# ---- constructed plaintexts: every branch of the recombination decides a record (tests/recv_model.py) ---------------------
+LEVELS = {(4096, 3): (1, 2, 3), (8192, 6): (1, 2, 3, 4, 5, 6), (16384, 13): (1, 2, 3, 4, 8, 12, 13)}
+
+
+@pytest.fixture(scope="module")
+def recv_cases(env):
+    """recv_cases(shape) -> computed once and left unchanged: a context with one secret key installed, the oracle, the
+    named vectors (the first n_in in range, the rest out of range) and host slabs c0, c1 [B][np][n] that decrypt to them."""
+    from oracle.pyoracle import Oracle
+    cache = {}
+
+    def get(shape):
+        if shape not in cache:
+            n, npr = shape
+            o = Oracle(n, npr)
+            ctx = env["pkg"].Context(n, npr)
+            sk = V.secret_key(n, seed=3)
+            ctx.set_secret_key(sk)
+            s_hat = ntt_secret(o, sk)
+            inside = in_range_vectors(o)
+            named = inside + ([(r["name"], r["vec"]) for r in out_of_range_vectors(o)] if npr >= 3 else [])
+            rng = np.random.default_rng(31 * n + npr)
+            rows = [ciphertext_of(o, vec, s_hat, rng) for _, vec in named]
+            cache[shape] = dict(ctx=ctx, o=o, named=named, n_in=len(inside), c0=np.stack([r[0] for r in rows]),
+                                c1=np.stack([r[1] for r in rows]))
+        return cache[shape]
+
+    yield get
+    for c in cache.values():
+        c["ctx"].close()
+
+
+def assert_planted(got, b, o, y, what, scale=None):
+    """Record b has status 1, pte equal to the Python integers y and values_f64 / values bit-equal to the oracle's decode
+    of them."""
+    pte = np.array(y, dtype=np.int64)
+    f64 = decode_expect(o, pte, scale)
+    assert_matches(got, b, dict(status=1, pte=pte, values_f64=f64, values=f64.astype(np.float32)), what)
+
+
+@pytest.mark.parametrize("shape", RECV_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_constructed_in_range(env, recv_cases, shape):
+    """The in-range records: zero, and every multiple and half-way point of the primes and of q_0 q_1 with both ends of
+    int64 (np <= 2: of the centred range of Q), each held by a low and by a high thread.  Status 1, pte the planted
+    integers, both decodes bit-equal to the oracle's decode of them."""
+    c = recv_cases(shape)
+    k = c["n_in"]
+    got = run_decrypt(env, c["ctx"], dev_t(env, c["c0"][:k]), dev_t(env, c["c1"][:k]))
+    for b, (name, vec) in enumerate(c["named"][:k]):
+        assert_planted(got, b, c["o"], vec, (shape, name))
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6), (16384, 13)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_constructed_out_of_range(env, recv_cases, shape):
+    """Every out-of-range record (ONE coefficient outside int64, decided at the prime recv_model names, at a rotating
+    position) has status 0; the in-range records interleaved in the same call keep status 1 and their exact outputs."""
+    c = recv_cases(shape)
+    k, B = c["n_in"], len(c["named"])
+    order = []
+    for i, b in enumerate(range(k, B)):
+        if i % 2 == 0:
+            order.append((i // 2) % k)
+        order.append(b)
+    order.append(0)
+    assert len(order) <= 40
+    got = run_decrypt(env, c["ctx"], dev_t(env, c["c0"][order]), dev_t(env, c["c1"][order]))
+    for at, b in enumerate(order):
+        name, vec = c["named"][b]
+        if b < k:
+            assert_planted(got, at, c["o"], vec, (shape, at, name))
+        else:
+            assert int(got["status"][at]) == 0, (shape, at, name)
+
+
+@pytest.mark.parametrize("shape,p", [(s, p) for s in LEVELS for p in LEVELS[s]], ids=CASE_IDS)
+def test_levels_cut_the_recombination(env, recv_cases, shape, p):
+    """decrypt_level with primes = p on the first p rows of the full-chain slab stops after p primes: status and, where
+    it is 1, pte and the decodes are those of the coefficients' centred representatives mod q_0 ... q_{p-1}.  A record
+    12345 + q_0 ... q_{j-1} is 12345 at level j and out of range from level j + 1 on."""
+    c = recv_cases(shape)
+    o, ctx = c["o"], c["ctx"]
+    got = run_decrypt(env, ctx, dev_t(env, c["c0"][:, :p]), dev_t(env, c["c1"][:, :p]), primes=p)
+    seen = set()
+    for b, (name, vec) in enumerate(c["named"]):
+        status, y = expect_at_level(o, vec, p)
+        seen.add(status)
+        if status == 1:
+            assert_planted(got, b, o, y, (shape, p, name), ctx.scale())
+        else:
+            assert int(got["status"][b]) == 0, (shape, p, name)
+    assert seen == ({1} if p <= 2 else {0, 1}), (shape, p)
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (8192, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_constructed_keyed_and_degree2(env, shape):
+    """The same vectors through decrypt_full_keyed, decrypt3_level and decrypt3_level_keyed: record b is built under key
+    b mod 3 of a ring of three distinct keys (degree 2: c0 = m - c1 s - c2 s^2 with random c1, c2), the unkeyed degree-2
+    records under the installed key.  The expectations are the planted integers; a last record with index K comes back
+    with status 2 and zeros."""
+    from oracle.pyoracle import Oracle
+    torch = env["torch"]
+    n, npr = shape
+    K = 3
+    o = Oracle(n, npr)
+    ctx = env["pkg"].Context(n, npr)
+    sks = [V.secret_key(n, seed=s) for s in (11, 12, 13)]
+    assert len({sk.tobytes() for sk in sks}) == K
+    s_hats = [ntt_secret(o, sk) for sk in sks]
+    ctx.set_secret_keyring(np.stack(sks))
+    ctx.set_secret_key(sks[1])
+    inside = in_range_vectors(o)
+    named = inside + [(r["name"], r["vec"]) for r in out_of_range_vectors(o)]
+    B = len(named)
+    idx = np.arange(B + 1, dtype=np.uint32) % K
+    idx[B] = K
+    rng = np.random.default_rng(7 * n + npr)
+    source = list(range(B)) + [0]                       # the rejected record is a copy of record 0's vector
+
+    def slabs(degree, key_of):
+        rows = [ciphertext_of(o, named[b][1], s_hats[key_of(at)], rng, degree) for at, b in enumerate(source)]
+        return [dev_t(env, np.stack([r[i] for r in rows])) for i in range(degree + 1)]
+
+    def check(got, what, rejected):
+        for b, (name, vec) in enumerate(named):
+            if b < len(inside):
+                assert_planted(got, b, o, vec, (shape, what, name))
+            else:
+                assert int(got["status"][b]) == 0, (shape, what, name)
+        if rejected:
+            assert int(got["status"][B]) == 2, what
+            for f in ("pte", "values", "values_f64"):
+                assert int(torch.count_nonzero(got[f][B])) == 0, (what, f)
+        else:
+            assert_planted(got, B, o, named[0][1], (shape, what, "copy of record 0"))
+
+    ring_key = lambda at: int(idx[at]) % K  # noqa: E731  (the rejected record is built under key 0)
+    ti = dev_t(env, idx)
+    c0, c1 = slabs(1, ring_key)
+    check(run_decrypt(env, ctx, c0, c1, key_idx=ti), "full_keyed", True)
+    c0, c1, c2 = slabs(2, ring_key)
+    check(run_decrypt(env, ctx, c0, c1, key_idx=ti, c2=c2), "decrypt3_level_keyed", True)
+    c0, c1, c2 = slabs(2, lambda at: 1)
+    check(run_decrypt(env, ctx, c0, c1, c2=c2), "decrypt3_level", False)
+    ctx.close()
+
+
+@pytest.mark.parametrize("shape", [(4096, 3), (1024, 1)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_zero_record_single_prime_entry(env, recv_cases, shape):
+    """The zero record (c0 = -c1 s with random c1: every word of c0 + c1 s is q or 0 before the reduction) through
+    se_amd_decrypt_decode_device, for every prime: dec_ntt, pt and values are all zero."""
+    torch = env["torch"]
+    n, npr = shape
+    c = recv_cases(shape)
+    b = [name for name, _ in c["named"]].index("zero")
+    assert not any(c["named"][b][1]) and c["c1"][b].any()
+    c0, c1 = dev_t(env, c["c0"][b:b + 1]), dev_t(env, c["c1"][b:b + 1])
+    for j in range(npr):
+        dec_ntt = torch.full((1, n), 0x5A5A5A5A, dtype=torch.int32, device=env["dev"])
+        pt = torch.full_like(dec_ntt, 0x5A5A5A5A)
+        values = torch.full((1, n // 2), -7.0, dtype=torch.float32, device=env["dev"])
+        c["ctx"].decrypt_decode(c0, c1, j, dec_ntt, pt, values)
+        torch.cuda.synchronize()
+        for name, t in (("dec_ntt", dec_ntt), ("pt", pt), ("values", values)):
+            assert int(torch.count_nonzero(t)) == 0, (shape, j, name)
