@@ -283,15 +283,16 @@ def galois_table(n, elt):
     return src
 
 
-class BsgsPlan:
-    """Handle of se_amd_bsgs_create (Context.bsgs_plan)."""
+class _Plan:
+    """Handle of a plan of the library; DESTROY names the symbol that frees it."""
+    DESTROY = None
 
     def __init__(self, L, h):
         self.L, self.h = L, h
 
     def close(self):
         if self.h:
-            self.L.se_amd_bsgs_destroy(self.h)
+            getattr(self.L, self.DESTROY)(self.h)
             self.h = None
 
     def __del__(self):
@@ -299,6 +300,16 @@ class BsgsPlan:
             self.close()
         except Exception:
             pass
+
+
+class BsgsPlan(_Plan):
+    """Handle of se_amd_bsgs_create (Context.bsgs_plan)."""
+    DESTROY = "se_amd_bsgs_destroy"
+
+
+class LintransPlan(_Plan):
+    """Handle of se_amd_lintrans_create (Context.lintrans_plan)."""
+    DESTROY = "se_amd_lintrans_destroy"
 
 
 class Group:
@@ -375,24 +386,6 @@ class Group:
         _check(self.L.se_amd_encode_ntt_multi_device(
             self.h, C.c_size_t(B), self._arr(values), self._arr(out), self._arr(status), C.c_int(gather_root),
             _ptr(out_all)), "se_amd_encode_ntt_multi_device")
-
-
-class LintransPlan:
-    """Handle of se_amd_lintrans_create (Context.lintrans_plan)."""
-
-    def __init__(self, L, h):
-        self.L, self.h = L, h
-
-    def close(self):
-        if self.h:
-            self.L.se_amd_lintrans_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Context:
@@ -858,127 +851,114 @@ class Context:
                                                            _ptr(out1), _ptr(status), _stream_ptr()),
                "se_amd_ct_switch_sum_keyed_sp_device")
 
+    # ---- the rotation family: one private helper per shape of call; the public methods name the symbol and what differs
+    def _galois_set(self, sym, in0, in1, elts, out0, out1, primes, stacked=False, flags=()):
+        """A call on a set of Galois elements: records [B][primes][n], or a stack [G][B][primes][n]; `flags` stand
+        between the elements and the outputs."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = in0.shape[2 if stacked else 1]
+        _check(getattr(self.L, sym)(self.h, _ptr(in0), _ptr(in1), in0.shape[1 if stacked else 0], primes, _ptr(el),
+                                    el.size, *flags, _ptr(out0), _ptr(out1), _stream_ptr()), sym)
+
+    def _make_plan(self, cls, sym, lists, tensors, pt_primes):
+        """A plan from host element lists and device diagonals."""
+        import numpy as np
+        els = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in lists]   # alive until the call returns
+        args = [a for el in els for a in (_ptr(el), el.size)]
+        h = C.c_void_p()
+        _check(getattr(self.L, sym)(self.h, *args, *[_ptr(t) for t in tensors], pt_primes, C.byref(h)), sym)
+        return cls(self.L, h)
+
+    def _plan_call(self, sym, plan, c0, c1, out0, out1, primes, tail=()):
+        """A plan's call on the records (c0, c1) [B][primes][n]; `tail` stands between the outputs and the stream."""
+        if primes is None:
+            primes = c0.shape[1]
+        _check(getattr(self.L, sym)(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1), c0.shape[0], primes,
+                                    _ptr(out0), _ptr(out1), *tail, _stream_ptr()), sym)
+
+    def _bsgs_call(self, sym, plan, c0, c1, out0, out1, workspace, primes, workspace_bytes):
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+        self._plan_call(sym, plan, c0, c1, out0, out1, primes, (_ptr(workspace), workspace_bytes))
+
+    def _mul_plain_sum(self, sym, in0, in1, pt, out0, out1, primes, ext):
+        """The weighted sum over a stack; ext: of extended records, whose level is one below their rows and whose
+        plaintexts have all np rows (no pt_primes argument)."""
+        if primes is None:
+            primes = in0.shape[2] - ext
+        pt_rows = () if ext else (pt.shape[2],)
+        _check(getattr(self.L, sym)(self.h, _ptr(in0), _ptr(in1), in0.shape[0], in0.shape[1], primes, _ptr(pt),
+                                    pt.shape[0], *pt_rows, _ptr(out0), _ptr(out1), _stream_ptr()), sym)
+
     def ct_galois_many(self, c0, c1, elts, out0, out1, primes=None):
         """Hoisted rotations: out[e] = the rotation of the records (c0, c1) [B][primes][n] by elts[e], for all G
         elements from ONE digit decomposition of c1, with the installed Galois keys; out0, out1 are [G][B][primes][n].
         Decrypts like ct_galois per element, but is not bit-identical to it (the digits are those of c1, permuted after
         the transform)."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if primes is None:
-            primes = c0.shape[1]
-        _check(self.L.se_amd_ct_galois_many_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el), el.size,
-                                                   _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_galois_many_device")
+        self._galois_set("se_amd_ct_galois_many_device", c0, c1, elts, out0, out1, primes)
 
     def ct_galois_sum(self, c0, c1, elts, out0, out1, add_input=False, primes=None):
         """The sum of the hoisted rotations by elts[0 .. G) in one record, plus the record itself with add_input:
         out0, out1 are [B][primes][n].  The transforms are those of one rotation whatever G is; an element listed twice
         counts twice."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if primes is None:
-            primes = c0.shape[1]
-        _check(self.L.se_amd_ct_galois_sum_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el), el.size,
-                                                  1 if add_input else 0, _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_galois_sum_device")
+        self._galois_set("se_amd_ct_galois_sum_device", c0, c1, elts, out0, out1, primes,
+                         flags=(1 if add_input else 0,))
 
     def lintrans_plan(self, elts, diag, diag0=None, pt_primes=None):
         """The plan of y = diag0 . x + sum_e diag[e] . rot_{elts[e]}(x): diag [G][pt_primes][n], diag0 [pt_primes][n] or
         None, device tensors in the layout encode_ntt writes.  Folds the diagonals into the installed Galois keys of
         `elts` (a snapshot; it synchronises) and returns an object with .close(); close it before the context."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if pt_primes is None:
-            pt_primes = diag.shape[1]
-        h = C.c_void_p()
-        _check(self.L.se_amd_lintrans_create(self.h, _ptr(el), el.size, _ptr(diag), _ptr(diag0), pt_primes,
-                                             C.byref(h)), "se_amd_lintrans_create")
-        return LintransPlan(self.L, h)
+        return self._make_plan(LintransPlan, "se_amd_lintrans_create", (elts,), (diag, diag0),
+                               diag.shape[1] if pt_primes is None else pt_primes)
 
     def ct_lintrans(self, plan, c0, c1, out0, out1, primes=None):
         """One launch: the plan's weighted sum of hoisted rotations of the records (c0, c1) [B][primes][n] ->
         (out0, out1) [B][primes][n]; the scale is multiplied by the diagonals' scale, the level is unchanged."""
-        if primes is None:
-            primes = c0.shape[1]
-        _check(self.L.se_amd_ct_lintrans_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
-                                                c0.shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_lintrans_device")
+        self._plan_call("se_amd_ct_lintrans_device", plan, c0, c1, out0, out1, primes)
 
     def ct_galois_sum_sp(self, c0, c1, elts, out0, out1, add_input=False, primes=None):
         """ct_galois_sum with the installed special-prime Galois keys on records (c0, c1) [B][primes][n], primes <=
         np - 1: the sum of the rotations by elts[0 .. G), plus the record itself with add_input, at the record's own
         scale from ONE decomposition and ONE division by the special prime.  One element without add_input gives the
         bits of ct_galois_sp; several carry one rounding instead of one each."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if primes is None:
-            primes = c0.shape[1]
-        _check(self.L.se_amd_ct_galois_sum_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el),
-                                                     el.size, 1 if add_input else 0, _ptr(out0), _ptr(out1),
-                                                     _stream_ptr()), "se_amd_ct_galois_sum_sp_device")
+        self._galois_set("se_amd_ct_galois_sum_sp_device", c0, c1, elts, out0, out1, primes,
+                         flags=(1 if add_input else 0,))
 
     def lintrans_plan_sp(self, elts, diag, diag0=None, pt_primes=None):
         """lintrans_plan on the installed special-prime Galois keys: diag [G][np][n], diag0 [np][n] or None -- the
         diagonals need ALL np rows, the one at the special prime is folded into the key.  The plan serves ct_lintrans_sp
         at the levels 1 .. np - 1."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if pt_primes is None:
-            pt_primes = diag.shape[1]
-        h = C.c_void_p()
-        _check(self.L.se_amd_lintrans_create_sp(self.h, _ptr(el), el.size, _ptr(diag), _ptr(diag0), pt_primes,
-                                                C.byref(h)), "se_amd_lintrans_create_sp")
-        return LintransPlan(self.L, h)
+        return self._make_plan(LintransPlan, "se_amd_lintrans_create_sp", (elts,), (diag, diag0),
+                               diag.shape[1] if pt_primes is None else pt_primes)
 
     def ct_lintrans_sp(self, plan, c0, c1, out0, out1, primes=None):
         """One launch: the special-prime plan's weighted sum of rotations of the records (c0, c1) [B][primes][n],
         primes <= np - 1 -> (out0, out1) [B][primes][n]; the scale is multiplied by the diagonals' scale, the level is
         unchanged and no lift is needed."""
-        if primes is None:
-            primes = c0.shape[1]
-        _check(self.L.se_amd_ct_lintrans_sp_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
-                                                   c0.shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_lintrans_sp_device")
+        self._plan_call("se_amd_ct_lintrans_sp_device", plan, c0, c1, out0, out1, primes)
 
     # ---- baby-step / giant-step linear transforms on the digit Galois keys
     def ct_mul_plain_sum(self, in0, pt, out0, in1=None, out1=None, primes=None):
         """Key-free weighted sum over a stack: in [E][B][primes][n] (one slab or two), pt [Gout][E][pt_primes][n] in
         encode_ntt's layout, out [Gout][B][primes][n]; out[g][b] = sum_e pt[g][e] . in[e][b] mod q_i, canonical.  Any
         32-bit plaintext word stands for its residue."""
-        E, B = in0.shape[0], in0.shape[1]
-        if primes is None:
-            primes = in0.shape[2]
-        _check(self.L.se_amd_ct_mul_plain_sum_device(self.h, _ptr(in0), _ptr(in1), E, B, primes, _ptr(pt), pt.shape[0],
-                                                     pt.shape[2], _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_mul_plain_sum_device")
+        self._mul_plain_sum("se_amd_ct_mul_plain_sum_device", in0, in1, pt, out0, out1, primes, 0)
 
     def ct_galois_accum(self, in0, in1, elts, out0, out1, primes=None):
         """Rotate G different records and add: in [G][B][primes][n], out[b] = sum_g ct_galois(in[g][b], elts[g]) mod q_i
         with the installed Galois keys, [B][primes][n]; element 1 is the identity and needs no key.  Bit-identical to
         the modular sum of G ct_galois outputs."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if primes is None:
-            primes = in0.shape[2]
-        _check(self.L.se_amd_ct_galois_accum_device(self.h, _ptr(in0), _ptr(in1), in0.shape[1], primes, _ptr(el),
-                                                    el.size, _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_galois_accum_device")
+        self._galois_set("se_amd_ct_galois_accum_device", in0, in1, elts, out0, out1, primes, stacked=True)
 
     def bsgs_plan(self, baby, giant, diag, pt_primes=None):
         """The plan of y = sum_{g,b} diag[g][b] . rot_{giant[g] baby[b] mod 2n}(x): diag [n2][n1][pt_primes][n], a device
         tensor in the layout encode_ntt writes, the diagonal of the COMPOSITE element unrotated.  A snapshot of the
         diagonals only (it synchronises); keys are read at call time.  Returns an object with .close(); close it before
         the context."""
-        import numpy as np
-        bs = np.ascontiguousarray(baby, dtype=np.uint32).reshape(-1)
-        gs = np.ascontiguousarray(giant, dtype=np.uint32).reshape(-1)
-        if pt_primes is None:
-            pt_primes = diag.shape[2]
-        h = C.c_void_p()
-        _check(self.L.se_amd_bsgs_create(self.h, _ptr(bs), bs.size, _ptr(gs), gs.size, _ptr(diag), pt_primes,
-                                         C.byref(h)), "se_amd_bsgs_create")
-        return BsgsPlan(self.L, h)
+        return self._make_plan(BsgsPlan, "se_amd_bsgs_create", (baby, giant), (diag,),
+                               diag.shape[2] if pt_primes is None else pt_primes)
 
     def bsgs_workspace_bytes(self, plan, records, primes):
         """Bytes of workspace ct_bsgs needs to take `records` records of level `primes` in one chunk."""
@@ -988,13 +968,7 @@ class Context:
         """The plan's transform of the records (c0, c1) [B][primes][n] -> (out0, out1) [B][primes][n]: the many form for
         the baby steps, ct_mul_plain_sum, ct_galois_accum for the giant steps, in chunks of what `workspace` (a device
         tensor, 16-byte aligned) holds.  Every chunk size gives the same bits."""
-        if primes is None:
-            primes = c0.shape[1]
-        if workspace_bytes is None:
-            workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
-        _check(self.L.se_amd_ct_bsgs_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
-                                            c0.shape[0], primes, _ptr(out0), _ptr(out1), _ptr(workspace),
-                                            workspace_bytes, _stream_ptr()), "se_amd_ct_bsgs_device")
+        self._bsgs_call("se_amd_ct_bsgs_device", plan, c0, c1, out0, out1, workspace, primes, workspace_bytes)
 
     # ---- baby-step / giant-step linear transforms on the special-prime keys, division by P deferred
     def ct_galois_many_ext_sp(self, c0, c1, elts, out0, out1, primes=None):
@@ -1002,23 +976,12 @@ class Context:
         L modulo q_r, row L modulo the special prime), out[e] = P times the rotation by elts[e] plus its key-switch sum,
         from ONE decomposition of c1 under the installed special-prime keys.  Element 1 needs no key.  ct_mod_down_sp
         of out[e] is ct_galois_sp by elts[e]."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if primes is None:
-            primes = c0.shape[1]
-        _check(self.L.se_amd_ct_galois_many_ext_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el),
-                                                          el.size, _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_galois_many_ext_sp_device")
+        self._galois_set("se_amd_ct_galois_many_ext_sp_device", c0, c1, elts, out0, out1, primes)
 
     def ct_mul_plain_sum_ext_sp(self, in0, pt, out0, in1=None, out1=None, primes=None):
         """ct_mul_plain_sum on stacks of extended records: in [E][B][L+1][n], pt [Gout][E][np][n] (all np rows: row L of
         a record meets the plaintext's row at the special prime), out [Gout][B][L+1][n].  primes = L."""
-        E, B = in0.shape[0], in0.shape[1]
-        if primes is None:
-            primes = in0.shape[2] - 1
-        _check(self.L.se_amd_ct_mul_plain_sum_ext_sp_device(self.h, _ptr(in0), _ptr(in1), E, B, primes, _ptr(pt),
-                                                            pt.shape[0], _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_mul_plain_sum_ext_sp_device")
+        self._mul_plain_sum("se_amd_ct_mul_plain_sum_ext_sp_device", in0, in1, pt, out0, out1, primes, 1)
 
     def ct_mod_down_sp(self, in0, out0, in1=None, out1=None, primes=None, count=None):
         """The division by the special prime, rounded: extended records [..][L+1][n] (one slab or two) -> [..][L][n].
@@ -1034,38 +997,19 @@ class Context:
         """Rotate G different records under the special-prime keys and add, with ONE division by the special prime: in
         [G][B][L][n] -> [B][L][n].  Element 1 is the identity.  G = 1 has the bytes of ct_galois_sp; G >= 2 rounds once
         where G calls round G times."""
-        import numpy as np
-        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
-        if primes is None:
-            primes = in0.shape[2]
-        _check(self.L.se_amd_ct_galois_accum_sp_device(self.h, _ptr(in0), _ptr(in1), in0.shape[1], primes, _ptr(el),
-                                                       el.size, _ptr(out0), _ptr(out1), _stream_ptr()),
-               "se_amd_ct_galois_accum_sp_device")
+        self._galois_set("se_amd_ct_galois_accum_sp_device", in0, in1, elts, out0, out1, primes, stacked=True)
 
     def bsgs_plan_sp(self, baby, giant, diag, pt_primes=None):
         """bsgs_plan for ct_bsgs_sp: diag [n2][n1][np][n] with ALL np rows.  Diagonals only; the special-prime keys are
         read at call time.  The plan serves the levels 1 .. np - 1."""
-        import numpy as np
-        bs = np.ascontiguousarray(baby, dtype=np.uint32).reshape(-1)
-        gs = np.ascontiguousarray(giant, dtype=np.uint32).reshape(-1)
-        if pt_primes is None:
-            pt_primes = diag.shape[2]
-        h = C.c_void_p()
-        _check(self.L.se_amd_bsgs_create_sp(self.h, _ptr(bs), bs.size, _ptr(gs), gs.size, _ptr(diag), pt_primes,
-                                            C.byref(h)), "se_amd_bsgs_create_sp")
-        return BsgsPlan(self.L, h)
+        return self._make_plan(BsgsPlan, "se_amd_bsgs_create_sp", (baby, giant), (diag,),
+                               diag.shape[2] if pt_primes is None else pt_primes)
 
     def ct_bsgs_sp(self, plan, c0, c1, out0, out1, workspace, primes=None, workspace_bytes=None):
         """The special-prime plan's transform of fresh records (c0, c1) [B][L][n], L <= np - 1 -> [B][L][n] at the
         record's scale times the diagonals': ct_galois_many_ext_sp, ct_mul_plain_sum_ext_sp, ct_mod_down_sp,
         ct_galois_accum_sp in chunks of what `workspace` holds.  Every chunk size gives the same bits."""
-        if primes is None:
-            primes = c0.shape[1]
-        if workspace_bytes is None:
-            workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
-        _check(self.L.se_amd_ct_bsgs_sp_device(self.h, plan.h if plan is not None else None, _ptr(c0), _ptr(c1),
-                                               c0.shape[0], primes, _ptr(out0), _ptr(out1), _ptr(workspace),
-                                               workspace_bytes, _stream_ptr()), "se_amd_ct_bsgs_sp_device")
+        self._bsgs_call("se_amd_ct_bsgs_sp_device", plan, c0, c1, out0, out1, workspace, primes, workspace_bytes)
 
     def prng_blocks(self, seeds, ctrs, out, outlen):
         _check(self.L.se_amd_prng_blocks_device(self.h, _ptr(seeds), _ptr(ctrs), _ptr(out), outlen,

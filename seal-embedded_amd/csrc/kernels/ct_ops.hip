@@ -1799,7 +1799,7 @@ constexpr int kManyExtGroup = kHoistGroup;
 
 template <int LOGN>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_many_ext_sp(const DevParams P, const DevTables T,
-                                                                                 const GaloisManyExtSpArgs A)
+                                                                                 const GaloisSetArgs A)
 {
     using G          = XformGeom<LOGN>;
     constexpr int N  = G::N;
@@ -1895,7 +1895,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_many_ext
 }
 
 // LOGN 12 .. 14 only, by the rule of launch_ct_key_switch_sp.
-hipError_t launch_ct_galois_many_ext_sp(const DevParams &P, const DevTables &T, const GaloisManyExtSpArgs &A,
+hipError_t launch_ct_galois_many_ext_sp(const DevParams &P, const DevTables &T, const GaloisSetArgs &A,
                                         hipStream_t st)
 {
     if (A.B == 0) return hipSuccess;
@@ -1923,7 +1923,7 @@ hipError_t launch_ct_galois_many_ext_sp(const DevParams &P, const DevTables &T, 
 template <int LOGN>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum_sp(const DevParams P, const DevTables T,
                                                                               const RescaleParams R,
-                                                                              const GaloisAccumSpArgs A)
+                                                                              const GaloisSetArgs A)
 {
     using G         = XformGeom<LOGN>;
     constexpr int N = G::N;
@@ -1951,7 +1951,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum_sp
             {
                 const uint32_t g = A.elt[s];
                 if (g == 1) continue;
-                const uint32_t *sw = A.in1 + ((size_t)s * A.B + b) * A.primes * N;
+                const uint32_t *sw = A.c1 + ((size_t)s * A.B + b) * A.primes * N;
                 for (uint32_t j = 0; j < A.primes; j++)
                 {
                     uint32_t y[16];
@@ -1983,17 +1983,17 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum_sp
             uint32_t c[16];
             if (g != 1)
             {
-                load_row_sigma<LOGN, true>(c, A.in0 + o, g, lds, te);
+                load_row_sigma<LOGN, true>(c, A.c0 + o, g, lds, te);
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc0[e] = csub(acc0[e] + c[e], qi);
                 __syncthreads();   // the next park writes the plane the gather reads
             }
             else
             {
-                load_quads(c, A.in0 + o, te);
+                load_quads(c, A.c0 + o, te);
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc0[e] = csub(acc0[e] + c[e], qi);
-                load_quads(c, A.in1 + o, te);
+                load_quads(c, A.c1 + o, te);
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc1[e] = csub(acc1[e] + c[e], qi);
             }
@@ -2007,7 +2007,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum_sp
 
 // LOGN 12 .. 14 only, by the rule of launch_ct_key_switch_sp.
 hipError_t launch_ct_galois_accum_sp(const DevParams &P, const DevTables &T, const RescaleParams &R,
-                                     const GaloisAccumSpArgs &A, hipStream_t st)
+                                     const GaloisSetArgs &A, hipStream_t st)
 {
     if (A.B == 0) return hipSuccess;
     if (P.logn < 12) return hipErrorInvalidValue;
@@ -2134,7 +2134,7 @@ hipError_t launch_ct_mul_plain_sum(const DevParams &P, const MulPlainSumArgs &A,
 // ------------------------------------------------------------------------------------------
 template <int LOGN>
 __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum(const DevParams P, const DevTables T,
-                                                                           const GaloisAccumArgs A)
+                                                                           const GaloisSetArgs A)
 {
     using G         = XformGeom<LOGN>;
     constexpr int N = G::N;
@@ -2163,7 +2163,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum(co
                     const int tj      = opaque_index(t);
                     const uint32_t qj = P.q[j];
                     uint32_t x[16];
-                    evk_row_coeffs<LOGN>(x, A.in1 + rec + (size_t)j * N, j, P, T, lds, tj);
+                    evk_row_coeffs<LOGN>(x, A.c1 + rec + (size_t)j * N, j, P, T, lds, tj);
                     // sigma, the scatter of k_ct_galois (its own copy: see there)
 #pragma unroll
                     for (int e = 0; e < 16; e++)
@@ -2181,7 +2181,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum(co
             const int te   = opaque_index(t);
             const size_t o = rec + (size_t)i * N;
             uint32_t c[16];
-            load_quads(c, A.in0 + o, te);
+            load_quads(c, A.c0 + o, te);
             if (g != 1)
             {
                 const int k4 = quad_index(te, 0);
@@ -2199,7 +2199,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum(co
                 __syncthreads();   // the next transpose writes the plane the gather reads
             else
             {
-                load_quads(c, A.in1 + o, te);
+                load_quads(c, A.c1 + o, te);
 #pragma unroll
                 for (int e = 0; e < 16; e++)
                 {
@@ -2221,7 +2221,7 @@ __global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_galois_accum(co
     }
 }
 
-hipError_t launch_ct_galois_accum(const DevParams &P, const DevTables &T, const GaloisAccumArgs &A, hipStream_t st)
+hipError_t launch_ct_galois_accum(const DevParams &P, const DevTables &T, const GaloisSetArgs &A, hipStream_t st)
 {
     if (A.B == 0) return hipSuccess;
     return for_logn(P.logn, [&](auto l) {

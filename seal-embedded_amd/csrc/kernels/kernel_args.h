@@ -188,7 +188,7 @@ struct MulArgs
     uint32_t primes;
 };
 hipError_t launch_ct_mul(const DevParams &, const MulArgs &, hipStream_t);
-// The key switch of ct_ops.hip, shared by every kernel from here to HoistSpArgs (evk_row_coeffs, evk_digits, evk_mac;
+// The key switch of ct_ops.hip, shared by every kernel from here to launch_ct_galois_accum_sp (evk_row_coeffs, evk_digits, evk_mac;
 // grid evk_grid(B, primes)).  `key` is one device evaluation-key block, built
 // by Context::build_evk from the host's two halves: [2][R][np][2][n], R = 2 np rows of the CONTEXT's np columns, each
 // column a row of n key words followed by the row of their Shoup companions floor(w 2^32 / q_i); half 1 starts `half`
@@ -279,39 +279,38 @@ hipError_t launch_ct_switch_sp(const DevParams &, const DevTables &, const Resca
 // (c0, c1)[b] + sum_e rot[elt[e]], outputs [B][primes][n].  The elements and the key block of each travel in the
 // argument block (kernarg): no device table, no scratch.
 constexpr uint32_t kMaxGaloisKeys = 64;   // elements of one installed set, and of one call (SE_AMD_MAX_GALOIS_KEYS)
-struct GaloisHoistArgs
+// The element-set block: what every kernel of a set of Galois elements reads alike, filled on the host by
+// Context::evk_call_args (batch and key layout) and Context::resolve_keys (elements and key blocks).  The slab layouts
+// differ per kernel and stand at its launcher.
+struct GaloisSetArgs
 {
-    const uint32_t *c0, *c1;        // [B][primes][n]
-    uint32_t *out0, *out1;          // many: [G][B][primes][n]; sum: [B][primes][n]
-    size_t half;                    // words of one key half: R np 2 n
+    const uint32_t *c0, *c1;        // the input slabs
+    uint32_t *out0, *out1;          // the output slabs
+    size_t half;                    // words of one key half: R np 2 n (R' = np - 1 rows on the special-prime keys)
     size_t B;
-    uint32_t np;                    // columns of a key row (the context's primes)
-    uint32_t primes;                // 1 .. np
+    uint32_t np;                    // columns of a key row (the context's primes; >= 2 on the special-prime keys)
+    uint32_t primes;                // 1 .. np (1 .. np - 1 on the special-prime keys)
     uint32_t G;                     // 1 .. kMaxGaloisKeys
-    uint32_t sum, add_input;        // 0 / 1 each; add_input only with sum
     uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kMaxGaloisKeys];   // the device key block of elt[e]
+    const uint32_t *key[kMaxGaloisKeys];   // the device key block of elt[e]; NULL where the kernel needs none (elt[e] == 1)
 };
+struct GaloisHoistArgs : GaloisSetArgs
+{
+    uint32_t sum, add_input;        // 0 / 1 each; add_input only with sum
+};
+// in [B][primes][n]; out many: [G][B][primes][n], sum: [B][primes][n]
 hipError_t launch_ct_galois_hoist(const DevParams &, const DevTables &, const GaloisHoistArgs &, hipStream_t);
 // Linear transform (k_ct_lintrans): the sum form above with a plaintext weight per element, the diagonal method
 //   out0[b][i][k] = d0[i][k] c0[b][i][k] + sum_e d_e[i][k] rot0[elt[e]][b][i][k]   (out1: c1 and rot1)   mod q_i.
 // d_e does not depend on the key row, so it is folded into the key block when the plan is made (k_lintrans_fold):
 // key[e] holds gk . d_e mod q_i with its Shoup companions in the installed block's layout, and the digit loop is the sum
 // form's.  Only the epilogue carries weights: the (word, Shoup) rows diag[e][np][2][n], and diag0 [np][2][n] or NULL.
-struct LintransArgs
+struct LintransArgs : GaloisSetArgs   // key[e]: the folded key block of entry e; primes 1 .. the plan's levels
 {
-    const uint32_t *c0, *c1;        // [B][primes][n]
-    uint32_t *out0, *out1;          // [B][primes][n]
-    size_t half;                    // words of one key half: R np 2 n
-    size_t B;
-    uint32_t np;                    // columns of a key row (the context's primes)
-    uint32_t primes;                // 1 .. the plan's levels
-    uint32_t G;                     // 1 .. kMaxGaloisKeys
     const uint32_t *diag;           // [G][np][2][n]
     const uint32_t *diag0;          // [np][2][n], or NULL: the record itself does not enter
-    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kMaxGaloisKeys];   // the folded key block of entry e
 };
+// in, out [B][primes][n]
 hipError_t launch_ct_lintrans(const DevParams &, const DevTables &, const LintransArgs &, hipStream_t);
 // Hoisted rotations on the special-prime key (k_ct_galois_sum_sp, k_ct_lintrans_sp): the sum form and the linear
 // transform above on blocks [2][R'][np][2][n] of R' = np - 1 rows, records of `primes` <= np - 1 rows.  With D_j =
@@ -324,21 +323,13 @@ hipError_t launch_ct_lintrans(const DevParams &, const DevTables &, const Lintra
 //     folded in on every column (np - 1 included), diag / diag0 as in LintransArgs.
 // One decomposition and one division by P per record whatever G is.  The constants P^-1 mod q_i are the RescaleParams of
 // level np.
-struct HoistSpArgs
+struct HoistSpArgs : GaloisSetArgs
 {
-    const uint32_t *c0, *c1;        // [B][primes][n]
-    uint32_t *out0, *out1;          // [B][primes][n]
-    size_t half;                    // words of one key half: R' np 2 n
-    size_t B;
-    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
-    uint32_t primes;                // 1 .. np - 1
-    uint32_t G;                     // 1 .. kMaxGaloisKeys
     uint32_t weighted, add_input;   // 0 / 1 each; add_input only without weighted
     const uint32_t *diag;           // weighted: [G][np][2][n]
     const uint32_t *diag0;          // weighted: [np][2][n], or NULL: the record itself does not enter
-    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kMaxGaloisKeys];   // the key block of entry e
 };
+// in, out [B][primes][n]
 hipError_t launch_ct_hoist_sp(const DevParams &, const DevTables &, const RescaleParams &, const HoistSpArgs &,
                               hipStream_t);
 // Plan set-up (k_lintrans_fold), one entry per launch.  d = diag_in[i][k] mod q_i for columns i < pt, 0 beyond (any
@@ -366,57 +357,24 @@ struct MulPlainSumArgs
 hipError_t launch_ct_mul_plain_sum(const DevParams &, const MulPlainSumArgs &, hipStream_t);
 // Rotate different ciphertexts and add (k_ct_galois_accum): out[b] = sum_{g < G} rho_g(in[g][b]) mod q_i, canonical, rho_g
 // the map of GaloisArgs with elt[g] and key[g]; elt[g] == 1 is the identity (key[g] unused).  The elements and the key
-// block of each travel in the argument block, as in GaloisHoistArgs.
-struct GaloisAccumArgs
-{
-    const uint32_t *in0, *in1;      // [G][B][primes][n]
-    uint32_t *out0, *out1;          // [B][primes][n]
-    size_t half;                    // words of one key half: R np 2 n
-    size_t B;
-    uint32_t np;                    // columns of a key row (the context's primes)
-    uint32_t primes;                // 1 .. np
-    uint32_t G;                     // 1 .. kMaxGaloisKeys; G B below 2^32
-    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kMaxGaloisKeys];   // the device key block of elt[g]; NULL where elt[g] == 1
-};
-hipError_t launch_ct_galois_accum(const DevParams &, const DevTables &, const GaloisAccumArgs &, hipStream_t);
+// block of each travel in the argument block, a GaloisSetArgs as it is.
+// in (c0, c1) [G][B][primes][n], out [B][primes][n]; G B below 2^32
+hipError_t launch_ct_galois_accum(const DevParams &, const DevTables &, const GaloisSetArgs &, hipStream_t);
 // Baby steps on the special-prime keys, UNDIVIDED (k_ct_galois_many_ext_sp): G rotations of a level-`primes` record
 // (primes <= np - 1) as extended records of primes + 1 rows -- rows r < primes modulo q_r, row `primes` modulo P = q_{np-1}
 // -- from ONE decomposition of c1.  With D_j, F_{j,i}, E and src_e as in HoistSpArgs and i_r = r, or np - 1 for r = primes:
 //   out_k[e][b][r][x] = sum_{j < primes} F_{j,i_r}[src_e(x)] . key_k[e][j][i_r][x]  (+ (P mod q_r) . c0[b][r][src_e(x)] for
 //   k = 0, r < primes)   mod q_{i_r}, canonical.  elt[e] == 1: out_k = (P mod q_r) . c_k[b][r], row `primes` zero, no key.
 // "P times the rotated ciphertext plus the key-switch sum": k_ct_mod_down_sp of it is the rotation by elt[e].
-struct GaloisManyExtSpArgs
-{
-    const uint32_t *c0, *c1;        // [B][primes][n]
-    uint32_t *out0, *out1;          // [G][B][primes + 1][n]
-    size_t half;                    // words of one key half: R' np 2 n
-    size_t B;
-    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
-    uint32_t primes;                // 1 .. np - 1
-    uint32_t G;                     // 1 .. kMaxGaloisKeys; G B below 2^32
-    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kMaxGaloisKeys];   // the special-prime key block of elt[e]; NULL where elt[e] == 1
-};
-hipError_t launch_ct_galois_many_ext_sp(const DevParams &, const DevTables &, const GaloisManyExtSpArgs &, hipStream_t);
+// in [B][primes][n], out [G][B][primes + 1][n]; G B below 2^32; key[e] the special-prime block of elt[e]
+hipError_t launch_ct_galois_many_ext_sp(const DevParams &, const DevTables &, const GaloisSetArgs &, hipStream_t);
 // Giant steps on the special-prime keys with ONE division (k_ct_galois_accum_sp): G different level-`primes` records
 // (a^g, b^g) = in[g][b] are rotated and added.  With D^g_j = centred(INTT_j(sigma_g(b^g[j])), q_j) for the keyed g (elt[g]
 // != 1):  acc_k[i] = sum_g sum_j NTT_i(D^g_j mod q_i) . key_k[g][j][i], i in E;  delta_k, ks_k as in KeySwitchSpArgs;
 //   out0 = ks_0 + sum_{keyed g} sigma_g(a^g) + sum_{elt[g] == 1} a^g,   out1 = ks_1 + sum_{elt[g] == 1} b^g.
-struct GaloisAccumSpArgs
-{
-    const uint32_t *in0, *in1;      // [G][B][primes][n]
-    uint32_t *out0, *out1;          // [B][primes][n]
-    size_t half;                    // words of one key half: R' np 2 n
-    size_t B;
-    uint32_t np;                    // columns of a key row (the context's primes, >= 2)
-    uint32_t primes;                // 1 .. np - 1
-    uint32_t G;                     // 1 .. kMaxGaloisKeys; G B below 2^32
-    uint32_t elt[kMaxGaloisKeys];   // odd, below 2n (checked by the host: the kernel forms LDS addresses from them)
-    const uint32_t *key[kMaxGaloisKeys];   // the special-prime key block of elt[g]; NULL where elt[g] == 1
-};
-hipError_t launch_ct_galois_accum_sp(const DevParams &, const DevTables &, const RescaleParams &,
-                                     const GaloisAccumSpArgs &, hipStream_t);
+// in (c0, c1) [G][B][primes][n], out [B][primes][n]; G B below 2^32; key[g] the special-prime block of elt[g]
+hipError_t launch_ct_galois_accum_sp(const DevParams &, const DevTables &, const RescaleParams &, const GaloisSetArgs &,
+                                     hipStream_t);
 // Plan set-up: out[r][k] = in[r][src_elt(k)] on `rows` rows of n words, src the permutation of the automorphism of `elt`
 // (odd, below 2n, checked by the host) on a bit-reversed NTT-form row.
 hipError_t launch_bsgs_permute(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, uint32_t elt,

@@ -590,7 +590,8 @@ int se_amd_ct_galois_sum_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const 
                                    void *stream)
 {
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
-    return ctx->c.ct_galois_sum_sp(d_c0, d_c1, B, primes, elts, G, add_input != 0, d_out0, d_out1, as_stream(stream));
+    return ctx->c.ct_galois_hoist(d_c0, d_c1, B, primes, elts, G, true, add_input != 0, d_out0, d_out1,
+                                  as_stream(stream), true);
 }
 
 int se_amd_ct_lintrans_sp_device(se_amd_ctx *ctx, const se_amd_lintrans *plan, const uint32_t *d_c0,
@@ -657,9 +658,8 @@ void se_amd_bsgs_destroy(se_amd_bsgs *plan)
 size_t se_amd_bsgs_workspace_bytes(const se_amd_bsgs *plan, size_t records, size_t primes)
 {
     if (!plan) return 0;
-    if (plan->p.sp)
-        return records * seamd::Context::bsgs_sp_record_bytes(plan->p.baby.size(), plan->p.giant.size(), primes, plan->p.n);
-    return records * 2 * (plan->p.baby.size() + plan->p.giant.size()) * primes * plan->p.n * sizeof(uint32_t);
+    const seamd::BsgsPlan &p = plan->p;
+    return records * seamd::Context::bsgs_record_bytes(p.sp, p.baby.size(), p.giant.size(), primes, p.n);
 }
 
 int se_amd_ct_bsgs_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B,
@@ -684,7 +684,7 @@ int se_amd_ct_mul_plain_sum_ext_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0
                                           uint32_t *d_out1, void *stream)
 {
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
-    return ctx->c.ct_mul_plain_sum_ext_sp(d_in0, d_in1, E, B, primes, d_pt, Gout, d_out0, d_out1, as_stream(stream));
+    return ctx->c.ct_mul_plain_sum(d_in0, d_in1, E, B, primes, d_pt, Gout, 0, d_out0, d_out1, as_stream(stream), true);
 }
 
 int se_amd_ct_mod_down_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, const uint32_t *d_in1, size_t count,
@@ -699,7 +699,7 @@ int se_amd_ct_galois_accum_sp_device(se_amd_ctx *ctx, const uint32_t *d_in0, con
                                      void *stream)
 {
     if (!ctx) return SE_ERR_INVALD_ARGUMENT;
-    return ctx->c.ct_galois_accum_sp(d_in0, d_in1, B, primes, elts, G, d_out0, d_out1, as_stream(stream));
+    return ctx->c.ct_galois_accum(d_in0, d_in1, B, primes, elts, G, d_out0, d_out1, as_stream(stream), true);
 }
 
 int se_amd_ct_bsgs_sp_device(se_amd_ctx *ctx, const se_amd_bsgs *plan, const uint32_t *d_c0, const uint32_t *d_c1,

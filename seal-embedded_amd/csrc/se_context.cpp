@@ -1526,6 +1526,50 @@ const uint32_t *Context::galois_key(bool sp, uint32_t elt) const
     return key;
 }
 
+// evk_call_args on an element-set block, whose four slabs it fills too (a composite replaces them per chunk).
+bool Context::set_call_args(GaloisSetArgs &a, const uint32_t *c0, const uint32_t *c1, uint32_t *out0, uint32_t *out1,
+                            size_t B, size_t primes, bool sp) const
+{
+    if (!evk_call_args(a, {c0, c1, out0, out1}, B, primes, sp)) return false;
+    a.c0   = c0;
+    a.c1   = c1;
+    a.out0 = out0;
+    a.out1 = out1;
+    return true;
+}
+
+// The elements of a call and the installed block of each in a family, into the block.  one_keyless: element 1 is the
+// identity and needs no key (NULL).  kErrNoKey, with galois_key's last error, at the first element without its key.  The
+// caller holds `mu` and has checked the elements (galois_elts_ok).
+int Context::resolve_keys(GaloisSetArgs &a, const uint32_t *elts, size_t G, bool sp, bool one_keyless) const
+{
+    a.G = (uint32_t)G;
+    for (size_t e = 0; e < G; e++)
+    {
+        const bool keyless = one_keyless && elts[e] == 1;
+        a.elt[e] = elts[e];
+        a.key[e] = keyless ? nullptr : galois_key(sp, elts[e]);
+        if (!keyless && !a.key[e]) return kErrNoKey;
+    }
+    return 0;
+}
+
+// A plan serves the context that made it, the entry of its kind and the levels up to its own; else the last error is
+// set.  `what` names the transform, `create` the digit-key creator, `level_msg` what a level above the plan's means.
+template <class Plan>
+bool Context::plan_ok(const Plan *plan, bool sp, size_t primes, const char *what, const char *create,
+                      const char *level_msg) const
+{
+    if (plan && plan->owner == this && plan->sp == sp && primes <= plan->levels) return true;
+    const std::string w = std::string(what) + ": ", c = create;
+    set_last_error(w + (!plan ? "no plan"
+                        : plan->owner != this ? "the plan belongs to another context"
+                        : plan->sp != sp ? (sp ? "a digit-key plan (" + c + ") does not serve the special-prime entry"
+                                               : "a special-prime plan (" + c + "_sp) does not serve the digit-key entry")
+                                         : std::string(level_msg)));
+    return false;
+}
+
 // Evaluation keys are public material: validated like a public key (a word >= q_i is refused), then built beside the
 // installed key and swapped in once every call already enqueued has finished (build_evk ends in a synchronisation).
 // Anything refused, or a HIP call that fails, leaves the previous key installed and usable.
@@ -1779,58 +1823,31 @@ int Context::ct_galois(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, siz
 // One launch, no scratch, no secret key, no host synchronisation; reads the installed Galois keys of elts[0 .. G).  The
 // checks of ct_galois in its order, the element check once per element; nothing is launched unless every element has a
 // key.  The key-block pointers travel in the argument block, so a call already enqueued keeps the blocks it was given.
+// sp (the sum form only): on the special-prime keys, the digit keys do not serve it -- the checks of ct_key_switch_sp (a
+// context of one prime, the level in [1, np - 1]) in front; one decomposition and one division by P whatever G is.
 int Context::ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
-                             size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+                             size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st,
+                             bool sp)
 {
-    GaloisHoistArgs ha{};
-    if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes)) return kErrInvalid;
+    if (sp && !special_prime_ok()) return kErrInvalid;
+    GaloisSetArgs a{};
+    if (!set_call_args(a, d_c0, d_c1, d_out0, d_out1, B, primes, sp)) return kErrInvalid;
     if (!galois_elts_ok(elts, G, "hoisted rotations: between 1 and 64 elements")) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    for (size_t e = 0; e < G; e++)
-    {
-        ha.elt[e] = elts[e];
-        ha.key[e] = galois_key(false, elts[e]);
-        if (!ha.key[e]) return kErrNoKey;
-    }
+    if (int rc = resolve_keys(a, elts, G, sp, false)) return rc;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    ha.c0        = d_c0;
-    ha.c1        = d_c1;
-    ha.out0      = d_out0;
-    ha.out1      = d_out1;
-    ha.G         = (uint32_t)G;
+    if (sp)
+    {
+        HoistSpArgs hs{a};
+        hs.add_input = add_input;
+        SEAMD_HIP(launch_ct_hoist_sp(dp, dt, host_rescale_params(hp, hp.nprimes), hs, st));
+        return 0;
+    }
+    GaloisHoistArgs ha{a};
     ha.sum       = sum;
     ha.add_input = sum && add_input;
     SEAMD_HIP(launch_ct_galois_hoist(dp, dt, ha, st));
-    return 0;
-}
-
-// The sum form on the special-prime key: ct_galois_hoist's checks in its order behind those of ct_key_switch_sp (a
-// context of one prime, the level in [1, np - 1]); reads the installed special-prime Galois keys, the digit keys do not
-// serve it.  One launch, no scratch, no host synchronisation.
-int Context::ct_galois_sum_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
-                              size_t G, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
-{
-    if (!special_prime_ok()) return kErrInvalid;
-    HoistSpArgs ha{};
-    if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
-    if (!galois_elts_ok(elts, G, "hoisted rotations: between 1 and 64 elements")) return kErrInvalid;
-    std::lock_guard<std::mutex> lk(mu);
-    for (size_t e = 0; e < G; e++)
-    {
-        ha.elt[e] = elts[e];
-        ha.key[e] = galois_key(true, elts[e]);
-        if (!ha.key[e]) return kErrNoKey;
-    }
-    if (B == 0) return 0;
-    SEAMD_HIP(hipSetDevice(device));
-    ha.c0        = d_c0;
-    ha.c1        = d_c1;
-    ha.out0      = d_out0;
-    ha.out1      = d_out1;
-    ha.G         = (uint32_t)G;
-    ha.add_input = add_input;
-    SEAMD_HIP(launch_ct_hoist_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ha, st));
     return 0;
 }
 
@@ -1854,12 +1871,8 @@ int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_d
     }
     if (!galois_elts_ok(elts, G, args_msg)) return kErrInvalid;
     std::lock_guard<std::mutex> lk(mu);
-    std::vector<const uint32_t *> from(G);
-    for (size_t e = 0; e < G; e++)
-    {
-        from[e] = galois_key(sp, elts[e]);
-        if (!from[e]) return kErrNoKey;
-    }
+    GaloisSetArgs from{};
+    if (int rc = resolve_keys(from, elts, G, sp, false)) return rc;
     SEAMD_HIP(hipSetDevice(device));
     // the diagonal columns that are folded: all of a special-prime plan's, the first pt_primes of a digit plan's
     const size_t cols = pt_primes < np ? pt_primes : np, pairs = np * 2 * n, R = evk_rows(sp), block = 2 * R * pairs;
@@ -1869,7 +1882,7 @@ int Context::lintrans_create(const uint32_t *elts, size_t G, const uint32_t *d_d
     for (size_t e = 0; e < G; e++)
     {
         SEAMD_HIP(built.keys[e].grow(block));
-        SEAMD_HIP(launch_lintrans_fold(dp, from[e], built.keys[e], R, d_diag + e * pt_primes * n,
+        SEAMD_HIP(launch_lintrans_fold(dp, from.key[e], built.keys[e], R, d_diag + e * pt_primes * n,
                                        built.diag + e * pairs, (uint32_t)cols, nullptr));
     }
     if (d_diag0)
@@ -1891,69 +1904,96 @@ int Context::ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const u
                          uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp)
 {
     if (sp && !special_prime_ok()) return kErrInvalid;
-    LintransArgs la{};
-    HoistSpArgs ha{};
-    if (!(sp ? evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes, true)
-             : evk_call_args(la, {d_c0, d_c1, d_out0, d_out1}, B, primes)))
+    GaloisSetArgs a{};
+    if (!set_call_args(a, d_c0, d_c1, d_out0, d_out1, B, primes, sp)) return kErrInvalid;
+    if (!plan_ok(plan, sp, primes, "linear transform", "se_amd_lintrans_create",
+                 "the plan's diagonals have fewer primes than the call"))
         return kErrInvalid;
-    if (!plan || plan->owner != this || plan->sp != sp || primes > plan->levels)
-    {
-        set_last_error(!plan ? "linear transform: no plan"
-                       : plan->owner != this ? "linear transform: the plan belongs to another context"
-                       : plan->sp != sp ? (sp ? "linear transform: a digit-key plan (se_amd_lintrans_create) does not serve "
-                                                "the special-prime entry"
-                                              : "linear transform: a special-prime plan (se_amd_lintrans_create_sp) does "
-                                                "not serve the digit-key entry")
-                                        : "linear transform: the plan's diagonals have fewer primes than the call");
-        return kErrInvalid;
-    }
     if (B == 0) return 0;
     std::lock_guard<std::mutex> lk(mu);
     SEAMD_HIP(hipSetDevice(device));
     const size_t G = plan->elts.size(), pairs = hp.nprimes * 2 * hp.n;
     const uint32_t *diag0 = plan->diag0 ? plan->diag + G * pairs : nullptr;
-    if (sp)
-    {
-        ha.c0       = d_c0;
-        ha.c1       = d_c1;
-        ha.out0     = d_out0;
-        ha.out1     = d_out1;
-        ha.G        = (uint32_t)G;
-        ha.weighted = 1;
-        ha.diag     = plan->diag;
-        ha.diag0    = diag0;
-        for (size_t e = 0; e < G; e++)
-        {
-            ha.elt[e] = plan->elts[e];
-            ha.key[e] = plan->keys[e];
-        }
-        SEAMD_HIP(launch_ct_hoist_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ha, st));
-        return 0;
-    }
-    la.c0    = d_c0;
-    la.c1    = d_c1;
-    la.out0  = d_out0;
-    la.out1  = d_out1;
-    la.G     = (uint32_t)G;
-    la.diag  = plan->diag;
-    la.diag0 = diag0;
+    a.G = (uint32_t)G;
     for (size_t e = 0; e < G; e++)
     {
-        la.elt[e] = plan->elts[e];
-        la.key[e] = plan->keys[e];
+        a.elt[e] = plan->elts[e];
+        a.key[e] = plan->keys[e];
     }
+    if (sp)
+    {
+        HoistSpArgs hs{a};
+        hs.weighted = 1;
+        hs.diag     = plan->diag;
+        hs.diag0    = diag0;
+        SEAMD_HIP(launch_ct_hoist_sp(dp, dt, host_rescale_params(hp, hp.nprimes), hs, st));
+        return 0;
+    }
+    LintransArgs la{a};
+    la.diag  = plan->diag;
+    la.diag0 = diag0;
     SEAMD_HIP(launch_ct_lintrans(dp, dt, la, st));
     return 0;
 }
 
+// The unchecked halves of the step entries below, which the composites (ct_bsgs, ct_bsgs_sp) call too: fill the argument
+// block and launch.  The caller has made the entry's checks and has the device current.  `primes` is the LEVEL of the
+// records; sp: extended records of primes + 1 rows, the last one modulo the special prime against row np - 1 of
+// plaintexts that have all np rows.  These alone know that convention.
+int Context::mul_plain_sum_step(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
+                                const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0, uint32_t *d_out1,
+                                bool sp, hipStream_t st)
+{
+    MulPlainSumArgs ma{};
+    ma.in0        = d_in0;
+    ma.in1        = d_in1;
+    ma.pt         = d_pt;
+    ma.out0       = d_out0;
+    ma.out1       = d_out1;
+    ma.B          = (uint32_t)B;
+    ma.E          = (uint32_t)E;
+    ma.Gout       = (uint32_t)Gout;
+    ma.primes     = (uint32_t)(primes + sp);
+    ma.pt_primes  = (uint32_t)(sp ? hp.nprimes : pt_primes);
+    ma.last_prime = (uint32_t)(sp ? hp.nprimes : primes) - 1;
+    SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
+    return 0;
+}
+
+int Context::mod_down_sp_step(const uint32_t *d_in0, const uint32_t *d_in1, size_t count, size_t primes,
+                              uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    RescaleArgs ra{};
+    ra.in0    = d_in0;
+    ra.in1    = d_in1;
+    ra.out0   = d_out0;
+    ra.out1   = d_out1;
+    ra.primes = (uint32_t)primes + 1;
+    ra.drop   = (uint32_t)hp.nprimes - 1;
+    SEAMD_HIP(launch_ct_mod_down_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ra, count, st));
+    return 0;
+}
+
+int Context::galois_accum_step(const GaloisSetArgs &aa, bool sp, hipStream_t st)
+{
+    if (sp)
+        SEAMD_HIP(launch_ct_galois_accum_sp(dp, dt, host_rescale_params(hp, hp.nprimes), aa, st));
+    else
+        SEAMD_HIP(launch_ct_galois_accum(dp, dt, aa, st));
+    return 0;
+}
+
 // Key-free, one launch, nothing of the context is written.  The checks of ct_mul_plain, then the stack's.
+// sp: on stacks of extended records, behind the check of ct_key_switch_sp for a context of one prime; the level is in
+// [1, np - 1] and pt_primes is not read.
 int Context::ct_mul_plain_sum(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
                               const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0, uint32_t *d_out1,
-                              hipStream_t st)
+                              hipStream_t st, bool sp)
 {
     constexpr size_t k32 = (size_t)1 << 32;
+    if (sp && !special_prime_ok()) return kErrInvalid;
     if (!d_in0 || !d_out0 || !d_pt || !d_in1 != !d_out1) return kErrInvalid;
-    if (primes < 1 || primes > hp.nprimes || pt_primes < primes || pt_primes >= k32) return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes - sp || (!sp && (pt_primes < primes || pt_primes >= k32))) return kErrInvalid;
     if (B >= k32 || !aligned16({d_in0, d_in1, d_out0, d_out1, d_pt})) return kErrInvalid;
     if (E < 1 || E > kMaxGaloisKeys || Gout < 1 || Gout > kMaxGaloisKeys || E * B >= k32 || Gout * B >= k32)
     {
@@ -1962,29 +2002,18 @@ int Context::ct_mul_plain_sum(const uint32_t *d_in0, const uint32_t *d_in1, size
     }
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    MulPlainSumArgs ma{};
-    ma.in0       = d_in0;
-    ma.in1       = d_in1;
-    ma.pt        = d_pt;
-    ma.out0      = d_out0;
-    ma.out1      = d_out1;
-    ma.B         = (uint32_t)B;
-    ma.E         = (uint32_t)E;
-    ma.Gout      = (uint32_t)Gout;
-    ma.primes    = (uint32_t)primes;
-    ma.pt_primes = (uint32_t)pt_primes;
-    ma.last_prime = (uint32_t)primes - 1;
-    SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
-    return 0;
+    return mul_plain_sum_step(d_in0, d_in1, E, B, primes, d_pt, Gout, pt_primes, d_out0, d_out1, sp, st);
 }
 
 // One launch, no scratch, no secret key, no host synchronisation; reads the installed Galois keys of the elements other
 // than 1.  The checks of ct_galois_hoist in its order, then G B; nothing is launched unless every such element has a key.
+// sp: on the special-prime keys with ONE division by P, the checks of ct_key_switch_sp in front.
 int Context::ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
-                             size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+                             size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp)
 {
-    GaloisAccumArgs aa{};
-    if (!evk_call_args(aa, {d_in0, d_in1, d_out0, d_out1}, B, primes)) return kErrInvalid;
+    if (sp && !special_prime_ok()) return kErrInvalid;
+    GaloisSetArgs aa{};
+    if (!set_call_args(aa, d_in0, d_in1, d_out0, d_out1, B, primes, sp)) return kErrInvalid;
     if (!galois_elts_ok(elts, G, "rotate and accumulate: between 1 and 64 elements")) return kErrInvalid;
     if (G * B >= ((size_t)1 << 32))
     {
@@ -1992,21 +2021,10 @@ int Context::ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_
         return kErrInvalid;
     }
     std::lock_guard<std::mutex> lk(mu);
-    for (size_t g = 0; g < G; g++)
-    {
-        aa.elt[g] = elts[g];
-        aa.key[g] = elts[g] == 1 ? nullptr : galois_key(false, elts[g]);
-        if (elts[g] != 1 && !aa.key[g]) return kErrNoKey;
-    }
+    if (int rc = resolve_keys(aa, elts, G, sp, true)) return rc;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    aa.in0  = d_in0;
-    aa.in1  = d_in1;
-    aa.out0 = d_out0;
-    aa.out1 = d_out1;
-    aa.G    = (uint32_t)G;
-    SEAMD_HIP(launch_ct_galois_accum(dp, dt, aa, st));
-    return 0;
+    return galois_accum_step(aa, sp, st);
 }
 
 // The plan of a baby-step / giant-step transform: argument checks, then one permutation launch per giant step -- row
@@ -2071,63 +2089,31 @@ int Context::ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t 
                      uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st)
 {
     GaloisHoistArgs ha{};
-    GaloisAccumArgs aa{};
-    if (!evk_call_args(ha, {d_c0, d_c1, d_out0, d_out1}, B, primes) ||
-        !evk_call_args(aa, {d_c0, d_c1, d_out0, d_out1}, B, primes))
+    if (!set_call_args(ha, d_c0, d_c1, d_out0, d_out1, B, primes, false)) return kErrInvalid;
+    if (!plan_ok(plan, false, primes, "baby-step / giant-step transform", "se_amd_bsgs_create",
+                 "the plan's diagonals have fewer primes than the call"))
         return kErrInvalid;
-    if (!plan || plan->owner != this || plan->sp || primes > plan->levels)
-    {
-        set_last_error(!plan ? "baby-step / giant-step transform: no plan"
-                       : plan->owner != this ? "baby-step / giant-step transform: the plan belongs to another context"
-                       : plan->sp ? "baby-step / giant-step transform: a special-prime plan (se_amd_bsgs_create_sp) does "
-                                    "not serve the digit-key entry"
-                                  : "baby-step / giant-step transform: the plan's diagonals have fewer primes "
-                                    "than the call");
-        return kErrInvalid;
-    }
     const size_t n1 = plan->baby.size(), n2 = plan->giant.size(), row = primes * hp.n;
-    const size_t per = 2 * (n1 + n2) * row * sizeof(uint32_t);
+    const size_t per = bsgs_record_bytes(false, n1, n2, primes, hp.n);
     if (!d_workspace || !aligned16({d_workspace}) || workspace_bytes < per)
     {
         set_last_error("baby-step / giant-step transform: the workspace must be 16-byte aligned and hold at least one "
                        "record (se_amd_bsgs_workspace_bytes)");
         return kErrInvalid;
     }
+    GaloisSetArgs aa = ha;   // the giant steps: the same batch and key layout
     std::lock_guard<std::mutex> lk(mu);
     const bool own   = plan->baby[0] == 1;   // the record itself is baby step 0
     const size_t many = n1 - own;
-    for (size_t e = 0; e < many; e++)
-    {
-        ha.elt[e] = plan->baby[own + e];
-        ha.key[e] = galois_key(false, ha.elt[e]);
-        if (!ha.key[e]) return kErrNoKey;
-    }
-    for (size_t g = 0; g < n2; g++)
-    {
-        aa.elt[g] = plan->giant[g];
-        aa.key[g] = aa.elt[g] == 1 ? nullptr : galois_key(false, aa.elt[g]);
-        if (aa.elt[g] != 1 && !aa.key[g]) return kErrNoKey;
-    }
+    if (int rc = resolve_keys(ha, plan->baby.data() + own, many, false, false)) return rc;
+    if (int rc = resolve_keys(aa, plan->giant.data(), n2, false, true)) return rc;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     const size_t Bc = std::min(B, workspace_bytes / per);
     uint32_t *rot0 = static_cast<uint32_t *>(d_workspace), *rot1 = rot0 + n1 * Bc * row;
     uint32_t *inner0 = rot1 + n1 * Bc * row, *inner1 = inner0 + n2 * Bc * row;
-    ha.G = (uint32_t)many;
-    aa.G = (uint32_t)n2;
-    MulPlainSumArgs ma{};
-    ma.in0       = rot0;
-    ma.in1       = rot1;
-    ma.pt        = plan->diag;
-    ma.out0      = inner0;
-    ma.out1      = inner1;
-    ma.E         = (uint32_t)n1;
-    ma.Gout      = (uint32_t)n2;
-    ma.primes    = (uint32_t)primes;
-    ma.pt_primes = (uint32_t)plan->pt_primes;
-    ma.last_prime = (uint32_t)primes - 1;
-    aa.in0       = inner0;
-    aa.in1       = inner1;
+    aa.c0 = inner0;
+    aa.c1 = inner1;
     for (size_t b0 = 0; b0 < B; b0 += Bc)
     {
         const size_t c = std::min(Bc, B - b0), bytes = c * row * sizeof(uint32_t);
@@ -2146,26 +2132,28 @@ int Context::ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t 
             ha.B    = c;
             SEAMD_HIP(launch_ct_galois_hoist(dp, dt, ha, st));
         }
-        ma.B = (uint32_t)c;
-        SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
+        if (int rc = mul_plain_sum_step(rot0, rot1, n1, c, primes, plan->diag, n2, plan->pt_primes, inner0, inner1, false,
+                                        st))
+            return rc;
         aa.B    = c;
         aa.out0 = d_out0 + b0 * row;
         aa.out1 = d_out1 + b0 * row;
-        SEAMD_HIP(launch_ct_galois_accum(dp, dt, aa, st));
+        if (int rc = galois_accum_step(aa, false, st)) return rc;
     }
     return 0;
 }
 
-// The four steps of the special-prime baby-step / giant-step transform.  Each: the checks of ct_key_switch_sp in their
-// order (a context of one prime, the slabs, the level in [1, np - 1], alignment), then its own; one launch, no scratch, no
-// host synchronisation; the keyed ones read the installed special-prime Galois keys of the elements other than 1 (the
-// digit keys do not serve them) and launch nothing unless every such element has one.
+// The steps of the special-prime baby-step / giant-step transform that have no digit-key twin (the other two are
+// ct_mul_plain_sum and ct_galois_accum with sp).  Each: the checks of ct_key_switch_sp in their order (a context of one
+// prime, the slabs, the level in [1, np - 1], alignment), then its own; one launch, no scratch, no host synchronisation.
+// The keyed one reads the installed special-prime Galois keys of the elements other than 1 (the digit keys do not serve
+// it) and launches nothing unless every such element has one.
 int Context::ct_galois_many_ext_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                    const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
 {
     if (!special_prime_ok()) return kErrInvalid;
-    GaloisManyExtSpArgs ma{};
-    if (!evk_call_args(ma, {d_c0, d_c1, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
+    GaloisSetArgs ma{};
+    if (!set_call_args(ma, d_c0, d_c1, d_out0, d_out1, B, primes, true)) return kErrInvalid;
     if (!galois_elts_ok(elts, G, "undivided rotations: between 1 and 64 elements")) return kErrInvalid;
     if (G * B >= ((size_t)1 << 32))
     {
@@ -2173,54 +2161,10 @@ int Context::ct_galois_many_ext_sp(const uint32_t *d_c0, const uint32_t *d_c1, s
         return kErrInvalid;
     }
     std::lock_guard<std::mutex> lk(mu);
-    for (size_t e = 0; e < G; e++)
-    {
-        ma.elt[e] = elts[e];
-        ma.key[e] = elts[e] == 1 ? nullptr : galois_key(true, elts[e]);
-        if (elts[e] != 1 && !ma.key[e]) return kErrNoKey;
-    }
+    if (int rc = resolve_keys(ma, elts, G, true, true)) return rc;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    ma.c0   = d_c0;
-    ma.c1   = d_c1;
-    ma.out0 = d_out0;
-    ma.out1 = d_out1;
-    ma.G    = (uint32_t)G;
     SEAMD_HIP(launch_ct_galois_many_ext_sp(dp, dt, ma, st));
-    return 0;
-}
-
-// ct_mul_plain_sum on stacks of extended records: primes + 1 rows, the last one modulo the special prime against row
-// np - 1 of the plaintexts, which have all np rows.
-int Context::ct_mul_plain_sum_ext_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
-                                     const uint32_t *d_pt, size_t Gout, uint32_t *d_out0, uint32_t *d_out1,
-                                     hipStream_t st)
-{
-    constexpr size_t k32 = (size_t)1 << 32;
-    if (!special_prime_ok()) return kErrInvalid;
-    if (!d_in0 || !d_out0 || !d_pt || !d_in1 != !d_out1) return kErrInvalid;
-    if (primes < 1 || primes > hp.nprimes - 1) return kErrInvalid;
-    if (B >= k32 || !aligned16({d_in0, d_in1, d_out0, d_out1, d_pt})) return kErrInvalid;
-    if (E < 1 || E > kMaxGaloisKeys || Gout < 1 || Gout > kMaxGaloisKeys || E * B >= k32 || Gout * B >= k32)
-    {
-        set_last_error("weighted sum over a stack: E and Gout between 1 and 64, E B and Gout B below 2^32");
-        return kErrInvalid;
-    }
-    if (B == 0) return 0;
-    SEAMD_HIP(hipSetDevice(device));
-    MulPlainSumArgs ma{};
-    ma.in0        = d_in0;
-    ma.in1        = d_in1;
-    ma.pt         = d_pt;
-    ma.out0       = d_out0;
-    ma.out1       = d_out1;
-    ma.B          = (uint32_t)B;
-    ma.E          = (uint32_t)E;
-    ma.Gout       = (uint32_t)Gout;
-    ma.primes     = (uint32_t)primes + 1;
-    ma.pt_primes  = (uint32_t)hp.nprimes;
-    ma.last_prime = (uint32_t)hp.nprimes - 1;
-    SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
     return 0;
 }
 
@@ -2234,45 +2178,7 @@ int Context::ct_mod_down_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t
     if (!aligned16({d_in0, d_in1, d_out0, d_out1})) return kErrInvalid;
     if (count == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
-    RescaleArgs ra{};
-    ra.in0    = d_in0;
-    ra.in1    = d_in1;
-    ra.out0   = d_out0;
-    ra.out1   = d_out1;
-    ra.primes = (uint32_t)primes + 1;
-    ra.drop   = (uint32_t)hp.nprimes - 1;
-    SEAMD_HIP(launch_ct_mod_down_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ra, count, st));
-    return 0;
-}
-
-int Context::ct_galois_accum_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes,
-                                const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
-{
-    if (!special_prime_ok()) return kErrInvalid;
-    GaloisAccumSpArgs aa{};
-    if (!evk_call_args(aa, {d_in0, d_in1, d_out0, d_out1}, B, primes, true)) return kErrInvalid;
-    if (!galois_elts_ok(elts, G, "rotate and accumulate: between 1 and 64 elements")) return kErrInvalid;
-    if (G * B >= ((size_t)1 << 32))
-    {
-        set_last_error("rotate and accumulate: G B must stay below 2^32");
-        return kErrInvalid;
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    for (size_t g = 0; g < G; g++)
-    {
-        aa.elt[g] = elts[g];
-        aa.key[g] = elts[g] == 1 ? nullptr : galois_key(true, elts[g]);
-        if (elts[g] != 1 && !aa.key[g]) return kErrNoKey;
-    }
-    if (B == 0) return 0;
-    SEAMD_HIP(hipSetDevice(device));
-    aa.in0  = d_in0;
-    aa.in1  = d_in1;
-    aa.out0 = d_out0;
-    aa.out1 = d_out1;
-    aa.G    = (uint32_t)G;
-    SEAMD_HIP(launch_ct_galois_accum_sp(dp, dt, host_rescale_params(hp, hp.nprimes), aa, st));
-    return 0;
+    return mod_down_sp_step(d_in0, d_in1, count, primes, d_out0, d_out1, st);
 }
 
 // ct_bsgs on the special-prime keys.  The checks of ct_key_switch_sp first, then the plan's and the workspace's, then
@@ -2285,42 +2191,24 @@ int Context::ct_bsgs_sp(const BsgsPlan *plan, const uint32_t *d_c0, const uint32
                         uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st)
 {
     if (!special_prime_ok()) return kErrInvalid;
-    GaloisManyExtSpArgs ua{};
-    GaloisAccumSpArgs aa{};
-    if (!evk_call_args(ua, {d_c0, d_c1, d_out0, d_out1}, B, primes, true) ||
-        !evk_call_args(aa, {d_c0, d_c1, d_out0, d_out1}, B, primes, true))
+    GaloisSetArgs ua{};
+    if (!set_call_args(ua, d_c0, d_c1, d_out0, d_out1, B, primes, true)) return kErrInvalid;
+    if (!plan_ok(plan, true, primes, "baby-step / giant-step transform", "se_amd_bsgs_create",
+                 "the level is above the plan's"))
         return kErrInvalid;
-    if (!plan || plan->owner != this || !plan->sp || primes > plan->levels)
-    {
-        set_last_error(!plan ? "baby-step / giant-step transform: no plan"
-                       : plan->owner != this ? "baby-step / giant-step transform: the plan belongs to another context"
-                       : !plan->sp ? "baby-step / giant-step transform: a digit-key plan (se_amd_bsgs_create) does not "
-                                     "serve the special-prime entry"
-                                   : "baby-step / giant-step transform: the level is above the plan's");
-        return kErrInvalid;
-    }
-    const size_t n1 = plan->baby.size(), n2 = plan->giant.size(), n = hp.n, np = hp.nprimes;
+    const size_t n1 = plan->baby.size(), n2 = plan->giant.size(), n = hp.n;
     const size_t row = primes * n, xrow = (primes + 1) * n;
-    const size_t per = bsgs_sp_record_bytes(n1, n2, primes, n);
+    const size_t per = bsgs_record_bytes(true, n1, n2, primes, n);
     if (!d_workspace || !aligned16({d_workspace}) || workspace_bytes < per)
     {
         set_last_error("baby-step / giant-step transform: the workspace must be 16-byte aligned and hold at least one "
                        "record (se_amd_bsgs_workspace_bytes)");
         return kErrInvalid;
     }
+    GaloisSetArgs aa = ua;   // the giant steps: the same batch and key layout
     std::lock_guard<std::mutex> lk(mu);
-    for (size_t e = 0; e < n1; e++)
-    {
-        ua.elt[e] = plan->baby[e];
-        ua.key[e] = ua.elt[e] == 1 ? nullptr : galois_key(true, ua.elt[e]);
-        if (ua.elt[e] != 1 && !ua.key[e]) return kErrNoKey;
-    }
-    for (size_t g = 0; g < n2; g++)
-    {
-        aa.elt[g] = plan->giant[g];
-        aa.key[g] = aa.elt[g] == 1 ? nullptr : galois_key(true, aa.elt[g]);
-        if (aa.elt[g] != 1 && !aa.key[g]) return kErrNoKey;
-    }
+    if (int rc = resolve_keys(ua, plan->baby.data(), n1, true, true)) return rc;
+    if (int rc = resolve_keys(aa, plan->giant.data(), n2, true, true)) return rc;
     if (B == 0) return 0;
     SEAMD_HIP(hipSetDevice(device));
     // a chunk's stacks are launch grids too: n1 c and n2 c stay below 2^31
@@ -2328,31 +2216,10 @@ int Context::ct_bsgs_sp(const BsgsPlan *plan, const uint32_t *d_c0, const uint32
     uint32_t *u0 = static_cast<uint32_t *>(d_workspace), *u1 = u0 + n1 * Bc * xrow;
     uint32_t *v0 = u1 + n1 * Bc * xrow, *v1 = v0 + n2 * Bc * xrow;
     uint32_t *w0 = v1 + n2 * Bc * xrow, *w1 = w0 + n2 * Bc * row;
-    const RescaleParams rp = host_rescale_params(hp, np);
-    ua.G    = (uint32_t)n1;
     ua.out0 = u0;
     ua.out1 = u1;
-    aa.G    = (uint32_t)n2;
-    aa.in0  = w0;
-    aa.in1  = w1;
-    MulPlainSumArgs ma{};
-    ma.in0        = u0;
-    ma.in1        = u1;
-    ma.pt         = plan->diag;
-    ma.out0       = v0;
-    ma.out1       = v1;
-    ma.E          = (uint32_t)n1;
-    ma.Gout       = (uint32_t)n2;
-    ma.primes     = (uint32_t)primes + 1;
-    ma.pt_primes  = (uint32_t)np;
-    ma.last_prime = (uint32_t)np - 1;
-    RescaleArgs ra{};
-    ra.in0    = v0;
-    ra.in1    = v1;
-    ra.out0   = w0;
-    ra.out1   = w1;
-    ra.primes = (uint32_t)primes + 1;
-    ra.drop   = (uint32_t)np - 1;
+    aa.c0   = w0;
+    aa.c1   = w1;
     for (size_t b0 = 0; b0 < B; b0 += Bc)
     {
         const size_t c = std::min(Bc, B - b0);
@@ -2360,13 +2227,12 @@ int Context::ct_bsgs_sp(const BsgsPlan *plan, const uint32_t *d_c0, const uint32
         ua.c1 = d_c1 + b0 * row;
         ua.B  = c;
         SEAMD_HIP(launch_ct_galois_many_ext_sp(dp, dt, ua, st));
-        ma.B = (uint32_t)c;
-        SEAMD_HIP(launch_ct_mul_plain_sum(dp, ma, st));
-        SEAMD_HIP(launch_ct_mod_down_sp(dp, dt, rp, ra, n2 * c, st));
+        if (int rc = mul_plain_sum_step(u0, u1, n1, c, primes, plan->diag, n2, 0, v0, v1, true, st)) return rc;
+        if (int rc = mod_down_sp_step(v0, v1, n2 * c, primes, w0, w1, st)) return rc;
         aa.B    = c;
         aa.out0 = d_out0 + b0 * row;
         aa.out1 = d_out1 + b0 * row;
-        SEAMD_HIP(launch_ct_galois_accum_sp(dp, dt, rp, aa, st));
+        if (int rc = galois_accum_step(aa, true, st)) return rc;
     }
     return 0;
 }

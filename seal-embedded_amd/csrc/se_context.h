@@ -274,8 +274,11 @@ struct Context
     // hoisted rotations (GaloisHoistArgs): G rotations of every record from one digit decomposition, each to its own
     // output (sum false: outputs [G][B][primes][n]) or summed into one record, with the record itself when add_input
     // (sum true: outputs [B][primes][n]); elts is a host pointer; one launch, no scratch
+    // sp (the sum form only; HoistSpArgs): on the special-prime Galois keys, one decomposition and one division by P
+    // whatever G is
     int ct_galois_hoist(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
-                        size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+                        size_t G, bool sum, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st,
+                        bool sp = false);
     // linear transforms (LintransArgs): the plan folds device diagonals [G][pt_primes][n] (+ d_diag0 [pt_primes][n] or
     // NULL) into the installed Galois keys of elts (host) and synchronises; a call is one launch, no scratch
     // sp: on the special-prime keys (pt_primes = np, levels 1 .. np - 1; HoistSpArgs); a plan serves the calls of its kind
@@ -284,39 +287,36 @@ struct Context
     int ct_lintrans(const LintransPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                     uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp = false);
     // baby-step / giant-step linear transforms: the weighted sum over a stack (MulPlainSumArgs, key-free), the rotate-and-
-    // accumulate of G different records (GaloisAccumArgs, elts a host pointer, element 1 needs no key), one launch each;
+    // accumulate of G different records (GaloisSetArgs, elts a host pointer, element 1 needs no key), one launch each;
     // the plan (device diagonals [n2][n1][pt_primes][n], host element lists; synchronises) and its call, which walks the
-    // batch in chunks of what the caller's workspace holds: copies, the many form, the two entries above, all on `st`
+    // batch in chunks of what the caller's workspace holds: copies, the many form, the two steps above, all on `st`.
+    // sp on the two steps: the forms ct_bsgs_sp chains -- the sum on stacks of extended records (primes + 1 rows, the
+    // last one modulo the special prime; pt_primes is not read, the plaintexts have all np rows), the accumulate on the
+    // special-prime keys with one division by P
     int ct_mul_plain_sum(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
                          const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0, uint32_t *d_out1,
-                         hipStream_t st);
+                         hipStream_t st, bool sp = false);
     int ct_galois_accum(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
-                        size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
+                        size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st, bool sp = false);
     int bsgs_create(const uint32_t *baby, size_t n1, const uint32_t *giant, size_t n2, const uint32_t *d_diag,
                     size_t pt_primes, BsgsPlan &plan, bool sp = false);
     int ct_bsgs(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                 uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st);
-    // the same on the special-prime keys with the division by P deferred: the four steps below, one launch each and
-    // useful on their own, and the call that chains them in the caller's workspace.  An extended record has primes + 1
-    // rows, the last one modulo the special prime (GaloisManyExtSpArgs)
+    // the same on the special-prime keys with the division by P deferred: the baby steps as extended records and the
+    // division, one launch each and useful on their own beside the two sp steps above, and the call that chains the four
+    // in the caller's workspace
     int ct_galois_many_ext_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
                               size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
-    int ct_mul_plain_sum_ext_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
-                                const uint32_t *d_pt, size_t Gout, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     int ct_mod_down_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t count, size_t primes, uint32_t *d_out0,
                        uint32_t *d_out1, hipStream_t st);
-    int ct_galois_accum_sp(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *elts,
-                           size_t G, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     int ct_bsgs_sp(const BsgsPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                    uint32_t *d_out0, uint32_t *d_out1, void *d_workspace, size_t workspace_bytes, hipStream_t st);
-    static size_t bsgs_sp_record_bytes(size_t n1, size_t n2, size_t primes, size_t n)
+    // workspace bytes of one record of a plan's call, the only place they are computed: two halves each of the digit
+    // plan's rot [n1] and inner [n2] of `primes` rows; sp: of U [n1] and V [n2] of primes + 1 rows and W [n2] of `primes`
+    static size_t bsgs_record_bytes(bool sp, size_t n1, size_t n2, size_t primes, size_t n)
     {
-        // U [n1] and V [n2] of primes + 1 rows, W [n2] of primes rows, two halves each
-        return 2 * ((n1 + n2) * (primes + 1) + n2 * primes) * n * sizeof(uint32_t);
+        return 2 * ((n1 + n2) * (primes + sp) + sp * n2 * primes) * n * sizeof(uint32_t);
     }
-    // the sum form on the special-prime Galois keys (HoistSpArgs): one decomposition and one division by P whatever G is
-    int ct_galois_sum_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
-                         size_t G, bool add_input, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // key-free rescale (RescaleArgs) and slot-wise plaintext product (MulPlainArgs): one launch each, no scratch
     int ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, uint32_t *d_out0,
                    uint32_t *d_out1, hipStream_t st);
@@ -383,6 +383,21 @@ private:
     bool galois_elt_ok(uint32_t elt) const { return (elt & 1) && elt < 2 * hp.n; }   // odd and below 2n
     bool galois_elts_ok(const uint32_t *elts, size_t G, const char *count_msg, bool distinct = false) const;
     const uint32_t *galois_key(bool sp, uint32_t elt) const;
+    // the rotation-family entries (se_context.cpp): one fill of the element-set block's call shape and slabs, one
+    // resolver of elements into installed key blocks (the only loop over galois_key), one plan check, and the unchecked
+    // "fill and launch" halves of the step entries that the composites chain
+    bool set_call_args(GaloisSetArgs &a, const uint32_t *c0, const uint32_t *c1, uint32_t *out0, uint32_t *out1, size_t B,
+                       size_t primes, bool sp) const;
+    int resolve_keys(GaloisSetArgs &a, const uint32_t *elts, size_t G, bool sp, bool one_keyless) const;
+    template <class Plan>
+    bool plan_ok(const Plan *plan, bool sp, size_t primes, const char *what, const char *create,
+                 const char *level_msg) const;
+    int mul_plain_sum_step(const uint32_t *d_in0, const uint32_t *d_in1, size_t E, size_t B, size_t primes,
+                           const uint32_t *d_pt, size_t Gout, size_t pt_primes, uint32_t *d_out0, uint32_t *d_out1, bool sp,
+                           hipStream_t st);
+    int mod_down_sp_step(const uint32_t *d_in0, const uint32_t *d_in1, size_t count, size_t primes, uint32_t *d_out0,
+                         uint32_t *d_out1, hipStream_t st);
+    int galois_accum_step(const GaloisSetArgs &aa, bool sp, hipStream_t st);
     int decrypt_level_impl(const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2, bool deg2, size_t B,
                            size_t primes, double scale, const uint32_t *d_key_idx, bool keyed, int64_t *d_pte,
                            float *d_values, double *d_values_f64, uint8_t *d_status, hipStream_t st);

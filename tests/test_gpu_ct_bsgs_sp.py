@@ -513,6 +513,65 @@ def test_bsgs_sp_arguments(env):
     ctx.close()
 
 
+def test_digit_and_special_prime_twins_refuse_in_their_own_order(env):
+    """The three pairs of entries that share one host body (ct_galois_accum, ct_galois_sum, ct_mul_plain_sum and their
+    special-prime forms) on calls that are wrong in TWO ways at once, B = 1: the code and the last error say which check
+    came first.  The expected values are literals read off the two separate bodies each pair had before they were merged.
+    A refusal of the call's shape (a slab, the level, an alignment) sets no message, so the last error is seeded before
+    every call and must come back unchanged.
+      1. a misaligned output slab and an element without an installed key (the key-free pair: and E = 65): the shape
+         check comes first on both sides, -22 and no message -- not SE_ERR_NO_KEY, not the stack's message.
+      2. a level of np and an even element (the key-free pair: and E = 65): np is a level of the digit side, which goes
+         on to refuse the element resp. the stack with its message; the special-prime side stops at the level, silently.
+    Nothing is written.  4096 x 2 is the smallest parameter set with a special prime (the chains of 1024 and 2048 have
+    one prime)."""
+    torch, pkg = env["torch"], env["pkg"]
+    n, npr, B = 4096, 2, 1
+    ctx = pkg.Context(n, npr)
+    lib, h = ctx.L, ctx.h
+    ctx.set_galois_keys([3], *(np.zeros((1, 2 * npr, npr, n), dtype=np.uint32),) * 2)
+    ctx.set_galois_keys_sp([3], *(np.zeros((1, npr - 1, npr, n), dtype=np.uint32),) * 2)
+    stack = torch.zeros((2, B, npr + 1, n), dtype=torch.int32, device=env["dev"])
+    pt = torch.ones((1, 2, npr, n), dtype=torch.int32, device=env["dev"])
+    out0 = torch.full((2 * B * (npr + 1) * n,), SENTINEL, dtype=torch.int32, device=env["dev"])
+    out1 = torch.full_like(out0, SENTINEL)
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    s = stream_of(env)
+    I0, I1, O0, O1, M0, D = p(stack), p(stack), p(out0), p(out1), p(out0, 4), p(pt)
+    keyless, even = np.array([3, 7], dtype=np.uint32), np.array([3, 4], dtype=np.uint32)
+    SEED = "unsupported parameter set (degree, primes), or primes < 2"
+    ELEMENT = "Galois element 4 is not odd and below 2n"
+    STACK = "weighted sum over a stack: E and Gout between 1 and 64, E B and Gout B below 2^32"
+
+    def refused(what, f, args, text):
+        assert lib.se_amd_rescale_constants(n, 1, None, None) == SE_ERR_INVALD_ARGUMENT      # seeds the last error
+        assert lib.se_amd_last_error().decode() == SEED
+        assert f(*args) == SE_ERR_INVALD_ARGUMENT, what
+        assert lib.se_amd_last_error().decode() == text, what
+
+    fa, fa_sp = lib.se_amd_ct_galois_accum_device, lib.se_amd_ct_galois_accum_sp_device
+    fg, fg_sp = lib.se_amd_ct_galois_sum_device, lib.se_amd_ct_galois_sum_sp_device
+    fs, fs_sp = lib.se_amd_ct_mul_plain_sum_device, lib.se_amd_ct_mul_plain_sum_ext_sp_device
+    # 1. a misaligned output slab in front of everything else
+    for f in (fa, fa_sp):
+        refused((f.__name__, 1), f, (h, I0, I1, B, 1, hp(keyless), 2, M0, O1, s), SEED)
+    for f in (fg, fg_sp):
+        refused((f.__name__, 1), f, (h, I0, I1, B, 1, hp(keyless), 2, 0, M0, O1, s), SEED)
+    refused((fs.__name__, 1), fs, (h, I0, I1, 65, B, 1, D, 1, npr, M0, O1, s), SEED)
+    refused((fs_sp.__name__, 1), fs_sp, (h, I0, I1, 65, B, 1, D, 1, M0, O1, s), SEED)
+    # 2. the level np: the digit side's highest, above the special-prime side's
+    refused((fa.__name__, 2), fa, (h, I0, I1, B, npr, hp(even), 2, O0, O1, s), ELEMENT)
+    refused((fa_sp.__name__, 2), fa_sp, (h, I0, I1, B, npr, hp(even), 2, O0, O1, s), SEED)
+    refused((fg.__name__, 2), fg, (h, I0, I1, B, npr, hp(even), 2, 0, O0, O1, s), ELEMENT)
+    refused((fg_sp.__name__, 2), fg_sp, (h, I0, I1, B, npr, hp(even), 2, 0, O0, O1, s), SEED)
+    refused((fs.__name__, 2), fs, (h, I0, I1, 65, B, npr, D, 1, npr, O0, O1, s), STACK)
+    refused((fs_sp.__name__, 2), fs_sp, (h, I0, I1, 65, B, npr, D, 1, O0, O1, s), SEED)
+    torch.cuda.synchronize()
+    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    ctx.close()
+
+
 # ---- end to end with a real key -------------------------------------------------------------------------------------
 DIM = 16
 N1 = N2 = 4
