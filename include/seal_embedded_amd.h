@@ -891,6 +891,52 @@ int se_amd_ct_switch_sum_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, 
                                          const uint32_t *d_key_idx /*[B]*/, size_t G, const uint32_t *d_row_ptr /*[G+1]*/,
                                          const uint32_t *d_idx /*[nnz]*/, size_t nnz, uint32_t *d_out0, uint32_t *d_out1
                                          /*[G][primes][n]*/, uint8_t *d_status /*[G], optional*/, void *stream);
+/* Encrypted inner products: grouped product sums.  A variance, an inner product of two senders' vectors, a polynomial
+ * score are sums of products, and relinearisation is linear in d2: sum the tensors, key-switch once.  Row g takes the
+ * pairs k in [d_row_ptr[g], d_row_ptr[g + 1]) (the CSR rows of se_amd_ct_lincomb_device, unweighted); pair k is record
+ * d_ia[k] of (a0, a1) times record d_ib[k] of (b0, b1); with d_ia = d_ib = NULL pair k is (k, k) and nnz == Ba == Bb is
+ * required.  A pair listed twice counts twice; the a and b slabs may be the same pointers (squares).  Per prime
+ * j < primes and element, canonical in [0, q_j):
+ *     T0[g] = sum_k x0 . y0     T1[g] = sum_k (x0 . y1 + x1 . y0)     T2[g] = sum_k x1 . y1      mod q_j
+ * se_amd_ct_mul_sum_device, key-free, 1 <= primes <= np: (out0, out1, out2) = (T0, T1, T2), each [G][primes][n].  No key,
+ * no scratch, one asynchronous launch, and no per-pair record in memory.  BIT-IDENTICAL to se_amd_ct_mul_device on the
+ * pairs followed by the unweighted se_amd_ct_lincomb_device row sums of each slab: the map is exact modular arithmetic,
+ * so any evaluation order gives those bits.  The result decrypts with se_amd_decrypt3_level_device, or goes into either
+ * relinearisation (se_amd_ct_relin_device serves the digit key).
+ * se_amd_ct_dot_sp_device, 1 <= primes <= np - 1, under the installed key of se_amd_set_relin_key_sp: with ks the "key
+ * switch of a level-L row polynomial" above applied to d = T2[g] (centred digits, one division by P),
+ *     out_k[g] = T_k[g] + ks_k          k = 0, 1,   [G][primes][n] each
+ * in ONE launch, with no workspace and the tensor sums never in memory.  Three facts.  (1) A row of one pair is
+ * BIT-IDENTICAL to se_amd_ct_mul_device followed by se_amd_ct_relin_sp_device on that pair.  (2) Any row is BIT-IDENTICAL
+ * to se_amd_ct_mul_sum_device followed by se_amd_ct_relin_sp_device.  (3) A row of m >= 2 pairs is NOT the modular sum of
+ * m relinearised products: it makes one rounding centred(INTT_p(ACC[p]), P) on the summed T2 instead of m, and it needs
+ * 4 L + 2 transforms per output row and prime, not (4 L + 2) . m.
+ * Scale and level: the product's D_a . D_b at the operands' level, which is unchanged; the result goes straight into
+ * se_amd_ct_rescale_device.  Range: the sum of m products of messages must stay below Q_L / 2 like any record, so an
+ * inner product of fresh records is one se_amd_ct_drop_primes_device to np - 1, one call, one rescale.  Both entries are
+ * defined on arbitrary residue slabs (and key words); no secret key is needed.
+ * Status (uint8 [G], optional): an empty row is all zero with status 1; a row with a d_ia[k] >= Ba, a d_ib[k] >= Bb, or a
+ * d_row_ptr pair that decreases or reaches beyond nnz is all zero in every output slab with status 2, and the other rows
+ * are unaffected.  Nothing is read out of bounds -- an index is compared before it forms an address -- and the status is
+ * decided before anything of the row is written.  G = 0 is a successful no-op; Ba or Bb = 0 with non-empty rows gives
+ * those rows status 2.  A row runs on L workgroups (dot_sp) whatever its length and is not sliced: sum long rows in two
+ * tiers, groups of tens of pairs here, then se_amd_ct_lincomb_device over the group sums.
+ * SE_ERR_INVALD_ARGUMENT, with nothing written: NULL ctx, slab or d_row_ptr; only one of d_ia / d_ib NULL; both NULL with
+ * nnz != Ba or nnz != Bb; primes outside [1, np] resp. [1, np - 1], and se_amd_ct_dot_sp_device on a context of one
+ * prime; Ba, Bb, G or nnz at or above 2^32; a slab pointer that is not 16-byte aligned.  SE_ERR_NO_KEY from
+ * se_amd_ct_dot_sp_device without a special-prime relinearisation key: an installed digit key, Galois key or switch ring
+ * does not serve.  Out of scope: a digit-key fused form, weighted rows, slicing long rows, a fused rescale, host-pointer
+ * and multi-device forms. */
+int se_amd_ct_mul_sum_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba,
+                             const uint32_t *d_b0, const uint32_t *d_b1, size_t Bb, size_t primes, size_t G,
+                             const uint32_t *d_row_ptr /*[G+1]*/, const uint32_t *d_ia,
+                             const uint32_t *d_ib /*[nnz] or both NULL*/, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                             uint32_t *d_out2 /*[G][primes][n] each*/, uint8_t *d_status /*[G], optional*/, void *stream);
+int se_amd_ct_dot_sp_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0,
+                            const uint32_t *d_b1, size_t Bb, size_t primes, size_t G, const uint32_t *d_row_ptr /*[G+1]*/,
+                            const uint32_t *d_ia, const uint32_t *d_ib /*[nnz] or both NULL*/, size_t nnz,
+                            uint32_t *d_out0, uint32_t *d_out1 /*[G][primes][n]*/, uint8_t *d_status /*[G], optional*/,
+                            void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

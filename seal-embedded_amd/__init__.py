@@ -79,6 +79,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_ct_galois_accum_sp_device", "se_amd_bsgs_create_sp", "se_amd_ct_bsgs_sp_device",
     "se_amd_gen_switch_keys_sp", "se_amd_set_switch_keyring_sp", "se_amd_ct_switch_keyed_sp_device",
     "se_amd_ct_switch_sum_keyed_sp_device",
+    "se_amd_ct_mul_sum_device", "se_amd_ct_dot_sp_device",
 )
 
 
@@ -209,6 +210,8 @@ def lib():
     L.se_amd_set_switch_keyring_sp.argtypes = [vp, sz, vp, vp]
     L.se_amd_ct_switch_keyed_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.se_amd_ct_switch_sum_keyed_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp]
+    L.se_amd_ct_mul_sum_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.se_amd_ct_dot_sp_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -647,6 +650,32 @@ class Context:
         _check(self.L.se_amd_ct_mul_device(self.h, _ptr(a0), _ptr(a1), a0.shape[0], _ptr(b0), _ptr(b1), b0.shape[0],
                                            primes, P, _ptr(ia), _ptr(ib), _ptr(out0), _ptr(out1), _ptr(out2),
                                            _ptr(status), _stream_ptr()), "se_amd_ct_mul_device")
+
+    def _mul_sum_shape(self, a0, row_ptr, ia, primes):
+        """(primes, G, nnz) of a grouped product call: ia = ib = None is the identity pair list over the whole batch."""
+        return (a0.shape[1] if primes is None else primes, row_ptr.numel() - 1,
+                ia.numel() if ia is not None else a0.shape[0])
+
+    def ct_mul_sum(self, a0, a1, b0, b1, row_ptr, ia, ib, out0, out1, out2, primes=None, status=None):
+        """Key-free grouped product sums: output row g = the sum over k in [row_ptr[g], row_ptr[g + 1]) of the tensor of
+        record ia[k] of (a0, a1) and record ib[k] of (b0, b1) (ia = ib = None: pair k is (k, k)); out0, out1, out2 are
+        [G][primes][n].  The bits of ct_mul on the pairs and unweighted ct_lincomb row sums, without the per-pair
+        record.  status uint8 [G]: 2 and a zero row for a pair index out of range or a bad row_ptr pair."""
+        primes, G, nnz = self._mul_sum_shape(a0, row_ptr, ia, primes)
+        _check(self.L.se_amd_ct_mul_sum_device(self.h, _ptr(a0), _ptr(a1), a0.shape[0], _ptr(b0), _ptr(b1), b0.shape[0],
+                                               primes, G, _ptr(row_ptr), _ptr(ia), _ptr(ib), nnz, _ptr(out0),
+                                               _ptr(out1), _ptr(out2), _ptr(status), _stream_ptr()),
+               "se_amd_ct_mul_sum_device")
+
+    def ct_dot_sp(self, a0, a1, b0, b1, row_ptr, ia, ib, out0, out1, primes=None, status=None):
+        """Encrypted inner products: the rows of ct_mul_sum relinearised under the installed special-prime key inside the
+        same launch, ONE key switch and one division by the special prime per row; primes <= np - 1, out0, out1 are
+        [G][primes][n] at the product's scale and the operands' level.  The bits of ct_mul_sum followed by ct_relin_sp,
+        with the tensor sums never in memory.  status as ct_mul_sum."""
+        primes, G, nnz = self._mul_sum_shape(a0, row_ptr, ia, primes)
+        _check(self.L.se_amd_ct_dot_sp_device(self.h, _ptr(a0), _ptr(a1), a0.shape[0], _ptr(b0), _ptr(b1), b0.shape[0],
+                                              primes, G, _ptr(row_ptr), _ptr(ia), _ptr(ib), nnz, _ptr(out0), _ptr(out1),
+                                              _ptr(status), _stream_ptr()), "se_amd_ct_dot_sp_device")
 
     def decrypt3_level(self, c0, c1, c2, primes, scale, pte=None, values=None, values_f64=None, status=None):
         """decrypt_level on the degree-2 form (c0, c1, c2): d = c0 + s (c1 + s c2) per prime."""

@@ -13,7 +13,9 @@
 // extended records and the one-division giant sum (se_amd_ct_galois_many_ext_sp_device, se_amd_ct_mod_down_sp_device,
 // se_amd_ct_galois_accum_sp_device, se_amd_ct_bsgs_sp_device, between the two), and the switch-key ring: the special-prime
 // key switch with the key chosen per record, alone or summed over CSR rows with one division by P per row
-// (se_amd_ct_switch_keyed_sp_device, se_amd_ct_switch_sum_keyed_sp_device, behind k_ct_galois_sp).
+// (se_amd_ct_switch_keyed_sp_device, se_amd_ct_switch_sum_keyed_sp_device, behind k_ct_galois_sp), and the grouped
+// product sums: the tensor summed over CSR rows of pairs, key-free (se_amd_ct_mul_sum_device, behind k_ct_mul) or with
+// one special-prime relinearisation per row (se_amd_ct_dot_sp_device, behind the switch-key ring).
 //
 // A slab is uint32 [record][prime][coeff] in NTT form, so a linear combination of records, or a product with a
 // plaintext in the same form, is element-wise arithmetic mod q_j: no transform, no key, no table.  Unlike the rest of
@@ -359,6 +361,117 @@ hipError_t launch_ct_mul(const DevParams &P, const MulArgs &A, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------
+// Grouped product sums (se_amd_ct_mul_sum_device; MulSumArgs): the tensor above summed over the pairs of a CSR row,
+//   T0[g] = sum_k x0 y0,   T1[g] = sum_k (x0 y1 + x1 y0),   T2[g] = sum_k x1 y1   mod q_j,
+// with the per-pair record (3 slabs per pair) never written.  Streaming, in the shape of k_ct_mul: a 256-thread
+// workgroup owns 1024 consecutive residues of an output row -- inside one prime, q_j scalar -- walks the rows
+// blockIdx.y, blockIdx.y + gridDim.y, ... and inside a row its pairs; row_ptr and the pair indices are
+// workgroup-uniform (scalar loads).  A row is not sliced.
+// Lazy accumulation.  Residues are below q < 2^30, so one product is at most (q - 1)^2 <= 2^60 - 2^32 + 4 and the T1
+// term of a pair at most 2^61 - 2^33 + 8.  An accumulator enters a period canonical (< 2^30) and takes kMsPeriod = 8
+// pairs:  2^30 + 8 (2^61 - 2^33 + 8) < 2^64,  so 8 pairs fit a uint64 before barrett64 (exact for every 64-bit input);
+// 9 would not.  T0 and T2 take the same period: one rule for the three sums, here and in k_ct_dot_sp.
+// The map is exact modular arithmetic: any order of the pairs and any placing of the reductions gives the bits of
+// k_ct_mul followed by the unweighted k_ct_lincomb of each slab.
+// grid (primes n / 1024, min(G, 65 535)).
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t kMsPeriod = 8;   // pairs between two reductions
+constexpr uint32_t kMsFlight = 2;   // pairs (8 input rows) in flight per wave
+static_assert(kMsPeriod % kMsFlight == 0, "a period is a whole number of load groups");
+
+// The pairs [lo, hi) of output row g and whether the row is invalid, decided before anything of it is read or written:
+// the row_ptr pair, then every pair index against its batch.  Nothing but row_ptr[g], row_ptr[g + 1] and ia / ib[k] with
+// k < hi <= nnz is read, and no index forms an address here.  Depends on g alone: wave-uniform.  Ba = 0 or Bb = 0 makes
+// every non-empty row invalid.  An invalid row has lo = hi.
+__device__ __forceinline__ bool mul_sum_row(const MulSumArgs &A, size_t g, uint32_t &lo, uint32_t &hi)
+{
+    const uint32_t a = A.row_ptr[g], b = A.row_ptr[g + 1];
+    bool bad = a > b || b > A.nnz;
+    lo       = a;
+    hi       = bad ? a : b;
+    for (uint32_t k = lo; k < hi; k++) bad |= (A.ia ? A.ia[k] : k) >= A.Ba || (A.ib ? A.ib[k] : k) >= A.Bb;
+    if (bad) hi = lo;
+    return bad;
+}
+
+// the end of the period that starts at pair k < hi (hi - k, not k + kMsPeriod: nnz may be close to 2^32)
+__device__ __forceinline__ uint32_t mul_sum_period_end(uint32_t k, uint32_t hi)
+{
+    return hi - k < kMsPeriod ? hi : k + kMsPeriod;
+}
+
+__global__ __launch_bounds__(kLcThreads) void k_ct_mul_sum(const DevParams P, const MulSumArgs A)
+{
+    const size_t row     = (size_t)A.primes << P.logn;
+    const uint32_t chunk = blockIdx.x;
+    const uint32_t j     = (chunk << kLcTileLog) >> P.logn;
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+    const size_t off = ((size_t)chunk << kLcTileLog) + 4 * threadIdx.x;
+    auto pair_of = [&](uint32_t k, size_t &ia, size_t &ib) {   // checked by mul_sum_row
+        ia = A.ia ? A.ia[k] : k;
+        ib = A.ib ? A.ib[k] : k;
+    };
+
+    for (size_t g = blockIdx.y; g < A.G; g += gridDim.y)
+    {
+        uint32_t lo, hi;
+        const bool bad = mul_sum_row(A, g, lo, hi);
+        Lane4 t0, t1, t2;
+        for (uint32_t k = lo; k < hi;)
+        {
+            const uint32_t end = mul_sum_period_end(k, hi);
+            for (; end - k >= kMsFlight; k += kMsFlight)
+            {
+                uint4 x0[kMsFlight], x1[kMsFlight], y0[kMsFlight], y1[kMsFlight];
+#pragma unroll
+                for (uint32_t u = 0; u < kMsFlight; u++)
+                {
+                    size_t ia, ib;
+                    pair_of(k + u, ia, ib);
+                    x0[u] = load_row(A.a0, ia, row, off), x1[u] = load_row(A.a1, ia, row, off);
+                    y0[u] = load_row(A.b0, ib, row, off), y1[u] = load_row(A.b1, ib, row, off);
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < kMsFlight; u++)
+                {
+                    t0.mad4(x0[u], y0[u]);
+                    t1.mad4(x0[u], y1[u]);
+                    t1.mad4(x1[u], y0[u]);
+                    t2.mad4(x1[u], y1[u]);
+                }
+            }
+            for (; k < end; k++)   // the last, short group of a row
+            {
+                size_t ia, ib;
+                pair_of(k, ia, ib);
+                const uint4 x0 = load_row(A.a0, ia, row, off), x1 = load_row(A.a1, ia, row, off);
+                const uint4 y0 = load_row(A.b0, ib, row, off), y1 = load_row(A.b1, ib, row, off);
+                t0.mad4(x0, y0);
+                t1.mad4(x0, y1);
+                t1.mad4(x1, y0);
+                t2.mad4(x1, y1);
+            }
+            t0.reduce(q, cr_hi, cr_lo);
+            t1.reduce(q, cr_hi, cr_lo);
+            t2.reduce(q, cr_hi, cr_lo);
+        }
+        // an empty or invalid row never entered the loop: the accumulators are zero
+        *reinterpret_cast<uint4 *>(A.out0 + g * row + off) = t0.get();
+        *reinterpret_cast<uint4 *>(A.out1 + g * row + off) = t1.get();
+        *reinterpret_cast<uint4 *>(A.out2 + g * row + off) = t2.get();
+        if (A.status && blockIdx.x == 0 && threadIdx.x == 0) A.status[g] = bad ? 2 : 1;
+    }
+}
+
+hipError_t launch_ct_mul_sum(const DevParams &P, const MulSumArgs &A, hipStream_t st)
+{
+    if (A.G == 0) return hipSuccess;
+    const uint32_t chunks = (uint32_t)(((size_t)A.primes << P.logn) >> kLcTileLog);
+    const dim3 grid(chunks, A.G < 65535u ? A.G : 65535u);
+    return launch(k_ct_mul_sum, grid, dim3(kLcThreads), 0, st, P, A);
+}
+
+// ------------------------------------------------------------------------------------------
 // Rescale: level L -> level L - 1, the exact quotient (c - delta) / q_last with delta = c mod q_last centred, i.e.
 // c / q_last rounded to nearest (SEAL's rescale_to_next on NTT-form data).  One workgroup of n/16 threads per
 // (record, slab), the tiling of the rest of the tree:
@@ -528,19 +641,27 @@ hipError_t launch_ct_mod_down_sp(const DevParams &P, const DevTables &T, const R
 // thread: 276 bytes of private memory).  Each transform takes an opaque copy of the index instead (opaque_index,
 // transform.cuh): the caller hands one to evk_row_coeffs, evk_digits takes its own per digit from the plain index.
 // ------------------------------------------------------------------------------------------
+// the part behind the load: x = a row of prime j in quad layout in registers (k_ct_dot_sp forms its rows there)
 template <int LOGN>
-__device__ __forceinline__ void evk_row_coeffs(uint32_t (&x)[16], const uint32_t *row, uint32_t j, const DevParams &P,
-                                               const DevTables &T, uint32_t *lds, int tj)
+__device__ __forceinline__ void evk_quads_coeffs(uint32_t (&x)[16], uint32_t j, const DevParams &P, const DevTables &T,
+                                                 uint32_t *lds, int tj)
 {
     constexpr int N   = XformGeom<LOGN>::N;
     const uint32_t qj = P.q[j];
-    load_quads(x, row, tj);
     quads_to_tile<16>(x, lds, tj);
     __syncthreads();
     intt_tiles<LOGN>(x, T.intt_rw + (size_t)2 * N * j, qj, lds, tj);
     const uint32_t inv_n = P.inv_n[j], inv_n_sh = P.inv_n_sh[j];
 #pragma unroll
     for (int e = 0; e < 16; e++) x[e] = csub(mul_shoup_lazy(x[e], inv_n, inv_n_sh, qj), qj);
+}
+
+template <int LOGN>
+__device__ __forceinline__ void evk_row_coeffs(uint32_t (&x)[16], const uint32_t *row, uint32_t j, const DevParams &P,
+                                               const DevTables &T, uint32_t *lds, int tj)
+{
+    load_quads(x, row, tj);
+    evk_quads_coeffs<LOGN>(x, j, P, T, lds, tj);
 }
 
 // One quad of a (word, Shoup) row pair, the layout of every key column and plan diagonal (kernel_args.h): the words
@@ -887,14 +1008,13 @@ hipError_t launch_ct_galois(const DevParams &P, const DevTables &T, const Galois
 // NTT_c(D_j mod q) in quad layout, q = q_c the prime of key column c and rw its roots: the centred coefficients of input
 // row j (GALOIS: of sigma_g of it) reduced mod q and transformed.  Ends with the plane in use by the wave-local
 // transpose: the caller's barrier after the multiply-accumulate releases it.
+// sp_quads_digit: the same on x = row j in quad layout in registers, as load_quads with the opaque index tj leaves it.
 template <int LOGN, bool GALOIS>
-__device__ __forceinline__ void sp_row_digit(uint32_t (&x)[16], const uint32_t *row, uint32_t j, uint32_t g, uint32_t q,
-                                             const uint32_t *rw, const DevParams &P, const DevTables &T, uint32_t *lds,
-                                             int t)
+__device__ __forceinline__ void sp_quads_digit(uint32_t (&x)[16], uint32_t j, uint32_t g, uint32_t q, const uint32_t *rw,
+                                               const DevParams &P, const DevTables &T, uint32_t *lds, int t, int tj)
 {
-    const int tj      = opaque_index(t);
     const uint32_t qj = P.q[j], hj = qj >> 1, up = q - qj;   // up: mod 2^32 where q < q_j
-    evk_row_coeffs<LOGN>(x, row, j, P, T, lds, tj);
+    evk_quads_coeffs<LOGN>(x, j, P, T, lds, tj);
     constexpr int N = XformGeom<LOGN>::N;
     if constexpr (GALOIS)
     {
@@ -917,6 +1037,16 @@ __device__ __forceinline__ void sp_row_digit(uint32_t (&x)[16], const uint32_t *
     const int td = opaque_index(t);
     ntt_tiles<LOGN>(x, rw, q, lds, td);
     tile_to_quads<16>(x, lds, td);
+}
+
+template <int LOGN, bool GALOIS>
+__device__ __forceinline__ void sp_row_digit(uint32_t (&x)[16], const uint32_t *row, uint32_t j, uint32_t g, uint32_t q,
+                                             const uint32_t *rw, const DevParams &P, const DevTables &T, uint32_t *lds,
+                                             int t)
+{
+    const int tj = opaque_index(t);
+    load_quads(x, row, tj);
+    sp_quads_digit<LOGN, GALOIS>(x, j, g, q, rw, P, T, lds, t, tj);
 }
 
 // Between the passes of every special-prime kernel (ct_key_switch_sp, ct_hoist_sp): the accumulators hold acc_k[p] in
@@ -1209,6 +1339,160 @@ hipError_t launch_ct_switch_sp(const DevParams &P, const DevTables &T, const Res
         const size_t plane = (size_t)G::SLOTS * sizeof(uint32_t);
         return A.row_ptr ? launch(k_ct_switch_sum_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A)
                          : launch(k_ct_switch_sp<L>, grid, dim3(G::THREADS), plane, st, P, T, R, A);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Encrypted inner products: se_amd_ct_dot_sp_device (MulSumArgs).  Relinearisation is linear in d2, so the products of a
+// CSR row are summed as tensors (T0, T1, T2 of k_ct_mul_sum) and T2 of the ROW is key-switched once:
+//   out_k[g] = T_k[g] + ks_k(T2[g]),   ks as in ct_key_switch_sp (centred digits, one division by P).
+// The body of ct_key_switch_sp<LOGN, false> in its geometry -- one workgroup of n/16 threads per (output row, output
+// prime i < L), LDS the exchange plane alone, no scratch, no global temporary -- with every row it would load formed in
+// registers instead, in the quad layout load_quads gives (dot_rows), so the tensor sums never touch memory:
+//   row:    validity first (mul_sum_row): the row_ptr pair, then every ia[k] < Ba and ib[k] < Bb, before an index forms
+//           an address; blockIdx and loop counters only: wave-uniform.  Invalid (status 2) and empty (status 1) rows are
+//           all zero.
+//   pass 0: per j < L: row j of T2 = sum_k a1[ia[k]][j] . b1[ib[k]][j], a quad at a time (two quad loads per pair, the
+//           lazy rule of k_ct_mul_sum), canonical -> sp_quads_digit mod P -> evk_mac against row j, column p;
+//           then sp_delta once;
+//   pass 1: the same for j != i against column i; row i of T2 enters as it was summed, with no transform;
+//   epilogue: . P^-1, canonical; T1[i] is formed (four quad loads per pair) and added into the divided acc1, which is
+//           stored; then T0[i] (two) into the divided acc0.  Exact and canonical at every step; no third accumulator.
+// Every value that meets evk_mac, sp_delta and the epilogue is the one k_ct_relin_sp reads from the slabs k_ct_mul_sum
+// wrote, and the operations on it are the same in the same order: the same bits, for a row of any length; a row of one
+// pair has those of k_ct_mul and k_ct_relin_sp.  A row of m >= 2 pairs is NOT the sum of m relinearised products: one
+// rounding centred(INTT_p(acc[p]), P) instead of m.
+// Transforms per workgroup: 4 L + 2 whatever m is (against (4 L + 2) m).  Input rows read per workgroup: 2 m for each of
+// the 2 L rows of T2 it forms and 6 m in the epilogue, (4 L + 6) m, where k_ct_mul_sum (its share: 4 m) and k_ct_relin_sp
+// (2 L + 2) read 4 m + 2 L + 2: the price of no intermediate, and it grows with m L.
+// Live set: two accumulator tiles, the row being formed (16) and ONE quad in flight (a 64-bit accumulator quad and the
+// pair's input quads), as evk_mac works the key a quad at a time.
+// A long row is not sliced: it runs on L workgroups (sum in groups, then se_amd_ct_lincomb_device over the group sums).
+// grid evk_grid(G, L).
+// ------------------------------------------------------------------------------------------
+// r = quad c of row `off / N` of T_TERM summed over the pairs [lo, hi), canonical.  off = j N + quad_index(t, c).
+template <int TERM>
+__device__ __forceinline__ void dot_quad(uint32_t (&r)[4], const MulSumArgs &A, uint32_t lo, uint32_t hi, size_t words,
+                                         size_t off, uint32_t q, uint32_t cr_hi, uint32_t cr_lo)
+{
+    auto quad = [&](const uint32_t *slab, size_t rec) { return *reinterpret_cast<const uint4 *>(slab + rec * words + off); };
+    Lane4 acc;
+    for (uint32_t k = lo; k < hi;)
+    {
+        const uint32_t end = mul_sum_period_end(k, hi);
+        for (; k < end; k++)
+        {
+            const size_t ia = A.ia ? A.ia[k] : k, ib = A.ib ? A.ib[k] : k;   // checked by mul_sum_row
+            if constexpr (TERM == 0) acc.mad4(quad(A.a0, ia), quad(A.b0, ib));
+            if constexpr (TERM == 1)
+            {
+                acc.mad4(quad(A.a0, ia), quad(A.b1, ib));
+                acc.mad4(quad(A.a1, ia), quad(A.b0, ib));
+            }
+            if constexpr (TERM == 2) acc.mad4(quad(A.a1, ia), quad(A.b1, ib));
+        }
+        acc.reduce(q, cr_hi, cr_lo);
+    }
+    const uint4 v = acc.get();
+    r[0] = v.x, r[1] = v.y, r[2] = v.z, r[3] = v.w;
+}
+
+// x = row j of T_TERM in quad layout (TERM 2), or x += that row mod q_j, canonical (TERM 0, 1: the epilogue's addends)
+template <int TERM>
+__device__ __forceinline__ void dot_rows(uint32_t (&x)[16], const MulSumArgs &A, uint32_t lo, uint32_t hi, size_t words,
+                                         size_t row_off, uint32_t j, const DevParams &P, int tq)
+{
+    const uint32_t q = P.q[j], cr_hi = P.cr_hi[j], cr_lo = P.cr_lo[j];
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        uint32_t r[4];
+        dot_quad<TERM>(r, A, lo, hi, words, row_off + quad_index(tq, c), q, cr_hi, cr_lo);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            if constexpr (TERM == 2)
+                x[4 * c + k] = r[k];
+            else
+                x[4 * c + k] = csub(x[4 * c + k] + r[k], q);
+        }
+    }
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS) void k_ct_dot_sp(const DevParams P, const DevTables T,
+                                                                     const RescaleParams R, const MulSumArgs A)
+{
+    using G         = XformGeom<LOGN>;
+    constexpr int N = G::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lds      = reinterpret_cast<uint32_t *>(smem);
+    const int t        = threadIdx.x;
+    const uint32_t i   = blockIdx.y;
+    const uint32_t sp  = A.np - 1;
+    const uint32_t qi  = P.q[i];
+    const size_t words = (size_t)A.primes * N;   // of a record
+
+    for (size_t g = blockIdx.x; g < A.G; g += gridDim.x)
+    {
+        uint32_t lo, hi;
+        const bool bad = mul_sum_row(A, g, lo, hi);
+        const int te   = opaque_index(t);
+        const size_t o = g * words + (size_t)i * N;
+        uint32_t acc0[16], acc1[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;
+        if (lo == hi)   // empty, or invalid
+        {
+            store_quads(A.out0 + o, acc0, te);
+            store_quads(A.out1 + o, acc1, te);
+            if (A.status && i == 0 && t == 0) A.status[g] = bad ? 2 : 1;
+            continue;
+        }
+        // pass 0: modulo P against key column p; pass 1: modulo q_i against key column i.  One body for both.
+#pragma unroll 1
+        for (uint32_t pass = 0; pass < 2; pass++)
+        {
+            const uint32_t col = pass ? i : sp;
+            const uint32_t q   = P.q[col];
+            const uint32_t *rw = T.ntt_rw + 2 * xform_table_len(N) * col;
+            for (uint32_t j = 0; j < A.primes; j++)
+            {
+                uint32_t y[16];
+                const int tj = opaque_index(t);
+                dot_rows<2>(y, A, lo, hi, words, (size_t)j * N, j, P, tj);
+                if (!(pass && j == i)) sp_quads_digit<LOGN, false>(y, j, 0, q, rw, P, T, lds, t, tj);
+                const uint32_t *key = A.key + ((size_t)j * A.np + col) * 2 * N + quad_index(opaque_index(t), 0);
+                evk_mac<LOGN>(acc0, acc1, y, key, A.half, q);
+                __syncthreads();
+            }
+            if (pass == 0) sp_delta<LOGN>(acc0, acc1, i, sp, P, T, lds, t);
+        }
+        // ks_k = acc_k . P^-1; T1[i] joins the divided acc1, which leaves first, then T0[i] the divided acc0
+        const uint32_t w = R.inv[i], wp = R.inv_sh[i];
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc1[e] = csub(mul_shoup_lazy(acc1[e], w, wp, qi), qi);
+        dot_rows<1>(acc1, A, lo, hi, words, (size_t)i * N, i, P, te);
+        store_quads(A.out1 + o, acc1, te);
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc0[e] = csub(mul_shoup_lazy(acc0[e], w, wp, qi), qi);
+        dot_rows<0>(acc0, A, lo, hi, words, (size_t)i * N, i, P, te);
+        store_quads(A.out0 + o, acc0, te);
+        if (A.status && i == 0 && t == 0) A.status[g] = 1;
+    }
+}
+
+// LOGN 12 .. 14, as launch_ct_key_switch_sp.
+hipError_t launch_ct_dot_sp(const DevParams &P, const DevTables &T, const RescaleParams &R, const MulSumArgs &A,
+                            hipStream_t st)
+{
+    if (A.G == 0) return hipSuccess;
+    if (P.logn < 12) return hipErrorInvalidValue;
+    return for_logn(P.logn, [&](auto l) {
+        constexpr int L = decltype(l)::value < 12 ? 12 : decltype(l)::value;
+        using G         = XformGeom<L>;
+        return launch(k_ct_dot_sp<L>, evk_grid(A.G, A.primes), dim3(G::THREADS), (size_t)G::SLOTS * sizeof(uint32_t), st,
+                      P, T, R, A);
     });
 }
 

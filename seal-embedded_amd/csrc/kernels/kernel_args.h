@@ -188,6 +188,31 @@ struct MulArgs
     uint32_t primes;
 };
 hipError_t launch_ct_mul(const DevParams &, const MulArgs &, hipStream_t);
+// Grouped product sums (ct_ops.hip: k_ct_mul_sum, k_ct_dot_sp): output row g takes the pairs k in
+// [row_ptr[g], row_ptr[g + 1]) (CSR rows as LincombArgs, unweighted), pair k = record ia[k] of (a0, a1) times record
+// ib[k] of (b0, b1) (ia = ib = NULL: k, k), and per prime j < primes and element, canonical mod q_j:
+//   T0[g] = sum_k x0 y0,   T1[g] = sum_k (x0 y1 + x1 y0),   T2[g] = sum_k x1 y1.
+// k_ct_mul_sum stores (T0, T1, T2) and reads no key.  k_ct_dot_sp adds the special-prime key switch of d = T2[g] under
+// the relinearisation key (KeySwitchSpArgs: acc_k, delta_k, ks_k) and stores out_k[g] = T_k[g] + ks_k: one division by
+// P per row, and (T0, T1, T2) never in memory.
+// status[g] (optional): 1; 2 with an all-zero row in every output slab for an ia[k] >= Ba, an ib[k] >= Bb or a row_ptr
+// pair that decreases or passes nnz.  An empty row is all zero with status 1.
+struct MulSumArgs
+{
+    const uint32_t *a0, *a1;        // [Ba][primes][n]
+    const uint32_t *b0, *b1;        // [Bb][primes][n]
+    const uint32_t *row_ptr;        // [G + 1]
+    const uint32_t *ia, *ib;        // [nnz] each, or both NULL
+    uint32_t *out0, *out1, *out2;   // [G][primes][n]; k_ct_dot_sp: out2 unused
+    uint8_t *status;                // [G], optional
+    const uint32_t *key;            // k_ct_dot_sp: the special-prime relinearisation key block
+    size_t half;                    // words of one key half: R' np 2 n
+    uint32_t G, nnz, Ba, Bb;
+    uint32_t np;                    // columns of a key row (the context's primes)
+    uint32_t primes;                // 1 .. np; k_ct_dot_sp: 1 .. np - 1
+};
+hipError_t launch_ct_mul_sum(const DevParams &, const MulSumArgs &, hipStream_t);
+hipError_t launch_ct_dot_sp(const DevParams &, const DevTables &, const RescaleParams &, const MulSumArgs &, hipStream_t);
 // The key switch of ct_ops.hip, shared by every kernel from here to launch_ct_galois_accum_sp (evk_row_coeffs, evk_digits, evk_mac;
 // grid evk_grid(B, primes)).  `key` is one device evaluation-key block, built
 // by Context::build_evk from the host's two halves: [2][R][np][2][n], R = 2 np rows of the CONTEXT's np columns, each

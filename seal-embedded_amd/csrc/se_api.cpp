@@ -340,6 +340,26 @@ int se_amd_ct_mul_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *
                          as_stream(stream));
 }
 
+int se_amd_ct_mul_sum_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0,
+                             const uint32_t *d_b1, size_t Bb, size_t primes, size_t G, const uint32_t *d_row_ptr,
+                             const uint32_t *d_ia, const uint32_t *d_ib, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                             uint32_t *d_out2, uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mul_sum(d_a0, d_a1, Ba, d_b0, d_b1, Bb, primes, G, d_row_ptr, d_ia, d_ib, nnz, false, d_out0, d_out1,
+                             d_out2, d_status, as_stream(stream));
+}
+
+int se_amd_ct_dot_sp_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0,
+                            const uint32_t *d_b1, size_t Bb, size_t primes, size_t G, const uint32_t *d_row_ptr,
+                            const uint32_t *d_ia, const uint32_t *d_ib, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
+                            uint8_t *d_status, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_mul_sum(d_a0, d_a1, Ba, d_b0, d_b1, Bb, primes, G, d_row_ptr, d_ia, d_ib, nnz, true, d_out0, d_out1,
+                             nullptr, d_status, as_stream(stream));
+}
+
 int se_amd_decrypt3_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2,
                                  size_t B, size_t primes, double scale, int64_t *d_pte, float *d_values,
                                  double *d_values_f64, uint8_t *d_status, void *stream)

@@ -1445,6 +1445,62 @@ int Context::ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const
     return 0;
 }
 
+// The tensor summed over CSR rows of pairs (MulSumArgs).  dot false: key-free, (T0, T1, T2) to three slabs, nothing of
+// the context is written.  dot true: T2 of every row key-switched under the installed special-prime relinearisation
+// key inside the same launch (the digit key, Galois keys and a switch ring do not serve), d_out2 unused.  One launch, no
+// scratch, no host synchronisation; the pair indices are compared with Ba / Bb inside the kernel (status 2).
+int Context::ct_mul_sum(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0, const uint32_t *d_b1,
+                        size_t Bb, size_t primes, size_t G, const uint32_t *d_row_ptr, const uint32_t *d_ia,
+                        const uint32_t *d_ib, size_t nnz, bool dot, uint32_t *d_out0, uint32_t *d_out1, uint32_t *d_out2,
+                        uint8_t *d_status, hipStream_t st)
+{
+    if (dot && !special_prime_ok()) return kErrInvalid;
+    constexpr size_t k32 = (size_t)1 << 32;
+    if (!d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_out0 || !d_out1 || (!dot && !d_out2) || !d_row_ptr || !d_ia != !d_ib)
+        return kErrInvalid;
+    if (primes < 1 || primes > hp.nprimes - dot || G >= k32 || nnz >= k32 || Ba >= k32 || Bb >= k32) return kErrInvalid;
+    if (!d_ia && (nnz != Ba || nnz != Bb)) return kErrInvalid;
+    if (!aligned16({d_a0, d_a1, d_b0, d_b1, d_out0, d_out1, d_out2})) return kErrInvalid;
+    MulSumArgs ma{};
+    ma.a0      = d_a0;
+    ma.a1      = d_a1;
+    ma.b0      = d_b0;
+    ma.b1      = d_b1;
+    ma.row_ptr = d_row_ptr;
+    ma.ia      = d_ia;
+    ma.ib      = d_ib;
+    ma.out0    = d_out0;
+    ma.out1    = d_out1;
+    ma.out2    = d_out2;
+    ma.status  = d_status;
+    ma.G       = (uint32_t)G;
+    ma.nnz     = (uint32_t)nnz;
+    ma.Ba      = (uint32_t)Ba;
+    ma.Bb      = (uint32_t)Bb;
+    ma.np      = (uint32_t)hp.nprimes;
+    ma.primes  = (uint32_t)primes;
+    if (!dot)
+    {
+        if (G == 0) return 0;
+        SEAMD_HIP(hipSetDevice(device));
+        SEAMD_HIP(launch_ct_mul_sum(dp, ma, st));
+        return 0;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    const uint32_t *key = (const uint32_t *)evk[1].relin;
+    if (!key)
+    {
+        set_last_error("no special-prime relinearisation key is installed (se_amd_set_relin_key_sp)");
+        return kErrNoKey;
+    }
+    if (G == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    ma.key  = key;
+    ma.half = evk_rows(true) * hp.nprimes * 2 * hp.n;
+    SEAMD_HIP(launch_ct_dot_sp(dp, dt, host_rescale_params(hp, hp.nprimes), ma, st));
+    return 0;
+}
+
 // One device evaluation-key block [2][R][np][2][n] (kernels/kernel_args.h) from the host's halves k0, k1 [R][np][n],
 // R = 2 np rows of a digit key or np - 1 of a special-prime key:
 // staged through `stage`, every column given its Shoup companions on the device (launch_relin_key_rows), and

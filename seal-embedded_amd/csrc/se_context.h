@@ -240,6 +240,12 @@ struct Context
     int ct_mul(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0, const uint32_t *d_b1,
                size_t Bb, size_t primes, size_t P, const uint32_t *d_ia, const uint32_t *d_ib, uint32_t *d_out0,
                uint32_t *d_out1, uint32_t *d_out2, uint8_t *d_status, hipStream_t st);
+    // the tensor summed over CSR rows of pairs (MulSumArgs): key-free to three slabs, or (dot) with the special-prime
+    // relinearisation of every row's T2 inside the same launch, to two; one launch, no scratch
+    int ct_mul_sum(const uint32_t *d_a0, const uint32_t *d_a1, size_t Ba, const uint32_t *d_b0, const uint32_t *d_b1,
+                   size_t Bb, size_t primes, size_t G, const uint32_t *d_row_ptr, const uint32_t *d_ia,
+                   const uint32_t *d_ib, size_t nnz, bool dot, uint32_t *d_out0, uint32_t *d_out1, uint32_t *d_out2,
+                   uint8_t *d_status, hipStream_t st);
     // sp (here and on the Galois keys): the special-prime key of R' = np - 1 rows instead of the digit key of 2 np
     int gen_relin_key(const uint8_t *sk_packed, const uint8_t *a_seeds, const uint8_t *e_seeds, uint32_t *evk0_out,
                       uint32_t *evk1_out, bool sp = false);
