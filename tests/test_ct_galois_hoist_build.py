@@ -1,42 +1,21 @@
 """CPU-side checks of the hoisted rotations (many rotations of a record from one digit decomposition): the two entries
-are declared, exported and wrapped, every instantiation of the kernel compiles for gfx950 without private memory and
-keeps the waves per SIMD it was built with, the moving-sum example is plain C, and the algebra the definition rests on
--- sigma applied to a TRANSFORMED digit is the permutation src_g of the transform of sigma applied to the integer digit
--- holds with the oracle and Python integers (no GPU needed)."""
+are declared, exported and wrapped (what the kernel compiles to: tests/test_ct_ops_build.py), the moving-sum example is
+plain C, and the algebra the definition rests on -- sigma applied to a TRANSFORMED digit is the permutation src_g of the
+transform of sigma applied to the integer digit -- holds with the oracle and Python integers (no GPU needed)."""
 import os
 
 import numpy as np
 import pytest
 
-from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from build_support import ROOT, assert_entries, compile_only, pkg  # noqa: F401  (pkg is a fixture)
 from vectors import galois_image, sigma_coeff
 
 ENTRIES = ("se_amd_ct_galois_many_device", "se_amd_ct_galois_sum_device")
 METHODS = ("ct_galois_many", "ct_galois_sum")
-# Waves per SIMD of k_ct_galois_hoist<logn, SUM> as built (tools/resource_usage.py ct_ops): the sum form carries one
-# accumulator pair like its siblings k_ct_relin / k_ct_galois and keeps their 4 (107 / 122 / 121 / 127 / 111 VGPRs for
-# logn 10 .. 14); the many form carries kHoistGroup = 2 pairs, 139 / 154 / 153 / 159 VGPRs and 3 waves for logn 10 .. 13,
-# and at logn 14, where the workgroup of 1024 threads is 4 waves per SIMD by itself, 128 VGPRs with the coefficients of
-# the input row parked in LDS.  A floor: fewer waves than these is a regression, scratch at any degree is one too.
-HOIST_WAVES = {f"k_ct_galois_hoist<{logn}, true>": 4 for logn in range(10, 15)}
-HOIST_WAVES.update({f"k_ct_galois_hoist<{logn}, false>": 3 for logn in range(10, 14)})
-HOIST_WAVES["k_ct_galois_hoist<14, false>"] = 4
 
 
 def test_header_declares_and_library_exports_the_entries(pkg):
     assert_entries(pkg, ENTRIES, methods=METHODS)
-
-
-def test_hoist_kernels_use_no_scratch_and_keep_their_waves():
-    rows = resource_rows("ct_ops")
-    assert rows, "tools/resource_usage.py gave no table for ct_ops"
-    assert len(HOIST_WAVES) == 10
-    for k, waves in HOIST_WAVES.items():
-        assert k in rows, (k, sorted(rows))
-        vgpr, scratch, occ = rows[k]
-        print(f"{k}: {vgpr} VGPRs, {scratch} B scratch, {occ} waves/SIMD")
-        assert scratch == 0, (k, scratch)
-        assert occ >= waves, (k, rows[k], waves)
 
 
 def test_moving_sum_example_compiles_as_plain_c(tmp_path):

@@ -1,49 +1,21 @@
 """CPU-side checks of the hoisted rotations on the special-prime key (se_amd_ct_galois_sum_sp_device,
-se_amd_lintrans_create_sp, se_amd_ct_lintrans_sp_device): the entries are declared, exported and wrapped, the two kernels
-compile for gfx950 without private memory at the family's occupancy and cost their siblings nothing, the example is plain
-C, the definition has the two properties the header states, and the CPU simulation of a moving sum and of a matrix-vector
-product on fresh records stays inside the reference's 0.1 (no GPU needed)."""
+se_amd_lintrans_create_sp, se_amd_ct_lintrans_sp_device): the entries are declared, exported and wrapped (what the kernels
+compile to: tests/test_ct_ops_build.py), the example is plain C, the definition has the two properties the header states,
+and the CPU simulation of a moving sum and of a matrix-vector product on fresh records stays inside the reference's 0.1
+(no GPU needed)."""
 import os
 
 import numpy as np
 
-from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from build_support import ROOT, assert_entries, compile_only, pkg  # noqa: F401  (pkg is a fixture)
 from ct_model import edge_row, galois_sp_expect, hoist_sp_expect, sum_of_single_calls
 
 ENTRIES = ("se_amd_ct_galois_sum_sp_device", "se_amd_lintrans_create_sp", "se_amd_ct_lintrans_sp_device")
 METHODS = ("ct_galois_sum_sp", "lintrans_plan_sp", "ct_lintrans_sp")
-NEW = ("k_ct_galois_sum_sp", "k_ct_lintrans_sp")
-NEW_WAVES = {f"{k}<{logn}>": 4 for k in NEW for logn in (12, 13, 14)}
-# the siblings whose helpers the new body shares, at the waves per SIMD they had before it (tools/resource_usage.py ct_ops)
-SIBLING_WAVES = {**{f"{k}<{logn}>": 4 for k in ("k_ct_relin_sp", "k_ct_galois_sp") for logn in (12, 13, 14)},
-                 **{f"k_ct_lintrans<{logn}>": 4 for logn in range(10, 15)},
-                 **{f"k_ct_galois_hoist<{logn}, true>": 4 for logn in range(10, 15)},
-                 **{f"k_ct_galois_hoist<{logn}, false>": 3 for logn in range(10, 14)},
-                 "k_ct_galois_hoist<14, false>": 4}
 
 
 def test_header_declares_and_library_exports_the_entries(pkg):
     assert_entries(pkg, ENTRIES, methods=METHODS)
-
-
-def test_hoisted_special_prime_kernels_use_no_scratch_and_keep_the_occupancy():
-    """Both kernels exist for LOGN 12, 13, 14 and for no other degree, with 0 bytes of scratch and the family's 4 waves per
-    SIMD; every other kernel of ct_ops.hip is at 0 scratch, and k_ct_relin_sp, k_ct_galois_sp, k_ct_galois_hoist and
-    k_ct_lintrans keep their waves per SIMD."""
-    rows = resource_rows("ct_ops")
-    assert rows, "tools/resource_usage.py gave no table for ct_ops"
-    assert len(NEW_WAVES) == 6
-    for k, waves in NEW_WAVES.items():
-        assert k in rows, (k, sorted(rows))
-        vgpr, scratch, occ = rows[k]
-        print(f"{k}: {vgpr} VGPRs, {scratch} B scratch, {occ} waves/SIMD")
-        assert scratch == 0 and occ == waves, (k, rows[k])
-    assert not [k for k in rows if k.startswith(tuple(n + "<" for n in NEW)) and k not in NEW_WAVES]
-    for k, (_, scratch, _) in rows.items():
-        assert scratch == 0, (k, scratch)
-    assert len(SIBLING_WAVES) == 21
-    for k, waves in SIBLING_WAVES.items():
-        assert k in rows and rows[k][2] == waves, (k, rows.get(k), waves)
 
 
 def test_matvec_fresh_example_compiles_as_plain_c(tmp_path):

@@ -1,14 +1,13 @@
 """CPU-side checks of the linear transforms (plaintext-weighted sums of hoisted rotations): the three entries are
-declared, exported and wrapped, every instantiation of the kernel and the fold kernel compile for gfx950 without private
-memory and with the waves per SIMD of the sum form of the hoisted rotations, the matrix-vector example is plain C, and
-the identity the plan rests on -- a weight that does not depend on the key row can be folded into the key -- holds with
-the oracle and Python integers (no GPU needed)."""
+declared, exported and wrapped (what the kernels compile to: tests/test_ct_ops_build.py), the matrix-vector example is
+plain C, and the identity the plan rests on -- a weight that does not depend on the key row can be folded into the key --
+holds with the oracle and Python integers (no GPU needed)."""
 import os
 import re
 
 import numpy as np
 
-from build_support import ROOT, assert_entries, compile_only, pkg, resource_rows  # noqa: F401  (pkg is a fixture)
+from build_support import ROOT, assert_entries, compile_only, pkg  # noqa: F401  (pkg is a fixture)
 
 ENTRIES = ("se_amd_lintrans_create", "se_amd_ct_lintrans_device")      # declared `int name(`
 DESTROY = "se_amd_lintrans_destroy"                                    # declared `void name(`
@@ -22,26 +21,6 @@ def test_header_declares_and_library_exports_the_entries(pkg):
     assert re.search(r"\bvoid\s+%s\s*\(\s*se_amd_lintrans\s*\*" % DESTROY, text)
     assert re.search(r"typedef\s+struct\s+se_amd_lintrans\s+se_amd_lintrans\s*;", text)
     assert DESTROY in pkg.EXPORTED_SYMBOLS and hasattr(pkg.lib(), DESTROY)
-
-
-def test_lintrans_kernels_use_no_scratch_and_keep_the_sum_forms_waves():
-    """k_ct_lintrans<logn> carries the accumulator pair of k_ct_galois_hoist<logn, true> and a weighted epilogue that
-    starts when the transform's registers are dead: at every degree it holds at least the waves per SIMD the same report
-    gives for that sibling (whose own pinned floor is 4), without scratch.  As built: 127 / 121 / 121 / 126 / 111 VGPRs
-    for logn 10 .. 14 beside the sibling's 107 / 122 / 121 / 127 / 111 -- no degree needs the many form's lower floor."""
-    rows = resource_rows("ct_ops")
-    assert rows, "tools/resource_usage.py gave no table for ct_ops"
-    for logn in range(10, 15):
-        k, sibling = f"k_ct_lintrans<{logn}>", f"k_ct_galois_hoist<{logn}, true>"
-        assert k in rows and sibling in rows, (k, sorted(rows))
-        vgpr, scratch, occ = rows[k]
-        print(f"{k}: {vgpr} VGPRs, {scratch} B scratch, {occ} waves/SIMD; {sibling}: {rows[sibling]}")
-        assert scratch == 0, (k, scratch)
-        assert occ >= rows[sibling][2] >= 4, (k, rows[k], rows[sibling])
-    assert "k_lintrans_fold" in rows, sorted(rows)
-    vgpr, scratch, occ = rows["k_lintrans_fold"]
-    print(f"k_lintrans_fold: {vgpr} VGPRs, {scratch} B scratch, {occ} waves/SIMD")
-    assert scratch == 0
 
 
 def test_matvec_example_compiles_as_plain_c(tmp_path):
