@@ -476,8 +476,8 @@ int se_amd_ct_relin_device(se_amd_ctx *ctx, const uint32_t *d_d0, const uint32_t
  * product before its rescale is already at scale^2; a fresh record is first lifted by se_amd_ct_lincomb_device with
  * weight 2^30, which costs one level -- or rotated at its own scale by the special-prime
  * entry further down, se_amd_ct_galois_sp_device, which reserves the last prime for the key instead.
- * Out of scope: plaintext-weighted sums of rotations (the diagonal method), a per-record element list,
- * multi-GPU group entries.
+ * Out of scope: plaintext-weighted sums of rotations (the diagonal method), multi-GPU group entries.  (A per-record
+ * element list is the single form of se_amd_ct_pack_sp_device, on the special-prime keys.)
  *
  * se_amd_galois_element (host only, no context): *elt = 3^(step mod n/2) mod 2n, the step reduced into [0, n/2); step 0
  * gives 1.  se_amd_galois_table (host only): src [n] uint16 with sigma_elt(x)[k] = x[src[k]]; element 1 gives the
@@ -891,6 +891,60 @@ int se_amd_ct_switch_sum_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, 
                                          const uint32_t *d_key_idx /*[B]*/, size_t G, const uint32_t *d_row_ptr /*[G+1]*/,
                                          const uint32_t *d_idx /*[nnz]*/, size_t nnz, uint32_t *d_out0, uint32_t *d_out1
                                          /*[G][primes][n]*/, uint8_t *d_status /*[G], optional*/, void *stream);
+/* Slot packing: per-entry rotations of many records summed in one call,
+ *     out[g] = sum_{k in row g} rot_{elts[d_eidx[k]]}( record d_idx[k] ).
+ * Devices send short records: a 16- or 128-entry vector in the low slots of a 2048-slot ciphertext at n = 4096, and every
+ * later step pays for the empty slots.  Packing m = slots / width records into one divides all of that by m.  The same
+ * entry is the per-record element list (the single form) and the shift-and-add across time-ordered records (a row of
+ * several records with different steps).
+ * Notation of the special-prime blocks above: p = np - 1, P = q_p, records [B][L][n] at level L = primes, 1 <= L <= np - 1,
+ * E = {0 .. L-1, p} the output primes of the key switch, centred(x, q) in (-q/2, q/2], and (k0^e, k1^e) the INSTALLED
+ * special-prime Galois key of elts[e] (se_amd_set_galois_keys_sp): no new key type and no new generator.
+ * Elements: `elts` is a host list of 1 <= E <= SE_AMD_MAX_GALOIS_KEYS odd elements below 2n (the argument E is its
+ * length).  Element 1 is allowed and needs no key: the identity, with no key switch.  A repeated element is allowed.
+ * Entries: entry k is the pair (record d_idx[k], element elts[d_eidx[k]]); row g takes the entries k in [d_row_ptr[g],
+ * d_row_ptr[g + 1]); an entry listed twice counts twice.  Single form: d_row_ptr == d_idx == NULL makes row g the one
+ * entry (record g, element elts[d_eidx[g]]) and requires G == B == nnz: a different element per record.
+ * Per row, with sigma_k the automorphism of elts[d_eidx[k]], b_k = d_idx[k], everything canonical:
+ *     D_{k,j}    = centred(INTT_j(c1[b_k][j]), q_j)                                            j < L
+ *     F_{k,j,i}  = NTT_i(sigma_k(D_{k,j}) mod q_i)                                             i in E (for i = j:
+ *                                                                                              sigma_k(c1[b_k][j]) as it lies)
+ *     ACC_h[i]   = sum_{k in row, elt_k != 1} sum_{j<L} F_{k,j,i} . k_h^{e_k}[j][i]   mod q_i,    h in {0, 1}
+ *     delta_h    = centred(INTT_p(ACC_h[p]), P)
+ *     ks_h[i]    = (ACC_h[i] - NTT_i(delta_h mod q_i)) . P^-1   mod q_i, i < L        (se_amd_rescale_constants(degree, np, ..))
+ *     out0[g][i] = ks_0[i] + sum_{k in row} sigma_k(c0[b_k])[i]
+ *     out1[g][i] = ks_1[i] + sum_{k in row, elt_k = 1} c1[b_k][i]
+ * The c0 terms and the identity entries are added after the division: they are exact.  Five facts.
+ * (1) A row of one entry with element g != 1 is BIT-IDENTICAL to se_amd_ct_galois_sp_device on that record with elt = g:
+ *     the single form is a batch of such calls with a different element per record.
+ * (2) A row that lists ONE record once per element of `elts` is BIT-IDENTICAL to se_amd_ct_galois_sum_sp_device on that
+ *     record with the non-identity elements (the identity, if listed, is served by add_input = 1): the sums in ACC are
+ *     exact and centring commutes with sigma, fact (1) of that block.
+ * (3) A row of identity entries only has ks = 0 and is the plain modular sum of the records.
+ * (4) A row of m >= 2 rotated entries is NOT the modular sum of m single rotations: it carries centred(sum_k delta^k mod P)
+ *     instead of m roundings, and differs wherever |sum_k delta^k| > P/2.
+ * (5) Scale and level are unchanged: the result is an ordinary level-L record under the same key.
+ * One launch, no scratch, no global temporary: (4 L - 2) m + 4 transforms per output row and prime for m rotated entries
+ * against (4 L + 2) m for m single rotations, whose m intermediate records and the sum over them are not needed either.
+ * A row runs on L workgroups whatever its length and is not sliced: pack a long row in two tiers, in groups, then
+ * se_amd_ct_lincomb_device over the group results.
+ * Status (uint8 [G], optional): an empty row is all zero with status 1; a row with a d_idx[k] >= B, a d_eidx[k] >= E, or a
+ * d_row_ptr pair that decreases or reaches beyond nnz is all zero in both slabs with status 2; other rows are unaffected.
+ * Every index is compared before it forms an address, and the status is decided before anything of the row is written.
+ * SE_ERR_INVALD_ARGUMENT, with nothing written, for a NULL ctx, slab, elts or d_eidx; exactly one of d_row_ptr / d_idx
+ * NULL; the single form with G != B or nnz != B; E = 0 or E > SE_AMD_MAX_GALOIS_KEYS; an even element or one >= 2n;
+ * primes outside [1, np - 1]; a context of one prime; B, G or nnz >= 2^32; a slab pointer that is not 16-byte aligned.
+ * SE_ERR_NO_KEY when a listed element other than 1 has no installed SPECIAL-PRIME Galois key (digit keys, the
+ * relinearisation key and the switch ring do not serve); the last-error text names the element.  G = 0 is a successful
+ * no-op.  Out of scope: plaintext masks or weights per entry; a ring key that switches and rotates in one step
+ * (se_amd_ct_switch_keyed_sp_device first); hoisting when one record appears under many elements
+ * (se_amd_ct_galois_sum_sp_device); a digit-key twin; several special primes; host-pointer and multi-device forms. */
+int se_amd_ct_pack_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                             const uint32_t *elts /*host, [E]*/, size_t E,
+                             size_t G, const uint32_t *d_row_ptr /*[G+1] or NULL*/, const uint32_t *d_idx /*[nnz] or NULL*/,
+                             const uint32_t *d_eidx /*[nnz]*/, size_t nnz,
+                             uint32_t *d_out0, uint32_t *d_out1 /*[G][primes][n]*/,
+                             uint8_t *d_status /*[G], optional*/, void *stream);
 /* Encrypted inner products: grouped product sums.  A variance, an inner product of two senders' vectors, a polynomial
  * score are sums of products, and relinearisation is linear in d2: sum the tensors, key-switch once.  Row g takes the
  * pairs k in [d_row_ptr[g], d_row_ptr[g + 1]) (the CSR rows of se_amd_ct_lincomb_device, unweighted); pair k is record

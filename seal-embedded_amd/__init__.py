@@ -80,6 +80,7 @@ EXPORTED_SYMBOLS = (
     "se_amd_gen_switch_keys_sp", "se_amd_set_switch_keyring_sp", "se_amd_ct_switch_keyed_sp_device",
     "se_amd_ct_switch_sum_keyed_sp_device",
     "se_amd_ct_mul_sum_device", "se_amd_ct_dot_sp_device",
+    "se_amd_ct_pack_sp_device",
 )
 
 
@@ -210,6 +211,7 @@ def lib():
     L.se_amd_set_switch_keyring_sp.argtypes = [vp, sz, vp, vp]
     L.se_amd_ct_switch_keyed_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.se_amd_ct_switch_sum_keyed_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp]
+    L.se_amd_ct_pack_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.se_amd_ct_mul_sum_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.se_amd_ct_dot_sp_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     _lib = L
@@ -879,6 +881,23 @@ class Context:
                                                            _ptr(key_idx), G, _ptr(row_ptr), _ptr(idx), nnz, _ptr(out0),
                                                            _ptr(out1), _ptr(status), _stream_ptr()),
                "se_amd_ct_switch_sum_keyed_sp_device")
+
+    def ct_pack_sp(self, c0, c1, elts, eidx, out0, out1, primes=None, row_ptr=None, idx=None, status=None):
+        """Slot packing: entry k = record idx[k] of (c0, c1) [B][primes][n], primes <= np - 1, rotated by the element
+        elts[eidx[k]] (a host list; element 1 is the identity and needs no key) under the installed special-prime Galois
+        keys; output row g = the sum of the entries row_ptr[g] .. row_ptr[g + 1] with ONE division by the special prime
+        per row; out0, out1 are [G][primes][n].  row_ptr = idx = None: the single form, row g = record g under
+        elts[eidx[g]], the bits of ct_galois_sp per record.  status uint8 [G]: 2 and a zero row for a record index >= B,
+        an element index >= len(elts) or a bad row_ptr pair."""
+        import numpy as np
+        el = np.ascontiguousarray(elts, dtype=np.uint32).reshape(-1)
+        if primes is None:
+            primes = c0.shape[1]
+        G = row_ptr.numel() - 1 if row_ptr is not None else c0.shape[0]
+        _check(self.L.se_amd_ct_pack_sp_device(self.h, _ptr(c0), _ptr(c1), c0.shape[0], primes, _ptr(el), el.size, G,
+                                               _ptr(row_ptr), _ptr(idx), _ptr(eidx), eidx.numel(), _ptr(out0),
+                                               _ptr(out1), _ptr(status), _stream_ptr()),
+               "se_amd_ct_pack_sp_device")
 
     # ---- the rotation family: one private helper per shape of call; the public methods name the symbol and what differs
     def _galois_set(self, sym, in0, in1, elts, out0, out1, primes, stacked=False, flags=()):

@@ -400,6 +400,26 @@ hipError_t launch_ct_galois_many_ext_sp(const DevParams &, const DevTables &, co
 // in (c0, c1) [G][B][primes][n], out [B][primes][n]; G B below 2^32; key[g] the special-prime block of elt[g]
 hipError_t launch_ct_galois_accum_sp(const DevParams &, const DevTables &, const RescaleParams &, const GaloisSetArgs &,
                                      hipStream_t);
+// Slot packing (k_ct_pack_sp, ct_pack.hip): entry k is (record idx[k], element elt[eidx[k]]); an output row takes the
+// entries row_ptr[g] .. row_ptr[g + 1] (CSR rows as SwitchSpArgs), or the one entry (record g, elt[eidx[g]]) (row_ptr =
+// idx = NULL, rows = B = nnz).  With sigma_k the automorphism of entry k, D_{k,j} = centred(INTT_j(c1[b_k][j])) and E as
+// in KeySwitchSpArgs:
+//   acc_h[i] = sum_{k in row, elt_k != 1} sum_{j < primes} NTT_i(sigma_k(D_{k,j}) mod q_i) . key[eidx[k]]_h[j][i],  i in E;
+//   delta_h, ks_h as in KeySwitchSpArgs: one division by P per row;
+//   out0[g][i] = ks_0[i] + sum_{k in row} sigma_k(c0[b_k])[i],   out1[g][i] = ks_1[i] + sum_{k in row, elt_k = 1} c1[b_k][i].
+// The block's G is the number of listed elements and B the records of the input slabs; key[e] the special-prime block of
+// elt[e], NULL for the identity.  status[g] (optional): 1; 2 with an all-zero row in both slabs for a record index >= B,
+// an element index >= G or a row_ptr pair that decreases or passes nnz.  An empty row is all zero with status 1.
+struct PackSpArgs : GaloisSetArgs
+{
+    const uint32_t *row_ptr, *idx;  // [rows + 1], [nnz]; both NULL: row g is the entry g
+    const uint32_t *eidx;           // [nnz]
+    uint8_t *status;                // [rows], optional
+    size_t rows, nnz;               // each below 2^32
+};
+// in [B][primes][n], out [rows][primes][n]
+hipError_t launch_ct_pack_sp(const DevParams &, const DevTables &, const RescaleParams &, const PackSpArgs &,
+                             hipStream_t);
 // Plan set-up: out[r][k] = in[r][src_elt(k)] on `rows` rows of n words, src the permutation of the automorphism of `elt`
 // (odd, below 2n, checked by the host) on a bit-reversed NTT-form row.
 hipError_t launch_bsgs_permute(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, uint32_t elt,

@@ -544,6 +544,16 @@ int se_amd_ct_switch_sum_keyed_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, 
                                      d_status, as_stream(stream));
 }
 
+int se_amd_ct_pack_sp_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
+                             const uint32_t *elts, size_t E, size_t G, const uint32_t *d_row_ptr, const uint32_t *d_idx,
+                             const uint32_t *d_eidx, size_t nnz, uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status,
+                             void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_pack_sp(d_c0, d_c1, B, primes, elts, E, G, d_row_ptr, d_idx, d_eidx, nnz, d_out0, d_out1, d_status,
+                             as_stream(stream));
+}
+
 int se_amd_ct_galois_many_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes,
                                  const uint32_t *elts, size_t G, uint32_t *d_out0, uint32_t *d_out1, void *stream)
 {

@@ -1838,6 +1838,46 @@ int Context::ct_switch_keyed_sp(const uint32_t *d_c0, const uint32_t *d_c1, size
     return 0;
 }
 
+// Slot packing.  The checks of ct_key_switch_sp in their order (a context of one prime, the slabs, the level in
+// [1, np - 1], alignment), then the entry tables and the elements; under `mu` the special-prime Galois key of every
+// listed element other than 1, read NOW (the digit keys, the relinearisation key and the switch ring do not serve);
+// nothing is launched unless every such element has one.  One launch, no scratch, no host synchronisation: the record
+// and element indices are compared inside the kernel (status 2), never sanitised on the way.
+int Context::ct_pack_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts,
+                        size_t E, size_t G, const uint32_t *d_row_ptr, const uint32_t *d_idx, const uint32_t *d_eidx,
+                        size_t nnz, uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status, hipStream_t st)
+{
+    if (!special_prime_ok()) return kErrInvalid;
+    constexpr size_t k32 = (size_t)1 << 32;
+    PackSpArgs pa{};
+    if (!set_call_args(pa, d_c0, d_c1, d_out0, d_out1, B, primes, true) || !d_eidx) return kErrInvalid;
+    const bool single = !d_row_ptr && !d_idx;
+    if (!single && (!d_row_ptr || !d_idx))
+    {
+        set_last_error("slot packing: d_row_ptr and d_idx are given together, or both NULL (the single form)");
+        return kErrInvalid;
+    }
+    if (single && (G != B || nnz != B))
+    {
+        set_last_error("slot packing: the single form takes one entry per record, G = B = nnz");
+        return kErrInvalid;
+    }
+    if (G >= k32 || nnz >= k32) return kErrInvalid;
+    if (!galois_elts_ok(elts, E, "slot packing: between 1 and 64 elements")) return kErrInvalid;
+    std::lock_guard<std::mutex> lk(mu);
+    if (int rc = resolve_keys(pa, elts, E, true, true)) return rc;
+    if (G == 0) return 0;
+    SEAMD_HIP(hipSetDevice(device));
+    pa.row_ptr = d_row_ptr;
+    pa.idx     = d_idx;
+    pa.eidx    = d_eidx;
+    pa.status  = d_status;
+    pa.rows    = G;
+    pa.nnz     = nnz;
+    SEAMD_HIP(launch_ct_pack_sp(dp, dt, host_rescale_params(hp, hp.nprimes), pa, st));
+    return 0;
+}
+
 // Rows 0 .. primes_out-1 of every record: [B][primes_in][n] -> [B][primes_out][n], one pitched asynchronous device copy
 // per slab, no kernel.  Dropping primes changes neither message nor scale.
 int Context::ct_drop_primes(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes_in, size_t primes_out,

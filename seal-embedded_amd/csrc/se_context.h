@@ -277,6 +277,13 @@ struct Context
                            const uint32_t *d_key_idx, bool sum, size_t G, const uint32_t *d_row_ptr,
                            const uint32_t *d_idx, size_t nnz, uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status,
                            hipStream_t st);
+    // slot packing (PackSpArgs): entry k = (record d_idx[k], element elts[d_eidx[k]]) rotated under the installed
+    // special-prime Galois key of its element (element 1: the identity, no key) and the CSR rows summed with one
+    // division by P per row; d_row_ptr = d_idx = NULL: row g is the entry (g, elts[d_eidx[g]]), G = B = nnz; elts is a
+    // host pointer; one launch, no scratch
+    int ct_pack_sp(const uint32_t *d_c0, const uint32_t *d_c1, size_t B, size_t primes, const uint32_t *elts, size_t E,
+                   size_t G, const uint32_t *d_row_ptr, const uint32_t *d_idx, const uint32_t *d_eidx, size_t nnz,
+                   uint32_t *d_out0, uint32_t *d_out1, uint8_t *d_status, hipStream_t st);
     // hoisted rotations (GaloisHoistArgs): G rotations of every record from one digit decomposition, each to its own
     // output (sum false: outputs [G][B][primes][n]) or summed into one record, with the record itself when add_input
     // (sum true: outputs [B][primes][n]); elts is a host pointer; one launch, no scratch
