@@ -5,6 +5,10 @@ second module needs moves here (device code) or to ct_model (definitions and inp
 - env: the module-scoped fixture (torch, the loaded package, cuda:0); gpu_env() is the same setup as a plain function.
 - dev_t, host_u32, bits, stream_of, same_bytes: host <-> device and bit-pattern conveniences.
 - SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY: the C ABI's error codes; SEED_A, SEED_B, SEED_PK, SEED_EP: the golden seeds.
+- the C entries called directly (the arguments tests): NULL, dptr, hptr (pointers); CEntry, a good argument list by name
+  whose calls replace named fields and whose refused() runs a table of such edits; create_handle, creates_refused (the
+  same for the create entries, which hand back a handle); assert_untouched, assert_zero_prefix (what the refused and
+  the zero-slab calls may have written).
 - the receiving side: records, encrypt_sym, fresh_records, ntt_secret, decode_expect, expectation (oracle + Python ints),
   run_decrypt (decrypt_full / decrypt_level / decrypt3_level and their keyed twins over filled outputs), assert_matches,
   check_level_decrypt.
@@ -82,6 +86,71 @@ def stream_of(env):
 
 def same_bytes(a, b):
     return a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+
+
+# ---- the C entries called directly: pointers, a good argument list by name, what a refused call must leave alone ------
+NULL = C.c_void_p(None)
+
+
+def dptr(t, off=0):
+    """The device pointer of tensor `t`, `off` bytes in (the misalignment cases)."""
+    return C.c_void_p(t.data_ptr() + off)
+
+
+def hptr(a):
+    """The host pointer of NumPy array `a`."""
+    return C.c_void_p(a.ctypes.data)
+
+
+class CEntry:
+    """A C entry with a good argument list by name: CEntry(fn, ctx=h, c0=dptr(c0), ..., stream=s), the keywords in the
+    C parameter order.  entry(**edits) calls fn with the named fields replaced and returns its code."""
+
+    def __init__(self, fn, **good):
+        self.fn, self.good = fn, good
+
+    def __call__(self, **edits):
+        unknown = [k for k in edits if k not in self.good]
+        if unknown:
+            raise TypeError(f"no argument named {unknown} among {list(self.good)}")
+        return self.fn(*{**self.good, **edits}.values())
+
+    def refused(self, cases, code=SE_ERR_INVALD_ARGUMENT):
+        """Every edit dict of `cases`, in order, must make the entry return `code`."""
+        name = getattr(self.fn, "__name__", self.fn)
+        for k, edits in enumerate(cases):
+            got = self(**edits)
+            assert got == code, f"{name}, case {k} {edits}: returned {got}, not {code}"
+
+
+def create_handle(entry, **edits):
+    """One call of a create entry (se_amd_lintrans_create*, se_amd_bsgs_create*) whose `out` field, unless edited, is
+    the byref of a handle that holds 0xDEAD: a failed create must overwrite it with NULL.  -> code, handle."""
+    handle = C.c_void_p(0xDEAD)
+    return entry(**{"out": C.byref(handle), **edits}), handle
+
+
+def creates_refused(entry, cases, code=SE_ERR_INVALD_ARGUMENT):
+    """CEntry.refused for a create entry: every case returns `code` and leaves the handle NULL."""
+    for k, edits in enumerate(cases):
+        rc, handle = create_handle(entry, **edits)
+        assert rc == code and handle.value is None, (k, edits, rc, handle.value)
+
+
+def assert_untouched(*tensors, fill=SENTINEL):
+    """After a synchronise every word of every tensor still holds its fill (status tensors: 77)."""
+    import torch
+    torch.cuda.synchronize()
+    for k, t in enumerate(tensors):
+        assert bool((t == fill).all()), f"tensor {k} was written"
+
+
+def assert_zero_prefix(t, words):
+    """After a synchronise the first `words` words of `t` are zero and everything behind is SENTINEL."""
+    import torch
+    torch.cuda.synchronize()
+    flat = t.reshape(-1)
+    assert int(torch.count_nonzero(flat[:words])) == 0 and bool((flat[words:] == SENTINEL).all())
 
 
 # ---- the receiving side: expectations from the oracle's primitives and Python integers ------------------------------

@@ -13,10 +13,11 @@ import pytest
 from ct_model import (CASE_IDS, GALOIS_CASES, accum_expect, bsgs_expect, edge_row, inverse_element, matrix,
                       matrix_diagonals, permute_diagonals, rand_slab, random_keys, random_plaintexts, stack_sum_expect,
                       stack_sum_python)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_headroom, dev_t, encode_diagonals,  # noqa: F401
-                         env, fresh_records, guarded_pair, host_u32, install_galois_keys, keyed_cases, lift_records,
-                         periodic_values, rescale_records, run_decrypt, run_example, run_galois, run_many, run_plan,
-                         sentinel_out, step_elements, stream_of, take)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_headroom, create_handle, creates_refused, dev_t, dptr,
+                         encode_diagonals, env, fresh_records, guarded_pair, host_u32, hptr, install_galois_keys,
+                         keyed_cases, lift_records, periodic_values, rescale_records, run_decrypt, run_example,
+                         run_galois, run_many, run_plan, sentinel_out, step_elements, stream_of, take)
 
 pytestmark = pytest.mark.gpu
 
@@ -304,168 +305,134 @@ def test_bsgs_arguments(env):
     out0 = torch.full((2, B, npr, n), SENTINEL, dtype=torch.int32, device=dev)
     out1 = torch.full_like(out0, SENTINEL)
     pt = torch.ones((2, 2, npr, n), dtype=torch.int32, device=dev)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
     s = stream_of(env)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the 65-element calls
     good, even, big, nokey, twice, ident = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 5), el(3, 3), el(1, 3)
-    I0, I1, O0, O1, PT, E = p(stack0), p(stack1), p(out0), p(out1), p(pt), hp(good)
 
-    def untouched():
-        torch.cuda.synchronize()
-        assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    msum = CEntry(L.se_amd_ct_mul_plain_sum_device, ctx=h, in0=dptr(stack0), in1=dptr(stack1), E=2, B=B, primes=npr,
+                  pt=dptr(pt), Gout=2, pt_primes=npr, out0=dptr(out0), out1=dptr(out1), stream=s)
+    msum.refused([
+        dict(ctx=None),
+        dict(in0=NULL),                                            # NULL in0, out0, pt
+        dict(out0=NULL),
+        dict(pt=NULL),
+        dict(in1=NULL),                                            # one of in1 / out1 alone
+        dict(out1=NULL),
+        dict(primes=0),                                            # primes outside [1, np]
+        dict(primes=npr + 1, pt_primes=npr + 1),
+        dict(pt_primes=npr - 1),                                   # pt_primes < primes
+        dict(B=2 ** 32),                                           # B >= 2^32
+        dict(in0=dptr(stack0, 4)),                                 # alignment, each pointer
+        dict(in1=dptr(stack1, 8)),
+        dict(pt=dptr(pt, 12)),
+        dict(out0=dptr(out0, 4)),
+        dict(out1=dptr(out1, 8)),
+        dict(E=0),                                                 # E, Gout outside [1, 64]
+        dict(E=65),
+        dict(Gout=0),
+        dict(Gout=65),
+        dict(B=2 ** 31, Gout=1),                                   # E B, Gout B at or above 2^32
+        dict(E=1, B=2 ** 31),
+    ])
+    assert msum(B=0) == 0
+    assert_untouched(out0, out1)
 
-    # -- entry 1: (ctx, in0, in1, E, B, primes, pt, Gout, pt_primes, out0, out1)
-    def msum(*a):
-        return L.se_amd_ct_mul_plain_sum_device(*a, s)
-
-    bad = [
-        (None, I0, I1, 2, B, npr, PT, 2, npr, O0, O1),
-        (h, z, I1, 2, B, npr, PT, 2, npr, O0, O1),                 # NULL in0, out0, pt
-        (h, I0, I1, 2, B, npr, PT, 2, npr, z, O1),
-        (h, I0, I1, 2, B, npr, z, 2, npr, O0, O1),
-        (h, I0, z, 2, B, npr, PT, 2, npr, O0, O1),                 # one of in1 / out1 alone
-        (h, I0, I1, 2, B, npr, PT, 2, npr, O0, z),
-        (h, I0, I1, 2, B, 0, PT, 2, npr, O0, O1),                  # primes outside [1, np]
-        (h, I0, I1, 2, B, npr + 1, PT, 2, npr + 1, O0, O1),
-        (h, I0, I1, 2, B, npr, PT, 2, npr - 1, O0, O1),            # pt_primes < primes
-        (h, I0, I1, 2, 2 ** 32, npr, PT, 2, npr, O0, O1),          # B >= 2^32
-        (h, p(stack0, 4), I1, 2, B, npr, PT, 2, npr, O0, O1),      # alignment, each pointer
-        (h, I0, p(stack1, 8), 2, B, npr, PT, 2, npr, O0, O1),
-        (h, I0, I1, 2, B, npr, p(pt, 12), 2, npr, O0, O1),
-        (h, I0, I1, 2, B, npr, PT, 2, npr, p(out0, 4), O1),
-        (h, I0, I1, 2, B, npr, PT, 2, npr, O0, p(out1, 8)),
-        (h, I0, I1, 0, B, npr, PT, 2, npr, O0, O1),                # E, Gout outside [1, 64]
-        (h, I0, I1, 65, B, npr, PT, 2, npr, O0, O1),
-        (h, I0, I1, 2, B, npr, PT, 0, npr, O0, O1),
-        (h, I0, I1, 2, B, npr, PT, 65, npr, O0, O1),
-        (h, I0, I1, 2, 2 ** 31, npr, PT, 1, npr, O0, O1),          # E B, Gout B at or above 2^32
-        (h, I0, I1, 1, 2 ** 31, npr, PT, 2, npr, O0, O1),
-    ]
-    for k, a in enumerate(bad):
-        assert msum(*a) == SE_ERR_INVALD_ARGUMENT, ("sum", k)
-    assert msum(h, I0, I1, 2, 0, npr, PT, 2, npr, O0, O1) == 0
-    untouched()
-
-    # -- entry 2: (ctx, in0, in1, B, primes, elts, G, out0, out1)
-    def accum(*a):
-        return L.se_amd_ct_galois_accum_device(*a, s)
-
-    bad = [
-        (None, I0, I1, B, npr, E, 2, O0, O1),
-        (h, z, I1, B, npr, E, 2, O0, O1),                          # NULL slab pointers
-        (h, I0, z, B, npr, E, 2, O0, O1),
-        (h, I0, I1, B, npr, E, 2, z, O1),
-        (h, I0, I1, B, npr, E, 2, O0, z),
-        (h, I0, I1, B, 0, E, 2, O0, O1),                           # primes outside [1, np]
-        (h, I0, I1, B, npr + 1, E, 2, O0, O1),
-        (h, I0, I1, 2 ** 32, npr, E, 2, O0, O1),                   # B >= 2^32
-        (h, p(stack0, 4), I1, B, npr, E, 2, O0, O1),               # alignment, each slab
-        (h, I0, p(stack1, 8), B, npr, E, 2, O0, O1),
-        (h, I0, I1, B, npr, E, 2, p(out0, 12), O1),
-        (h, I0, I1, B, npr, E, 2, O0, p(out1, 4)),
-        (h, I0, I1, B, npr, z, 2, O0, O1),                         # elts NULL, G = 0, G = 65
-        (h, I0, I1, B, npr, E, 0, O0, O1),
-        (h, I0, I1, B, npr, E, 65, O0, O1),
-        (h, I0, I1, B, npr, hp(even), 2, O0, O1),                  # an even element, one >= 2n
-        (h, I0, I1, B, npr, hp(big), 2, O0, O1),
-        (h, I0, I1, 2 ** 31, npr, E, 2, O0, O1),                   # G B at or above 2^32
-    ]
-    for k, a in enumerate(bad):
-        assert accum(*a) == SE_ERR_INVALD_ARGUMENT, ("accum", k)
-    assert accum(h, I0, I1, B, npr, hp(nokey), 2, O0, O1) == SE_ERR_NO_KEY
+    accum = CEntry(L.se_amd_ct_galois_accum_device, ctx=h, in0=dptr(stack0), in1=dptr(stack1), B=B, primes=npr,
+                   elts=hptr(good), G=2, out0=dptr(out0), out1=dptr(out1), stream=s)
+    accum.refused([
+        dict(ctx=None),
+        dict(in0=NULL),                                            # NULL slab pointers
+        dict(in1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                            # primes outside [1, np]
+        dict(primes=npr + 1),
+        dict(B=2 ** 32),                                           # B >= 2^32
+        dict(in0=dptr(stack0, 4)),                                 # alignment, each slab
+        dict(in1=dptr(stack1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(elts=NULL),                                           # elts NULL, G = 0, G = 65
+        dict(G=0),
+        dict(G=65),
+        dict(elts=hptr(even)),                                     # an even element, one >= 2n
+        dict(elts=hptr(big)),
+        dict(B=2 ** 31),                                           # G B at or above 2^32
+    ])
+    assert accum(elts=hptr(nokey)) == SE_ERR_NO_KEY
     assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
-    assert accum(h, I0, I1, 0, npr, E, 2, O0, O1) == 0
-    untouched()
+    assert accum(B=0) == 0
+    assert_untouched(out0, out1)
     # element 1 needs no key; a repeat is allowed: zero keys and zero slabs give zero rows
     for elts in (ident, twice):
-        assert accum(h, I0, I1, B, npr, hp(elts), 2, O0, O1) == 0
-        torch.cuda.synchronize()
+        assert accum(elts=hptr(elts)) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:B * npr * n])) == 0 and bool((flat[B * npr * n:] == SENTINEL).all())
+            assert_zero_prefix(o, B * npr * n)
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
 
-    # -- create: (ctx, baby, n1, giant, n2, d_diag, pt_primes, out)
-    def create(ctx_h, baby, n1, giant, n2, d, ptp, want_out=True):
-        handle = C.c_void_p(0xDEAD)                         # a failed create must overwrite it with NULL
-        rc = L.se_amd_bsgs_create(ctx_h, baby, n1, giant, n2, d, ptp, C.byref(handle) if want_out else None)
-        return rc, handle
-
-    G1 = hp(ident)
-    bad = [
-        (None, E, 2, G1, 2, PT, npr),
-        (h, z, 2, G1, 2, PT, npr),                                 # NULL lists, NULL diagonals
-        (h, E, 2, z, 2, PT, npr),
-        (h, E, 2, G1, 2, z, npr),
-        (h, E, 0, G1, 2, PT, npr),                                 # n1, n2 outside [1, 64]
-        (h, E, 65, G1, 2, PT, npr),
-        (h, E, 2, G1, 0, PT, npr),
-        (h, E, 2, G1, 65, PT, npr),
-        (h, E, 2, G1, 2, PT, 0),                                   # pt_primes = 0
-        (h, hp(even), 2, G1, 2, PT, npr),                          # an even element, one >= 2n, in either list
-        (h, E, 2, hp(big), 2, PT, npr),
-        (h, E, 2, G1, 2, p(pt, 4), npr),                           # alignment
-        (h, hp(twice), 2, G1, 2, PT, npr),                         # a repeat within a list
-        (h, E, 2, hp(twice), 2, PT, npr),
-    ]
-    for k, a in enumerate(bad):
-        rc, handle = create(*a)
-        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, ("create", k, rc, handle.value)
-    assert create(h, E, 2, G1, 2, PT, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT     # NULL out
-    rc, plan = create(h, E, 2, G1, 2, PT, 2)                # baby (3, 9), giant (1, 3), two levels
+    mk = CEntry(L.se_amd_bsgs_create, ctx=h, baby=hptr(good), n1=2, giant=hptr(ident), n2=2, diag=dptr(pt),
+                pt_primes=npr, out=None)
+    creates_refused(mk, [
+        dict(ctx=None),
+        dict(baby=NULL),                                           # NULL lists, NULL diagonals
+        dict(giant=NULL),
+        dict(diag=NULL),
+        dict(n1=0),                                                # n1, n2 outside [1, 64]
+        dict(n1=65),
+        dict(n2=0),
+        dict(n2=65),
+        dict(pt_primes=0),                                         # pt_primes = 0
+        dict(baby=hptr(even)),                                     # an even element, one >= 2n, in either list
+        dict(giant=hptr(big)),
+        dict(diag=dptr(pt, 4)),                                    # alignment
+        dict(baby=hptr(twice)),                                    # a repeat within a list
+        dict(giant=hptr(twice)),
+    ])
+    assert create_handle(mk, out=None)[0] == SE_ERR_INVALD_ARGUMENT                         # NULL out
+    rc, plan = create_handle(mk, pt_primes=2)               # baby (3, 9), giant (1, 3), two levels
     assert rc == 0 and plan.value
-    rc, foreign = create(other.h, E, 2, G1, 2, PT, npr)
+    rc, foreign = create_handle(mk, ctx=other.h)
     assert rc == 0 and foreign.value
-    rc, unkeyed = create(h, hp(nokey), 2, G1, 2, PT, npr)   # create reads no key: element 5 is found at call time
+    rc, unkeyed = create_handle(mk, baby=hptr(nokey))       # create reads no key: element 5 is found at call time
     assert rc == 0 and unkeyed.value
     L.se_amd_bsgs_workspace_bytes.restype = C.c_size_t
     per = 2 * (2 + 2) * 2 * n * 4
     assert L.se_amd_bsgs_workspace_bytes(plan, 5, 2) == 5 * per and L.se_amd_bsgs_workspace_bytes(None, 5, 2) == 0
 
-    # -- the call: (ctx, plan, c0, c1, B, primes, out0, out1, workspace, bytes)
     ws = torch.full((B * per // 4 + 4,), SENTINEL, dtype=torch.int32, device=dev)
-    W, WB = p(ws), B * per
-
-    def call(*a):
-        return L.se_amd_ct_bsgs_device(*a, s)
-
-    bad = [
-        (None, plan, I0, I1, B, 2, O0, O1, W, WB),
-        (h, plan, z, I1, B, 2, O0, O1, W, WB),                     # NULL slab pointers
-        (h, plan, I0, z, B, 2, O0, O1, W, WB),
-        (h, plan, I0, I1, B, 2, z, O1, W, WB),
-        (h, plan, I0, I1, B, 2, O0, z, W, WB),
-        (h, plan, I0, I1, B, 0, O0, O1, W, WB),                    # primes outside [1, np]
-        (h, plan, I0, I1, B, 4, O0, O1, W, WB),
-        (h, plan, I0, I1, 2 ** 32, 2, O0, O1, W, WB),              # B >= 2^32
-        (h, plan, p(stack0, 4), I1, B, 2, O0, O1, W, WB),          # alignment, each slab
-        (h, plan, I0, p(stack1, 8), B, 2, O0, O1, W, WB),
-        (h, plan, I0, I1, B, 2, p(out0, 12), O1, W, WB),
-        (h, plan, I0, I1, B, 2, O0, p(out1, 4), W, WB),
-        (h, z, I0, I1, B, 2, O0, O1, W, WB),                       # no plan, a plan of another context
-        (h, foreign, I0, I1, B, 2, O0, O1, W, WB),
-        (other.h, plan, I0, I1, B, 2, O0, O1, W, WB),
-        (h, plan, I0, I1, B, 3, O0, O1, W, WB),                    # a level above the plan's
-        (h, plan, I0, I1, B, 2, O0, O1, z, WB),                    # the workspace: NULL, misaligned, below one record
-        (h, plan, I0, I1, B, 2, O0, O1, p(ws, 8), WB - 8),
-        (h, plan, I0, I1, B, 2, O0, O1, W, per - 16),
-    ]
-    for k, a in enumerate(bad):
-        assert call(*a) == SE_ERR_INVALD_ARGUMENT, ("call", k)
-    assert call(h, unkeyed, I0, I1, B, 2, O0, O1, W, WB) == SE_ERR_NO_KEY
+    call = CEntry(L.se_amd_ct_bsgs_device, ctx=h, plan=plan, c0=dptr(stack0), c1=dptr(stack1), B=B, primes=2,
+                  out0=dptr(out0), out1=dptr(out1), workspace=dptr(ws), bytes=B * per, stream=s)
+    call.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                             # NULL slab pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                            # primes outside [1, np]
+        dict(primes=4),
+        dict(B=2 ** 32),                                           # B >= 2^32
+        dict(c0=dptr(stack0, 4)),                                  # alignment, each slab
+        dict(c1=dptr(stack1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(plan=NULL),                                           # no plan, a plan of another context
+        dict(plan=foreign),
+        dict(ctx=other.h),
+        dict(primes=3),                                            # a level above the plan's
+        dict(workspace=NULL),                                      # the workspace: NULL, misaligned, below one record
+        dict(workspace=dptr(ws, 8), bytes=B * per - 8),
+        dict(bytes=per - 16),
+    ])
+    assert call(plan=unkeyed) == SE_ERR_NO_KEY
     assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
-    assert call(h, plan, I0, I1, 0, 2, O0, O1, W, WB) == 0
-    untouched()
+    assert call(B=0) == 0
+    assert_untouched(out0, out1)
     assert bool((ws == SENTINEL).all()), "an error or a no-op wrote the workspace"
     # the plan works: zero keys and zero slabs give zero rows at level 2, one record per chunk
-    assert call(h, plan, I0, I1, B, 2, O0, O1, W, per) == 0
-    torch.cuda.synchronize()
+    assert call(bytes=per) == 0
     for o in (out0, out1):
-        flat = o.reshape(-1)
-        assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+        assert_zero_prefix(o, B * 2 * n)
     assert bool((ws[per // 4:] == SENTINEL).all()), "words behind one record of workspace are written"
     L.se_amd_bsgs_destroy(None)
     for pl in (plan, foreign, unkeyed):

@@ -5,8 +5,6 @@ Every expectation is the definition in tests/ct_model_bsgs_sp.py (and tests/ct_m
 oracle's primitives and Python / NumPy integers, never the code under test.  Every comparison is bit-exact except the
 reference's own acceptance criterion |values - expected| < 0.1.
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -14,10 +12,11 @@ from ct_model import (CASE_IDS, SHAPE_IDS, SP_CASES, add_mod, edge_diagonals, ed
                       matrix_diagonals, rand_key, rand_slab)
 from ct_model_bsgs_sp import (accum_sp_expect, bsgs_sp_expect, ext_primes, many_ext_expect, mod_down_expect,
                               stack_sum_ext_expect)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
-                         encode_diagonals, env, fresh_records, guarded_pair, host_u32, install_galois_keys, keyed_cases,
-                         periodic_values, rescale_records, run_example, run_galois_sp, sentinel_out, step_elements,
-                         stream_of, take)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_level_decrypt, create_handle, creates_refused, dev_t, dptr,
+                         drop_records, encode_diagonals, env, fresh_records, guarded_pair, host_u32, hptr,
+                         install_galois_keys, keyed_cases, periodic_values, rescale_records, run_example, run_galois_sp,
+                         sentinel_out, step_elements, stream_of, take)
 
 pytestmark = pytest.mark.gpu
 
@@ -355,30 +354,27 @@ def test_plan_reads_the_keys_at_call_time_and_kinds_are_refused(env):
     ws_bytes = ctx.bsgs_workspace_bytes(plan, B, L)
     assert ws_bytes >= ctx.bsgs_workspace_bytes(digit, B, L) > 0
     ws = torch.full((ws_bytes // 4,), SENTINEL, dtype=torch.int32, device=env["dev"])
-    p = lambda t: C.c_void_p(t.data_ptr())
-    s = stream_of(env)
-    fd, fp = lib.se_amd_ct_bsgs_device, lib.se_amd_ct_bsgs_sp_device
-    call = lambda f, hh, pl: f(hh, pl.h, p(d0), p(d1), B, L, p(out0), p(out1), p(ws), ws_bytes, s)
-    assert call(fp, h, plan) == SE_ERR_NO_KEY
+    run = dict(ctx=h, plan=plan.h, c0=dptr(d0), c1=dptr(d1), B=B, primes=L, out0=dptr(out0), out1=dptr(out1),
+               workspace=dptr(ws), bytes=ws_bytes, stream=stream_of(env))
+    fd, fp = CEntry(lib.se_amd_ct_bsgs_device, **run), CEntry(lib.se_amd_ct_bsgs_sp_device, **run)
+    assert fp() == SE_ERR_NO_KEY
     assert "special-prime" in lib.se_amd_last_error().decode() and "element 3" in lib.se_amd_last_error().decode()
     dkey = np.zeros((2, 2 * npr, npr, n), dtype=np.uint32)
     ctx.set_galois_keys([3, 9], dkey, dkey)
-    assert call(fp, h, plan) == SE_ERR_NO_KEY                      # an installed digit key does not serve
+    assert fp() == SE_ERR_NO_KEY                                   # an installed digit key does not serve
     keys = {g: (rand_key(rng, o.q, n), rand_key(rng, o.q, n)) for g in (3, 9)}
     ctx.set_galois_keys_sp([3], keys[3][0][None], keys[3][1][None])
-    assert call(fp, h, plan) == SE_ERR_NO_KEY and "element 9" in lib.se_amd_last_error().decode()
+    assert fp() == SE_ERR_NO_KEY and "element 9" in lib.se_amd_last_error().decode()
     ctx.set_galois_keys_sp([3, 9], np.stack([keys[3][0], keys[9][0]]), np.stack([keys[3][1], keys[9][1]]))
     other.set_galois_keys_sp([3, 9], np.stack([keys[3][0], keys[9][0]]), np.stack([keys[3][1], keys[9][1]]))
-    assert call(fp, h, digit) == SE_ERR_INVALD_ARGUMENT
-    assert call(fd, h, plan) == SE_ERR_INVALD_ARGUMENT
-    assert call(fp, h, foreign) == SE_ERR_INVALD_ARGUMENT
-    assert call(fp, other.h, plan) == SE_ERR_INVALD_ARGUMENT
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((ws == SENTINEL).all())
+    fp.refused([dict(plan=digit.h)])                               # each entry refuses the other kind's plan
+    fd.refused([dict(plan=plan.h)])
+    fp.refused([dict(plan=foreign.h), dict(ctx=other.h)])          # and a plan of another context
+    assert_untouched(out0, out1, ws)
     g0, g1 = run_bsgs_sp(env, ctx, plan, d0, d1, L, B)
     e0, e1 = bsgs_sp_expect(pkg.galois_table, o, c0, c1, baby, giant, diag, keys)
     assert (g0 == e0).all() and (g1 == e1).all()
-    assert call(fd, h, digit) == 0                                 # the digit plan still serves its own entry
+    assert fd(plan=digit.h) == 0                                   # the digit plan still serves its own entry
     torch.cuda.synchronize()
     for pl in (plan, digit, foreign):
         pl.close()
@@ -405,110 +401,94 @@ def test_bsgs_sp_arguments(env):
     out1 = torch.full_like(out0, SENTINEL)
     ws = torch.full((1 << 20,), SENTINEL, dtype=torch.int32, device=env["dev"])
     diag = torch.ones((2, 2, npr, n), dtype=torch.int32, device=env["dev"])
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
     s = stream_of(env)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)
-    good, even, big, twice = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 3)
-    P0, P1, I0, I1, O0, O1, E, D = p(c0), p(c1), p(big_in), p(big_in), p(out0), p(out1), hp(good), p(diag)
-    fm, fs = lib.se_amd_ct_galois_many_ext_sp_device, lib.se_amd_ct_mul_plain_sum_ext_sp_device
-    fd, fa = lib.se_amd_ct_mod_down_sp_device, lib.se_amd_ct_galois_accum_sp_device
-    fc, fp = lib.se_amd_bsgs_create_sp, lib.se_amd_ct_bsgs_sp_device
-    for f, a, b in ((fm, P0, P1), (fa, I0, I1)):               # (ctx, in0, in1, B, primes, elts, G, out0, out1, stream)
-        bad = [
-            (None, a, b, B, 2, E, 2, O0, O1, s),
-            (h, z, b, B, 2, E, 2, O0, O1, s), (h, a, z, B, 2, E, 2, O0, O1, s),
-            (h, a, b, B, 2, E, 2, z, O1, s), (h, a, b, B, 2, E, 2, O0, z, s),
-            (h, a, b, B, 0, E, 2, O0, O1, s), (h, a, b, B, npr, E, 2, O0, O1, s), (h, a, b, B, npr + 1, E, 2, O0, O1, s),
-            (h, a, b, 2 ** 32, 2, E, 2, O0, O1, s), (h, a, b, 2 ** 31, 2, E, 2, O0, O1, s),       # B, G . B
-            (h, p(c0, 4), b, B, 2, E, 2, O0, O1, s), (h, a, p(c1, 8), B, 2, E, 2, O0, O1, s),
-            (h, a, b, B, 2, E, 2, p(out0, 12), O1, s), (h, a, b, B, 2, E, 2, O0, p(out1, 4), s),
-            (h, a, b, B, 2, z, 2, O0, O1, s), (h, a, b, B, 2, E, 0, O0, O1, s), (h, a, b, B, 2, E, 65, O0, O1, s),
-            (h, a, b, B, 2, hp(even), 2, O0, O1, s), (h, a, b, B, 2, hp(big), 2, O0, O1, s),
-        ]
-        for k, args in enumerate(bad):
-            assert f(*args) == SE_ERR_INVALD_ARGUMENT, (f.__name__, k)
-        assert f(h, a, b, B, 2, hp(el(3, 5)), 2, O0, O1, s) == SE_ERR_NO_KEY
+    good, even, big, twice, nokey = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 3), el(3, 5)
+    rot = dict(ctx=h, in0=dptr(c0), in1=dptr(c1), B=B, primes=2, elts=hptr(good), G=2, out0=dptr(out0), out1=dptr(out1),
+               stream=s)
+    fm = CEntry(lib.se_amd_ct_galois_many_ext_sp_device, **rot)
+    fa = CEntry(lib.se_amd_ct_galois_accum_sp_device, **{**rot, "in0": dptr(big_in), "in1": dptr(big_in)})
+    for f in (fm, fa):
+        f.refused([
+            dict(ctx=None),
+            dict(in0=NULL), dict(in1=NULL),
+            dict(out0=NULL), dict(out1=NULL),
+            dict(primes=0), dict(primes=npr), dict(primes=npr + 1),
+            dict(B=2 ** 32), dict(B=2 ** 31),                                                     # B, G . B
+            dict(in0=dptr(c0, 4)), dict(in1=dptr(c1, 8)),
+            dict(out0=dptr(out0, 12)), dict(out1=dptr(out1, 4)),
+            dict(elts=NULL), dict(G=0), dict(G=65),
+            dict(elts=hptr(even)), dict(elts=hptr(big)),
+        ])
+        assert f(elts=hptr(nokey)) == SE_ERR_NO_KEY
         assert "element 5" in lib.se_amd_last_error().decode()
-        assert f(h, a, b, 0, 2, E, 2, O0, O1, s) == 0
-    bad_sums = [                                                # (ctx, in0, in1, E, B, primes, pt, Gout, out0, out1, stream)
-        (None, I0, I1, 2, B, 2, D, 2, O0, O1, s),
-        (h, z, I1, 2, B, 2, D, 2, O0, O1, s), (h, I0, I1, 2, B, 2, z, 2, O0, O1, s), (h, I0, I1, 2, B, 2, D, 2, z, O1, s),
-        (h, I0, z, 2, B, 2, D, 2, O0, O1, s), (h, I0, I1, 2, B, 2, D, 2, O0, z, s),            # one of in1 / out1 alone
-        (h, I0, I1, 2, B, 0, D, 2, O0, O1, s), (h, I0, I1, 2, B, npr, D, 2, O0, O1, s),
-        (h, I0, I1, 0, B, 2, D, 2, O0, O1, s), (h, I0, I1, 65, B, 2, D, 2, O0, O1, s),
-        (h, I0, I1, 2, B, 2, D, 0, O0, O1, s), (h, I0, I1, 2, B, 2, D, 65, O0, O1, s),
-        (h, I0, I1, 2, 2 ** 32, 2, D, 2, O0, O1, s), (h, I0, I1, 2, 2 ** 31, 2, D, 1, O0, O1, s),
-        (h, I0, I1, 1, 2 ** 31, 2, D, 2, O0, O1, s),
-        (h, p(big_in, 4), I1, 2, B, 2, D, 2, O0, O1, s), (h, I0, I1, 2, B, 2, p(diag, 8), 2, O0, O1, s),
-        (h, I0, I1, 2, B, 2, D, 2, O0, p(out1, 4), s),
-    ]
-    for k, args in enumerate(bad_sums):
-        assert fs(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert fs(h, I0, I1, 2, 0, 2, D, 2, O0, O1, s) == 0
-    bad_downs = [                                               # (ctx, in0, in1, count, primes, out0, out1, stream)
-        (None, I0, I1, B, 2, O0, O1, s), (h, z, I1, B, 2, O0, O1, s), (h, I0, I1, B, 2, z, O1, s),
-        (h, I0, z, B, 2, O0, O1, s), (h, I0, I1, B, 2, O0, z, s),
-        (h, I0, I1, B, 0, O0, O1, s), (h, I0, I1, B, npr, O0, O1, s), (h, I0, I1, 2 ** 31, 2, O0, O1, s),
-        (h, p(big_in, 4), I1, B, 2, O0, O1, s), (h, I0, I1, B, 2, p(out0, 8), O1, s),
-    ]
-    for k, args in enumerate(bad_downs):
-        assert fd(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert fd(h, I0, I1, 0, 2, O0, O1, s) == 0 and fd(h, I0, z, 0, 2, O0, z, s) == 0
+        assert f(B=0) == 0
+    fs = CEntry(lib.se_amd_ct_mul_plain_sum_ext_sp_device, ctx=h, in0=dptr(big_in), in1=dptr(big_in), E=2, B=B, primes=2,
+                pt=dptr(diag), Gout=2, out0=dptr(out0), out1=dptr(out1), stream=s)
+    fs.refused([
+        dict(ctx=None),
+        dict(in0=NULL), dict(pt=NULL), dict(out0=NULL),
+        dict(in1=NULL), dict(out1=NULL),                                                       # one of in1 / out1 alone
+        dict(primes=0), dict(primes=npr),
+        dict(E=0), dict(E=65),
+        dict(Gout=0), dict(Gout=65),
+        dict(B=2 ** 32), dict(B=2 ** 31, Gout=1),
+        dict(E=1, B=2 ** 31),
+        dict(in0=dptr(big_in, 4)), dict(pt=dptr(diag, 8)),
+        dict(out1=dptr(out1, 4)),
+    ])
+    assert fs(B=0) == 0
+    fd = CEntry(lib.se_amd_ct_mod_down_sp_device, ctx=h, in0=dptr(big_in), in1=dptr(big_in), count=B, primes=2,
+                out0=dptr(out0), out1=dptr(out1), stream=s)
+    fd.refused([
+        dict(ctx=None), dict(in0=NULL), dict(out0=NULL),
+        dict(in1=NULL), dict(out1=NULL),
+        dict(primes=0), dict(primes=npr), dict(count=2 ** 31),
+        dict(in0=dptr(big_in, 4)), dict(out0=dptr(out0, 8)),
+    ])
+    assert fd(count=0) == 0 and fd(in1=NULL, count=0, out1=NULL) == 0
 
-    def create(ctx_h, bs, n1, gs, n2, d, pt, want_out=True, f=fc):
-        handle = C.c_void_p(0xDEAD)
-        return f(ctx_h, bs, n1, gs, n2, d, pt, C.byref(handle) if want_out else None), handle
-
-    bad_creates = [
-        (None, E, 2, E, 2, D, npr), (h, z, 2, E, 2, D, npr), (h, E, 2, z, 2, D, npr), (h, E, 2, E, 2, z, npr),
-        (h, E, 0, E, 2, D, npr), (h, E, 65, E, 2, D, npr), (h, E, 2, E, 0, D, npr), (h, E, 2, E, 65, D, npr),
-        (h, E, 2, E, 2, D, 0), (h, E, 2, E, 2, D, npr - 1), (h, E, 2, E, 2, D, npr + 1),        # pt_primes must be np
-        (h, hp(even), 2, E, 2, D, npr), (h, E, 2, hp(big), 2, D, npr), (h, hp(twice), 2, E, 2, D, npr),
-        (h, E, 2, E, 2, p(diag, 4), npr),
-    ]
-    for k, args in enumerate(bad_creates):
-        rc, handle = create(*args)
-        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, (k, rc, handle.value)
-    assert create(h, E, 2, E, 2, D, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT
-    rc, plan = create(h, E, 2, E, 2, D, npr)
+    fc = CEntry(lib.se_amd_bsgs_create_sp, ctx=h, baby=hptr(good), n1=2, giant=hptr(good), n2=2, diag=dptr(diag),
+                pt_primes=npr, out=None)
+    creates_refused(fc, [
+        dict(ctx=None), dict(baby=NULL), dict(giant=NULL), dict(diag=NULL),
+        dict(n1=0), dict(n1=65), dict(n2=0), dict(n2=65),
+        dict(pt_primes=0), dict(pt_primes=npr - 1), dict(pt_primes=npr + 1),                    # pt_primes must be np
+        dict(baby=hptr(even)), dict(giant=hptr(big)), dict(baby=hptr(twice)),
+        dict(diag=dptr(diag, 4)),
+    ])
+    assert create_handle(fc, out=None)[0] == SE_ERR_INVALD_ARGUMENT
+    rc, plan = create_handle(fc)
     assert rc == 0 and plan.value
     per = lib.se_amd_bsgs_workspace_bytes(plan, 1, 2)
     assert per == 2 * ((2 + 2) * 3 + 2 * 2) * n * 4 and lib.se_amd_bsgs_workspace_bytes(None, 1, 2) == 0
-    W, wb = p(ws), ws.numel() * 4
+    wb = ws.numel() * 4
     assert wb >= 2 * per
-    bad_calls = [                              # (ctx, plan, c0, c1, B, primes, out0, out1, workspace, bytes, stream)
-        (None, plan, P0, P1, B, 2, O0, O1, W, wb, s), (h, z, P0, P1, B, 2, O0, O1, W, wb, s),
-        (h, plan, z, P1, B, 2, O0, O1, W, wb, s), (h, plan, P0, z, B, 2, O0, O1, W, wb, s),
-        (h, plan, P0, P1, B, 2, z, O1, W, wb, s), (h, plan, P0, P1, B, 2, O0, z, W, wb, s),
-        (h, plan, P0, P1, B, 0, O0, O1, W, wb, s), (h, plan, P0, P1, B, npr, O0, O1, W, wb, s),
-        (h, plan, P0, P1, 2 ** 32, 2, O0, O1, W, wb, s),
-        (h, plan, p(c0, 4), P1, B, 2, O0, O1, W, wb, s), (h, plan, P0, P1, B, 2, O0, p(out1, 8), W, wb, s),
-        (h, plan, P0, P1, B, 2, O0, O1, z, wb, s), (h, plan, P0, P1, B, 2, O0, O1, p(ws, 4), wb - 4, s),
-        (h, plan, P0, P1, B, 2, O0, O1, W, per - 4, s),
-    ]
-    for k, args in enumerate(bad_calls):
-        assert fp(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert fp(h, plan, P0, P1, 0, 2, O0, O1, W, wb, s) == 0
+    fp = CEntry(lib.se_amd_ct_bsgs_sp_device, ctx=h, plan=plan, c0=dptr(c0), c1=dptr(c1), B=B, primes=2,
+                out0=dptr(out0), out1=dptr(out1), workspace=dptr(ws), bytes=wb, stream=s)
+    fp.refused([
+        dict(ctx=None), dict(plan=NULL),
+        dict(c0=NULL), dict(c1=NULL),
+        dict(out0=NULL), dict(out1=NULL),
+        dict(primes=0), dict(primes=npr),
+        dict(B=2 ** 32),
+        dict(c0=dptr(c0, 4)), dict(out1=dptr(out1, 8)),
+        dict(workspace=NULL), dict(workspace=dptr(ws, 4), bytes=wb - 4),
+        dict(bytes=per - 4),
+    ])
+    assert fp(B=0) == 0
     # a context of one prime has no prime to reserve
     one = pkg.Context(1024, 1)
-    ol, oh = one.L, one.h
-    assert ol.se_amd_ct_galois_many_ext_sp_device(oh, P0, P1, B, 1, E, 2, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
-    assert ol.se_amd_ct_galois_accum_sp_device(oh, I0, I1, B, 1, E, 2, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
-    assert ol.se_amd_ct_mul_plain_sum_ext_sp_device(oh, I0, I1, 2, B, 1, D, 2, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
-    assert ol.se_amd_ct_mod_down_sp_device(oh, I0, I1, B, 1, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
-    rc, handle = create(oh, E, 2, E, 2, D, 1, f=ol.se_amd_bsgs_create_sp)
-    assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None
-    assert ol.se_amd_ct_bsgs_sp_device(oh, plan, P0, P1, B, 1, O0, O1, W, wb, s) == SE_ERR_INVALD_ARGUMENT
+    for f in (fm, fa, fs, fd):
+        f.refused([dict(ctx=one.h, primes=1)])
+    creates_refused(fc, [dict(ctx=one.h, pt_primes=1)])
+    fp.refused([dict(ctx=one.h, primes=1)])
     one.close()
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((ws == SENTINEL).all())
+    assert_untouched(out0, out1, ws)
     # a level-1 call on zero slabs and zero keys writes B . n zero words and nothing behind them
-    assert fp(h, plan, P0, P1, B, 1, O0, O1, W, wb, s) == 0
-    torch.cuda.synchronize()
+    assert fp(primes=1) == 0
     for o in (out0, out1):
-        assert int(torch.count_nonzero(o[:B * n])) == 0 and bool((o[B * n:] == SENTINEL).all())
+        assert_zero_prefix(o, B * n)
     lib.se_amd_bsgs_destroy(plan)
     ctx.close()
 
@@ -535,40 +515,42 @@ def test_digit_and_special_prime_twins_refuse_in_their_own_order(env):
     pt = torch.ones((1, 2, npr, n), dtype=torch.int32, device=env["dev"])
     out0 = torch.full((2 * B * (npr + 1) * n,), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     s = stream_of(env)
-    I0, I1, O0, O1, M0, D = p(stack), p(stack), p(out0), p(out1), p(out0, 4), p(pt)
-    keyless, even = np.array([3, 7], dtype=np.uint32), np.array([3, 4], dtype=np.uint32)
+    keyed, keyless, even = (np.array(g, dtype=np.uint32) for g in ([3, 3], [3, 7], [3, 4]))
     SEED = "unsupported parameter set (degree, primes), or primes < 2"
     ELEMENT = "Galois element 4 is not odd and below 2n"
     STACK = "weighted sum over a stack: E and Gout between 1 and 64, E B and Gout B below 2^32"
+    # the lists the edits below start from; none is called as it stands
+    rot = dict(ctx=h, in0=dptr(stack), in1=dptr(stack), B=B, primes=1, elts=hptr(keyed), G=2, out0=dptr(out0),
+               out1=dptr(out1), stream=s)
+    tot = dict(ctx=h, in0=dptr(stack), in1=dptr(stack), B=B, primes=1, elts=hptr(keyed), G=2, add_input=0,
+               out0=dptr(out0), out1=dptr(out1), stream=s)
+    fa, fa_sp = CEntry(lib.se_amd_ct_galois_accum_device, **rot), CEntry(lib.se_amd_ct_galois_accum_sp_device, **rot)
+    fg, fg_sp = CEntry(lib.se_amd_ct_galois_sum_device, **tot), CEntry(lib.se_amd_ct_galois_sum_sp_device, **tot)
+    fs = CEntry(lib.se_amd_ct_mul_plain_sum_device, ctx=h, in0=dptr(stack), in1=dptr(stack), E=1, B=B, primes=1,
+                pt=dptr(pt), Gout=1, pt_primes=npr, out0=dptr(out0), out1=dptr(out1), stream=s)
+    fs_sp = CEntry(lib.se_amd_ct_mul_plain_sum_ext_sp_device, ctx=h, in0=dptr(stack), in1=dptr(stack), E=1, B=B, primes=1,
+                   pt=dptr(pt), Gout=1, out0=dptr(out0), out1=dptr(out1), stream=s)
 
-    def refused(what, f, args, text):
+    def refused(f, edits, text):
         assert lib.se_amd_rescale_constants(n, 1, None, None) == SE_ERR_INVALD_ARGUMENT      # seeds the last error
         assert lib.se_amd_last_error().decode() == SEED
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, what
-        assert lib.se_amd_last_error().decode() == text, what
+        f.refused([edits])
+        assert lib.se_amd_last_error().decode() == text, (f.fn.__name__, edits)
 
-    fa, fa_sp = lib.se_amd_ct_galois_accum_device, lib.se_amd_ct_galois_accum_sp_device
-    fg, fg_sp = lib.se_amd_ct_galois_sum_device, lib.se_amd_ct_galois_sum_sp_device
-    fs, fs_sp = lib.se_amd_ct_mul_plain_sum_device, lib.se_amd_ct_mul_plain_sum_ext_sp_device
     # 1. a misaligned output slab in front of everything else
-    for f in (fa, fa_sp):
-        refused((f.__name__, 1), f, (h, I0, I1, B, 1, hp(keyless), 2, M0, O1, s), SEED)
-    for f in (fg, fg_sp):
-        refused((f.__name__, 1), f, (h, I0, I1, B, 1, hp(keyless), 2, 0, M0, O1, s), SEED)
-    refused((fs.__name__, 1), fs, (h, I0, I1, 65, B, 1, D, 1, npr, M0, O1, s), SEED)
-    refused((fs_sp.__name__, 1), fs_sp, (h, I0, I1, 65, B, 1, D, 1, M0, O1, s), SEED)
+    for f in (fa, fa_sp, fg, fg_sp):
+        refused(f, dict(elts=hptr(keyless), out0=dptr(out0, 4)), SEED)
+    refused(fs, dict(E=65, out0=dptr(out0, 4)), SEED)
+    refused(fs_sp, dict(E=65, out0=dptr(out0, 4)), SEED)
     # 2. the level np: the digit side's highest, above the special-prime side's
-    refused((fa.__name__, 2), fa, (h, I0, I1, B, npr, hp(even), 2, O0, O1, s), ELEMENT)
-    refused((fa_sp.__name__, 2), fa_sp, (h, I0, I1, B, npr, hp(even), 2, O0, O1, s), SEED)
-    refused((fg.__name__, 2), fg, (h, I0, I1, B, npr, hp(even), 2, 0, O0, O1, s), ELEMENT)
-    refused((fg_sp.__name__, 2), fg_sp, (h, I0, I1, B, npr, hp(even), 2, 0, O0, O1, s), SEED)
-    refused((fs.__name__, 2), fs, (h, I0, I1, 65, B, npr, D, 1, npr, O0, O1, s), STACK)
-    refused((fs_sp.__name__, 2), fs_sp, (h, I0, I1, 65, B, npr, D, 1, O0, O1, s), SEED)
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    refused(fa, dict(primes=npr, elts=hptr(even)), ELEMENT)
+    refused(fa_sp, dict(primes=npr, elts=hptr(even)), SEED)
+    refused(fg, dict(primes=npr, elts=hptr(even)), ELEMENT)
+    refused(fg_sp, dict(primes=npr, elts=hptr(even)), SEED)
+    refused(fs, dict(E=65, primes=npr), STACK)
+    refused(fs_sp, dict(E=65, primes=npr), SEED)
+    assert_untouched(out0, out1)
     ctx.close()
 
 

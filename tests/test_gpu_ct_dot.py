@@ -4,17 +4,16 @@ intt, decrypt, fft, expand_ternary) and Python / NumPy integers, never the code 
 except the reference's own acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another, and a
 Context(n, L) is the context whose ct_lincomb takes level-L slabs."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ct_model import (CASE_IDS, SHAPE_IDS, SP_CASES, centred, edge_row, galois_seeds, key_errors, rand_key, rand_slab,
                       switch_quotient)
 from ct_model_dot import csr_pairs, dot_sp_expect, mul_sum_expect, product_sum
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
-                         encrypt_sym, env, expectation, guarded_pair, keyed_cases, rescale_records, run_decrypt,
-                         run_example, run_relin_sp, sentinel_out, stream_of, take, unit_values)
+from gpu_support import (NULL, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched, assert_zero_prefix,  # noqa: F401
+                         check_level_decrypt, dev_t, dptr, drop_records, encrypt_sym, env, expectation, guarded_pair,
+                         keyed_cases, rescale_records, run_decrypt, run_example, run_relin_sp, sentinel_out, stream_of,
+                         take, unit_values)
 
 pytestmark = pytest.mark.gpu
 
@@ -274,7 +273,6 @@ def test_dot_arguments(env):
     torch = env["torch"]
     n, npr, B, G = 4096, 3, 2, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     a0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     a1, b0, b1 = (torch.zeros_like(a0) for _ in range(3))
     outs = [torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"]) for _ in range(3)]
@@ -282,70 +280,51 @@ def test_dot_arguments(env):
     rp = dev_t(env, np.array([0, 1, 2], dtype=np.uint32))
     ia = dev_t(env, np.array([1, 0], dtype=np.uint32))
     ib = dev_t(env, np.array([0, 1], dtype=np.uint32))
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)  # noqa: E731
-    z = C.c_void_p(None)
-    s = stream_of(env)
     key = np.zeros((npr - 1, npr, n), dtype=np.uint32)
     ctx.set_relin_key_sp(key, key)
-    # positions: 0 ctx, 1 a0, 2 a1, 3 Ba, 4 b0, 5 b1, 6 Bb, 7 primes, 8 G, 9 row_ptr, 10 ia, 11 ib, 12 nnz, 13.. outputs
-    base1 = [h, p(a0), p(a1), B, p(b0), p(b1), B, 2, G, p(rp), p(ia), p(ib), 2, p(outs[0]), p(outs[1]), p(outs[2]), p(st), s]
-    base2 = base1[:15] + [p(st), s]
+    ins = dict(ctx=ctx.h, a0=dptr(a0), a1=dptr(a1), Ba=B, b0=dptr(b0), b1=dptr(b1), Bb=B, primes=2, G=G, row_ptr=dptr(rp),
+               ia=dptr(ia), ib=dptr(ib), nnz=2, o0=dptr(outs[0]), o1=dptr(outs[1]))
+    f1 = CEntry(ctx.L.se_amd_ct_mul_sum_device, **ins, o2=dptr(outs[2]), status=dptr(st), stream=stream_of(env))
+    f2 = CEntry(ctx.L.se_amd_ct_dot_sp_device, **ins, status=dptr(st), stream=stream_of(env))
 
-    def variants(base, n_out, top):
-        slabs = [1, 2, 4, 5] + list(range(13, 13 + n_out))
-        tens = dict(zip(slabs, [a0, a1, b0, b1] + outs[:n_out]))
-        edits = [(0, None)] + [(k, z) for k in slabs + [9]]                        # NULL ctx, slab, row_ptr
-        edits += [(10, z), (11, z)]                                                # only one of ia / ib NULL
-        edits += [(7, 0), (7, top + 1)]                                            # primes outside the range
-        edits += [(k, 2 ** 32) for k in (3, 6, 8, 12)]                             # Ba, Bb, G, nnz >= 2^32
-        edits += [(k, p(tens[k], 4 * (1 + i % 3))) for i, k in enumerate(slabs)]   # alignment, each slab
-        out = []
-        for k, v in edits:
-            args = list(base)
-            args[k] = v
-            out.append(tuple(args))
-        for nnz, Ba, Bb in ((3, B, B), (2, 3, B), (2, B, 3)):                      # both NULL: nnz != Ba or nnz != Bb
-            args = list(base)
-            args[10] = args[11] = z
-            args[12], args[3], args[6] = nnz, Ba, Bb
-            out.append(tuple(args))
-        return out
+    def cases(top, o2_null=(), o2_off=()):
+        """The refusals both entries share; entry 1's third output slab in its two places."""
+        return [
+            dict(ctx=None),                                                        # NULL ctx, slab, row_ptr
+            dict(a0=NULL), dict(a1=NULL), dict(b0=NULL), dict(b1=NULL), dict(o0=NULL), dict(o1=NULL), *o2_null,
+            dict(row_ptr=NULL),
+            dict(ia=NULL), dict(ib=NULL),                                          # only one of ia / ib NULL
+            dict(primes=0), dict(primes=top + 1),                                  # primes outside the range
+            dict(Ba=2 ** 32), dict(Bb=2 ** 32), dict(G=2 ** 32), dict(nnz=2 ** 32),    # Ba, Bb, G, nnz >= 2^32
+            dict(a0=dptr(a0, 4)), dict(a1=dptr(a1, 8)), dict(b0=dptr(b0, 12)), dict(b1=dptr(b1, 4)),   # alignment, each slab
+            dict(o0=dptr(outs[0], 8)), dict(o1=dptr(outs[1], 12)), *o2_off,
+            dict(ia=NULL, ib=NULL, nnz=3),                                         # both NULL: nnz != Ba or nnz != Bb
+            dict(ia=NULL, ib=NULL, Ba=3),
+            dict(ia=NULL, ib=NULL, Bb=3),
+        ]
 
-    f1, f2 = L.se_amd_ct_mul_sum_device, L.se_amd_ct_dot_sp_device
-    for k, args in enumerate(variants(base1, 3, npr)):
-        assert f1(*args) == SE_ERR_INVALD_ARGUMENT, k
-    for k, args in enumerate(variants(base2, 2, npr - 1)):
-        assert f2(*args) == SE_ERR_INVALD_ARGUMENT, k
-    g0 = list(base1)
-    g0[8] = 0
-    assert f1(*g0) == 0
-    g0 = list(base2)
-    g0[8] = 0
-    assert f2(*g0) == 0
+    f1.refused(cases(npr, [dict(o2=NULL)], [dict(o2=dptr(outs[2], 4))]))
+    f2.refused(cases(npr - 1))
+    assert f1(G=0) == 0
+    assert f2(G=0) == 0
     # a context of one prime has no prime to reserve; entry 1 serves it
     one = env["pkg"].Context(1024, 1)
-    assert one.L.se_amd_ct_dot_sp_device(one.h, *base2[1:7], 1, *base2[8:]) == SE_ERR_INVALD_ARGUMENT
+    f2.refused([dict(ctx=one.h, primes=1)])
     one.close()
-    torch.cuda.synchronize()
-    assert all(bool((o == SENTINEL).all()) for o in outs) and bool((st == 77).all())
+    assert_untouched(*outs)
+    assert_untouched(st, fill=77)
     # Ba = 0: the non-empty rows get status 2, zero rows
-    for f, base, n_out in ((f1, base1, 3), (f2, base2, 2)):
-        args = list(base)
-        args[3] = 0
-        args[7] = 1
+    for f, n_out in ((f1, 3), (f2, 2)):
         for o in outs:
             o.fill_(SENTINEL)
         st.fill_(77)
-        assert f(*args) == 0
+        assert f(Ba=0, primes=1) == 0
         torch.cuda.synchronize()
         assert st.tolist() == [2, 2]
         # a level-1 call writes G . n words per slab and nothing behind them
-        args[3] = B
-        assert f(*args) == 0
-        torch.cuda.synchronize()
+        assert f(primes=1) == 0
         for o in outs[:n_out]:
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:G * n])) == 0 and bool((flat[G * n:] == SENTINEL).all())
+            assert_zero_prefix(o, G * n)
         assert st.tolist() == [1, 1]
     assert bool((outs[2] == SENTINEL).all())                                       # entry 2 has no third slab
     ctx.close()
@@ -368,9 +347,9 @@ def test_dot_key_sets(env):
     out0 = torch.full((1, L, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
     st = torch.full((1,), 77, dtype=torch.uint8, device=env["dev"])
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
-    dot = lambda: ctx.L.se_amd_ct_dot_sp_device(ctx.h, ptr(a[0]), ptr(a[1]), 2, ptr(b[0]), ptr(b[1]), 2, L, 1, ptr(d_rp),  # noqa: E731
-                                                ptr(d_ia), ptr(d_ib), nnz, ptr(out0), ptr(out1), ptr(st), stream_of(env))
+    dot = CEntry(ctx.L.se_amd_ct_dot_sp_device, ctx=ctx.h, a0=dptr(a[0]), a1=dptr(a[1]), Ba=2, b0=dptr(b[0]),
+                 b1=dptr(b[1]), Bb=2, primes=L, G=1, row_ptr=dptr(d_rp), ia=dptr(d_ia), ib=dptr(d_ib), nnz=nnz,
+                 out0=dptr(out0), out1=dptr(out1), status=dptr(st), stream=stream_of(env))
     assert dot() == SE_ERR_NO_KEY
     digit = np.zeros((2 * npr, npr, n), dtype=np.uint32)
     ctx.set_relin_key(digit, digit)
@@ -378,8 +357,8 @@ def test_dot_key_sets(env):
     ctx.set_galois_keys_sp([3], ek[0][None], ek[1][None])
     ctx.set_switch_keyring_sp(ek[0][None], ek[1][None])
     assert dot() == SE_ERR_NO_KEY
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     T = mul_sum_expect(o, *slabs, rows)
     bare = env["pkg"].Context(n, npr)
     g = run_mul_sum(env, bare, a, b, rows, L)

@@ -5,18 +5,16 @@ integers, never from the code under test.  The automorphism of an expectation is
 x^k -> +-x^(k g mod n) pushed through o.intt and o.ntt, never se_amd_galois_table.  Every comparison is bit-exact except
 the reference's own acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
 Oracle(n, L - 1) is the oracle of the level below Oracle(n, L): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import vectors as V
 from ct_model import (CASE_IDS, GALOIS_CASES, SHAPE_IDS, digit_key_errors, digits_of, edge_row, galois_diagonal,
                       galois_expect, galois_seeds, lift_expect, negacyclic, rand_slab, random_keys, sigma_slab, src_table)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_headroom, check_level_decrypt,  # noqa: F401
-                         dev_t, env, expectation, fresh_records, host_u32, install_galois_keys, keyed_cases,
-                         lift_records, ntt_secret, rescale_records, run_example, run_galois, step_elements, stream_of,
-                         unit_values)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_headroom, check_level_decrypt, dev_t, dptr, env, expectation,
+                         fresh_records, host_u32, hptr, install_galois_keys, keyed_cases, lift_records, ntt_secret,
+                         rescale_records, run_example, run_galois, step_elements, stream_of, unit_values)
 from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
@@ -115,26 +113,24 @@ def test_galois_key_generation(env, shape):
     B = 2
     slab = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    p = lambda x: C.c_void_p(x.data_ptr())
-    z = C.c_void_p(None)
-    assert ctx.L.se_amd_decrypt_level_device(ctx.h, p(slab), p(slab), B, npr, ctx.scale(), z, z, z, p(st),
-                                             stream_of(env)) == SE_ERR_NO_KEY
+    assert ctx.L.se_amd_decrypt_level_device(ctx.h, dptr(slab), dptr(slab), B, npr, ctx.scale(), NULL, NULL, NULL,
+                                             dptr(st), stream_of(env)) == SE_ERR_NO_KEY
     out0, out1 = torch.full_like(slab, SENTINEL), torch.full_like(slab, SENTINEL)
-    gal = lambda elt: ctx.L.se_amd_ct_galois_device(ctx.h, p(slab), p(slab), B, npr, elt, p(out0), p(out1),
-                                                    stream_of(env))
-    assert gal(3) == SE_ERR_NO_KEY
+    gal = CEntry(ctx.L.se_amd_ct_galois_device, ctx=ctx.h, c0=dptr(slab), c1=dptr(slab), B=B, primes=npr, elt=3,
+                 out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    assert gal(elt=3) == SE_ERR_NO_KEY
     # a refused first install installs nothing
     bad0 = gk0.copy()
     bad0[0, 0, 0, 0] = o.q[0]
     with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
         ctx.set_galois_keys(elts, bad0, gk1)
     assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
-    assert gal(3) == SE_ERR_NO_KEY
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    assert gal(elt=3) == SE_ERR_NO_KEY
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     # the first two elements are installed: the third is not there
     ctx.set_galois_keys(elts[:2], gk0[:2], gk1[:2])
-    assert gal(elts[2]) == SE_ERR_NO_KEY and gal(5) == SE_ERR_NO_KEY
+    assert gal(elt=elts[2]) == SE_ERR_NO_KEY and gal(elt=5) == SE_ERR_NO_KEY
     rng = np.random.default_rng(n + npr)
     c0, c1 = rand_slab(rng, o.q, B, n), rand_slab(rng, o.q, B, n)
     d0, d1 = dev_t(env, c0), dev_t(env, c1)
@@ -143,7 +139,7 @@ def test_galois_key_generation(env, shape):
     def previous_set_works():
         g0, g1 = run_galois(env, ctx, d0, d1, elts[1], npr)
         assert (g0[:1] == want[0]).all() and (g1[:1] == want[1]).all()
-        assert gal(elts[2]) == SE_ERR_NO_KEY
+        assert gal(elt=elts[2]) == SE_ERR_NO_KEY
 
     previous_set_works()
     refused = []
@@ -161,7 +157,7 @@ def test_galois_key_generation(env, shape):
         previous_set_works()
     # a new install replaces the whole set
     ctx.set_galois_keys(elts[2:], gk0[2:], gk1[2:])
-    assert gal(elts[1]) == SE_ERR_NO_KEY and gal(elts[2]) == 0
+    assert gal(elt=elts[1]) == SE_ERR_NO_KEY and gal(elt=elts[2]) == 0
     torch.cuda.synchronize()
     assert int(torch.count_nonzero(out0)) == 0 and int(torch.count_nonzero(out1)) == 0    # zero slabs rotate to zero
     # the generator's own refusals
@@ -171,13 +167,14 @@ def test_galois_key_generation(env, shape):
         with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
             ctx.gen_galois_keys(args[0], args[1], sa, se)
         assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
-    f = ctx.L.se_amd_gen_galois_keys
     el = np.array(elts, dtype=np.uint32)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
+    gen = CEntry(ctx.L.se_amd_gen_galois_keys, ctx=ctx.h, sk=hptr(sk), elts=hptr(el), G=G, seeds_a=hptr(sa),
+                 seeds_e=hptr(se), gk0=hptr(gk0), gk1=hptr(gk1))
+    install = CEntry(ctx.L.se_amd_set_galois_keys, ctx=ctx.h, elts=hptr(el), G=G, gk0=hptr(gk0), gk1=hptr(gk1))
     for Gbad in (0, 65):
-        assert f(ctx.h, hp(sk), hp(el), Gbad, hp(sa), hp(se), hp(gk0), hp(gk1)) == SE_ERR_INVALD_ARGUMENT
-        assert ctx.L.se_amd_set_galois_keys(ctx.h, hp(el), Gbad, hp(gk0), hp(gk1)) == SE_ERR_INVALD_ARGUMENT
-    assert gal(elts[2]) == 0
+        gen.refused([dict(G=Gbad)])
+        install.refused([dict(G=Gbad)])
+    assert gal(elt=elts[2]) == 0
     ctx.close()
 
 
@@ -188,46 +185,38 @@ def test_galois_arguments(env):
     torch = env["torch"]
     n, npr, B = 4096, 3, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     key = np.zeros((1, 2 * npr, npr, n), dtype=np.uint32)
     ctx.set_galois_keys([3], key, key)
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1 = torch.zeros_like(c0)
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f = L.se_amd_ct_galois_device
-    bad_calls = [
-        (None, p(c0), p(c1), B, 3, 3, p(out0), p(out1), s),
-        (h, z, p(c1), B, 3, 3, p(out0), p(out1), s),                   # NULL mandatory pointers
-        (h, p(c0), z, B, 3, 3, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 3, 3, z, p(out1), s),
-        (h, p(c0), p(c1), B, 3, 3, p(out0), z, s),
-        (h, p(c0), p(c1), B, 0, 3, p(out0), p(out1), s),               # primes outside [1, np]
-        (h, p(c0), p(c1), B, 4, 3, p(out0), p(out1), s),
-        (h, p(c0), p(c1), 2 ** 32, 3, 3, p(out0), p(out1), s),         # B >= 2^32
-        (h, p(c0, 4), p(c1), B, 3, 3, p(out0), p(out1), s),            # alignment, each slab
-        (h, p(c0), p(c1, 8), B, 3, 3, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 3, 3, p(out0, 12), p(out1), s),
-        (h, p(c0), p(c1), B, 3, 3, p(out0), p(out1, 4), s),
-        (h, p(c0), p(c1), B, 3, 0, p(out0), p(out1), s),               # an even element, one >= 2n
-        (h, p(c0), p(c1), B, 3, 4, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 3, 2 * n, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 3, 2 * n + 3, p(out0), p(out1), s),
-    ]
-    for k, args in enumerate(bad_calls):
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert f(h, p(c0), p(c1), B, 3, 5, p(out0), p(out1), s) == SE_ERR_NO_KEY
-    assert f(h, p(c0), p(c1), 0, 3, 3, p(out0), p(out1), s) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
-    assert f(h, p(c0), p(c1), B, 2, 3, p(out0), p(out1), s) == 0
-    torch.cuda.synchronize()
+    f = CEntry(ctx.L.se_amd_ct_galois_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=3, elt=3,
+               out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    f.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                                 # NULL mandatory pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                                # primes outside [1, np]
+        dict(primes=4),
+        dict(B=2 ** 32),                                               # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                          # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(elt=0),                                                   # an even element, one >= 2n
+        dict(elt=4),
+        dict(elt=2 * n),
+        dict(elt=2 * n + 3),
+    ])
+    assert f(elt=5) == SE_ERR_NO_KEY
+    assert f(B=0) == 0
+    assert_untouched(out0, out1)
+    assert f(primes=2) == 0
     for o in (out0, out1):
-        flat = o.reshape(-1)
-        assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+        assert_zero_prefix(o, B * 2 * n)
     ctx.close()
 
 

@@ -8,18 +8,16 @@ automorphism by tests/test_ct_galois_build.py -- and Python / NumPy integers, ne
     rot1[g][b][i][k] =                      sum_r NTT_i(D_r)[src_g(k)] . gk1_g[r][i][k]   mod q_i.
 Every comparison is bit-exact except the reference's own acceptance criterion |values - expected| < 0.1
 (device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below Oracle(n, L)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ct_model import (CASE_IDS, DIGIT_MASK, GALOIS_CASES, SHAPE_IDS, call_elements, digit_key_errors, digits_of,
                       edge_row, galois_diagonal, hoist_expect, lift_expect, modular_sum, negacyclic, rand_slab,
                       random_keys)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_headroom, check_level_decrypt,  # noqa: F401
-                         dev_t, env, expectation, fresh_records, host_u32, install_galois_keys, keyed_cases,
-                         lift_records, rescale_records, run_example, run_many, run_sum, step_elements, stream_of,
-                         unit_values)
+from gpu_support import (NULL, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched, assert_zero_prefix,  # noqa: F401
+                         check_headroom, check_level_decrypt, dev_t, dptr, env, expectation, fresh_records, host_u32,
+                         hptr, install_galois_keys, keyed_cases, lift_records, rescale_records, run_example, run_many,
+                         run_sum, step_elements, stream_of, unit_values)
 from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
@@ -110,54 +108,44 @@ def test_hoist_arguments(env):
     torch, pkg = env["torch"], env["pkg"]
     n, npr, B = 4096, 3, 2
     ctx = pkg.Context(n, npr)
-    L, h = ctx.L, ctx.h
     key = np.zeros((2, 2 * npr, npr, n), dtype=np.uint32)
     ctx.set_galois_keys([3, 9], key, key)
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1 = torch.zeros_like(c0)
     out0 = torch.full((2, B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the G = 65 call
     good, even, big, nokey = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 5)
-
-    def many(ctx_h, a0, a1, Bv, primes, elts, G, o0, o1):
-        return L.se_amd_ct_galois_many_device(ctx_h, a0, a1, Bv, primes, elts, G, o0, o1, s)
-
-    def total(ctx_h, a0, a1, Bv, primes, elts, G, o0, o1):
-        return L.se_amd_ct_galois_sum_device(ctx_h, a0, a1, Bv, primes, elts, G, 1, o0, o1, s)
-
-    P0, P1, O0, O1, E = p(c0), p(c1), p(out0), p(out1), hp(good)
+    L = ctx.L
+    many = CEntry(L.se_amd_ct_galois_many_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=3, elts=hptr(good),
+                  G=2, out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    total = CEntry(L.se_amd_ct_galois_sum_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=3, elts=hptr(good),
+                   G=2, add_input=1, out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
     bad_calls = [
-        (None, P0, P1, B, 3, E, 2, O0, O1),
-        (h, z, P1, B, 3, E, 2, O0, O1),                       # NULL mandatory pointers
-        (h, P0, z, B, 3, E, 2, O0, O1),
-        (h, P0, P1, B, 3, E, 2, z, O1),
-        (h, P0, P1, B, 3, E, 2, O0, z),
-        (h, P0, P1, B, 3, z, 2, O0, O1),                      # NULL element list
-        (h, P0, P1, B, 0, E, 2, O0, O1),                      # primes outside [1, np]
-        (h, P0, P1, B, 4, E, 2, O0, O1),
-        (h, P0, P1, 2 ** 32, 3, E, 2, O0, O1),                # B >= 2^32
-        (h, p(c0, 4), P1, B, 3, E, 2, O0, O1),                # alignment, each slab
-        (h, P0, p(c1, 8), B, 3, E, 2, O0, O1),
-        (h, P0, P1, B, 3, E, 2, p(out0, 12), O1),
-        (h, P0, P1, B, 3, E, 2, O0, p(out1, 4)),
-        (h, P0, P1, B, 3, E, 0, O0, O1),                      # G = 0, G = 65
-        (h, P0, P1, B, 3, E, 65, O0, O1),
-        (h, P0, P1, B, 3, hp(even), 2, O0, O1),               # an even element, one >= 2n
-        (h, P0, P1, B, 3, hp(big), 2, O0, O1),
+        dict(ctx=None),
+        dict(c0=NULL),                                        # NULL mandatory pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(elts=NULL),                                      # NULL element list
+        dict(primes=0),                                       # primes outside [1, np]
+        dict(primes=4),
+        dict(B=2 ** 32),                                      # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                 # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(G=0),                                            # G = 0, G = 65
+        dict(G=65),
+        dict(elts=hptr(even)),                                # an even element, one >= 2n
+        dict(elts=hptr(big)),
     ]
     for f in (many, total):
-        for k, args in enumerate(bad_calls):
-            assert f(*args) == SE_ERR_INVALD_ARGUMENT, (f.__name__, k)
-        assert f(h, P0, P1, B, 3, hp(nokey), 2, O0, O1) == SE_ERR_NO_KEY, f.__name__
+        f.refused(bad_calls)
+        assert f(elts=hptr(nokey)) == SE_ERR_NO_KEY
         assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
-        assert f(h, P0, P1, 0, 3, E, 2, O0, O1) == 0, f.__name__
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+        assert f(B=0) == 0
+    assert_untouched(out0, out1)
     # a refused install leaves the previous set to the hoisted entries: zero keys and zero slabs give zero rows
     bad = key.copy()
     bad[1, 0, 0, 0] = ctx.moduli()[0]
@@ -166,19 +154,15 @@ def test_hoist_arguments(env):
     with pytest.raises(pkg.SealEmbeddedAmdError):
         ctx.set_galois_keys([3, 5, 3], np.zeros((3,) + key.shape[1:], dtype=np.uint32),
                             np.zeros((3,) + key.shape[1:], dtype=np.uint32))
-    assert many(h, P0, P1, B, 2, hp(nokey), 2, O0, O1) == SE_ERR_NO_KEY        # 5 was not installed
-    assert many(h, P0, P1, B, 2, E, 2, O0, O1) == 0                            # a level-2 call: 2 . B . 2 . n words
-    torch.cuda.synchronize()
+    assert many(primes=2, elts=hptr(nokey)) == SE_ERR_NO_KEY                   # 5 was not installed
+    assert many(primes=2) == 0                                                 # a level-2 call: 2 . B . 2 . n words
     for o in (out0, out1):
-        flat = o.reshape(-1)
-        assert int(torch.count_nonzero(flat[:2 * B * 2 * n])) == 0 and bool((flat[2 * B * 2 * n:] == SENTINEL).all())
+        assert_zero_prefix(o, 2 * B * 2 * n)
     out0.fill_(SENTINEL)
     out1.fill_(SENTINEL)
-    assert total(h, P0, P1, B, 3, E, 2, O0, O1) == 0
-    torch.cuda.synchronize()
+    assert total() == 0
     for o in (out0, out1):
-        flat = o.reshape(-1)
-        assert int(torch.count_nonzero(flat[:B * 3 * n])) == 0 and bool((flat[B * 3 * n:] == SENTINEL).all())
+        assert_zero_prefix(o, B * 3 * n)
     ctx.close()
 
 

@@ -5,8 +5,6 @@ expand_ternary) and Python / NumPy integers, never the code under test.  The aut
 coefficient-domain definition pushed through o.intt and o.ntt.  Every comparison is bit-exact except the reference's own
 acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -14,8 +12,9 @@ import vectors as V
 from ct_model import (CASE_IDS, SHAPE_IDS, SP_CASES, centred, edge_row, galois_seeds, galois_sp_expect, key_errors,
                       key_switch_sp, rand_key, rand_slab, relin_sp_expect, sigma_rows, sigma_slab, sp_diagonal,
                       src_table, switch_quotient)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
-                         env, expectation, fresh_records, install_galois_keys, keyed_cases, ntt_secret, rescale_records,
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_level_decrypt, dev_t, dptr, drop_records, env, expectation,
+                         fresh_records, hptr, install_galois_keys, keyed_cases, ntt_secret, rescale_records,
                          run_decrypt, run_example, run_galois, run_galois_sp, run_relin, run_relin_sp, sentinel_out,
                          step_elements, stream_of, take, unit_values)
 from vectors import sigma_coeff
@@ -180,16 +179,14 @@ def test_sp_key_generation(env, shape):
     B = 2
     slab = torch.zeros((B, L, n), dtype=torch.int32, device=env["dev"])
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    ptr = lambda x: C.c_void_p(x.data_ptr())
-    z = C.c_void_p(None)
-    assert ctx.L.se_amd_decrypt_level_device(ctx.h, ptr(slab), ptr(slab), B, L, ctx.scale(), z, z, z, ptr(st),
-                                             stream_of(env)) == SE_ERR_NO_KEY
+    assert ctx.L.se_amd_decrypt_level_device(ctx.h, dptr(slab), dptr(slab), B, L, ctx.scale(), NULL, NULL, NULL,
+                                             dptr(st), stream_of(env)) == SE_ERR_NO_KEY
     out0, out1 = torch.full_like(slab, SENTINEL), torch.full_like(slab, SENTINEL)
-    gal = lambda elt: ctx.L.se_amd_ct_galois_sp_device(ctx.h, ptr(slab), ptr(slab), B, L, elt, ptr(out0), ptr(out1),
-                                                       stream_of(env))
-    rel = lambda: ctx.L.se_amd_ct_relin_sp_device(ctx.h, ptr(slab), ptr(slab), ptr(slab), B, L, ptr(out0), ptr(out1),
-                                                  stream_of(env))
-    assert gal(3) == SE_ERR_NO_KEY and rel() == SE_ERR_NO_KEY
+    gal = CEntry(ctx.L.se_amd_ct_galois_sp_device, ctx=ctx.h, c0=dptr(slab), c1=dptr(slab), B=B, primes=L, elt=3,
+                 out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    rel = CEntry(ctx.L.se_amd_ct_relin_sp_device, ctx=ctx.h, d0=dptr(slab), d1=dptr(slab), d2=dptr(slab), B=B, primes=L,
+                 out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    assert gal(elt=3) == SE_ERR_NO_KEY and rel() == SE_ERR_NO_KEY
     # a refused first install installs nothing
     bad0 = gk0.copy()
     bad0[0, 0, 0, 0] = o.q[0]
@@ -201,13 +198,13 @@ def test_sp_key_generation(env, shape):
     with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
         ctx.set_relin_key_sp(evk0, bad1)
     assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
-    assert gal(3) == SE_ERR_NO_KEY and rel() == SE_ERR_NO_KEY
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    assert gal(elt=3) == SE_ERR_NO_KEY and rel() == SE_ERR_NO_KEY
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     # the first two elements are installed: the third is not there
     ctx.set_galois_keys_sp(elts[:2], gk0[:2], gk1[:2])
     ctx.set_relin_key_sp(evk0, evk1)
-    assert gal(elts[2]) == SE_ERR_NO_KEY and gal(5) == SE_ERR_NO_KEY
+    assert gal(elt=elts[2]) == SE_ERR_NO_KEY and gal(elt=5) == SE_ERR_NO_KEY
     rng = np.random.default_rng(n + npr)
     c0, c1, c2 = (rand_slab(rng, o.q, B, n, L) for _ in range(3))
     d0, d1, d2 = dev_t(env, c0), dev_t(env, c1), dev_t(env, c2)
@@ -219,7 +216,7 @@ def test_sp_key_generation(env, shape):
         assert (g0[:1] == want_g[0]).all() and (g1[:1] == want_g[1]).all()
         r0, r1 = run_relin_sp(env, ctx, d0, d1, d2, L)
         assert (r0[:1] == want_r[0]).all() and (r1[:1] == want_r[1]).all()
-        assert gal(elts[2]) == SE_ERR_NO_KEY
+        assert gal(elt=elts[2]) == SE_ERR_NO_KEY
         return g0, g1, r0, r1
 
     sp_before = previous_set_works()
@@ -252,7 +249,7 @@ def test_sp_key_generation(env, shape):
     assert all((a == b).all() for x, y in zip(digit_before, digit_now) for a, b in zip(x, y))
     # a new install replaces the whole set
     ctx.set_galois_keys_sp(elts[2:], gk0[2:], gk1[2:])
-    assert gal(elts[1]) == SE_ERR_NO_KEY and gal(elts[2]) == 0
+    assert gal(elt=elts[1]) == SE_ERR_NO_KEY and gal(elt=elts[2]) == 0
     torch.cuda.synchronize()
     assert int(torch.count_nonzero(out0)) == 0 and int(torch.count_nonzero(out1)) == 0    # zero slabs rotate to zero
     # the generators' own refusals
@@ -266,14 +263,16 @@ def test_sp_key_generation(env, shape):
         ctx.gen_relin_key_sp(bad_sk, ra, re_)
     assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
     el = np.array(elts, dtype=np.uint32)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
+    gen = CEntry(ctx.L.se_amd_gen_galois_keys_sp, ctx=ctx.h, sk=hptr(sk), elts=hptr(el), G=G, seeds_a=hptr(sa),
+                 seeds_e=hptr(se), gk0=hptr(gk0), gk1=hptr(gk1))
+    install = CEntry(ctx.L.se_amd_set_galois_keys_sp, ctx=ctx.h, elts=hptr(el), G=G, gk0=hptr(gk0), gk1=hptr(gk1))
     for Gbad in (0, 65):
-        assert ctx.L.se_amd_gen_galois_keys_sp(ctx.h, hp(sk), hp(el), Gbad, hp(sa), hp(se), hp(gk0),
-                                               hp(gk1)) == SE_ERR_INVALD_ARGUMENT
-        assert ctx.L.se_amd_set_galois_keys_sp(ctx.h, hp(el), Gbad, hp(gk0), hp(gk1)) == SE_ERR_INVALD_ARGUMENT
-    assert ctx.L.se_amd_set_relin_key_sp(ctx.h, z, hp(evk1)) == SE_ERR_INVALD_ARGUMENT
-    assert ctx.L.se_amd_gen_relin_key_sp(ctx.h, hp(sk), z, hp(re_), hp(evk0), hp(evk1)) == SE_ERR_INVALD_ARGUMENT
-    assert gal(elts[2]) == 0
+        gen.refused([dict(G=Gbad)])
+        install.refused([dict(G=Gbad)])
+    assert ctx.L.se_amd_set_relin_key_sp(ctx.h, NULL, hptr(evk1)) == SE_ERR_INVALD_ARGUMENT
+    assert ctx.L.se_amd_gen_relin_key_sp(ctx.h, hptr(sk), NULL, hptr(re_), hptr(evk0),
+                                         hptr(evk1)) == SE_ERR_INVALD_ARGUMENT
+    assert gal(elt=elts[2]) == 0
     ctx.close()
 
 
@@ -286,93 +285,84 @@ def test_sp_arguments(env):
     torch = env["torch"]
     n, npr, B = 4096, 3, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1, c2 = torch.zeros_like(c0), torch.zeros_like(c0)
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    fg, fr = L.se_amd_ct_galois_sp_device, L.se_amd_ct_relin_sp_device
+    L, s = ctx.L, stream_of(env)
+    fg = CEntry(L.se_amd_ct_galois_sp_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=2, elt=3, out0=dptr(out0),
+                out1=dptr(out1), stream=s)
+    fr = CEntry(L.se_amd_ct_relin_sp_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), c2=dptr(c2), B=B, primes=2,
+                out0=dptr(out0), out1=dptr(out1), stream=s)
     # only digit keys installed: they do not serve these entries
     dkey = np.zeros((1, 2 * npr, npr, n), dtype=np.uint32)
     ctx.set_galois_keys([3], dkey, dkey)
     ctx.set_relin_key(dkey[0], dkey[0])
-    assert fg(h, p(c0), p(c1), B, 2, 3, p(out0), p(out1), s) == SE_ERR_NO_KEY
-    assert fr(h, p(c0), p(c1), p(c2), B, 2, p(out0), p(out1), s) == SE_ERR_NO_KEY
+    assert fg() == SE_ERR_NO_KEY
+    assert fr() == SE_ERR_NO_KEY
     key = np.zeros((1, npr - 1, npr, n), dtype=np.uint32)
     ctx.set_galois_keys_sp([3], key, key)
     ctx.set_relin_key_sp(key[0], key[0])
-    bad_galois = [
-        (None, p(c0), p(c1), B, 2, 3, p(out0), p(out1), s),
-        (h, z, p(c1), B, 2, 3, p(out0), p(out1), s),                   # NULL mandatory pointers
-        (h, p(c0), z, B, 2, 3, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 2, 3, z, p(out1), s),
-        (h, p(c0), p(c1), B, 2, 3, p(out0), z, s),
-        (h, p(c0), p(c1), B, 0, 3, p(out0), p(out1), s),               # primes outside [1, np - 1]
-        (h, p(c0), p(c1), B, 3, 3, p(out0), p(out1), s),               # primes = np: the special prime is not data
-        (h, p(c0), p(c1), B, 4, 3, p(out0), p(out1), s),
-        (h, p(c0), p(c1), 2 ** 32, 2, 3, p(out0), p(out1), s),         # B >= 2^32
-        (h, p(c0, 4), p(c1), B, 2, 3, p(out0), p(out1), s),            # alignment, each slab
-        (h, p(c0), p(c1, 8), B, 2, 3, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 2, 3, p(out0, 12), p(out1), s),
-        (h, p(c0), p(c1), B, 2, 3, p(out0), p(out1, 4), s),
-        (h, p(c0), p(c1), B, 2, 0, p(out0), p(out1), s),               # an even element, one >= 2n
-        (h, p(c0), p(c1), B, 2, 4, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 2, 2 * n, p(out0), p(out1), s),
-        (h, p(c0), p(c1), B, 2, 2 * n + 3, p(out0), p(out1), s),
-    ]
-    for k, args in enumerate(bad_galois):
-        assert fg(*args) == SE_ERR_INVALD_ARGUMENT, k
-    bad_relin = [
-        (None, p(c0), p(c1), p(c2), B, 2, p(out0), p(out1), s),
-        (h, z, p(c1), p(c2), B, 2, p(out0), p(out1), s),
-        (h, p(c0), z, p(c2), B, 2, p(out0), p(out1), s),
-        (h, p(c0), p(c1), z, B, 2, p(out0), p(out1), s),
-        (h, p(c0), p(c1), p(c2), B, 2, z, p(out1), s),
-        (h, p(c0), p(c1), p(c2), B, 2, p(out0), z, s),
-        (h, p(c0), p(c1), p(c2), B, 0, p(out0), p(out1), s),
-        (h, p(c0), p(c1), p(c2), B, 3, p(out0), p(out1), s),           # primes = np
-        (h, p(c0), p(c1), p(c2), 2 ** 32, 2, p(out0), p(out1), s),
-        (h, p(c0, 4), p(c1), p(c2), B, 2, p(out0), p(out1), s),
-        (h, p(c0), p(c1, 8), p(c2), B, 2, p(out0), p(out1), s),
-        (h, p(c0), p(c1), p(c2, 4), B, 2, p(out0), p(out1), s),
-        (h, p(c0), p(c1), p(c2), B, 2, p(out0, 12), p(out1), s),
-        (h, p(c0), p(c1), p(c2), B, 2, p(out0), p(out1, 4), s),
-    ]
-    for k, args in enumerate(bad_relin):
-        assert fr(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert fg(h, p(c0), p(c1), B, 2, 5, p(out0), p(out1), s) == SE_ERR_NO_KEY
-    assert fg(h, p(c0), p(c1), 0, 2, 3, p(out0), p(out1), s) == 0
-    assert fr(h, p(c0), p(c1), p(c2), 0, 2, p(out0), p(out1), s) == 0
+    fg.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                                 # NULL mandatory pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                                # primes outside [1, np - 1]
+        dict(primes=3),                                                # primes = np: the special prime is not data
+        dict(primes=4),
+        dict(B=2 ** 32),                                               # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                          # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(elt=0),                                                   # an even element, one >= 2n
+        dict(elt=4),
+        dict(elt=2 * n),
+        dict(elt=2 * n + 3),
+    ])
+    fr.refused([
+        dict(ctx=None),
+        dict(c0=NULL),
+        dict(c1=NULL),
+        dict(c2=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),
+        dict(primes=3),                                                # primes = np
+        dict(B=2 ** 32),
+        dict(c0=dptr(c0, 4)),
+        dict(c1=dptr(c1, 8)),
+        dict(c2=dptr(c2, 4)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+    ])
+    assert fg(elt=5) == SE_ERR_NO_KEY
+    assert fg(B=0) == 0
+    assert fr(B=0) == 0
     # a context of one prime has no prime to reserve
     one = env["pkg"].Context(1024, 1)
     k1 = np.zeros((1, 1, 1, 1024), dtype=np.uint32)
     sd = np.zeros((1, 64), dtype=np.uint8)
     sk = V.secret_key(1024, seed=3)
     el = np.array([3], dtype=np.uint32)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    oh, oL = one.h, one.L
-    assert oL.se_amd_ct_galois_sp_device(oh, p(c0), p(c1), B, 1, 3, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_ct_relin_sp_device(oh, p(c0), p(c1), p(c2), B, 1, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_set_relin_key_sp(oh, hp(k1), hp(k1)) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_set_galois_keys_sp(oh, hp(el), 1, hp(k1), hp(k1)) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_gen_relin_key_sp(oh, hp(sk), hp(sd), hp(sd), hp(k1), hp(k1)) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_gen_galois_keys_sp(oh, hp(sk), hp(el), 1, hp(sd), hp(sd), hp(k1), hp(k1)) == SE_ERR_INVALD_ARGUMENT
+    fg.refused([dict(ctx=one.h, primes=1)])
+    fr.refused([dict(ctx=one.h, primes=1)])
+    assert L.se_amd_set_relin_key_sp(one.h, hptr(k1), hptr(k1)) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_set_galois_keys_sp(one.h, hptr(el), 1, hptr(k1), hptr(k1)) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_gen_relin_key_sp(one.h, hptr(sk), hptr(sd), hptr(sd), hptr(k1), hptr(k1)) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_gen_galois_keys_sp(one.h, hptr(sk), hptr(el), 1, hptr(sd), hptr(sd), hptr(k1),
+                                       hptr(k1)) == SE_ERR_INVALD_ARGUMENT
     assert not k1.any()
     one.close()
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
-    for call in (lambda: fg(h, p(c0), p(c1), B, 1, 3, p(out0), p(out1), s),
-                 lambda: fr(h, p(c0), p(c1), p(c2), B, 1, p(out0), p(out1), s)):
+    assert_untouched(out0, out1)
+    for f in (fg, fr):
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
-        assert call() == 0
-        torch.cuda.synchronize()
+        assert f(primes=1) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:B * n])) == 0 and bool((flat[B * n:] == SENTINEL).all())
+            assert_zero_prefix(o, B * n)
     ctx.close()
 
 
@@ -399,33 +389,28 @@ def test_drop_primes(env):
             ctx.ct_drop_primes(db, o0, primes_in=pin, primes_out=pout)          # one slab
             torch.cuda.synchronize()
             assert (take(o0, words, (B, pout, n), "drop one slab") == b[:, :pout]).all(), (pin, pout)
-    f, h = ctx.L.se_amd_ct_drop_primes_device, ctx.h
     da, db = dev_t(env, full[0]), dev_t(env, full[1])
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    bad = [
-        (None, p(da), p(db), B, 3, 2, p(out0), p(out1), s),
-        (h, z, p(db), B, 3, 2, p(out0), p(out1), s),
-        (h, p(da), p(db), B, 3, 2, z, p(out1), s),
-        (h, p(da), p(db), B, 3, 2, p(out0), z, s),                     # one of in1 / out1 alone
-        (h, p(da), z, B, 3, 2, p(out0), p(out1), s),
-        (h, p(da), p(db), B, 3, 0, p(out0), p(out1), s),               # 1 <= primes_out <= primes_in <= np
-        (h, p(da), p(db), B, 2, 3, p(out0), p(out1), s),
-        (h, p(da), p(db), B, 4, 2, p(out0), p(out1), s),
-        (h, p(da), p(db), 2 ** 32, 3, 2, p(out0), p(out1), s),
-        (h, p(da, 4), p(db), B, 3, 2, p(out0), p(out1), s),            # alignment
-        (h, p(da), p(db, 8), B, 3, 2, p(out0), p(out1), s),
-        (h, p(da), p(db), B, 3, 2, p(out0, 4), p(out1), s),
-        (h, p(da), p(db), B, 3, 2, p(out0), p(out1, 12), s),
-    ]
-    for k, args in enumerate(bad):
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert f(h, p(da), p(db), 0, 3, 2, p(out0), p(out1), s) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    f = CEntry(ctx.L.se_amd_ct_drop_primes_device, ctx=ctx.h, in0=dptr(da), in1=dptr(db), B=B, primes_in=3, primes_out=2,
+               out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    f.refused([
+        dict(ctx=None),
+        dict(in0=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),                                               # one of in1 / out1 alone
+        dict(in1=NULL),
+        dict(primes_out=0),                                            # 1 <= primes_out <= primes_in <= np
+        dict(primes_in=2, primes_out=3),
+        dict(primes_in=4),
+        dict(B=2 ** 32),
+        dict(in0=dptr(da, 4)),                                         # alignment
+        dict(in1=dptr(db, 8)),
+        dict(out0=dptr(out0, 4)),
+        dict(out1=dptr(out1, 12)),
+    ])
+    assert f(B=0) == 0
+    assert_untouched(out0, out1)
     ctx.close()
 
 

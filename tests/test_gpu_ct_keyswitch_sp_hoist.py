@@ -4,8 +4,6 @@ Every expectation is the definition in tests/ct_model.py (hoist_sp_expect and, f
 the oracle's primitives and Python / NumPy integers, never the code under test.  Every comparison is bit-exact except
 the reference's own acceptance criterion |values - expected| < 0.1.
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -13,10 +11,11 @@ import vectors as V
 from ct_model import (CASE_IDS, SHAPE_IDS, SP_CASES, add_mod, centred, edge_diagonals, edge_row, hoist_sp_expect,
                       key_errors, key_switch_sp, matrix, matrix_diagonals, negacyclic, rand_key, rand_slab, sigma_rows,
                       sum_of_single_calls)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
-                         encode_diagonals, env, expectation, fresh_records, guarded_pair, install_galois_keys,
-                         keyed_cases, periodic_values, rescale_records, run_example, run_galois_sp, step_elements,
-                         stream_of, unit_values)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_level_decrypt, create_handle, creates_refused, dev_t, dptr,
+                         drop_records, encode_diagonals, env, expectation, fresh_records, guarded_pair, hptr,
+                         install_galois_keys, keyed_cases, periodic_values, rescale_records, run_example, run_galois_sp,
+                         step_elements, stream_of, unit_values)
 from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
@@ -388,52 +387,42 @@ def test_sp_hoist_installs_and_kinds(env):
     out1 = torch.full_like(out0, SENTINEL)
     diag = torch.ones((2, npr, n), dtype=torch.int32, device=env["dev"])
     diag0 = torch.ones((npr, n), dtype=torch.int32, device=env["dev"])
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
     s = stream_of(env)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     good, nokey = np.array([3, 9], dtype=np.uint32), np.array([3, 5], dtype=np.uint32)
-
-    def create(f, ctx_h, elts, G, d, d0, pt):
-        handle = C.c_void_p(0xDEAD)                         # a failed create must overwrite it with NULL
-        return f(ctx_h, hp(elts), G, d, d0, pt, C.byref(handle)), handle
-
-    fs = L.se_amd_ct_galois_sum_sp_device
+    mk = dict(ctx=h, elts=hptr(good), G=2, diag=dptr(diag), diag0=dptr(diag0), pt_primes=npr, out=None)
+    mk_digit, mk_sp = CEntry(L.se_amd_lintrans_create, **mk), CEntry(L.se_amd_lintrans_create_sp, **mk)
+    fs = CEntry(L.se_amd_ct_galois_sum_sp_device, ctx=h, c0=dptr(c0), c1=dptr(c1), B=B, primes=2, elts=hptr(good), G=2,
+                add_input=1, out0=dptr(out0), out1=dptr(out1), stream=s)
     dkey = np.zeros((2, 2 * npr, npr, n), dtype=np.uint32)
     ctx.set_galois_keys([3, 9], dkey, dkey)
-    assert fs(h, p(c0), p(c1), B, 2, hp(good), 2, 1, p(out0), p(out1), s) == SE_ERR_NO_KEY
-    rc, handle = create(L.se_amd_lintrans_create_sp, h, good, 2, p(diag), p(diag0), npr)
-    assert rc == SE_ERR_NO_KEY and handle.value is None
+    assert fs() == SE_ERR_NO_KEY
+    creates_refused(mk_sp, [{}], SE_ERR_NO_KEY)
     key = np.zeros((2, npr - 1, npr, n), dtype=np.uint32)
     ctx.set_galois_keys_sp([3, 9], key, key)
     other.set_galois_keys_sp([3, 9], key, key)
-    assert fs(h, p(c0), p(c1), B, 2, hp(nokey), 2, 1, p(out0), p(out1), s) == SE_ERR_NO_KEY
+    assert fs(elts=hptr(nokey)) == SE_ERR_NO_KEY
     assert "special-prime" in L.se_amd_last_error().decode() and "element 5" in L.se_amd_last_error().decode()
-    rc, handle = create(L.se_amd_lintrans_create_sp, h, nokey, 2, p(diag), p(diag0), npr)
-    assert rc == SE_ERR_NO_KEY and handle.value is None
+    creates_refused(mk_sp, [dict(elts=hptr(nokey))], SE_ERR_NO_KEY)
     assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
-    rc, digit = create(L.se_amd_lintrans_create, h, good, 2, p(diag), p(diag0), npr)
+    rc, digit = create_handle(mk_digit)
     assert rc == 0 and digit.value
-    rc, sp = create(L.se_amd_lintrans_create_sp, h, good, 2, p(diag), p(diag0), npr)
+    rc, sp = create_handle(mk_sp)
     assert rc == 0 and sp.value
-    rc, foreign = create(L.se_amd_lintrans_create_sp, other.h, good, 2, p(diag), p(diag0), npr)
+    rc, foreign = create_handle(mk_sp, ctx=other.h)
     assert rc == 0 and foreign.value
-    fd, fp = L.se_amd_ct_lintrans_device, L.se_amd_ct_lintrans_sp_device
-    assert fp(h, digit, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
-    assert fd(h, sp, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
-    assert fp(h, foreign, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
-    assert fp(other.h, sp, p(c0), p(c1), B, 2, p(out0), p(out1), s) == SE_ERR_INVALD_ARGUMENT
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    run = dict(ctx=h, plan=None, c0=dptr(c0), c1=dptr(c1), B=B, primes=2, out0=dptr(out0), out1=dptr(out1), stream=s)
+    fd, fp = CEntry(L.se_amd_ct_lintrans_device, **run), CEntry(L.se_amd_ct_lintrans_sp_device, **run)
+    fp.refused([dict(plan=digit)])
+    fd.refused([dict(plan=sp)])
+    fp.refused([dict(plan=foreign), dict(ctx=other.h, plan=sp)])
+    assert_untouched(out0, out1)
     # each plan serves the entry of its kind: zero keys and zero slabs give zero rows
     for f, pl in ((fd, digit), (fp, sp)):
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
-        assert f(h, pl, p(c0), p(c1), B, 2, p(out0), p(out1), s) == 0
-        torch.cuda.synchronize()
+        assert f(plan=pl) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+            assert_zero_prefix(o, B * 2 * n)
     L.se_amd_lintrans_destroy(None)
     for pl in (digit, sp, foreign):
         L.se_amd_lintrans_destroy(pl)
@@ -457,98 +446,83 @@ def test_sp_hoist_arguments(env):
     out1 = torch.full_like(out0, SENTINEL)
     diag = torch.ones((2, npr, n), dtype=torch.int32, device=env["dev"])
     diag0 = torch.ones((npr, n), dtype=torch.int32, device=env["dev"])
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
     s = stream_of(env)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the G = 65 call
     good, even, big = el(3, 9), el(3, 4), el(3, 2 * n + 1)
-    P0, P1, O0, O1, E, D, D0 = p(c0), p(c1), p(out0), p(out1), hp(good), p(diag), p(diag0)
-    fs, fc, fp = L.se_amd_ct_galois_sum_sp_device, L.se_amd_lintrans_create_sp, L.se_amd_ct_lintrans_sp_device
-    bad_sums = [
-        (None, P0, P1, B, 2, E, 2, 1, O0, O1, s),
-        (h, z, P1, B, 2, E, 2, 1, O0, O1, s),                        # NULL mandatory pointers
-        (h, P0, z, B, 2, E, 2, 1, O0, O1, s),
-        (h, P0, P1, B, 2, E, 2, 1, z, O1, s),
-        (h, P0, P1, B, 2, E, 2, 1, O0, z, s),
-        (h, P0, P1, B, 0, E, 2, 1, O0, O1, s),                       # primes outside [1, np - 1]
-        (h, P0, P1, B, npr, E, 2, 1, O0, O1, s),                     # primes = np: the special prime is not data
-        (h, P0, P1, B, npr + 1, E, 2, 1, O0, O1, s),
-        (h, P0, P1, 2 ** 32, 2, E, 2, 1, O0, O1, s),                 # B >= 2^32
-        (h, p(c0, 4), P1, B, 2, E, 2, 1, O0, O1, s),                 # alignment, each slab
-        (h, P0, p(c1, 8), B, 2, E, 2, 1, O0, O1, s),
-        (h, P0, P1, B, 2, E, 2, 1, p(out0, 12), O1, s),
-        (h, P0, P1, B, 2, E, 2, 1, O0, p(out1, 4), s),
-        (h, P0, P1, B, 2, z, 2, 1, O0, O1, s),                       # elts NULL, G = 0, G = 65
-        (h, P0, P1, B, 2, E, 0, 1, O0, O1, s),
-        (h, P0, P1, B, 2, E, 65, 1, O0, O1, s),
-        (h, P0, P1, B, 2, hp(even), 2, 1, O0, O1, s),                # an even element, one >= 2n
-        (h, P0, P1, B, 2, hp(big), 2, 1, O0, O1, s),
-    ]
-    for k, args in enumerate(bad_sums):
-        assert fs(*args) == SE_ERR_INVALD_ARGUMENT, k
-
-    def create(ctx_h, elts, G, d, d0, pt, want_out=True, f=fc):
-        handle = C.c_void_p(0xDEAD)
-        return f(ctx_h, elts, G, d, d0, pt, C.byref(handle) if want_out else None), handle
-
-    bad_creates = [
-        (None, E, 2, D, D0, npr),
-        (h, z, 2, D, D0, npr),                               # NULL elts, d_diag
-        (h, E, 2, z, D0, npr),
-        (h, E, 0, D, D0, npr),                               # G = 0, G = 65
-        (h, E, 65, D, D0, npr),
-        (h, E, 2, D, D0, 0),                                 # pt_primes must be np
-        (h, E, 2, D, D0, npr - 1),
-        (h, E, 2, D, D0, npr + 1),
-        (h, hp(even), 2, D, D0, npr),                        # an even element, one >= 2n
-        (h, hp(big), 2, D, D0, npr),
-        (h, E, 2, p(diag, 4), D0, npr),                      # alignment of either diagonal pointer
-        (h, E, 2, D, p(diag0, 8), npr),
-    ]
-    for k, args in enumerate(bad_creates):
-        rc, handle = create(*args)
-        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, (k, rc, handle.value)
-    assert create(h, E, 2, D, D0, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT       # NULL out
-    rc, plan = create(h, E, 2, D, D0, npr)
+    fs = CEntry(L.se_amd_ct_galois_sum_sp_device, ctx=h, c0=dptr(c0), c1=dptr(c1), B=B, primes=2, elts=hptr(good), G=2,
+                add_input=1, out0=dptr(out0), out1=dptr(out1), stream=s)
+    fs.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                               # NULL mandatory pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                              # primes outside [1, np - 1]
+        dict(primes=npr),                                            # primes = np: the special prime is not data
+        dict(primes=npr + 1),
+        dict(B=2 ** 32),                                             # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                        # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(elts=NULL),                                             # elts NULL, G = 0, G = 65
+        dict(G=0),
+        dict(G=65),
+        dict(elts=hptr(even)),                                       # an even element, one >= 2n
+        dict(elts=hptr(big)),
+    ])
+    fc = CEntry(L.se_amd_lintrans_create_sp, ctx=h, elts=hptr(good), G=2, diag=dptr(diag), diag0=dptr(diag0),
+                pt_primes=npr, out=None)
+    creates_refused(fc, [
+        dict(ctx=None),
+        dict(elts=NULL),                                     # NULL elts, d_diag
+        dict(diag=NULL),
+        dict(G=0),                                           # G = 0, G = 65
+        dict(G=65),
+        dict(pt_primes=0),                                   # pt_primes must be np
+        dict(pt_primes=npr - 1),
+        dict(pt_primes=npr + 1),
+        dict(elts=hptr(even)),                               # an even element, one >= 2n
+        dict(elts=hptr(big)),
+        dict(diag=dptr(diag, 4)),                            # alignment of either diagonal pointer
+        dict(diag0=dptr(diag0, 8)),
+    ])
+    assert create_handle(fc, out=None)[0] == SE_ERR_INVALD_ARGUMENT                       # NULL out
+    rc, plan = create_handle(fc)
     assert rc == 0 and plan.value
-    bad_calls = [
-        (None, plan, P0, P1, B, 2, O0, O1, s),
-        (h, plan, z, P1, B, 2, O0, O1, s),                   # NULL slab pointers
-        (h, plan, P0, z, B, 2, O0, O1, s),
-        (h, plan, P0, P1, B, 2, z, O1, s),
-        (h, plan, P0, P1, B, 2, O0, z, s),
-        (h, plan, P0, P1, B, 0, O0, O1, s),                  # primes outside [1, np - 1]
-        (h, plan, P0, P1, B, npr, O0, O1, s),
-        (h, plan, P0, P1, B, npr + 1, O0, O1, s),
-        (h, plan, P0, P1, 2 ** 32, 2, O0, O1, s),            # B >= 2^32
-        (h, plan, p(c0, 4), P1, B, 2, O0, O1, s),            # alignment, each slab
-        (h, plan, P0, p(c1, 8), B, 2, O0, O1, s),
-        (h, plan, P0, P1, B, 2, p(out0, 12), O1, s),
-        (h, plan, P0, P1, B, 2, O0, p(out1, 4), s),
-        (h, z, P0, P1, B, 2, O0, O1, s),                     # no plan
-    ]
-    for k, args in enumerate(bad_calls):
-        assert fp(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert fs(h, P0, P1, 0, 2, E, 2, 1, O0, O1, s) == 0
-    assert fp(h, plan, P0, P1, 0, 2, O0, O1, s) == 0
+    fp = CEntry(L.se_amd_ct_lintrans_sp_device, ctx=h, plan=plan, c0=dptr(c0), c1=dptr(c1), B=B, primes=2,
+                out0=dptr(out0), out1=dptr(out1), stream=s)
+    fp.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                       # NULL slab pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                      # primes outside [1, np - 1]
+        dict(primes=npr),
+        dict(primes=npr + 1),
+        dict(B=2 ** 32),                                     # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(plan=NULL),                                     # no plan
+    ])
+    assert fs(B=0) == 0
+    assert fp(B=0) == 0
     # a context of one prime has no prime to reserve
     one = pkg.Context(1024, 1)
-    assert one.L.se_amd_ct_galois_sum_sp_device(one.h, P0, P1, B, 1, E, 2, 1, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
-    rc, handle = create(one.h, E, 2, D, D0, 1, f=one.L.se_amd_lintrans_create_sp)
-    assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None
-    assert one.L.se_amd_ct_lintrans_sp_device(one.h, plan, P0, P1, B, 1, O0, O1, s) == SE_ERR_INVALD_ARGUMENT
+    fs.refused([dict(ctx=one.h, primes=1)])
+    creates_refused(fc, [dict(ctx=one.h, pt_primes=1)])
+    fp.refused([dict(ctx=one.h, primes=1)])
     one.close()
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
-    for call in (lambda: fs(h, P0, P1, B, 1, E, 2, 1, O0, O1, s), lambda: fp(h, plan, P0, P1, B, 1, O0, O1, s)):
+    assert_untouched(out0, out1)
+    for f in (fs, fp):
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
-        assert call() == 0
-        torch.cuda.synchronize()
+        assert f(primes=1) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:B * n])) == 0 and bool((flat[B * n:] == SENTINEL).all())
+            assert_zero_prefix(o, B * n)
     L.se_amd_lintrans_destroy(plan)
     ctx.close()
 

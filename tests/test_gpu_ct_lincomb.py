@@ -1,18 +1,16 @@
 """Weighted sums of ciphertexts (-m gpu): se_amd_ct_lincomb_device, the key-free aggregation entry.
 Every expectation is built from NumPy integers (exact: every intermediate stays below 2^64), Python integers and the
 oracle, never from the code under test; every comparison is bit-exact."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import vectors as V
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, bits, decode_expect, dev_t, encrypt_sym, env, expectation,  # noqa: F401
-                         host_u32, ntt_secret, run_decrypt, stream_of)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SENTINEL, CEntry, assert_untouched, bits,  # noqa: F401
+                         decode_expect, dev_t, dptr, encrypt_sym, env, expectation, host_u32, ntt_secret, run_decrypt,
+                         stream_of)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
 SPLITS = (0, 1, 2, 7, 64)      # 0 = the automatic choice; 64 is more slices than most rows have entries
 B_CONSTRUCTED = 40
@@ -238,9 +236,8 @@ def test_empty_batch_rows(env):
     st = torch.full((2,), 77, dtype=torch.uint8, device=env["dev"])
     ptr, idx = dev_t(env, np.array([0, 0, 2], dtype=np.uint32)), dev_t(env, np.array([0, 1], dtype=np.uint32))
     stream = stream_of(env)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = ctx.L.se_amd_ct_lincomb_device(ctx.h, p(anchor), None, 0, 2, p(ptr), p(idx), None, 2, p(out0), None, p(st),
-                                        stream)
+    rc = ctx.L.se_amd_ct_lincomb_device(ctx.h, dptr(anchor), None, 0, 2, dptr(ptr), dptr(idx), None, 2, dptr(out0), None,
+                                        dptr(st), stream)
     torch.cuda.synchronize()
     assert rc == 0
     assert list(st.cpu().numpy()) == [1, 2]
@@ -254,7 +251,6 @@ def test_argument_errors(env, constructed):
     torch = env["torch"]
     c = constructed((4096, 3))
     ctx = c["ctx"]
-    L, h = ctx.L, ctx.h
     n, npr, B, G = 4096, 3, B_CONSTRUCTED, 2
     in0, in1 = c["dev"]
     out0 = torch.full((G, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
@@ -264,38 +260,34 @@ def test_argument_errors(env, constructed):
     idx = dev_t(env, np.array([0, 1, 2, 3], dtype=np.uint32))
     w = dev_t(env, np.array([1, 2, 3, 4], dtype=np.int32))
     wd = dev_t(env, np.ones(G * B, dtype=np.int32))
-    stream = stream_of(env)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    f = L.se_amd_ct_lincomb_device
+    f = CEntry(ctx.L.se_amd_ct_lincomb_device, ctx=ctx.h, in0=dptr(in0), in1=dptr(in1), B=B, G=G, row_ptr=dptr(ptr),
+               idx=dptr(idx), w=dptr(w), nnz=4, out0=dptr(out0), out1=dptr(out1), status=dptr(st), stream=stream_of(env))
     big = 2 ** 32
-    bad_calls = [
-        (None, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),
-        (h, z, p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),          # NULL d_in0
-        (h, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), 4, z, p(out1), p(st), stream),           # NULL d_out0
-        (h, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0), z, p(st), stream),           # in1 without out1
-        (h, p(in0), z, B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),          # out1 without in1
-        (h, p(in0), p(in1), B, G, p(ptr), z, p(w), 4, p(out0), p(out1), p(st), stream),          # row_ptr without idx
-        (h, p(in0), p(in1), B, G, z, p(idx), p(w), 4, p(out0), p(out1), p(st), stream),          # idx without row_ptr
-        (h, p(in0), p(in1), B, G, z, z, p(wd), G * B - 1, p(out0), p(out1), p(st), stream),      # dense, nnz != G B
-        (h, p(in0), p(in1), big, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),   # B >= 2^32
-        (h, p(in0), p(in1), B, big, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),   # G >= 2^32
-        (h, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), big, p(out0), p(out1), p(st), stream),   # nnz >= 2^32
-        (h, p(in0, 4), p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),  # alignment, each slab
-        (h, p(in0), p(in1, 8), B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream),
-        (h, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0, 4), p(out1), p(st), stream),
-        (h, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1, 12), p(st), stream),
-    ]
-    for k, args in enumerate(bad_calls):
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
-    assert f(h, p(in0), p(in1), B, 0, p(ptr), p(idx), p(w), 4, p(out0), p(out1), p(st), stream) == 0
-    assert f(h, p(in0), p(in1), B, 0, z, z, z, 0, p(out0), p(out1), z, stream) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    f.refused([
+        dict(ctx=None),
+        dict(in0=NULL),                                                    # NULL d_in0
+        dict(out0=NULL),                                                   # NULL d_out0
+        dict(out1=NULL),                                                   # in1 without out1
+        dict(in1=NULL),                                                    # out1 without in1
+        dict(idx=NULL),                                                    # row_ptr without idx
+        dict(row_ptr=NULL),                                                # idx without row_ptr
+        dict(row_ptr=NULL, idx=NULL, w=dptr(wd), nnz=G * B - 1),           # dense, nnz != G B
+        dict(B=big),                                                       # B >= 2^32
+        dict(G=big),                                                       # G >= 2^32
+        dict(nnz=big),                                                     # nnz >= 2^32
+        dict(in0=dptr(in0, 4)),                                            # alignment, each slab
+        dict(in1=dptr(in1, 8)),
+        dict(out0=dptr(out0, 4)),
+        dict(out1=dptr(out1, 12)),
+    ])
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
+    assert f(G=0) == 0
+    assert f(G=0, row_ptr=NULL, idx=NULL, w=NULL, nnz=0, status=NULL) == 0
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     # and the valid call works without a key (status optional)
-    assert f(h, p(in0), p(in1), B, G, p(ptr), p(idx), p(w), 4, p(out0), p(out1), z, stream) == 0
+    assert f(status=NULL) == 0
     torch.cuda.synchronize()
     rows = [([0, 1], [1, 2]), ([2, 3], [3, 4])]
     assert (host_u32(out0) == lincomb_expect(c["slabs"][0], c["q"], rows)).all()

@@ -11,17 +11,16 @@ code under test:
 with the keys installed when the plan was created, any 32-bit word of a diagonal standing for its residue.
 Every comparison is bit-exact except the reference's own acceptance criterion |values - expected| < 0.1
 (device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below Oracle(n, L)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ct_model import (CASE_IDS, GALOIS_CASES, SHAPE_IDS, call_elements, edge_row, hoist_expect, lintrans_expect, matrix,
                       matrix_diagonals, rand_slab, random_diagonals, random_keys)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_headroom, check_level_decrypt,  # noqa: F401
-                         dev_t, encode_diagonals, env, fresh_records, install_galois_keys, keyed_cases, lift_records,
-                         periodic_values, rescale_records, run_example, run_many, run_plan, sentinel_out, step_elements,
-                         stream_of, take)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_headroom, check_level_decrypt, create_handle, creates_refused, dev_t,
+                         dptr, encode_diagonals, env, fresh_records, hptr, install_galois_keys, keyed_cases,
+                         lift_records, periodic_values, rescale_records, run_example, run_many, run_plan, sentinel_out,
+                         step_elements, stream_of, take)
 
 pytestmark = pytest.mark.gpu
 
@@ -180,80 +179,61 @@ def test_lintrans_arguments(env):
     out1 = torch.full_like(out0, SENTINEL)
     diag = torch.ones((2, npr, n), dtype=torch.int32, device=env["dev"])
     diag0 = torch.ones((npr, n), dtype=torch.int32, device=env["dev"])
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     el = lambda *g: np.array(g + (0,) * (65 - len(g)), dtype=np.uint32)     # room for the G = 65 call
     good, even, big, nokey = el(3, 9), el(3, 4), el(3, 2 * n + 1), el(3, 5)
-    P0, P1, O0, O1, E, D, D0 = p(c0), p(c1), p(out0), p(out1), hp(good), p(diag), p(diag0)
-
-    def create(ctx_h, elts, G, d, d0, pt, want_out=True):
-        handle = C.c_void_p(0xDEAD)                         # a failed create must overwrite it with NULL
-        rc = L.se_amd_lintrans_create(ctx_h, elts, G, d, d0, pt, C.byref(handle) if want_out else None)
-        return rc, handle
-
-    bad_creates = [
-        (None, E, 2, D, D0, npr),
-        (h, z, 2, D, D0, npr),                               # NULL elts, d_diag
-        (h, E, 2, z, D0, npr),
-        (h, E, 0, D, D0, npr),                               # G = 0, G = 65
-        (h, E, 65, D, D0, npr),
-        (h, E, 2, D, D0, 0),                                 # pt_primes = 0
-        (h, hp(even), 2, D, D0, npr),                        # an even element, one >= 2n
-        (h, hp(big), 2, D, D0, npr),
-        (h, E, 2, p(diag, 4), D0, npr),                      # alignment of either diagonal pointer
-        (h, E, 2, D, p(diag0, 8), npr),
-    ]
-    for k, args in enumerate(bad_creates):
-        rc, handle = create(*args)
-        assert rc == SE_ERR_INVALD_ARGUMENT and handle.value is None, (k, rc, handle.value)
-    assert create(h, E, 2, D, D0, npr, want_out=False)[0] == SE_ERR_INVALD_ARGUMENT       # NULL out
-    rc, handle = create(h, hp(nokey), 2, D, D0, npr)
-    assert rc == SE_ERR_NO_KEY and handle.value is None
+    mk = CEntry(L.se_amd_lintrans_create, ctx=h, elts=hptr(good), G=2, diag=dptr(diag), diag0=dptr(diag0), pt_primes=npr,
+                out=None)
+    creates_refused(mk, [
+        dict(ctx=None),
+        dict(elts=NULL),                                     # NULL elts, d_diag
+        dict(diag=NULL),
+        dict(G=0),                                           # G = 0, G = 65
+        dict(G=65),
+        dict(pt_primes=0),                                   # pt_primes = 0
+        dict(elts=hptr(even)),                               # an even element, one >= 2n
+        dict(elts=hptr(big)),
+        dict(diag=dptr(diag, 4)),                            # alignment of either diagonal pointer
+        dict(diag0=dptr(diag0, 8)),
+    ])
+    assert create_handle(mk, out=None)[0] == SE_ERR_INVALD_ARGUMENT                       # NULL out
+    creates_refused(mk, [dict(elts=hptr(nokey))], SE_ERR_NO_KEY)
     assert "element 5" in L.se_amd_last_error().decode(), L.se_amd_last_error()
-    rc, plan = create(h, E, 2, D, D0, 2)                     # a plan of two levels, with diag0
+    rc, plan = create_handle(mk, pt_primes=2)                # a plan of two levels, with diag0
     assert rc == 0 and plan.value
-    rc, foreign = create(other.h, E, 2, D, D0, npr)
+    rc, foreign = create_handle(mk, ctx=other.h)
     assert rc == 0 and foreign.value
-    rc, no0 = create(h, E, 1, D, z, 7)                       # no diag0; pt_primes above np serves np levels
+    rc, no0 = create_handle(mk, G=1, diag0=NULL, pt_primes=7)    # no diag0; pt_primes above np serves np levels
     assert rc == 0 and no0.value
 
-    def call(ctx_h, pl, a0, a1, Bv, primes, o0, o1):
-        return L.se_amd_ct_lintrans_device(ctx_h, pl, a0, a1, Bv, primes, o0, o1, s)
-
-    bad_calls = [
-        (None, plan, P0, P1, B, 2, O0, O1),
-        (h, plan, z, P1, B, 2, O0, O1),                      # NULL slab pointers
-        (h, plan, P0, z, B, 2, O0, O1),
-        (h, plan, P0, P1, B, 2, z, O1),
-        (h, plan, P0, P1, B, 2, O0, z),
-        (h, plan, P0, P1, B, 0, O0, O1),                     # primes outside [1, np]
-        (h, plan, P0, P1, B, 4, O0, O1),
-        (h, plan, P0, P1, 2 ** 32, 2, O0, O1),               # B >= 2^32
-        (h, plan, p(c0, 4), P1, B, 2, O0, O1),               # alignment, each slab
-        (h, plan, P0, p(c1, 8), B, 2, O0, O1),
-        (h, plan, P0, P1, B, 2, p(out0, 12), O1),
-        (h, plan, P0, P1, B, 2, O0, p(out1, 4)),
-        (h, z, P0, P1, B, 2, O0, O1),                        # no plan
-        (h, foreign, P0, P1, B, 2, O0, O1),                  # a plan of another context
-        (other.h, plan, P0, P1, B, 2, O0, O1),
-        (h, plan, P0, P1, B, 3, O0, O1),                     # a level above the plan's
-    ]
-    for k, args in enumerate(bad_calls):
-        assert call(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert call(h, plan, P0, P1, 0, 2, O0, O1) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    call = CEntry(L.se_amd_ct_lintrans_device, ctx=h, plan=plan, c0=dptr(c0), c1=dptr(c1), B=B, primes=2,
+                  out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    call.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                       # NULL slab pointers
+        dict(c1=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                      # primes outside [1, np]
+        dict(primes=4),
+        dict(B=2 ** 32),                                     # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+        dict(plan=NULL),                                     # no plan
+        dict(plan=foreign),                                  # a plan of another context
+        dict(ctx=other.h),
+        dict(primes=3),                                      # a level above the plan's
+    ])
+    assert call(B=0) == 0
+    assert_untouched(out0, out1)
     # the plans work: zero keys and zero slabs give zero rows, at level 2 resp. 3
     for pl, lv in ((plan, 2), (no0, 3)):
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
-        assert call(h, pl, P0, P1, B, lv, O0, O1) == 0
-        torch.cuda.synchronize()
+        assert call(plan=pl, primes=lv) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:B * lv * n])) == 0 and bool((flat[B * lv * n:] == SENTINEL).all())
+            assert_zero_prefix(o, B * lv * n)
     L.se_amd_lintrans_destroy(None)
     for pl in (plan, foreign, no0):
         L.se_amd_lintrans_destroy(pl)

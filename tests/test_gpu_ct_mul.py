@@ -5,18 +5,16 @@ Every expectation is built from the oracle's primitives (ntt, intt, decrypt, fft
 integers, never from the code under test; every comparison is bit-exact except the reference's own acceptance criterion
 |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below
 Oracle(n, L): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import vectors as V
 from ct_model import (DIGIT_MASK, SHAPE_IDS, crt_centred, digit_key_errors, digits_of, negacyclic, rand_slab,
                       relin_diagonal, relin_expect)
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, check_level_decrypt,  # noqa: F401
-                         decode_expect, dev_t, encrypt_sym, env, expectation, fresh_records, keyed_cases, ntt_secret,
-                         rescale_records, run_decrypt, run_example, run_relin, same_bytes, sentinel_out, stream_of, take,
-                         unit_values)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_matches,  # noqa: F401
+                         assert_untouched, assert_zero_prefix, check_level_decrypt, decode_expect, dev_t, dptr,
+                         encrypt_sym, env, expectation, fresh_records, keyed_cases, ntt_secret, rescale_records,
+                         run_decrypt, run_example, run_relin, same_bytes, sentinel_out, stream_of, take, unit_values)
 
 pytestmark = pytest.mark.gpu
 
@@ -129,38 +127,29 @@ def test_tensor_arguments(env):
     torch = env["torch"]
     n, npr, B = 4096, 3, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     a0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     a1, b0, b1 = torch.zeros_like(a0), torch.zeros_like(a0), torch.zeros_like(a0)
     o0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     o1, o2 = torch.full_like(o0, SENTINEL), torch.full_like(o0, SENTINEL)
     idx = torch.zeros(B, dtype=torch.int32, device=env["dev"])
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f = L.se_amd_ct_mul_device
+    call = CEntry(ctx.L.se_amd_ct_mul_device, ctx=ctx.h, A0=dptr(a0), A1=dptr(a1), Ba=B, B0=dptr(b0), B1=dptr(b1), Bb=B,
+                  primes=3, P=B, ia=dptr(idx), ib=dptr(idx), O0=dptr(o0), O1=dptr(o1), O2=dptr(o2), status=dptr(st),
+                  stream=stream_of(env))
     big = 2 ** 32
-
-    def call(ctxh=h, A0=p(a0), A1=p(a1), Ba=B, B0=p(b0), B1=p(b1), Bb=B, primes=3, P=B, ia=p(idx), ib=p(idx), O0=p(o0),
-             O1=p(o1), O2=p(o2)):
-        return f(ctxh, A0, A1, Ba, B0, B1, Bb, primes, P, ia, ib, O0, O1, O2, p(st), s)
-
-    bad = [dict(ctxh=None), dict(A0=z), dict(A1=z), dict(B0=z), dict(B1=z), dict(O0=z), dict(O1=z), dict(O2=z),
-           dict(ia=z), dict(ib=z),                                  # only one index list
-           dict(ia=z, ib=z, P=B + 1), dict(ia=z, ib=z, Ba=B + 1), dict(ia=z, ib=z, Bb=B + 1),
-           dict(primes=0), dict(primes=4),
-           dict(P=big), dict(Ba=big), dict(Bb=big),
-           dict(A0=p(a0, 4)), dict(A1=p(a1, 8)), dict(B0=p(b0, 12)), dict(B1=p(b1, 4)), dict(O0=p(o0, 4)),
-           dict(O1=p(o1, 8)), dict(O2=p(o2, 12))]
-    for kw in bad:
-        assert call(**kw) == SE_ERR_INVALD_ARGUMENT, kw
+    call.refused([
+        dict(ctx=None), dict(A0=NULL), dict(A1=NULL), dict(B0=NULL), dict(B1=NULL), dict(O0=NULL), dict(O1=NULL),
+        dict(O2=NULL),
+        dict(ia=NULL), dict(ib=NULL),                               # only one index list
+        dict(ia=NULL, ib=NULL, P=B + 1), dict(ia=NULL, ib=NULL, Ba=B + 1), dict(ia=NULL, ib=NULL, Bb=B + 1),
+        dict(primes=0), dict(primes=4),
+        dict(P=big), dict(Ba=big), dict(Bb=big),
+        dict(A0=dptr(a0, 4)), dict(A1=dptr(a1, 8)), dict(B0=dptr(b0, 12)), dict(B1=dptr(b1, 4)), dict(O0=dptr(o0, 4)),
+        dict(O1=dptr(o1, 8)), dict(O2=dptr(o2, 12))])
     assert call(P=0) == 0
-    torch.cuda.synchronize()
-    for o in (o0, o1, o2):
-        assert bool((o == SENTINEL).all())
-    assert bool((st == 77).all())
-    assert call() == 0 and call(ia=z, ib=z) == 0
+    assert_untouched(o0, o1, o2)
+    assert_untouched(st, fill=77)
+    assert call() == 0 and call(ia=NULL, ib=NULL) == 0
     torch.cuda.synchronize()
     assert int(torch.count_nonzero(o0)) == 0 and int(torch.count_nonzero(o1)) == 0 and int(torch.count_nonzero(o2)) == 0
     assert bool((st == 1).all())
@@ -311,17 +300,12 @@ def test_decrypt3_keyed_twin(env):
     for f in ("pte", "values", "values_f64"):
         assert int(torch.count_nonzero(got[f][4])) == 0, f
     # the argument errors of the level entry, and the third slab
-    L, h = ctx.L, ctx.h
-    p = lambda x: C.c_void_p(x.data_ptr())
-    z = C.c_void_p(None)
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    f3 = L.se_amd_decrypt3_level_device
-    assert f3(h, p(d[0]), p(d[1]), z, B, npr, scale, z, z, z, p(st), stream_of(env)) == SE_ERR_INVALD_ARGUMENT
-    assert f3(h, p(d[0]), p(d[1]), p(d[2]), B, npr + 1, scale, z, z, z, p(st), stream_of(env)) == SE_ERR_INVALD_ARGUMENT
-    assert f3(h, p(d[0]), p(d[1]), p(d[2]), B, npr, 0.0, z, z, z, p(st), stream_of(env)) == SE_ERR_INVALD_ARGUMENT
-    assert f3(h, p(d[0]), p(d[1]), p(d[2]), 0, npr, scale, z, z, z, p(st), stream_of(env)) == 0
-    torch.cuda.synchronize()
-    assert bool((st == 77).all())
+    f3 = CEntry(ctx.L.se_amd_decrypt3_level_device, ctx=ctx.h, c0=dptr(d[0]), c1=dptr(d[1]), c2=dptr(d[2]), B=B,
+                primes=npr, scale=scale, pte=NULL, values=NULL, values_f64=NULL, status=dptr(st), stream=stream_of(env))
+    f3.refused([dict(c2=NULL), dict(primes=npr + 1), dict(scale=0.0)])
+    assert f3(B=0) == 0
+    assert_untouched(st, fill=77)
     ctx.close()
 
 
@@ -358,14 +342,12 @@ def test_relin_key_generation(env, shape):
     B = 1
     slab = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    p = lambda x: C.c_void_p(x.data_ptr())
-    z = C.c_void_p(None)
-    assert ctx.L.se_amd_decrypt_level_device(ctx.h, p(slab), p(slab), B, npr, ctx.scale(), z, z, z, p(st),
-                                             stream_of(env)) == SE_ERR_NO_KEY
+    assert ctx.L.se_amd_decrypt_level_device(ctx.h, dptr(slab), dptr(slab), B, npr, ctx.scale(), NULL, NULL, NULL,
+                                             dptr(st), stream_of(env)) == SE_ERR_NO_KEY
     # ct_relin before an install, a refused install, and ct_relin after the refused install
     out0, out1 = torch.full_like(slab, SENTINEL), torch.full_like(slab, SENTINEL)
-    relin = lambda: ctx.L.se_amd_ct_relin_device(ctx.h, p(slab), p(slab), p(slab), B, npr, p(out0), p(out1),
-                                                 stream_of(env))
+    relin = CEntry(ctx.L.se_amd_ct_relin_device, ctx=ctx.h, d0=dptr(slab), d1=dptr(slab), d2=dptr(slab), B=B, primes=npr,
+                   out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
     assert relin() == SE_ERR_NO_KEY
     for which, (r, i, c) in ((0, (0, 0, 0)), (1, (R - 1, npr - 1, n - 1))):
         k0, k1 = evk0.copy(), evk1.copy()
@@ -378,7 +360,7 @@ def test_relin_key_generation(env, shape):
     assert relin() == 0
     torch.cuda.synchronize()
     assert int(torch.count_nonzero(out0)) == 0 and int(torch.count_nonzero(out1)) == 0     # the zero slabs relinearise to zero
-    assert bool((st == 77).all())
+    assert_untouched(st, fill=77)
     ctx.close()
 
 
@@ -455,43 +437,35 @@ def test_relin_arguments(env):
     torch = env["torch"]
     n, npr, B = 4096, 3, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     key = np.zeros((2 * npr, npr, n), dtype=np.uint32)
     ctx.set_relin_key(key, key)
     d0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     d1, d2 = torch.zeros_like(d0), torch.zeros_like(d0)
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f = L.se_amd_ct_relin_device
-    bad_calls = [
-        (None, p(d0), p(d1), p(d2), B, 3, p(out0), p(out1), s),
-        (h, z, p(d1), p(d2), B, 3, p(out0), p(out1), s),               # NULL mandatory pointers
-        (h, p(d0), z, p(d2), B, 3, p(out0), p(out1), s),
-        (h, p(d0), p(d1), z, B, 3, p(out0), p(out1), s),
-        (h, p(d0), p(d1), p(d2), B, 3, z, p(out1), s),
-        (h, p(d0), p(d1), p(d2), B, 3, p(out0), z, s),
-        (h, p(d0), p(d1), p(d2), B, 0, p(out0), p(out1), s),           # primes outside [1, np]
-        (h, p(d0), p(d1), p(d2), B, 4, p(out0), p(out1), s),
-        (h, p(d0), p(d1), p(d2), 2 ** 32, 3, p(out0), p(out1), s),     # B >= 2^32
-        (h, p(d0, 4), p(d1), p(d2), B, 3, p(out0), p(out1), s),        # alignment, each slab
-        (h, p(d0), p(d1, 8), p(d2), B, 3, p(out0), p(out1), s),
-        (h, p(d0), p(d1), p(d2, 12), B, 3, p(out0), p(out1), s),
-        (h, p(d0), p(d1), p(d2), B, 3, p(out0, 4), p(out1), s),
-        (h, p(d0), p(d1), p(d2), B, 3, p(out0), p(out1, 8), s),
-    ]
-    for k, args in enumerate(bad_calls):
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert f(h, p(d0), p(d1), p(d2), 0, 3, p(out0), p(out1), s) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    f = CEntry(ctx.L.se_amd_ct_relin_device, ctx=ctx.h, d0=dptr(d0), d1=dptr(d1), d2=dptr(d2), B=B, primes=3,
+               out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
+    f.refused([
+        dict(ctx=None),
+        dict(d0=NULL),                                                 # NULL mandatory pointers
+        dict(d1=NULL),
+        dict(d2=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                                # primes outside [1, np]
+        dict(primes=4),
+        dict(B=2 ** 32),                                               # B >= 2^32
+        dict(d0=dptr(d0, 4)),                                          # alignment, each slab
+        dict(d1=dptr(d1, 8)),
+        dict(d2=dptr(d2, 12)),
+        dict(out0=dptr(out0, 4)),
+        dict(out1=dptr(out1, 8)),
+    ])
+    assert f(B=0) == 0
+    assert_untouched(out0, out1)
     # a level-2 call writes B . 2 . n words and nothing behind them
-    assert f(h, p(d0), p(d1), p(d2), B, 2, p(out0), p(out1), s) == 0
-    torch.cuda.synchronize()
-    flat = out0.reshape(-1)
-    assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+    assert f(primes=2) == 0
+    assert_zero_prefix(out0, B * 2 * n)
     ctx.close()
 
 

@@ -3,17 +3,15 @@ Every expectation is the definition in tests/ct_model_pack.py on top of tests/ct
 intt, decrypt, fft, expand_ternary) and Python / NumPy integers, never the code under test.  Every comparison is bit-exact
 except the reference's own acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ct_model import (SHAPE_IDS, call_elements, centred, edge_row, inverse_element, key_errors, rand_key, rand_slab,
                       sigma_rows)
 from ct_model_pack import csr_entries, pack_expect, pack_row_quotient
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
-                         env, expectation, fresh_records, guarded_pair, install_galois_keys, keyed_cases, run_example,
-                         run_galois_sp, step_elements, stream_of)
+from gpu_support import (NULL, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched, assert_zero_prefix,  # noqa: F401
+                         check_level_decrypt, dev_t, dptr, drop_records, env, expectation, fresh_records, guarded_pair,
+                         hptr, install_galois_keys, keyed_cases, run_example, run_galois_sp, step_elements, stream_of)
 from vectors import sigma_coeff
 
 pytestmark = pytest.mark.gpu
@@ -267,7 +265,7 @@ def test_pack_arguments(env):
     torch, pkg = env["torch"], env["pkg"]
     n, npr, B, G = 4096, 3, 2, 2
     ctx = pkg.Context(n, npr)
-    L, h = ctx.L, ctx.h
+    L = ctx.L
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1 = torch.zeros_like(c0)
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
@@ -276,34 +274,27 @@ def test_pack_arguments(env):
     rp = dev_t(env, np.array([0, 1, 2], dtype=np.uint32))
     ix = dev_t(env, np.array([1, 0], dtype=np.uint32))
     ex = dev_t(env, np.array([0, 1], dtype=np.uint32))
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)  # noqa: E731
-    hp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f = L.se_amd_ct_pack_sp_device
     good = np.array([3, 1], dtype=np.uint32)
     many = np.full(65, 3, dtype=np.uint32)
     even, big = np.array([3, 4], dtype=np.uint32), np.array([2 * n + 1, 3], dtype=np.uint32)
-    P0, P1, O0, O1, S, EL = p(c0), p(c1), p(out0), p(out1), p(st), hp(good)
-
-    def csr_call(ctx_h=h, a0=P0, a1=P1, nb=B, primes=2, el=EL, ne=2, g=G, r=p(rp), i=p(ix), e=p(ex), nnz=2, o0=O0, o1=O1):
-        return f(ctx_h, a0, a1, nb, primes, el, ne, g, r, i, e, nnz, o0, o1, S, s)
-
-    single_call = lambda **kw: csr_call(r=z, i=z, **kw)  # noqa: E731
+    csr_call = CEntry(L.se_amd_ct_pack_sp_device, ctx=ctx.h, a0=dptr(c0), a1=dptr(c1), nb=B, primes=2, el=hptr(good), ne=2,
+                      g=G, r=dptr(rp), i=dptr(ix), e=dptr(ex), nnz=2, o0=dptr(out0), o1=dptr(out1), status=dptr(st),
+                      stream=stream_of(env))
+    single = dict(r=NULL, i=NULL)                           # the single form: no row_ptr, no idx
     # nothing is installed yet: the refusals come before the keys are looked at
-    bad = [csr_call(ctx_h=None), csr_call(a0=z), csr_call(a1=z), csr_call(o0=z), csr_call(o1=z), csr_call(el=z),
-           csr_call(e=z), single_call(e=z),
-           csr_call(r=z), csr_call(i=z),                                   # exactly one of row_ptr / idx
-           single_call(g=1), single_call(g=3), single_call(nnz=1), single_call(nnz=3),
-           csr_call(ne=0), csr_call(el=hp(many), ne=65),
-           csr_call(el=hp(even)), csr_call(el=hp(big)),
-           csr_call(primes=0), csr_call(primes=3), csr_call(primes=4),
-           csr_call(nb=2 ** 32), csr_call(g=2 ** 32), csr_call(nnz=2 ** 32),
-           csr_call(a0=p(c0, 4)), csr_call(a1=p(c1, 8)), csr_call(o0=p(out0, 12)), csr_call(o1=p(out1, 4))]
-    assert [k for k, rc in enumerate(bad) if rc != SE_ERR_INVALD_ARGUMENT] == []
+    csr_call.refused([
+        dict(ctx=None), dict(a0=NULL), dict(a1=NULL), dict(o0=NULL), dict(o1=NULL), dict(el=NULL),
+        dict(e=NULL), dict(single, e=NULL),
+        dict(r=NULL), dict(i=NULL),                                        # exactly one of row_ptr / idx
+        dict(single, g=1), dict(single, g=3), dict(single, nnz=1), dict(single, nnz=3),
+        dict(ne=0), dict(el=hptr(many), ne=65),
+        dict(el=hptr(even)), dict(el=hptr(big)),
+        dict(primes=0), dict(primes=3), dict(primes=4),
+        dict(nb=2 ** 32), dict(g=2 ** 32), dict(nnz=2 ** 32),
+        dict(a0=dptr(c0, 4)), dict(a1=dptr(c1, 8)), dict(o0=dptr(out0, 12)), dict(o1=dptr(out1, 4))])
     # a context of one prime has no prime to reserve
     one = pkg.Context(1024, 1)
-    assert f(one.h, P0, P1, B, 1, EL, 2, G, p(rp), p(ix), p(ex), 2, O0, O1, S, s) == SE_ERR_INVALD_ARGUMENT
+    csr_call.refused([dict(ctx=one.h, primes=1)])
     one.close()
     # no key of the right family: digit Galois keys, a relinearisation key and a switch ring do not serve
     assert csr_call() == SE_ERR_NO_KEY and "element 3" in L.se_amd_last_error().decode()
@@ -312,28 +303,27 @@ def test_pack_arguments(env):
     ctx.set_galois_keys([3, 9], dkey, dkey)
     ctx.set_relin_key_sp(key[0], key[0])
     ctx.set_switch_keyring_sp(key, key)
-    assert csr_call() == SE_ERR_NO_KEY and single_call() == SE_ERR_NO_KEY
+    assert csr_call() == SE_ERR_NO_KEY and csr_call(**single) == SE_ERR_NO_KEY
     ctx.set_galois_keys_sp([9, 5], key, key)
     assert csr_call() == SE_ERR_NO_KEY
     msg = L.se_amd_last_error().decode()
     assert "special-prime" in msg and "element 3" in msg, msg
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     # with the key: the identity alone needs none; G = 0 is a no-op; a level-1 call writes G . n words
     ctx.set_galois_keys_sp([3, 9], key, key)
     assert csr_call(g=0) == 0
-    assert csr_call(el=hp(np.array([1], dtype=np.uint32)), ne=1, e=p(torch.zeros_like(ex)), primes=1) == 0
+    ident, e0 = np.array([1], dtype=np.uint32), torch.zeros_like(ex)
+    assert csr_call(el=hptr(ident), ne=1, e=dptr(e0), primes=1) == 0
     torch.cuda.synchronize()
     assert bool((out0.reshape(-1)[G * n:] == SENTINEL).all()) and bool((st == 1).all())
-    for call in (lambda: csr_call(primes=1), lambda: single_call(primes=1)):
+    for form in ({}, single):
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
         st.fill_(77)
-        assert call() == 0
-        torch.cuda.synchronize()
+        assert csr_call(**form, primes=1) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:G * n])) == 0 and bool((flat[G * n:] == SENTINEL).all())
+            assert_zero_prefix(o, G * n)
         assert bool((st == 1).all())
     ctx.close()
 

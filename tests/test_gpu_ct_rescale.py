@@ -4,16 +4,14 @@ Every expectation is built from the oracle's primitives (ntt, intt, decrypt, fft
 integers, never from the code under test; every comparison is bit-exact except the reference's own acceptance criterion
 |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).  Oracle(n, L - 1) is the oracle of the level below
 Oracle(n, L): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import vectors as V
 from ct_model import SHAPE_IDS, centred, negacyclic, rescale_expect
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, assert_matches, bits, check_level_decrypt,  # noqa: F401
-                         dev_t, encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, run_example,
-                         same_bytes, stream_of)
+from gpu_support import (NULL, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_matches, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, bits, check_level_decrypt, dev_t, dptr, encrypt_sym, env, expectation,
+                         host_u32, ntt_secret, records, run_decrypt, run_example, same_bytes, stream_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -103,39 +101,31 @@ def test_rescale_arguments(env):
     torch = env["torch"]
     n, npr, B = 4096, 3, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     in0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     in1 = torch.zeros_like(in0)
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
     out1 = torch.full_like(out0, SENTINEL)
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f = L.se_amd_ct_rescale_device
-    bad_calls = [
-        (None, p(in0), p(in1), B, 3, p(out0), p(out1), s),
-        (h, z, p(in1), B, 3, p(out0), p(out1), s),             # NULL d_in0
-        (h, p(in0), p(in1), B, 3, z, p(out1), s),              # NULL d_out0
-        (h, p(in0), p(in1), B, 3, p(out0), z, s),              # half a second pair
-        (h, p(in0), z, B, 3, p(out0), p(out1), s),
-        (h, p(in0), p(in1), B, 1, p(out0), p(out1), s),        # primes outside [2, np]
-        (h, p(in0), p(in1), B, 0, p(out0), p(out1), s),
-        (h, p(in0), p(in1), B, 4, p(out0), p(out1), s),
-        (h, p(in0, 4), p(in1), B, 3, p(out0), p(out1), s),     # alignment, each slab
-        (h, p(in0), p(in1, 8), B, 3, p(out0), p(out1), s),
-        (h, p(in0), p(in1), B, 3, p(out0, 12), p(out1), s),
-        (h, p(in0), p(in1), B, 3, p(out0), p(out1, 4), s),
-    ]
-    for k, args in enumerate(bad_calls):
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert f(h, p(in0), p(in1), 0, 3, p(out0), p(out1), s) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all())
+    f = CEntry(ctx.L.se_amd_ct_rescale_device, ctx=ctx.h, in0=dptr(in0), in1=dptr(in1), B=B, primes=3, out0=dptr(out0),
+               out1=dptr(out1), stream=stream_of(env))
+    f.refused([
+        dict(ctx=None),
+        dict(in0=NULL),                                        # NULL d_in0
+        dict(out0=NULL),                                       # NULL d_out0
+        dict(out1=NULL),                                       # half a second pair
+        dict(in1=NULL),
+        dict(primes=1),                                        # primes outside [2, np]
+        dict(primes=0),
+        dict(primes=4),
+        dict(in0=dptr(in0, 4)),                                # alignment, each slab
+        dict(in1=dptr(in1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+    ])
+    assert f(B=0) == 0
+    assert_untouched(out0, out1)
     # the all-zero slab rescales to zero: (0 - NTT(0)) . inv
-    assert f(h, p(in0), z, B, 3, p(out0), z, s) == 0
-    torch.cuda.synchronize()
-    flat = out0.reshape(-1)
-    assert int(torch.count_nonzero(flat[:B * 2 * n])) == 0 and bool((flat[B * 2 * n:] == SENTINEL).all())
+    assert f(in1=NULL, out1=NULL) == 0
+    assert_zero_prefix(out0, B * 2 * n)
     ctx.close()
 
 
@@ -306,36 +296,31 @@ def test_level_arguments(env):
     torch = env["torch"]
     n, npr, B = 4096, 3, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1 = torch.zeros_like(c0)
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    p = lambda t: C.c_void_p(t.data_ptr())
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f, fk = L.se_amd_decrypt_level_device, L.se_amd_decrypt_level_keyed_device
     good = ctx.scale()
-    assert f(h, p(c0), p(c1), B, 3, good, z, z, z, p(st), s) == SE_ERR_NO_KEY
+    f = CEntry(ctx.L.se_amd_decrypt_level_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=3, scale=good,
+               pte=NULL, values=NULL, values_f64=NULL, status=dptr(st), stream=stream_of(env))
+    assert f() == SE_ERR_NO_KEY
     ctx.set_secret_key(V.secret_key(n))
-    for primes, scale in ((0, good), (4, good), (3, 0.0), (3, float("nan")), (3, -good), (3, float("inf"))):
-        assert f(h, p(c0), p(c1), B, primes, scale, z, z, z, p(st), s) == SE_ERR_INVALD_ARGUMENT, (primes, scale)
-    assert f(None, p(c0), p(c1), B, 3, good, z, z, z, p(st), s) == SE_ERR_INVALD_ARGUMENT
-    assert f(h, z, p(c1), B, 3, good, z, z, z, p(st), s) == SE_ERR_INVALD_ARGUMENT
-    assert f(h, p(c0), z, B, 3, good, z, z, z, p(st), s) == SE_ERR_INVALD_ARGUMENT
-    assert f(h, p(c0), p(c1), B, 3, good, z, z, z, z, s) == SE_ERR_INVALD_ARGUMENT          # no output requested
-    assert f(h, p(c0), p(c1), 0, 3, good, z, z, z, p(st), s) == 0
+    f.refused([dict(primes=0), dict(primes=4), dict(scale=0.0), dict(scale=float("nan")), dict(scale=-good),
+               dict(scale=float("inf")),
+               dict(ctx=None), dict(c0=NULL), dict(c1=NULL),
+               dict(status=NULL)])                                                           # no output requested
+    assert f(B=0) == 0
     # keyed twin
     ki = torch.zeros(B, dtype=torch.int32, device=env["dev"])
-    assert fk(h, p(c0), p(c1), B, 3, good, p(ki), z, z, z, p(st), s) == SE_ERR_NO_KEY
+    fk = CEntry(ctx.L.se_amd_decrypt_level_keyed_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=3, scale=good,
+                key_idx=dptr(ki), pte=NULL, values=NULL, values_f64=NULL, status=dptr(st), stream=stream_of(env))
+    assert fk() == SE_ERR_NO_KEY
     sk, _, _ = ctx.gen_keys_batch(V.derive_seeds("larg-pk", 2), V.derive_seeds("larg-ep", 2),
                                   sk_seeds=V.derive_seeds("larg-sk", 2))
     ctx.set_secret_keyring(sk)
-    for primes, scale in ((0, good), (4, good), (3, 0.0), (3, float("nan"))):
-        assert fk(h, p(c0), p(c1), B, primes, scale, p(ki), z, z, z, p(st), s) == SE_ERR_INVALD_ARGUMENT
-    assert fk(h, p(c0), p(c1), B, 3, good, z, z, z, z, p(st), s) == SE_ERR_INVALD_ARGUMENT   # NULL d_key_idx
-    torch.cuda.synchronize()
-    assert bool((st == 77).all())
-    assert fk(h, p(c0), p(c1), B, 2, good, p(ki), z, z, z, p(st), s) == 0
+    fk.refused([dict(primes=0), dict(primes=4), dict(scale=0.0), dict(scale=float("nan")),
+                dict(key_idx=NULL)])                                                         # NULL d_key_idx
+    assert_untouched(st, fill=77)
+    assert fk(primes=2) == 0
     torch.cuda.synchronize()
     assert bool((st == 1).all())
     ctx.close()
@@ -442,7 +427,6 @@ def test_mul_plain_arguments(env):
     torch = env["torch"]
     n, npr, B, P = 4096, 3, 4, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
     in0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     in1 = torch.zeros_like(in0)
     out0 = torch.full_like(in0, SENTINEL)
@@ -450,40 +434,37 @@ def test_mul_plain_arguments(env):
     pt = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     idx = torch.zeros(B, dtype=torch.int32, device=env["dev"])
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    z = C.c_void_p(None)
-    s = stream_of(env)
-    f = L.se_amd_ct_mul_plain_device
+    f = CEntry(ctx.L.se_amd_ct_mul_plain_device, ctx=ctx.h, in0=dptr(in0), in1=dptr(in1), B=B, primes=3, pt=dptr(pt),
+               P=P, pt_primes=3, pt_idx=dptr(idx), out0=dptr(out0), out1=dptr(out1), status=dptr(st),
+               stream=stream_of(env))
     big = 2 ** 32
-    bad_calls = [
-        (None, p(in0), p(in1), B, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),
-        (h, z, p(in1), B, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),            # NULL d_in0
-        (h, p(in0), p(in1), B, 3, p(pt), P, 3, p(idx), z, p(out1), p(st), s),             # NULL d_out0
-        (h, p(in0), p(in1), B, 3, z, P, 3, p(idx), p(out0), p(out1), p(st), s),           # NULL d_pt
-        (h, p(in0), p(in1), B, 3, p(pt), P, 3, p(idx), p(out0), z, p(st), s),             # half a second pair
-        (h, p(in0), z, B, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),
-        (h, p(in0), p(in1), B, 0, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),       # primes outside [1, np]
-        (h, p(in0), p(in1), B, 4, p(pt), P, 4, p(idx), p(out0), p(out1), p(st), s),
-        (h, p(in0), p(in1), B, 3, p(pt), P, 2, p(idx), p(out0), p(out1), p(st), s),       # pt_primes < primes
-        (h, p(in0), p(in1), B, 3, p(pt), 2, 3, z, p(out0), p(out1), p(st), s),            # no index, P neither 1 nor B
-        (h, p(in0), p(in1), B, 3, p(pt), 0, 3, z, p(out0), p(out1), p(st), s),
-        (h, p(in0), p(in1), B, 3, p(pt), B + 1, 3, z, p(out0), p(out1), p(st), s),
-        (h, p(in0), p(in1), big, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),     # B, P >= 2^32
-        (h, p(in0), p(in1), B, 3, p(pt), big, 3, p(idx), p(out0), p(out1), p(st), s),
-        (h, p(in0, 4), p(in1), B, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),    # alignment
-        (h, p(in0), p(in1, 8), B, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s),
-        (h, p(in0), p(in1), B, 3, p(pt, 4), P, 3, p(idx), p(out0), p(out1), p(st), s),
-        (h, p(in0), p(in1), B, 3, p(pt), P, 3, p(idx), p(out0, 12), p(out1), p(st), s),
-        (h, p(in0), p(in1), B, 3, p(pt), P, 3, p(idx), p(out0), p(out1, 4), p(st), s),
-    ]
-    for k, args in enumerate(bad_calls):
-        assert f(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert f(h, p(in0), p(in1), 0, 3, p(pt), P, 3, p(idx), p(out0), p(out1), p(st), s) == 0
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    f.refused([
+        dict(ctx=None),
+        dict(in0=NULL),                                        # NULL d_in0
+        dict(out0=NULL),                                       # NULL d_out0
+        dict(pt=NULL),                                         # NULL d_pt
+        dict(out1=NULL),                                       # half a second pair
+        dict(in1=NULL),
+        dict(primes=0),                                        # primes outside [1, np]
+        dict(primes=4, pt_primes=4),
+        dict(pt_primes=2),                                     # pt_primes < primes
+        dict(P=2, pt_idx=NULL),                                # no index, P neither 1 nor B
+        dict(P=0, pt_idx=NULL),
+        dict(P=B + 1, pt_idx=NULL),
+        dict(B=big),                                           # B, P >= 2^32
+        dict(P=big),
+        dict(in0=dptr(in0, 4)),                                # alignment
+        dict(in1=dptr(in1, 8)),
+        dict(pt=dptr(pt, 4)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+    ])
+    assert f(B=0) == 0
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     # the valid calls work without a key and without a status
-    assert f(h, p(in0), p(in1), B, 3, p(pt), B, 3, z, p(out0), p(out1), z, s) == 0
-    assert f(h, p(in0), z, B, 3, p(pt), 1, 3, z, p(out0), z, z, s) == 0
+    assert f(P=B, pt_idx=NULL, status=NULL) == 0
+    assert f(in1=NULL, P=1, pt_idx=NULL, out1=NULL, status=NULL) == 0
     torch.cuda.synchronize()
     assert int(torch.count_nonzero(out0)) == 0 and int(torch.count_nonzero(out1)) == 0
     ctx.close()

@@ -4,8 +4,6 @@ Every expectation is the definition in tests/ct_model_switch.py on top of tests/
 intt, decrypt, fft, expand_ternary) and Python / NumPy integers, never the code under test.  Every comparison is bit-exact
 except the reference's own acceptance criterion |values - expected| < 0.1 (device/test/ckks_tests_common.c:132).
 Oracle(n, L) is the oracle of a level-L record of Oracle(n, np): the default chains are prefixes of one another."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -13,9 +11,10 @@ import vectors as V
 from ct_model import (CASE_IDS, SHAPE_IDS, SP_CASES, centred, edge_row, galois_seeds, galois_sp_expect, key_errors,
                       rand_key, rand_slab, relin_sp_expect, sp_diagonal, switch_quotient)
 from ct_model_switch import random_ring, ring_seeds, row_quotient, switch_expect, switch_sum_expect
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, check_level_decrypt, dev_t, drop_records,  # noqa: F401
-                         env, expectation, guarded_pair, install_galois_keys, keyed_cases, ntt_secret, run_decrypt,
-                         run_example, run_galois_sp, run_relin_sp, step_elements, stream_of, unit_values)
+from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, SENTINEL, CEntry, assert_untouched,  # noqa: F401
+                         assert_zero_prefix, check_level_decrypt, dev_t, dptr, drop_records, env, expectation,
+                         guarded_pair, hptr, install_galois_keys, keyed_cases, ntt_secret, run_decrypt, run_example,
+                         run_galois_sp, run_relin_sp, step_elements, stream_of, unit_values)
 
 pytestmark = pytest.mark.gpu
 
@@ -227,16 +226,14 @@ def test_switch_key_generation_and_installs(env, shape):
     rows = [[0, 1], [1]]
     rp, idx, nnz = csr(rows)
     d_rp, d_idx = dev_t(env, rp), dev_t(env, idx)
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
-    hp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
-    z = C.c_void_p(None)
     out0, out1 = torch.full_like(d0, SENTINEL), torch.full_like(d0, SENTINEL)
     st = torch.full((B,), 77, dtype=torch.uint8, device=env["dev"])
-    one = lambda: ctx.L.se_amd_ct_switch_keyed_sp_device(ctx.h, ptr(d0), ptr(d1), B, L, ptr(dk), ptr(out0), ptr(out1),  # noqa: E731
-                                                         ptr(st), stream_of(env))
-    many = lambda: ctx.L.se_amd_ct_switch_sum_keyed_sp_device(ctx.h, ptr(d0), ptr(d1), B, L, ptr(dk), len(rows), ptr(d_rp),  # noqa: E731
-                                                              ptr(d_idx), nnz, ptr(out0), ptr(out1), ptr(st), stream_of(env))
-    assert ctx.L.se_amd_decrypt_level_device(ctx.h, ptr(d0), ptr(d1), B, L, ctx.scale(), z, z, z, ptr(st),
+    one = CEntry(ctx.L.se_amd_ct_switch_keyed_sp_device, ctx=ctx.h, c0=dptr(d0), c1=dptr(d1), B=B, primes=L,
+                 key_idx=dptr(dk), out0=dptr(out0), out1=dptr(out1), status=dptr(st), stream=stream_of(env))
+    many = CEntry(ctx.L.se_amd_ct_switch_sum_keyed_sp_device, ctx=ctx.h, c0=dptr(d0), c1=dptr(d1), B=B, primes=L,
+                  key_idx=dptr(dk), G=len(rows), row_ptr=dptr(d_rp), idx=dptr(d_idx), nnz=nnz, out0=dptr(out0),
+                  out1=dptr(out1), status=dptr(st), stream=stream_of(env))
+    assert ctx.L.se_amd_decrypt_level_device(ctx.h, dptr(d0), dptr(d1), B, L, ctx.scale(), NULL, NULL, NULL, dptr(st),
                                              stream_of(env)) == SE_ERR_NO_KEY
     assert one() == SE_ERR_NO_KEY and many() == SE_ERR_NO_KEY
     # a refused first install installs nothing
@@ -246,8 +243,8 @@ def test_switch_key_generation_and_installs(env, shape):
         ctx.set_switch_keyring_sp(bad0, wk1)
     assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
     assert one() == SE_ERR_NO_KEY and many() == SE_ERR_NO_KEY
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
     ctx.set_switch_keyring_sp(wk0, wk1)
     want = switch_expect(o, c0[:1], c1[:1], key_idx[:1], wk0, wk1)
 
@@ -263,8 +260,8 @@ def test_switch_key_generation_and_installs(env, shape):
         with pytest.raises(pkg.SealEmbeddedAmdError) as ei:
             ctx.set_switch_keyring_sp(k0, k1)
         assert f"code {SE_ERR_INVALD_ARGUMENT}" in str(ei.value)
-    assert ctx.L.se_amd_set_switch_keyring_sp(ctx.h, 0, hp(wk0), hp(wk1)) == SE_ERR_INVALD_ARGUMENT      # K = 0
-    assert ctx.L.se_amd_set_switch_keyring_sp(ctx.h, K, z, hp(wk1)) == SE_ERR_INVALD_ARGUMENT
+    install = CEntry(ctx.L.se_amd_set_switch_keyring_sp, ctx=ctx.h, K=K, wk0=hptr(wk0), wk1=hptr(wk1))
+    install.refused([dict(K=0), dict(wk0=NULL)])
     assert all((a == b).all() for a, b in zip(before, ring_works()))          # the same bits as before
     # the generator's own refusals; nothing is written
     bad_sk = sk_to.copy()
@@ -272,16 +269,13 @@ def test_switch_key_generation_and_installs(env, shape):
     bad_from = sk_from.copy()
     bad_from[1, n // 4 - 1] |= 0x30
     t0, t1 = np.zeros_like(wk0), np.zeros_like(wk1)
-    gen = lambda Kx, f, t: ctx.L.se_amd_gen_switch_keys_sp(ctx.h, Kx, hp(f), hp(t), hp(sa), hp(se), hp(t0), hp(t1))  # noqa: E731
-    assert gen(K, sk_from, bad_sk) == SE_ERR_INVALD_ARGUMENT
-    assert gen(K, bad_from, sk_to) == SE_ERR_INVALD_ARGUMENT
-    assert gen(0, sk_from, sk_to) == SE_ERR_INVALD_ARGUMENT
-    assert ctx.L.se_amd_gen_switch_keys_sp(ctx.h, K, z, hp(sk_to), hp(sa), hp(se), hp(t0), hp(t1)) == SE_ERR_INVALD_ARGUMENT
-    assert ctx.L.se_amd_gen_switch_keys_sp(ctx.h, K, hp(sk_from), hp(sk_to), hp(sa), hp(se), hp(t0), z) == SE_ERR_INVALD_ARGUMENT
+    gen = CEntry(ctx.L.se_amd_gen_switch_keys_sp, ctx=ctx.h, K=K, sk_from=hptr(sk_from), sk_to=hptr(sk_to),
+                 seeds_a=hptr(sa), seeds_e=hptr(se), wk0=hptr(t0), wk1=hptr(t1))
+    gen.refused([dict(sk_to=hptr(bad_sk)), dict(sk_from=hptr(bad_from)), dict(K=0), dict(sk_from=NULL), dict(wk1=NULL)])
     assert not t0.any() and not t1.any()
     # the ring and the special-prime evaluation keys are installed sets of their own
-    rel = lambda: ctx.L.se_amd_ct_relin_sp_device(ctx.h, ptr(d0), ptr(d1), ptr(d2), B, L, ptr(out0), ptr(out1),  # noqa: E731
-                                                  stream_of(env))
+    rel = CEntry(ctx.L.se_amd_ct_relin_sp_device, ctx=ctx.h, c0=dptr(d0), c1=dptr(d1), c2=dptr(d2), B=B, primes=L,
+                 out0=dptr(out0), out1=dptr(out1), stream=stream_of(env))
     assert rel() == SE_ERR_NO_KEY                                             # the ring does not serve the relinearisation
     ek = [rand_key(rng, o.q, n) for _ in range(4)]
     ctx.set_relin_key_sp(ek[0], ek[1])
@@ -346,7 +340,7 @@ def test_switch_arguments(env):
     torch = env["torch"]
     n, npr, B, G = 4096, 3, 2, 2
     ctx = env["pkg"].Context(n, npr)
-    L, h = ctx.L, ctx.h
+    L = ctx.L
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1 = torch.zeros_like(c0)
     out0 = torch.full((B, npr, n), SENTINEL, dtype=torch.int32, device=env["dev"])
@@ -355,79 +349,71 @@ def test_switch_arguments(env):
     ki = torch.zeros(B, dtype=torch.int32, device=env["dev"])
     rp = dev_t(env, np.array([0, 1, 2], dtype=np.uint32))
     ix = dev_t(env, np.array([1, 0], dtype=np.uint32))
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)  # noqa: E731
-    z = C.c_void_p(None)
     s = stream_of(env)
-    f2, f3 = L.se_amd_ct_switch_keyed_sp_device, L.se_amd_ct_switch_sum_keyed_sp_device
+    f2 = CEntry(L.se_amd_ct_switch_keyed_sp_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=2, key_idx=dptr(ki),
+                out0=dptr(out0), out1=dptr(out1), status=dptr(st), stream=s)
+    f3 = CEntry(L.se_amd_ct_switch_sum_keyed_sp_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, primes=2,
+                key_idx=dptr(ki), G=G, row_ptr=dptr(rp), idx=dptr(ix), nnz=2, out0=dptr(out0), out1=dptr(out1),
+                status=dptr(st), stream=s)
     key = np.zeros((2, npr - 1, npr, n), dtype=np.uint32)
     ctx.set_switch_keyring_sp(key, key)
-    bad2 = [
-        (None, p(c0), p(c1), B, 2, p(ki), p(out0), p(out1), p(st), s),
-        (h, z, p(c1), B, 2, p(ki), p(out0), p(out1), p(st), s),                 # NULL mandatory pointers
-        (h, p(c0), z, B, 2, p(ki), p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, z, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), z, p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), p(out0), z, p(st), s),
-        (h, p(c0), p(c1), B, 0, p(ki), p(out0), p(out1), p(st), s),             # primes outside [1, np - 1]
-        (h, p(c0), p(c1), B, 3, p(ki), p(out0), p(out1), p(st), s),             # primes = np
-        (h, p(c0), p(c1), B, 4, p(ki), p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), 2 ** 32, 2, p(ki), p(out0), p(out1), p(st), s),       # B >= 2^32
-        (h, p(c0, 4), p(c1), B, 2, p(ki), p(out0), p(out1), p(st), s),          # alignment, each slab
-        (h, p(c0), p(c1, 8), B, 2, p(ki), p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), p(out0, 12), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), p(out0), p(out1, 4), p(st), s),
-    ]
-    for k, args in enumerate(bad2):
-        assert f2(*args) == SE_ERR_INVALD_ARGUMENT, k
-    bad3 = [
-        (None, p(c0), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, z, p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), z, B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, z, G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, z, p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, p(rp), z, 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, z, p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), z, p(st), s),
-        (h, p(c0), p(c1), B, 0, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 3, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), 2 ** 32, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), 2 ** 32, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2 ** 32, p(out0), p(out1), p(st), s),
-        (h, p(c0, 4), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1, 8), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0, 12), p(out1), p(st), s),
-        (h, p(c0), p(c1), B, 2, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1, 4), p(st), s),
-    ]
-    for k, args in enumerate(bad3):
-        assert f3(*args) == SE_ERR_INVALD_ARGUMENT, k
-    assert f2(h, p(c0), p(c1), 0, 2, p(ki), p(out0), p(out1), p(st), s) == 0
-    assert f3(h, p(c0), p(c1), B, 2, p(ki), 0, p(rp), p(ix), 2, p(out0), p(out1), p(st), s) == 0
+    f2.refused([
+        dict(ctx=None),
+        dict(c0=NULL),                                                          # NULL mandatory pointers
+        dict(c1=NULL),
+        dict(key_idx=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),                                                         # primes outside [1, np - 1]
+        dict(primes=3),                                                         # primes = np
+        dict(primes=4),
+        dict(B=2 ** 32),                                                        # B >= 2^32
+        dict(c0=dptr(c0, 4)),                                                   # alignment, each slab
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+    ])
+    f3.refused([
+        dict(ctx=None),
+        dict(c0=NULL),
+        dict(c1=NULL),
+        dict(key_idx=NULL),
+        dict(row_ptr=NULL),
+        dict(idx=NULL),
+        dict(out0=NULL),
+        dict(out1=NULL),
+        dict(primes=0),
+        dict(primes=3),
+        dict(B=2 ** 32),
+        dict(G=2 ** 32),
+        dict(nnz=2 ** 32),
+        dict(c0=dptr(c0, 4)),
+        dict(c1=dptr(c1, 8)),
+        dict(out0=dptr(out0, 12)),
+        dict(out1=dptr(out1, 4)),
+    ])
+    assert f2(B=0) == 0
+    assert f3(G=0) == 0
     # a context of one prime has no prime to reserve
     one = env["pkg"].Context(1024, 1)
     k1 = np.zeros((1, 1, 1, 1024), dtype=np.uint32)
     sd = np.zeros((1, 64), dtype=np.uint8)
     sk = V.secret_key(1024, seed=3)
-    hp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
-    oh, oL = one.h, one.L
-    assert oL.se_amd_ct_switch_keyed_sp_device(oh, p(c0), p(c1), B, 1, p(ki), p(out0), p(out1), p(st),
-                                               s) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_ct_switch_sum_keyed_sp_device(oh, p(c0), p(c1), B, 1, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1),
-                                                   p(st), s) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_set_switch_keyring_sp(oh, 1, hp(k1), hp(k1)) == SE_ERR_INVALD_ARGUMENT
-    assert oL.se_amd_gen_switch_keys_sp(oh, 1, hp(sk), hp(sk), hp(sd), hp(sd), hp(k1), hp(k1)) == SE_ERR_INVALD_ARGUMENT
+    f2.refused([dict(ctx=one.h, primes=1)])
+    f3.refused([dict(ctx=one.h, primes=1)])
+    assert L.se_amd_set_switch_keyring_sp(one.h, 1, hptr(k1), hptr(k1)) == SE_ERR_INVALD_ARGUMENT
+    assert L.se_amd_gen_switch_keys_sp(one.h, 1, hptr(sk), hptr(sk), hptr(sd), hptr(sd), hptr(k1),
+                                       hptr(k1)) == SE_ERR_INVALD_ARGUMENT
     assert not k1.any()
     one.close()
-    torch.cuda.synchronize()
-    assert bool((out0 == SENTINEL).all()) and bool((out1 == SENTINEL).all()) and bool((st == 77).all())
-    for call in (lambda: f2(h, p(c0), p(c1), B, 1, p(ki), p(out0), p(out1), p(st), s),
-                 lambda: f3(h, p(c0), p(c1), B, 1, p(ki), G, p(rp), p(ix), 2, p(out0), p(out1), p(st), s)):
+    assert_untouched(out0, out1)
+    assert_untouched(st, fill=77)
+    for f in (f2, f3):
         out0.fill_(SENTINEL)
         out1.fill_(SENTINEL)
-        assert call() == 0
-        torch.cuda.synchronize()
+        assert f(primes=1) == 0
         for o in (out0, out1):
-            flat = o.reshape(-1)
-            assert int(torch.count_nonzero(flat[:B * n])) == 0 and bool((flat[B * n:] == SENTINEL).all())
+            assert_zero_prefix(o, B * n)
         assert bool((st == 1).all())
     ctx.close()
 

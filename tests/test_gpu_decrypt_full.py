@@ -3,15 +3,14 @@ Every expectation is built from the oracle's primitives (decrypt, intt, fft) and
 under test; every comparison is bit-exact except the reference's own acceptance criterion |values - input| < 0.1
 (device/test/ckks_tests_common.c:132).  The constructed records at the end (tests/recv_model.py) are planted Python integers,
 one for every branch of the recombination: the record's own integers are the expectation."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import vectors as V
 from ct_model import CASE_IDS
-from gpu_support import (SE_ERR_INVALD_ARGUMENT, SE_ERR_NO_KEY, assert_matches, bits, decode_expect, dev_t,  # noqa: F401
-                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, run_example, stream_of)
+from gpu_support import (NULL, SE_ERR_NO_KEY, CEntry, assert_matches, bits, decode_expect, dev_t, dptr,  # noqa: F401
+                         encrypt_sym, env, expectation, host_u32, ntt_secret, records, run_decrypt, run_example,
+                         stream_of)
 from recv_model import SHAPES as RECV_SHAPES
 from recv_model import ciphertext_of, expect_at_level, in_range_vectors, out_of_range_vectors
 
@@ -230,16 +229,15 @@ def test_optional_outputs_and_arguments(env):
     n, npr, B = 4096, 3, 5
     ctx = pkg.Context(n, npr)
     L = ctx.L
-    z = C.c_void_p(None)
     stream = stream_of(env)
     vals = V.bench_values(B, n, first=9)
     vals[2] *= 300.0
     c0 = torch.zeros((B, npr, n), dtype=torch.int32, device=env["dev"])
     c1 = torch.zeros_like(c0)
     st = torch.zeros(B, dtype=torch.uint8, device=env["dev"])
-    p = lambda t: C.c_void_p(t.data_ptr())
     # no secret key yet
-    assert L.se_amd_decrypt_full_device(ctx.h, p(c0), p(c1), B, z, z, z, p(st), stream) == SE_ERR_NO_KEY
+    assert L.se_amd_decrypt_full_device(ctx.h, dptr(c0), dptr(c1), B, NULL, NULL, NULL, dptr(st),
+                                        stream) == SE_ERR_NO_KEY
     ctx.set_secret_key(V.secret_key(n))
     c0, c1, _, _ = encrypt_sym(env, ctx, vals, first=9)
     full = run_decrypt(env, ctx, c0, c1)
@@ -249,22 +247,20 @@ def test_optional_outputs_and_arguments(env):
         for g in ("pte", "values", "values_f64", "status"):
             if g != f:      # an output that was not requested is not written
                 assert alone[g].cpu().numpy().tobytes() != full[g].cpu().numpy().tobytes(), (f, g)
-    assert L.se_amd_decrypt_full_device(ctx.h, p(c0), p(c1), B, z, z, z, z, stream) == SE_ERR_INVALD_ARGUMENT
-    assert L.se_amd_decrypt_full_device(ctx.h, z, p(c1), B, z, z, z, p(st), stream) == SE_ERR_INVALD_ARGUMENT
-    assert L.se_amd_decrypt_full_device(ctx.h, p(c0), z, B, z, z, z, p(st), stream) == SE_ERR_INVALD_ARGUMENT
-    assert L.se_amd_decrypt_full_device(None, p(c0), p(c1), B, z, z, z, p(st), stream) == SE_ERR_INVALD_ARGUMENT
-    assert L.se_amd_decrypt_full_device(ctx.h, p(c0), p(c1), 0, z, z, z, p(st), stream) == 0
+    f = CEntry(L.se_amd_decrypt_full_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, pte=NULL, values=NULL,
+               values_f64=NULL, status=dptr(st), stream=stream)
+    f.refused([dict(status=NULL), dict(c0=NULL), dict(c1=NULL), dict(ctx=None)])
+    assert f(B=0) == 0
     # keyed twin
     sk, _, _ = ctx.gen_keys_batch(V.derive_seeds("arg-pk", 2), V.derive_seeds("arg-ep", 2),
                                   sk_seeds=V.derive_seeds("arg-sk", 2))
     ctx.set_secret_keyring(sk)
     ki = torch.zeros(B, dtype=torch.int32, device=env["dev"])
-    fk = L.se_amd_decrypt_full_keyed_device
-    assert fk(ctx.h, p(c0), p(c1), B, p(ki), z, z, z, z, stream) == SE_ERR_INVALD_ARGUMENT
-    assert fk(ctx.h, p(c0), p(c1), B, z, z, z, z, p(st), stream) == SE_ERR_INVALD_ARGUMENT
-    assert fk(ctx.h, z, p(c1), B, p(ki), z, z, z, p(st), stream) == SE_ERR_INVALD_ARGUMENT
-    assert fk(ctx.h, p(c0), p(c1), 0, p(ki), z, z, z, p(st), stream) == 0
-    assert fk(ctx.h, p(c0), p(c1), B, p(ki), z, z, z, p(st), stream) == 0
+    fk = CEntry(L.se_amd_decrypt_full_keyed_device, ctx=ctx.h, c0=dptr(c0), c1=dptr(c1), B=B, key_idx=dptr(ki), pte=NULL,
+                values=NULL, values_f64=NULL, status=dptr(st), stream=stream)
+    fk.refused([dict(status=NULL), dict(key_idx=NULL), dict(c0=NULL)])
+    assert fk(B=0) == 0
+    assert fk() == 0
     torch.cuda.synchronize()
     ctx.close()
 
