@@ -991,6 +991,79 @@ int se_amd_ct_dot_sp_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_
                             const uint32_t *d_ia, const uint32_t *d_ib /*[nnz] or both NULL*/, size_t nnz,
                             uint32_t *d_out0, uint32_t *d_out1 /*[G][primes][n]*/, uint8_t *d_status /*[G], optional*/,
                             void *stream);
+/* ---- Slot-wise polynomials: a power ladder and a fused weighted-sum rescale -----------------------------------------
+ * se_amd_ct_affine_rescale_device, key-free: the weighted sum of T term records that live at their own levels, ONE
+ * rescale of the sum and a constant, in one launch.  d_term0 / d_term1 are HOST arrays of T device pointers; term t is the
+ * pair of level-term_primes[t] slabs [B][term_primes[t]][n] with term_primes[t] >= primes, of which only the first
+ * `primes` rows of a record are read (the pt_primes convention of se_amd_ct_mul_plain_device); term_primes and w are host
+ * arrays [T].  With
+ *     acc_s[b][j] = sum_t (w_t mod q_j) . term_s[t][b][j]  mod q_j,   j < primes,
+ * w mod q_j the non-negative residue of the int64,
+ *     out1[b] = rescale(acc1[b]),   out0[b] = rescale(acc0[b]) + (c_after mod q_i) in every position of every row
+ * i < primes - 1 (a constant polynomial is constant in NTT form), both [B][primes - 1][n], canonical.  `rescale` is exactly
+ * the map of se_amd_ct_rescale_device: centred delta of the last row, exact quotient.  The map is defined on arbitrary
+ * residue slabs and is BIT-IDENTICAL to se_amd_ct_drop_primes_device of every term to `primes`, the weighted modular sum,
+ * se_amd_ct_rescale_device, then the constant added to slab 0 -- without the dropped copies and without the sum in
+ * memory.  No scratch, no key, nothing uploaded (the residues of the weights and of the constant travel in the kernel's
+ * argument block), one asynchronous launch; outputs must not overlap inputs (not checked).  Every int64 is a valid weight
+ * and a valid constant.  CKKS meaning: the scale of the sum is w_t . scale_t, which the caller makes equal across the
+ * terms; the rescale divides it by q_{primes-1}; c_after is a constant at the resulting scale.
+ * SE_ERR_INVALD_ARGUMENT, with nothing written: a NULL ctx, pointer array, term_primes, w or output; a NULL term pointer; T
+ * outside [1, SE_AMD_AFFINE_MAX_TERMS]; primes outside [2, np]; a term_primes[t] outside [primes, np]; a device pointer
+ * that is not 16-byte aligned; B at or above 2^31.  B = 0 is a successful no-op. */
+#define SE_AMD_AFFINE_MAX_TERMS 16
+int se_amd_ct_affine_rescale_device(se_amd_ctx *ctx, const uint32_t *const *d_term0,
+                                    const uint32_t *const *d_term1 /* HOST arrays of T device pointers */,
+                                    const uint32_t *term_primes /* host [T] */, const int64_t *w /* host [T] */, size_t T,
+                                    int64_t c_after, size_t B, size_t primes, uint32_t *d_out0,
+                                    uint32_t *d_out1 /* [B][primes-1][n] */, void *stream);
+/* Polynomial plans.  se_amd_poly_create (host-only, no device, no context) makes the schedule that evaluates
+ * p(x) = sum_d a_d x^d slot-wise on level-`primes` records (L = primes) at scale scale_in; se_amd_ct_poly_sp_device runs it
+ * under the installed special-prime relinearisation key (se_amd_set_relin_key_sp).  The schedule:
+ * Ladder.  For d >= 2: depth(d) = ceil(log2 d), h(d) = 2^(depth(d) - 1), and x^d = x^h . x^(d-h).  The product is taken at
+ * level m = L - depth(d) + 1; x^h lives at exactly that level, the other operand is dropped to it with
+ * se_amd_ct_drop_primes_device when it is higher.  The product is a one-pair row of se_amd_ct_dot_sp_device, followed by
+ * se_amd_ct_rescale_device.  x^d is then at level L - depth(d) with scale(d) = scale(h) . scale(d-h) / (double)q_{m-1};
+ * scale(1) = scale_in.
+ * Needed powers.  {d >= 1 : a_d != 0}, closed under d -> h(d), d - h(d).  Nothing else is computed: for an odd polynomial
+ * of degree 7, x^6 is not.
+ * Combine.  One se_amd_ct_affine_rescale_device call at level l = L - depth(D), D the degree; its terms are the powers with
+ * a_d != 0, each read in place at its own level, with
+ *     w_d = nearbyint(((a_d . scale_out) . (double)q_{l-1}) / scale(d)),     c_after = nearbyint(a_0 . scale_out),
+ * IEEE doubles evaluated in that order, ties to even (Python's round on the same doubles gives the same integers).  The
+ * result is at level l - 1, at scale scale_out by construction.
+ * se_amd_poly_terms: the needed powers in increasing order -- power, level (primes of the record that holds it), scale(d)
+ * and w_d (0 for a power with a_d = 0) -- at most `cap` of them into each array that is not NULL; returns their count.
+ * se_amd_poly_result: out_primes = l - 1 and c_after.  se_amd_poly_workspace_bytes: what a call on `records` records needs:
+ * the row pointers of the one-pair rows, both slabs of every power above 1 at its level, of one product and of one
+ * dropped operand (0 for a plan of degree 1).
+ * The call.  The workspace is the caller's, as with se_amd_ct_bsgs_device (device memory, 16-byte aligned); nothing is
+ * allocated, nothing synchronises, every launch is on `stream`.  Launches: with K the needed powers above 1 and K' those
+ * of them whose lower operand is dropped, 1 (the row pointers) + 2 K (product, rescale) + 1 (combine) kernels and 2 K'
+ * pitched copies; a plan of degree 1 is the combine alone.  d_out0, d_out1 are [B][l - 1][n].
+ * Range, the caller's: |p(x)| . scale_out . q_{l-1} < Q_l / 2 for the combine's sum, and every power x^d below
+ * Q_level(d) / 2 at its scale(d) (its product below Q_m / 2 before the rescale).  Lift fresh records so that
+ * scale_in is about q: one se_amd_ct_lincomb_device with the weight round(q_{L-1} / se_amd_scale(ctx)), which keeps every
+ * scale(d) near q and every weight near a_d . scale_out.
+ * se_amd_poly_create refuses, with SE_ERR_INVALD_ARGUMENT and *out untouched: an unsupported (n, np); degree outside
+ * [1, SE_AMD_POLY_MAX_DEGREE]; a_D == 0; a non-finite coefficient or scale; a scale <= 0; primes outside
+ * [depth(D) + 2, np - 1]; a |w_d| or |c_after| at or above 2^62; NULL coeff or out.  se_amd_ct_poly_sp_device refuses NULL
+ * or misaligned pointers, a context whose (n, np) is not the plan's, B at or above 2^31 and work_bytes below
+ * se_amd_poly_workspace_bytes(plan, B); it returns SE_ERR_NO_KEY without a special-prime relinearisation key (a digit key
+ * does not serve); B = 0 is a successful no-op.
+ * Out of scope: a digit-key form (on the special-prime path 4096 x 3 reaches degree 1 only), Paterson-Stockmeyer, a
+ * Chebyshev basis, a ladder step fused with its rescale, multi-device forms. */
+typedef struct se_amd_poly se_amd_poly;
+#define SE_AMD_POLY_MAX_DEGREE 15
+int se_amd_poly_create(size_t n, size_t np, size_t primes, const double *coeff /* host [degree+1], a_0 .. a_D */,
+                       size_t degree, double scale_in, double scale_out, se_amd_poly **out);
+void se_amd_poly_destroy(se_amd_poly *plan);
+size_t se_amd_poly_terms(const se_amd_poly *plan, uint32_t *power, uint32_t *level, double *scale, int64_t *weight,
+                         size_t cap);
+int se_amd_poly_result(const se_amd_poly *plan, size_t *out_primes, int64_t *c_after);
+size_t se_amd_poly_workspace_bytes(const se_amd_poly *plan, size_t records);
+int se_amd_ct_poly_sp_device(se_amd_ctx *ctx, const se_amd_poly *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                             size_t B, void *d_work, size_t work_bytes, uint32_t *d_out0, uint32_t *d_out1, void *stream);
 /* Host-only: the constants the rescale from level `primes` uses: inv[j] = q_{primes-1}^-1 mod q_j and inv_shoup[j] =
  * floor(inv[j] * 2^32 / q_j) for j < primes - 1 (primes - 1 entries are written).  inv_shoup may be NULL.
  * SE_ERR_INVALD_ARGUMENT for an unsupported (degree, primes) or primes < 2. */

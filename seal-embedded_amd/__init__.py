@@ -81,6 +81,8 @@ EXPORTED_SYMBOLS = (
     "se_amd_ct_switch_sum_keyed_sp_device",
     "se_amd_ct_mul_sum_device", "se_amd_ct_dot_sp_device",
     "se_amd_ct_pack_sp_device",
+    "se_amd_ct_affine_rescale_device", "se_amd_poly_create", "se_amd_poly_destroy", "se_amd_poly_terms",
+    "se_amd_poly_result", "se_amd_poly_workspace_bytes", "se_amd_ct_poly_sp_device",
 )
 
 
@@ -214,6 +216,16 @@ def lib():
     L.se_amd_ct_pack_sp_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.se_amd_ct_mul_sum_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.se_amd_ct_dot_sp_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.se_amd_ct_affine_rescale_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int64, sz, sz, vp, vp, vp]
+    L.se_amd_poly_create.argtypes = [sz, sz, sz, vp, sz, C.c_double, C.c_double, C.POINTER(vp)]
+    L.se_amd_poly_destroy.argtypes = [vp]
+    L.se_amd_poly_destroy.restype = None
+    L.se_amd_poly_terms.argtypes = [vp, vp, vp, vp, vp, sz]
+    L.se_amd_poly_terms.restype = sz
+    L.se_amd_poly_result.argtypes = [vp, vp, vp]
+    L.se_amd_poly_workspace_bytes.argtypes = [vp, sz]
+    L.se_amd_poly_workspace_bytes.restype = sz
+    L.se_amd_ct_poly_sp_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -315,6 +327,53 @@ class BsgsPlan(_Plan):
 class LintransPlan(_Plan):
     """Handle of se_amd_lintrans_create (Context.lintrans_plan)."""
     DESTROY = "se_amd_lintrans_destroy"
+
+
+class PolyPlan(_Plan):
+    """Handle of se_amd_poly_create (poly_create): the schedule of a slot-wise polynomial, host data only."""
+    DESTROY = "se_amd_poly_destroy"
+
+    def terms(self):
+        """poly_terms(self)."""
+        return poly_terms(self)
+
+    def result(self):
+        """poly_result(self)."""
+        return poly_result(self)
+
+    def workspace_bytes(self, records):
+        return int(self.L.se_amd_poly_workspace_bytes(self.h, records))
+
+
+def poly_create(n, nprimes, primes, coeff, scale_in, scale_out):
+    """The plan of p(x) = sum coeff[d] x^d on level-`primes` records of the parameter set (n, nprimes) at scale scale_in,
+    result at scale_out (host only: no context, no device).  The degree is len(coeff) - 1."""
+    import numpy as np
+    L = lib()
+    a = np.ascontiguousarray(coeff, dtype=np.float64)
+    h = C.c_void_p(None)
+    _check(L.se_amd_poly_create(n, nprimes, primes, _ptr(a), len(a) - 1, scale_in, scale_out, C.byref(h)),
+           "se_amd_poly_create")
+    return PolyPlan(L, h)
+
+
+def poly_terms(plan):
+    """The needed powers of a plan in increasing order: list of dict(power, level, scale, weight), weight a Python int
+    (0 for a power that is no term of the combine)."""
+    import numpy as np
+    cap = 16
+    d = np.zeros(cap, np.uint32); lv = np.zeros(cap, np.uint32); sc = np.zeros(cap, np.float64); w = np.zeros(cap, np.int64)
+    k = int(plan.L.se_amd_poly_terms(plan.h, _ptr(d), _ptr(lv), _ptr(sc), _ptr(w), cap))
+    return [dict(power=int(d[i]), level=int(lv[i]), scale=float(sc[i]), weight=int(w[i])) for i in range(k)]
+
+
+def poly_result(plan):
+    """(out_primes, c_after) of a plan: the level of the result and the constant of the combine."""
+    out_primes = C.c_size_t(0)
+    c_after = C.c_int64(0)
+    _check(plan.L.se_amd_poly_result(plan.h, C.c_void_p(C.addressof(out_primes)), C.c_void_p(C.addressof(c_after))),
+           "se_amd_poly_result")
+    return int(out_primes.value), int(c_after.value)
 
 
 class Group:
@@ -678,6 +737,38 @@ class Context:
         _check(self.L.se_amd_ct_dot_sp_device(self.h, _ptr(a0), _ptr(a1), a0.shape[0], _ptr(b0), _ptr(b1), b0.shape[0],
                                               primes, G, _ptr(row_ptr), _ptr(ia), _ptr(ib), nnz, _ptr(out0), _ptr(out1),
                                               _ptr(status), _stream_ptr()), "se_amd_ct_dot_sp_device")
+
+    def ct_affine_rescale(self, terms0, terms1, w, c_after, out0, out1, primes):
+        """Key-free weighted sum of T <= 16 term records at their own levels, ONE rescale and a constant: terms0 / terms1
+        are lists of device slabs [B][term_primes][n] (term_primes = shape[1] >= primes, the first `primes` rows are read),
+        w a list of Python ints within int64, c_after an int within int64 added to slab 0 after the rescale; out0, out1
+        are [B][primes - 1][n].  The bits of ct_drop_primes per term, the weighted modular sum, ct_rescale and the
+        constant, without the copies and the sum in memory."""
+        import numpy as np
+        T = len(terms0)
+        p0 = (C.c_void_p * T)(*[t.data_ptr() for t in terms0])
+        p1 = (C.c_void_p * T)(*[t.data_ptr() for t in terms1])
+        assert all(t.is_contiguous() for t in list(terms0) + list(terms1))
+        tp = np.array([t.shape[1] for t in terms0], dtype=np.uint32)
+        wv = np.array([int(x) for x in w], dtype=np.int64)
+        _check(self.L.se_amd_ct_affine_rescale_device(self.h, p0, p1, _ptr(tp), _ptr(wv), T, int(c_after),
+                                                      terms0[0].shape[0], primes, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_affine_rescale_device")
+
+    def poly_workspace_bytes(self, plan, records):
+        """Bytes of device workspace a ct_poly_sp call of `plan` on `records` records needs."""
+        return plan.workspace_bytes(records)
+
+    def ct_poly_sp(self, plan, c0, c1, out0, out1, workspace, workspace_bytes=None):
+        """p(x) slot-wise on level-L records [B][L][n] under the installed special-prime relinearisation key, by the
+        schedule of `plan` (poly_create) in the caller's `workspace` (a device tensor of at least plan.workspace_bytes(B)
+        bytes; None for a plan of degree 1): the ladder of one-pair ct_dot_sp rows and rescales, then one
+        ct_affine_rescale.  out0, out1 are [B][plan.result()[0]][n] at scale_out."""
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+        _check(self.L.se_amd_ct_poly_sp_device(self.h, plan.h, _ptr(c0), _ptr(c1), c0.shape[0], _ptr(workspace),
+                                               workspace_bytes, _ptr(out0), _ptr(out1), _stream_ptr()),
+               "se_amd_ct_poly_sp_device")
 
     def decrypt3_level(self, c0, c1, c2, primes, scale, pte=None, values=None, values_f64=None, status=None):
         """decrypt_level on the degree-2 form (c0, c1, c2): d = c0 + s (c1 + s c2) per prime."""

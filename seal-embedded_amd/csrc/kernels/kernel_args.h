@@ -420,6 +420,29 @@ struct PackSpArgs : GaloisSetArgs
 // in [B][primes][n], out [rows][primes][n]
 hipError_t launch_ct_pack_sp(const DevParams &, const DevTables &, const RescaleParams &, const PackSpArgs &,
                              hipStream_t);
+// The last step of a slot-wise polynomial (k_ct_affine_rescale, ct_poly.hip), key-free: the weighted sum of T term records
+// that live at their own levels, one rescale of the sum and a constant.  Term t is the pair of slabs term0[t], term1[t]
+// [B][term_primes[t]][n], term_primes[t] >= primes, of which the first `primes` rows of a record are read.  With
+//   acc_s[b][j] = sum_t w[t][j] . term_s[t][b][j]  mod q_j,   j < primes,   last = primes - 1,
+//   out_s[b][i] = (acc_s[b][i] - NTT_i(centred(INTT_last(acc_s[b][last])) mod q_i)) . q_last^-1 + (s == 0 ? c[i] : 0)  mod q_i,
+// canonical, i < last: RescaleArgs' map on a row that is never in memory.  w[t][j] and c[i] are canonical residues the host
+// forms from the int64 weights and constant; the block is a kernel argument, so nothing is uploaded.
+constexpr uint32_t kAffineMaxTerms = 16;   // SE_AMD_AFFINE_MAX_TERMS
+struct AffineRescaleArgs
+{
+    const uint32_t *term0[kAffineMaxTerms], *term1[kAffineMaxTerms];
+    uint32_t term_primes[kAffineMaxTerms];   // rows of a record of term t
+    uint32_t w[kAffineMaxTerms][kMaxPrimes];   // w_t mod q_j in [0, q_j)
+    uint32_t c[kMaxPrimes];                    // c_after mod q_i in [0, q_i)
+    uint32_t *out0, *out1;                     // [B][primes - 1][n]
+    uint32_t T;                                // 1 .. kAffineMaxTerms
+    uint32_t primes;                           // 2 .. np
+};
+hipError_t launch_ct_affine_rescale(const DevParams &, const DevTables &, const RescaleParams &, const AffineRescaleArgs &,
+                                    size_t B, hipStream_t);
+// out[k] = k for k < count: the row pointers of `count - 1` one-pair rows (stage_ops.hip), for the plans that call a CSR
+// entry from a caller's workspace.
+hipError_t launch_row_iota(uint32_t *out, size_t count, hipStream_t);
 // Plan set-up: out[r][k] = in[r][src_elt(k)] on `rows` rows of n words, src the permutation of the automorphism of `elt`
 // (odd, below 2n, checked by the host) on a bit-reversed NTT-form row.
 hipError_t launch_bsgs_permute(const DevParams &, const uint32_t *in, uint32_t *out, size_t rows, uint32_t elt,

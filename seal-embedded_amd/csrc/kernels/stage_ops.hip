@@ -458,4 +458,18 @@ hipError_t launch_lower_asym_prime(const DevParams &P, const DevTables &T, const
     return launch_lower(P, T, A, count, st);
 }
 
+// out[k] = k: the row pointers of one-pair CSR rows, written into a caller's workspace on its stream (the polynomial
+// plans call se_amd_ct_dot_sp_device's kernel on rows of one pair; no upload, no allocation).  Not a reference step.
+__global__ void k_row_iota(uint32_t *out, size_t count)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = (uint32_t)i;
+}
+
+hipError_t launch_row_iota(uint32_t *out, size_t count, hipStream_t st)
+{
+    if (count == 0) return hipSuccess;
+    return launch(k_row_iota, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, out, count);
+}
+
 }  // namespace seamd

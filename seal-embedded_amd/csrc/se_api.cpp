@@ -360,6 +360,71 @@ int se_amd_ct_dot_sp_device(se_amd_ctx *ctx, const uint32_t *d_a0, const uint32_
                              nullptr, d_status, as_stream(stream));
 }
 
+int se_amd_ct_affine_rescale_device(se_amd_ctx *ctx, const uint32_t *const *d_term0, const uint32_t *const *d_term1,
+                                    const uint32_t *term_primes, const int64_t *w, size_t T, int64_t c_after, size_t B,
+                                    size_t primes, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_affine_rescale(d_term0, d_term1, term_primes, w, T, c_after, B, primes, d_out0, d_out1,
+                                    as_stream(stream));
+}
+
+int se_amd_poly_create(size_t n, size_t np, size_t primes, const double *coeff, size_t degree, double scale_in,
+                       double scale_out, se_amd_poly **out)
+{
+    if (!out) return SE_ERR_INVALD_ARGUMENT;
+    se_amd_poly *h = new (std::nothrow) se_amd_poly();
+    if (!h) return SE_ERR_NO_MEMORY;
+    if (seamd::poly_plan_init(h->p, n, np, primes, coeff, degree, scale_in, scale_out) != 0)
+    {
+        delete h;
+        seamd::set_last_error("polynomial plan: unsupported (n, np), a degree outside [1, 15], a zero leading or a "
+                              "non-finite coefficient, a scale that is not positive and finite, primes outside "
+                              "[depth + 2, np - 1], or a weight at or above 2^62");
+        return SE_ERR_INVALD_ARGUMENT;
+    }
+    *out = h;
+    return SE_SUCCESS;
+}
+
+void se_amd_poly_destroy(se_amd_poly *plan) { delete plan; }
+
+size_t se_amd_poly_terms(const se_amd_poly *plan, uint32_t *power, uint32_t *level, double *scale, int64_t *weight,
+                         size_t cap)
+{
+    if (!plan) return 0;
+    const std::vector<seamd::PolyPower> &pw = plan->p.powers;
+    for (size_t k = 0; k < pw.size() && k < cap; k++)
+    {
+        if (power) power[k] = pw[k].d;
+        if (level) level[k] = pw[k].level;
+        if (scale) scale[k] = pw[k].scale;
+        if (weight) weight[k] = pw[k].w;
+    }
+    return pw.size();
+}
+
+int se_amd_poly_result(const se_amd_poly *plan, size_t *out_primes, int64_t *c_after)
+{
+    if (!plan) return SE_ERR_INVALD_ARGUMENT;
+    if (out_primes) *out_primes = plan->p.comb_level - 1;
+    if (c_after) *c_after = plan->p.c_after;
+    return SE_SUCCESS;
+}
+
+size_t se_amd_poly_workspace_bytes(const se_amd_poly *plan, size_t records)
+{
+    return plan ? plan->p.workspace_words(records) * sizeof(uint32_t) : 0;
+}
+
+int se_amd_ct_poly_sp_device(se_amd_ctx *ctx, const se_amd_poly *plan, const uint32_t *d_c0, const uint32_t *d_c1,
+                             size_t B, void *d_work, size_t work_bytes, uint32_t *d_out0, uint32_t *d_out1, void *stream)
+{
+    if (!ctx) return SE_ERR_INVALD_ARGUMENT;
+    return ctx->c.ct_poly_sp(plan ? &plan->p : nullptr, d_c0, d_c1, B, d_work, work_bytes, d_out0, d_out1,
+                             as_stream(stream));
+}
+
 int se_amd_decrypt3_level_device(se_amd_ctx *ctx, const uint32_t *d_c0, const uint32_t *d_c1, const uint32_t *d_c2,
                                  size_t B, size_t primes, double scale, int64_t *d_pte, float *d_values,
                                  double *d_values_f64, uint8_t *d_status, void *stream)

@@ -1385,6 +1385,102 @@ int Context::ct_rescale(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, 
     return 0;
 }
 
+// Key-free, one launch, nothing of the context is written and nothing is uploaded: the residues of the weights and of the
+// constant travel in the argument block.
+int Context::ct_affine_rescale(const uint32_t *const *d_term0, const uint32_t *const *d_term1, const uint32_t *term_primes,
+                               const int64_t *w, size_t T, int64_t c_after, size_t B, size_t primes, uint32_t *d_out0,
+                               uint32_t *d_out1, hipStream_t st)
+{
+    if (!d_term0 || !d_term1 || !term_primes || !w || !d_out0 || !d_out1) return kErrInvalid;
+    if (T < 1 || T > kAffineMaxTerms || primes < 2 || primes > hp.nprimes || B > 0x7fffffffu) return kErrInvalid;
+    if (!aligned16({d_out0, d_out1})) return kErrInvalid;
+    // the non-negative residue of any int64 (the remainder of a negative value is in (-q, 0])
+    auto residue = [](int64_t v, uint32_t q) { return (uint32_t)((v % (int64_t)q + (int64_t)q) % (int64_t)q); };
+    AffineRescaleArgs aa{};
+    for (size_t t = 0; t < T; t++)
+    {
+        if (!d_term0[t] || !d_term1[t] || !aligned16({d_term0[t], d_term1[t]})) return kErrInvalid;
+        if (term_primes[t] < primes || term_primes[t] > hp.nprimes) return kErrInvalid;
+        aa.term0[t]       = d_term0[t];
+        aa.term1[t]       = d_term1[t];
+        aa.term_primes[t] = term_primes[t];
+        for (size_t j = 0; j < primes; j++) aa.w[t][j] = residue(w[t], hp.q[j]);
+    }
+    if (B == 0) return 0;
+    for (size_t i = 0; i + 1 < primes; i++) aa.c[i] = residue(c_after, hp.q[i]);
+    aa.out0   = d_out0;
+    aa.out1   = d_out1;
+    aa.T      = (uint32_t)T;
+    aa.primes = (uint32_t)primes;
+    SEAMD_HIP(hipSetDevice(device));
+    SEAMD_HIP(launch_ct_affine_rescale(dp, dt, host_rescale_params(hp, primes), aa, B, st));
+    return 0;
+}
+
+// The schedule of a polynomial plan, every step an entry of this file on `st` in the caller's workspace (PolyPlan::
+// workspace_words is its layout): row pointers | per power above 1 its two slabs | a product | a dropped operand.
+int Context::ct_poly_sp(const PolyPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, void *d_work,
+                        size_t work_bytes, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st)
+{
+    if (!plan || !d_c0 || !d_c1 || !d_out0 || !d_out1 || !aligned16({d_c0, d_c1, d_out0, d_out1, d_work}))
+        return kErrInvalid;
+    if (plan->n != hp.n || plan->np != hp.nprimes || B > 0x7fffffffu) return kErrInvalid;
+    const size_t need = plan->workspace_words(B) * sizeof(uint32_t);
+    if (work_bytes < need || (need && !d_work)) return kErrInvalid;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!(const uint32_t *)evk[1].relin)
+        {
+            set_last_error("no special-prime relinearisation key is installed (se_amd_set_relin_key_sp)");
+            return kErrNoKey;
+        }
+    }
+    if (B == 0) return 0;
+    const size_t n = hp.n, L = plan->L;
+    const std::vector<PolyPower> &pw = plan->powers;
+    // where x^d lives: the input, or its slabs in the workspace
+    const uint32_t *s0[16] = {}, *s1[16] = {};
+    uint32_t lv[16]        = {};
+    s0[1] = d_c0, s1[1] = d_c1, lv[1] = (uint32_t)L;
+    uint32_t *row_ptr = (uint32_t *)d_work, *slab[16][2] = {}, *prod0 = nullptr, *prod1 = nullptr, *drop0 = nullptr,
+             *drop1 = nullptr;
+    if (pw.size() > 1)
+    {
+        uint32_t *at = row_ptr + ((B + 1 + 3) & ~(size_t)3);
+        for (size_t k = 1; k < pw.size(); k++)
+            for (int h = 0; h < 2; h++, at += B * pw[k].level * n) slab[pw[k].d][h] = at;
+        prod0 = at, prod1 = prod0 + B * L * n, drop0 = prod1 + B * L * n, drop1 = drop0 + B * (L - 1) * n;
+        SEAMD_HIP(hipSetDevice(device));
+        SEAMD_HIP(launch_row_iota(row_ptr, B + 1, st));
+    }
+    for (size_t k = 1; k < pw.size(); k++)
+    {
+        const uint32_t d = pw[k].d, m = pw[k].level + 1;
+        uint32_t h = 1;
+        while (2 * h < d) h *= 2;   // 2^(depth(d) - 1)
+        const uint32_t *b0 = s0[d - h], *b1 = s1[d - h];
+        if (lv[d - h] > m)
+        {
+            const int rc = ct_drop_primes(b0, b1, B, lv[d - h], m, drop0, drop1, st);
+            if (rc != 0) return rc;
+            b0 = drop0, b1 = drop1;
+        }
+        int rc = ct_mul_sum(s0[h], s1[h], B, b0, b1, B, m, B, row_ptr, nullptr, nullptr, B, true, prod0, prod1, nullptr,
+                            nullptr, st);
+        if (rc != 0) return rc;
+        rc = ct_rescale(prod0, prod1, B, m, slab[d][0], slab[d][1], st);
+        if (rc != 0) return rc;
+        s0[d] = slab[d][0], s1[d] = slab[d][1], lv[d] = pw[k].level;
+    }
+    const uint32_t *t0[kAffineMaxTerms], *t1[kAffineMaxTerms];
+    uint32_t tp[kAffineMaxTerms];
+    int64_t tw[kAffineMaxTerms];
+    size_t T = 0;
+    for (const PolyPower &p : pw)
+        if (p.term) t0[T] = s0[p.d], t1[T] = s1[p.d], tp[T] = p.level, tw[T] = p.w, T++;
+    return ct_affine_rescale(t0, t1, tp, tw, T, plan->c_after, B, plan->comb_level, d_out0, d_out1, st);
+}
+
 // Key-free, one launch, nothing of the context is written.
 int Context::ct_mul_plain(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *d_pt,
                           size_t P, size_t pt_primes, const uint32_t *d_pt_idx, uint32_t *d_out0, uint32_t *d_out1,

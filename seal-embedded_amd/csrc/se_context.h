@@ -336,6 +336,16 @@ struct Context
     int ct_mul_plain(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t primes, const uint32_t *d_pt,
                      size_t P, size_t pt_primes, const uint32_t *d_pt_idx, uint32_t *d_out0, uint32_t *d_out1,
                      uint8_t *d_status, hipStream_t st);
+    // slot-wise polynomials.  ct_affine_rescale (AffineRescaleArgs): the weighted sum of T term records at their own
+    // levels, one rescale and a constant; host arrays of device pointers, levels and int64 weights; key-free, one launch, no
+    // scratch.  ct_poly_sp: the schedule of a PolyPlan in the caller's workspace under the installed special-prime
+    // relinearisation key -- the row pointers, then per power above 1 the drop (where the operand is higher), the one-pair
+    // product rows and the rescale, then the combine; every launch on `st`, nothing allocated
+    int ct_affine_rescale(const uint32_t *const *d_term0, const uint32_t *const *d_term1, const uint32_t *term_primes,
+                          const int64_t *w, size_t T, int64_t c_after, size_t B, size_t primes, uint32_t *d_out0,
+                          uint32_t *d_out1, hipStream_t st);
+    int ct_poly_sp(const PolyPlan *plan, const uint32_t *d_c0, const uint32_t *d_c1, size_t B, void *d_work,
+                   size_t work_bytes, uint32_t *d_out0, uint32_t *d_out1, hipStream_t st);
     // key-free weighted sums of records (kernels/kernel_args.h, LincombArgs)
     int ct_lincomb(const uint32_t *d_in0, const uint32_t *d_in1, size_t B, size_t G, const uint32_t *d_row_ptr,
                    const uint32_t *d_idx, const int32_t *d_w, size_t nnz, uint32_t *d_out0, uint32_t *d_out1,
@@ -439,6 +449,10 @@ struct se_amd_lintrans
 struct se_amd_bsgs
 {
     seamd::BsgsPlan p;
+};
+struct se_amd_poly
+{
+    seamd::PolyPlan p;
 };
 
 #define SEAMD_HIP(call)                                             \

@@ -14,6 +14,8 @@
 #include <math.h>
 #include <string.h>
 
+#include <utility>
+
 namespace seamd {
 
 namespace {
@@ -155,6 +157,72 @@ RescaleParams host_rescale_params(const HostParams &hp, size_t primes)
         r.inv_sh[j]        = (uint32_t)(((uint64_t)inv << 32) / hp.q[j]);
     }
     return r;
+}
+
+// depth(d) = ceil(log2 d)
+static unsigned poly_depth(size_t d)
+{
+    unsigned k = 0;
+    while (((size_t)1 << k) < d) k++;
+    return k;
+}
+
+size_t PolyPlan::workspace_words(size_t B) const
+{
+    if (powers.size() < 2) return 0;   // degree 1: the combine reads the input in place
+    size_t rows = L + (L - 1);
+    for (size_t k = 1; k < powers.size(); k++) rows += powers[k].level;
+    return ((B + 1 + 3) & ~(size_t)3) + 2 * B * rows * n;
+}
+
+// The ladder and the combine of include/seal_embedded_amd.h, in IEEE doubles in the order written there.
+int poly_plan_init(PolyPlan &plan, size_t n, size_t np, size_t primes, const double *coeff, size_t degree, double scale_in,
+                   double scale_out)
+{
+    HostParams hp;
+    if (host_params_init(hp, n, np) != 0 || !coeff || degree < 1 || degree > 15) return -1;
+    for (size_t d = 0; d <= degree; d++)
+        if (!isfinite(coeff[d])) return -1;
+    if (coeff[degree] == 0.0 || !isfinite(scale_in) || !isfinite(scale_out) || scale_in <= 0 || scale_out <= 0) return -1;
+    const size_t L = primes, depth_D = poly_depth(degree);
+    if (np < 2 || L < depth_D + 2 || L > np - 1) return -1;
+    bool need[16] = {};
+    for (size_t d = 1; d <= degree; d++) need[d] = coeff[d] != 0.0;
+    for (size_t d = degree; d >= 2; d--)   // h(d) and d - h(d) are below d: one descending pass closes the set
+        if (need[d])
+        {
+            const size_t h = (size_t)1 << (poly_depth(d) - 1);
+            need[h] = need[d - h] = true;
+        }
+    double scale[16] = {};
+    scale[1]         = scale_in;
+    const size_t l   = L - depth_D;
+    PolyPlan p;
+    p.n = n, p.np = np, p.L = L, p.comb_level = l;
+    for (size_t d = 1; d <= degree; d++)
+    {
+        if (!need[d]) continue;
+        const size_t depth = poly_depth(d);
+        if (d >= 2)
+        {
+            const size_t h = (size_t)1 << (depth - 1), m = L - depth + 1;
+            scale[d]       = (scale[h] * scale[d - h]) / (double)hp.q[m - 1];
+        }
+        PolyPower pw;
+        pw.d = (uint32_t)d, pw.level = (uint32_t)(L - depth), pw.scale = scale[d], pw.term = coeff[d] != 0.0;
+        if (pw.term)
+        {
+            const double w = nearbyint(((coeff[d] * scale_out) * (double)hp.q[l - 1]) / scale[d]);
+            if (!(fabs(w) < 0x1p62)) return -1;   // a NaN fails the comparison too
+            pw.w = (int64_t)w;
+        }
+        p.powers.push_back(pw);
+    }
+    const double c = nearbyint(coeff[0] * scale_out);
+    if (!(fabs(c) < 0x1p62)) return -1;
+    p.c_after = (int64_t)c;
+    plan      = std::move(p);
+    return 0;
 }
 
 size_t bitrev(size_t x, size_t nbits)
