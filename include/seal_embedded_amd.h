@@ -1164,7 +1164,8 @@ int se_amd_reserve(se_amd_ctx *ctx, size_t B);
  * word changes a result):
  *   8 no helper waves, 16 helper waves without speculation, 32 / 64 force the lane / wave form of the chain kernels,
  *   128 early encoder at n = 16384, 256 speculation windows of one guess (forces the miss path), 512 / 1024 force /
- *   forbid the pair-form staged sampler, 4096 ternary window of blocks + 2 counters (forces the fallback).
+ *   forbid the pair-form staged sampler, 4096 ternary window of blocks + 2 counters (forces the fallback), 8192 the
+ *   fused n = 4096 symmetric / encode-only kernels keep the one-plane pair form instead of the two-way pair form.
  * The environment overrides SE_AMD_STAGED, SE_AMD_SPECULATION are read at context creation into
  * members of their own and survive this call. */
 int se_amd_set_debug_flags(se_amd_ctx *ctx, uint32_t flags);

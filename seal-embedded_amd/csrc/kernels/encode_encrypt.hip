@@ -320,8 +320,9 @@ constexpr size_t kPairParkWords = 5120;   // parked coefficients start here (32-
 
 // Everything behind the encoder for ONE plaintext whose coefficients k = t + (n/16) e sit in m[]: + error, per prime
 // {representative, NTT, fused ciphertext arithmetic}.  PAIR: the caller transforms two plaintexts per workgroup
-// (encrypt_pair) and parks the second one's coefficients in LDS behind the first 9 216 words -- the transpose region
-// then lives inside the NTT plane (one workgroup barrier more per prime: measured neutral, profiles/r05_ab_qalias28.log).
+// (encrypt_pair) and parks the second one's coefficients in LDS behind the first 5 120 words (kPairParkWords) -- the
+// transpose region then lives inside the NTT plane (one workgroup barrier more per prime: measured neutral,
+// profiles/r05_ab_qalias28.log).
 template <int LOGN, int MODE, bool GENERAL, bool PAIR, typename MT>
 __device__ __forceinline__ void encrypt_tail(const DevParams &P, const DevTables &T, const EncArgs &A,
                                              const size_t b, unsigned char *smem, MT (&m)[16], const bool small)
@@ -372,6 +373,7 @@ __device__ __forceinline__ void encrypt_tail(const DevParams &P, const DevTables
     // for the symmetric / encode-only forms, 28-word rows: no gain, profiles/r05_ab_qalias28.log.)
     constexpr bool QALIAS  = (MODE == kModeAsym && ASYM3 && !GENERAL) || PAIR;
     static_assert(!PAIR || (size_t)(G::N / 16) * QSTRIDE <= kPairParkWords, "the transpose region ends below the parked plaintext");
+    static_assert(!PAIR || (size_t)G::SLOTS <= kPairParkWords, "the NTT plane ends below the parked plaintext");
     uint32_t *qlds         = lds32 + (QALIAS ? 0 : (MODE == kModeAsym && ASYM3 ? 3 : 1)) * G::SLOTS;
     auto to_quads = [&](uint32_t (&v)[16]) {
         if constexpr (QUADS) tile_to_quads<QSTRIDE>(v, qlds, t);
@@ -763,6 +765,171 @@ __device__ __forceinline__ void encrypt_pair(const DevParams &P, const DevTables
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The two-way pair form (k_encode_encrypt_pair2): the same pair encoder, guard band and exact redo, but BOTH plaintexts
+// stay in registers and the tail runs prime-major -- per prime ONE two-way transform (transform.cuh, ntt_tiles2) whose
+// root pairs are loaded once for the two butterfly streams under one barrier pair per exchange, and ONE load of the
+// (NTT(s), Shoup) quads for the two epilogues.  Its resource plan is the public-key kernel's: three workgroups per CU
+// (<= 168 VGPRs), two independent butterfly streams per thread.
+// LDS: the encoder's two f64 half-planes and the two u32 NTT planes are the same 2 SLOTS words; the wave-local transpose
+// region (rows of 20 words) lies INSIDE the planes, free after the transform's last barrier, and one workgroup barrier
+// per prime keeps the next prime's first exchange off it.  Nothing is parked.
+// run: bit 0 / bit 1 = plaintext A / B is live (not declined to the general kernel); a declined partner still goes
+// through the transform (its registers hold whatever the encoder left) and is never stored.
+// ------------------------------------------------------------------------------------------
+template <int LOGN, int MODE>
+__device__ __forceinline__ void encrypt_pair2_tail(const DevParams &P, const DevTables &T, const EncArgs &A,
+                                                   const size_t bA, const size_t bB, unsigned char *smem,
+                                                   int32_t (&mA)[16], int32_t (&mB)[16], const int run)
+{
+    static_assert(LOGN <= 12 && MODE != kModeAsym, "quad-layout outputs, one key row per prime");
+    const int t = threadIdx.x;
+    using G            = XformGeom<LOGN>;
+    constexpr int N    = G::N;
+    constexpr int CTOP = LOGN - 4;
+    constexpr int QSTRIDE = enc_quad_stride<MODE>();
+    static_assert((size_t)(G::N / 16) * QSTRIDE <= (size_t)2 * G::SLOTS, "the transpose region lies inside the two planes");
+    uint32_t *lds32 = reinterpret_cast<uint32_t *>(smem);
+    const int np    = P.nprimes;
+    const bool doA = run & 1, doB = run & 2;   // workgroup-uniform
+
+    if constexpr (MODE == kModeSym)
+    {
+#pragma unroll
+        for (int e = 0; e < 16; e++) mA[e] += A.err[bA * N + (e << CTOP) + t];
+#pragma unroll
+        for (int e = 0; e < 16; e++) mB[e] += A.err[bB * N + (e << CTOP) + t];
+    }
+    // (the int64 stores take an opaque 32-bit copy: sign-extended in place, every coefficient would stay the low half of a
+    // 64-bit register pair across the prime loop -- 32 VGPRs of unused high halves and 124 B of spills on the hot path)
+    if (A.pte)
+    {
+        if (doA)
+        {
+#pragma unroll
+            for (int e = 0; e < 16; e++) A.pte[bA * N + (e << CTOP) + t] = opaque_index(mA[e]);
+        }
+        if (doB)
+        {
+#pragma unroll
+            for (int e = 0; e < 16; e++) A.pte[bB * N + (e << CTOP) + t] = opaque_index(mB[e]);
+        }
+    }
+    if constexpr (MODE == kModeEncodeOnly)
+    {
+        if (!A.c0) return;  // plain ckks_encode_base: only the int64 plaintexts were requested
+    }
+    for (int j = 0; j < np; j++)
+    {
+        const uint32_t q = P.q[j], two_q = q << 1;
+        const uint32_t *RW = T.ntt_rw + 2 * xform_table_len(N) * j;
+        const size_t pbA   = (bA * np + j) * N, pbB = (bB * np + j) * N;
+        const size_t kb    = (size_t)2 * N * j;
+        const int tg       = MODE == kModeEncodeOnly ? t : opaque_index(t);   // see encrypt_tail
+        uint32_t xA[16], xB[16];
+        // a_j of both plaintexts comes from HBM: requested before the transform, it lands while the NTT runs
+        uint32_t aA[16], aB[16];
+        if constexpr (MODE == kModeSym)
+        {
+            load_quads(aA, A.c1 + pbA, tg);
+            load_quads(aB, A.c1 + pbB, tg);
+        }
+        reduce_signed16(mA, xA, q, 0u, 0u, true);   // m + 2q (modarith.cuh)
+        reduce_signed16(mB, xB, q, 0u, 0u, true);
+        ntt_tiles2<LOGN>(xA, xB, RW, q, lds32, t);
+        if constexpr (MODE != kModeSym)
+        {
+#pragma unroll
+            for (int e = 0; e < 16; e++) xA[e] = canon4(xA[e], q, two_q), xB[e] = canon4(xB[e], q, two_q);
+        }
+        // one wave-local region for both transposes: LDS executes a wave's accesses in order
+        tile_to_quads<QSTRIDE>(xA, lds32, t);
+        tile_to_quads<QSTRIDE>(xB, lds32, t);
+        if (A.ntt_pte)
+        {
+            uint32_t cx[16];
+            if (doA)
+            {
+#pragma unroll
+                for (int e = 0; e < 16; e++) cx[e] = canon4(xA[e], q, two_q);
+                store_quads(A.ntt_pte + pbA, cx, tg);
+            }
+            if (doB)
+            {
+#pragma unroll
+                for (int e = 0; e < 16; e++) cx[e] = canon4(xB[e], q, two_q);
+                store_quads(A.ntt_pte + pbB, cx, tg);
+            }
+        }
+        if constexpr (MODE == kModeSym)
+        {
+            // c0 = -(s_hat . a) + NTT(m+e)   (ckks_sym.c:273-300) for both plaintexts from ONE load of the key quads
+            uint32_t w[16], wp[16];
+            load_quads_pairs(w, wp, T.s_hat + kb, tg);
+#pragma unroll
+            for (int e = 0; e < 16; e++) xA[e] = sub_mul_canon(xA[e], aA[e], w[e], wp[e], q, two_q);
+            if (doA) store_quads(A.c0 + pbA, xA, tg);
+#pragma unroll
+            for (int e = 0; e < 16; e++) xB[e] = sub_mul_canon(xB[e], aB[e], w[e], wp[e], q, two_q);
+            if (doB) store_quads(A.c0 + pbB, xB, tg);
+        }
+        else
+        {
+            if (doA) store_quads(A.c0 + pbA, xA, tg);
+            if (doB) store_quads(A.c0 + pbB, xB, tg);
+        }
+        __syncthreads();   // the transpose region is the next prime's exchange plane
+    }
+}
+
+// plaintexts bA and bA + 1 (the launcher sends only whole pairs here)
+template <int LOGN, int MODE>
+__device__ __forceinline__ void encrypt_pair2(const DevParams &P, const DevTables &T, const EncArgs &A, const size_t bA,
+                                              unsigned char *smem)
+{
+    const int t     = threadIdx.x;
+    const size_t bB = bA + 1;
+    int32_t mA[16], mB[16];
+    const int flags = encode_pair_half<LOGN>(P, T, A.values, bA, bB, smem, mA, mB);
+    // per plaintext as in encrypt_pair: declined, or coefficients valid after an exact redo where the guard band asks
+    int run = 0;
+    auto settle = [&](int32_t (&mm)[16], const int f, const size_t b, const int bit) {
+        bool small = !(f & (kWgNotSmall | kWgNonfinite));
+        if (small && (f & kWgRisky))
+        {
+            int wg;   // the full transform decides (it writes the status and may still decline)
+            encode_plaintext<LOGN, int32_t, false>(P, T, A.values, A.status, b, smem, mm, small, wg);
+        }
+        else if (small && A.status && t == 0)
+            A.status[b] = 1;
+        if (!small && t == 0) A.general[1 + atomicAdd(A.general, 1u)] = (uint32_t)b;
+        run |= small ? bit : 0;
+    };
+    settle(mA, flags & 0xFF, bA, 1);
+    settle(mB, (flags >> 8) & 0xFF, bB, 2);
+    if (!run) return;   // workgroup-uniform
+    __syncthreads();    // an exact redo may still be reading the planes
+    encrypt_pair2_tail<LOGN, MODE>(P, T, A, bA, bB, smem, mA, mB, run);
+}
+
+// Bytes of dynamic LDS the pair forms address, which launch_enc_mode holds against the size it launches with.
+// encrypt_pair: the pair encoder's two f64 half-planes; the NTT plane and the transpose region end below the parked
+// plaintext (static_asserts of encrypt_tail), which ends N words behind kPairParkWords.
+template <int LOGN>
+constexpr size_t pair_lds_extent()
+{
+    using G = XformGeom<LOGN>;
+    return std::max((size_t)G::SLOTS * sizeof(double), (kPairParkWords + (size_t)G::N) * sizeof(uint32_t));
+}
+// encrypt_pair2: the same half-planes, two NTT planes, the transpose region from word 0
+template <int LOGN, int MODE>
+constexpr size_t pair2_lds_extent()
+{
+    using G = XformGeom<LOGN>;
+    return std::max(std::max((size_t)G::SLOTS * sizeof(double), (size_t)2 * G::SLOTS * sizeof(uint32_t)),
+                    (size_t)(G::N / 16) * enc_quad_stride<MODE>() * sizeof(uint32_t));
+}
+
 // two plaintexts per workgroup (encrypt_pair)
 template <int LOGN, int MODE>
 constexpr bool enc_pairs()
@@ -785,7 +952,10 @@ __device__ __forceinline__ void encode_encrypt_fast(const DevParams &P, const De
                                                     const KeyRing &R, unsigned char *smem)
 {
     if constexpr (enc_pairs<LOGN, MODE>())
-        encrypt_pair<LOGN, MODE, KEYED>(P, T, A, R, (size_t)2 * blockIdx.x, (size_t)2 * blockIdx.x + 1 < A.count, smem);
+    {
+        const size_t bA = A.first + (size_t)2 * blockIdx.x;
+        encrypt_pair<LOGN, MODE, KEYED>(P, T, A, R, bA, bA + 1 < A.count, smem);
+    }
     else
         encrypt_one<LOGN, MODE, false, KEYED>(P, T, A, R, blockIdx.x, smem);
 }
@@ -821,6 +991,17 @@ void k_encode_encrypt_general(DevParams P, DevTables T, EncArgs A)
         encrypt_one<LOGN, MODE, true>(P, T, A, KeyRing{}, A.general[1 + i], smem);
         __syncthreads();
     }
+}
+
+// the two-way pair form (encrypt_pair2): fast, unkeyed, n = 4096 symmetric / encode-only; workgroup i takes the plaintexts
+// 2 i and 2 i + 1.  Three workgroups per CU.
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(XformGeom<LOGN>::THREADS, 3)
+void k_encode_encrypt_pair2(DevParams P, DevTables T, EncArgs A)
+{
+    static_assert(3 * (pair2_lds_extent<LOGN, MODE>() + 256) <= 160 * 1024, "three workgroups per CU fit the 160 KiB of LDS");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    encrypt_pair2<LOGN, MODE>(P, T, A, (size_t)2 * blockIdx.x, smem);
 }
 
 // keyed twins (symmetric / public-key modes): the same bodies, key rows of record b from ring key R.idx[b]
@@ -1551,7 +1732,12 @@ static hipError_t launch_enc_mode(const DevParams &P, const DevTables &T, const 
     if (e != hipSuccess) return e;
     EncArgs Af = A;
     Af.count   = B;
-    if (enc_pairs<LOGN, MODE>()) shmem_fast = std::max(shmem_fast, (kPairParkWords + (size_t)G::N) * sizeof(uint32_t));
+    Af.first   = 0;
+    if (enc_pairs<LOGN, MODE>())
+    {
+        shmem_fast = std::max(shmem_fast, (kPairParkWords + (size_t)G::N) * sizeof(uint32_t));
+        if (shmem_fast < pair_lds_extent<LOGN>()) return hipErrorInvalidValue;
+    }
     const unsigned grid_fast = (unsigned)(enc_pairs<LOGN, MODE>() ? (B + 1) / 2 : B);   // two plaintexts per workgroup
     // the plaintexts the fast form declined (normally none: the workgroups read a zero count and leave)
     const dim3 fast(grid_fast), gen((unsigned)std::min<size_t>(B, (size_t)4 * cus_or_default(P.num_cus))), block(G::THREADS);
@@ -1562,6 +1748,26 @@ static hipError_t launch_enc_mode(const DevParams &P, const DevTables &T, const 
             e = launch(k_encode_encrypt_keyed<LOGN, MODE>, fast, block, shmem_fast, st, P, T, Af, *ring);
             if (e != hipSuccess) return e;
             return launch(k_encode_encrypt_general_keyed<LOGN, MODE>, gen, block, shmem_gen, st, P, T, A, *ring);
+        }
+    }
+    if constexpr (enc_pairs<LOGN, MODE>())
+    {
+        // The whole pairs of a fast, unkeyed launch take the two-way pair form; an odd last plaintext takes the one-plane
+        // form, and so does everything under kEncFlagOnePlane (A.debug_flags: the forms are bit-identical).
+        if (!(A.debug_flags & kEncFlagOnePlane) && B >= 2)
+        {
+            // two u32 NTT planes = the encoder's two f64 half-planes; the transpose region lies inside them
+            const size_t shmem_pair2 = std::max(planes, (size_t)2 * G::SLOTS * sizeof(uint32_t));
+            if (shmem_pair2 < pair2_lds_extent<LOGN, MODE>()) return hipErrorInvalidValue;
+            e = launch(k_encode_encrypt_pair2<LOGN, MODE>, dim3((unsigned)(B / 2)), block, shmem_pair2, st, P, T, Af);
+            if (e != hipSuccess) return e;
+            if (B & 1)
+            {
+                Af.first = B - 1;
+                e = launch(k_encode_encrypt<LOGN, MODE>, dim3(1), block, shmem_fast, st, P, T, Af);
+                if (e != hipSuccess) return e;
+            }
+            return launch(k_encode_encrypt_general<LOGN, MODE>, gen, block, shmem_gen, st, P, T, A);
         }
     }
     e = launch(k_encode_encrypt<LOGN, MODE>, fast, block, shmem_fast, st, P, T, Af);

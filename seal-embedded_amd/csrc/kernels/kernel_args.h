@@ -25,7 +25,12 @@ struct EncArgs
                          // residue rows
     size_t count;        // fused kernel: plaintexts of the launch (set by the launcher: n = 4096 symmetric /
                          // encode-only workgroups take two plaintexts each)
+    size_t first;        // fused kernel, pair forms: the first plaintext of workgroup 0 (set by the launcher)
+    uint32_t debug_flags;   // form selection for tests / A/B runs (results are bit-identical): kEncFlagOnePlane
 };
+// EncArgs::debug_flags: the fast unkeyed n = 4096 symmetric / encode-only launches keep the one-plane pair form
+// (k_encode_encrypt) instead of the two-way form (k_encode_encrypt_pair2)
+constexpr uint32_t kEncFlagOnePlane = 8192;
 struct UniformArgs
 {
     const uint8_t *seeds;

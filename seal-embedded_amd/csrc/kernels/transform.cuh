@@ -633,6 +633,81 @@ __device__ __forceinline__ void ntt_tiles3(uint32_t (&x)[16], uint32_t (&y)[16],
 }
 
 // ------------------------------------------------------------------------------------------
+// Two forward NTTs mod the same prime at once (the symmetric / encode-only pair kernel: the two plaintexts of a
+// workgroup, encode_encrypt.hip, encrypt_pair2_tail): the two-array form of the three-way transform above.  Two LDS
+// planes, every root pair loaded once for two butterflies, one barrier pair per exchange.
+// ------------------------------------------------------------------------------------------
+template <int LOGN, int C_FROM, int C_TO>
+__device__ __forceinline__ void redeal2(uint32_t (&a)[16], uint32_t (&b)[16], uint32_t *lds, int t)
+{
+    constexpr int SL = XformGeom<LOGN>::SLOTS;
+    uint32_t *wr = lds + lds_slot<C_FROM, C_TO>(tile_index<C_FROM>(t, 0));
+    static_for<0, 16>([&](auto ec) {
+        constexpr int e = decltype(ec)::value;
+        constexpr int s = lds_slot<C_FROM, C_TO>(e << C_FROM);
+        wr[s] = a[e], wr[SL + s] = b[e];
+    });
+    __syncthreads();
+    const uint32_t *rd = lds + lds_slot<C_FROM, C_TO>(tile_index<C_TO>(t, 0));
+    static_for<0, 16>([&](auto ec) {
+        constexpr int e = decltype(ec)::value;
+        constexpr int s = lds_slot<C_FROM, C_TO>(e << C_TO);
+        a[e] = rd[s], b[e] = rd[SL + s];
+    });
+    __syncthreads();
+}
+
+template <int LOGN, int C, int B_LO, int B_HI>
+__device__ __forceinline__ void ntt_pass2(uint32_t (&x)[16], uint32_t (&y)[16], const uint32_t *__restrict__ RW,
+                                          uint32_t q, uint32_t two_q, int t)
+{
+    constexpr int N = 1 << LOGN;
+    const int thi   = (C + 4 >= LOGN) ? 0 : (t >> C);
+    static_for<0, B_HI - B_LO>([&](auto sc) {
+        constexpr int b      = B_HI - 1 - decltype(sc)::value;  // descending
+        constexpr int h      = N >> (C + b + 1);
+        constexpr int groups = 1 << (3 - b);
+        static_for<0, groups>([&](auto gc) {
+            constexpr int g = decltype(gc)::value;
+            const int idx   = (C == 0) ? N + ((8 >> b) - 1 + g) * (N / 16) + t : h + ((thi << (3 - b)) | g);
+            const uint2 rw  = *reinterpret_cast<const uint2 *>(RW + 2 * idx);
+            static_for<0, (1 << b)>([&](auto rc) {
+                constexpr int e0 = (g << (b + 1)) | decltype(rc)::value;
+                constexpr int e1 = e0 | (1 << b);
+                ct_butterfly(x[e0], x[e1], rw.x, rw.y, q, two_q);
+                ct_butterfly(y[e0], y[e1], rw.x, rw.y, q, two_q);
+            });
+        });
+    });
+}
+
+template <int LOGN>
+__device__ __forceinline__ void ntt_tiles2(uint32_t (&x)[16], uint32_t (&y)[16], const uint32_t *__restrict__ RW,
+                                           uint32_t q, uint32_t *lds, int t)
+{
+    using G              = XformGeom<LOGN>;
+    const uint32_t two_q = q << 1;
+    constexpr int C0     = LOGN - 4;
+    constexpr int C1     = G::ntt_c(1);
+    ntt_pass2<LOGN, C0, 0, 4>(x, y, RW, q, two_q, t);
+    redeal2<LOGN, C0, C1>(x, y, lds, t);
+    ntt_pass2<LOGN, C1, 0, 4>(x, y, RW, q, two_q, t);
+    if constexpr (LOGN <= 12)
+    {
+        redeal2<LOGN, C1, 0>(x, y, lds, t);
+        ntt_pass2<LOGN, 0, 0, C1>(x, y, RW, q, two_q, t);
+    }
+    else
+    {
+        constexpr int C2 = G::ntt_c(2);
+        redeal2<LOGN, C1, C2>(x, y, lds, t);
+        ntt_pass2<LOGN, C2, 0, 4>(x, y, RW, q, two_q, t);
+        redeal2<LOGN, C2, 0>(x, y, lds, t);
+        ntt_pass2<LOGN, 0, 0, C2>(x, y, RW, q, two_q, t);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Verification side (used by k_decrypt_decode): inverse NTT and forward FFT, same tiling.
 // ------------------------------------------------------------------------------------------
 

@@ -792,6 +792,7 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
     ea.status  = d_status;
     ea.general = d_general;
     ea.compact = d_compact;
+    ea.debug_flags = debug_flags;
     // a from the shareable seed, written straight into c1 (ckks_sym.c:220)
     UniformArgs ua = uniform_args();
     ua.seeds       = d_share_seeds;
@@ -2510,6 +2511,7 @@ int Context::encode_ntt(const float *d_values, size_t B, uint32_t *d_out, int64_
         ea.pte     = d_pte;
         ea.status  = d_status;
         ea.general = d_general;
+        ea.debug_flags = debug_flags;
         stage_begin(3, st);
         SEAMD_HIP(launch_encode_encrypt(dp, dt, ea, kModeEncodeOnly, B, st));
         stage_end(st);

@@ -137,7 +137,7 @@ struct Context
     DevBuf<uint32_t> d_lc_part;   // [slabs][G S][np][n]
     DevBuf<uint8_t> d_lc_flag;    // [G S]
     uint32_t lincomb_split = 0;   // test hook (se_amd_set_lincomb_split): slices per output row, 0 = lincomb_slices
-    uint32_t debug_flags = 0;  // timing ablations of the uniform sampler (tests/tools only)
+    uint32_t debug_flags = 0;  // form selection of the samplers, pipelines and fused kernels (tests/tools only)
 
     // second stream: the CBD error sampler runs beside the uniform sampler (different seeds, no
     // data dependency); joined before the fused encode+encrypt kernel.

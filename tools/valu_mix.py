@@ -48,9 +48,12 @@ TRIPS = [("k_encode_encrypt", 3.0), ("k_encode_rns", 3.0), ("k_ntt_fuse", 1.0), 
 DEFAULT_TRIP = 12.0
 # source file -> (key bench.py looks up: "<kernel>@<workload mode or logn>", mangled-name fragment)
 KERNELS = {
-    "encode_encrypt": [("k_encode_encrypt@sym12", "k_encode_encryptILi12ELi0E"),
+    # (n = 4096 symmetric / encode-only: the stage runs the two-way pair form; the one-plane form beside it)
+    "encode_encrypt": [("k_encode_encrypt@sym12", "k_encode_encrypt_pair2ILi12ELi0E"),
                        ("k_encode_encrypt@asym12", "k_encode_encryptILi12ELi1E"),
-                       ("k_encode_encrypt@encode12", "k_encode_encryptILi12ELi2E"),
+                       ("k_encode_encrypt@encode12", "k_encode_encrypt_pair2ILi12ELi2E"),
+                       ("k_encode_encrypt_one_plane@sym12", "k_encode_encryptILi12ELi0E"),
+                       ("k_encode_encrypt_one_plane@encode12", "k_encode_encryptILi12ELi2E"),
                        ("k_encode_encrypt@sym10", "k_encode_encryptILi10ELi0E"),
                        ("k_encode_rns@sym14", "k_encode_rnsILi14ELb1E"), ("k_ntt_fuse@sym14", "k_ntt_fuseILi14ELi0E"),
                        ("k_encode_rns@sym13", "k_encode_rnsILi13ELb1E"), ("k_ntt_fuse@sym13", "k_ntt_fuseILi13ELi0E"),
