@@ -16,32 +16,18 @@ chunk reuses one set of stacks).  Key words, diagonal words and slabs are random
 one).  The engine clock is sampled (bench.ClockSampler) while the loops run.  Prints one JSON line; --out also writes it.
   python tools/ct_bsgs_sp_bench.py [--B 16384 --chunk 2048 --reps 10 --warmup 2 --out profiles/ct_bsgs_sp_bench.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--B", type=int, default=16384, help="resident records")
 ap.add_argument("--chunk", type=int, default=2048, help="records per chunk (the plan's workspace holds one)")
-ap.add_argument("--reps", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=2)
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=10, warmup=2)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_bsgs_sp_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_bsgs_sp_bench")
 N, NP = 4096, 3
 L = NP - 1
 LIFT = 1 << 18
@@ -49,24 +35,9 @@ B, BC = args.B, min(args.chunk, args.B)
 
 
 def timed(fns, reps, warmup):
-    """Median / min / max ms of each function, the functions alternating inside one loop; the clock summary."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(reps):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-    rep = lambda v: dict(ms=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4),
-                         reps=len(v), records_per_s=round(B / statistics.median(v) * 1e3))
-    return [rep(v) for v in ms], cs.summary()
+    """bs.timed with every list of milliseconds made a record."""
+    ms, clock = bs.timed(fns, reps, warmup)
+    return [bs.record(v, records_per_s=bs.per_s(B, v)) for v in ms], clock
 
 
 def measure(n1, n2):
@@ -76,12 +47,12 @@ def measure(n1, n2):
     assert low.moduli() == q[:L]
     gen = torch.Generator(device=dev)
     gen.manual_seed(n1)
-    rand = lambda *shape: torch.randint(0, min(q), shape, dtype=torch.int32, device=dev, generator=gen)
+    rand = lambda *shape: bs.slab(q, shape, dev, gen)
     f0, f1 = rand(B, NP, N), rand(B, NP, N)                    # the fresh records; their first L rows are the level-L ones
     c0, c1 = f0[:, :L].contiguous(), f1[:, :L].contiguous()
     o0, o1, r0, r1, t0, t1 = (torch.empty_like(c0) for _ in range(6))
     rng = np.random.default_rng(n1 + 100)
-    words = lambda rows: np.stack([rng.integers(0, q[i], (rows, N), dtype=np.uint32) for i in range(NP)], axis=1)
+    words = lambda rows: bs.key_words(rng, q, rows, N, NP)
     G = n1 * n2
     baby = [pkg.galois_element(N, b) for b in range(n1)]
     giant = [pkg.galois_element(N, n1 * g) for g in range(n2)]
@@ -181,9 +152,4 @@ result = dict(tool="ct_bsgs_sp_bench", device=torch.cuda.get_device_name(0), n=N
 torch.cuda.empty_cache()
 result["plan_16x16"] = measure(16, 16)
 result["plan_faster_than_a"] = all(result[k]["plan_over_a_ms"] < 1.0 for k in ("plan_8x8", "plan_16x16"))
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

@@ -15,54 +15,19 @@ residues (no secret key: no entry needs one).  The engine clock is sampled (benc
 No ratio is required: the figures are reported.  Prints one JSON line; --out also writes it.
   python tools/ct_dot_bench.py [--reps 20 --warmup 2 --configs 0,1 --out profiles/ct_dot_bench.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--configs", default="0,1", help="indices into CONFIGS")
 ap.add_argument("--pairs", type=int, default=0, help="override P of every configuration (a rehearsal at a small size)")
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=20, warmup=2)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_dot_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_dot_bench")
 CONFIGS = [dict(n=4096, primes=3, pairs=32768, m=(1, 8, 64)), dict(n=16384, primes=13, pairs=1024, m=(1, 8))]
-
-
-def timed(fns, reps, warmup, pairs):
-    """Median / min / max ms of each function, the functions alternating inside one loop; the clock summary."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(reps):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-    rep = lambda v: dict(ms=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4),
-                         reps=len(v), pairs_per_s=round(pairs / statistics.median(v) * 1e3))
-    return [rep(v) for v in ms], cs.summary()
 
 
 def run_config(cfg):
@@ -74,10 +39,9 @@ def run_config(cfg):
     assert low.moduli() == q[:L]
     gen = torch.Generator(device=dev)
     gen.manual_seed(13)
-    rand = lambda *shape: torch.randint(0, min(q), shape, dtype=torch.int32, device=dev, generator=gen)
-    a0, a1, b0, b1 = (rand(P, L, N) for _ in range(4))
+    a0, a1, b0, b1 = (bs.slab(q, (P, L, N), dev, gen) for _ in range(4))
     rng = np.random.default_rng(17)
-    words = lambda: np.stack([rng.integers(0, q[i], (NP - 1, N), dtype=np.uint32) for i in range(NP)], axis=1)
+    words = lambda: bs.key_words(rng, q, NP - 1, N, NP)
     ctx.set_relin_key_sp(words(), words())
     rec = L * N * 4                                                # bytes of one slab row of a record
     t = [torch.empty((P, L, N), dtype=torch.int32, device=dev) for _ in range(3)]     # the per-pair tensor, sides 3 and 4
@@ -110,7 +74,8 @@ def run_config(cfg):
             ctx.ct_relin_sp(*t, *r)
             low.ct_lincomb(r[0], res[3][0], r[1], res[3][1], row_ptr=ptr, idx=every)
 
-        sides, clock = timed([dot_sp, mul_sum, lazy, eager], max(args.reps, 3), args.warmup, P)
+        ms, clock = bs.timed([dot_sp, mul_sum, lazy, eager], max(args.reps, 3), args.warmup)
+        sides = [bs.record(v, pairs_per_s=bs.per_s(P, v)) for v in ms]
         same = lambda k: bool((res[0][0] == res[k][0]).all()) and bool((res[0][1] == res[k][1]).all())  # noqa: E731
         extra = [0, 3 * G * rec, 3 * P * rec + 3 * G * rec, 3 * P * rec + 2 * P * rec]
         names = ("dot_sp", "mul_sum_relin_sp", "mul_lincomb2_relin_sp", "mul_relin_sp_lincomb")
@@ -128,9 +93,4 @@ def run_config(cfg):
 
 result = dict(tool="ct_dot_bench", device=torch.cuda.get_device_name(0),
               configs=[run_config(CONFIGS[int(k)]) for k in args.configs.split(",")])
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

@@ -14,79 +14,42 @@ The engine clock is sampled (bench.ClockSampler) while each loop runs.  Prints o
   python tools/ct_galois_hoist_bench.py [--n 4096 --primes 3 --batch 65536 --batch-many 16384 --reps 20 --warmup 3
                                          --out FILE]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=3)
 ap.add_argument("--batch", type=int, default=65536)
 ap.add_argument("--batch-many", type=int, default=16384)
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=20, warmup=3)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_galois_hoist_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_galois_hoist_bench")
 n, L, B, Bm = args.n, args.primes, args.batch, args.batch_many
 G_MANY, WINDOW = 8, 8
 ctx = pkg.Context(n, L)                         # no secret key: no entry here needs one
 q = ctx.moduli()
-qmin = min(q)
 gen = torch.Generator(device=dev)
 gen.manual_seed(1)
 rng = np.random.default_rng(2)
 steps = list(range(1, G_MANY + 1))
 elts = [pkg.galois_element(n, s) for s in steps]
-keys = [np.stack([np.stack([rng.integers(0, q[i], (2 * L, n), dtype=np.uint32) for i in range(L)], axis=1)
-                  for _ in elts]) for _ in range(2)]
+keys = [np.stack([bs.key_words(rng, q, 2 * L, n, L) for _ in elts]) for _ in range(2)]
 ctx.set_galois_keys(elts, *keys)
 
 
-def timed(fns, reps, warmup):
-    """The contenders alternate inside one loop; -> per contender the list of milliseconds, and the clock summary."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(max(reps, 10)):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-    return ms, cs.summary()
-
-
 def report(v, records):
-    med = statistics.median(v)
-    return dict(ms=round(med, 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4), reps=len(v),
-                records_per_s=round(records / med * 1e3))
+    return bs.record(v, records_per_s=bs.per_s(records, v))
 
 
 result = dict(tool="ct_galois_hoist_bench", n=n, primes=L, device=torch.cuda.get_device_name(0))
 
 # ---- many form ----
-c0 = torch.randint(0, qmin, (Bm, L, n), dtype=torch.int32, device=dev, generator=gen)
-c1 = torch.randint(0, qmin, (Bm, L, n), dtype=torch.int32, device=dev, generator=gen)
+c0 = bs.slab(q, (Bm, L, n), dev, gen)
+c1 = bs.slab(q, (Bm, L, n), dev, gen)
 m0, m1 = (torch.empty((G_MANY, Bm, L, n), dtype=torch.int32, device=dev) for _ in range(2))
 
 
@@ -95,7 +58,7 @@ def many_singles():
         ctx.ct_galois(c0, c1, g, m0[e], m1[e])
 
 
-ms, clock = timed([lambda: ctx.ct_galois_many(c0, c1, elts, m0, m1), many_singles], args.reps, args.warmup)
+ms, clock = bs.timed([lambda: ctx.ct_galois_many(c0, c1, elts, m0, m1), many_singles], max(args.reps, 10), args.warmup)
 result["many"] = dict(B=Bm, G=G_MANY, steps=steps, many=report(ms[0], Bm), singles=report(ms[1], Bm), clock=clock)
 result["many"]["many_over_singles_ms"] = round(result["many"]["many"]["ms"] / result["many"]["singles"]["ms"], 3)
 del c0, c1, m0, m1
@@ -104,7 +67,7 @@ torch.cuda.empty_cache()
 # ---- sum form ----
 cur0, cur1, nxt0, nxt1 = (torch.empty((2 * B, L, n), dtype=torch.int32, device=dev) for _ in range(4))
 for t in (cur0, cur1):
-    t[:B] = torch.randint(0, qmin, (B, L, n), dtype=torch.int32, device=dev, generator=gen)
+    t[:B] = bs.slab(q, (B, L, n), dev, gen)
 s0, s1 = (torch.empty((B, L, n), dtype=torch.int32, device=dev) for _ in range(2))
 row_ptr = torch.arange(0, 2 * B + 1, 2, dtype=torch.int32, device=dev)
 idx = torch.stack([torch.arange(B, dtype=torch.int32, device=dev), torch.arange(B, 2 * B, dtype=torch.int32, device=dev)],
@@ -126,16 +89,11 @@ def sum_singles():
         ctx.ct_galois(cur0[:B], cur1[:B], g, s0, s1)
 
 
-ms, clock = timed([lambda: ctx.ct_galois_sum(cur0[:B], cur1[:B], window, s0, s1, add_input=True), rounds, sum_singles],
-                  args.reps, args.warmup)
+ms, clock = bs.timed([lambda: ctx.ct_galois_sum(cur0[:B], cur1[:B], window, s0, s1, add_input=True), rounds,
+                      sum_singles], max(args.reps, 10), args.warmup)
 result["sum"] = dict(B=B, G=WINDOW - 1, add_input=True, sum=report(ms[0], B), rounds=report(ms[1], B),
                      singles=report(ms[2], B), clock=clock)
 result["sum"]["sum_over_rounds_ms"] = round(result["sum"]["sum"]["ms"] / result["sum"]["rounds"]["ms"], 3)
 result["sum"]["sum_over_singles_ms"] = round(result["sum"]["sum"]["ms"] / result["sum"]["singles"]["ms"], 3)
 ctx.close()
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

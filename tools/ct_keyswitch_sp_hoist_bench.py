@@ -18,31 +18,17 @@ diagonal words and slabs are random residues (no secret key: no entry needs one)
 (bench.ClockSampler) while the loop runs.  Prints one JSON line; --out also writes it.
   python tools/ct_keyswitch_sp_hoist_bench.py [--shapes 4096x3:65536 16384x13:2048 --reps 20 --warmup 3 --out FILE]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", nargs="*", default=["4096x3:65536", "16384x13:2048"], help="n x np : resident records")
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=20, warmup=3)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_keyswitch_sp_hoist_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_keyswitch_sp_hoist_bench")
 G = 7
 
 
@@ -52,10 +38,9 @@ def measure(n, npr, B):
     low = pkg.Context(n, L)                                    # ct_lincomb on level-L records: rows of L n words
     q = ctx.moduli()
     assert low.moduli() == q[:L]
-    qmin = min(q)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
-    rand = lambda *shape: torch.randint(0, qmin, shape, dtype=torch.int32, device=dev, generator=gen)
+    rand = lambda *shape: bs.slab(q, shape, dev, gen)
     f0, f1 = rand(B, npr, n), rand(B, npr, n)                  # fresh records, level np
     c0, c1 = torch.empty((B, L, n), dtype=torch.int32, device=dev), torch.empty((B, L, n), dtype=torch.int32, device=dev)
     ctx.ct_drop_primes(f0, c0, f1, c1)
@@ -67,7 +52,7 @@ def measure(n, npr, B):
     r0[:B].copy_(c0)
     r1[:B].copy_(c1)
     rng = np.random.default_rng(2)
-    words = lambda rows: np.stack([rng.integers(0, q[i], (rows, n), dtype=np.uint32) for i in range(npr)], axis=1)
+    words = lambda rows: bs.key_words(rng, q, rows, n, npr)
     elts = [pkg.galois_element(n, s) for s in range(1, G + 1)]
     ctx.set_galois_keys(elts, np.stack([words(2 * npr) for _ in elts]), np.stack([words(2 * npr) for _ in elts]))
     ctx.set_galois_keys_sp(elts, np.stack([words(npr - 1) for _ in elts]), np.stack([words(npr - 1) for _ in elts]))
@@ -105,38 +90,19 @@ def measure(n, npr, B):
     names = ("sum_sp", "a_seven_single_calls_and_sum", "b_today_lift_sum_rescale", "lintrans_sp",
              "d_today_lift_lintrans_rescale")
     fns = [sum_sp, a_single, b_today, lintrans_sp, d_today]
-    for _ in range(args.warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
+    ms, clock = bs.timed(fns, max(args.reps, 10), args.warmup)
     # the seven single calls and their sum give what the definition says they may not: another rounding
     same = bool((a0 == s0).all())
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(max(args.reps, 10)):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-
-    def report(v):
-        med = statistics.median(v)
-        return dict(ms=round(med, 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4), reps=len(v),
-                    records_per_s=round(B / med * 1e3))
-
     r = dict(n=n, primes=npr, level=L, B=B, G=G, single_calls_equal_the_sum_form=same)
     for name, v in zip(names, ms):
-        r[name] = report(v)
+        r[name] = bs.record(v, records_per_s=bs.per_s(B, v))
     ratio = lambda x, y: round(r[x]["ms"] / r[y]["ms"], 3)
     r["sum_sp_over_a_ms"] = ratio("sum_sp", "a_seven_single_calls_and_sum")
     r["sum_sp_over_b_ms"] = ratio("sum_sp", "b_today_lift_sum_rescale")
     r["lintrans_sp_over_sum_sp_ms"] = ratio("lintrans_sp", "sum_sp")
     r["lintrans_sp_over_d_ms"] = ratio("lintrans_sp", "d_today_lift_lintrans_rescale")
     r["sum_sp_faster_than_the_calls_it_replaces"] = r["sum_sp"]["ms"] < r["a_seven_single_calls_and_sum"]["ms"]
-    r["clock"] = cs.summary()
+    r["clock"] = clock
     plan_sp.close()
     plan.close()
     low.close()
@@ -150,9 +116,4 @@ for sh in args.shapes:
     n, npr = (int(v) for v in shape.split("x"))
     result["shapes"].append(measure(n, npr, int(B)))
     torch.cuda.empty_cache()
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

@@ -9,66 +9,37 @@
 The two sides of a pair alternate inside one loop.  Prints one JSON line; --out also writes it to a file.
   python tools/ct_mul_bench.py [--n 4096 --primes 3 --batch 65536 --reps 20 --warmup 3 --out FILE]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=3)
 ap.add_argument("--batch", type=int, default=65536)
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=20, warmup=3)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-
-if not torch.cuda.is_available():
-    sys.exit("ct_mul_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_mul_bench")
 n, L, B = args.n, args.primes, args.batch
 slab_words = B * L * n
 slab_bytes = slab_words * 4
 ctx = pkg.Context(n, L)                         # no secret key: neither entry needs one
 q = ctx.moduli()
-qmin = min(q)
 gen = torch.Generator(device=dev)
 gen.manual_seed(1)
-c0 = torch.randint(0, qmin, (B, L, n), dtype=torch.int32, device=dev, generator=gen)
-c1 = torch.randint(0, qmin, (B, L, n), dtype=torch.int32, device=dev, generator=gen)
+c0 = bs.slab(q, (B, L, n), dev, gen)
+c1 = bs.slab(q, (B, L, n), dev, gen)
 
 
 def timed(fns):
-    """Median-ready lists of milliseconds, one per function; the functions alternate inside every repetition."""
-    for _ in range(args.warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(max(args.reps, 10)):
-        for k, fn in enumerate(fns):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
-    return ms
+    """The lists of milliseconds, one per function; the clock is not sampled."""
+    return bs.timed(fns, max(args.reps, 10), args.warmup, clock=False)[0]
 
 
 def report(ms, nbytes):
-    med = statistics.median(ms)
-    return dict(ms=round(med, 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), reps=len(ms), bytes=nbytes,
-                tb_per_s=round(nbytes / med / 1e9, 3))
+    return bs.record(ms, bytes=nbytes, tb_per_s=bs.tb_per_s(nbytes, ms))
 
 
 result = dict(tool="ct_mul_bench", n=n, primes=L, B=B, device=torch.cuda.get_device_name(0))
@@ -77,7 +48,7 @@ result = dict(tool="ct_mul_bench", n=n, primes=L, B=B, device=torch.cuda.get_dev
 t0, t1, t2 = (torch.empty_like(c0) for _ in range(3))
 st = torch.zeros(B, dtype=torch.uint8, device=dev)
 half = (7 * slab_words) // 2
-src = torch.randint(0, qmin, (half,), dtype=torch.int32, device=dev, generator=gen)
+src = bs.slab(q, (half,), dev, gen)
 dst = torch.empty_like(src)
 mul, copy = timed([lambda: ctx.ct_mul(c0, c1, c0, c1, t0, t1, t2, status=st), lambda: dst.copy_(src)])
 assert bool((st == 1).all())
@@ -88,10 +59,10 @@ del src, dst
 
 # ---- relin against the stage operators it replaces
 rng = np.random.default_rng(2)
-key = [np.stack([rng.integers(0, q[i], (2 * L, n), dtype=np.uint32) for i in range(L)], axis=1) for _ in range(2)]
+key = [bs.key_words(rng, q, 2 * L, n, L) for _ in range(2)]
 ctx.set_relin_key(*key)
 m0, m1 = torch.empty_like(c0), torch.empty_like(c0)
-rows = torch.randint(0, qmin, (B, n), dtype=torch.int32, device=dev, generator=gen)
+rows = bs.slab(q, (B, n), dev, gen)
 
 
 def stage_ops():
@@ -109,9 +80,4 @@ result["stage_ops"]["calls"] = dict(intt=L, ntt=2 * L * L, rows_per_call=B)
 result["relin_over_stage_ops_ms"] = round(result["relin"]["ms"] / result["stage_ops"]["ms"], 3)
 
 ctx.close()
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

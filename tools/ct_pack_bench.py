@@ -15,53 +15,24 @@ secret key: no entry needs one).  The engine clock is sampled (bench.ClockSample
 line; --out also writes it.
   python tools/ct_pack_bench.py [--reps 20 --warmup 2 --small --out profiles/ct_pack_bench.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--small", action="store_true", help="1/16 of the records of every shape (a quick look)")
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=20, warmup=2)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_pack_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_pack_bench")
 SHAPES = [(4096, 3, 65536, (1, 8, 16)), (16384, 13, 2048, (8,))]      # n, np, records, row lengths
 
 
 def timed(fns, reps, warmup, B):
-    """Median / min / max ms of each function, the functions alternating inside one loop; the clock summary."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(reps):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-    rep = lambda v: dict(ms=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4),  # noqa: E731
-                         reps=len(v), records_per_s=round(B / statistics.median(v) * 1e3))
-    return [rep(v) for v in ms], cs.summary()
+    """bs.timed with every list of milliseconds made a record."""
+    ms, clock = bs.timed(fns, reps, warmup)
+    return [bs.record(v, records_per_s=bs.per_s(B, v)) for v in ms], clock
 
 
 result = dict(tool="ct_pack_bench", device=torch.cuda.get_device_name(0), cases=[])
@@ -76,8 +47,8 @@ for N, NP, B, lengths in SHAPES:
     assert low.moduli() == q[:L]
     gen = torch.Generator(device=dev)
     gen.manual_seed(7)
-    c0 = torch.randint(0, min(q), (B, L, N), dtype=torch.int32, device=dev, generator=gen)
-    c1 = torch.randint(0, min(q), (B, L, N), dtype=torch.int32, device=dev, generator=gen)
+    c0 = bs.slab(q, (B, L, N), dev, gen)
+    c1 = bs.slab(q, (B, L, N), dev, gen)
     rng = np.random.default_rng(11)
     for m in lengths:
         width = slots // m
@@ -121,9 +92,4 @@ for N, NP, B, lengths in SHAPES:
     ctx.close()
     low.close()
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

@@ -16,55 +16,26 @@ re-reads every dropped term and the sum.  Slabs and key words are random residue
 The engine clock is sampled (bench.ClockSampler) while the loops run.  Prints one JSON line; --out also writes it.
   python tools/ct_poly_bench.py [--reps 20 --warmup 2 --small --out profiles/ct_poly_bench.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--small", action="store_true", help="1/16 of the records of every shape (a quick look)")
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=20, warmup=2)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_poly_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_poly_bench")
 SHAPES = [(4096, 3, 2, 65536, (4, 15)), (16384, 13, 12, 2048, (4, 15))]      # n, np, primes, records, term counts
 PLAN = (8192, 6, 5, 4096)                                                     # n, np, L, records
 LOGISTIC7 = [0.5, 0.25, 0.0, -1.0 / 48, 0.0, 1.0 / 480, 0.0, -17.0 / 80640]
 
 
 def timed(fns, reps, warmup, B):
-    """Median / min / max ms of each function, the functions alternating inside one loop; the clock summary."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(reps):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-    rep = lambda v: dict(ms=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4),  # noqa: E731
-                         reps=len(v), records_per_s=round(B / statistics.median(v) * 1e3))
-    return [rep(v) for v in ms], cs.summary()
+    """bs.timed with every list of milliseconds made a record."""
+    ms, clock = bs.timed(fns, reps, warmup)
+    return [bs.record(v, records_per_s=bs.per_s(B, v)) for v in ms], clock
 
 
 result = dict(tool="ct_poly_bench", device=torch.cuda.get_device_name(0), cases=[])
@@ -77,8 +48,7 @@ for N, NP, P, B, counts in SHAPES:
     low = pkg.Context(N, P)                                    # ct_lincomb on level-P records: rows of P n words
     q = ctx.moduli()
     assert low.moduli() == q[:P]
-    slab = lambda rows, lead=B: torch.randint(0, min(q), (lead, rows, N), dtype=torch.int32, device=dev,  # noqa: E731
-                                              generator=gen)
+    slab = lambda rows: bs.slab(q, (B, rows, N), dev, gen)  # noqa: E731
     for T in counts:
         levels = [P if t % 3 == 0 else min(P + 1, NP) for t in range(T)]
         terms0, terms1 = [slab(lv) for lv in levels], [slab(lv) for lv in levels]
@@ -120,11 +90,10 @@ if args.small:
 ctx = pkg.Context(N, NP)
 q = ctx.moduli()
 rng = np.random.default_rng(13)
-words = lambda: np.stack([rng.integers(0, q[i], (NP - 1, N), dtype=np.uint32) for i in range(NP)], axis=1)  # noqa: E731
-ctx.set_relin_key_sp(words(), words())
+ctx.set_relin_key_sp(bs.key_words(rng, q, NP - 1, N, NP), bs.key_words(rng, q, NP - 1, N, NP))
 plan = pkg.poly_create(N, NP, L, LOGISTIC7, float(q[L - 1]), ctx.scale())
-c0 = torch.randint(0, min(q), (B, L, N), dtype=torch.int32, device=dev, generator=gen)
-c1 = torch.randint(0, min(q), (B, L, N), dtype=torch.int32, device=dev, generator=gen)
+c0 = bs.slab(q, (B, L, N), dev, gen)
+c1 = bs.slab(q, (B, L, N), dev, gen)
 out_primes = plan.result()[0]
 o0, o1 = (torch.empty((B, out_primes, N), dtype=torch.int32, device=dev) for _ in range(2))
 work = torch.empty((plan.workspace_bytes(B) // 4,), dtype=torch.int32, device=dev)
@@ -134,9 +103,4 @@ result["plan"] = dict(n=N, primes=NP, level=L, B=B, degree=7, powers=[t["power"]
 plan.close()
 ctx.close()
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

@@ -12,32 +12,18 @@ Key words and slabs are random residues (no secret key: no entry needs one).  Th
 (bench.ClockSampler) while the loops run.  Prints one JSON line; --out also writes it.
   python tools/ct_switch_bench.py [--B 65536 --K 64 --reps 40 --warmup 3 --out profiles/ct_switch_bench.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--B", type=int, default=65536, help="resident records (a multiple of 64)")
 ap.add_argument("--K", type=int, default=64, help="keys in the ring")
-ap.add_argument("--reps", type=int, default=40)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=40, warmup=3)
 args = ap.parse_args()
 
 import numpy as np
-import torch
 
-import __graft_entry__ as ge
-from bench import ClockSampler
-
-if not torch.cuda.is_available():
-    sys.exit("ct_switch_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("ct_switch_bench")
 N, NP = 4096, 3
 L = NP - 1
 B, K = args.B, args.K
@@ -45,24 +31,9 @@ assert B % 64 == 0
 
 
 def timed(fns, reps, warmup):
-    """Median / min / max ms of each function, the functions alternating inside one loop; the clock summary."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    with ClockSampler(torch, 0) as cs:
-        for _ in range(reps):
-            for k, fn in enumerate(fns):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-    rep = lambda v: dict(ms=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4),
-                         reps=len(v), records_per_s=round(B / statistics.median(v) * 1e3))
-    return [rep(v) for v in ms], cs.summary()
+    """bs.timed with every list of milliseconds made a record."""
+    ms, clock = bs.timed(fns, reps, warmup)
+    return [bs.record(v, records_per_s=bs.per_s(B, v)) for v in ms], clock
 
 
 ctx = pkg.Context(N, NP)
@@ -71,8 +42,7 @@ q = ctx.moduli()
 assert low.moduli() == q[:L]
 gen = torch.Generator(device=dev)
 gen.manual_seed(7)
-rand = lambda *shape: torch.randint(0, min(q), shape, dtype=torch.int32, device=dev, generator=gen)
-c0, c1 = rand(B, L, N), rand(B, L, N)
+c0, c1 = bs.slab(q, (B, L, N), dev, gen), bs.slab(q, (B, L, N), dev, gen)
 zero = torch.zeros_like(c1)
 o0, o1, s0, s1 = (torch.empty_like(c0) for _ in range(4))
 rng = np.random.default_rng(11)
@@ -119,9 +89,4 @@ for m in (8, 64):
 
 ctx.close()
 low.close()
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

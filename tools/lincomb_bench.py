@@ -8,63 +8,37 @@ Both slabs (c0, c1) in every call.  Algorithmic bytes = inputs read once per use
 line; --out also writes it to a file.
   python tools/lincomb_bench.py [--n 4096 --primes 3 --batch 65536 --reps 50 --warmup 5 --split 0 --out FILE]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=3)
 ap.add_argument("--batch", type=int, default=65536)
-ap.add_argument("--reps", type=int, default=50)
-ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--split", type=int, default=0, help="se_amd_set_lincomb_split (0 = automatic)")
 ap.add_argument("--only", default="", help="comma list of a,b,c (default all); the copy always runs")
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=50, warmup=5)
 args = ap.parse_args()
 
-import torch
-
-import __graft_entry__ as ge
-
-if not torch.cuda.is_available():
-    sys.exit("lincomb_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("lincomb_bench")
 n, npr, B = args.n, args.primes, args.batch
 row_bytes = npr * n * 4
 ctx = pkg.Context(n, npr)                       # no key: the entry needs none
-qmin = min(ctx.moduli())
+q = ctx.moduli()
 gen = torch.Generator(device=dev)
 gen.manual_seed(1)
-c0 = torch.randint(0, qmin, (B, npr, n), dtype=torch.int32, device=dev, generator=gen)
-c1 = torch.randint(0, qmin, (B, npr, n), dtype=torch.int32, device=dev, generator=gen)
+c0 = bs.slab(q, (B, npr, n), dev, gen)
+c1 = bs.slab(q, (B, npr, n), dev, gen)
 ctx.set_lincomb_split(args.split)
 
 
 def timed(fn):
-    for _ in range(args.warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(max(args.reps, 50)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
+    """The list of milliseconds of one function; the clock is not sampled."""
+    return bs.timed([fn], max(args.reps, 50), args.warmup, clock=False)[0][0]
 
 
 def report(ms, nbytes):
-    med = statistics.median(ms)
-    return dict(ms=round(med, 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), reps=len(ms), bytes=nbytes,
-                tb_per_s=round(nbytes / med / 1e9, 3))
+    return bs.record(ms, bytes=nbytes, tb_per_s=bs.tb_per_s(nbytes, ms))
 
 
 result = dict(tool="lincomb_bench", n=n, primes=npr, B=B, split=args.split, device=torch.cuda.get_device_name(0))
@@ -108,9 +82,4 @@ for k in ("a", "b", "c"):
     if k in result:
         result[k]["ratio_to_copy"] = round(result[k]["tb_per_s"] / result["copy"]["tb_per_s"], 3)
 ctx.close()
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)

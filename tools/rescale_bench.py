@@ -8,65 +8,37 @@
 The two sides of a pair alternate inside one loop.  Prints one JSON line; --out also writes it to a file.
   python tools/rescale_bench.py [--n 4096 --primes 3 --batch 65536 --reps 50 --warmup 5 --out FILE]"""
 import argparse
-import json
-import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+import bench_support as bs
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=3)
 ap.add_argument("--batch", type=int, default=65536)
-ap.add_argument("--reps", type=int, default=50)
-ap.add_argument("--warmup", type=int, default=5)
-ap.add_argument("--out", default="")
+bs.add_common_args(ap, reps=50, warmup=5)
 args = ap.parse_args()
 
-import torch
-
-import __graft_entry__ as ge
-
-if not torch.cuda.is_available():
-    sys.exit("rescale_bench needs a GPU")
-pkg = ge.load_package()
-dev = torch.device("cuda:0")
+pkg, torch, dev = bs.start("rescale_bench")
 n, L, B = args.n, args.primes, args.batch
 if L < 2:
     sys.exit("the rescale needs at least two primes")
 row_bytes = L * n * 4
 ctx = pkg.Context(n, L)                         # no key: neither entry needs one
-qmin = min(ctx.moduli())
+q = ctx.moduli()
 gen = torch.Generator(device=dev)
 gen.manual_seed(1)
-c0 = torch.randint(0, qmin, (B, L, n), dtype=torch.int32, device=dev, generator=gen)
-c1 = torch.randint(0, qmin, (B, L, n), dtype=torch.int32, device=dev, generator=gen)
+c0 = bs.slab(q, (B, L, n), dev, gen)
+c1 = bs.slab(q, (B, L, n), dev, gen)
 
 
 def timed(fns):
-    """Median-ready lists of milliseconds, one per function; the functions alternate inside every repetition."""
-    for _ in range(args.warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(max(args.reps, 20)):
-        for k, fn in enumerate(fns):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
-    return ms
+    """The lists of milliseconds, one per function; the clock is not sampled."""
+    return bs.timed(fns, max(args.reps, 20), args.warmup, clock=False)[0]
 
 
 def report(ms, nbytes):
-    med = statistics.median(ms)
-    return dict(ms=round(med, 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), reps=len(ms), bytes=nbytes,
-                tb_per_s=round(nbytes / med / 1e9, 3))
+    return bs.record(ms, bytes=nbytes, tb_per_s=bs.tb_per_s(nbytes, ms))
 
 
 result = dict(tool="rescale_bench", n=n, primes=L, B=B, device=torch.cuda.get_device_name(0))
@@ -74,8 +46,8 @@ result = dict(tool="rescale_bench", n=n, primes=L, B=B, device=torch.cuda.get_de
 # ---- rescale against the stage operators
 r0 = torch.empty((B, L - 1, n), dtype=torch.int32, device=dev)
 r1 = torch.empty_like(r0)
-last = torch.randint(0, qmin, (2 * B, n), dtype=torch.int32, device=dev, generator=gen)
-lower = torch.randint(0, qmin, (2 * B * (L - 1), n), dtype=torch.int32, device=dev, generator=gen)
+last = bs.slab(q, (2 * B, n), dev, gen)
+lower = bs.slab(q, (2 * B * (L - 1), n), dev, gen)
 fused, intt, ntt = timed([lambda: ctx.ct_rescale(c0, r0, c1, r1),
                           lambda: ctx.intt(L - 1, last),
                           lambda: ctx.ntt(0, lower)])
@@ -89,7 +61,7 @@ result["rescale_over_stage_sum"] = round(result["rescale"]["ms"] / stage_sum, 3)
 del r0, r1, last, lower
 
 # ---- plaintext product against a copy of one slab
-pt = torch.randint(0, qmin, (B, L, n), dtype=torch.int32, device=dev, generator=gen)
+pt = bs.slab(q, (B, L, n), dev, gen)
 o0 = torch.empty_like(c0)
 o1 = torch.empty_like(c0)
 st = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -101,9 +73,4 @@ result["mul_plain_over_copy_ms"] = round(result["mul_plain"]["ms"] / result["cop
 result["mul_plain_rate_over_copy_rate"] = round(result["mul_plain"]["tb_per_s"] / result["copy_one_slab"]["tb_per_s"], 3)
 
 ctx.close()
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
+bs.emit(result, args.out)
