@@ -89,6 +89,27 @@ def lift_expect(o, slab, weight):
     return ((slab.astype(np.uint64) * np.uint64(weight)) % qv).astype(np.uint32)
 
 
+def lincomb_expect(slab, q, rows):
+    """slab uint32 [B][np][n], q Python ints, rows = list of (indices, weights | None)  ->  uint32 [G][np][n].
+    sum_k (w_k % q) c[idx_k] % q, regrouped per distinct record: its coefficient sum_k (w_k % q) % q is a Python int
+    below 2^30, the products stay below 2^60 and are reduced one by one, and at most B < 2^34 of them are summed."""
+    npr, n = slab.shape[1], slab.shape[2]
+    qv = np.array(q, dtype=np.uint64)[:, None]
+    out = np.zeros((len(rows), npr, n), dtype=np.uint32)
+    for g, (idx, w) in enumerate(rows):
+        coef = {}
+        for k, i in enumerate(idx):
+            wk = 1 if w is None else int(w[k])
+            c = coef.setdefault(int(i), [0] * npr)
+            for j in range(npr):
+                c[j] = (c[j] + wk % q[j]) % q[j]
+        acc = np.zeros((npr, n), dtype=np.uint64)
+        for i, c in coef.items():
+            acc += (slab[i].astype(np.uint64) * np.array(c, dtype=np.uint64)[:, None]) % qv
+        out[g] = (acc % qv).astype(np.uint32)
+    return out
+
+
 # ---- rescale, digits and the digit key switch -----------------------------------------------------------------------
 def rescale_expect(o, slab):
     """slab uint32 [B][L][n] -> uint32 [B][L-1][n]: out[j] = (in[j] - NTT_j(delta mod q_j)) . q_last^-1 mod q_j with

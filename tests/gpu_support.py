@@ -17,6 +17,9 @@ second module needs moves here (device code) or to ct_model (definitions and inp
   run_galois_sp), each one call with two rows of sentinels behind each output; keyed_cases, the module-scoped fixture of
   the end-to-end tests, with step_elements, install_galois_keys, lift_records, rescale_records and encode_diagonals, the
   blocks those tests repeat.
+- batches at scale (tests/test_gpu_ct_scale.py; shown on the CPU by tests/test_tiled_support.py): tiled (K records repeated
+  to B on the device), assert_tiles (every record of a slab against its pattern record, on the device, with slab_position
+  in its report), tiled_row_ptr, tiled_idx, tiled_entries (CSR rows that repeat a local pattern per tile).
 - build_example, build_caller, run_example: plain-gcc programs of examples/ and tests/c/ linked against the product library.
 - check_host_tables: every setup-time table against the oracle and the golden digests (CPU suite and GPU box).
 """
@@ -423,6 +426,108 @@ def keyed_cases(env, request):
     yield get
     for c in cache.values():
         c["ctx"].close()
+
+
+# ---- K records tiled to a batch of B: built and compared on the device (tests/test_gpu_ct_scale.py) -------------------
+def as_tensor(env, a):
+    """A tensor on env["dev"] of a host array (dev_t) or of a tensor, which is returned as it is."""
+    return dev_t(env, a) if isinstance(a, np.ndarray) else a
+
+
+def tiled(env, base, B, out=None):
+    """base [K, ...] (a tensor on the device, or a host array that goes there) -> [B, ...] whose record b is base[b % K],
+    B a multiple of K, from one broadcast assignment into the [B / K, K, ...] view: no host slab.  `out`: a contiguous
+    view of a caller's buffer of that shape and type, which is written and returned."""
+    base = as_tensor(env, base)
+    K, rest = base.shape[0], tuple(base.shape[1:])
+    assert K >= 1 and B >= K and B % K == 0, (B, K)
+    if out is None:
+        out = env["torch"].empty((B,) + rest, dtype=base.dtype, device=base.device)
+    assert tuple(out.shape) == (B,) + rest and out.dtype == base.dtype and out.is_contiguous(), (out.shape, out.dtype)
+    out.view(B // K, K, *rest)[...] = base
+    return out
+
+
+def _bit_view(env, t):
+    """The same bytes as integers: floats compare by bit pattern (a NaN equals itself, -0.0 differs from 0.0)."""
+    torch = env["torch"]
+    return t.view({torch.float32: torch.int32, torch.float64: torch.int64}.get(t.dtype, t.dtype))
+
+
+def slab_position(record, words, size):
+    """Where record `record` of a slab of `words`-word records of `size`-byte words starts, against the three offsets at
+    which a narrow index wraps: byte 2^32, word 2^31 (an int) and word 2^32 (a uint32_t)."""
+    off = record * words
+    side = lambda past: "at or past" if past else "before"  # noqa: E731
+    return (f"starts at word {off} = byte {off * size} of the slab: {side(off * size >= 2 ** 32)} byte 2^32, "
+            f"{side(off >= 2 ** 31)} word 2^31, {side(off >= 2 ** 32)} word 2^32")
+
+
+def assert_tiles(env, got, exp, what, guard=None, chunk_bytes=1 << 30):
+    """Every record b of the device tensor got [B, ...] equals exp[b % K] (exp [K, ...], a tensor or a host array),
+    compared on the device bit for bit in chunks of whole tiles whose temporaries stay within about `chunk_bytes`; no
+    record is left out.  `guard`: the words behind the result, which must all still hold SENTINEL.  A mismatch names the
+    first bad record with its row and word, how many records differ, and where that record's first word lies relative
+    to byte 2^32, word 2^31 and word 2^32 of the slab."""
+    torch = env["torch"]
+    exp = _bit_view(env, as_tensor(env, exp)).contiguous()
+    got = _bit_view(env, got)
+    assert got.is_contiguous() and got.dtype == exp.dtype, (what, got.dtype, exp.dtype)
+    B, K = got.shape[0], exp.shape[0]
+    assert B % K == 0 and tuple(got.shape[1:]) == tuple(exp.shape[1:]), (what, tuple(got.shape), tuple(exp.shape))
+    words = max(1, exp[0].numel())                                       # words of one record
+    last = exp.shape[-1] if exp.dim() > 1 else 1                         # words of one row
+    # per compared word: one bool of the comparison and, for the broadcast, at most one word of `exp`
+    tiles_per_chunk = max(1, chunk_bytes // (K * words * (1 + exp.element_size())))
+    g3, e3 = got.view(B // K, K, words), exp.view(1, K, words)
+    bad = torch.zeros((B // K, K), dtype=torch.bool, device=got.device)
+    for t0 in range(0, B // K, tiles_per_chunk):
+        t1 = min(B // K, t0 + tiles_per_chunk)
+        bad[t0:t1] = (g3[t0:t1] != e3).any(dim=2)
+    bad = bad.view(B)
+    count = int(bad.sum())
+    if count:
+        first = int(torch.nonzero(bad)[0, 0])
+        diff = torch.nonzero(g3.view(B, words)[first] != e3.view(K, words)[first % K])
+        at = int(diff[0, 0])
+        raise AssertionError(
+            f"{what}: {count} of {B} records differ; first bad record {first} (tile {first // K}, pattern record "
+            f"{first % K}), row {at // last}, word {at % last}: got {int(g3.view(B, words)[first, at]):#x}, expected "
+            f"{int(e3.view(K, words)[first % K, at]):#x} ({int(diff.shape[0])} words of that record differ); the record "
+            + slab_position(first, words, exp.element_size()))
+    if guard is not None:
+        wrong = int((guard != SENTINEL).sum())
+        assert wrong == 0, f"{what}: {wrong} of the {guard.numel()} guard words behind the result are written"
+
+
+def tiled_row_ptr(env, local_ptr, tiles):
+    """CSR row_ptr of `tiles` copies of a pattern of R rows with local row_ptr `local_ptr` [R + 1] (local_ptr[0] == 0):
+    row g starts at (g // R) . nnz + local_ptr[g % R], built on the device -> int32 [tiles . R + 1]."""
+    torch = env["torch"]
+    lp = torch.as_tensor(np.asarray(local_ptr, dtype=np.int64), device=env["dev"])
+    R, nnz = lp.numel() - 1, int(local_ptr[-1])
+    assert R >= 1 and int(local_ptr[0]) == 0 and tiles * nnz < 2 ** 31, (R, nnz, tiles)
+    out = torch.empty(tiles * R + 1, dtype=torch.int64, device=env["dev"])
+    out[:tiles * R].view(tiles, R)[...] = torch.arange(tiles, device=env["dev"])[:, None] * nnz + lp[None, :R]
+    out[tiles * R] = tiles * nnz
+    return out.to(torch.int32)
+
+
+def tiled_idx(env, local_idx, K, tiles):
+    """CSR record indices of the same: entry k = (k // nnz) . K + local_idx[k % nnz], every local index below K, so that
+    a row of tile t reads records of tile t alone -> int32 [tiles . nnz]."""
+    torch = env["torch"]
+    li = torch.as_tensor(np.asarray(local_idx, dtype=np.int64), device=env["dev"])
+    assert li.numel() >= 1 and 0 <= int(li.min()) and int(li.max()) < K and tiles * K < 2 ** 31, (K, tiles)
+    out = torch.arange(tiles, device=env["dev"])[:, None] * K + li[None, :]
+    return out.reshape(-1).to(torch.int32)
+
+
+def tiled_entries(env, local, tiles):
+    """What a CSR entry carries beside its record index (eidx, weights) or a record carries beside its rows (key_idx):
+    the pattern's values as they are, repeated per tile -> [tiles . len(local)] of the pattern's own type."""
+    base = as_tensor(env, np.ascontiguousarray(local))
+    return tiled(env, base, tiles * base.shape[0])
 
 
 # ---- C callers ------------------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import vectors as V
+from ct_model import lincomb_expect
 from gpu_support import (NULL, SE_ERR_INVALD_ARGUMENT, SENTINEL, CEntry, assert_untouched, bits,  # noqa: F401
                          decode_expect, dev_t, dptr, encrypt_sym, env, expectation, host_u32, ntt_secret, run_decrypt,
                          stream_of)
@@ -18,27 +19,6 @@ ALL_MAX = (3, 17)              # the records whose residues are all q_j - 1
 
 
 # ---- the expectation -------------------------------------------------------------------------------------------------
-def lincomb_expect(slab, q, rows):
-    """slab uint32 [B][np][n], q Python ints, rows = list of (indices, weights | None)  ->  uint32 [G][np][n].
-    sum_k (w_k % q) c[idx_k] % q, regrouped per distinct record: its coefficient sum_k (w_k % q) % q is a Python int
-    below 2^30, the products stay below 2^60 and are reduced one by one, and at most B < 2^34 of them are summed."""
-    npr, n = slab.shape[1], slab.shape[2]
-    qv = np.array(q, dtype=np.uint64)[:, None]
-    out = np.zeros((len(rows), npr, n), dtype=np.uint32)
-    for g, (idx, w) in enumerate(rows):
-        coef = {}
-        for k, i in enumerate(idx):
-            wk = 1 if w is None else int(w[k])
-            c = coef.setdefault(int(i), [0] * npr)
-            for j in range(npr):
-                c[j] = (c[j] + wk % q[j]) % q[j]
-        acc = np.zeros((npr, n), dtype=np.uint64)
-        for i, c in coef.items():
-            acc += (slab[i].astype(np.uint64) * np.array(c, dtype=np.uint64)[:, None]) % qv
-        out[g] = (acc % qv).astype(np.uint32)
-    return out
-
-
 def spot_check(slab, q, rows, exp, rng):
     """The regrouped NumPy expectation against the issue's formula in plain Python integers, on a few elements."""
     npr, n = slab.shape[1], slab.shape[2]
