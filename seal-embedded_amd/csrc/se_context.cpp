@@ -697,11 +697,37 @@ void Context::collect_events()
     events.clear();
 }
 
+// The refusals of the whole-path entries: no key, then (for a batch that is not empty) a missing pointer.  The unkeyed
+// entries ask before they open a call scope, so that a refused call makes no runtime call at all (the scope's error path
+// drains the device); the *_impl functions ask again for the keyed entries, which arrive with a ring.
+static int refuse_sym(bool have_key, size_t B, const void *d_values, const void *d_share_seeds, const void *d_seeds,
+                      const void *d_c0, const void *d_c1)
+{
+    if (!have_key)
+    {
+        set_last_error("symmetric encryption needs a secret key (se_amd_set_secret_key)");
+        return kErrNoKey;
+    }
+    return B != 0 && (!d_values || !d_share_seeds || !d_seeds || !d_c0 || !d_c1) ? kErrInvalid : 0;
+}
+
+static int refuse_asym(bool have_key, size_t B, const void *d_values, const void *d_seeds, const void *d_c0,
+                       const void *d_c1)
+{
+    if (!have_key)
+    {
+        set_last_error("asymmetric encryption needs a public key (se_amd_set_public_key)");
+        return kErrNoKey;
+    }
+    return B != 0 && (!d_values || !d_seeds || !d_c0 || !d_c1) ? kErrInvalid : 0;
+}
+
 int Context::encrypt_sym(const float *d_values, size_t B, const uint8_t *d_share_seeds,
                          const uint8_t *d_seeds, uint32_t *d_c0, uint32_t *d_c1,
                          uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
+    if (int rc = refuse_sym(have_sk, B, d_values, d_share_seeds, d_seeds, d_c0, d_c1)) return rc;
     return call_scope(st, [&] {
         return encrypt_sym_impl(d_values, B, d_share_seeds, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st);
     });
@@ -715,6 +741,7 @@ int Context::encrypt_sym_seeded(const float *d_values, size_t B, const uint8_t *
                                 const uint8_t *d_seeds, uint32_t *d_c0, uint8_t *d_status, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
+    if (int rc = refuse_sym(have_sk, B, d_values, d_share_seeds, d_seeds, d_c0, d_c0)) return rc;
     SEAMD_HIP(hipSetDevice(device));
     if (B * hp.nprimes * hp.n > d_a.size())
     {
@@ -731,6 +758,7 @@ int Context::encrypt_asym(const float *d_values, size_t B, const uint8_t *d_seed
                           hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(mu);
+    if (int rc = refuse_asym(have_pk, B, d_values, d_seeds, d_c0, d_c1)) return rc;
     return call_scope(st, [&] {
         return encrypt_asym_impl(d_values, B, d_seeds, d_c0, d_c1, d_ntt_pte, d_pte, d_status, st);
     });
@@ -761,13 +789,8 @@ int Context::encrypt_sym_impl(const float *d_values, size_t B, const uint8_t *d_
                               uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status, hipStream_t st,
                               const KeyRing *ring)
 {
-    if (!have_sk && !ring)
-    {
-        set_last_error("symmetric encryption needs a secret key (se_amd_set_secret_key)");
-        return kErrNoKey;
-    }
+    if (int rc = refuse_sym(have_sk || ring, B, d_values, d_share_seeds, d_seeds, d_c0, d_c1)) return rc;
     if (B == 0) return 0;
-    if (!d_values || !d_share_seeds || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
     SEAMD_HIP(hipSetDevice(device));
     // a handful of ciphertexts: latency path (all primes' samplers at once, prime speculation)
     SpecPlan plan;
@@ -1086,13 +1109,8 @@ int Context::encrypt_asym_impl(const float *d_values, size_t B, const uint8_t *d
                                uint32_t *d_c1, uint32_t *d_ntt_pte, int64_t *d_pte, uint8_t *d_status,
                                hipStream_t st, const KeyRing *ring)
 {
-    if (!have_pk && !ring)
-    {
-        set_last_error("asymmetric encryption needs a public key (se_amd_set_public_key)");
-        return kErrNoKey;
-    }
+    if (int rc = refuse_asym(have_pk || ring, B, d_values, d_seeds, d_c0, d_c1)) return rc;
     if (B == 0) return 0;
-    if (!d_values || !d_seeds || !d_c0 || !d_c1) return kErrInvalid;
     SEAMD_HIP(hipSetDevice(device));
     int rc = ensure_scratch(B);
     if (rc) return rc;
